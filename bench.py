@@ -8,7 +8,7 @@ TrajectoryOptimizerAgent.act does per environment step, on BASELINE.json configs
 Inputs (weights, s0, bounds) are resident in HBM before the timed region; synthetic random-init
 weights (reference initialiser), fp32 arithmetic end to end (fp64 input normaliser like the reference).
 
-    python bench.py [--gpus N --steps K --warmup W] [--mode device|fast]     # N>1: launched by torch.distributed.run
+    python bench.py [--gpus N --steps K --warmup W] [--mode device|fast] [--dump-outputs DIR]     # N>1: launched by torch.distributed.run
 
 --mode (randomness of the rollouts inside the fused plan):
   device  the reference's propagation semantics: ONE balanced permutation of all 10 000 rows per step, iid eps, drawn
@@ -281,6 +281,14 @@ def torch_rocm_port(device, plans=2):
             "what": "reference op sequence (oracle port) on this GPU via PyTorch-ROCm eager ops, not the product path"}
 
 
+def dump_outputs(out_dir, arrays):
+    """Write each array as out_dir/<name>.npy in float32: the same arguments give the same inputs from run to run (seeded weights,
+    s0, optimizer and rollout streams), so two builds can be compared output for output."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a.detach().to("cpu", torch.float32).numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -294,6 +302,8 @@ def main():
     ap.add_argument("--no-extras", "--no-batched", dest="no_extras", action="store_true", help="skip the extra blocks (other mode, batched planning, agent.act)")
     ap.add_argument("--cpu-budget", type=float, default=30.0)
     ap.add_argument("--cpu-baseline-only", action="store_true", help="print the cpu_baseline object alone (needs no GPU) and exit")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline plan returned in its last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args()
     if args.cpu_baseline_only:
         print(json.dumps({"cpu_baseline": cpu_baseline(args.cpu_budget)}))
@@ -372,7 +382,7 @@ def main():
 
     def run(mode, pop_total, steps, warmup, spec_=None):
         """`warmup` untimed plans, then exactly `steps` plans between barrier + synchronize; MAX over ranks.
-        Returns (seconds, rollout-kernel launches, summed kernel ms, steps per launch, event sampling stride)."""
+        Returns (seconds, rollout-kernel launches, summed kernel ms, steps per launch, event sampling stride, last timed plan)."""
         mode_kw = {} if (headline_is_default and mode == args.mode) else {"mode": mode}  # the headline: no mode argument at all
         eval_fn = hipets.make_eval_fn(spec_ if spec_ is not None else spec, PARTICLES, engine=engine, seed=0, **mode_kw)
         assert eval_fn.mode == mode
@@ -420,7 +430,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
         assert torch.isfinite(sol).all()
-        return el, launches_, kernel_ms_, max(1, round(ITERS * HORIZON / max(per_plan, 1))), stride
+        return el, launches_, kernel_ms_, max(1, round(ITERS * HORIZON / max(per_plan, 1))), stride, sol
 
     def roofline_block(mode, pop_total, launches, kernel_ms, steps_per_launch, stride):
         """Dominant kernel = hipets::rollout_kernel.  One launch covers `steps_per_launch` steps of the local rows: the whole
@@ -448,7 +458,9 @@ def main():
 
     # N = 1: BASELINE.json configs[1].  N > 1: configs[2] = the SAME pop-500 plan sharded ("strong"); --scaling weak keeps pop 500 / rank
     pop = POP * world if (world > 1 and args.scaling == "weak") else POP
-    elapsed, launches, kernel_ms, spl, stride = run(args.mode, pop, args.steps, args.warmup)
+    elapsed, launches, kernel_ms, spl, stride, headline_plan = run(args.mode, pop, args.steps, args.warmup)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"plan": headline_plan})
     roof = roofline_block(args.mode, pop, launches, kernel_ms, spl, stride)
     if world > 1:
         # every rank's own rollout kernel: its shard (the first pop % world ranks hold one more candidate), its average launch
@@ -469,7 +481,7 @@ def main():
     other = "fast" if args.mode == "device" else "device"
     if not args.no_extras:
         n_other = max(3, args.steps // 3)
-        e2, l2, k2, spl2, stride2 = run(other, pop, n_other, 2)
+        e2, l2, k2, spl2, stride2, _ = run(other, pop, n_other, 2)
         r2 = roofline_block(other, pop, l2, k2, spl2, stride2)
         extras[f"{other}_mode"] = {"workload": f"the same plan with mode='{other}' rollouts", "value": n_other * ITERS * pop * PARTICLES * HORIZON / e2,
                                    "unit": "candidate-steps/s", "ms_per_plan": 1e3 * e2 / n_other, "roofline": r2}
@@ -482,7 +494,7 @@ def main():
                "parity": "tests/test_gpu_bf16x3.py: T1 / T2 against the oracle at the fp32 mode's tolerances; <= 2e-5 relative to the fp32-MFMA kernel"}
         for m in ("device", "fast"):
             n3 = max(3, args.steps // 3)
-            e3_, l3, k3, spl3, stride3 = run(m, pop, n3, 2, spec_=spec3)
+            e3_, l3, k3, spl3, stride3, _ = run(m, pop, n3, 2, spec_=spec3)
             avg_s = (k3 / max(l3, 1)) * 1e-3
             alg = flops_cs * pop * PARTICLES * spl3
             blk[m] = {"value": n3 * ITERS * pop * PARTICLES * HORIZON / e3_, "unit": "candidate-steps/s", "ms_per_plan": 1e3 * e3_ / n3,

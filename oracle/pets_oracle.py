@@ -10,10 +10,10 @@ It is the *checker* for the HIP engine in ``mbrl-lib_amd/``.  Only ``tests/``,
 ``__graft_entry__.smoke()`` and ``bench.py``'s ``cpu_baseline`` leg may import it; the
 product package never does (and fails loudly when its HIP library is missing).
 
-Parity status: PINNED.  ``tests/test_oracle_vs_reference.py`` (runs where /root/reference is
-mounted) asserts this restatement is bitwise equal to the reference classes, and
-``tests/golden/*.npz`` (made by ``oracle/make_golden.py`` from the reference itself) pin it on
-machines where the reference is absent.
+Parity status: PINNED.  ``tests/test_oracle_vs_reference.py`` asserts this restatement is bitwise
+equal to what the reference classes returned (recorded by ``oracle/ref_cases.py``), and
+``tests/golden/*.npz`` (made by ``oracle/make_golden.py`` from the reference itself) pin it at
+more sizes and through the agent.
 
 Every function cites the reference file:line it follows (paths relative to the reference
 root).  Nothing here is copied: the reference spreads this logic over seven classes; this is

@@ -1,7 +1,6 @@
 """The N>1 path on CPU: world_size 2, gloo backend.  Exercises the real sharding + all-gather code
 (hipets.dist) with a CPU objective; the rollout kernel itself is covered by the -m gpu tests."""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -10,27 +9,19 @@ import torch.distributed as dist
 import torch.multiprocessing as mp
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _objective(initial_state, action_sequences):
     # any deterministic per-candidate function: candidates are independent, like rollouts
     return -(action_sequences ** 2).sum(dim=(1, 2)) + float(initial_state[0])
 
 
-def _worker(rank, world, port, pop, tmpdir):
+def _worker(rank, world, pop, tmpdir):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     sys.path.insert(0, os.path.join(root, "mbrl-lib_amd"))
     from hipets import dist as hdist
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method="file://" + os.path.join(tmpdir, "pg_store"), rank=rank, world_size=world)
     try:
         g = torch.Generator().manual_seed(0)  # replicated sampling: same seed on every rank
         population = torch.rand(pop, 4, 3, generator=g)
@@ -61,7 +52,7 @@ def _worker(rank, world, port, pop, tmpdir):
 @pytest.mark.parametrize("pop", [10, 7, 501])
 def test_sharded_eval_world2_gloo(tmp_path, pop):
     world = 2
-    mp.spawn(_worker, args=(world, _free_port(), pop, str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, pop, str(tmp_path)), nprocs=world, join=True)
     v0 = torch.load(tmp_path / "v0.pt")
     v1 = torch.load(tmp_path / "v1.pt")
     assert torch.equal(v0, v1) and v0.shape[0] == pop
@@ -192,7 +183,7 @@ def test_failed_sharded_mppi_and_icem_attempts_are_undone_before_the_single_gpu_
     assert fell_back and out == "icem plan" and torch.equal(eng.seen, torch.arange(12.0).reshape(2, 3, 2))
 
 
-def _timeout_worker(rank, world, port, tmpdir):
+def _timeout_worker(rank, world, tmpdir):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -201,9 +192,7 @@ def _timeout_worker(rank, world, port, tmpdir):
     from hipets.engine import Engine
     from hipets.planning import _BoundObjective, _OptimizerSnapshot
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method="file://" + os.path.join(tmpdir, "pg_store"), rank=rank, world_size=world)
     try:
         class Eng(Engine):  # an engine whose time-out flag is scripted (no GPU here)
             def __init__(self, hits):
@@ -241,7 +230,7 @@ def test_timed_out_plan_is_rerun_on_every_rank_or_none_world2_gloo(tmp_path):
     """Round-3 advice: TrajectoryOptimizer.optimize re-runs a plan whose rollouts timed out; with a ShardedEvalFn objective a
     rank re-running alone would issue all-gathers its peers never match.  The flag is all-reduced over the objective's group."""
     world = 2
-    mp.spawn(_timeout_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_timeout_worker, args=(world, str(tmp_path)), nprocs=world, join=True)
     r0, r1 = torch.load(tmp_path / "t0.pt"), torch.load(tmp_path / "t1.pt")
     assert r0[:2] == (True, False) and r1[:2] == (True, False)
     assert r0[2] is True and r1[2] is False  # purely local

@@ -1,7 +1,6 @@
 """The N>1 path end to end on ONE GPU: two ranks (gloo, both on cuda:0) shard the population, run the real rollout
 kernel on their shard, all-gather the returns and refit.  (The driver's 8-GPU run uses the same code with nccl.)"""
 import os
-import socket
 
 import numpy as np
 import pytest
@@ -13,13 +12,7 @@ import hipets  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-def _free_port():
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
-def _worker(rank, world, port, tmpdir):
+def _worker(rank, world, tmpdir):
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -32,9 +25,7 @@ def _worker(rank, world, port, tmpdir):
     from hipets.planning import _BoundObjective
     from oracle import pets_oracle as po
 
-    os.environ["MASTER_ADDR"] = "127.0.0.1"
-    os.environ["MASTER_PORT"] = str(port)
-    dist.init_process_group("gloo", rank=rank, world_size=world)
+    dist.init_process_group("gloo", init_method="file://" + os.path.join(tmpdir, "pg_store"), rank=rank, world_size=world)
     try:
         obs, act, H, P, pop = 17, 6, 8, 10, 101  # uneven shards: 51 + 50
         om = po.make_synthetic_model(obs, act, ensemble_size=5, hid=64, seed=4)
@@ -52,7 +43,7 @@ def _worker(rank, world, port, tmpdir):
 
 def test_two_ranks_one_gpu_sharded_cem(tmp_path):
     world = 2
-    mp.spawn(_worker, args=(world, _free_port(), str(tmp_path)), nprocs=world, join=True)
+    mp.spawn(_worker, args=(world, str(tmp_path)), nprocs=world, join=True)
     a, b = torch.load(tmp_path / "r0.pt"), torch.load(tmp_path / "r1.pt")
     assert torch.equal(a["plan"], b["plan"]) and torch.isfinite(a["plan"]).all()  # replicated refit, no broadcast
     for pa, pb, va, vb in zip(a["pops"], b["pops"], a["vals"], b["vals"]):

@@ -25,6 +25,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLD = 0x9E3779B97F4A7C15
 OBS, ACT, H, P, ITERS, K = 17, 6, 6, 5, 3, 50
 SEED, PLAN_ID = 5, 2
+# Every rank is a process of its own holding cuda:0 open, beside the test process.  Hosts that share a GPU among many users may cap
+# the processes it serves at once.  HIPETS_MAX_PROCS_PER_GPU states that cap (default 6: such hosts are assumed unless told otherwise);
+# a world that does not fit is skipped before it starts.  Set it to 9 or more where one GPU may serve 9 processes to run the 8-rank cases.
+MAX_PROCS_PER_GPU = int(os.environ.get("HIPETS_MAX_PROCS_PER_GPU", "6"))
+
+
+def _require_procs(world):
+    if world + 1 > MAX_PROCS_PER_GPU:
+        pytest.skip(f"needs {world + 1} processes on one GPU ({world} ranks + the test), HIPETS_MAX_PROCS_PER_GPU allows "
+                    f"{MAX_PROCS_PER_GPU}; set it to {world + 1} or more where the GPU may serve that many")
 
 
 def _setup_paths():
@@ -111,6 +121,7 @@ def _run(tmp_path, world, pop, mode="fast", particles=P, fail_at=0):
 def test_sharded_plan_over_world_ranks_on_one_gpu(tmp_path, engine, world, pop, mode):
     import hipets
 
+    _require_procs(world)
     res = _run(tmp_path, world, pop, mode)
     for r, a in enumerate(res):
         assert "error" not in a, a.get("error")
@@ -142,6 +153,7 @@ def test_injected_collective_error_takes_the_single_gpu_fallback_on_every_rank(t
     import hipets
 
     world, pop = 4, 500
+    _require_procs(world)
     res = _run(tmp_path, world, pop, "fast", fail_at=2)  # the second all-gather of the plan fails on every rank
     for a in res:
         assert a["fell_back"] and a["comm_world_after"] == 1
@@ -165,7 +177,18 @@ def _setup_and_model():
 def test_device_mode_shards_the_rollout_cannot_take_are_refused_on_every_rank(tmp_path):
     """pop 501 over 8 ranks with 4 particles: shards of 63 and 62 candidates = 252 / 248 rows, not multiples of 5 members
     (gaussian_mlp.py:195-200).  Every rank gets the reference's error text before any collective: nobody hangs."""
+    _require_procs(8)
     res = _run(tmp_path, 8, 501, "device", particles=4)
+    for a in res:
+        assert "multiple of the number of models" in a.get("error", ""), a
+
+
+def test_device_mode_shards_the_rollout_cannot_take_are_refused_on_every_rank_of_four(tmp_path):
+    """The same refusal in a world that fits beside the test process on a GPU serving at most 6: pop 506 over 4 ranks with 4
+    particles = uneven shards of 127 and 126 candidates = 508 / 504 rows, none a multiple of 5 members."""
+    _require_procs(4)
+    res = _run(tmp_path, 4, 506, "device", particles=4)
+    assert len(res) == 4
     for a in res:
         assert "multiple of the number of models" in a.get("error", ""), a
 
@@ -306,6 +329,7 @@ def test_sharded_mppi_plan_over_world_ranks_on_one_gpu(tmp_path, engine, world, 
     for bit: every rank holds the identical mean, populations and gathered values; the gathered values are the ranks' own shard
     rollouts; every refinement's new mean is the library's own importance-weighted update (trajectory_opt.py:297-311: global max and
     sum over ALL candidates) of the recorded population and gathered values."""
+    _require_procs(world)
     res = _run_opt(tmp_path, world, "mppi", mode)
     for a in res:
         assert "error" not in a, a.get("error")
@@ -331,6 +355,7 @@ def test_sharded_icem_plan_over_world_ranks_on_one_gpu(tmp_path, engine, world, 
     refit (biased variance, :479) of the recorded population and gathered values; elite = population[elite_idx] (:476)."""
     import hipets
 
+    _require_procs(world)
     res = _run_opt(tmp_path, world, "icem", mode)
     for a in res:
         assert "error" not in a, a.get("error")
@@ -376,10 +401,9 @@ def _observations():
     return (np.random.default_rng(5).standard_normal((3, OBS)) * 0.1).astype(np.float32)
 
 
-def _act_worker(rank, world, port, kind, mode, tmpdir, fail_at):
+def _act_worker(rank, world, kind, mode, tmpdir, fail_at):
     _setup_paths()
     os.environ["HIPETS_NO_PERSISTENT"] = "1"
-    os.environ["MASTER_ADDR"], os.environ["MASTER_PORT"] = "127.0.0.1", str(port)
     if fail_at:
         os.environ["FAKE_RCCL_FAIL_AT"] = str(fail_at)
     import warnings
@@ -389,7 +413,7 @@ def _act_worker(rank, world, port, kind, mode, tmpdir, fail_at):
     import hipets
     from hipets import dist as hdist
 
-    tdist.init_process_group("gloo", rank=rank, world_size=world)  # carries the communicator id and the ranks' agreement on outcomes
+    tdist.init_process_group("gloo", init_method="file://" + os.path.join(tmpdir, "pg_store"), rank=rank, world_size=world)  # carries the communicator id and the ranks' agreement on outcomes
     try:
         eng = hipets.get_engine(DEV)
         hdist.init_engine_comm(eng)  # <- the ONLY line a multi-GPU user adds: the agent below is the stock drop-in
@@ -404,20 +428,12 @@ def _act_worker(rank, world, port, kind, mode, tmpdir, fail_at):
         tdist.destroy_process_group()
 
 
-def _free_port():
-    import socket
-
-    with socket.socket() as s:
-        s.bind(("127.0.0.1", 0))
-        return s.getsockname()[1]
-
-
 def _run_act(tmp_path, world, kind, mode, fail_at=0):
     import __graft_entry__ as ge
 
     os.environ["HIPETS_RCCL_LIB"] = ge.build_fake_rccl()
     try:
-        mp.spawn(_act_worker, args=(world, _free_port(), kind, mode, str(tmp_path), fail_at), nprocs=world, join=True)
+        mp.spawn(_act_worker, args=(world, kind, mode, str(tmp_path), fail_at), nprocs=world, join=True)
     finally:
         del os.environ["HIPETS_RCCL_LIB"]
     return [torch.load(tmp_path / f"a{r}.pt", weights_only=False) for r in range(world)]

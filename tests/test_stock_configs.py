@@ -4,9 +4,10 @@ trajectory_opt.py:527 / :741 (an OmegaConf-like node whose `???` fields raise wh
 hipets.create_trajectory_optim_agent_for_model -- once with the stock `_target_: mbrl.planning.*` (redirected) and once with the
 documented opt-in override `_target_=hipets.*`.
 
-hydra-core / omegaconf / the reference tree are not on the GPU box, so the YAML texts are embedded here verbatim; the CPU test
-below compares them with the files under /root/reference whenever that tree is mounted (it is, where this suite runs without
-a GPU), so the embedded copies cannot drift from what the reference ships."""
+hydra-core / omegaconf / the reference tree are not part of this repository, so the YAML texts are embedded here verbatim; the CPU
+test below compares them with tests/golden/reference_conf.json (recorded from the reference's conf/ tree by oracle/ref_cases.py:
+the sha256 of every action_optimizer text and the values of the files used here), so the embedded copies cannot drift from what
+the reference ships."""
 import math
 import os
 import re
@@ -16,7 +17,7 @@ import pytest
 import torch
 import yaml
 
-REF_CONF = "/root/reference/mbrl/examples/conf"
+CONF_RECORD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_conf.json")
 
 # conf/action_optimizer/*.yaml, verbatim
 ACTION_OPTIMIZER_YAML = {
@@ -94,18 +95,22 @@ def resolved(name, device):
     return out
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_CONF), reason="the reference tree is not mounted (GPU box)")
 def test_embedded_yaml_is_what_the_reference_ships():
+    import hashlib
+    import json
+
+    record = json.load(open(CONF_RECORD))
+    assert sorted(record["action_optimizer_sha256"]) == sorted(ACTION_OPTIMIZER_YAML)
     for name, text in ACTION_OPTIMIZER_YAML.items():
-        assert open(os.path.join(REF_CONF, "action_optimizer", f"{name}.yaml")).read().strip() == text.strip(), name
+        assert hashlib.sha256(text.strip().encode()).hexdigest() == record["action_optimizer_sha256"][name], name
     for name, (path, values) in OVERRIDES.items():
-        shipped = yaml.safe_load(open(os.path.join(REF_CONF, path)))
+        shipped = record["values"][path]
         for k, v in values.items():
             assert shipped[k] == v, (path, k)
-    pets = yaml.safe_load(open(os.path.join(REF_CONF, "algorithm", "pets.yaml")))
+    pets = record["values"]["algorithm/pets.yaml"]
     assert pets["num_particles"] == NUM_PARTICLES
     assert {k: pets["agent"][k] for k in ("_target_", "action_lb", "action_ub", "replan_freq")} == {k: PETS_AGENT[k] for k in ("_target_", "action_lb", "action_ub", "replan_freq")}
-    gmlp = yaml.safe_load(open(os.path.join(REF_CONF, "dynamics_model", "gaussian_mlp_ensemble.yaml")))
+    gmlp = record["values"]["dynamics_model/gaussian_mlp_ensemble.yaml"]
     assert gmlp["ensemble_size"] == ENSEMBLE_SIZE
 
 
