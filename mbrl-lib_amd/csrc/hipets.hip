@@ -188,14 +188,11 @@ size_t lds_for(const hipets_engine* e, int R, int horizon, bool wide = false) {
 // A CU holds two workgroups of an R <= 2 instance at once (256 registers each) and their fixed parts hide behind each other's MFMAs:
 // a pair costs a + 2 units; R >= 3 instances own the CU (512 registers) and their workgroups run one after the other.  A (shape, R)
 // pair without a shape-specialised instance (launch.hpp lean_shape_exists) runs the hidden-static or the generic kernel: + 8 %.
-// `desync`: the workgroups of the launch do not wait for each other (FAST mode: one launch for the horizon, no hand-over).  Two of them
+// `drift`: the workgroups of the launch do not wait for each other (FAST mode: one launch for the horizon, no hand-over).  Two of them
 // on a CU then drift apart and their heavy waves stop meeting on a SIMD: a pair costs a + 2 x the AVERAGE units per SIMD (C R / 4: 3.25
 // instead of 4 per row tile at hid 200).  Step-synchronous launches (DEVICE / EXACT: hand-over or one launch per step) pay the busiest one.
 // Calibrated on MI355X (profiles/r4_stock_workloads.json, r4_learned_reward_workloads.json, r4_device_r_sweep.json: every R forced, 12
 // workloads, both modes -- the rule picks the fastest R in 23 of the 24 cases and loses 0.3 % in the other).
-
-// FAST-mode geometry: the B = pop x P rows are one run (rollout.hpp, prologue) of ceil(B / 16) row tiles, R per workgroup
-inline long long fast_tiles(long long pop, int P) { return (pop * P + kTile - 1) / kTile; }
 
 int wave_units(int C, int R) {  // MFMA units per k-chunk of the busiest SIMD (waves w and w + 4 share SIMD w % 4)
     const int full = C / kWaves, rem = C % kWaves, nu = rem * R;
@@ -204,13 +201,14 @@ int wave_units(int C, int R) {  // MFMA units per k-chunk of the busiest SIMD (w
     return std::max(std::max(simd[0], simd[1]), std::max(simd[2], simd[3]));
 }
 
-int choose_R(const hipets_engine* e, long long tiles_total_per_slice, int slices, int forced, int horizon, bool wide, bool desync) {
+// `fast_instances`: price R by the instance set of the FAST form (launch.hpp lean_shape_exists), else by that of the step-synchronous form.
+int choose_R(const hipets_engine* e, long long tiles_total_per_slice, int slices, int forced, int horizon, bool wide, bool drift, bool fast_instances) {
     if (forced > 0) return forced;
     const int C = e->md.hidC;
     // the fixed part scales with the layer width like the units do.  WIDE instances (Humanoid-v4: 47 output column tiles, one workgroup per
     // CU) carry their output layer and its tail in it: a round of two-tile workgroups costs 1.29 x a round of one-tile ones in FAST mode,
     // 1.45 x in the turn-based DEVICE form (profiles/r5_cfg4p_iterations.json: the five population sizes of the cfg4' iCEM plan, both R)
-    const double a = (wide ? (desync ? 6.45 : 2.67) : 1.77) * (double)C / 13.0;
+    const double a = (wide ? (drift ? 6.45 : 2.67) : 1.77) * (double)C / 13.0;
     int best = 1;
     double best_cost = 1e300;
     // bf16x3 arithmetic exists in shape-specialised instances only: among the R that have one (if any has: else the launch reports it)
@@ -226,16 +224,85 @@ int choose_R(const hipets_engine* e, long long tiles_total_per_slice, int slices
         const long long n = (nwg + e->num_cu - 1) / e->num_cu;  // workgroups the busiest CU serves
         const int co = (R <= 2 && !wide) ? 2 : 1;               // ... of which it holds this many at once
         const double u = wave_units(C, R);
-        const double u_pair = (co == 2 && desync) ? (double)C * R / 4.0 : u;
+        const double u_pair = (co == 2 && drift) ? (double)C * R / 4.0 : u;
         const long long full = n / co, rem = n % co;
         double cost = (double)full * (a + co * u_pair) + (rem ? a + (double)rem * u : 0.0);
-        if (!lean_shape_exists(e->md, R, desync)) cost *= 1.08;
+        if (!lean_shape_exists(e->md, R, fast_instances)) cost *= 1.08;
         if (cost < best_cost - 1e-9) {
             best_cost = cost;
             best = R;
         }
     }
     return best;
+}
+
+// The launch geometry of one rollout / step call: everything the launch of the rollout kernel is sized by.
+enum class GeoCall { rollout, step, query };  // hipets_rollout, hipets_step, or a query of hipets_rollout's geometry (no launch)
+struct Geometry {
+    int domains;         // member domains: M for EXACT / DEVICE (1 under expectation propagation), 1 for FAST
+    long long rpd;       // rows per domain: B / domains, or opts.rows_per_member (EXACT with per-row member maps)
+    long long tiles;     // row tiles per domain
+    bool wide;           // the KSpec::WIDE layout (RolloutArgs::wide_lds)
+    bool whole_horizon;  // the FAST form: one launch for the horizon (RolloutArgs::whole_horizon); else step-synchronous, state in HBM
+    int R;               // row tiles per workgroup
+    int groups;          // workgroups per domain
+    size_t lds;          // dynamic LDS bytes
+};
+
+// `probe`: the RolloutArgs the launcher's lean_call will see (in-kernel draws / injected eps, traces, generic_only); `rows_per_member`:
+// opts.rows_per_member (0 for queries).  hipets_step runs the step-synchronous form in every mode (for ONE step it is the FAST form too,
+// and every shape-specialised instance has it) and never the WIDE layout.
+int rollout_geometry(const hipets_engine* e, int mode, long long B, int rows_per_member, int H, int rows_per_group, GeoCall call,
+                     const RolloutArgs& probe, Geometry* g) {
+    const ModelDev& md = e->md;
+    const bool fast = mode == HIPETS_MODE_FAST;
+    const bool expectation = md.propagation == HIPETS_PROP_EXPECTATION;
+    g->domains = (fast || expectation) ? 1 : md.M;
+    const bool slots = mode == HIPETS_MODE_EXACT && !expectation && rows_per_member > 0;
+    g->rpd = slots ? rows_per_member : B / g->domains;
+    g->tiles = (g->rpd + kTile - 1) / kTile;
+    g->whole_horizon = fast && call != GeoCall::step;
+    g->wide = call != GeoCall::step && rows_per_group <= 2 && wide_model(md) && lean_call(md, probe);
+    // (a caller-sized member schedule follows hipets_fast_geometry: the default call's geometry -- the WIDE instance's where one will run;
+    // rows_per_group = -1 asks for the general layout's, which is what calls with injected eps / traces run)
+    if (g->whole_horizon && !g->wide && wide_model(md) && probe.schedule && rows_per_group == 0)
+        return fail("this call runs the general kernel layout (injected eps / traces / generic_kernel) on a model whose default geometry is "
+                    "the wide-output instance's: size member_schedule with hipets_fast_geometry(rows_per_group = -1) and pass its row-tile "
+                    "count as opts->rows_per_group");
+    // Only a whole-horizon launch of more than one step drifts apart.  The same flag picks the instance set R is priced by, so a FAST
+    // rollout with H = 1 is priced against the step-synchronous set although it runs (and hipets_kernel_class classifies it by) the FAST
+    // one.  The two sets agree today (launch.hpp HIPETS_LEAN_FAST_SHAPES_* are empty).
+    const bool drift = g->whole_horizon && H > 1;
+    g->R = choose_R(e, g->tiles, g->domains, rows_per_group, H, g->wide, drift, drift);
+    g->lds = lds_for(e, g->R, H, g->wide);
+    if (g->lds > e->lds_max) return fail("rows_per_group %d does not fit LDS", g->R);
+    g->groups = (int)((g->tiles + g->R - 1) / g->R);
+    if (fast && call != GeoCall::query && g->groups > 8000)
+        return fail("FAST mode supports at most 8000 workgroups per launch (got %d)%s", g->groups, call == GeoCall::rollout ? "; shard the population" : "");
+    return 0;
+}
+
+// The member maps of an EXACT / DEVICE call (hipets_rollout, hipets_step): per step ONE balanced permutation of all B rows, slot j ->
+// member j / (B / M) (gaussian_mlp.py:164-166, 203-205), or explicit per-row member maps (padded member slots, opts.rows_per_member):
+// what BasicEnsemble draws with randint (basic_ensemble.py:122-129) and mbrl.util.math.propagate_from_indices expresses (util/math.py:
+// 180-196), accepted for GaussianMLP models too (any batch size, members may own unequal row counts).
+int check_member_maps(const hipets_engine* e, const hipets_rollout_opts* o, long long B, bool one_step) {
+    const ModelDev& md = e->md;
+    const bool device = o->mode == HIPETS_MODE_DEVICE;
+    const bool expectation = md.propagation == HIPETS_PROP_EXPECTATION;
+    const bool slots = o->mode == HIPETS_MODE_EXACT && !expectation && o->rows_per_member > 0;
+    // the reference's ValueError (gaussian_mlp.py:195-200), raised for every propagation method.  hipets_step raises it in every mode and
+    // exempts every EXACT call with rows_per_member
+    const bool exempt = one_step ? o->mode == HIPETS_MODE_EXACT && o->rows_per_member > 0 : slots;
+    if (!md.iid_members && !exempt && B % md.M != 0)
+        return fail("GaussianMLP ensemble requires batch size to be a multiple of the number of models. "
+                    "Current batch size is %lld for %d models.", B, md.M);
+    if ((o->mode != HIPETS_MODE_EXACT && !device) || expectation) return 0;
+    if (device && md.iid_members) return fail("DEVICE mode has no BasicEnsemble (iid member map) variant: use FAST, or EXACT with injected maps");
+    if (!device && !o->perms) return fail("EXACT mode with random_model/fixed_model propagation needs opts.perms");
+    if ((md.iid_members && !device && !slots) || (slots && o->rows_per_member > B))
+        return fail("EXACT mode with per-row member maps needs opts.rows_per_member in [1, B] (padded member slots)");
+    return 0;
 }
 
 // MPPI sampling (optim.hpp): whole candidates staged in LDS where one fits, else one thread per series
@@ -679,13 +746,13 @@ int hipets_fast_geometry(hipets_engine* e, int32_t pop, int32_t P, int32_t horiz
     if (!e || !e->has_model) return fail("engine has no model");
     if (pop < 1 || P < 1) return fail("bad pop/P");
     if (rows_per_group < -1 || rows_per_group > kMaxR) return fail("rows_per_group outside [-1, %d]", kMaxR);
-    const long long tiles = fast_tiles(pop, P);
-    const bool wide = rows_per_group >= 0 && rows_per_group <= 2 && wide_model(e->md);  // a default call runs the WIDE instance there
-    const int R = choose_R(e, tiles, 1, rows_per_group < 0 ? 0 : rows_per_group, horizon, wide, horizon > 1);  // (one step: nothing drifts apart, hipets_step)
-    if (lds_for(e, R, horizon, wide) > e->lds_max) return fail("rows_per_group %d does not fit LDS", R);
-    const long long groups = (tiles + R - 1) / R;
-    if (n_workgroups) *n_workgroups = (int)groups;
-    if (row_tiles) *row_tiles = R;
+    RolloutArgs probe{};  // a default call: in-kernel draws, nothing injected or traced; -1: a call that runs the general layout
+    probe.use_philox = 1;
+    probe.generic_only = rows_per_group < 0 ? 1 : 0;
+    Geometry g;
+    if (rollout_geometry(e, HIPETS_MODE_FAST, (long long)pop * P, 0, horizon, std::max(rows_per_group, 0), GeoCall::query, probe, &g)) return 1;
+    if (n_workgroups) *n_workgroups = g.groups;
+    if (row_tiles) *row_tiles = g.R;
     return 0;
 }
 
@@ -696,34 +763,24 @@ int hipets_kernel_class(hipets_engine* e, int32_t pop, int32_t P, int32_t horizo
     if (rows_per_group < 0 || rows_per_group > kMaxR) return fail("rows_per_group outside [0, %d]", kMaxR);
     if (mode != HIPETS_MODE_FAST && mode != HIPETS_MODE_DEVICE) return fail("hipets_kernel_class: mode must be HIPETS_MODE_FAST or HIPETS_MODE_DEVICE");
     const ModelDev& md = e->md;
+    const long long B = (long long)pop * P;
+    if (mode == HIPETS_MODE_DEVICE && md.propagation != HIPETS_PROP_EXPECTATION) {
+        if (md.iid_members && md.M > 1) return fail("DEVICE mode has no BasicEnsemble (iid member map) variant");
+        if (B % md.M != 0) return fail("GaussianMLP ensemble requires batch size to be a multiple of the number of models. "
+                                       "Current batch size is %lld for %d models.", B, md.M);
+    }
     RolloutArgs probe{};  // what a default call's arguments look like to the launcher: in-kernel draws, nothing injected or traced
     probe.use_philox = 1;
-    probe.mode = mode;
+    Geometry g;
+    if (rollout_geometry(e, mode, B, 0, horizon, rows_per_group, GeoCall::query, probe, &g)) return fail("the model does not fit LDS");
     const bool call_lean = lean_call(md, probe);
-    long long tiles;
-    int slices;
-    if (mode == HIPETS_MODE_DEVICE) {  // rollout_impl's geometry: one slice of B / M rows per member
-        const long long B = (long long)pop * P;
-        const int domains = md.propagation == HIPETS_PROP_EXPECTATION ? 1 : md.M;
-        if (md.iid_members && domains > 1) return fail("DEVICE mode has no BasicEnsemble (iid member map) variant");
-        if (B % domains != 0) return fail("GaussianMLP ensemble requires batch size to be a multiple of the number of models. "
-                                          "Current batch size is %lld for %d models.", B, md.M);
-        tiles = (B / domains + kTile - 1) / kTile;
-        slices = domains;
-    } else {  // all B rows in one run
-        tiles = fast_tiles(pop, P);
-        slices = 1;
-    }
-    const bool wide = wide_model(md) && call_lean && rows_per_group <= 2;
-    const int R = choose_R(e, tiles, slices, rows_per_group, horizon, wide, mode == HIPETS_MODE_FAST && horizon > 1);
-    if (lds_for(e, R, horizon, wide) > e->lds_max) return fail("the model does not fit LDS");
     int cls = HIPETS_KERNEL_GENERIC;
     if (md.precision == HIPETS_PREC_BF16X3) {
-        if (!(call_lean && b3_shape_exists(md, R))) return fail("bf16x3 arithmetic exists for the shape-specialised instances only");
+        if (!(call_lean && b3_shape_exists(md, g.R))) return fail("bf16x3 arithmetic exists for the shape-specialised instances only");
         cls = HIPETS_KERNEL_FUSED;
-    } else if (wide) {
+    } else if (g.wide) {
         cls = HIPETS_KERNEL_WIDE;
-    } else if (call_lean && !wide_model(md) && lean_shape_exists(md, R, mode == HIPETS_MODE_FAST)) {
+    } else if (call_lean && !wide_model(md) && lean_shape_exists(md, g.R, g.whole_horizon)) {
         cls = HIPETS_KERNEL_FUSED;
     } else {
 #define HIPETS_CLASS_HID(HC) if (hid_static_call(md, probe, HC)) cls = HIPETS_KERNEL_HIDDEN_STATIC;
@@ -731,7 +788,7 @@ int hipets_kernel_class(hipets_engine* e, int32_t pop, int32_t P, int32_t horizo
 #undef HIPETS_CLASS_HID
     }
     if (kernel_class) *kernel_class = cls;
-    if (row_tiles) *row_tiles = R;
+    if (row_tiles) *row_tiles = g.R;
     return 0;
 }
 
@@ -786,7 +843,6 @@ int rollout_impl(hipets_engine* e, const float* actions, const float* s0, int32_
 
     RolloutArgs ra{};
     ra.pop = pop; ra.P = P; ra.H = H; ra.B = (int)B;
-    ra.mode = o->mode;
     ra.actions = actions;
     ra.s0 = e->s0.as<float>();
     ra.totals = e->totals.as<float>();
@@ -799,51 +855,12 @@ int rollout_impl(hipets_engine* e, const float* actions, const float* s0, int32_
     ra.generic_only = o->generic_kernel;
 
     if (o->mode == HIPETS_MODE_EXACT || o->mode == HIPETS_MODE_DEVICE) {
-        // Reference propagation semantics: per step ONE balanced permutation of all B rows, slot j -> member j / (B / M)
-        // (gaussian_mlp.py:164-166, 203-205).  EXACT takes the permutations and eps from the caller (the reference's own
-        // draws); DEVICE evaluates a keyed bijection and Philox normals in-kernel (no input tensors, no host work).
+        // EXACT takes the permutations and eps from the caller (the reference's own draws); DEVICE evaluates a keyed bijection and
+        // Philox normals in-kernel (no input tensors, no host work)
         const bool device = o->mode == HIPETS_MODE_DEVICE;
         const bool expectation = md.propagation == HIPETS_PROP_EXPECTATION;
-        const int domains = expectation ? 1 : md.M;
-        // explicit per-row member maps (padded member slots, opts.rows_per_member): what BasicEnsemble draws with randint
-        // (basic_ensemble.py:122-129) and what mbrl.util.math.propagate_from_indices expresses (util/math.py:180-196);
-        // accepted for GaussianMLP models too (any batch size, members may own unequal row counts)
-        const bool slots = !device && !expectation && o->rows_per_member > 0;
-        if (!md.iid_members && !slots && B % md.M != 0)  // the reference's ValueError (gaussian_mlp.py:195-200), raised for every propagation method
-            return fail("GaussianMLP ensemble requires batch size to be a multiple of the number of models. "
-                        "Current batch size is %lld for %d models.", B, md.M);
-        if (!expectation) {
-            if (device && md.iid_members)
-                return fail("DEVICE mode has no BasicEnsemble (iid member map) variant: use FAST, or EXACT with injected maps");
-            if (!device && !o->perms) return fail("EXACT mode with random_model/fixed_model propagation needs opts.perms");
-            if ((md.iid_members && !device && !slots) || (slots && o->rows_per_member > B))
-                return fail("EXACT mode with per-row member maps needs opts.rows_per_member in [1, B] (padded member slots)");
-        }
-        const int rpd = expectation ? (int)B : (slots ? o->rows_per_member : (int)(B / domains));
-        const long long tiles = (rpd + kTile - 1) / kTile;
-        bool wide = false;
-        if (device && wide_model(md)) {  // will the launcher pick the WIDE instance?  (its lean_call on what `ra` is going to hold)
-            RolloutArgs probe = ra;
-            probe.eps = nullptr;
-            probe.use_philox = o->no_sample ? 0 : 1;
-            wide = lean_call(md, probe) && o->rows_per_group <= 2;
-        }
-        ra.wide_lds = wide ? 1 : 0;
-        const int R = choose_R(e, tiles, domains, o->rows_per_group, H, wide, false);
-        const size_t lds = lds_for(e, R, H, wide);
-        if (lds > e->lds_max) return fail("rows_per_group %d does not fit LDS", R);
-        const int groups = (int)((tiles + R - 1) / R);
-        // rows change workgroups between steps only when a fresh permutation is drawn per step: one launch per step then
-        // (state through HBM); TS-infinity / expectation rollouts of DEVICE mode keep their rows and run as ONE launch
-        const bool per_step = !device || md.propagation == HIPETS_PROP_RANDOM_MODEL;
-        if (e->state.ensure((size_t)B * md.obs_dim * 4) || e->term.ensure((size_t)B)) return 1;
-        ra.groups = groups;
-        ra.rows_per_domain = rpd;
-        ra.state = e->state.as<float>();
-        ra.term = e->term.as<unsigned char>();
+        if (check_member_maps(e, o, B, false)) return 1;
         if (device) {
-            ra.perm = nullptr;
-            ra.eps = nullptr;
             ra.use_philox = o->no_sample ? 0 : 1;
             if (!expectation) {
                 ra.perm_n = (unsigned)B;
@@ -852,10 +869,22 @@ int rollout_impl(hipets_engine* e, const float* actions, const float* s0, int32_
             }
         } else {
             ra.perm = expectation ? nullptr : reinterpret_cast<const long long*>(o->perms);
-            ra.perm_step = md.propagation == HIPETS_PROP_RANDOM_MODEL ? (long long)domains * rpd : 0;
             ra.eps = o->eps;
-            ra.use_philox = 0;
         }
+        Geometry g;
+        if (rollout_geometry(e, o->mode, B, o->rows_per_member, H, o->rows_per_group, GeoCall::rollout, ra, &g)) return 1;
+        const int R = g.R, domains = g.domains, groups = g.groups;
+        const size_t lds = g.lds;
+        if (!device && md.propagation == HIPETS_PROP_RANDOM_MODEL) ra.perm_step = (long long)domains * g.rpd;
+        // rows change workgroups between steps only when a fresh permutation is drawn per step: one launch per step then
+        // (state through HBM); TS-infinity / expectation rollouts of DEVICE mode keep their rows and run as ONE launch
+        const bool per_step = !device || md.propagation == HIPETS_PROP_RANDOM_MODEL;
+        if (e->state.ensure((size_t)B * md.obs_dim * 4) || e->term.ensure((size_t)B)) return 1;
+        ra.wide_lds = g.wide ? 1 : 0;
+        ra.groups = groups;
+        ra.rows_per_domain = (int)g.rpd;
+        ra.state = e->state.as<float>();
+        ra.term = e->term.as<unsigned char>();
         // DEVICE + random_model: ONE launch for the horizon, rows handed over between workgroups through the tagged-granule
         // table.  Only as many workgroups as are resident at once are launched; a batch with more logical workgroups (cfg4: 435)
         // is served in turns, workgroup b taking b, b + grid, ... every step.
@@ -920,7 +949,7 @@ int rollout_impl(hipets_engine* e, const float* actions, const float* s0, int32_
             // KSpec::WIDE two-tile instances deal a ragged last turn in one-tile logical workgroups (rollout.hpp "Ragged last turn": same
             // bits, 0.69 of the turn's time); HIPETS_RAGGED_LAST_TURN=0 keeps two-tile turns throughout (A/B measurements)
             static const bool ragged_ok = [] { const char* v = std::getenv("HIPETS_RAGGED_LAST_TURN"); return !(v && v[0] == '0'); }();
-            ra.ragged_last_turn = (wide && R == 2 && ragged_ok) ? 1 : 0;
+            ra.ragged_last_turn = (g.wide && R == 2 && ragged_ok) ? 1 : 0;
 
             if (launch_rollout(e, R, domains * groups, lds, ra, st)) return 1;  // cut to the resident capacity by the launcher
         } else if (per_step) {
@@ -936,33 +965,23 @@ int rollout_impl(hipets_engine* e, const float* actions, const float* s0, int32_
             if (launch_rollout(e, R, domains * groups, lds, ra, st)) return 1;
         }
     } else if (o->mode == HIPETS_MODE_FAST) {
-        const long long tiles = fast_tiles(pop, P);
         ra.eps = o->fast_eps;
         ra.use_philox = (o->fast_eps || o->no_sample) ? 0 : 1;
-        // (a caller-sized member schedule follows hipets_fast_geometry: the default call's geometry -- the WIDE instance's where one
-        // will run; rows_per_group = -1 asks for the general layout's, which is what calls with injected eps / traces run)
-        const bool wide = wide_model(md) && lean_call(md, ra) && o->rows_per_group <= 2;
-        if (!wide && wide_model(md) && o->member_schedule && o->rows_per_group == 0)
-            return fail("this call runs the general kernel layout (injected eps / traces / generic_kernel) on a model whose default geometry is "
-                        "the wide-output instance's: size member_schedule with hipets_fast_geometry(rows_per_group = -1) and pass its row-tile "
-                        "count as opts->rows_per_group");
-        ra.wide_lds = wide ? 1 : 0;
-        const int R = choose_R(e, tiles, 1, o->rows_per_group, H, wide, H > 1);
-        const size_t lds = lds_for(e, R, H, wide);
-        if (lds > e->lds_max) return fail("rows_per_group %d does not fit LDS", R);
-        const int groups = (int)((tiles + R - 1) / R);
-        const int nwg = groups;
-        if (nwg > 8000) return fail("FAST mode supports at most 8000 workgroups per launch (got %d); shard the population", nwg);
-        ra.groups = groups;
+        // the caller's schedule, or (null) every workgroup draws its own entries in its prologue (common.hpp fast_member)
+        ra.schedule = md.propagation != HIPETS_PROP_EXPECTATION ? o->member_schedule : nullptr;
+        Geometry g;
+        if (rollout_geometry(e, o->mode, B, 0, H, o->rows_per_group, GeoCall::rollout, ra, &g)) return 1;
+        const int nwg = g.groups;
         if (o->member_schedule && o->member_schedule_len != 0 && (long long)o->member_schedule_len != (long long)H * nwg)
             return fail("member_schedule holds %d entries, this call's geometry is horizon %d x %d workgroups (hipets_fast_geometry)",
                         o->member_schedule_len, H, nwg);
-        // the caller's schedule, or (null) every workgroup draws its own entries in its prologue (common.hpp fast_member)
-        ra.schedule = md.propagation != HIPETS_PROP_EXPECTATION ? o->member_schedule : nullptr;
+        ra.whole_horizon = g.whole_horizon ? 1 : 0;
+        ra.wide_lds = g.wide ? 1 : 0;
+        ra.groups = nwg;
         perm_radices((uint32_t)nwg, &ra.fm_a, &ra.fm_b);
         ra.t_begin = 0;
         ra.t_end = H;
-        if (launch_rollout(e, R, nwg, lds, ra, st)) return 1;
+        if (launch_rollout(e, g.R, nwg, g.lds, ra, st)) return 1;
     } else {
         return fail("unknown rollout mode %d", o->mode);
     }
@@ -1059,94 +1078,56 @@ int hipets_step(hipets_engine* e, const float* obs, const float* actions, int32_
     ENTER_STREAM(e, st);
     const ModelDev& md = e->md;
     if (o->rows_per_group < 0 || o->rows_per_group > kMaxR) return fail("rows_per_group outside [0, %d]", kMaxR);
-    if (!md.iid_members && B % md.M != 0 && !(o->mode == HIPETS_MODE_EXACT && o->rows_per_member > 0))  // gaussian_mlp.py:195-200
-        return fail("GaussianMLP ensemble requires batch size to be a multiple of the number of models. "
-                    "Current batch size is %d for %d models.", B, md.M);
-    // the kernel updates state / totals / terminated in place: run it on the caller's output buffers
-    HCHECK(hipMemcpyAsync(next_obs, obs, (size_t)B * md.obs_dim * 4, hipMemcpyDeviceToDevice, st));
-    HCHECK(hipMemsetAsync(rewards, 0, (size_t)B * 4, st));
-    HCHECK(hipMemsetAsync(dones, 0, (size_t)B, st));
+    if (check_member_maps(e, o, B, true)) return 1;
+    if (o->mode != HIPETS_MODE_EXACT && o->mode != HIPETS_MODE_DEVICE && o->mode != HIPETS_MODE_FAST) return fail("unknown rollout mode %d", o->mode);
     RolloutArgs ra{};
     ra.pop = B; ra.P = 1; ra.H = 1; ra.B = B;
-    ra.mode = o->mode;
     ra.actions = actions;
-    ra.s0 = nullptr;
-    ra.state = next_obs;
+    ra.state = next_obs;  // the kernel updates state / totals / terminated in place: it runs on the caller's output buffers
     ra.totals = rewards;
     ra.term = dones;
     ra.seed = o->seed;
     ra.stream_id = o->stream_id;
-    ra.trace_next_obs = nullptr;
-    ra.trace_rewards = nullptr;
-    ra.phase_cycles = nullptr;
     ra.generic_only = o->generic_kernel;
     ra.t_begin = 0;
     ra.t_end = 1;
-    if (o->mode == HIPETS_MODE_EXACT || o->mode == HIPETS_MODE_DEVICE) {
-        const bool device = o->mode == HIPETS_MODE_DEVICE;
-        const bool expectation = md.propagation == HIPETS_PROP_EXPECTATION;
-        const int domains = expectation ? 1 : md.M;
-        const bool slots = !device && !expectation && o->rows_per_member > 0;  // explicit per-row member maps, see hipets_rollout
-        if (!expectation && device && md.iid_members)
-            return fail("DEVICE mode has no BasicEnsemble (iid member map) variant: use FAST, or EXACT with injected maps");
-        if (!expectation && !device && !o->perms) return fail("EXACT mode with random_model/fixed_model propagation needs opts.perms");
-        if (!expectation && ((md.iid_members && !device && !slots) || (slots && o->rows_per_member > B)))
-            return fail("EXACT mode with per-row member maps needs opts.rows_per_member in [1, B] (padded member slots)");
-        const int rpd = expectation ? B : (slots ? o->rows_per_member : B / domains);
-        const long long tiles = (rpd + kTile - 1) / kTile;
-        const int R = choose_R(e, tiles, domains, o->rows_per_group, 1, false, false);
-        const size_t lds = lds_for(e, R, 1);
-        if (lds > e->lds_max) return fail("rows_per_group %d does not fit LDS", R);
-        ra.groups = (int)((tiles + R - 1) / R);
-        ra.rows_per_domain = rpd;
-        if (device) {
-            ra.use_philox = o->no_sample ? 0 : 1;
-            if (!expectation) {
-                ra.perm_n = (unsigned)B;
-                perm_radices((uint32_t)B, &ra.perm_a, &ra.perm_b);
-                // random_model: the permutation of (seed, stream_id), step 0.  fixed_model (a ModelEnv.step of a TS-infinity rollout keeps
-                // its member map while the eps change): the TS-infinity permutation of (seed, perm_stream_id) -- the stream of the reset --
-                // next to eps drawn from (seed, stream_id), the stream of the step
-                const bool fixed = md.propagation == HIPETS_PROP_FIXED_MODEL;
-                const uint64_t pstream = (fixed && o->perm_stream_id) ? o->perm_stream_id : o->stream_id;
-                ra.perm_keys = perm_round_keys(perm_key(o->seed, pstream, fixed ? 0xFFFFFFFFu : 0u));
-            }
-        } else {
-            ra.perm = expectation ? nullptr : reinterpret_cast<const long long*>(o->perms);
-            ra.perm_step = 0;
-            ra.eps = o->eps;
-            ra.use_philox = 0;
+    Geometry g;
+    if (rollout_geometry(e, o->mode, B, o->rows_per_member, 1, o->rows_per_group, GeoCall::step, ra, &g)) return 1;
+    ra.groups = g.groups;
+    ra.rows_per_domain = (int)g.rpd;
+    const bool expectation = md.propagation == HIPETS_PROP_EXPECTATION;
+    if (o->mode == HIPETS_MODE_DEVICE) {
+        ra.use_philox = o->no_sample ? 0 : 1;
+        if (!expectation) {
+            ra.perm_n = (unsigned)B;
+            perm_radices((uint32_t)B, &ra.perm_a, &ra.perm_b);
+            // random_model: the permutation of (seed, stream_id), step 0.  fixed_model (a ModelEnv.step of a TS-infinity rollout keeps
+            // its member map while the eps change): the TS-infinity permutation of (seed, perm_stream_id) -- the stream of the reset --
+            // next to eps drawn from (seed, stream_id), the stream of the step
+            const bool fixed = md.propagation == HIPETS_PROP_FIXED_MODEL;
+            const uint64_t pstream = (fixed && o->perm_stream_id) ? o->perm_stream_id : o->stream_id;
+            ra.perm_keys = perm_round_keys(perm_key(o->seed, pstream, fixed ? 0xFFFFFFFFu : 0u));
         }
-        if (launch_rollout(e, R, domains * ra.groups, lds, ra, st)) return 1;
-    } else if (o->mode == HIPETS_MODE_FAST) {
-        // One step of B independent rows: workgroup w owns rows [w * 16 R, (w + 1) * 16 R) and runs the member the FAST rule gives it
-        // (the caller's schedule, else common.hpp fast_member).  For ONE step the per-step launch form -- rows and state in HBM around
-        // the launch -- IS the FAST form, and every shape-specialised instance has it: the launch below is a DEVICE-form launch with
-        // the identity permutation (one domain of B rows) and RolloutArgs::fast_members.  (Until round 6 this was a FAST-path launch
-        // with per-row initial states, which only the generic / hidden-static instances have, behind a member-schedule kernel that
-        // ranked all workgroups' sort keys: a 100 000-row call took 0.44 ms where DEVICE mode took 0.34.)
-        const long long tiles = (B + kTile - 1) / kTile;
-        const int R = choose_R(e, tiles, 1, o->rows_per_group, 1, false, false);  // (a single step: two workgroups on a CU do not drift apart -- priced like DEVICE's)
-        const size_t lds = lds_for(e, R, 1);
-        if (lds > e->lds_max) return fail("rows_per_group %d does not fit LDS", R);
-        const int nwg = (int)((tiles + R - 1) / R);
-        if (nwg > 8000) return fail("FAST mode supports at most 8000 workgroups per launch (got %d)", nwg);
-        if (o->member_schedule && o->member_schedule_len != 0 && o->member_schedule_len != nwg)
+    } else if (o->mode == HIPETS_MODE_EXACT) {
+        ra.perm = expectation ? nullptr : reinterpret_cast<const long long*>(o->perms);
+        ra.eps = o->eps;
+    } else {
+        // FAST: one step of B independent rows, workgroup w owns rows [w * 16 R, (w + 1) * 16 R) and runs the member the FAST rule gives
+        // it (the caller's schedule, else common.hpp fast_member): the step-synchronous form with the identity permutation (one domain of
+        // B rows) and RolloutArgs::fast_members
+        if (o->member_schedule && o->member_schedule_len != 0 && o->member_schedule_len != g.groups)
             return fail("member_schedule holds %d entries, this call's geometry is %d workgroups (hipets_fast_geometry with rows_per_group -1)",
-                        o->member_schedule_len, nwg);
-        ra.mode = HIPETS_MODE_DEVICE;  // the kernel's per-step launch form (see above); nothing else reads the mode
-        ra.groups = nwg;
-        ra.rows_per_domain = B;
+                        o->member_schedule_len, g.groups);
         ra.eps = o->fast_eps;
         ra.use_philox = (o->fast_eps || o->no_sample) ? 0 : 1;
         ra.fast_members = 1;
-        ra.schedule = md.propagation != HIPETS_PROP_EXPECTATION ? o->member_schedule : nullptr;
-        perm_radices((uint32_t)nwg, &ra.fm_a, &ra.fm_b);
-        if (launch_rollout(e, R, nwg, lds, ra, st)) return 1;
-    } else {
-        return fail("unknown rollout mode %d", o->mode);
+        ra.schedule = expectation ? nullptr : o->member_schedule;
+        perm_radices((uint32_t)g.groups, &ra.fm_a, &ra.fm_b);
     }
-    return 0;
+    HCHECK(hipMemcpyAsync(next_obs, obs, (size_t)B * md.obs_dim * 4, hipMemcpyDeviceToDevice, st));
+    HCHECK(hipMemsetAsync(rewards, 0, (size_t)B * 4, st));
+    HCHECK(hipMemsetAsync(dones, 0, (size_t)B, st));
+    return launch_rollout(e, g.R, g.domains * g.groups, g.lds, ra, st);
 }
 
 int hipets_fast_schedule(hipets_engine* e, int32_t H, int32_t nwg, uint64_t seed, uint64_t stream_id, int32_t* schedule,

@@ -138,9 +138,9 @@ inline bool lean_call(const ModelDev& md, const RolloutArgs& ra) {
     return !ra.generic_only && md.activation == HIPETS_ACT_SILU && md.normalizer == HIPETS_NORM_F64 &&
            !md.deterministic && md.propagation != HIPETS_PROP_EXPECTATION && md.lv_rows == 1 && fused_term_ok(md) && !ra.eps && ra.use_philox &&
 #if defined(HIPETS_STEP_TRACE) || (defined(HIPETS_LEAN_PROF) && HIPETS_LEAN_PROF)
-           !ra.trace_next_obs && !ra.trace_rewards && ra.pop_env == 0 && !ra.init_states && !ra.write_back;  // the stamps go to phase_cycles
+           !ra.trace_next_obs && !ra.trace_rewards && ra.pop_env == 0;  // the stamps go to phase_cycles
 #else
-           !ra.trace_next_obs && !ra.trace_rewards && !ra.phase_cycles && ra.pop_env == 0 && !ra.init_states && !ra.write_back;
+           !ra.trace_next_obs && !ra.trace_rewards && !ra.phase_cycles && ra.pop_env == 0;
 #endif
 }
 

@@ -87,7 +87,8 @@ struct ModelDev {
 
 struct RolloutArgs {
     int pop, P, H, B;
-    int mode;
+    int whole_horizon;  // the kernel form: 1 = FAST (one launch for the horizon, rows tiled from s0, state in LDS); 0 = step-synchronous
+                        //   (rows by identity / permutation, state in HBM around the launch, or handed over in the persistent form)
     int t_begin, t_end;
     int groups;           // FAST: candidate groups per particle; EXACT: workgroups per member domain
     int rows_per_domain;  // EXACT: B / M (or B for expectation)
@@ -106,15 +107,13 @@ struct RolloutArgs {
     const int* schedule;   // FAST: [H, nWG] member slot per (step, workgroup), injected by the caller; null = every workgroup draws its own
                            //   entries in its prologue (common.hpp fast_member, radices fm_a x fm_b = perm_radices(gridDim.x))
     unsigned fm_a, fm_b;
-    int fast_members;      // the NON-fast kernel path (rows by identity / permutation, state in HBM around the launch) with the workgroup's
-                           //   member chosen as in FAST mode (`schedule`, or the in-kernel draw for step t_begin): hipets_step in FAST mode --
-                           //   for one step the per-step launch form IS the FAST form, and it exists in every shape-specialised instance
+    int fast_members;      // the step-synchronous form (whole_horizon = 0) with the workgroup's member chosen as in FAST mode (`schedule`,
+                           //   or the in-kernel draw for step t_begin): hipets_step in FAST mode -- for one step that form IS the FAST form,
+                           //   and it exists in every shape-specialised instance
     float* trace_next_obs;
     float* trace_rewards;
     long long* phase_cycles;  // optional [kWaves][16 phases] cycle counters of workgroup 0 (profiling aid)
     int pop_env;               // FAST batched planning: candidates per environment (candidate c starts from s0[c / pop_env]); 0 = one env
-    const float* init_states;  // FAST: optional per-row initial states [B,obs] (ModelEnv.step path) instead of tiling s0
-    int write_back;            // FAST: also write the final state [B,obs] to `state` and the done flags to `term`
     int generic_only;          // hipets_rollout_opts.generic_kernel: 1 = only the fully generic kernel instance; 2 = no shape-specialised
                                // (lean) instance, but the hidden-static one (KSpec::HID_STATIC) where the model has its width
     int wide_lds;              // the host sized the LDS (and chose R) for the KSpec::WIDE layout: the launcher runs that instance or fails
@@ -1767,7 +1766,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     }
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool fast = S::KMODE >= 0 ? S::KMODE == HIPETS_MODE_FAST : ra.mode == HIPETS_MODE_FAST;
+    const bool fast = S::KMODE >= 0 ? S::KMODE == HIPETS_MODE_FAST : ra.whole_horizon != 0;
     const bool expectation = kLean ? false : md.propagation == HIPETS_PROP_EXPECTATION;
     // Modes whose workgroups are bound to a member (EXACT / DEVICE: member = wg / groups): hardware deals block b to XCD b % 8
     // (observed, used for speed only), so the logical workgroup index is taken XCD-major -- XCD x runs a CONTIGUOUS range of
@@ -1973,8 +1972,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                     const int s = i / md.obs_dim, d = i - s * md.obs_dim;
                     const int rid = sm.rowid[s];
                     if (fast) {
-                        if (!kLean && ra.init_states) v[q] = rid >= 0 ? ra.init_states[(size_t)rid * md.obs_dim + d] : 0.f;
-                        else if (!kLean && ra.pop_env > 0) v[q] = rid >= 0 ? ra.s0[(size_t)((rid / ra.P) / ra.pop_env) * md.obs_dim + d] : 0.f;
+                        if (!kLean && ra.pop_env > 0) v[q] = rid >= 0 ? ra.s0[(size_t)((rid / ra.P) / ra.pop_env) * md.obs_dim + d] : 0.f;
                         else v[q] = ra.s0[d];
                     } else if (rid >= 0) {
                         // persistent form: starts from the tiled s0 itself (batched planning: the s0 of the row's environment)
@@ -3123,13 +3121,13 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
         const int rid = sm.rowid[s];
         if (rid < 0 || persist) continue;  // persistent form: written in the last step's reward phase
         ra.totals[rid] = sm.tot[s];
-        if ((!fast && !persist) || (!kLean && ra.write_back)) ra.term[rid] = (unsigned char)sm.term[s];
+        if (!fast && !persist) ra.term[rid] = (unsigned char)sm.term[s];
     }
     if (prof.on) {  // flush the phase accumulators of this wave
 #pragma unroll
         for (int i = 0; i < 16; ++i) ra.phase_cycles[wave * 16 + i] += prof.slot[i];
     }
-    if ((!fast && !persist) || (!kLean && ra.write_back)) {
+    if (!fast && !persist) {
         for (int i = tid; i < ROWS * md.obs_dim; i += kThreads) {
             const int s = i / md.obs_dim, d = i % md.obs_dim;
             const int rid = sm.rowid[s];

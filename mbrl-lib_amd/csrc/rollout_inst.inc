@@ -236,7 +236,7 @@ hipError_t HIPETS_FN(_fast)(int grid, unsigned lds, int lds_max, const ModelDev&
 #if HIPETS_PART == 1
 hipError_t HIPETS_FN()(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start,
                             hipEvent_t stop) {
-    const bool fast = ra.mode == HIPETS_MODE_FAST;
+    const bool fast = ra.whole_horizon != 0;
     if (md.precision == HIPETS_PREC_BF16X3) {
         if (lean_call(md, ra)) {
             if (fast) {

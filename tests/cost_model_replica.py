@@ -15,14 +15,14 @@ def wave_units(C, R):
     return max(simd)
 
 
-def cost(tiles, slices, R, lean, desync, C=13, wide=False):
-    a = ((6.45 if desync else 2.67) if wide else 1.77) * C / 13.0
+def cost(tiles, slices, R, lean, drift, C=13, wide=False):
+    a = ((6.45 if drift else 2.67) if wide else 1.77) * C / 13.0
     groups = (tiles + R - 1) // R
     nwg = groups * slices
     n = (nwg + NUM_CU - 1) // NUM_CU
     co = 2 if (R <= 2 and not wide) else 1
     u = wave_units(C, R)
-    u_pair = C * R / 4.0 if (co == 2 and desync) else u
+    u_pair = C * R / 4.0 if (co == 2 and drift) else u
     full, rem = divmod(n, co)
     c = full * (a + co * u_pair) + ((a + rem * u) if rem else 0.0)
     return c * (1.0 if lean else 1.08)
