@@ -215,12 +215,12 @@ class Engine:
     def step(self, obs: torch.Tensor, actions: torch.Tensor, *, mode: str = "fast", sample: bool = True,
              perm: Optional[torch.Tensor] = None, eps: Optional[torch.Tensor] = None, seed: int = 0, stream_id: int = 0,
              member_schedule: Optional[torch.Tensor] = None, rows_per_group: int = 0,
-             members: Optional[torch.Tensor] = None, perm_stream_id: int = 0):
+             members: Optional[torch.Tensor] = None, perm_stream_id: int = 0, generic_kernel=False):
         """One model transition for B independent rows (ModelEnv.step, mbrl/models/model_env.py:87-140).
         Returns (next_obs [B,obs], rewards [B,1], dones [B,1] bool) on the device.  ``members`` int64 [B]: EXACT-mode
         member of every row for BasicEnsemble models (GaussianMLP models take ``perm``).  ``perm_stream_id`` (DEVICE mode,
         fixed_model propagation): the stream whose TS-infinity permutation the step uses -- the rollout's reset -- while
-        ``stream_id`` keys this step's eps; 0 = ``stream_id``."""
+        ``stream_id`` keys this step's eps; 0 = ``stream_id``.  ``generic_kernel`` as for :meth:`rollout`."""
         if self.spec is None:
             raise HipetsError("Engine.set_model() has not been called")
         dev = self.device
@@ -235,6 +235,7 @@ class Engine:
         o.rows_per_group = int(rows_per_group)
         o.no_sample = int(not sample)
         o.perm_stream_id = int(perm_stream_id) & (2**64 - 1)
+        o.generic_kernel = int(generic_kernel)
         if mode == "device":
             if perm is not None or eps is not None or members is not None:
                 raise ValueError("mode='device' draws its permutation and eps in-kernel")

@@ -16,6 +16,7 @@ from __future__ import annotations
 
 import importlib
 import time
+import weakref
 from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -212,7 +213,18 @@ class HipTrajectoryEvalFn:
 class ModelEnv:
     """The model-as-environment interface of mbrl/models/model_env.py:15-191 on the fused kernels:
     ``reset`` / ``step`` (one transition for a batch of independent rows: what MBPO-style model rollouts and the
-    visualisers call) and ``evaluate_action_sequences``.  Built from a ``ModelSpec`` or a live mbrl ``ModelEnv``."""
+    visualisers call) and ``evaluate_action_sequences``.  Built from a ``ModelSpec`` or a live mbrl ``ModelEnv``.
+
+    TS-infinity (``fixed_model``) member maps travel in the model state, as the reference's ``propagation_indices`` do
+    (gaussian_mlp.py:207-212, basic_ensemble.py:182-187): a step is a function of its state and the env's model and seed.
+    Every ``reset`` draws a fresh map and returns it as ``propagation_indices`` -- a [B] permutation of the rows for GaussianMLP
+    models in 'device' / 'exact' mode, [B] int64 member slots for BasicEnsemble models and for every model in 'fast' mode
+    (``schedule[row // (16 r)]``) -- and, in the in-kernel modes, the stream that keys it, under ``MAP_STREAM_KEY`` (an int64
+    scalar tensor).  A step whose state still holds the very tensor that reset returned re-derives that map in-kernel from
+    (seed, stream); any other ``propagation_indices`` tensor is used as given (the EXACT kernel, eps still drawn from the step's own
+    stream); a ``fixed_model`` state without one raises the reference's ValueError."""
+
+    MAP_STREAM_KEY = "hipets_map_stream"
 
     def __init__(self, model, engine: Optional[Engine] = None, mode: str = "device", seed: int = 0, device=None,
                  generator: Optional[torch.Generator] = None):
@@ -222,10 +234,8 @@ class ModelEnv:
         self.engine, self.device, self.mode, self.seed = self._eval.engine, self._eval.device, mode, int(seed)
         self._return_as_np = True
         self._steps = 0
-        self._fixed_perm = None
-        self._fixed_members = None
-        self._fixed_schedule = None
-        self._reset_stream = 0
+        self._resets = 0
+        self._exported = weakref.WeakValueDictionary()  # reset stream -> the propagation_indices tensor that reset returned
 
     def _step_mode(self) -> str:
         """Kernel mode of ``step`` for the in-kernel randomness modes: 'device' where the library has it (GaussianMLP ensembles; any
@@ -239,31 +249,60 @@ class ModelEnv:
         return self._eval.spec
 
     def reset(self, initial_obs_batch: np.ndarray, return_as_np: bool = True) -> Dict[str, torch.Tensor]:
-        """model_env.py:62-85: returns the model state {"obs", "propagation_indices"}."""
+        """model_env.py:62-85: returns the model state {"obs", "propagation_indices"} (+ ``MAP_STREAM_KEY``, see the class)."""
         assert len(initial_obs_batch.shape) == 2  # batch, obs_dim
         self._eval.refresh()
+        if self.engine.spec is not self.spec:  # engines are shared per GPU: the maps below are exported for THIS model
+            self.engine.set_model(self.spec)
         obs = torch.as_tensor(np.asarray(initial_obs_batch, dtype=np.float32)).to(self.device).contiguous()
         self._return_as_np = return_as_np
         B = obs.shape[0]
         self._eval.num_particles = 1
         self._eval.check_batch(B)
-        self._fixed_perm = self._fixed_schedule = None
-        self._fixed_members = None
-        if self.spec.propagation == "fixed_model":  # model.py:404-407 -> gaussian_mlp.py:363-375
-            if self.mode == "exact" and self.spec.ensemble_kind == "basic_ensemble":  # basic_ensemble.py:255-260
-                self._fixed_members = torch.randint(len(self.spec.members), (B,), generator=self._eval._cpu_rng())
-                return {"obs": obs, "propagation_indices": self._fixed_members}
-            if self.mode == "exact":
-                self._fixed_perm = torch.randperm(B).to(self.device)
-            elif self._step_mode() == "device":
-                # the TS-infinity permutation of this rollout: keyed by the stream of the reset, evaluated in-kernel at every step
-                # (hipets_rollout_opts.perm_stream_id); exported here as the reference's ``propagation_indices``
-                self._reset_stream = self._steps + 1
-                self._fixed_perm = self.engine.device_perms(1, B, self.seed, self._reset_stream)
+        state = {"obs": obs, "propagation_indices": None}
+        if self.spec.propagation != "fixed_model":
+            return state
+        # model.py:404-407 -> gaussian_mlp.py:363-375 / basic_ensemble.py:255-260: one fresh map per reset
+        basic = self.spec.ensemble_kind == "basic_ensemble"
+        if self.mode == "exact":
+            if basic:
+                state["propagation_indices"] = torch.randint(len(self.spec.members), (B,), generator=self._eval._cpu_rng())
             else:
-                nwg, _ = self.engine.fast_geometry(B, 1, 1, -1)  # hipets_step runs the general kernel layout
-                self._fixed_schedule = self.engine.fast_schedule(1, nwg, self.seed, self._steps + 1).contiguous()
-        return {"obs": obs, "propagation_indices": self._fixed_perm}
+                state["propagation_indices"] = torch.randperm(B).to(self.device)
+            return state
+        self._resets += 1
+        stream = self._resets  # (0 would mean "none" to hipets_rollout_opts.perm_stream_id)
+        if self._step_mode() == "device":
+            # the TS-infinity permutation of (seed, stream), evaluated in-kernel at every step (hipets_rollout_opts.perm_stream_id)
+            idx = self.engine.device_perms(1, B, self.seed, stream)
+        else:
+            idx = self._fast_map(B, stream)[1]
+        self._exported[stream] = idx
+        state["propagation_indices"] = idx
+        state[self.MAP_STREAM_KEY] = torch.tensor(stream, dtype=torch.int64)
+        return state
+
+    def _fast_map(self, B: int, stream: int):
+        """(member schedule, per-row member slots) of the FAST-mode TS-infinity map of (seed, stream): hipets_step runs the general
+        kernel layout, workgroup w owns rows [16 r w, 16 r (w + 1))."""
+        nwg, r = self.engine.fast_geometry(B, 1, 1, -1)
+        sched = self.engine.fast_schedule(1, nwg, self.seed, stream).contiguous()
+        return sched, sched[0].long()[torch.arange(B, device=self.device) // (16 * r)]
+
+    def _explicit_map(self, indices, B: int):
+        """A caller's ``propagation_indices``, checked on the host before a kernel reads them as row / member indices: member slots in
+        [0, M) for BasicEnsemble models and in 'fast' mode, else a permutation of [0, B).  Returns (perm, members) for Engine.step."""
+        m = torch.as_tensor(indices).detach().to("cpu", torch.int64).reshape(-1)
+        if m.numel() != B:
+            raise ValueError(f"propagation_indices holds {m.numel()} entries for a batch of {B} rows")
+        if self.spec.ensemble_kind == "basic_ensemble" or self.mode == "fast":
+            M = len(self.spec.members)
+            if int(m.min()) < 0 or int(m.max()) >= M:
+                raise ValueError(f"propagation_indices must hold member slots in [0, {M})")
+            return None, m
+        if not torch.equal(m.sort().values, torch.arange(B)):
+            raise ValueError("propagation_indices of a GaussianMLP model must be a permutation of the batch rows")
+        return m.to(self.device), None
 
     def step(self, actions, model_state: Dict[str, torch.Tensor], sample: bool = False):
         """model_env.py:87-140: (next_observs, rewards, dones, next_model_state)."""
@@ -276,28 +315,42 @@ class ModelEnv:
         actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
         obs = model_state["obs"].to(device=self.device, dtype=torch.float32).contiguous()
         B = obs.shape[0]
+        fixed = self.spec.propagation == "fixed_model"
+        indices = model_state.get("propagation_indices")
+        if fixed and indices is None:  # gaussian_mlp.py:207-211, basic_ensemble.py:182-186
+            raise ValueError("When using propagation='fixed_model', `propagation_indices` must be provided.")
         self._steps += 1
+        keyed = 0  # the stream of the reset whose own map this state carries (in-kernel modes)
+        if fixed and self.mode != "exact":
+            s = model_state.get(self.MAP_STREAM_KEY)
+            if s is not None and self._exported.get(int(s)) is indices:
+                keyed = int(s)
+        draws = sample and not self.spec.deterministic
         if self.mode == "exact":
             perm = eps = members = None
-            basic = self.spec.ensemble_kind == "basic_ensemble"
             if self.spec.propagation == "random_model":
-                if basic:  # basic_ensemble.py:122-129 (the generator, before this step's normal)
+                if self.spec.ensemble_kind == "basic_ensemble":  # basic_ensemble.py:122-129 (the generator, before this step's normal)
                     members = torch.randint(len(self.spec.members), (B,), generator=self._eval._cpu_rng())
                 else:
                     perm = torch.randperm(B).to(self.device)  # gaussian_mlp.py:205 (global RNG)
-            elif self.spec.propagation == "fixed_model":
-                perm, members = self._fixed_perm, self._fixed_members
-            if sample and not self.spec.deterministic:
+            elif fixed:
+                perm, members = self._explicit_map(indices, B)
+            if draws:
                 eps = torch.empty(B, self.spec.out_dim).normal_(0.0, 1.0, generator=self._eval._cpu_rng()).to(self.device)
             nobs, rew, done = self.engine.step(obs, actions, mode="exact", sample=sample, perm=perm, eps=eps, members=members)
+        elif fixed and not keyed:
+            # a map the caller supplied: exactly that map, with the eps the in-kernel modes draw for this step's stream
+            perm, members = self._explicit_map(indices, B)
+            eps = self.engine.fast_normals(1, B, self.seed, self._steps)[0] if draws else None
+            nobs, rew, done = self.engine.step(obs, actions, mode="exact", sample=sample, perm=perm, eps=eps, members=members)
         elif self._step_mode() == "device":
-            fixed = self.spec.propagation == "fixed_model"
             nobs, rew, done = self.engine.step(obs, actions, mode="device", sample=sample, seed=self.seed, stream_id=self._steps,
-                                               perm_stream_id=self._reset_stream if fixed else 0)
+                                               perm_stream_id=keyed)
         else:
+            sched = self._fast_map(B, keyed)[0] if keyed else None
             nobs, rew, done = self.engine.step(obs, actions, mode="fast", sample=sample, seed=self.seed, stream_id=self._steps,
-                                               member_schedule=self._fixed_schedule)
-        next_state = {"obs": nobs, "propagation_indices": model_state.get("propagation_indices")}
+                                               member_schedule=sched)
+        next_state = {**model_state, "obs": nobs}
         if self._return_as_np:
             return nobs.cpu().numpy(), rew.cpu().numpy(), done.cpu().numpy(), next_state
         return nobs, rew, done, next_state
