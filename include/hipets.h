@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define HIPETS_ABI_VERSION 6
+#define HIPETS_ABI_VERSION 7
 #define HIPETS_MAX_LAYERS 8
 
 typedef struct hipets_engine hipets_engine;
@@ -485,11 +485,14 @@ typedef struct {
     float* trace_rewards;
     int64_t* phase_cycles;   /* ABI v6: DEVICE [8,16] phase accumulators of workgroup 0, as hipets_rollout_opts.phase_cycles;    */
                              /*   filled by profiling builds (-DHIPETS_LEAN_PROF=1) only, ignored by the shipped library         */
+    int32_t n_env;           /* ABI v7: batched rollouts: the pop candidates are n_env groups of pop / n_env (pop must divide),  */
+                             /*   group g starts from latent0[g] / belief0[g] (then [n_env, latent] / [n_env, belief]); 0/1 = one */
 } hipets_planet_opts;
 /* ModelEnv.evaluate_action_sequences on a PlaNetModel with no_termination and the learned reward head
  * (model_env.py:145-191, mbrl/algorithms/planet.py): actions DEVICE [pop,H,A]; latent0 / belief0 DEVICE [latent] /
- * [belief] = the model's saved posterior sample and belief (planet.py:669-672), tiled over the pop * P rows;
- * returns DEVICE [pop] particle-averaged.  One kernel launch for the whole horizon.                              */
+ * [belief] = the model's saved posterior sample and belief (planet.py:669-672), tiled over the pop * P rows (one per
+ * environment with opts.n_env > 1); returns DEVICE [pop] particle-averaged.  One kernel launch for the whole horizon.
+ * eps, the traces and the in-kernel draws are indexed by the launch-global row (candidate * P + particle).          */
 int hipets_planet_rollout(hipets_engine* e, const float* actions, const float* latent0, const float* belief0, int32_t pop,
                           int32_t horizon, int32_t num_particles, const hipets_planet_opts* opts, float* returns, void* stream);
 
@@ -499,6 +502,24 @@ int hipets_planet_rollout(hipets_engine* e, const float* actions, const float* l
 int hipets_plan_planet_cem(hipets_engine* e, const hipets_cem_params* p, const float* x0, const float* lower, const float* upper,
                            const float* latent0, const float* belief0, int32_t num_particles, uint64_t seed, uint64_t plan_id,
                            float* out, void* stream);
+
+/* Batched PlaNet planning: the three fused plans for n_env environments in ONE set of launches per
+ * iteration, each environment rolled out from its own latent start state (planet.py:656-672 per environment).  Arguments as
+ * hipets_plan_cem_batched / hipets_plan_mppi_batched / hipets_plan_icem_batched, with DEVICE latent0 [n_env, latent] /
+ * belief0 [n_env, belief] instead of the HOST s0; population_size is PER environment, n_env = 1 is allowed.  The rollouts draw
+ * their eps in-kernel (Philox, keyed by the launch-global row).  Local GPU only: an engine's communicator is not used.
+ * hipets_set_plan_trace records them like the ensemble's batched plans.                                                  */
+int hipets_plan_planet_cem_batched(hipets_engine* e, const hipets_cem_params* p, int32_t n_env, const float* x0, const float* lower,
+                                   const float* upper, const float* latent0, const float* belief0, int32_t num_particles, uint64_t seed,
+                                   uint64_t plan_id, float* out, void* stream);
+int hipets_plan_planet_mppi_batched(hipets_engine* e, int32_t population_size, int32_t horizon, int32_t act_dim, int32_t num_iterations,
+                                    double gamma, double beta, int32_t n_env, float* mean, const float* lower, const float* upper,
+                                    const float* latent0, const float* belief0, int32_t num_particles, uint64_t seed, uint64_t plan_id,
+                                    void* stream);
+int hipets_plan_planet_icem_batched(hipets_engine* e, const hipets_icem_params* p, int32_t n_env, const float* x0, const float* lower,
+                                    const float* upper, float* elite, int32_t has_elite, const int32_t* keep_idx, const float* latent0,
+                                    const float* belief0, int32_t num_particles, uint64_t seed, uint64_t plan_id, float* out,
+                                    void* stream);
 
 /* ---- instrumentation (bench.py roofline leg) ----------------------------------------------- */
 /* on = 1: every rollout-kernel launch carries a start / stop hipEvent pair on its dispatch packet; on = k > 1: every

@@ -1057,11 +1057,60 @@ int sharded_evaluate(hipets_engine* e, const float* population, const int rows, 
     return 0;
 }
 
+int planet_rollout_impl(hipets_engine* e, const float* actions, const float* latent0, const float* belief0, int32_t pop, int32_t H,
+                        int32_t P, const hipets_planet_opts* o, float* returns, hipStream_t st);
+
+// The objective a fused plan rolls out every iteration (trajectory_opt.py's obj_fun, model_env.py:145-191): the engine's ensemble
+// from HOST observations s0 [n_env, obs_dim], staged once by the plan's prologue, or the PlaNet latent model from DEVICE start states
+// latent0 [n_env, latent] / belief0 [n_env, belief] (planet.py:656-672, one per environment; nothing to stage, no communicator).
+// The plan drivers below are shared; evaluate() is where the two differ inside the iteration loop.
+struct PlanObjective {
+    bool planet = false;
+    const float* s0 = nullptr;
+    const float* latent0 = nullptr;
+    const float* belief0 = nullptr;
+
+    bool has_model(const hipets_engine* e) const { return e && (planet ? e->has_planet : e->has_model); }
+    int no_model() const {
+        return planet ? fail("engine has no PlaNet model (call hipets_planet_set_model)") : fail("engine has no model (call hipets_set_model)");
+    }
+    bool has_start() const { return planet ? (latent0 && belief0) : s0 != nullptr; }
+    int check_act_dim(const hipets_engine* e, int A) const {
+        if (planet) return A != e->pd.action ? fail("act_dim %d != model action_size %d", A, e->pd.action) : 0;
+        return A != e->md.act_dim ? fail("act_dim %d != model act_dim %d", A, e->md.act_dim) : 0;
+    }
+    // `rows` candidates of ro->n_env environments (environment after environment), iteration ro->stream_id; returns == nullptr: the
+    // per-row totals stay in e->totals and the refit kernel forms the particle means (CemDev::totals)
+    int evaluate(hipets_engine* e, const float* population, int rows, int H, int P, const hipets_rollout_opts* ro, float* returns,
+                 void* stream) const {
+        if (!planet) return rollout_impl(e, population, nullptr, rows, H, P, ro, returns, stream);
+        hipets_planet_opts po{};
+        po.seed = ro->seed;
+        po.stream_id = ro->stream_id;
+        po.n_env = ro->n_env;
+        return planet_rollout_impl(e, population, latent0, belief0, rows, H, P, &po, returns, reinterpret_cast<hipStream_t>(stream));
+    }
+};
+PlanObjective ensemble_objective(const float* s0) {
+    PlanObjective o;
+    o.s0 = s0;
+    return o;
+}
+PlanObjective planet_objective(const float* latent0, const float* belief0) {
+    PlanObjective o;
+    o.planet = true;
+    o.latent0 = latent0;
+    o.belief0 = belief0;
+    return o;
+}
+
+int plan_cem_impl(hipets_engine* e, const hipets_cem_params* p, int32_t n_env, const float* x0, const float* lower, const float* upper,
+                  const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id, float* out, void* stream);
 int plan_mppi_impl(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t num_iterations, double gamma, double beta, int32_t n_env,
-                   float* mean, const float* lower, const float* upper, const float* s0, int32_t P, uint64_t seed, uint64_t plan_id,
+                   float* mean, const float* lower, const float* upper, const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id,
                    void* stream, bool sharded);
 int plan_icem_impl(hipets_engine* e, const hipets_icem_params* p, int32_t n_env, const float* x0, const float* lower, const float* upper,
-                   float* elite, int32_t has_elite, const int32_t* keep_idx, const float* s0, int32_t P, uint64_t seed, uint64_t plan_id,
+                   float* elite, int32_t has_elite, const int32_t* keep_idx, const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id,
                    float* out, void* stream, bool sharded);
 
 }  // namespace
@@ -1321,11 +1370,20 @@ int hipets_plan_cem(hipets_engine* e, const hipets_cem_params* p, const float* x
 int hipets_plan_cem_batched(hipets_engine* e, const hipets_cem_params* p, int32_t n_env, const float* x0, const float* lower,
                             const float* upper, const float* s0, int32_t P, uint64_t seed, uint64_t plan_id, float* out,
                             void* stream) {
-    if (!e || !e->has_model) return fail("engine has no model (call hipets_set_model)");
+    return plan_cem_impl(e, p, n_env, x0, lower, upper, ensemble_objective(s0), P, seed, plan_id, out, stream);
+}
+
+}  // extern "C"
+
+namespace {
+int plan_cem_impl(hipets_engine* e, const hipets_cem_params* p, int32_t n_env, const float* x0, const float* lower, const float* upper,
+                  const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id, float* out, void* stream) {
+    if (!obj.has_model(e)) return obj.no_model();
     if (check_cem(p)) return 1;
-    if (!x0 || !lower || !upper || !s0 || !out) return fail("null argument");
-    if (p->act_dim != e->md.act_dim) return fail("act_dim %d != model act_dim %d", p->act_dim, e->md.act_dim);
+    if (!x0 || !lower || !upper || !obj.has_start() || !out) return fail("null argument");
+    if (obj.check_act_dim(e, p->act_dim)) return 1;
     if (n_env < 1 || n_env > 4096) return fail("n_env %d outside [1, 4096]", n_env);
+    if (obj.planet && P < 1) return fail("bad pop/horizon/particles");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
@@ -1344,7 +1402,7 @@ int hipets_plan_cem_batched(hipets_engine* e, const hipets_cem_params* p, int32_
     ro.n_env = n_env;
     int n2 = 1;
     while (n2 < c.pop) n2 <<= 1;
-    if (plan_prologue(e, s0, n_env, c.H, p->num_iterations, seed, plan_id * (uint64_t)p->num_iterations, st)) return 1;
+    if (!obj.planet && plan_prologue(e, obj.s0, n_env, c.H, p->num_iterations, seed, plan_id * (uint64_t)p->num_iterations, st)) return 1;
     for (int i = 0; i < p->num_iterations; ++i) {
         const uint64_t sid = plan_id * (uint64_t)p->num_iterations + (uint64_t)i;
         const long long n = (long long)npop * c.D;
@@ -1354,7 +1412,7 @@ int hipets_plan_cem_batched(hipets_engine* e, const hipets_cem_params* p, int32_
         HCHECK(hipGetLastError());
         ro.stream_id = sid;
         // the particle mean of the returns (model_env.py:190-191) happens inside the refit kernel: one launch less per iteration
-        if (rollout_impl(e, e->population.as<float>(), nullptr, (int32_t)npop, c.H, P, &ro, nullptr, stream)) return 1;
+        if (obj.evaluate(e, e->population.as<float>(), (int32_t)npop, c.H, P, &ro, nullptr, stream)) return 1;
         int* eidx = (e->has_trace && e->trace.elite_idx) ? e->trace.elite_idx + (size_t)i * n_env * c.K : nullptr;
         CemDev cr = c;
         cr.totals = e->totals.as<float>();
@@ -1369,6 +1427,9 @@ int hipets_plan_cem_batched(hipets_engine* e, const hipets_cem_params* p, int32_
     HCHECK(hipMemcpyAsync(out, p->return_mean_elites ? e->mu.p : e->best_solution.p, nd * 4, hipMemcpyDeviceToDevice, st));
     return 0;
 }
+}  // namespace
+
+extern "C" {
 
 int hipets_plan_mppi(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t num_iterations, double gamma, double beta,
                      float* mean, const float* lower, const float* upper, const float* s0, int32_t P, uint64_t seed,
@@ -1379,28 +1440,29 @@ int hipets_plan_mppi(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_
 int hipets_plan_mppi_batched(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t num_iterations, double gamma, double beta,
                              int32_t n_env, float* mean, const float* lower, const float* upper, const float* s0, int32_t P,
                              uint64_t seed, uint64_t plan_id, void* stream) {
-    return plan_mppi_impl(e, pop, H, A, num_iterations, gamma, beta, n_env, mean, lower, upper, s0, P, seed, plan_id, stream, false);
+    return plan_mppi_impl(e, pop, H, A, num_iterations, gamma, beta, n_env, mean, lower, upper, ensemble_objective(s0), P, seed, plan_id, stream, false);
 }
 
 int hipets_plan_mppi_sharded(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t num_iterations, double gamma, double beta,
                              float* mean, const float* lower, const float* upper, const float* s0, int32_t P, uint64_t seed,
                              uint64_t plan_id, void* stream) {
     if (e && !e->comm) return fail("no communicator (call hipets_comm_init)");
-    return plan_mppi_impl(e, pop, H, A, num_iterations, gamma, beta, 1, mean, lower, upper, s0, P, seed, plan_id, stream, true);
+    return plan_mppi_impl(e, pop, H, A, num_iterations, gamma, beta, 1, mean, lower, upper, ensemble_objective(s0), P, seed, plan_id, stream, true);
 }
 
 }  // extern "C"
 
 namespace {
 int plan_mppi_impl(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t num_iterations, double gamma, double beta, int32_t n_env,
-                   float* mean, const float* lower, const float* upper, const float* s0, int32_t P, uint64_t seed, uint64_t plan_id,
+                   float* mean, const float* lower, const float* upper, const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id,
                    void* stream, const bool sharded) {
-    if (!e || !e->has_model) return fail("engine has no model (call hipets_set_model)");
-    if (!mean || !lower || !upper || !s0) return fail("null argument");
+    if (!obj.has_model(e)) return obj.no_model();
+    if (!mean || !lower || !upper || !obj.has_start()) return fail("null argument");
     if (pop < 1 || pop > 12000) return fail("population_size %d outside [1, 12000]", pop);
     if (H < 1 || num_iterations < 0) return fail("bad horizon/num_iterations");
-    if (A != e->md.act_dim) return fail("act_dim %d != model act_dim %d", A, e->md.act_dim);
+    if (obj.check_act_dim(e, A)) return 1;
     if (n_env < 1 || n_env > 4096) return fail("n_env %d outside [1, 4096]", n_env);
+    if (obj.planet && P < 1) return fail("bad pop/horizon/particles");
     if (sharded && check_shards(e, pop, P)) return 1;  // identical on every rank, before any collective
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
@@ -1424,7 +1486,7 @@ int plan_mppi_impl(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t 
         hipLaunchKernelGGL(mppi_shift_kernel, dim3((unsigned)((n_env * nd + 255) / 256)), dim3(256), 0, st, n_env, H, A, e->mu.as<float>(), mean,
                            e->past_action.as<float>());
         HCHECK(hipGetLastError());
-        return plan_prologue(e, s0, n_env, H, num_iterations, ro.seed, plan_id * (uint64_t)num_iterations, st);
+        return obj.planet ? 0 : plan_prologue(e, obj.s0, n_env, H, num_iterations, ro.seed, plan_id * (uint64_t)num_iterations, st);
     };
     le.note(prologue());
     if (!sharded && !le.ok()) return le.report();
@@ -1443,7 +1505,7 @@ int plan_mppi_impl(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t 
         if (sharded) {
             if (sharded_evaluate(e, e->population.as<float>(), pop, H, P, &ro, stream, &le)) return 1;
         } else if (le.ok()) {
-            le.note(rollout_impl(e, e->population.as<float>(), nullptr, (int32_t)npop, H, P, &ro, e->values.as<float>(), stream));
+            le.note(obj.evaluate(e, e->population.as<float>(), (int32_t)npop, H, P, &ro, e->values.as<float>(), stream));
         }
         if (le.ok()) le.note(update());
         if (!sharded && !le.ok()) break;
@@ -1463,30 +1525,31 @@ int hipets_plan_icem(hipets_engine* e, const hipets_icem_params* p, const float*
 int hipets_plan_icem_batched(hipets_engine* e, const hipets_icem_params* p, int32_t n_env, const float* x0, const float* lower,
                              const float* upper, float* elite, int32_t has_elite, const int32_t* keep_idx, const float* s0, int32_t P,
                              uint64_t seed, uint64_t plan_id, float* out, void* stream) {
-    return plan_icem_impl(e, p, n_env, x0, lower, upper, elite, has_elite, keep_idx, s0, P, seed, plan_id, out, stream, false);
+    return plan_icem_impl(e, p, n_env, x0, lower, upper, elite, has_elite, keep_idx, ensemble_objective(s0), P, seed, plan_id, out, stream, false);
 }
 
 int hipets_plan_icem_sharded(hipets_engine* e, const hipets_icem_params* p, const float* x0, const float* lower, const float* upper,
                              float* elite, int32_t has_elite, const int32_t* keep_idx, const float* s0, int32_t P, uint64_t seed,
                              uint64_t plan_id, float* out, void* stream) {
     if (e && !e->comm) return fail("no communicator (call hipets_comm_init)");
-    return plan_icem_impl(e, p, 1, x0, lower, upper, elite, has_elite, keep_idx, s0, P, seed, plan_id, out, stream, true);
+    return plan_icem_impl(e, p, 1, x0, lower, upper, elite, has_elite, keep_idx, ensemble_objective(s0), P, seed, plan_id, out, stream, true);
 }
 
 }  // extern "C"
 
 namespace {
 int plan_icem_impl(hipets_engine* e, const hipets_icem_params* p, int32_t n_env, const float* x0, const float* lower, const float* upper,
-                   float* elite, int32_t has_elite, const int32_t* keep_idx, const float* s0, int32_t P, uint64_t seed, uint64_t plan_id,
+                   float* elite, int32_t has_elite, const int32_t* keep_idx, const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id,
                    float* out, void* stream, const bool sharded) {
-    if (!e || !e->has_model) return fail("engine has no model (call hipets_set_model)");
-    if (!p || !x0 || !lower || !upper || !elite || !s0 || !out) return fail("null argument");
-    if (p->act_dim != e->md.act_dim) return fail("act_dim %d != model act_dim %d", p->act_dim, e->md.act_dim);
+    if (!obj.has_model(e)) return obj.no_model();
+    if (!p || !x0 || !lower || !upper || !elite || !obj.has_start() || !out) return fail("null argument");
+    if (obj.check_act_dim(e, p->act_dim)) return 1;
     if (p->horizon < 2 || p->horizon > kMaxHorizon) return fail("iCEM horizon %d outside [2, %d]", p->horizon, kMaxHorizon);
     const int K = p->elite_num, keep = p->keep_elite_size, iters = p->num_iterations, H = p->horizon, A = p->act_dim;
     if (K < 1 || keep < 0 || keep > K) return fail("elite_num %d / keep_elite_size %d invalid", K, keep);
     if (p->population_size < 1 || iters < 0 || !(p->population_decay_factor > 0.0)) return fail("bad iCEM parameters");
     if (n_env < 1 || n_env > 4096) return fail("n_env %d outside [1, 4096]", n_env);
+    if (obj.planet && P < 1) return fail("bad pop/horizon/particles");
     // population sizes (:419-431) and the rows every iteration evaluates are known up front: size the workspace for the largest, and
     // (sharded) refuse on EVERY rank, before the first collective, what one rank's shard of some iteration could not take
     std::vector<int> sizes(iters), rows_of(iters);
@@ -1511,7 +1574,7 @@ int plan_icem_impl(hipets_engine* e, const hipets_icem_params* p, int32_t n_env,
     if (e->mu.ensure(ne * nd * 4) || e->disp.ensure(ne * nd * 4) || e->best_solution.ensure(ne * nd * 4) || e->best_value.ensure(ne * 4 + 16) ||
         e->population.ensure(ne * max_rows * nd * 4) || e->values.ensure(ne * max_rows * 4) ||
         e->kept.ensure(ne * std::max(keep, 1) * nd * 4) || e->elite_idx.ensure(ne * K * 4) || e->keep_idx.ensure(ne * std::max(keep, 1) * 4) ||
-        e->s0.ensure(ne * e->md.obs_dim * 4))
+        (!obj.planet && e->s0.ensure(ne * e->md.obs_dim * 4)))
         return 1;
     if (sharded && (e->shard_values.ensure((size_t)max_width * 4) || e->gathered.ensure((size_t)world * max_width * 4))) return 1;
     hipets_cem_params cp{};
@@ -1536,7 +1599,8 @@ int plan_icem_impl(hipets_engine* e, const hipets_icem_params* p, int32_t n_env,
                            e->mu.as<float>(), e->disp.as<float>(), e->best_value.as<float>());
         HCHECK(hipGetLastError());
         HCHECK(hipMemsetAsync(e->best_solution.p, 0, ne * nd * 4, st));
-        return stage_h2d(e, e->s0.p, s0, ne * e->md.obs_dim * 4, st);  // the observations are the same for every iteration: staged once
+        // the observations are the same for every iteration: staged once (a PlaNet objective reads its DEVICE start states in place)
+        return obj.planet ? 0 : stage_h2d(e, e->s0.p, obj.s0, ne * e->md.obs_dim * 4, st);
     };
     le.note(prologue());
     if (!sharded && !le.ok()) return le.report();
@@ -1605,7 +1669,7 @@ int plan_icem_impl(hipets_engine* e, const hipets_icem_params* p, int32_t n_env,
         if (sharded) {
             if (sharded_evaluate(e, popbuf, rows, H, P, &ro, stream, &le)) return 1;
         } else if (le.ok()) {
-            le.note(rollout_impl(e, popbuf, nullptr, n_env * rows, H, P, &ro, nullptr, stream));  // s0 staged above; returns: refit (CemDev::totals)
+            le.note(obj.evaluate(e, popbuf, n_env * rows, H, P, &ro, nullptr, stream));  // s0 staged above; returns: refit (CemDev::totals)
         }
         if (le.ok()) le.note(refit());
         if (!sharded && !le.ok()) break;
@@ -1701,15 +1765,20 @@ int hipets_planet_set_model(hipets_engine* e, const hipets_planet_desc* d, void*
 }  // extern "C"
 
 namespace {
-// hipets_planet_rollout; returns == nullptr: the caller reduces e->totals over the particles itself (hipets_plan_planet_cem: inside the
-// refit kernel, CemDev::totals)
+// hipets_planet_rollout; returns == nullptr: the caller reduces e->totals over the particles itself (the CEM / iCEM plans: inside the
+// refit kernel, CemDev::totals).  o->n_env > 1: pop is n_env groups of pop / n_env candidates, group g starts from latent0[g] / belief0[g].
 int planet_rollout_impl(hipets_engine* e, const float* actions, const float* latent0, const float* belief0, int32_t pop, int32_t H,
                         int32_t P, const hipets_planet_opts* o, float* returns, hipStream_t st) {
+    const int n_env = std::max(o->n_env, 1);
+    if (o->n_env < 0 || n_env > 4096) return fail("n_env %d outside [0, 4096]", o->n_env);
+    if (pop % n_env) return fail("PlaNet rollout: population %d is not divisible by n_env %d", pop, n_env);
     const long long B = (long long)pop * P;
     if (B > 0x7FFFFFFF / std::max(e->pd.belief, 16)) return fail("batch too large");
     if (e->totals.ensure((size_t)B * 4)) return 1;
     PlanetArgs ra{};
     ra.pop = pop; ra.P = P; ra.H = H; ra.B = (int)B;
+    ra.n_env = n_env;
+    ra.rows_env = pop / n_env * P;
     ra.actions = actions;
     ra.latent0 = latent0;
     ra.belief0 = belief0;
@@ -1750,49 +1819,29 @@ int hipets_planet_rollout(hipets_engine* e, const float* actions, const float* l
 int hipets_plan_planet_cem(hipets_engine* e, const hipets_cem_params* p, const float* x0, const float* lower, const float* upper,
                            const float* latent0, const float* belief0, int32_t P, uint64_t seed, uint64_t plan_id, float* out,
                            void* stream) {
-    if (!e || !e->has_planet) return fail("engine has no PlaNet model (call hipets_planet_set_model)");
-    if (check_cem(p)) return 1;
-    if (!x0 || !lower || !upper || !latent0 || !belief0 || !out) return fail("null argument");
-    if (p->act_dim != e->pd.action) return fail("act_dim %d != model action_size %d", p->act_dim, e->pd.action);
-    if (P < 1) return fail("bad pop/horizon/particles");
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HCHECK(hipSetDevice(e->device));
-    ENTER_STREAM(e, st);
-    const CemDev c = make_cem(p, 1);
-    const size_t nd = (size_t)c.D;
-    if (e->mu.ensure(nd * 4) || e->disp.ensure(nd * 4) || e->best_solution.ensure(nd * 4) || e->best_value.ensure(16) ||
-        e->population.ensure((size_t)c.pop * nd * 4) || e->values.ensure((size_t)c.pop * 4))
-        return 1;
-    hipLaunchKernelGGL(cem_init_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, c, x0, lower, upper, e->mu.as<float>(),
-                       e->disp.as<float>(), e->best_value.as<float>());
-    HCHECK(hipGetLastError());
-    HCHECK(hipMemsetAsync(e->best_solution.p, 0, nd * 4, st));
-    hipets_planet_opts po{};
-    po.seed = seed;
-    int n2 = 1;
-    while (n2 < c.pop) n2 <<= 1;
-    for (int i = 0; i < p->num_iterations; ++i) {
-        const uint64_t sid = plan_id * (uint64_t)p->num_iterations + (uint64_t)i;
-        const long long n = (long long)c.pop * c.D;
-        hipLaunchKernelGGL(cem_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c, e->mu.as<float>(), e->disp.as<float>(),
-                           lower, upper, (const float*)nullptr, (unsigned long long)seed, (unsigned long long)sid, e->population.as<float>());
-        HCHECK(hipGetLastError());
-        po.stream_id = sid;
-        // (the particle means of the returns are formed inside the refit kernel -- the same sequential sum and division as
-        // particle_mean_kernel, so the same bits -- instead of a launch of its own in between: round 6)
-        if (planet_rollout_impl(e, e->population.as<float>(), latent0, belief0, c.pop, c.H, P, &po, nullptr, st)) return 1;
-        int* eidx = (e->has_trace && e->trace.elite_idx) ? e->trace.elite_idx + (size_t)i * c.K : nullptr;
-        CemDev cr = c;
-        cr.totals = e->totals.as<float>();
-        cr.P = P;
-        hipLaunchKernelGGL(cem_refit_kernel, dim3(refit_blocks(c.D), 1), dim3(kRefitThreads), (size_t)n2 * 8 + kRefitScratchBytes, st, cr, e->values.as<float>(),
-                           e->population.as<float>(), e->mu.as<float>(), e->disp.as<float>(), e->best_value.as<float>(),
-                           e->best_solution.as<float>(), eidx);
-        HCHECK(hipGetLastError());
-        if (trace_iter(e, i, c.pop, nd, e->population.as<float>(), e->values.as<float>(), e->mu.as<float>(), e->disp.as<float>(), st)) return 1;
-    }
-    HCHECK(hipMemcpyAsync(out, p->return_mean_elites ? e->mu.p : e->best_solution.p, nd * 4, hipMemcpyDeviceToDevice, st));
-    return 0;
+    return plan_cem_impl(e, p, 1, x0, lower, upper, planet_objective(latent0, belief0), P, seed, plan_id, out, stream);
+}
+
+// Batched PlaNet plans: the ensemble's batched drivers with the PlaNet objective (trajectory_opt.py:142-188, 238-311, 391-487 per
+// environment over planet.py:531-581); never sharded, so an engine's communicator stays out of them
+int hipets_plan_planet_cem_batched(hipets_engine* e, const hipets_cem_params* p, int32_t n_env, const float* x0, const float* lower,
+                                   const float* upper, const float* latent0, const float* belief0, int32_t P, uint64_t seed,
+                                   uint64_t plan_id, float* out, void* stream) {
+    return plan_cem_impl(e, p, n_env, x0, lower, upper, planet_objective(latent0, belief0), P, seed, plan_id, out, stream);
+}
+
+int hipets_plan_planet_mppi_batched(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t num_iterations, double gamma, double beta,
+                                    int32_t n_env, float* mean, const float* lower, const float* upper, const float* latent0,
+                                    const float* belief0, int32_t P, uint64_t seed, uint64_t plan_id, void* stream) {
+    return plan_mppi_impl(e, pop, H, A, num_iterations, gamma, beta, n_env, mean, lower, upper, planet_objective(latent0, belief0), P, seed,
+                          plan_id, stream, false);
+}
+
+int hipets_plan_planet_icem_batched(hipets_engine* e, const hipets_icem_params* p, int32_t n_env, const float* x0, const float* lower,
+                                    const float* upper, float* elite, int32_t has_elite, const int32_t* keep_idx, const float* latent0,
+                                    const float* belief0, int32_t P, uint64_t seed, uint64_t plan_id, float* out, void* stream) {
+    return plan_icem_impl(e, p, n_env, x0, lower, upper, elite, has_elite, keep_idx, planet_objective(latent0, belief0), P, seed, plan_id,
+                          out, stream, false);
 }
 
 int hipets_comm_unique_id(void* id_out) {

@@ -1,7 +1,8 @@
 // planet.hpp -- latent-space rollouts of a PlaNet model as ONE kernel launch.
 //
 //   ModelEnv.evaluate_action_sequences            mbrl/models/model_env.py:145-191
-//    └ PlaNetModel.reset                          mbrl/models/planet.py:656-672  (saved posterior sample / belief, tiled)
+//    └ PlaNetModel.reset                          mbrl/models/planet.py:656-672  (saved posterior sample / belief, tiled;
+//                                                 batched: one per environment, rows_env consecutive rows each)
 //    └ PlaNetModel.sample                         mbrl/models/planet.py:531-581
 //       └ BeliefModel.forward                     :83-101   Linear + ReLU, GRUCell
 //       └ prior_transition_model + MeanStdCat     :229-234, :104-115
@@ -57,12 +58,15 @@ __global__ __launch_bounds__(kThreads) void planet_rollout_kernel(const PlanetDe
         tot[tid] = 0.f;
     }
     // recurrent state E = [belief | latent] and the latent half of A, in GEMM column order; padding columns are zeroed
-    // once (their weights are zero, but 0 * garbage could be NaN) and never written again
+    // once (their weights are zero, but 0 * garbage could be NaN) and never written again.  Each row starts from its own
+    // environment's state (planet.py:669-672 per environment); a tile may straddle two environments, rows past B take environment 0's
     for (int i = tid; i < kTile * pd.widE; i += kThreads) {
         const int s = i / pd.widE, c = i % pd.widE;
+        const int rid = blockIdx.x * kTile + s;
+        const int g = rid < ra.B ? rid / ra.rows_env : 0;
         float v = 0.f;
-        if (c < pd.belief) v = ra.belief0[c];
-        else if (c < pd.belief + pd.latent) v = ra.latent0[c - pd.belief];
+        if (c < pd.belief) v = ra.belief0[(size_t)g * pd.belief + c];
+        else if (c < pd.belief + pd.latent) v = ra.latent0[(size_t)g * pd.latent + (c - pd.belief)];
         rows[s * ld + pd.segE + lds_col(c)] = v;
     }
     __syncthreads();

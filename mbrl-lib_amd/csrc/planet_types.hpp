@@ -31,9 +31,10 @@ struct PlanetDev {
 
 struct PlanetArgs {
     int pop, P, H, B;
+    int n_env, rows_env;   // batched rollouts: row rid starts from environment rid / rows_env (rows_env = pop / n_env * P; one: B)
     const float* actions;  // [pop,H,A]
-    const float* latent0;  // DEVICE [latent]
-    const float* belief0;  // DEVICE [belief]
+    const float* latent0;  // DEVICE [n_env, latent]
+    const float* belief0;  // DEVICE [n_env, belief]
     float* totals;         // [B]
     const float* eps;      // [H,B,latent] or null
     int use_philox;

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # HIPETS_LIB selects another build of the SAME library (kernel-variant experiments under profiles/); there is no fallback
 LIB_PATH = os.environ.get("HIPETS_LIB") or os.path.join(_HERE, "libhipets.so")
 
-ABI_VERSION = 6
+ABI_VERSION = 7
 MAX_LAYERS = 8
 
 ACT = {"relu": 0, "silu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4}
@@ -93,7 +93,8 @@ class PlanetDesc(C.Structure):
 
 class PlanetOpts(C.Structure):
     _fields_ = [("eps", C.c_void_p), ("seed", C.c_uint64), ("stream_id", C.c_uint64), ("no_sample", C.c_int32),
-                ("trace_latent", C.c_void_p), ("trace_belief", C.c_void_p), ("trace_rewards", C.c_void_p), ("phase_cycles", C.c_void_p)]
+                ("trace_latent", C.c_void_p), ("trace_belief", C.c_void_p), ("trace_rewards", C.c_void_p), ("phase_cycles", C.c_void_p),
+                ("n_env", C.c_int32)]
 
 
 # every symbol include/hipets.h declares: name -> (restype, argtypes)
@@ -147,6 +148,12 @@ SYMBOLS = {
     "hipets_planet_set_model": (C.c_int, [_P, C.POINTER(PlanetDesc), _P]),
     "hipets_planet_rollout": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlanetOpts), _P, _P]),
     "hipets_plan_planet_cem": (C.c_int, [_P, C.POINTER(CemParams), _P, _P, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64, _P, _P]),
+    "hipets_plan_planet_cem_batched": (C.c_int, [_P, C.POINTER(CemParams), C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64,
+                                                 _P, _P]),
+    "hipets_plan_planet_mppi_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _P, _P,
+                                                  _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64, _P]),
+    "hipets_plan_planet_icem_batched": (C.c_int, [_P, C.POINTER(IcemParams), C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,
+                                                  C.c_uint64, C.c_uint64, _P, _P]),
     "hipets_timing_enable": (C.c_int, [_P, C.c_int32]),
     "hipets_timing_read": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int32]),
 }

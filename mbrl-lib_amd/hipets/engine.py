@@ -649,9 +649,11 @@ class Engine:
                        eps: Optional[torch.Tensor] = None, sample: bool = True, seed: int = 0, stream_id: int = 0,
                        trace_latent: Optional[torch.Tensor] = None, trace_belief: Optional[torch.Tensor] = None,
                        trace_rewards: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-                       phase_cycles: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       phase_cycles: Optional[torch.Tensor] = None, n_env: int = 1) -> torch.Tensor:
         """ModelEnv.evaluate_action_sequences on the PlaNet model (model_env.py:145-191): actions [pop, H, A]; latent0 /
-        belief0 = the saved posterior sample / belief ([latent] / [belief], any leading 1s) on the device."""
+        belief0 = the saved posterior sample / belief ([latent] / [belief], any leading 1s) on the device.  ``n_env > 1``: the
+        pop candidates are n_env groups of pop / n_env, group g starts from latent0[g] / belief0[g] ([n_env, latent] /
+        [n_env, belief]); eps and the traces stay indexed by the launch-global row."""
         spec = getattr(self, "planet_spec", None)
         if spec is None:
             raise HipetsError("Engine.planet_set_model() has not been called")
@@ -662,12 +664,13 @@ class Engine:
         pop, H, A = actions.shape
         if A != spec.action_size:
             raise ValueError(f"action dim {A} != model action_size {spec.action_size}")
-        _check_dev(latent0, torch.float32, dev, "latent0", numel=spec.latent_size)
-        _check_dev(belief0, torch.float32, dev, "belief0", numel=spec.belief_size)
+        _check_dev(latent0, torch.float32, dev, "latent0", numel=n_env * spec.latent_size)
+        _check_dev(belief0, torch.float32, dev, "belief0", numel=n_env * spec.belief_size)
         B = pop * num_particles
         o = _lib.PlanetOpts()
         o.seed, o.stream_id = int(seed) & (2**64 - 1), int(stream_id) & (2**64 - 1)
         o.no_sample = int(not sample)
+        o.n_env = int(n_env)
         if eps is not None:
             _check_dev(eps, torch.float32, dev, "eps", (H, B, spec.latent_size))
             o.eps = _ptr(eps)
@@ -688,24 +691,68 @@ class Engine:
                                                        C.byref(o), _ptr(out), _stream(dev)))
         return out
 
-    def plan_planet_cem(self, p: CemParams, x0, lower, upper, latent0: torch.Tensor, belief0: torch.Tensor, num_particles: int,
-                        seed: int = 0, plan_id: int = 0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """Whole CEM plan over the PlaNet latent model on the device (hipets_plan_planet_cem)."""
+    def _planet_plan_args(self, lower, upper, latent0, belief0, H: int, A: int, n_env: int):
         spec = getattr(self, "planet_spec", None)
         if spec is None:
             raise HipetsError("Engine.planet_set_model() has not been called")
         dev = self.device
-        shp = (p.horizon, p.act_dim)
-        for n_, t in (("x0", x0), ("lower", lower), ("upper", upper)):
-            _check_dev(t, torch.float32, dev, n_, shp)
-        _check_dev(latent0, torch.float32, dev, "latent0", numel=spec.latent_size)
-        _check_dev(belief0, torch.float32, dev, "belief0", numel=spec.belief_size)
+        for n_, t in (("lower", lower), ("upper", upper)):
+            _check_dev(t, torch.float32, dev, n_, (H, A))
+        _check_dev(latent0, torch.float32, dev, "latent0", numel=n_env * spec.latent_size)
+        _check_dev(belief0, torch.float32, dev, "belief0", numel=n_env * spec.belief_size)
+        return dev
+
+    def plan_planet_cem(self, p: CemParams, x0, lower, upper, latent0: torch.Tensor, belief0: torch.Tensor, num_particles: int,
+                        seed: int = 0, plan_id: int = 0, out: Optional[torch.Tensor] = None, n_env: int = 1) -> torch.Tensor:
+        """Whole CEM plan over the PlaNet latent model on the device.  x0 [H, A] with n_env = 1: hipets_plan_planet_cem; else
+        hipets_plan_planet_cem_batched with x0 / out [n_env, H, A], latent0 [n_env, latent], belief0 [n_env, belief] and
+        p.population_size per environment."""
+        dev = self._planet_plan_args(lower, upper, latent0, belief0, p.horizon, p.act_dim, n_env)
+        _check_dev(x0, torch.float32, dev, "x0", numel=n_env * p.horizon * p.act_dim)
         if out is None:
-            out = torch.empty(shp, dtype=torch.float32, device=dev)
+            out = torch.empty(tuple(x0.shape), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(self._lib.hipets_plan_planet_cem(self._h, C.byref(p), _ptr(x0), _ptr(lower), _ptr(upper), _ptr(latent0), _ptr(belief0),
-                                                        num_particles, int(seed) & (2**64 - 1), int(plan_id) & (2**64 - 1), _ptr(out),
-                                                        _stream(dev)))
+            if n_env == 1 and x0.ndim == 2:
+                _lib.check(self._lib.hipets_plan_planet_cem(self._h, C.byref(p), _ptr(x0), _ptr(lower), _ptr(upper), _ptr(latent0), _ptr(belief0),
+                                                            num_particles, int(seed) & (2**64 - 1), int(plan_id) & (2**64 - 1), _ptr(out),
+                                                            _stream(dev)))
+            else:
+                _lib.check(self._lib.hipets_plan_planet_cem_batched(self._h, C.byref(p), int(n_env), _ptr(x0), _ptr(lower), _ptr(upper),
+                                                                    _ptr(latent0), _ptr(belief0), num_particles, int(seed) & (2**64 - 1),
+                                                                    int(plan_id) & (2**64 - 1), _ptr(out), _stream(dev)))
+        return out
+
+    def plan_planet_mppi(self, pop: int, H: int, A: int, num_iterations: int, gamma: float, beta: float, mean: torch.Tensor, lower, upper,
+                         latent0: torch.Tensor, belief0: torch.Tensor, num_particles: int, seed: int = 0, plan_id: int = 0,
+                         n_env: int = 1) -> torch.Tensor:
+        """Whole MPPI plan over the PlaNet latent model (hipets_plan_planet_mppi_batched): ``mean`` [n_env, H, A] is the persistent
+        mean of every environment, shifted and refined IN PLACE; latent0 [n_env, latent], belief0 [n_env, belief]."""
+        dev = self._planet_plan_args(lower, upper, latent0, belief0, H, A, n_env)
+        _check_dev(mean, torch.float32, dev, "mean", numel=n_env * H * A)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.hipets_plan_planet_mppi_batched(self._h, pop, H, A, num_iterations, float(gamma), float(beta), int(n_env),
+                                                                 _ptr(mean), _ptr(lower), _ptr(upper), _ptr(latent0), _ptr(belief0),
+                                                                 num_particles, int(seed) & (2**64 - 1), int(plan_id) & (2**64 - 1),
+                                                                 _stream(dev)))
+        return mean
+
+    def plan_planet_icem(self, p: "_lib.IcemParams", x0, lower, upper, elite: torch.Tensor, has_elite: bool, latent0: torch.Tensor,
+                         belief0: torch.Tensor, num_particles: int, seed: int = 0, plan_id: int = 0, keep_idx: Optional[torch.Tensor] = None,
+                         out: Optional[torch.Tensor] = None, n_env: int = 1) -> torch.Tensor:
+        """Whole iCEM plan over the PlaNet latent model (hipets_plan_planet_icem_batched); arguments as :meth:`plan_icem` with
+        latent0 [n_env, latent] / belief0 [n_env, belief] in place of s0."""
+        dev = self._planet_plan_args(lower, upper, latent0, belief0, p.horizon, p.act_dim, n_env)
+        _check_dev(x0, torch.float32, dev, "x0", numel=n_env * p.horizon * p.act_dim)
+        _check_dev(elite, torch.float32, dev, "elite", numel=n_env * p.elite_num * p.horizon * p.act_dim)
+        if keep_idx is not None:
+            _check_dev(keep_idx, torch.int32, dev, "keep_idx", numel=p.num_iterations * n_env * p.keep_elite_size)
+        if out is None:
+            out = torch.empty(tuple(x0.shape), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.hipets_plan_planet_icem_batched(self._h, C.byref(p), int(n_env), _ptr(x0), _ptr(lower), _ptr(upper), _ptr(elite),
+                                                                 int(bool(has_elite)), _ptr(keep_idx) if keep_idx is not None else None,
+                                                                 _ptr(latent0), _ptr(belief0), num_particles, int(seed) & (2**64 - 1),
+                                                                 int(plan_id) & (2**64 - 1), _ptr(out), _stream(dev)))
         return out
 
     # ---- instrumentation ---------------------------------------------------------------------------

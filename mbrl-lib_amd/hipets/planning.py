@@ -495,12 +495,22 @@ class PlaNetTrajectoryEvalFn:
             self.engine.planet_set_model(self.spec)
             self._version = planet_version(self._planet)
 
-    def prepare(self):
-        """What a call does before its rollout: re-pack changed weights, make them the engine's PlaNet model, fetch the live
-        model's saved posterior sample / belief.  Returns (latent0, belief0)."""
+    @property
+    def kernel_mode(self) -> Optional[str]:
+        """'fast' / 'device' when the rollouts draw their eps in-kernel (what the batched agents' fused plans run), None for
+        'exact'.  The single-environment optimizers do not route on it."""
+        return self.mode if self.mode in ("fast", "device") else None
+
+    def bind_model(self):
+        """Re-pack changed weights and make them the engine's PlaNet model."""
         self.refresh()
         if self.engine.planet_spec is not self.spec:
             self.engine.planet_set_model(self.spec)
+
+    def prepare(self):
+        """What a call does before its rollout: re-pack changed weights, make them the engine's PlaNet model, fetch the live
+        model's saved posterior sample / belief.  Returns (latent0, belief0)."""
+        self.bind_model()
         if self._planet is not None:  # planet.py:669-672
             if self._planet._current_posterior_sample is None or self._planet._current_belief is None:
                 raise RuntimeError("PlaNetModel has no saved posterior: call update_posterior() before planning")
@@ -1176,13 +1186,35 @@ class TrajectoryOptimizerAgent(Agent):
         return self.optimizer.optimize(_BoundObjective(self.trajectory_eval_fn, obs))
 
 
+def _planet_start_states(eval_fn, n_env: int, obs_batch, latent, belief):
+    """The start states of a batched PlaNet plan: ``latent`` [n_env, latent] / ``belief`` [n_env, belief], one posterior sample and
+    belief per environment (``PlaNetModel.update_posterior`` of each env, planet.py:600-640).  Like ``PlaNetModel.reset``
+    (planet.py:656-672), ``obs_batch`` only fixes the batch size.  Also makes the objective's weights the engine's PlaNet model."""
+    if len(obs_batch) != n_env:
+        raise ValueError(f"obs_batch holds {len(obs_batch)} observations, the agent plans for n_env = {n_env}")
+    if latent is None or belief is None:
+        raise ValueError("a PlaNet objective plans from per-environment start states: pass latent=[n_env, latent] and belief=[n_env, belief]")
+    spec, dev = eval_fn.spec, eval_fn.device
+    states = []
+    for name, t, width in (("latent", latent, spec.latent_size), ("belief", belief, spec.belief_size)):
+        t = torch.as_tensor(t)
+        if tuple(t.shape) != (n_env, width):
+            raise ValueError(f"{name} must have shape {(n_env, width)}, got {tuple(t.shape)}")
+        states.append(t.detach().to(device=dev, dtype=torch.float32).contiguous())
+    eval_fn.bind_model()
+    return states
+
+
 class BatchedCEMAgent(Agent):
     """Batched planning: one CEM plan per environment for ``n_env`` environments (vectorised envs,
     MPC for many agents) in ONE set of launches.  Same algorithm per environment as ``TrajectoryOptimizerAgent`` +
     ``CEMOptimizer`` (warm start shifted by ``replan_freq`` per environment, trajectory_opt.py:563-567); a single cfg2
     plan leaves 36 of 256 CUs idle, a batch fills the chip.  The rollouts run the objective's randomness mode: 'device' (default:
     one balanced permutation per step over the rows of ALL environments -- every row meets every member with probability 1 / M and
-    the members stay exactly balanced, as in a single reference plan) or 'fast'."""
+    the members stay exactly balanced, as in a single reference plan) or 'fast'.
+
+    With a ``PlaNetTrajectoryEvalFn`` the environments' latent start states come as keyword arguments:
+    ``plan(obs_batch, latent=[n_env, latent], belief=[n_env, belief])``; eps are drawn in-kernel (hipets_plan_planet_cem_batched)."""
 
     def __init__(self, eval_fn: HipTrajectoryEvalFn, n_env: int, action_lb: Sequence[float], action_ub: Sequence[float],
                  planning_horizon: int, num_iterations: int, elite_ratio: float, population_size: int, alpha: float,
@@ -1205,33 +1237,41 @@ class BatchedCEMAgent(Agent):
     def reset(self):
         self.previous_solution = self.initial_solution.clone()
 
-    def plan(self, obs_batch: np.ndarray, **_kwargs) -> np.ndarray:
-        obs_batch = np.asarray(obs_batch, dtype=np.float32)
-        assert obs_batch.shape[0] == self.n_env
-        self.eval_fn.refresh()
-        if self.engine.spec is not self.eval_fn.spec:
-            self.engine.set_model(self.eval_fn.spec)
-        self.eval_fn.check_batch(self._params.population_size)
-        if self.engine.plan_mode != self.eval_fn.kernel_mode:
-            self.engine.set_plan_mode(self.eval_fn.kernel_mode)
-        self.calls += 1
-        best = self.engine.plan_cem(self._params, self.previous_solution, self.lower, self.upper, obs_batch,
-                                    self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed, plan_id=self.calls,
-                                    n_env=self.n_env)
+    def plan(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
+        if isinstance(self.eval_fn, PlaNetTrajectoryEvalFn):
+            latent0, belief0 = _planet_start_states(self.eval_fn, self.n_env, obs_batch, latent, belief)
+            self.calls += 1
+            best = self.engine.plan_planet_cem(self._params, self.previous_solution, self.lower, self.upper, latent0, belief0,
+                                               self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed, plan_id=self.calls,
+                                               n_env=self.n_env)
+        else:
+            obs_batch = np.asarray(obs_batch, dtype=np.float32)
+            assert obs_batch.shape[0] == self.n_env
+            self.eval_fn.refresh()
+            if self.engine.spec is not self.eval_fn.spec:
+                self.engine.set_model(self.eval_fn.spec)
+            self.eval_fn.check_batch(self._params.population_size)
+            if self.engine.plan_mode != self.eval_fn.kernel_mode:
+                self.engine.set_plan_mode(self.eval_fn.kernel_mode)
+            self.calls += 1
+            best = self.engine.plan_cem(self._params, self.previous_solution, self.lower, self.upper, obs_batch,
+                                        self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed, plan_id=self.calls,
+                                        n_env=self.n_env)
         self.previous_solution = best.roll(-self.replan_freq, dims=1)
         self.previous_solution[:, -self.replan_freq:] = self.initial_solution[:, :1]
         self.previous_solution = self.previous_solution.contiguous()
         return best.cpu().numpy()
 
-    def act(self, obs_batch: np.ndarray, **_kwargs) -> np.ndarray:
+    def act(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
         """One action per environment, [n_env, A]."""
-        return self.plan(obs_batch)[:, 0]
+        return self.plan(obs_batch, latent=latent, belief=belief)[:, 0]
 
 
 class BatchedMPPIAgent(Agent):
     """Batched planning with MPPI: ``MPPIOptimizer.optimize`` (trajectory_opt.py:238-311) for ``n_env``
     environments in one set of launches (hipets_plan_mppi_batched).  Every environment keeps its own persistent mean,
-    shifted one step per plan like the reference's (Appendix B4-B6)."""
+    shifted one step per plan like the reference's (Appendix B4-B6).  A ``PlaNetTrajectoryEvalFn`` plans from
+    ``latent=`` / ``belief=`` start states as in :class:`BatchedCEMAgent` (hipets_plan_planet_mppi_batched)."""
 
     def __init__(self, eval_fn: HipTrajectoryEvalFn, n_env: int, action_lb: Sequence[float], action_ub: Sequence[float],
                  planning_horizon: int, num_iterations: int, population_size: int, gamma: float, sigma: float, beta: float,
@@ -1248,7 +1288,14 @@ class BatchedMPPIAgent(Agent):
         self.refinements, self.population_size, self.gamma, self.sigma, self.beta = int(num_iterations), int(population_size), gamma, sigma, beta
         self.seed, self.calls = int(seed), 0
 
-    def plan(self, obs_batch: np.ndarray, **_kwargs) -> np.ndarray:
+    def plan(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
+        if isinstance(self.eval_fn, PlaNetTrajectoryEvalFn):
+            latent0, belief0 = _planet_start_states(self.eval_fn, self.n_env, obs_batch, latent, belief)
+            self.calls += 1
+            self.engine.plan_planet_mppi(self.population_size, self.horizon, self.act_dim, self.refinements, self.gamma, self.beta, self.mean,
+                                         self.lower, self.upper, latent0, belief0, self.eval_fn.num_particles,
+                                         seed=self.seed ^ self.eval_fn.seed, plan_id=self.calls, n_env=self.n_env)
+            return self.mean.cpu().numpy()
         obs_batch = np.asarray(obs_batch, dtype=np.float32)
         assert obs_batch.shape[0] == self.n_env
         _prepare_fused(self.eval_fn, [self.population_size])
@@ -1258,14 +1305,15 @@ class BatchedMPPIAgent(Agent):
                               plan_id=self.calls, n_env=self.n_env)
         return self.mean.cpu().numpy()
 
-    def act(self, obs_batch: np.ndarray, **_kwargs) -> np.ndarray:
-        return self.plan(obs_batch)[:, 0]
+    def act(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
+        return self.plan(obs_batch, latent=latent, belief=belief)[:, 0]
 
 
 class BatchedICEMAgent(Agent):
     """Batched planning with iCEM: ``ICEMOptimizer.optimize`` (trajectory_opt.py:391-487) for ``n_env``
     environments in one set of launches (hipets_plan_icem_batched): per-environment mean / variance / persistent elites,
-    warm start shifted by ``replan_freq`` per environment (trajectory_opt.py:563-567)."""
+    warm start shifted by ``replan_freq`` per environment (trajectory_opt.py:563-567).  A ``PlaNetTrajectoryEvalFn`` plans from
+    ``latent=`` / ``belief=`` start states as in :class:`BatchedCEMAgent` (hipets_plan_planet_icem_batched)."""
 
     def __init__(self, eval_fn: HipTrajectoryEvalFn, n_env: int, action_lb: Sequence[float], action_ub: Sequence[float],
                  planning_horizon: int, num_iterations: int, elite_ratio: float, population_size: int, population_decay_factor: float,
@@ -1297,21 +1345,29 @@ class BatchedICEMAgent(Agent):
     def reset(self):
         self.previous_solution = self.initial_solution.clone()  # the elites persist, like ICEMOptimizer.elite (Appendix B6)
 
-    def plan(self, obs_batch: np.ndarray, keep_idx: Optional[torch.Tensor] = None, **_kwargs) -> np.ndarray:
-        obs_batch = np.asarray(obs_batch, dtype=np.float32)
-        assert obs_batch.shape[0] == self.n_env
-        o, iters = self._opt, self._params.num_iterations
-        sizes = []
-        for i in range(iters):
-            extra = 0
-            if self.has_elite or i > 0:
-                extra = 1 if (i == iters - 1 and i != 0) else int(o.keep_elite_size)
-            sizes.append(o._iteration_size(i) + extra)
-        _prepare_fused(self.eval_fn, sizes)
-        self.calls += 1
-        best = self.engine.plan_icem(self._params, self.previous_solution, self.lower, self.upper, self.elite, self.has_elite, obs_batch,
-                                     self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed, plan_id=self.calls, keep_idx=keep_idx,
-                                     n_env=self.n_env)
+    def plan(self, obs_batch: np.ndarray, keep_idx: Optional[torch.Tensor] = None, latent=None, belief=None, **_kwargs) -> np.ndarray:
+        if isinstance(self.eval_fn, PlaNetTrajectoryEvalFn):
+            latent0, belief0 = _planet_start_states(self.eval_fn, self.n_env, obs_batch, latent, belief)
+            self.calls += 1
+            best = self.engine.plan_planet_icem(self._params, self.previous_solution, self.lower, self.upper, self.elite, self.has_elite,
+                                                latent0, belief0, self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed,
+                                                plan_id=self.calls, keep_idx=keep_idx, n_env=self.n_env)
+        else:
+            obs_batch = np.asarray(obs_batch, dtype=np.float32)
+            assert obs_batch.shape[0] == self.n_env
+            o, iters = self._opt, self._params.num_iterations
+            sizes = []
+            for i in range(iters):
+                extra = 0
+                if self.has_elite or i > 0:
+                    extra = 1 if (i == iters - 1 and i != 0) else int(o.keep_elite_size)
+                sizes.append(o._iteration_size(i) + extra)
+            _prepare_fused(self.eval_fn, sizes)
+            self.calls += 1
+            best = self.engine.plan_icem(self._params, self.previous_solution, self.lower, self.upper, self.elite, self.has_elite, obs_batch,
+                                         self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed, plan_id=self.calls, keep_idx=keep_idx,
+                                         n_env=self.n_env)
+        iters = self._params.num_iterations
         if iters > 0:
             self.has_elite = True
         self.previous_solution = best.roll(-self.replan_freq, dims=1)
@@ -1319,8 +1375,8 @@ class BatchedICEMAgent(Agent):
         self.previous_solution = self.previous_solution.contiguous()
         return best.cpu().numpy()
 
-    def act(self, obs_batch: np.ndarray, **_kwargs) -> np.ndarray:
-        return self.plan(obs_batch)[:, 0]
+    def act(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
+        return self.plan(obs_batch, latent=latent, belief=belief)[:, 0]
 
 
 def complete_agent_cfg(env, agent_cfg):
