@@ -1060,58 +1060,109 @@ int sharded_evaluate(hipets_engine* e, const float* population, const int rows, 
 int planet_rollout_impl(hipets_engine* e, const float* actions, const float* latent0, const float* belief0, int32_t pop, int32_t H,
                         int32_t P, const hipets_planet_opts* o, float* returns, hipStream_t st);
 
-// The objective a fused plan rolls out every iteration (trajectory_opt.py's obj_fun, model_env.py:145-191): the engine's ensemble
-// from HOST observations s0 [n_env, obs_dim], staged once by the plan's prologue, or the PlaNet latent model from DEVICE start states
-// latent0 [n_env, latent] / belief0 [n_env, belief] (planet.py:656-672, one per environment; nothing to stage, no communicator).
-// The plan drivers below are shared; evaluate() is where the two differ inside the iteration loop.
+// The objective a fused plan rolls out every iteration (trajectory_opt.py's obj_fun, model_env.py:145-191), of one of three kinds:
+//   ENSEMBLE  the engine's ensemble from HOST observations s0 [n_env, obs_dim], staged once by the plan's prologue;
+//   SHARDED   the same over the engine's communicator (one environment): every rank samples all candidates, rolls out its shard and
+//             all-gathers the returns (sharded_evaluate);
+//   PLANET    the PlaNet latent model from DEVICE start states latent0 [n_env, latent] / belief0 [n_env, belief] (planet.py:656-672,
+//             one per environment; nothing to stage, no communicator).
+// The plan drivers below are shared; this is where the kinds differ.
 struct PlanObjective {
-    bool planet = false;
+    enum Kind { ENSEMBLE, SHARDED, PLANET } kind = ENSEMBLE;
     const float* s0 = nullptr;
     const float* latent0 = nullptr;
     const float* belief0 = nullptr;
 
-    bool has_model(const hipets_engine* e) const { return e && (planet ? e->has_planet : e->has_model); }
-    int no_model() const {
-        return planet ? fail("engine has no PlaNet model (call hipets_planet_set_model)") : fail("engine has no model (call hipets_set_model)");
+    bool is_planet() const { return kind == PLANET; }
+    bool is_sharded() const { return kind == SHARDED; }
+    // ranks draw independent rollout randomness (rank 0, and every local plan: `seed` itself)
+    uint64_t rollout_seed(const hipets_engine* e, uint64_t seed) const {
+        return seed + (is_sharded() ? (uint64_t)e->comm_rank : 0ull) * 0x9E3779B97F4A7C15ull;
     }
-    bool has_start() const { return planet ? (latent0 && belief0) : s0 != nullptr; }
-    int check_act_dim(const hipets_engine* e, int A) const {
-        if (planet) return A != e->pd.action ? fail("act_dim %d != model action_size %d", A, e->pd.action) : 0;
-        return A != e->md.act_dim ? fail("act_dim %d != model act_dim %d", A, e->md.act_dim) : 0;
+    // sharded: the all-gather buffers for the widest iteration (`max_rows` candidates), and (in the prologue) their zeroed padding slot
+    size_t shard_width(const hipets_engine* e, int max_rows) const { return (size_t)((max_rows + e->comm_world - 1) / e->comm_world); }
+    int reserve_shards(hipets_engine* e, int max_rows) const {
+        if (!is_sharded()) return 0;
+        const size_t width = shard_width(e, max_rows);
+        return e->shard_values.ensure(width * 4) || e->gathered.ensure((size_t)e->comm_world * width * 4);
     }
-    // `rows` candidates of ro->n_env environments (environment after environment), iteration ro->stream_id; returns == nullptr: the
-    // per-row totals stay in e->totals and the refit kernel forms the particle means (CemDev::totals)
+    int clear_padding(hipets_engine* e, int max_rows, hipStream_t st) const {
+        if (is_sharded()) HCHECK(hipMemsetAsync(e->shard_values.p, 0, shard_width(e, max_rows) * 4, st));
+        return 0;
+    }
+    // a local rollout left its per-row totals: the refit kernel forms the particle means (same sum, same bits).  A sharded plan's
+    // values come from the all-gather.
+    void refit_from_totals(hipets_engine* e, CemDev* c, int P) const {
+        if (is_sharded()) return;
+        c->totals = e->totals.as<float>();
+        c->P = P;
+    }
+    // `rows` candidates of ro->n_env environments (environment after environment), iteration ro->stream_id, into `returns` (nullptr:
+    // the per-row totals stay in e->totals for the refit; a sharded objective always fills e->values).  Returns non-zero only when a
+    // collective failed; a local failure is noted in `le` (skipping the rollout), and a sharded objective still joins the all-gather.
     int evaluate(hipets_engine* e, const float* population, int rows, int H, int P, const hipets_rollout_opts* ro, float* returns,
-                 void* stream) const {
-        if (!planet) return rollout_impl(e, population, nullptr, rows, H, P, ro, returns, stream);
+                 void* stream, LocalErr& le) const {
+        if (is_sharded()) return sharded_evaluate(e, population, rows, H, P, ro, stream, &le);
+        if (!le.ok()) return 0;
+        if (!is_planet()) {
+            le.note(rollout_impl(e, population, nullptr, rows, H, P, ro, returns, stream));
+            return 0;
+        }
         hipets_planet_opts po{};
         po.seed = ro->seed;
         po.stream_id = ro->stream_id;
         po.n_env = ro->n_env;
-        return planet_rollout_impl(e, population, latent0, belief0, rows, H, P, &po, returns, reinterpret_cast<hipStream_t>(stream));
+        le.note(planet_rollout_impl(e, population, latent0, belief0, rows, H, P, &po, returns, reinterpret_cast<hipStream_t>(stream)));
+        return 0;
     }
 };
-PlanObjective ensemble_objective(const float* s0) {
+PlanObjective ensemble_objective(const float* s0, PlanObjective::Kind kind = PlanObjective::ENSEMBLE) {
     PlanObjective o;
+    o.kind = kind;
     o.s0 = s0;
     return o;
 }
 PlanObjective planet_objective(const float* latent0, const float* belief0) {
     PlanObjective o;
-    o.planet = true;
+    o.kind = PlanObjective::PLANET;
     o.latent0 = latent0;
     o.belief0 = belief0;
     return o;
+}
+
+// The front checks every fused plan shares: the objective's model, the driver's own pointers (`args`) and the start state, act_dim
+// against the model, n_env, and a PlaNet objective's particles
+int check_plan(const hipets_engine* e, const PlanObjective& obj, bool args, int A, int n_env, int P) {
+    const bool planet = obj.is_planet();
+    if (planet && !(e && e->has_planet)) return fail("engine has no PlaNet model (call hipets_planet_set_model)");
+    if (!planet && !(e && e->has_model)) return fail("engine has no model (call hipets_set_model)");
+    if (!args || (planet ? !(obj.latent0 && obj.belief0) : !obj.s0)) return fail("null argument");
+    if (planet && A != e->pd.action) return fail("act_dim %d != model action_size %d", A, e->pd.action);
+    if (!planet && A != e->md.act_dim) return fail("act_dim %d != model act_dim %d", A, e->md.act_dim);
+    if (n_env < 1 || n_env > 4096) return fail("n_env %d outside [1, 4096]", n_env);
+    if (planet && P < 1) return fail("bad pop/horizon/particles");
+    return 0;
+}
+
+// CEM refit (cem.hpp): one row of workgroups per environment; the elite selection sorts the next power of two >= c.pop values in LDS
+int launch_cem_refit(const CemDev& c, float* values, const float* population, float* mu, float* disp, float* best_value, float* best_solution,
+                     int* elite_idx, hipStream_t st) {
+    int n2 = 1;
+    while (n2 < c.pop) n2 <<= 1;
+    hipLaunchKernelGGL(cem_refit_kernel, dim3(refit_blocks(c.D), c.n_env), dim3(kRefitThreads), (size_t)n2 * 8 + kRefitScratchBytes, st, c, values,
+                       population, mu, disp, best_value, best_solution, elite_idx);
+    HCHECK(hipGetLastError());
+    return 0;
 }
 
 int plan_cem_impl(hipets_engine* e, const hipets_cem_params* p, int32_t n_env, const float* x0, const float* lower, const float* upper,
                   const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id, float* out, void* stream);
 int plan_mppi_impl(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t num_iterations, double gamma, double beta, int32_t n_env,
                    float* mean, const float* lower, const float* upper, const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id,
-                   void* stream, bool sharded);
+                   void* stream);
 int plan_icem_impl(hipets_engine* e, const hipets_icem_params* p, int32_t n_env, const float* x0, const float* lower, const float* upper,
                    float* elite, int32_t has_elite, const int32_t* keep_idx, const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id,
-                   float* out, void* stream, bool sharded);
+                   float* out, void* stream);
 
 }  // namespace
 
@@ -1284,13 +1335,7 @@ int hipets_cem_refit(hipets_engine* e, const hipets_cem_params* p, float* values
     if (check_cem(p)) return 1;
     if (!values || !population || !mu || !dispersion || !best_value || !best_solution) return fail("null argument");
     HCHECK(hipSetDevice(e->device));
-    const CemDev c = make_cem(p);
-    int n2 = 1;
-    while (n2 < c.pop) n2 <<= 1;
-    hipLaunchKernelGGL(cem_refit_kernel, dim3(refit_blocks(c.D), 1), dim3(kRefitThreads), (size_t)n2 * 8 + kRefitScratchBytes, reinterpret_cast<hipStream_t>(stream), c,
-                       values, population, mu, dispersion, best_value, best_solution, elite_idx);
-    HCHECK(hipGetLastError());
-    return 0;
+    return launch_cem_refit(make_cem(p), values, population, mu, dispersion, best_value, best_solution, elite_idx, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hipets_cem_refit_elites(hipets_engine* e, const hipets_cem_params* p, float* values, const float* population, const int32_t* elites,
@@ -1301,12 +1346,7 @@ int hipets_cem_refit_elites(hipets_engine* e, const hipets_cem_params* p, float*
     HCHECK(hipSetDevice(e->device));
     CemDev c = make_cem(p);
     c.elite_in = elites;
-    int n2 = 1;
-    while (n2 < c.pop) n2 <<= 1;
-    hipLaunchKernelGGL(cem_refit_kernel, dim3(refit_blocks(c.D), 1), dim3(kRefitThreads), (size_t)n2 * 8 + kRefitScratchBytes, reinterpret_cast<hipStream_t>(stream), c,
-                       values, population, mu, dispersion, best_value, best_solution, (int*)nullptr);
-    HCHECK(hipGetLastError());
-    return 0;
+    return launch_cem_refit(c, values, population, mu, dispersion, best_value, best_solution, nullptr, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hipets_gather_rows(hipets_engine* e, int32_t rows, int32_t dim, const float* src, const int32_t* index, float* dst,
@@ -1378,52 +1418,56 @@ int hipets_plan_cem_batched(hipets_engine* e, const hipets_cem_params* p, int32_
 namespace {
 int plan_cem_impl(hipets_engine* e, const hipets_cem_params* p, int32_t n_env, const float* x0, const float* lower, const float* upper,
                   const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id, float* out, void* stream) {
-    if (!obj.has_model(e)) return obj.no_model();
-    if (check_cem(p)) return 1;
-    if (!x0 || !lower || !upper || !obj.has_start() || !out) return fail("null argument");
-    if (obj.check_act_dim(e, p->act_dim)) return 1;
-    if (n_env < 1 || n_env > 4096) return fail("n_env %d outside [1, 4096]", n_env);
-    if (obj.planet && P < 1) return fail("bad pop/horizon/particles");
+    if (check_cem(p) || check_plan(e, obj, x0 && lower && upper && out, p->act_dim, n_env, P)) return 1;
+    if (obj.is_sharded() && check_shards(e, p->population_size, P)) return 1;  // identical on every rank, before any collective
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
     const CemDev c = make_cem(p, n_env);
     const size_t nd = (size_t)n_env * c.D, npop = (size_t)n_env * c.pop;
     if (e->mu.ensure(nd * 4) || e->disp.ensure(nd * 4) || e->best_solution.ensure(nd * 4) || e->best_value.ensure((size_t)n_env * 4 + 16) ||
-        e->population.ensure(npop * c.D * 4) || e->values.ensure(npop * 4))
+        e->population.ensure(npop * c.D * 4) || e->values.ensure(npop * 4) || obj.reserve_shards(e, c.pop))
         return 1;
-    hipLaunchKernelGGL(cem_init_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, c, x0, lower, upper, e->mu.as<float>(),
-                       e->disp.as<float>(), e->best_value.as<float>());
-    HCHECK(hipGetLastError());
-    HCHECK(hipMemsetAsync(e->best_solution.p, 0, nd * 4, st));
+    LocalErr le;  // (only a sharded plan carries on after a local failure: its peers wait in the collectives)
     hipets_rollout_opts ro{};
     ro.mode = e->plan_mode;
-    ro.seed = seed;
+    ro.seed = obj.rollout_seed(e, seed);
     ro.n_env = n_env;
-    int n2 = 1;
-    while (n2 < c.pop) n2 <<= 1;
-    if (!obj.planet && plan_prologue(e, obj.s0, n_env, c.H, p->num_iterations, seed, plan_id * (uint64_t)p->num_iterations, st)) return 1;
+    auto prologue = [&]() -> int {
+        if (obj.clear_padding(e, c.pop, st)) return 1;
+        hipLaunchKernelGGL(cem_init_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, c, x0, lower, upper, e->mu.as<float>(),
+                           e->disp.as<float>(), e->best_value.as<float>());
+        HCHECK(hipGetLastError());
+        HCHECK(hipMemsetAsync(e->best_solution.p, 0, nd * 4, st));
+        return obj.is_planet() ? 0 : plan_prologue(e, obj.s0, n_env, c.H, p->num_iterations, ro.seed, plan_id * (uint64_t)p->num_iterations, st);
+    };
+    le.note(prologue());
+    if (!obj.is_sharded() && !le.ok()) return le.report();
     for (int i = 0; i < p->num_iterations; ++i) {
         const uint64_t sid = plan_id * (uint64_t)p->num_iterations + (uint64_t)i;
-        const long long n = (long long)npop * c.D;
-        hipLaunchKernelGGL(cem_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c, e->mu.as<float>(), e->disp.as<float>(),
-                           lower, upper, (const float*)nullptr, (unsigned long long)seed, (unsigned long long)sid,
-                           e->population.as<float>());
-        HCHECK(hipGetLastError());
+        auto sample = [&]() -> int {  // identical on every rank of a sharded plan: same seed, same counters
+            const long long n = (long long)npop * c.D;
+            hipLaunchKernelGGL(cem_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c, e->mu.as<float>(), e->disp.as<float>(),
+                               lower, upper, (const float*)nullptr, (unsigned long long)seed, (unsigned long long)sid, e->population.as<float>());
+            HCHECK(hipGetLastError());
+            return 0;
+        };
+        auto refit = [&]() -> int {
+            int* eidx = (e->has_trace && e->trace.elite_idx) ? e->trace.elite_idx + (size_t)i * n_env * c.K : nullptr;
+            CemDev cr = c;
+            obj.refit_from_totals(e, &cr, P);  // (the particle mean of the returns, model_env.py:190-191: one launch less per iteration)
+            if (launch_cem_refit(cr, e->values.as<float>(), e->population.as<float>(), e->mu.as<float>(), e->disp.as<float>(), e->best_value.as<float>(),
+                                 e->best_solution.as<float>(), eidx, st))
+                return 1;
+            return trace_iter(e, i, (int)npop, (size_t)c.D, e->population.as<float>(), e->values.as<float>(), e->mu.as<float>(), e->disp.as<float>(), st, n_env);
+        };
+        if (le.ok()) le.note(sample());
         ro.stream_id = sid;
-        // the particle mean of the returns (model_env.py:190-191) happens inside the refit kernel: one launch less per iteration
-        if (obj.evaluate(e, e->population.as<float>(), (int32_t)npop, c.H, P, &ro, nullptr, stream)) return 1;
-        int* eidx = (e->has_trace && e->trace.elite_idx) ? e->trace.elite_idx + (size_t)i * n_env * c.K : nullptr;
-        CemDev cr = c;
-        cr.totals = e->totals.as<float>();
-        cr.P = P;
-        hipLaunchKernelGGL(cem_refit_kernel, dim3(refit_blocks(cr.D), n_env), dim3(kRefitThreads), (size_t)n2 * 8 + kRefitScratchBytes, st, cr, e->values.as<float>(),
-                           e->population.as<float>(), e->mu.as<float>(), e->disp.as<float>(), e->best_value.as<float>(),
-                           e->best_solution.as<float>(), eidx);
-        HCHECK(hipGetLastError());
-        if (trace_iter(e, i, (int)npop, (size_t)c.D, e->population.as<float>(), e->values.as<float>(), e->mu.as<float>(), e->disp.as<float>(), st, n_env))
-            return 1;
+        if (obj.evaluate(e, e->population.as<float>(), (int32_t)npop, c.H, P, &ro, nullptr, stream, le)) return 1;
+        if (le.ok()) le.note(refit());
+        if (!obj.is_sharded() && !le.ok()) break;
     }
+    if (!le.ok()) return le.report();
     HCHECK(hipMemcpyAsync(out, p->return_mean_elites ? e->mu.p : e->best_solution.p, nd * 4, hipMemcpyDeviceToDevice, st));
     return 0;
 }
@@ -1440,14 +1484,14 @@ int hipets_plan_mppi(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_
 int hipets_plan_mppi_batched(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t num_iterations, double gamma, double beta,
                              int32_t n_env, float* mean, const float* lower, const float* upper, const float* s0, int32_t P,
                              uint64_t seed, uint64_t plan_id, void* stream) {
-    return plan_mppi_impl(e, pop, H, A, num_iterations, gamma, beta, n_env, mean, lower, upper, ensemble_objective(s0), P, seed, plan_id, stream, false);
+    return plan_mppi_impl(e, pop, H, A, num_iterations, gamma, beta, n_env, mean, lower, upper, ensemble_objective(s0), P, seed, plan_id, stream);
 }
 
 int hipets_plan_mppi_sharded(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t num_iterations, double gamma, double beta,
                              float* mean, const float* lower, const float* upper, const float* s0, int32_t P, uint64_t seed,
                              uint64_t plan_id, void* stream) {
     if (e && !e->comm) return fail("no communicator (call hipets_comm_init)");
-    return plan_mppi_impl(e, pop, H, A, num_iterations, gamma, beta, 1, mean, lower, upper, ensemble_objective(s0), P, seed, plan_id, stream, true);
+    return plan_mppi_impl(e, pop, H, A, num_iterations, gamma, beta, 1, mean, lower, upper, ensemble_objective(s0, PlanObjective::SHARDED), P, seed, plan_id, stream);
 }
 
 }  // extern "C"
@@ -1455,41 +1499,34 @@ int hipets_plan_mppi_sharded(hipets_engine* e, int32_t pop, int32_t H, int32_t A
 namespace {
 int plan_mppi_impl(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t num_iterations, double gamma, double beta, int32_t n_env,
                    float* mean, const float* lower, const float* upper, const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id,
-                   void* stream, const bool sharded) {
-    if (!obj.has_model(e)) return obj.no_model();
-    if (!mean || !lower || !upper || !obj.has_start()) return fail("null argument");
+                   void* stream) {
+    if (check_plan(e, obj, mean && lower && upper, A, n_env, P)) return 1;
     if (pop < 1 || pop > 12000) return fail("population_size %d outside [1, 12000]", pop);
     if (H < 1 || num_iterations < 0) return fail("bad horizon/num_iterations");
-    if (obj.check_act_dim(e, A)) return 1;
-    if (n_env < 1 || n_env > 4096) return fail("n_env %d outside [1, 4096]", n_env);
-    if (obj.planet && P < 1) return fail("bad pop/horizon/particles");
-    if (sharded && check_shards(e, pop, P)) return 1;  // identical on every rank, before any collective
+    if (obj.is_sharded() && check_shards(e, pop, P)) return 1;  // identical on every rank, before any collective
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
     const size_t nd = (size_t)H * A, npop = (size_t)n_env * pop;
-    const int world = sharded ? e->comm_world : 1, rank = sharded ? e->comm_rank : 0;
-    const int width = (pop + world - 1) / world;
     if (e->mu.ensure(n_env * nd * 4) || e->past_action.ensure((size_t)n_env * A * 4) || e->population.ensure(npop * nd * 4) ||
-        e->values.ensure(npop * 4))
+        e->values.ensure(npop * 4) || obj.reserve_shards(e, pop))
         return 1;
-    if (sharded && (e->shard_values.ensure((size_t)width * 4) || e->gathered.ensure((size_t)world * width * 4))) return 1;
     LocalErr le;  // (only a sharded plan carries on after a local failure: its peers wait in the collectives)
     hipets_rollout_opts ro{};
     ro.mode = e->plan_mode;
-    ro.seed = seed + (uint64_t)rank * 0x9E3779B97F4A7C15ull;  // ranks draw independent rollout randomness (rank 0: as hipets_plan_mppi)
+    ro.seed = obj.rollout_seed(e, seed);
     ro.n_env = n_env;
 
     auto prologue = [&]() -> int {
-        if (sharded) HCHECK(hipMemsetAsync(e->shard_values.p, 0, (size_t)width * 4, st));  // padding slot of the shorter shards
+        if (obj.clear_padding(e, pop, st)) return 1;
         HCHECK(hipMemcpyAsync(e->mu.p, mean, n_env * nd * 4, hipMemcpyDeviceToDevice, st));
         hipLaunchKernelGGL(mppi_shift_kernel, dim3((unsigned)((n_env * nd + 255) / 256)), dim3(256), 0, st, n_env, H, A, e->mu.as<float>(), mean,
                            e->past_action.as<float>());
         HCHECK(hipGetLastError());
-        return obj.planet ? 0 : plan_prologue(e, obj.s0, n_env, H, num_iterations, ro.seed, plan_id * (uint64_t)num_iterations, st);
+        return obj.is_planet() ? 0 : plan_prologue(e, obj.s0, n_env, H, num_iterations, ro.seed, plan_id * (uint64_t)num_iterations, st);
     };
     le.note(prologue());
-    if (!sharded && !le.ok()) return le.report();
+    if (!obj.is_sharded() && !le.ok()) return le.report();
     for (int k = 0; k < num_iterations; ++k) {
         const uint64_t sid = plan_id * (uint64_t)num_iterations + (uint64_t)k;
         auto sample = [&]() -> int {
@@ -1502,13 +1539,9 @@ int plan_mppi_impl(hipets_engine* e, int32_t pop, int32_t H, int32_t A, int32_t 
         };
         if (le.ok()) le.note(sample());
         ro.stream_id = sid;
-        if (sharded) {
-            if (sharded_evaluate(e, e->population.as<float>(), pop, H, P, &ro, stream, &le)) return 1;
-        } else if (le.ok()) {
-            le.note(obj.evaluate(e, e->population.as<float>(), (int32_t)npop, H, P, &ro, e->values.as<float>(), stream));
-        }
+        if (obj.evaluate(e, e->population.as<float>(), (int32_t)npop, H, P, &ro, e->values.as<float>(), stream, le)) return 1;
         if (le.ok()) le.note(update());
-        if (!sharded && !le.ok()) break;
+        if (!obj.is_sharded() && !le.ok()) break;
     }
     return le.report();
 }
@@ -1525,14 +1558,14 @@ int hipets_plan_icem(hipets_engine* e, const hipets_icem_params* p, const float*
 int hipets_plan_icem_batched(hipets_engine* e, const hipets_icem_params* p, int32_t n_env, const float* x0, const float* lower,
                              const float* upper, float* elite, int32_t has_elite, const int32_t* keep_idx, const float* s0, int32_t P,
                              uint64_t seed, uint64_t plan_id, float* out, void* stream) {
-    return plan_icem_impl(e, p, n_env, x0, lower, upper, elite, has_elite, keep_idx, ensemble_objective(s0), P, seed, plan_id, out, stream, false);
+    return plan_icem_impl(e, p, n_env, x0, lower, upper, elite, has_elite, keep_idx, ensemble_objective(s0), P, seed, plan_id, out, stream);
 }
 
 int hipets_plan_icem_sharded(hipets_engine* e, const hipets_icem_params* p, const float* x0, const float* lower, const float* upper,
                              float* elite, int32_t has_elite, const int32_t* keep_idx, const float* s0, int32_t P, uint64_t seed,
                              uint64_t plan_id, float* out, void* stream) {
     if (e && !e->comm) return fail("no communicator (call hipets_comm_init)");
-    return plan_icem_impl(e, p, 1, x0, lower, upper, elite, has_elite, keep_idx, ensemble_objective(s0), P, seed, plan_id, out, stream, true);
+    return plan_icem_impl(e, p, 1, x0, lower, upper, elite, has_elite, keep_idx, ensemble_objective(s0, PlanObjective::SHARDED), P, seed, plan_id, out, stream);
 }
 
 }  // extern "C"
@@ -1540,16 +1573,12 @@ int hipets_plan_icem_sharded(hipets_engine* e, const hipets_icem_params* p, cons
 namespace {
 int plan_icem_impl(hipets_engine* e, const hipets_icem_params* p, int32_t n_env, const float* x0, const float* lower, const float* upper,
                    float* elite, int32_t has_elite, const int32_t* keep_idx, const PlanObjective& obj, int32_t P, uint64_t seed, uint64_t plan_id,
-                   float* out, void* stream, const bool sharded) {
-    if (!obj.has_model(e)) return obj.no_model();
-    if (!p || !x0 || !lower || !upper || !elite || !obj.has_start() || !out) return fail("null argument");
-    if (obj.check_act_dim(e, p->act_dim)) return 1;
+                   float* out, void* stream) {
+    if (check_plan(e, obj, p && x0 && lower && upper && elite && out, p ? p->act_dim : 0, n_env, P)) return 1;
     if (p->horizon < 2 || p->horizon > kMaxHorizon) return fail("iCEM horizon %d outside [2, %d]", p->horizon, kMaxHorizon);
     const int K = p->elite_num, keep = p->keep_elite_size, iters = p->num_iterations, H = p->horizon, A = p->act_dim;
     if (K < 1 || keep < 0 || keep > K) return fail("elite_num %d / keep_elite_size %d invalid", K, keep);
     if (p->population_size < 1 || iters < 0 || !(p->population_decay_factor > 0.0)) return fail("bad iCEM parameters");
-    if (n_env < 1 || n_env > 4096) return fail("n_env %d outside [1, 4096]", n_env);
-    if (obj.planet && P < 1) return fail("bad pop/horizon/particles");
     // population sizes (:419-431) and the rows every iteration evaluates are known up front: size the workspace for the largest, and
     // (sharded) refuse on EVERY rank, before the first collective, what one rank's shard of some iteration could not take
     std::vector<int> sizes(iters), rows_of(iters);
@@ -1563,20 +1592,17 @@ int plan_icem_impl(hipets_engine* e, const hipets_icem_params* p, int32_t n_env,
         rows_of[i] = n + (he ? ((i == iters - 1 && i != 0) ? 1 : keep) : 0);
         if (K > rows_of[i]) return fail("elite_num %d invalid", K);
         max_rows = std::max(max_rows, n + keep);
-        if (sharded && check_shards(e, rows_of[i], P)) return 1;
+        if (obj.is_sharded() && check_shards(e, rows_of[i], P)) return 1;
     }
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
     const size_t nd = (size_t)H * A, ne = (size_t)n_env;
-    const int world = sharded ? e->comm_world : 1, rank = sharded ? e->comm_rank : 0;
-    const int max_width = (max_rows + world - 1) / world;
     if (e->mu.ensure(ne * nd * 4) || e->disp.ensure(ne * nd * 4) || e->best_solution.ensure(ne * nd * 4) || e->best_value.ensure(ne * 4 + 16) ||
         e->population.ensure(ne * max_rows * nd * 4) || e->values.ensure(ne * max_rows * 4) ||
         e->kept.ensure(ne * std::max(keep, 1) * nd * 4) || e->elite_idx.ensure(ne * K * 4) || e->keep_idx.ensure(ne * std::max(keep, 1) * 4) ||
-        (!obj.planet && e->s0.ensure(ne * e->md.obs_dim * 4)))
+        (!obj.is_planet() && e->s0.ensure(ne * e->md.obs_dim * 4)) || obj.reserve_shards(e, max_rows))
         return 1;
-    if (sharded && (e->shard_values.ensure((size_t)max_width * 4) || e->gathered.ensure((size_t)world * max_width * 4))) return 1;
     hipets_cem_params cp{};
     cp.population_size = std::max(K, 1);
     cp.horizon = H;
@@ -1590,20 +1616,20 @@ int plan_icem_impl(hipets_engine* e, const hipets_icem_params* p, int32_t n_env,
     LocalErr le;  // (only a sharded plan carries on after a local failure: its peers wait in the collectives)
     hipets_rollout_opts ro{};
     ro.mode = e->plan_mode;
-    ro.seed = seed + (uint64_t)rank * 0x9E3779B97F4A7C15ull;  // ranks draw independent rollout randomness (rank 0: as hipets_plan_icem)
+    ro.seed = obj.rollout_seed(e, seed);
     ro.n_env = n_env;
     float* popbuf = e->population.as<float>();  // [n_env][rows][H][A], rows = this iteration's candidates per environment
     auto prologue = [&]() -> int {
-        if (sharded) HCHECK(hipMemsetAsync(e->shard_values.p, 0, (size_t)max_width * 4, st));  // padding slot of the shorter shards
+        if (obj.clear_padding(e, max_rows, st)) return 1;
         hipLaunchKernelGGL(cem_init_kernel, dim3((unsigned)((ne * nd + 255) / 256)), dim3(256), 0, st, make_cem(&cp, n_env), x0, lower, upper,
                            e->mu.as<float>(), e->disp.as<float>(), e->best_value.as<float>());
         HCHECK(hipGetLastError());
         HCHECK(hipMemsetAsync(e->best_solution.p, 0, ne * nd * 4, st));
         // the observations are the same for every iteration: staged once (a PlaNet objective reads its DEVICE start states in place)
-        return obj.planet ? 0 : stage_h2d(e, e->s0.p, obj.s0, ne * e->md.obs_dim * 4, st);
+        return obj.is_planet() ? 0 : stage_h2d(e, e->s0.p, obj.s0, ne * e->md.obs_dim * 4, st);
     };
     le.note(prologue());
-    if (!sharded && !le.ok()) return le.report();
+    if (!obj.is_sharded() && !le.ok()) return le.report();
     for (int i = 0; i < iters; ++i) {
         const int n = sizes[i], rows = rows_of[i], extra = rows - n;
         const uint64_t sid = (plan_id * (uint64_t)iters + (uint64_t)i) * 4;
@@ -1644,17 +1670,11 @@ int plan_icem_impl(hipets_engine* e, const hipets_icem_params* p, int32_t n_env,
         auto refit = [&]() -> int {
             cp.population_size = rows;
             if (check_cem(&cp)) return 1;
-            int n2 = 1;
-            while (n2 < rows) n2 <<= 1;
             CemDev cr = make_cem(&cp, n_env);
-            if (!sharded) {  // the rollouts left their per-row totals: the particle means are formed inside the refit kernel (same sum, same bits)
-                cr.totals = e->totals.as<float>();
-                cr.P = P;
-            }
-            hipLaunchKernelGGL(cem_refit_kernel, dim3(refit_blocks((int)nd), n_env), dim3(kRefitThreads), (size_t)n2 * 8 + kRefitScratchBytes, st, cr,
-                               e->values.as<float>(), popbuf, e->mu.as<float>(), e->disp.as<float>(), e->best_value.as<float>(),
-                               e->best_solution.as<float>(), e->elite_idx.as<int>());
-            HCHECK(hipGetLastError());
+            obj.refit_from_totals(e, &cr, P);
+            if (launch_cem_refit(cr, e->values.as<float>(), popbuf, e->mu.as<float>(), e->disp.as<float>(), e->best_value.as<float>(),
+                                 e->best_solution.as<float>(), e->elite_idx.as<int>(), st))
+                return 1;
             const long long nk = (long long)K * nd;  // self.elite = population[elite_idx] (:476), per environment
             hipLaunchKernelGGL(gather_rows_kernel, dim3((unsigned)((nk + 255) / 256), n_env), dim3(256), 0, st, K, (int)nd, popbuf, e->elite_idx.as<int32_t>(),
                                elite, (long long)rows * nd, (long long)K * nd);
@@ -1666,13 +1686,9 @@ int plan_icem_impl(hipets_engine* e, const hipets_icem_params* p, int32_t n_env,
         };
         if (le.ok()) le.note(sample());
         ro.stream_id = sid + 3;
-        if (sharded) {
-            if (sharded_evaluate(e, popbuf, rows, H, P, &ro, stream, &le)) return 1;
-        } else if (le.ok()) {
-            le.note(obj.evaluate(e, popbuf, n_env * rows, H, P, &ro, nullptr, stream));  // s0 staged above; returns: refit (CemDev::totals)
-        }
+        if (obj.evaluate(e, popbuf, n_env * rows, H, P, &ro, nullptr, stream, le)) return 1;  // s0 staged above; returns: refit (CemDev::totals)
         if (le.ok()) le.note(refit());
-        if (!sharded && !le.ok()) break;
+        if (!obj.is_sharded() && !le.ok()) break;
     }
     if (!le.ok()) return le.report();
     HCHECK(hipMemcpyAsync(out, p->return_mean_elites ? e->mu.p : e->best_solution.p, ne * nd * 4, hipMemcpyDeviceToDevice, st));
@@ -1834,14 +1850,14 @@ int hipets_plan_planet_mppi_batched(hipets_engine* e, int32_t pop, int32_t H, in
                                     int32_t n_env, float* mean, const float* lower, const float* upper, const float* latent0,
                                     const float* belief0, int32_t P, uint64_t seed, uint64_t plan_id, void* stream) {
     return plan_mppi_impl(e, pop, H, A, num_iterations, gamma, beta, n_env, mean, lower, upper, planet_objective(latent0, belief0), P, seed,
-                          plan_id, stream, false);
+                          plan_id, stream);
 }
 
 int hipets_plan_planet_icem_batched(hipets_engine* e, const hipets_icem_params* p, int32_t n_env, const float* x0, const float* lower,
                                     const float* upper, float* elite, int32_t has_elite, const int32_t* keep_idx, const float* latent0,
                                     const float* belief0, int32_t P, uint64_t seed, uint64_t plan_id, float* out, void* stream) {
     return plan_icem_impl(e, p, n_env, x0, lower, upper, elite, has_elite, keep_idx, planet_objective(latent0, belief0), P, seed, plan_id,
-                          out, stream, false);
+                          out, stream);
 }
 
 int hipets_comm_unique_id(void* id_out) {
@@ -1894,64 +1910,8 @@ int hipets_comm_info(hipets_engine* e, int32_t* rank, int32_t* world_size) {
 
 int hipets_plan_cem_sharded(hipets_engine* e, const hipets_cem_params* p, const float* x0, const float* lower, const float* upper,
                             const float* s0, int32_t P, uint64_t seed, uint64_t plan_id, float* out, void* stream) {
-    if (!e || !e->has_model) return fail("engine has no model (call hipets_set_model)");
-    if (!e->comm) return fail("no communicator (call hipets_comm_init)");
-    if (check_cem(p)) return 1;
-    if (!x0 || !lower || !upper || !s0 || !out) return fail("null argument");
-    if (p->act_dim != e->md.act_dim) return fail("act_dim %d != model act_dim %d", p->act_dim, e->md.act_dim);
-    if (check_shards(e, p->population_size, P)) return 1;  // identical on every rank, before any collective
-    const int world = e->comm_world, rank = e->comm_rank;
-    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    HCHECK(hipSetDevice(e->device));
-    ENTER_STREAM(e, st);
-    const CemDev c = make_cem(p, 1);
-    const int width = (c.pop + world - 1) / world;
-    const size_t nd = (size_t)c.D;
-    if (e->mu.ensure(nd * 4) || e->disp.ensure(nd * 4) || e->best_solution.ensure(nd * 4) || e->best_value.ensure(16) ||
-        e->population.ensure((size_t)c.pop * nd * 4) || e->values.ensure((size_t)c.pop * 4) || e->shard_values.ensure((size_t)width * 4) ||
-        e->gathered.ensure((size_t)world * width * 4))
-        return 1;
-    LocalErr le;
-    hipets_rollout_opts ro{};
-    ro.mode = e->plan_mode;
-    ro.seed = seed + (uint64_t)rank * 0x9E3779B97F4A7C15ull;  // ranks draw independent rollout randomness (rank 0: as hipets_plan_cem)
-    int n2 = 1;
-    while (n2 < c.pop) n2 <<= 1;
-    auto prologue = [&]() -> int {
-        hipLaunchKernelGGL(cem_init_kernel, dim3((unsigned)((nd + 255) / 256)), dim3(256), 0, st, c, x0, lower, upper, e->mu.as<float>(),
-                           e->disp.as<float>(), e->best_value.as<float>());
-        HCHECK(hipGetLastError());
-        HCHECK(hipMemsetAsync(e->best_solution.p, 0, nd * 4, st));
-        HCHECK(hipMemsetAsync(e->shard_values.p, 0, (size_t)width * 4, st));  // padding slot of the shorter shards
-        return plan_prologue(e, s0, 1, c.H, p->num_iterations, ro.seed, plan_id * (uint64_t)p->num_iterations, st);
-    };
-    le.note(prologue());
-    for (int i = 0; i < p->num_iterations; ++i) {
-        const uint64_t sid = plan_id * (uint64_t)p->num_iterations + (uint64_t)i;
-        auto sample = [&]() -> int {
-            const long long n = (long long)c.pop * c.D;
-            hipLaunchKernelGGL(cem_sample_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, c, e->mu.as<float>(), e->disp.as<float>(),
-                               lower, upper, (const float*)nullptr, (unsigned long long)seed, (unsigned long long)sid,
-                               e->population.as<float>());  // identical on every rank: same seed, same counters
-            HCHECK(hipGetLastError());
-            return 0;
-        };
-        auto refit = [&]() -> int {
-            int* eidx = (e->has_trace && e->trace.elite_idx) ? e->trace.elite_idx + (size_t)i * c.K : nullptr;
-            hipLaunchKernelGGL(cem_refit_kernel, dim3(refit_blocks(c.D), 1), dim3(kRefitThreads), (size_t)n2 * 8 + kRefitScratchBytes, st, c, e->values.as<float>(),
-                               e->population.as<float>(), e->mu.as<float>(), e->disp.as<float>(), e->best_value.as<float>(),
-                               e->best_solution.as<float>(), eidx);
-            HCHECK(hipGetLastError());
-            return trace_iter(e, i, c.pop, nd, e->population.as<float>(), e->values.as<float>(), e->mu.as<float>(), e->disp.as<float>(), st);
-        };
-        if (le.ok()) le.note(sample());
-        ro.stream_id = sid;
-        if (sharded_evaluate(e, e->population.as<float>(), c.pop, c.H, P, &ro, stream, &le)) return 1;
-        if (le.ok()) le.note(refit());
-    }
-    if (!le.ok()) return le.report();
-    HCHECK(hipMemcpyAsync(out, p->return_mean_elites ? e->mu.p : e->best_solution.p, nd * 4, hipMemcpyDeviceToDevice, st));
-    return 0;
+    if (e && !e->comm) return fail("no communicator (call hipets_comm_init)");
+    return plan_cem_impl(e, p, 1, x0, lower, upper, ensemble_objective(s0, PlanObjective::SHARDED), P, seed, plan_id, out, stream);
 }
 
 int hipets_timing_enable(hipets_engine* e, int32_t on) {

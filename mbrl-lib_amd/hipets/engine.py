@@ -472,46 +472,55 @@ class Engine:
                                                    int(seed) & (2**64 - 1), int(stream_id) & (2**64 - 1), _ptr(out), _stream(dev)))
         return out
 
+    def _plan_args(self, tensors, n_env: int = 1, s0=None, latent0=None, belief0=None, sharded: bool = False, seed: int = 0, plan_id: int = 0):
+        """The checks every plan method shares, in this order: the bound model (the ensemble for ``s0``, the PlaNet model for
+        ``latent0`` / ``belief0``); ``tensors``, (name, tensor, shape tuple or element count) on the device, float32 (keep_idx:
+        int32; None: not passed); the start state, host s0 of n_env x obs_dim values or device latent0 [n_env, latent] / belief0
+        [n_env, belief].  Returns (device, the start state's C arguments, seed and plan id as uint64)."""
+        planet = s0 is None
+        spec = self.planet_spec if planet else self.spec
+        if spec is None:
+            raise HipetsError("Engine.planet_set_model() has not been called" if planet else "Engine.set_model() has not been called")
+        dev = self.device
+        for name, t, size in tensors:
+            if t is not None:
+                dtype = torch.int32 if name == "keep_idx" else torch.float32
+                _check_dev(t, dtype, dev, name, **({"shape": size} if isinstance(size, tuple) else {"numel": size}))
+        if planet:
+            _check_dev(latent0, torch.float32, dev, "latent0", numel=n_env * spec.latent_size)
+            _check_dev(belief0, torch.float32, dev, "belief0", numel=n_env * spec.belief_size)
+            start = (_ptr(latent0), _ptr(belief0))
+        else:
+            s0 = np.ascontiguousarray(np.asarray(s0, dtype=np.float32).reshape(-1))
+            if s0.shape[0] != spec.obs_dim * n_env:
+                expected = spec.obs_dim if sharded else f"{n_env} x {spec.obs_dim}"
+                raise ValueError(f"initial_state has {s0.shape[0]} values, expected {expected}")
+            start = (s0.ctypes.data_as(C.c_void_p),)  # (the pointer keeps the staged array alive)
+        return dev, start, int(seed) & (2**64 - 1), int(plan_id) & (2**64 - 1)
+
     def plan_cem(self, p: CemParams, x0, lower, upper, s0: np.ndarray, num_particles: int, seed: int = 0,
                  plan_id: int = 0, out: Optional[torch.Tensor] = None, n_env: int = 1) -> torch.Tensor:
         """Whole CEM plan on the device.  n_env > 1: x0 / out are [n_env, H, A], s0 is [n_env, obs_dim]; p.population_size is
         per environment (hipets_plan_cem_batched)."""
-        if self.spec is None:
-            raise HipetsError("Engine.set_model() has not been called")
-        dev = self.device
         shp = (p.horizon, p.act_dim)
-        _check_dev(x0, torch.float32, dev, "x0", numel=n_env * p.horizon * p.act_dim)
-        xshp = tuple(x0.shape)  # [H, A] or [n_env, H, A]
-        for n_, t in (("lower", lower), ("upper", upper)):
-            _check_dev(t, torch.float32, dev, n_, shp)
-        s0 = np.ascontiguousarray(np.asarray(s0, dtype=np.float32).reshape(-1))
-        if s0.shape[0] != self.spec.obs_dim * n_env:
-            raise ValueError(f"initial_state has {s0.shape[0]} values, expected {n_env} x {self.spec.obs_dim}")
+        dev, start, seed, plan_id = self._plan_args([("x0", x0, n_env * p.horizon * p.act_dim), ("lower", lower, shp), ("upper", upper, shp)],
+                                                    n_env, s0=s0, seed=seed, plan_id=plan_id)
         if out is None:
-            out = torch.empty(xshp, dtype=torch.float32, device=dev)
+            out = torch.empty(tuple(x0.shape), dtype=torch.float32, device=dev)  # [H, A] or [n_env, H, A]
         with torch.cuda.device(dev):
-            _lib.check(self._lib.hipets_plan_cem_batched(self._h, C.byref(p), int(n_env), _ptr(x0), _ptr(lower), _ptr(upper),
-                                                         s0.ctypes.data_as(C.c_void_p), num_particles, int(seed) & (2**64 - 1),
-                                                         int(plan_id) & (2**64 - 1), _ptr(out), _stream(dev)))
+            _lib.check(self._lib.hipets_plan_cem_batched(self._h, C.byref(p), int(n_env), _ptr(x0), _ptr(lower), _ptr(upper), *start,
+                                                         num_particles, seed, plan_id, _ptr(out), _stream(dev)))
         return out
 
     def plan_mppi(self, pop: int, H: int, A: int, num_iterations: int, gamma: float, beta: float, mean: torch.Tensor, lower,
                   upper, s0: np.ndarray, num_particles: int, seed: int = 0, plan_id: int = 0, n_env: int = 1) -> torch.Tensor:
         """Whole MPPI plan on the device (hipets_plan_mppi[_batched]).  ``mean`` [H, A] ([n_env, H, A] for a batch of
         environments, ``s0`` then [n_env, obs_dim]) is the optimizer's persistent mean: shifted and refined IN PLACE."""
-        if self.spec is None:
-            raise HipetsError("Engine.set_model() has not been called")
-        dev = self.device
-        _check_dev(mean, torch.float32, dev, "mean", numel=n_env * H * A)
-        for n_, t in (("lower", lower), ("upper", upper)):
-            _check_dev(t, torch.float32, dev, n_, (H, A))
-        s0 = np.ascontiguousarray(np.asarray(s0, dtype=np.float32).reshape(-1))
-        if s0.shape[0] != self.spec.obs_dim * n_env:
-            raise ValueError(f"initial_state has {s0.shape[0]} values, expected {n_env} x {self.spec.obs_dim}")
+        dev, start, seed, plan_id = self._plan_args([("mean", mean, n_env * H * A), ("lower", lower, (H, A)), ("upper", upper, (H, A))],
+                                                    n_env, s0=s0, seed=seed, plan_id=plan_id)
         with torch.cuda.device(dev):
             _lib.check(self._lib.hipets_plan_mppi_batched(self._h, pop, H, A, num_iterations, float(gamma), float(beta), int(n_env), _ptr(mean),
-                                                          _ptr(lower), _ptr(upper), s0.ctypes.data_as(C.c_void_p), num_particles,
-                                                          int(seed) & (2**64 - 1), int(plan_id) & (2**64 - 1), _stream(dev)))
+                                                          _ptr(lower), _ptr(upper), *start, num_particles, seed, plan_id, _stream(dev)))
         return mean
 
     def plan_icem(self, p: "_lib.IcemParams", x0, lower, upper, elite: torch.Tensor, has_elite: bool, s0: np.ndarray,
@@ -521,27 +530,22 @@ class Engine:
         persistent elite set (read when ``has_elite``, always overwritten); ``keep_idx`` int32 [num_iterations, keep]
         optionally injects the kept-elite draws.  n_env > 1: x0 / out [n_env, H, A], elite [n_env, elite_num, H, A],
         keep_idx [num_iterations, n_env, keep], s0 [n_env, obs_dim]."""
-        if self.spec is None:
-            raise HipetsError("Engine.set_model() has not been called")
-        dev = self.device
-        shp = (p.horizon, p.act_dim)
-        _check_dev(x0, torch.float32, dev, "x0", numel=n_env * p.horizon * p.act_dim)
-        for n_, t in (("lower", lower), ("upper", upper)):
-            _check_dev(t, torch.float32, dev, n_, shp)
-        _check_dev(elite, torch.float32, dev, "elite", numel=n_env * p.elite_num * p.horizon * p.act_dim)
-        if keep_idx is not None:
-            _check_dev(keep_idx, torch.int32, dev, "keep_idx", numel=p.num_iterations * n_env * p.keep_elite_size)
-        s0 = np.ascontiguousarray(np.asarray(s0, dtype=np.float32).reshape(-1))
-        if s0.shape[0] != self.spec.obs_dim * n_env:
-            raise ValueError(f"initial_state has {s0.shape[0]} values, expected {n_env} x {self.spec.obs_dim}")
+        dev, start, seed, plan_id = self._plan_args(self._icem_tensors(p, x0, lower, upper, elite, keep_idx, n_env), n_env, s0=s0, seed=seed,
+                                                    plan_id=plan_id)
         if out is None:
             out = torch.empty(tuple(x0.shape), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check(self._lib.hipets_plan_icem_batched(self._h, C.byref(p), int(n_env), _ptr(x0), _ptr(lower), _ptr(upper), _ptr(elite),
-                                                          int(bool(has_elite)), _ptr(keep_idx) if keep_idx is not None else None,
-                                                          s0.ctypes.data_as(C.c_void_p), num_particles, int(seed) & (2**64 - 1),
-                                                          int(plan_id) & (2**64 - 1), _ptr(out), _stream(dev)))
+                                                          int(bool(has_elite)), _ptr(keep_idx), *start, num_particles, seed, plan_id,
+                                                          _ptr(out), _stream(dev)))
         return out
+
+    @staticmethod
+    def _icem_tensors(p, x0, lower, upper, elite, keep_idx, n_env: int, x0_shape: bool = False):
+        """The device arguments of an iCEM plan for _plan_args (x0_shape: x0 exactly [H, A], not only its size)."""
+        shp, nd = (p.horizon, p.act_dim), p.horizon * p.act_dim
+        return [("x0", x0, shp if x0_shape else n_env * nd), ("lower", lower, shp), ("upper", upper, shp),
+                ("elite", elite, n_env * p.elite_num * nd), ("keep_idx", keep_idx, p.num_iterations * n_env * p.keep_elite_size)]
 
     # ---- in-library RCCL communicator (population-sharded fused plans) -----------------------------
     def comm_unique_id(self) -> bytes:
@@ -570,62 +574,37 @@ class Engine:
     def plan_cem_sharded(self, p: CemParams, x0, lower, upper, s0: np.ndarray, num_particles: int, seed: int = 0, plan_id: int = 0,
                          out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """hipets_plan_cem over all ranks of the communicator (identical arguments on every rank)."""
-        if self.spec is None:
-            raise HipetsError("Engine.set_model() has not been called")
-        dev = self.device
         shp = (p.horizon, p.act_dim)
-        for n_, t in (("x0", x0), ("lower", lower), ("upper", upper)):
-            _check_dev(t, torch.float32, dev, n_, shp)
-        s0 = np.ascontiguousarray(np.asarray(s0, dtype=np.float32).reshape(-1))
-        if s0.shape[0] != self.spec.obs_dim:
-            raise ValueError(f"initial_state has {s0.shape[0]} values, expected {self.spec.obs_dim}")
+        dev, start, seed, plan_id = self._plan_args([("x0", x0, shp), ("lower", lower, shp), ("upper", upper, shp)], s0=s0, sharded=True,
+                                                    seed=seed, plan_id=plan_id)
         if out is None:
             out = torch.empty(shp, dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
-            _lib.check(self._lib.hipets_plan_cem_sharded(self._h, C.byref(p), _ptr(x0), _ptr(lower), _ptr(upper),
-                                                         s0.ctypes.data_as(C.c_void_p), num_particles, int(seed) & (2**64 - 1),
-                                                         int(plan_id) & (2**64 - 1), _ptr(out), _stream(dev)))
+            _lib.check(self._lib.hipets_plan_cem_sharded(self._h, C.byref(p), _ptr(x0), _ptr(lower), _ptr(upper), *start, num_particles, seed,
+                                                         plan_id, _ptr(out), _stream(dev)))
         return out
 
     def plan_mppi_sharded(self, pop: int, H: int, A: int, num_iterations: int, gamma: float, beta: float, mean: torch.Tensor, lower,
                           upper, s0: np.ndarray, num_particles: int, seed: int = 0, plan_id: int = 0) -> torch.Tensor:
         """hipets_plan_mppi over all ranks of the communicator (identical arguments on every rank; ``mean`` in place)."""
-        if self.spec is None:
-            raise HipetsError("Engine.set_model() has not been called")
-        dev = self.device
-        for n_, t in (("mean", mean), ("lower", lower), ("upper", upper)):
-            _check_dev(t, torch.float32, dev, n_, (H, A))
-        s0 = np.ascontiguousarray(np.asarray(s0, dtype=np.float32).reshape(-1))
-        if s0.shape[0] != self.spec.obs_dim:
-            raise ValueError(f"initial_state has {s0.shape[0]} values, expected {self.spec.obs_dim}")
+        dev, start, seed, plan_id = self._plan_args([("mean", mean, (H, A)), ("lower", lower, (H, A)), ("upper", upper, (H, A))], s0=s0,
+                                                    sharded=True, seed=seed, plan_id=plan_id)
         with torch.cuda.device(dev):
             _lib.check(self._lib.hipets_plan_mppi_sharded(self._h, pop, H, A, num_iterations, float(gamma), float(beta), _ptr(mean), _ptr(lower),
-                                                          _ptr(upper), s0.ctypes.data_as(C.c_void_p), num_particles, int(seed) & (2**64 - 1),
-                                                          int(plan_id) & (2**64 - 1), _stream(dev)))
+                                                          _ptr(upper), *start, num_particles, seed, plan_id, _stream(dev)))
         return mean
 
     def plan_icem_sharded(self, p: "_lib.IcemParams", x0, lower, upper, elite: torch.Tensor, has_elite: bool, s0: np.ndarray,
                           num_particles: int, seed: int = 0, plan_id: int = 0, keep_idx: Optional[torch.Tensor] = None,
                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """hipets_plan_icem over all ranks of the communicator (identical arguments on every rank; ``elite`` in place)."""
-        if self.spec is None:
-            raise HipetsError("Engine.set_model() has not been called")
-        dev = self.device
-        shp = (p.horizon, p.act_dim)
-        for n_, t in (("x0", x0), ("lower", lower), ("upper", upper)):
-            _check_dev(t, torch.float32, dev, n_, shp)
-        _check_dev(elite, torch.float32, dev, "elite", numel=p.elite_num * p.horizon * p.act_dim)
-        if keep_idx is not None:
-            _check_dev(keep_idx, torch.int32, dev, "keep_idx", numel=p.num_iterations * p.keep_elite_size)
-        s0 = np.ascontiguousarray(np.asarray(s0, dtype=np.float32).reshape(-1))
-        if s0.shape[0] != self.spec.obs_dim:
-            raise ValueError(f"initial_state has {s0.shape[0]} values, expected {self.spec.obs_dim}")
+        dev, start, seed, plan_id = self._plan_args(self._icem_tensors(p, x0, lower, upper, elite, keep_idx, 1, x0_shape=True), s0=s0,
+                                                    sharded=True, seed=seed, plan_id=plan_id)
         if out is None:
-            out = torch.empty(shp, dtype=torch.float32, device=dev)
+            out = torch.empty((p.horizon, p.act_dim), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check(self._lib.hipets_plan_icem_sharded(self._h, C.byref(p), _ptr(x0), _ptr(lower), _ptr(upper), _ptr(elite), int(bool(has_elite)),
-                                                          _ptr(keep_idx) if keep_idx is not None else None, s0.ctypes.data_as(C.c_void_p),
-                                                          num_particles, int(seed) & (2**64 - 1), int(plan_id) & (2**64 - 1), _ptr(out), _stream(dev)))
+                                                          _ptr(keep_idx), *start, num_particles, seed, plan_id, _ptr(out), _stream(dev)))
         return out
 
     # ---- PlaNet latent planner (SURVEY.md 8f row 4) -----------------------------------------------
@@ -691,35 +670,23 @@ class Engine:
                                                        C.byref(o), _ptr(out), _stream(dev)))
         return out
 
-    def _planet_plan_args(self, lower, upper, latent0, belief0, H: int, A: int, n_env: int):
-        spec = getattr(self, "planet_spec", None)
-        if spec is None:
-            raise HipetsError("Engine.planet_set_model() has not been called")
-        dev = self.device
-        for n_, t in (("lower", lower), ("upper", upper)):
-            _check_dev(t, torch.float32, dev, n_, (H, A))
-        _check_dev(latent0, torch.float32, dev, "latent0", numel=n_env * spec.latent_size)
-        _check_dev(belief0, torch.float32, dev, "belief0", numel=n_env * spec.belief_size)
-        return dev
-
     def plan_planet_cem(self, p: CemParams, x0, lower, upper, latent0: torch.Tensor, belief0: torch.Tensor, num_particles: int,
                         seed: int = 0, plan_id: int = 0, out: Optional[torch.Tensor] = None, n_env: int = 1) -> torch.Tensor:
         """Whole CEM plan over the PlaNet latent model on the device.  x0 [H, A] with n_env = 1: hipets_plan_planet_cem; else
         hipets_plan_planet_cem_batched with x0 / out [n_env, H, A], latent0 [n_env, latent], belief0 [n_env, belief] and
         p.population_size per environment."""
-        dev = self._planet_plan_args(lower, upper, latent0, belief0, p.horizon, p.act_dim, n_env)
-        _check_dev(x0, torch.float32, dev, "x0", numel=n_env * p.horizon * p.act_dim)
+        shp = (p.horizon, p.act_dim)
+        dev, start, seed, plan_id = self._plan_args([("x0", x0, n_env * p.horizon * p.act_dim), ("lower", lower, shp), ("upper", upper, shp)],
+                                                    n_env, latent0=latent0, belief0=belief0, seed=seed, plan_id=plan_id)
         if out is None:
             out = torch.empty(tuple(x0.shape), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             if n_env == 1 and x0.ndim == 2:
-                _lib.check(self._lib.hipets_plan_planet_cem(self._h, C.byref(p), _ptr(x0), _ptr(lower), _ptr(upper), _ptr(latent0), _ptr(belief0),
-                                                            num_particles, int(seed) & (2**64 - 1), int(plan_id) & (2**64 - 1), _ptr(out),
-                                                            _stream(dev)))
+                _lib.check(self._lib.hipets_plan_planet_cem(self._h, C.byref(p), _ptr(x0), _ptr(lower), _ptr(upper), *start, num_particles, seed,
+                                                            plan_id, _ptr(out), _stream(dev)))
             else:
-                _lib.check(self._lib.hipets_plan_planet_cem_batched(self._h, C.byref(p), int(n_env), _ptr(x0), _ptr(lower), _ptr(upper),
-                                                                    _ptr(latent0), _ptr(belief0), num_particles, int(seed) & (2**64 - 1),
-                                                                    int(plan_id) & (2**64 - 1), _ptr(out), _stream(dev)))
+                _lib.check(self._lib.hipets_plan_planet_cem_batched(self._h, C.byref(p), int(n_env), _ptr(x0), _ptr(lower), _ptr(upper), *start,
+                                                                    num_particles, seed, plan_id, _ptr(out), _stream(dev)))
         return out
 
     def plan_planet_mppi(self, pop: int, H: int, A: int, num_iterations: int, gamma: float, beta: float, mean: torch.Tensor, lower, upper,
@@ -727,12 +694,11 @@ class Engine:
                          n_env: int = 1) -> torch.Tensor:
         """Whole MPPI plan over the PlaNet latent model (hipets_plan_planet_mppi_batched): ``mean`` [n_env, H, A] is the persistent
         mean of every environment, shifted and refined IN PLACE; latent0 [n_env, latent], belief0 [n_env, belief]."""
-        dev = self._planet_plan_args(lower, upper, latent0, belief0, H, A, n_env)
-        _check_dev(mean, torch.float32, dev, "mean", numel=n_env * H * A)
+        dev, start, seed, plan_id = self._plan_args([("mean", mean, n_env * H * A), ("lower", lower, (H, A)), ("upper", upper, (H, A))],
+                                                    n_env, latent0=latent0, belief0=belief0, seed=seed, plan_id=plan_id)
         with torch.cuda.device(dev):
             _lib.check(self._lib.hipets_plan_planet_mppi_batched(self._h, pop, H, A, num_iterations, float(gamma), float(beta), int(n_env),
-                                                                 _ptr(mean), _ptr(lower), _ptr(upper), _ptr(latent0), _ptr(belief0),
-                                                                 num_particles, int(seed) & (2**64 - 1), int(plan_id) & (2**64 - 1),
+                                                                 _ptr(mean), _ptr(lower), _ptr(upper), *start, num_particles, seed, plan_id,
                                                                  _stream(dev)))
         return mean
 
@@ -741,18 +707,14 @@ class Engine:
                          out: Optional[torch.Tensor] = None, n_env: int = 1) -> torch.Tensor:
         """Whole iCEM plan over the PlaNet latent model (hipets_plan_planet_icem_batched); arguments as :meth:`plan_icem` with
         latent0 [n_env, latent] / belief0 [n_env, belief] in place of s0."""
-        dev = self._planet_plan_args(lower, upper, latent0, belief0, p.horizon, p.act_dim, n_env)
-        _check_dev(x0, torch.float32, dev, "x0", numel=n_env * p.horizon * p.act_dim)
-        _check_dev(elite, torch.float32, dev, "elite", numel=n_env * p.elite_num * p.horizon * p.act_dim)
-        if keep_idx is not None:
-            _check_dev(keep_idx, torch.int32, dev, "keep_idx", numel=p.num_iterations * n_env * p.keep_elite_size)
+        dev, start, seed, plan_id = self._plan_args(self._icem_tensors(p, x0, lower, upper, elite, keep_idx, n_env), n_env, latent0=latent0,
+                                                    belief0=belief0, seed=seed, plan_id=plan_id)
         if out is None:
             out = torch.empty(tuple(x0.shape), dtype=torch.float32, device=dev)
         with torch.cuda.device(dev):
             _lib.check(self._lib.hipets_plan_planet_icem_batched(self._h, C.byref(p), int(n_env), _ptr(x0), _ptr(lower), _ptr(upper), _ptr(elite),
-                                                                 int(bool(has_elite)), _ptr(keep_idx) if keep_idx is not None else None,
-                                                                 _ptr(latent0), _ptr(belief0), num_particles, int(seed) & (2**64 - 1),
-                                                                 int(plan_id) & (2**64 - 1), _ptr(out), _stream(dev)))
+                                                                 int(bool(has_elite)), _ptr(keep_idx), *start, num_particles, seed, plan_id,
+                                                                 _ptr(out), _stream(dev)))
         return out
 
     # ---- instrumentation ---------------------------------------------------------------------------

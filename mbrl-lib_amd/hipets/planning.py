@@ -884,6 +884,22 @@ class ICEMOptimizer(Optimizer):
             n = self._round_up_to_module(n, self.population_size_module)
         return int(n)
 
+    def _fused_plan(self, H: int, A: int, has_elite: bool):
+        """The fused plan of one optimize(): the rows every iteration evaluates (its population, plus the kept elites or, in
+        the last of several iterations, the mean; trajectory_opt.py:450-466) and the library's IcemParams."""
+        iters, keep = int(self.num_iterations), int(self.keep_elite_size)
+        sizes = []
+        for i in range(iters):
+            extra = 0
+            if has_elite or i > 0:
+                extra = 1 if (i == iters - 1 and i != 0) else keep
+            sizes.append(self._iteration_size(i) + extra)
+        p = IcemParams(population_size=int(self.population_size), horizon=H, act_dim=A, num_iterations=iters, elite_num=int(self.elite_num),
+                       keep_elite_size=keep, population_size_module=int(self.population_size_module or 0),
+                       return_mean_elites=int(bool(self.return_mean_elites)), alpha=float(self.alpha),
+                       population_decay_factor=float(self.population_decay_factor), colored_noise_exponent=float(self.colored_noise_exponent))
+        return sizes, p
+
     def optimize(self, obj_fun: Callable[[torch.Tensor], torch.Tensor], x0: Optional[torch.Tensor] = None,
                  callback: Optional[Callable[[torch.Tensor, torch.Tensor, int], None]] = None, **kwargs) -> torch.Tensor:
         eng = self.engine
@@ -896,18 +912,8 @@ class ICEMOptimizer(Optimizer):
             fused = None
         seed = (self.seed ^ fused.seed) if fused is not None else self.seed
         if fused is not None and callback is None and kwargs.get("inject") is None and not kwargs.get("force_generic", False):
-            sizes = []
-            for i in range(self.num_iterations):
-                extra = 0
-                if self.elite is not None or i > 0:
-                    extra = 1 if (i == self.num_iterations - 1 and i != 0) else keep
-                sizes.append(self._iteration_size(i) + extra)
+            sizes, p = self._fused_plan(H, A, self.elite is not None)
             _prepare_fused(fused, sizes)
-            p = IcemParams(population_size=int(self.population_size), horizon=H, act_dim=A, num_iterations=int(self.num_iterations),
-                           elite_num=K, keep_elite_size=keep, population_size_module=int(self.population_size_module or 0),
-                           return_mean_elites=int(bool(self.return_mean_elites)), alpha=float(self.alpha),
-                           population_decay_factor=float(self.population_decay_factor),
-                           colored_noise_exponent=float(self.colored_noise_exponent))
             has_elite = self.elite is not None
             elite = self.elite.contiguous() if has_elite else torch.empty((K, H, A), device=self.device, dtype=torch.float32)
             if eng.comm_world > 1:  # sharded over the engine's communicator; the persistent elites stay replicated bit for bit
@@ -1205,7 +1211,56 @@ def _planet_start_states(eval_fn, n_env: int, obs_batch, latent, belief):
     return states
 
 
-class BatchedCEMAgent(Agent):
+class _BatchedAgent(Agent):
+    """What the batched agents share: action bounds tiled over the horizon, the warm start (the bounds' midpoint, shifted by
+    ``replan_freq`` after every plan, trajectory_opt.py:563-567), an objective with in-kernel randomness, and the start states of
+    a plan: the observation batch of an ensemble objective, or the ``latent=`` / ``belief=`` states of a PlaNet one."""
+
+    def __init__(self, eval_fn: HipTrajectoryEvalFn, n_env: int, action_lb: Sequence[float], action_ub: Sequence[float],
+                 planning_horizon: int, replan_freq: int = 1, seed: int = 0):
+        if eval_fn.kernel_mode is None:
+            raise ValueError("batched planning needs an objective with in-kernel randomness (mode='device' or 'fast')")
+        self.eval_fn, self.engine, self.device = eval_fn, eval_fn.engine, eval_fn.device
+        self.n_env, self.horizon, self.replan_freq = int(n_env), int(planning_horizon), int(replan_freq)
+        lb, ub = np.asarray(action_lb, np.float32), np.asarray(action_ub, np.float32)
+        self.act_dim = int(lb.shape[0])
+        self.lower = torch.tensor(np.tile(lb, (planning_horizon, 1)), device=self.device).contiguous()
+        self.upper = torch.tensor(np.tile(ub, (planning_horizon, 1)), device=self.device).contiguous()
+        self.initial_solution = torch.tensor((lb + ub) / 2, device=self.device).repeat(self.n_env, planning_horizon, 1).contiguous()
+        self.previous_solution = self.initial_solution.clone()
+        self.seed, self.calls = int(seed), 0
+
+    def reset(self):
+        self.previous_solution = self.initial_solution.clone()
+
+    def _plan(self, plan, plan_planet, args, obs_batch, latent, belief, population_sizes, **kw):
+        """One plan call: ``plan(*args, s0, ...)`` from the observation batch (after _prepare_fused for the batch sizes
+        ``population_sizes``), or ``plan_planet(*args, latent0, belief0, ...)`` for a PlaNet objective."""
+        planet = isinstance(self.eval_fn, PlaNetTrajectoryEvalFn)
+        if planet:
+            start = _planet_start_states(self.eval_fn, self.n_env, obs_batch, latent, belief)
+        else:
+            obs_batch = np.asarray(obs_batch, dtype=np.float32)
+            assert obs_batch.shape[0] == self.n_env
+            _prepare_fused(self.eval_fn, population_sizes)
+            start = [obs_batch]
+        self.calls += 1
+        return (plan_planet if planet else plan)(*args, *start, self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed,
+                                                 plan_id=self.calls, n_env=self.n_env, **kw)
+
+    def _shift(self, best: torch.Tensor) -> np.ndarray:
+        """The next plan's warm start from this plan's ``best`` [n_env, H, A]; returns ``best`` on the host."""
+        self.previous_solution = best.roll(-self.replan_freq, dims=1)
+        self.previous_solution[:, -self.replan_freq:] = self.initial_solution[:, :1]
+        self.previous_solution = self.previous_solution.contiguous()
+        return best.cpu().numpy()
+
+    def act(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
+        """One action per environment, [n_env, A]."""
+        return self.plan(obs_batch, latent=latent, belief=belief)[:, 0]
+
+
+class BatchedCEMAgent(_BatchedAgent):
     """Batched planning: one CEM plan per environment for ``n_env`` environments (vectorised envs,
     MPC for many agents) in ONE set of launches.  Same algorithm per environment as ``TrajectoryOptimizerAgent`` +
     ``CEMOptimizer`` (warm start shifted by ``replan_freq`` per environment, trajectory_opt.py:563-567); a single cfg2
@@ -1219,55 +1274,18 @@ class BatchedCEMAgent(Agent):
     def __init__(self, eval_fn: HipTrajectoryEvalFn, n_env: int, action_lb: Sequence[float], action_ub: Sequence[float],
                  planning_horizon: int, num_iterations: int, elite_ratio: float, population_size: int, alpha: float,
                  return_mean_elites: bool = True, clipped_normal: bool = False, replan_freq: int = 1, seed: int = 0):
-        if eval_fn.kernel_mode is None:
-            raise ValueError("batched planning needs an objective with in-kernel randomness (mode='device' or 'fast')")
-        self.eval_fn, self.engine, self.device = eval_fn, eval_fn.engine, eval_fn.device
-        self.n_env, self.horizon, self.replan_freq = int(n_env), int(planning_horizon), int(replan_freq)
-        lb, ub = np.asarray(action_lb, np.float32), np.asarray(action_ub, np.float32)
-        A = lb.shape[0]
-        self.lower = torch.tensor(np.tile(lb, (planning_horizon, 1)), device=self.device).contiguous()
-        self.upper = torch.tensor(np.tile(ub, (planning_horizon, 1)), device=self.device).contiguous()
-        self.initial_solution = torch.tensor((lb + ub) / 2, device=self.device).repeat(self.n_env, planning_horizon, 1).contiguous()
-        self.previous_solution = self.initial_solution.clone()
+        super().__init__(eval_fn, n_env, action_lb, action_ub, planning_horizon, replan_freq, seed)
         self.elite_num = int(np.ceil(population_size * elite_ratio))
-        self._params = Engine.cem_params(population_size, planning_horizon, A, num_iterations, self.elite_num, alpha,
+        self._params = Engine.cem_params(population_size, planning_horizon, self.act_dim, num_iterations, self.elite_num, alpha,
                                          return_mean_elites, clipped_normal, unbiased_var=True)
-        self.seed, self.calls = int(seed), 0
-
-    def reset(self):
-        self.previous_solution = self.initial_solution.clone()
 
     def plan(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
-        if isinstance(self.eval_fn, PlaNetTrajectoryEvalFn):
-            latent0, belief0 = _planet_start_states(self.eval_fn, self.n_env, obs_batch, latent, belief)
-            self.calls += 1
-            best = self.engine.plan_planet_cem(self._params, self.previous_solution, self.lower, self.upper, latent0, belief0,
-                                               self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed, plan_id=self.calls,
-                                               n_env=self.n_env)
-        else:
-            obs_batch = np.asarray(obs_batch, dtype=np.float32)
-            assert obs_batch.shape[0] == self.n_env
-            self.eval_fn.refresh()
-            if self.engine.spec is not self.eval_fn.spec:
-                self.engine.set_model(self.eval_fn.spec)
-            self.eval_fn.check_batch(self._params.population_size)
-            if self.engine.plan_mode != self.eval_fn.kernel_mode:
-                self.engine.set_plan_mode(self.eval_fn.kernel_mode)
-            self.calls += 1
-            best = self.engine.plan_cem(self._params, self.previous_solution, self.lower, self.upper, obs_batch,
-                                        self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed, plan_id=self.calls,
-                                        n_env=self.n_env)
-        self.previous_solution = best.roll(-self.replan_freq, dims=1)
-        self.previous_solution[:, -self.replan_freq:] = self.initial_solution[:, :1]
-        self.previous_solution = self.previous_solution.contiguous()
-        return best.cpu().numpy()
-
-    def act(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
-        """One action per environment, [n_env, A]."""
-        return self.plan(obs_batch, latent=latent, belief=belief)[:, 0]
+        best = self._plan(self.engine.plan_cem, self.engine.plan_planet_cem, (self._params, self.previous_solution, self.lower, self.upper),
+                          obs_batch, latent, belief, [self._params.population_size])
+        return self._shift(best)
 
 
-class BatchedMPPIAgent(Agent):
+class BatchedMPPIAgent(_BatchedAgent):
     """Batched planning with MPPI: ``MPPIOptimizer.optimize`` (trajectory_opt.py:238-311) for ``n_env``
     environments in one set of launches (hipets_plan_mppi_batched).  Every environment keeps its own persistent mean,
     shifted one step per plan like the reference's (Appendix B4-B6).  A ``PlaNetTrajectoryEvalFn`` plans from
@@ -1276,40 +1294,17 @@ class BatchedMPPIAgent(Agent):
     def __init__(self, eval_fn: HipTrajectoryEvalFn, n_env: int, action_lb: Sequence[float], action_ub: Sequence[float],
                  planning_horizon: int, num_iterations: int, population_size: int, gamma: float, sigma: float, beta: float,
                  seed: int = 0):
-        if eval_fn.kernel_mode is None:
-            raise ValueError("batched planning needs an objective with in-kernel randomness (mode='device' or 'fast')")
-        self.eval_fn, self.engine, self.device = eval_fn, eval_fn.engine, eval_fn.device
-        self.n_env, self.horizon = int(n_env), int(planning_horizon)
-        lb, ub = np.asarray(action_lb, np.float32), np.asarray(action_ub, np.float32)
-        self.act_dim = int(lb.shape[0])
-        self.lower = torch.tensor(np.tile(lb, (planning_horizon, 1)), device=self.device).contiguous()
-        self.upper = torch.tensor(np.tile(ub, (planning_horizon, 1)), device=self.device).contiguous()
+        super().__init__(eval_fn, n_env, action_lb, action_ub, planning_horizon, seed=seed)
         self.mean = torch.zeros(self.n_env, self.horizon, self.act_dim, device=self.device)
         self.refinements, self.population_size, self.gamma, self.sigma, self.beta = int(num_iterations), int(population_size), gamma, sigma, beta
-        self.seed, self.calls = int(seed), 0
 
     def plan(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
-        if isinstance(self.eval_fn, PlaNetTrajectoryEvalFn):
-            latent0, belief0 = _planet_start_states(self.eval_fn, self.n_env, obs_batch, latent, belief)
-            self.calls += 1
-            self.engine.plan_planet_mppi(self.population_size, self.horizon, self.act_dim, self.refinements, self.gamma, self.beta, self.mean,
-                                         self.lower, self.upper, latent0, belief0, self.eval_fn.num_particles,
-                                         seed=self.seed ^ self.eval_fn.seed, plan_id=self.calls, n_env=self.n_env)
-            return self.mean.cpu().numpy()
-        obs_batch = np.asarray(obs_batch, dtype=np.float32)
-        assert obs_batch.shape[0] == self.n_env
-        _prepare_fused(self.eval_fn, [self.population_size])
-        self.calls += 1
-        self.engine.plan_mppi(self.population_size, self.horizon, self.act_dim, self.refinements, self.gamma, self.beta, self.mean,
-                              self.lower, self.upper, obs_batch, self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed,
-                              plan_id=self.calls, n_env=self.n_env)
+        self._plan(self.engine.plan_mppi, self.engine.plan_planet_mppi, (self.population_size, self.horizon, self.act_dim, self.refinements,
+                   self.gamma, self.beta, self.mean, self.lower, self.upper), obs_batch, latent, belief, [self.population_size])
         return self.mean.cpu().numpy()
 
-    def act(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
-        return self.plan(obs_batch, latent=latent, belief=belief)[:, 0]
 
-
-class BatchedICEMAgent(Agent):
+class BatchedICEMAgent(_BatchedAgent):
     """Batched planning with iCEM: ``ICEMOptimizer.optimize`` (trajectory_opt.py:391-487) for ``n_env``
     environments in one set of launches (hipets_plan_icem_batched): per-environment mean / variance / persistent elites,
     warm start shifted by ``replan_freq`` per environment (trajectory_opt.py:563-567).  A ``PlaNetTrajectoryEvalFn`` plans from
@@ -1319,64 +1314,21 @@ class BatchedICEMAgent(Agent):
                  planning_horizon: int, num_iterations: int, elite_ratio: float, population_size: int, population_decay_factor: float,
                  colored_noise_exponent: float, keep_elite_frac: float, alpha: float, return_mean_elites: bool = True,
                  population_size_module: Optional[int] = None, replan_freq: int = 1, seed: int = 0):
-        if eval_fn.kernel_mode is None:
-            raise ValueError("batched planning needs an objective with in-kernel randomness (mode='device' or 'fast')")
-        self.eval_fn, self.engine, self.device = eval_fn, eval_fn.engine, eval_fn.device
-        self.n_env, self.horizon, self.replan_freq = int(n_env), int(planning_horizon), int(replan_freq)
-        lb, ub = np.asarray(action_lb, np.float32), np.asarray(action_ub, np.float32)
-        A = int(lb.shape[0])
-        self.lower = torch.tensor(np.tile(lb, (planning_horizon, 1)), device=self.device).contiguous()
-        self.upper = torch.tensor(np.tile(ub, (planning_horizon, 1)), device=self.device).contiguous()
-        self.initial_solution = torch.tensor((lb + ub) / 2, device=self.device).repeat(self.n_env, planning_horizon, 1).contiguous()
-        self.previous_solution = self.initial_solution.clone()
-        # sizes exactly as ICEMOptimizer computes them (:363-389)
+        super().__init__(eval_fn, n_env, action_lb, action_ub, planning_horizon, replan_freq, seed)
+        # sizes and parameters exactly as ICEMOptimizer computes them (:363-389)
         self._opt = ICEMOptimizer(num_iterations, elite_ratio, population_size, population_decay_factor, colored_noise_exponent,
                                   self.lower.tolist(), self.upper.tolist(), keep_elite_frac, alpha, self.device,
                                   return_mean_elites=return_mean_elites, population_size_module=population_size_module, seed=seed)
-        K, keep = int(self._opt.elite_num), int(self._opt.keep_elite_size)
-        self._params = IcemParams(population_size=int(population_size), horizon=self.horizon, act_dim=A, num_iterations=int(num_iterations),
-                                  elite_num=K, keep_elite_size=keep, population_size_module=int(population_size_module or 0),
-                                  return_mean_elites=int(bool(return_mean_elites)), alpha=float(alpha),
-                                  population_decay_factor=float(population_decay_factor), colored_noise_exponent=float(colored_noise_exponent))
-        self.elite = torch.empty(self.n_env, K, self.horizon, A, device=self.device)
-        self.has_elite = False
-        self.seed, self.calls = int(seed), 0
-
-    def reset(self):
-        self.previous_solution = self.initial_solution.clone()  # the elites persist, like ICEMOptimizer.elite (Appendix B6)
+        self.elite = torch.empty(self.n_env, int(self._opt.elite_num), self.horizon, self.act_dim, device=self.device)
+        self.has_elite = False  # (the elites persist across reset(), like ICEMOptimizer.elite, Appendix B6)
 
     def plan(self, obs_batch: np.ndarray, keep_idx: Optional[torch.Tensor] = None, latent=None, belief=None, **_kwargs) -> np.ndarray:
-        if isinstance(self.eval_fn, PlaNetTrajectoryEvalFn):
-            latent0, belief0 = _planet_start_states(self.eval_fn, self.n_env, obs_batch, latent, belief)
-            self.calls += 1
-            best = self.engine.plan_planet_icem(self._params, self.previous_solution, self.lower, self.upper, self.elite, self.has_elite,
-                                                latent0, belief0, self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed,
-                                                plan_id=self.calls, keep_idx=keep_idx, n_env=self.n_env)
-        else:
-            obs_batch = np.asarray(obs_batch, dtype=np.float32)
-            assert obs_batch.shape[0] == self.n_env
-            o, iters = self._opt, self._params.num_iterations
-            sizes = []
-            for i in range(iters):
-                extra = 0
-                if self.has_elite or i > 0:
-                    extra = 1 if (i == iters - 1 and i != 0) else int(o.keep_elite_size)
-                sizes.append(o._iteration_size(i) + extra)
-            _prepare_fused(self.eval_fn, sizes)
-            self.calls += 1
-            best = self.engine.plan_icem(self._params, self.previous_solution, self.lower, self.upper, self.elite, self.has_elite, obs_batch,
-                                         self.eval_fn.num_particles, seed=self.seed ^ self.eval_fn.seed, plan_id=self.calls, keep_idx=keep_idx,
-                                         n_env=self.n_env)
-        iters = self._params.num_iterations
-        if iters > 0:
+        sizes, params = self._opt._fused_plan(self.horizon, self.act_dim, self.has_elite)
+        best = self._plan(self.engine.plan_icem, self.engine.plan_planet_icem, (params, self.previous_solution, self.lower, self.upper,
+                          self.elite, self.has_elite), obs_batch, latent, belief, sizes, keep_idx=keep_idx)
+        if params.num_iterations > 0:
             self.has_elite = True
-        self.previous_solution = best.roll(-self.replan_freq, dims=1)
-        self.previous_solution[:, -self.replan_freq:] = self.initial_solution[:, :1]
-        self.previous_solution = self.previous_solution.contiguous()
-        return best.cpu().numpy()
-
-    def act(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
-        return self.plan(obs_batch, latent=latent, belief=belief)[:, 0]
+        return self._shift(best)
 
 
 def complete_agent_cfg(env, agent_cfg):
