@@ -8,13 +8,21 @@ namespace hipets {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
-constexpr int kWave = 64;          // CDNA wavefront
-#ifndef HIPETS_WAVES
-#define HIPETS_WAVES 4
+// Build switches of the kernel experiments that were measured and settled: the arms they selected were
+// removed with them and are in the version history.  A build that still names one would silently produce the default kernel and
+// be measured under the variant's label: refuse it.
+#if defined(HIPETS_CROSS_LAYER_PREFETCH) || defined(HIPETS_BUFFER_LOADS) || defined(HIPETS_KSTEP_NOP) || defined(HIPETS_PHILOX_MAD64) ||     \
+    defined(HIPETS_SHARED_DRAWS) || defined(HIPETS_DMA_COLLECT) || defined(HIPETS_INPUT_BY_GROUP) || defined(HIPETS_INPUT_BATCHED) ||       \
+    defined(HIPETS_INPUT_BY_COLUMN) || defined(HIPETS_KSPLIT) || defined(HIPETS_KS_TRIPLE) || defined(HIPETS_INTERLEAVE) ||                 \
+    defined(HIPETS_UNROLL_K) || defined(HIPETS_WIDE_FUSE) || defined(HIPETS_FUSE_TAIL) || defined(HIPETS_MINWAVES_R1) ||                    \
+    defined(HIPETS_MINWAVES_R2) || defined(HIPETS_COLLECT_WIDE) || defined(HIPETS_COLLECT_OUT4) || defined(HIPETS_WAVES) ||                  \
+    defined(HIPETS_DBG_NOSTRAIGHT) || defined(HIPETS_DBG_NOMAGIC) || defined(HIPETS_XCD_ROT)
+#error "a retired HIPETS_* kernel build switch is defined: the switch was retired and its arm is in the version history (DESIGN.md section 8)"
 #endif
-constexpr int kWaves = HIPETS_WAVES;  // waves per workgroup: 4 = one per SIMD (measured best on cfg2: 1.27 ms/rollout);
-                                      // 8 = two per SIMD builds and passes parity but measured 1.31 ms (VALU phases
-                                      // are shared by the SIMD partners and the kernel is capped at 256 VGPRs)
+
+constexpr int kWave = 64;          // CDNA wavefront
+constexpr int kWaves = 4;          // waves per workgroup: one per SIMD (measured best on cfg2: 1.27 ms/rollout; two per SIMD
+                                   // measured 1.31 ms)
 constexpr int kThreads = kWaves * kWave;
 constexpr int kMaxExtras = 4;         // max leftover (column tile, row tile) units per wave
 constexpr int kTile = 16;          // rows / cols of one v_mfma_f32_16x16x4_f32 tile
@@ -33,17 +41,9 @@ __device__ __forceinline__ Philox4 philox4x32_10(uint32_t c0, uint32_t c1, uint3
         // one 32 x 32 -> 64 product each (v_mad_u64_u32: high and low half from ONE quarter-rate instruction; written as __umulhi and
         // `*` the compiler issued v_mul_hi_u32 AND v_mul_lo_u32 -- 40 quarter-rate multiplies per call instead of 20, and the 10 rounds
         // are half of a fused tail unit's VALU time)
-#ifndef HIPETS_PHILOX_MAD64
-#define HIPETS_PHILOX_MAD64 1
-#endif
-#if HIPETS_PHILOX_MAD64
         const uint64_t p0 = (uint64_t)0xD2511F53u * (uint64_t)c0, p1 = (uint64_t)0xCD9E8D57u * (uint64_t)c2;
         const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0;
         const uint32_t hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-#else
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-#endif
         const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
         c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
         k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;

@@ -201,8 +201,7 @@ int wave_units(int C, int R) {  // MFMA units per k-chunk of the busiest SIMD (w
     return std::max(std::max(simd[0], simd[1]), std::max(simd[2], simd[3]));
 }
 
-// `fast_instances`: price R by the instance set of the FAST form (launch.hpp lean_shape_exists), else by that of the step-synchronous form.
-int choose_R(const hipets_engine* e, long long tiles_total_per_slice, int slices, int forced, int horizon, bool wide, bool drift, bool fast_instances) {
+int choose_R(const hipets_engine* e, long long tiles_total_per_slice, int slices, int forced, int horizon, bool wide, bool drift) {
     if (forced > 0) return forced;
     const int C = e->md.hidC;
     // the fixed part scales with the layer width like the units do.  WIDE instances (Humanoid-v4: 47 output column tiles, one workgroup per
@@ -227,7 +226,7 @@ int choose_R(const hipets_engine* e, long long tiles_total_per_slice, int slices
         const double u_pair = (co == 2 && drift) ? (double)C * R / 4.0 : u;
         const long long full = n / co, rem = n % co;
         double cost = (double)full * (a + co * u_pair) + (rem ? a + (double)rem * u : 0.0);
-        if (!lean_shape_exists(e->md, R, fast_instances)) cost *= 1.08;
+        if (!lean_shape_exists(e->md, R)) cost *= 1.08;
         if (cost < best_cost - 1e-9) {
             best_cost = cost;
             best = R;
@@ -269,11 +268,9 @@ int rollout_geometry(const hipets_engine* e, int mode, long long B, int rows_per
         return fail("this call runs the general kernel layout (injected eps / traces / generic_kernel) on a model whose default geometry is "
                     "the wide-output instance's: size member_schedule with hipets_fast_geometry(rows_per_group = -1) and pass its row-tile "
                     "count as opts->rows_per_group");
-    // Only a whole-horizon launch of more than one step drifts apart.  The same flag picks the instance set R is priced by, so a FAST
-    // rollout with H = 1 is priced against the step-synchronous set although it runs (and hipets_kernel_class classifies it by) the FAST
-    // one.  The two sets agree today (launch.hpp HIPETS_LEAN_FAST_SHAPES_* are empty).
+    // Only a whole-horizon launch of more than one step drifts apart.
     const bool drift = g->whole_horizon && H > 1;
-    g->R = choose_R(e, g->tiles, g->domains, rows_per_group, H, g->wide, drift, drift);
+    g->R = choose_R(e, g->tiles, g->domains, rows_per_group, H, g->wide, drift);
     g->lds = lds_for(e, g->R, H, g->wide);
     if (g->lds > e->lds_max) return fail("rows_per_group %d does not fit LDS", g->R);
     g->groups = (int)((g->tiles + g->R - 1) / g->R);
@@ -780,7 +777,7 @@ int hipets_kernel_class(hipets_engine* e, int32_t pop, int32_t P, int32_t horizo
         cls = HIPETS_KERNEL_FUSED;
     } else if (g.wide) {
         cls = HIPETS_KERNEL_WIDE;
-    } else if (call_lean && !wide_model(md) && lean_shape_exists(md, g.R, g.whole_horizon)) {
+    } else if (call_lean && !wide_model(md) && lean_shape_exists(md, g.R)) {
         cls = HIPETS_KERNEL_FUSED;
     } else {
 #define HIPETS_CLASS_HID(HC) if (hid_static_call(md, probe, HC)) cls = HIPETS_KERNEL_HIDDEN_STATIC;

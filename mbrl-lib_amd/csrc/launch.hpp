@@ -60,12 +60,8 @@ inline bool hid_static_call(const ModelDev& md, const RolloutArgs& ra, const int
     X(13, 3, HIPETS_REW_HALFCHEETAH, HIPETS_TERM_NONE, HIPETS_OBS_HALFCHEETAH) X(13, 1, HIPETS_REW_CARTPOLE_PETS, HIPETS_TERM_NONE, HIPETS_OBS_CARTPOLE_PETS) \
     X(13, 1, HIPETS_REW_LEARNED, HIPETS_TERM_INVERTED_PENDULUM, HIPETS_OBS_NONE)
 #define HIPETS_LEAN_SHAPES_R4(X) X(13, 6, HIPETS_REW_HALFCHEETAH, HIPETS_TERM_HUMANOID, HIPETS_OBS_NONE)
-// Shapes with FAST instances ONLY: none since round 5 (pets_hopper -- a termination function over every state dim of a model wider
-// than one column tile: obs 11 / act 3, learned reward, pop 350 x 20 -- was one until its DEVICE-mode instances existed: the tables above)
-#define HIPETS_LEAN_FAST_SHAPES_R1(X)
-#define HIPETS_LEAN_FAST_SHAPES_R2(X)
-#define HIPETS_LEAN_FAST_SHAPES_R3(X)
-#define HIPETS_LEAN_FAST_SHAPES_R4(X)
+// (every shape of these tables is instantiated in both launch modes: the FAST instances -- rollout_r<R>_fast.hip -- and the
+// step-synchronous ones cover the same shapes)
 
 // bf16x3 precision instances per R: X(hidden column tiles, output column tiles, reward fn, termination fn); no obs preprocessing
 // (round 6: the R = 1 instances -- cfg1, and a rank's shard of a strong-scaled cfg2 plan, in an arithmetic mode that is reported
@@ -88,6 +84,15 @@ inline bool fused_term_ok(const ModelDev& md) {
     return true;
 }
 
+// does the model have the shape of the lean fp32 instance X(hc, oc, rw, tm, ob) of the tables above (the LDS row stride included)?
+inline bool lean_shape_is(const ModelDev& md, const int hc, const int oc, const int rw, const int tm, const int ob) {
+    return md.hidC == hc && md.outC == oc && md.reward_fn == rw && md.term_fn == tm && md.obs_process == ob && md.ld == lean_ld(hc, oc);
+}
+// ... and of the bf16x3 instance X(hc, oc, rw, tm)
+inline bool b3_shape_is(const ModelDev& md, const int hc, const int oc, const int rw, const int tm) {
+    return md.hidC == hc && md.outC == oc && md.reward_fn == rw && md.term_fn == tm && md.obs_process == HIPETS_OBS_NONE;
+}
+
 // the model-side facts every lean fp32 instance shares (the call-side ones: lean_call below)
 inline bool lean_model(const ModelDev& md) {
     return md.precision == HIPETS_PREC_F32 && md.activation == HIPETS_ACT_SILU && md.normalizer == HIPETS_NORM_F64 && !md.deterministic &&
@@ -96,22 +101,15 @@ inline bool lean_model(const ModelDev& md) {
 
 // is there a lean fp32 instance of this model's shape for R row tiles? (what the launcher of rollout_r<R>.hip will find; the cost
 // model prices a (shape, R) pair with an instance lower than one that runs the hidden-static or the generic kernel)
-inline bool lean_shape_exists(const ModelDev& md, const int R, const bool fast = false) {
+inline bool lean_shape_exists(const ModelDev& md, const int R) {
     if (!lean_model(md)) return false;
 #define HIPETS_HAS_SHAPE(HC, OC, RW, TM, OB) \
-    if (md.hidC == HC && md.outC == OC && md.reward_fn == RW && md.term_fn == TM && md.obs_process == OB && md.ld == lean_ld(HC, OC)) return true;
+    if (lean_shape_is(md, HC, OC, RW, TM, OB)) return true;
     switch (R) {
         case 1: HIPETS_LEAN_SHAPES_R1(HIPETS_HAS_SHAPE) break;
         case 2: HIPETS_LEAN_SHAPES_R2(HIPETS_HAS_SHAPE) break;
         case 3: HIPETS_LEAN_SHAPES_R3(HIPETS_HAS_SHAPE) break;
         case 4: HIPETS_LEAN_SHAPES_R4(HIPETS_HAS_SHAPE) break;
-        default: break;
-    }
-    if (fast) switch (R) {
-        case 1: HIPETS_LEAN_FAST_SHAPES_R1(HIPETS_HAS_SHAPE) break;
-        case 2: HIPETS_LEAN_FAST_SHAPES_R2(HIPETS_HAS_SHAPE) break;
-        case 3: HIPETS_LEAN_FAST_SHAPES_R3(HIPETS_HAS_SHAPE) break;
-        case 4: HIPETS_LEAN_FAST_SHAPES_R4(HIPETS_HAS_SHAPE) break;
         default: break;
     }
 #undef HIPETS_HAS_SHAPE
@@ -121,7 +119,7 @@ inline bool lean_shape_exists(const ModelDev& md, const int R, const bool fast =
 // ... and the same question for the bf16x3 instances (rollout_inst.inc's HIPETS_TRY_B3)
 inline bool b3_shape_exists(const ModelDev& md, const int R) {
 #define HIPETS_HAS_B3(HC, OC, RW, TM) \
-    if (md.hidC == HC && md.outC == OC && md.reward_fn == RW && md.term_fn == TM && md.obs_process == HIPETS_OBS_NONE) return true;
+    if (b3_shape_is(md, HC, OC, RW, TM)) return true;
     switch (R) {
         case 1: HIPETS_B3_SHAPES_R1(HIPETS_HAS_B3) break;
         case 2: HIPETS_B3_SHAPES_R2(HIPETS_HAS_B3) break;
@@ -146,15 +144,13 @@ inline bool lean_call(const ModelDev& md, const RolloutArgs& ra) {
 
 // is the model one of the WIDE shapes (fp32 arithmetic, the row strides the instance was compiled for)?
 inline bool wide_model(const ModelDev& md) {
-#if HIPETS_WIDE_FUSE
     if (md.precision != HIPETS_PREC_F32 || md.activation != HIPETS_ACT_SILU || md.normalizer != HIPETS_NORM_F64 || md.obs_process != HIPETS_OBS_NONE ||
         md.deterministic || md.propagation == HIPETS_PROP_EXPECTATION || md.lv_rows != 1)
         return false;  // (the model-side conditions of lean_call)
 #define HIPETS_IS_WIDE(HC, OC, RW, TM) \
-    if (md.hidC == HC && md.outC == OC && md.reward_fn == RW && md.term_fn == TM && md.ld == lean_ld(HC, OC) && md.ld_in > 0) return true;
+    if (lean_shape_is(md, HC, OC, RW, TM, HIPETS_OBS_NONE) && md.ld_in > 0) return true;
     HIPETS_WIDE_SHAPES(HIPETS_IS_WIDE)
 #undef HIPETS_IS_WIDE
-#endif
     return false;
 }
 

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void planet_rollout_kernel(const PlanetDe
                 // one shape-specialised instantiation per DISTINCT (column tiles, k chunks) pair: six for the eight ops
                 using PS = PlanetConfShape;
                 auto run = [&](auto cs, auto kcs) __attribute__((always_inline)) {
-                    linear_op<1, HIPETS_ACT_RELU, decltype(cs)::value, false, NoTail, PS::LD, false, decltype(kcs)::value, 4>(
+                    linear_op<1, HIPETS_ACT_RELU, decltype(cs)::value, NoTail, PS::LD, false, decltype(kcs)::value, 4>(
                         pd.w + op.lm.woff, pd.b + op.lm.boff, op.lm, PS::LD, op.relu != 0, HIPETS_ACT_RELU, 0.f, rows + op.in_off, rows + op.out_off, wave, lane, prof);
                 };
                 using std::integral_constant;

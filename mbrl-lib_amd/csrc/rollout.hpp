@@ -190,24 +190,6 @@ struct GemmFrags {
     f32x4 ax[EX > 0 ? EX : 1];
 };
 
-// Cross-layer prefetch (shape-specialised kernels): a wave's chunk-0 weight fragments and biases of the NEXT linear op are
-// requested from L2 right after the current op's k loop, so that their ~800-cycle latency passes behind the epilogue
-// (activation, LDS stores), the layer barrier and the next op's address set-up instead of stalling the first MFMA.
-constexpr int kPreCT = 3;  // >= the column tiles a wave carries through one wave_gemm (kMaxCT in linear_op)
-struct Pre {
-    f32x4 b[kPreCT], bx[kMaxExtras];    // chunk-0 weight fragments of the strided / extra units
-    f32x4 bv[kPreCT], bvx[kMaxExtras];  // their biases
-};
-struct NextOp {  // this wave's share of the op to prefetch for (wave-uniform)
-    const float* W;
-    const float* bias;
-    int KC, c_first, ct, ex_n;  // ct strided column tiles from c_first, ex_n extra units
-    int tail_steps;             // LayerMeta::tail_steps of the op
-    Extras ex;
-    bool valid;
-};
-// workgroup barrier for data exchanged through LDS only: waits for this wave's LDS traffic, NOT for global loads in flight
-// (__syncthreads() also drains vmcnt, which would expose the latency of the prefetched weight fragments at every barrier)
 // 16-byte write-through store / load of a PAIR of hand-over granules {value, tag, value, tag} (persistent DEVICE form).  sc1 =
 // device scope: the store leaves the XCD's L2, the load never returns a stale L1 line (MI355X_MICROARCH.md: 8-byte sc1 stores
 // cost 2.7x the 16-byte ones per byte, and a workgroup's polls queue behind its own stores).  The load is asynchronous:
@@ -225,6 +207,8 @@ __device__ __forceinline__ void pair_store(unsigned long long* p, const unsigned
 __device__ __forceinline__ void pair_load_issue(u32x4g& d, const unsigned long long* p) {
     asm volatile("global_load_dwordx4 %0, %1, off sc1" : "=&v"(d) : "v"(p) : "memory");
 }
+// workgroup barrier for data exchanged through LDS only: waits for this wave's LDS traffic, NOT for global memory operations in flight
+// (__syncthreads() also drains vmcnt)
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 // LDS-DMA of 64 hand-over pairs (one per lane, device-scope loads like pair_load_issue) straight into LDS: lane l's 16 bytes land at
 // LDS byte address lds_dst + 16 l (lds_dst wave-uniform), no destination registers.  Counted on vmcnt; the compiler does not know
@@ -236,34 +220,10 @@ __device__ __forceinline__ void pair_dma_issue(const unsigned long long* gsrc, c
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 __device__ __forceinline__ void vmem_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void prefetch_issue(const NextOp& n, const int lane, Pre& pre) {
-    if (!n.valid) return;
-    const char* Wb = reinterpret_cast<const char*>(n.W);
-    const int exc[kMaxExtras] = {n.ex.c0, n.ex.c1, n.ex.c2, n.ex.c3};
-#pragma unroll
-    for (int ct = 0; ct < kPreCT; ++ct)
-        if (ct < n.ct) {
-            pre.b[ct] = *reinterpret_cast<const f32x4*>(Wb + (size_t)(unsigned)(((n.c_first + kWaves * ct) * n.KC * 64 + lane) * 16));
-            pre.bv[ct] = *reinterpret_cast<const f32x4*>(n.bias + (n.c_first + kWaves * ct) * 16 + 4 * (lane >> 4));
-        }
-#pragma unroll
-    for (int e = 0; e < kMaxExtras; ++e)
-        if (e < n.ex_n) {
-            pre.bx[e] = *reinterpret_cast<const f32x4*>(Wb + (size_t)(unsigned)((exc[e] * n.KC * 64 + lane) * 16));
-            pre.bvx[e] = *reinterpret_cast<const f32x4*>(n.bias + exc[e] * 16 + 4 * (lane >> 4));
-        }
-    __builtin_amdgcn_sched_barrier(0);  // keep the requests HERE (the scheduler would sink them to their first use)
-}
 
 // Minimum waves per SIMD the register allocation must leave room for (= workgroups of 4 waves per CU).  R <= 2 keeps two
 // workgroups per CU resident (their barrier / latency phases overlap); R = 3, 4 need the registers.
-#ifndef HIPETS_MINWAVES_R1
-#define HIPETS_MINWAVES_R1 2
-#endif
-#ifndef HIPETS_MINWAVES_R2
-#define HIPETS_MINWAVES_R2 2
-#endif
-template <int R> struct MinWavesOf { static constexpr int value = R == 1 ? HIPETS_MINWAVES_R1 : (R == 2 ? HIPETS_MINWAVES_R2 : 1); };
+template <int R> struct MinWavesOf { static constexpr int value = R <= 2 ? 2 : 1; };
 
 // Debug build (__graft_entry__.build_debug: -O1 -g -DHIPETS_DEBUG_BOUNDS=1, host side under AddressSanitizer): every LDS section of
 // the rollout kernel is checked against the dynamic LDS size of the launch, and the indexed LDS accesses of the elementwise phases
@@ -309,36 +269,16 @@ template <class P, class D, class F, class G>
 __device__ __forceinline__ TailStages<P, D, F, G> make_tail(P p, D d, F f, G g) { return TailStages<P, D, F, G>{p, d, f, g}; }
 
 // ACT >= 0: the activation is a compile-time fact (one epilogue in the code); ACT < 0: `act` selects it at run time.
-// PRE: chunk 0's weight fragments and the biases are already in `pre` (prefetch_issue by the previous op); after the k loop
-// the next op's are requested into `pre` again (`nxt`).
 // TL != NoTail: instead of the epilogue every finished accumulator is handed to (*tl)(acc, column tile, row tile) -- the fused
 // per-step tail of the output layer (KSpec::FUSE: sampling, next state, reward, next input straight from the registers).
 // LD > 0: the LDS row stride is a compile-time fact (shape-specialised instances): the A-fragment reads of the R row tiles become
 // ONE base register + immediate offsets (ds_read_b128 ... offset:r * 16 * LD * 4), no per-row address arithmetic in the k loop.
-#ifndef HIPETS_BUFFER_LOADS
-#define HIPETS_BUFFER_LOADS 1  // weight fragments through buffer_load ... s_off offen: the chunk offset rides in an SGPR
-#endif
-#ifndef HIPETS_KSTEP_NOP
-#define HIPETS_KSTEP_NOP 1  // s_nop 1 in front of every k-step (hazard guard, see kstep below)
-#endif
 // SPL: every unit sums its even and its odd k-steps in two accumulators and adds them at the end -- the order a wave whose whole
 // share is ONE unit uses anyway (hazard (2) below).  The OUTPUT layer runs with SPL in every instance: its columns are dealt to
 // the waves differently by the natural and the head-pair packs, and with SPL a column's sum does not depend on whether its wave
 // holds one unit or several -- shape-specialised and generic instances keep returning the same bits.
 // KCS > 0: the number of k chunks is a compile-time fact (ops whose K is the hidden width of a shape-specialised instance): the
 // k loop is fully unrolled -- straight-line code, no loop control, no accumulator copies where blocks meet.
-#ifndef HIPETS_UNROLL_K
-#define HIPETS_UNROLL_K 1
-#endif
-#ifndef HIPETS_INTERLEAVE
-#define HIPETS_INTERLEAVE 1  // the next chunk's fragment loads inside the MFMAs' shadows (compute_il in wave_gemm)
-#endif
-#ifndef HIPETS_SHARED_DRAWS
-#define HIPETS_SHARED_DRAWS 1  // fused tail: one Philox block per lane and PAIR of units (rollout_kernel tail_draw); 0 = every lane computes the whole block of every unit (A/B measurements)
-#endif
-#ifndef HIPETS_KS_TRIPLE
-#define HIPETS_KS_TRIPLE 1  // k-split (one-tile) instances: fragments fetched TWO chunks ahead (three register sets, wave_gemm kTriple)
-#endif
 // x * rcp(1 + exp2(-x log2 e)) on the 4 accumulator values of a lane: the two multiplies and the add as packed 2 x f32 ops
 __device__ __forceinline__ f32x4 silu4(const f32x4 a) {
     using f32x2 = __attribute__((ext_vector_type(2))) float;
@@ -377,17 +317,16 @@ struct KsArgs {
 
 // KS bit 0 (KSI): the input image's last k chunk is NOT in LDS -- it is rebuilt from ks->part_in; bit 1 (KSO): see above;
 // bit 2: no k-split, only the one-tile k loop that fetches two chunks ahead (kTriple: ops with a static chunk count, planet.hpp)
-template <int R, int CT, int EX, int ACT, bool PRE = false, class TL = NoTail, int LD = -1, bool SPL = false, int KCS = -1, int KS = 0>
+template <int R, int CT, int EX, int ACT, class TL = NoTail, int LD = -1, bool SPL = false, int KCS = -1, int KS = 0>
 __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* __restrict__ out, const int ld_rt,
                                           const float* __restrict__ W, const float* __restrict__ bias, const int KC_rt,
                                           const int tail_steps, const int c_first, const Extras ex,
                                           const bool apply_act, const int act, const float slope, const int lane,
-                                          Prof& prof, Pre* pre = nullptr, const NextOp* nxt = nullptr, const TL* tl = nullptr,
-                                          const int ldi_rt = 0, const KsArgs* ks = nullptr) {
+                                          Prof& prof, const TL* tl = nullptr, const int ldi_rt = 0, const KsArgs* ks = nullptr) {
     constexpr int CTn = CT > 0 ? CT : 1;
     constexpr int EXn = EX > 0 ? EX : 1;
     constexpr bool KSI = (KS & 1) != 0, KSO = (KS & 2) != 0;
-    static_assert(!KS || (R == 1 && LD > 0 && !PRE && HIPETS_BUFFER_LOADS), "k-split: one-tile shape-specialised instances, rolled k loop");
+    static_assert(!KS || (R == 1 && LD > 0), "k-split: one-tile shape-specialised instances, rolled k loop");
     static_assert(!KSO || (std::is_same<TL, NoTail>::value && EX == 0 && !SPL), "k-split producer: a hidden op");
     f32x4 acc[CTn][R];
     f32x4 accx[EXn];
@@ -409,22 +348,13 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
         wxoff[e] = (unsigned)((exc[e] * KC * 64 + lane) * 16);
         axoff[e] = exr[e] * 16 * ldi;
     }
-    const char* Wb = reinterpret_cast<const char*>(W);
     const float* ap = in + (lane & 15) * ldi + 4 * (lane >> 4);
     // biases of this lane's columns: loaded before the k loop so their latency hides behind it
     f32x4 bv[CTn], bvx[EXn];
-    if constexpr (PRE) {
 #pragma unroll
-        for (int ct = 0; ct < CT; ++ct) bv[ct] = pre->bv[ct];
+    for (int ct = 0; ct < CT; ++ct) bv[ct] = *reinterpret_cast<const f32x4*>(bias + (c_first + kWaves * ct) * 16 + 4 * (lane >> 4));
 #pragma unroll
-        for (int e = 0; e < EX; ++e) bvx[e] = pre->bvx[e];
-    } else {
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) bv[ct] = *reinterpret_cast<const f32x4*>(bias + (c_first + kWaves * ct) * 16 + 4 * (lane >> 4));
-#pragma unroll
-        for (int e = 0; e < EX; ++e) bvx[e] = *reinterpret_cast<const f32x4*>(bias + exc[e] * 16 + 4 * (lane >> 4));
-    }
-#if HIPETS_BUFFER_LOADS
+    for (int e = 0; e < EX; ++e) bvx[e] = *reinterpret_cast<const f32x4*>(bias + exc[e] * 16 + 4 * (lane >> 4));
     // The weight block of this op as a raw buffer (base = W, wave-uniform): a fragment load is buffer_load_dwordx4 v, v_off, s[rsrc],
     // s_chunk offen -- the loop-invariant per-lane offset in a VGPR, the chunk offset (kk KiB) in an SGPR, NO address VALU work in
     // the k loop (fp32 MFMAs and VALU instructions exclude each other on a SIMD: every v_lshl_add_u64 there is MFMA-pipe idle time)
@@ -440,20 +370,11 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
         __builtin_memcpy(&r, &v, 16);
         return r;
     };
-#endif
     auto load = [&](GemmFrags<R, CT, EX>& f, const int kk) __attribute__((always_inline)) {
-#if HIPETS_BUFFER_LOADS
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) f.b[ct] = wload(woff[ct], kk);
 #pragma unroll
         for (int e = 0; e < EX; ++e) f.bx[e] = wload(wxoff[e], kk);
-#else
-        const char* Wk = Wb + (size_t)kk * 1024;
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) f.b[ct] = *reinterpret_cast<const f32x4*>(Wk + woff[ct]);
-#pragma unroll
-        for (int e = 0; e < EX; ++e) f.bx[e] = *reinterpret_cast<const f32x4*>(Wk + wxoff[e]);
-#endif
 #pragma unroll
         for (int r = 0; r < R; ++r) f.a[r] = *reinterpret_cast<const f32x4*>(ap + r * 16 * ldi + kk * 16);
 #pragma unroll
@@ -474,11 +395,7 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
 #pragma unroll
     for (int e = 0; e < EXn; ++e) accxo[e] = f32x4{0.f, 0.f, 0.f, 0.f};
     auto kstep = [&](const GemmFrags<R, CT, EX>& f, const int s) __attribute__((always_inline)) {
-#if HIPETS_KSTEP_NOP
         asm volatile("s_nop 1");
-#else
-        if (s == 0) asm volatile("s_nop 1");  // experiment: the guard once per chunk (after the fragment loads' register writes) only
-#endif
         if constexpr (kSplit) {
             f32x4& dst = (s & 1) ? acc_odd : (CT ? acc[0][0] : accx[0]);
             if constexpr (CT) mfma16x16x4(f.b[0][s], f.a[0][s], dst);
@@ -503,27 +420,22 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
 #pragma unroll
         for (int s = 0; s < 4; ++s) kstep(f, s);
     };
-    // Interleaved form of "load the next chunk, then compute this one" (HIPETS_INTERLEAVE): the kNL fragment loads of chunk
+    // Interleaved form of "load the next chunk, then compute this one": the kNL fragment loads of chunk
     // kk_next are issued ONE AT A TIME, evenly spread behind the MFMAs of the current chunk, instead of as a clump in front of it.
     // Measured stand-alone (profiles/microbench/kloop_probe.hip, this wave's 3 x 3 + 1 tiling, 220 workgroups): a VMEM / LDS
     // instruction issued while no MFMA is executing costs ~12 cycles of matrix-pipe idle time (8 per 40 MFMAs: 34.46 cycles per
     // MFMA); issued inside an MFMA's 32-cycle shadow it is free (32.98).  Weight fragments first: they have the L2 round trip
     // ahead of them and are needed >= 30 MFMAs (~1 000 cycles) later; the LDS fragments follow in the order the next chunk's first
     // MFMAs consume them.  sched_barrier(0) on both sides pins each load where it is written.
-    constexpr bool kIL = HIPETS_INTERLEAVE && LD > 0;  // shape-specialised instances only: in the generic ones (every shape x activation in
-                                                        // one kernel, at the 256-VGPR limit) the longer live ranges spill 16-20 VGPRs to scratch
+    constexpr bool kIL = LD > 0;  // shape-specialised instances only: in the generic ones (every shape x activation in one kernel, at the
+                                  // 256-VGPR limit) the longer live ranges spill 16-20 VGPRs to scratch
     constexpr int kNU = CT * R + EX;                              // MFMA units of this wave
     constexpr int kNL = CT + EX + (CT > 0 ? R : 0) + EX;          // fragment loads per chunk
     static_assert(4 * kNU >= kNL + 1, "every load needs its own slot behind an MFMA");
     auto load_one = [&](GemmFrags<R, CT, EX>& g, const int kk, const int i) __attribute__((always_inline)) {
         __builtin_amdgcn_sched_barrier(0);
-#if HIPETS_BUFFER_LOADS
         if (i < CT) g.b[i < CT ? i : 0] = wload(woff[i < CT ? i : 0], kk);
         else if (i < CT + EX) g.bx[i - CT] = wload(wxoff[i - CT], kk);
-#else
-        if (i < CT) g.b[i < CT ? i : 0] = *reinterpret_cast<const f32x4*>(Wb + (size_t)kk * 1024 + woff[i < CT ? i : 0]);
-        else if (i < CT + EX) g.bx[i - CT] = *reinterpret_cast<const f32x4*>(Wb + (size_t)kk * 1024 + wxoff[i - CT]);
-#endif
         else if (CT > 0 && i < CT + EX + R) g.a[i - CT - EX] = *reinterpret_cast<const f32x4*>(ap + (i - CT - EX) * 16 * ldi + kk * 16);
         else {
             const int e = i - CT - EX - (CT > 0 ? R : 0);
@@ -626,23 +538,12 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
         }
     }
     GemmFrags<R, CT, EX> f0, f1;
-    if constexpr (PRE) {  // chunk 0: weights are in registers already, only the activation fragments come from LDS
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) f0.b[ct] = pre->b[ct];
-#pragma unroll
-        for (int e = 0; e < EX; ++e) f0.bx[e] = pre->bx[e];
-#pragma unroll
-        for (int r = 0; r < R; ++r) f0.a[r] = *reinterpret_cast<const f32x4*>(ap + r * 16 * ldi);
-#pragma unroll
-        for (int e = 0; e < EX; ++e) f0.ax[e] = *reinterpret_cast<const f32x4*>(ap + axoff[e]);
-    } else {
-        load(f0, 0);
-    }
+    load(f0, 0);
     // One-tile k-split instances fetch TWO chunks ahead (kTriple below): a wave's 12 MFMAs per chunk (384 cycles) are no cover for an
     // L2 round trip issued somewhere inside the previous chunk
     // (ops whose chunk count is a compile-time fact -- KCS: everything fed by a hidden layer -- so that the loop's remainder is no run-time
     // branch: the allocator copies accumulators where such arms begin and sinks the copies to just in front of their first MFMA)
-    constexpr bool kTriple = HIPETS_KS_TRIPLE && KS != 0 && KCS > 0 && HIPETS_INTERLEAVE && LD > 0;
+    constexpr bool kTriple = KS != 0 && KCS > 0 && LD > 0;
     static_assert(!KS || KCS <= 0 || kTriple, "k-split ops with a static chunk count run the three-set loop");
     if constexpr (kTriple) load(f1, KCS > 1 ? 1 : 0);
     // accumulators start at the bias (C input of the first MFMA) instead of zero: no add in the epilogue.  Initialised AFTER
@@ -857,7 +758,6 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
     mfma_drain();
     __builtin_amdgcn_sched_barrier(0);
     prof.mark(11);
-    if constexpr (PRE) prefetch_issue(*nxt, lane, *pre);
     if constexpr (!std::is_same<TL, NoTail>::value) {
         // (constant trip counts on both levels: every slot / accumulator index must be a constant after unrolling)
 #pragma unroll
@@ -951,14 +851,14 @@ __device__ __forceinline__ void wave_gemm_ex(int nex, const float* in, float* ou
     constexpr int kMaxEx = (3 * R + kWaves - 1) / kWaves;
     switch (nex) {
         case 0:
-            if constexpr (CT > 0) wave_gemm<R, CT, 0, ACT, false, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof);
+            if constexpr (CT > 0) wave_gemm<R, CT, 0, ACT, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof);
             break;
-        case 1: wave_gemm<R, CT, 1, ACT, false, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof); break;
+        case 1: wave_gemm<R, CT, 1, ACT, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof); break;
         case 2:
-            if constexpr (kMaxEx >= 2) wave_gemm<R, CT, 2, ACT, false, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof);
+            if constexpr (kMaxEx >= 2) wave_gemm<R, CT, 2, ACT, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof);
             break;
         default:
-            if constexpr (kMaxEx >= 3) wave_gemm<R, CT, 3, ACT, false, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof);
+            if constexpr (kMaxEx >= 3) wave_gemm<R, CT, 3, ACT, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof);
             break;
     }
 }
@@ -969,11 +869,11 @@ __device__ __forceinline__ void wave_gemm_ex(int nex, const float* in, float* ou
 // from it and the wave index through ONE branch, and only the two wave_gemm instances the shape needs are compiled;
 // CS < 0: it is read from the layer table and dispatched through the (full, nex) switches.
 // KS (shape-specialised ops of one-tile workgroups): wave_gemm's k-split bits; part_in / part_out: the partial-sum buffers (KsArgs)
-template <int R, int ACT = -1, int CS = -1, bool PRE = false, class TL = NoTail, int LD = -1, bool SPL = false, int KCS = -1, int KS = 0>
+template <int R, int ACT = -1, int CS = -1, class TL = NoTail, int LD = -1, bool SPL = false, int KCS = -1, int KS = 0>
 __device__ __forceinline__ void linear_op(const float* W, const float* bias, const LayerMeta lm, const int ld, const bool apply_act,
                                           const int activation, const float slope, const float* in, float* out, const int wave,
-                                          const int lane, Prof& prof, Pre* pre = nullptr, const NextOp* nxt = nullptr, const TL* tl = nullptr,
-                                          const int ldi = 0, const float* part_in = nullptr, float* part_out = nullptr) {
+                                          const int lane, Prof& prof, const TL* tl = nullptr, const int ldi = 0,
+                                          const float* part_in = nullptr, float* part_out = nullptr) {
     static_assert(std::is_same<TL, NoTail>::value || CS >= 0, "a fused tail needs a shape-specialised op");
     static_assert(!KS || CS >= 0, "k-split needs a shape-specialised op");
     const int KC = lm.Kp / kKChunk;
@@ -986,8 +886,8 @@ __device__ __forceinline__ void linear_op(const float* W, const float* bias, con
         ks.n = ((wave + 1) * KC) / kWaves - ks.k0;
         Extras ex0;
         ex0.c0 = ex0.c1 = ex0.c2 = ex0.c3 = 0; ex0.r0 = ex0.r1 = ex0.r2 = ex0.r3 = 0;
-        wave_gemm<R, CS / kWaves, 0, ACT, false, NoTail, LD, false, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, wave, ex0, apply_act, activation, slope, lane, prof,
-                                                                            nullptr, nullptr, nullptr, ldi, &ks);
+        wave_gemm<R, CS / kWaves, 0, ACT, NoTail, LD, false, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, wave, ex0, apply_act, activation, slope, lane, prof,
+                                                                     nullptr, ldi, &ks);
     } else {
     KsArgs ks;  // (KS == 1: a consumer only -- the output layer)
     ks.part_in = part_in; ks.part_out = nullptr; ks.tile = 0; ks.k0 = 0; ks.n = 0; ks.wave = wave;
@@ -1006,27 +906,24 @@ __device__ __forceinline__ void linear_op(const float* W, const float* bias, con
         if constexpr (std::is_same<TL, NoTail>::value) {
 #pragma unroll
             for (int p = 0; p < passes; ++p)
-                wave_gemm<R, kMaxCT, 0, ACT, false, TL, LD, SPL, KCS, (KS & 4)>(in, out, ld, W, bias, KC, lm.tail_steps, wave + kWaves * kMaxCT * p, ex, apply_act, activation, slope, lane, prof, nullptr, nullptr, tl, ldi);
+                wave_gemm<R, kMaxCT, 0, ACT, TL, LD, SPL, KCS, (KS & 4)>(in, out, ld, W, bias, KC, lm.tail_steps, wave + kWaves * kMaxCT * p, ex, apply_act, activation, slope, lane, prof, tl, ldi);
         } else {  // with a fused tail inlined per unit the body is large: ONE copy, a real loop over the passes
 #pragma nounroll
             for (int p = 0; p < passes; ++p)
-                wave_gemm<R, kMaxCT, 0, ACT, false, TL, LD, SPL, KCS, (KS & 4)>(in, out, ld, W, bias, KC, lm.tail_steps, wave + kWaves * kMaxCT * p, ex, apply_act, activation, slope, lane, prof, nullptr, nullptr, tl, ldi);
+                wave_gemm<R, kMaxCT, 0, ACT, TL, LD, SPL, KCS, (KS & 4)>(in, out, ld, W, bias, KC, lm.tail_steps, wave + kWaves * kMaxCT * p, ex, apply_act, activation, slope, lane, prof, tl, ldi);
         }
         const int c_first = wave + kWaves * kMaxCT * passes;
         // the nu leftover units are dealt round-robin: waves below nu % kWaves hold one more than the others
         constexpr int lo = nu / kWaves, hi = (nu + kWaves - 1) / kWaves;
-        static_assert(!PRE || passes == 0, "cross-layer prefetch needs the op to fit one wave_gemm per wave");
         if constexpr (lo == hi) {
             if constexpr (last > 0 || lo > 0)
-                wave_gemm<R, last, lo, ACT, PRE, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, pre, nxt, tl, ldi, &ks);
-            else if constexpr (PRE) prefetch_issue(*nxt, lane, *pre);  // nothing to compute here: still fetch for the next op
+                wave_gemm<R, last, lo, ACT, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks);
         } else {
             if (wave < nu % kWaves) {
-                wave_gemm<R, last, hi, ACT, PRE, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, pre, nxt, tl, ldi, &ks);
+                wave_gemm<R, last, hi, ACT, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks);
             } else {
                 if constexpr (last > 0 || lo > 0)
-                    wave_gemm<R, last, lo, ACT, PRE, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, pre, nxt, tl, ldi, &ks);
-                else if constexpr (PRE) prefetch_issue(*nxt, lane, *pre);
+                    wave_gemm<R, last, lo, ACT, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks);
             }
         }
     } else {
@@ -1042,7 +939,7 @@ __device__ __forceinline__ void linear_op(const float* W, const float* bias, con
         const int nex = wave < nu ? (nu - wave + kWaves - 1) / kWaves : 0;  // <= kMaxExtras since rem < kWaves, R <= 4
         int done = 0;
         while (full - done > kMaxCT) {
-            wave_gemm<R, kMaxCT, 0, ACT, false, NoTail, -1, SPL>(in, out, ld, W, bias, KC, lm.tail_steps, wave + kWaves * done, ex, apply_act, activation, slope, lane, prof);
+            wave_gemm<R, kMaxCT, 0, ACT, NoTail, -1, SPL>(in, out, ld, W, bias, KC, lm.tail_steps, wave + kWaves * done, ex, apply_act, activation, slope, lane, prof);
             done += kMaxCT;
         }
         const int c_first = wave + kWaves * done;
@@ -1307,10 +1204,7 @@ struct KSpec {
     // exists at all, so the two activation buffers hold hidden activations only (row stride for HIDC tiles) and the model-input
     // image -- wider than a hidden layer there: 393 columns -- lives in buf0 with its own run-time stride (ModelDev::ld_in).
     // 4.4 KB of LDS per row instead of 7.6: two row tiles per workgroup fit where one did.
-#ifndef HIPETS_WIDE_FUSE
-#define HIPETS_WIDE_FUSE 1
-#endif
-    static constexpr bool WIDE = HIPETS_WIDE_FUSE && FUSE_ != 0 && HIDC_ >= 0 && PREC_ == HIPETS_PREC_F32 && OUTC_ > kSplMaxTiles;
+    static constexpr bool WIDE = FUSE_ != 0 && HIDC_ >= 0 && PREC_ == HIPETS_PREC_F32 && OUTC_ > kSplMaxTiles;
     static constexpr int LD = (HIDC_ >= 0 && PREC_ == HIPETS_PREC_F32) ? lean_ld(HIDC_, WIDE ? HIDC_ : OUTC_) : -1;  // compile-time LDS row stride (fp32 lean instances)
     static constexpr int ACT = ACT_, HIDC = HIDC_, OUTC = OUTC_, NORM = NORM_, OBSP = OBSP_, REW = REW_, TERM = TERM_, KMODE = KMODE_;
     static constexpr int PREC = PREC_;  // HIPETS_PREC_F32 (fp32 MFMA) or HIPETS_PREC_BF16X3 (lean instances only)
@@ -1331,12 +1225,9 @@ struct KSpec {
     static constexpr bool SPL_OUT = OUTC_ >= 0 && OUTC_ <= kSplMaxTiles;  // the output layer sums even / odd k-steps separately (wave_gemm SPL)
     // K-split of the leftover hidden column tile (KsArgs above): the fused fp32 instances whose hidden layers leave ONE column tile over
     // (13 = 3 x 4 + 1), used by the kernel for ONE-TILE workgroups only (R = 1: rollout_kernel's kKS)
-#ifndef HIPETS_KSPLIT
-#define HIPETS_KSPLIT 1
-#endif
     // (13 column tiles only: the consumer side, wave_gemm KSI inside KSO, rebuilds the last k chunk from slot kKsSlots - 1 of the last wave,
     // which is where a 13-chunk range -- 3 + 3 + 3 + 4 chunks -- ends; a 5- or 9-tile shape would end in another slot and read unwritten LDS)
-    static constexpr bool KSPLIT = HIPETS_KSPLIT && FUSE && !WIDE && kWaves == 4 && HIDC_ == 13;
+    static constexpr bool KSPLIT = FUSE && !WIDE && kWaves == 4 && HIDC_ == 13;
     // termination functions that test EVERY state dim (inverted_pendulum: isfinite(next_obs).all(), termination_fns.py:47-55) are fused for
     // models with obs_dim <= 4 only -- then dims 0..3 ARE every dim (launch.hpp fused_term_ok checks the model)
     static_assert(!FUSE || ((REW_ == HIPETS_REW_HALFCHEETAH || REW_ == HIPETS_REW_CARTPOLE || REW_ == HIPETS_REW_CARTPOLE_PETS || REW_ == HIPETS_REW_LEARNED) &&
@@ -1364,47 +1255,6 @@ struct KSpec {
     static_assert(!FUSE || OBSP_ == HIPETS_OBS_NONE || OBSP_ == HIPETS_OBS_HALFCHEETAH || OBSP_ == HIPETS_OBS_CARTPOLE_PETS, "unknown obs preprocessing");
 };
 
-// can an op with CS column tiles take part in the cross-layer prefetch? (one wave_gemm per wave, see linear_op)
-template <int CS> struct PreOk { static constexpr bool value = CS >= 0 && CS / kWaves <= (kWaves >= 8 ? 2 : 3); };
-
-// this wave's share of an op with CS column tiles (the (CT, EX, c_first, extras) linear_op<.., CS> derives), for prefetch_issue
-template <int R, int CS>
-__device__ __forceinline__ NextOp describe_op(const float* W, const float* bias, const int KC, const int tail_steps, const int wave) {
-    constexpr int full = CS / kWaves, rem = CS % kWaves, nu = rem * R;
-    constexpr int lo = nu / kWaves, hi = (nu + kWaves - 1) / kWaves;
-    NextOp n;
-    n.W = W; n.bias = bias; n.KC = KC; n.c_first = wave; n.ct = full; n.tail_steps = tail_steps;
-    n.ex_n = lo == hi ? lo : (wave < nu % kWaves ? hi : lo);
-    n.ex.c0 = kWaves * full + wave / R;                n.ex.r0 = wave % R;
-    n.ex.c1 = kWaves * full + (wave + kWaves) / R;     n.ex.r1 = (wave + kWaves) % R;
-    n.ex.c2 = kWaves * full + (wave + 2 * kWaves) / R; n.ex.r2 = (wave + 2 * kWaves) % R;
-    n.ex.c3 = kWaves * full + (wave + 3 * kWaves) / R; n.ex.r3 = (wave + 3 * kWaves) % R;
-    n.valid = true;
-    return n;
-}
-
-// the op `l` of member `member` as a prefetch target (lean kernels: hidden ops have S::HIDC column tiles, the last S::OUTC)
-template <int R, class S>
-__device__ __forceinline__ NextOp describe_layer(const ModelDev& md, const LayerMeta* lmeta, const int l, const int member, const int wave) {
-    const LayerMeta lm = lmeta[l];
-    const float* W = md.w + (size_t)member * md.wmember + lm.woff;
-    const float* bias = md.b + (size_t)member * md.bmember + lm.boff;
-    if (l < md.n_layers - 1) return describe_op<R, S::HIDC>(W, bias, lm.Kp / kKChunk, lm.tail_steps, wave);
-    return describe_op<R, S::OUTC>(W, bias, lm.Kp / kKChunk, lm.tail_steps, wave);
-}
-
-// An op with the cross-layer prefetch: runs from the descriptor `cur` that was computed (and prefetched for) one op earlier --
-// every op's pointers and shares are derived exactly once --, consumes `pre`, refills it for `nxt`
-template <int R, class S>
-__device__ __forceinline__ void mlp_layer_pre(const ModelDev& md, const bool last_op, const NextOp& cur, const float* in, float* out,
-                                              const int wave, const int lane, Prof& prof, Pre& pre, const NextOp& nxt) {
-    LayerMeta lm;
-    lm.Kp = cur.KC * kKChunk;
-    lm.tail_steps = cur.tail_steps;
-    if (!last_op) linear_op<R, S::ACT, S::HIDC, true>(cur.W, cur.bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, &pre, &nxt);
-    else linear_op<R, S::ACT, S::OUTC, true>(cur.W, cur.bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof, &pre, &nxt);
-}
-
 // Layer l in bf16x3 arithmetic
 template <int R, class S>
 __device__ __forceinline__ void mlp_layer_b3(const ModelDev& md, const LayerMeta* lmeta, const int l, const int member, const float* in, float* out,
@@ -1431,32 +1281,32 @@ __device__ __forceinline__ void mlp_layer(const ModelDev& md, const LayerMeta* l
         // by a hidden layer rebuild their last k chunk from the previous op's partial sums (KSI)
         float* const po = part + (l & 1) * (kWaves * 64 * 4);
         const float* const pi = part + ((l & 1) ^ 1) * (kWaves * 64 * 4);
-        if (l == 0) linear_op<R, S::ACT, S::HIDC, false, NoTail, S::LD, false, -1, 2>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, nullptr, nullptr, 0, nullptr, po);
-        else linear_op<R, S::ACT, S::HIDC, false, NoTail, S::LD, false, HIPETS_KS_TRIPLE ? S::HIDC : -1, 3>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, nullptr, nullptr, 0, pi, po);
+        if (l == 0) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD, false, -1, 2>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, 0, nullptr, po);
+        else linear_op<R, S::ACT, S::HIDC, NoTail, S::LD, false, S::HIDC, 3>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, 0, pi, po);
     } else if constexpr (S::LEAN) {
         // ops fed by a hidden layer have K = hid: HIDC chunks, a compile-time count (the input layer's K is the model's input width)
         // Unrolled only where the register file is not the constraint (R >= 3: one workgroup per CU, 512 registers per lane).  At R = 2
         // (two workgroups per CU, 256-register cap) the allocator splits accumulator live ranges inside the unrolled stream and
         // puts v_mov copies straight behind asm MFMAs -- which it believes complete at once (wave_gemm, "drain_all") -- and the
         // interleaved + unrolled build returned wrong sums (caught by the cfg5 parity tests); R = 1 measured 1 % slower unrolled.
-        constexpr int kHidChunks = (HIPETS_UNROLL_K && MinWavesOf<R>::value == 1) ? S::HIDC : -1;
-        if (l == 0) linear_op<R, S::ACT, S::HIDC, false, NoTail, S::LD>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, nullptr, nullptr, S::WIDE ? md.ld_in : 0);
-        else if (l < md.n_layers - 1) linear_op<R, S::ACT, S::HIDC, false, NoTail, S::LD, false, kHidChunks>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof);
-        else linear_op<R, S::ACT, S::OUTC, false, NoTail, S::LD, (S::OUTC <= kSplMaxTiles), kHidChunks>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
+        constexpr int kHidChunks = MinWavesOf<R>::value == 1 ? S::HIDC : -1;
+        if (l == 0) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, S::WIDE ? md.ld_in : 0);
+        else if (l < md.n_layers - 1) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD, false, kHidChunks>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof);
+        else linear_op<R, S::ACT, S::OUTC, NoTail, S::LD, (S::OUTC <= kSplMaxTiles), kHidChunks>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
     } else if constexpr (S::HID_STATIC) {
         // (unrolled up to 13 MFMA units per wave -- the widest the shape-specialised instances run: at 16 units, hid 256 with R = 4,
         // the allocator splits accumulator live ranges inside the unrolled stream again and the build's ISA scan finds a v_mov of an
         // accumulator behind an MFMA still in flight; the rolled loop ends every block with drain_all)
-        constexpr int kHidChunks = (HIPETS_UNROLL_K && MinWavesOf<R>::value == 1 && ((S::HIDC + kWaves - 1) / kWaves) * R <= 13) ? S::HIDC : -1;
-        if (l == 0) linear_op<R, S::ACT, S::HIDC, false, NoTail, S::LD>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof);
-        else if (l < md.n_layers - 1) linear_op<R, S::ACT, S::HIDC, false, NoTail, S::LD, false, kHidChunks>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof);
+        constexpr int kHidChunks = (MinWavesOf<R>::value == 1 && ((S::HIDC + kWaves - 1) / kWaves) * R <= 13) ? S::HIDC : -1;
+        if (l == 0) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof);
+        else if (l < md.n_layers - 1) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD, false, kHidChunks>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof);
         else if (lm.Np / kTile <= kSplMaxTiles)  // the output layer: the generic instance's dispatch, the SAME summation rule (SPL)
-            linear_op<R, S::ACT, -1, false, NoTail, -1, true>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
+            linear_op<R, S::ACT, -1, NoTail, -1, true>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
         else linear_op<R, S::ACT>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
     } else {
         // the output layer of up to kSplMaxTiles column tiles: SPL (the SAME rule in the shape-specialised branch above)
         if (l == md.n_layers - 1 && lm.Np / kTile <= kSplMaxTiles)
-            linear_op<R, S::ACT, -1, false, NoTail, -1, true>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
+            linear_op<R, S::ACT, -1, NoTail, -1, true>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
         else linear_op<R, S::ACT>(W, bias, lm, md.ld, l < md.n_layers - 1, md.activation, md.slope, in, out, wave, lane, prof);
     }
 }
@@ -1470,9 +1320,9 @@ __device__ __forceinline__ void mlp_output_layer_fused(const ModelDev& md, const
     const float* bias = md.b + (size_t)member * md.bmember + lm.boff_pairs;
     if constexpr (S::KSPLIT && R == 1) {  // the last hidden layer (index n_layers - 2) left its 13th tile as partial sums
         const float* const pi = part + ((md.n_layers - 2) & 1) * (kWaves * 64 * 4);
-        linear_op<R, S::ACT, S::OUTC, false, TL, S::LD, S::SPL_OUT, HIPETS_KS_TRIPLE ? S::HIDC : -1, 1>(W, bias, lm, md.ld, false, md.activation, md.slope, in, nullptr, wave, lane, prof, nullptr, nullptr, &tl, 0, pi);
+        linear_op<R, S::ACT, S::OUTC, TL, S::LD, S::SPL_OUT, S::HIDC, 1>(W, bias, lm, md.ld, false, md.activation, md.slope, in, nullptr, wave, lane, prof, &tl, 0, pi);
     } else {
-        linear_op<R, S::ACT, S::OUTC, false, TL, S::LD, S::SPL_OUT, (HIPETS_UNROLL_K && MinWavesOf<R>::value == 1) ? S::HIDC : -1>(W, bias, lm, md.ld, false, md.activation, md.slope, in, nullptr, wave, lane, prof, nullptr, nullptr, &tl);
+        linear_op<R, S::ACT, S::OUTC, TL, S::LD, S::SPL_OUT, MinWavesOf<R>::value == 1 ? S::HIDC : -1>(W, bias, lm, md.ld, false, md.activation, md.slope, in, nullptr, wave, lane, prof, &tl);
     }
 }
 
@@ -1678,17 +1528,8 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     constexpr bool kLean = S::LEAN;
     constexpr bool kB3 = S::PREC == HIPETS_PREC_BF16X3;  // operands as three bf16 pieces on the bf16 matrix pipe (lean instances)
     static_assert(!kB3 || kLean, "bf16x3 arithmetic exists for the shape-specialised instances");
-    // cross-layer weight prefetch (wave_gemm PRE): measured on MI355X and left OFF -- cfg2 FAST 1.054 ms with it (1.073 before
-    // the descriptors were derived only once and the layer barriers stopped draining vmcnt) against 1.021 ms without: the
-    // ~800-cycle first-fragment latency it hides is outweighed by 56 more live VGPRs and the extra scalar work between layers
-#ifndef HIPETS_CROSS_LAYER_PREFETCH
-#define HIPETS_CROSS_LAYER_PREFETCH 0
-#endif
-    constexpr bool kPre = HIPETS_CROSS_LAYER_PREFETCH && kLean && PreOk<S::HIDC>::value && PreOk<S::OUTC>::value;
-    constexpr bool kFuse = S::FUSE && !kPre;  // the output layer's accumulators feed the step's tail directly (KSpec::FUSE)
-    // the k-split ops of one-tile workgroups (mlp_layer: S::KSPLIT && R == 1) exist in the fused step flow only -- the generic flow
-    // passes no partial-sum buffer (a build with HIPETS_CROSS_LAYER_PREFETCH=1 turns kFuse off: it must not keep KSPLIT on)
-    static_assert(!(S::KSPLIT && R == 1) || kFuse, "k-split one-tile ops need the fused step flow (sm.part)");
+    // (no cross-layer weight prefetch: the next op's chunk-0 fragments requested behind this op's k loop measured slower -- 56 more live
+    // VGPRs and the scalar work between layers outweigh the latency it hides)
     // facts that are template arguments in a lean instance and model / call fields in the generic one
     const int normalizer = S::NORM >= 0 ? S::NORM : md.normalizer;
     const int obs_process = S::OBSP >= 0 ? S::OBSP : md.obs_process;
@@ -1774,11 +1615,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     // all of them (bf16x3: 0.83 MB per member, all five = 4.2 MB do not fit one L2).  Any bijection is correct.
     int wg = blockIdx.x;
     if (!fast) {
-#ifdef HIPETS_XCD_ROT  // profiling builds, grids that are multiples of 8 only: which XCD hosts which logical range (is a slow range slow because of the XCD or the member?)
-        const int nwg = gridDim.x, x = ((wg & 7) + HIPETS_XCD_ROT) & 7, slot = wg >> 3;
-#else
         const int nwg = gridDim.x, x = wg & 7, slot = wg >> 3;
-#endif
         wg = x * (nwg >> 3) + min(x, nwg & 7) + slot;
     }
 
@@ -1889,23 +1726,13 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     // for the WIDE instances: 9.84 -> 10.36 ms per cfg4' rollout (the per-item state of the retry loop pushes the kernel's
     // accumulators into AccVGPR spill space: 98 -> 126), 8 instead of 4 for cfg4: 3.37 -> 3.41 ms -- and HALVING the hand-over
     // traffic changed nothing (9.84 vs 9.89 ms): the phase is bound by round-trip latency and its own bookkeeping, not by bandwidth)
-#ifndef HIPETS_COLLECT_WIDE
-#define HIPETS_COLLECT_WIDE 8
-#endif
-#ifndef HIPETS_COLLECT_OUT4
-#define HIPETS_COLLECT_OUT4 4
-#endif
-    constexpr int kGT = S::WIDE ? HIPETS_COLLECT_WIDE : ((kLean && S::OUTC >= 4) ? HIPETS_COLLECT_OUT4 : kG);
+    constexpr int kGT = (kLean && S::OUTC >= 4) ? 4 : kG;  // (KSpec::WIDE instances collect by LDS-DMA: below)
     // Round 6, KSpec::WIDE (cfg4', Humanoid-v4: 189 pairs per row, 6 048 per two-tile workgroup and turn): the rows of a turn are fetched
     // by LDS-DMA -- no destination registers, so ALL of a wave's ~24 KiB are in flight at once (the register path above manages 8 pairs
     // per thread and needs three round trips of ~3 us) -- into the activation buffers, which are idle between two turns, and validated
     // LDS -> LDS by the wave that issued them (dma_collect below).  Every persistent launch of the instance takes the turn-based flow
     // then, also when each workgroup serves one logical workgroup (the straight form's collect writes the input image while it polls:
     // the image IS the staging area here).
-#ifndef HIPETS_DMA_COLLECT
-#define HIPETS_DMA_COLLECT 1
-#endif
-    constexpr bool kDmaCollect = S::WIDE && HIPETS_DMA_COLLECT;
     int xs[kG], xv[kG];
 #pragma unroll
     for (int q = 0; q < kG; ++q) {
@@ -2035,11 +1862,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
         act_s[q] = i < n_act ? i / md.act_dim : -1;
         act_a[q] = i < n_act ? i - (i / md.act_dim) * md.act_dim : 0;
     }
-#ifdef HIPETS_DBG_NOMAGIC
-    const bool magic_ok = false;
-#else
     const bool magic_ok = ra.P > 1 && (unsigned long long)ra.B * (unsigned)ra.P < 0x100000000ull;  // (P = 1: the constant would be 2^32)
-#endif
     const unsigned magic_p = (unsigned)(0x100000000ull / (unsigned)max(ra.P, 2)) + 1u;
     const int act_stride = ra.H * md.act_dim;
     // whose rows the action fetch / action columns are for: the slot's current rows -- except in the straight persistent form
@@ -2090,21 +1913,15 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     // ds_write_b32, and consecutive threads read consecutive state floats / normaliser doubles (conflict free) where the old item
     // (four CONSECUTIVE columns) read with a stride of four (measured on cfg4', 393 columns x 32 rows: 8.3 us per turn in the step
     // trace, profiles/turn_trace.py).  Same arithmetic per element.  bf16x3 images keep consecutive columns (split3x4's layout).
-#ifndef HIPETS_INPUT_BY_GROUP
-#define HIPETS_INPUT_BY_GROUP 1
-#endif
     auto build_input_impl = [&](const int t, float* const dst, auto norm_tag, auto plain_tag) __attribute__((always_inline)) {
         constexpr int NORM = decltype(norm_tag)::value;
         constexpr bool PLAIN = decltype(plain_tag)::value;
         // (shape-specialised instances WITH obs preprocessing keep the old items: their input is narrow, this function runs in their
         // prologue and turn-based flows only, and the R = 2 halfcheetah DEVICE instance -- at the 256-register limit of two waves per
         // SIMD -- spilt one VGPR to scratch with four sinf / cosf-bearing elements held for one store)
-        constexpr bool kByGroup = HIPETS_INPUT_BY_GROUP && !kB3 && (PLAIN || !kLean);
+        constexpr bool kByGroup = !kB3 && (PLAIN || !kLean);
         const float* actn_t = sm.actn + (t & 1) * n_act;
-#ifndef HIPETS_INPUT_BATCHED
-#define HIPETS_INPUT_BATCHED 1
-#endif
-        if constexpr (HIPETS_INPUT_BATCHED && kByGroup && PLAIN && NORM != HIPETS_NORM_F32) {
+        if constexpr (kByGroup && PLAIN && NORM != HIPETS_NORM_F32) {
             // Round 5 (step trace of the turn-based DEVICE form, profiles/r5_turn_trace.json: 8.3 us per turn for cfg4''s 32 rows x 400
             // columns = 20 k cycles for 12.5 items per thread): the loop below is a chain of LDS round trips -- row id, then the value
             // (from the state or from the actions, behind a branch), then the two normaliser doubles, element after element.  Here an
@@ -2186,9 +2003,6 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     // lane: lanes 16 columns apart meet on a bank -- 4-way conflicts on the state reads, 8-way on the f64 constants -- and the pass
     // measured 7-8 us per turn in the step trace (profiles/r6_turn_trace.json: "arrived -> built"), a tenth of a cfg4' turn in BOTH
     // modes.  Same arithmetic per element: same bits.
-#ifndef HIPETS_INPUT_BY_COLUMN
-#define HIPETS_INPUT_BY_COLUMN 1
-#endif
     int in_rows = ROWS;  // rows of the input image the next MLP pass reads (kTile in a one-tile turn: "ragged last turn" above)
     auto build_input_cols = [&](const int t, float* const dst) __attribute__((always_inline)) {
         const float* actn_t = sm.actn + (t & 1) * n_act;
@@ -2218,7 +2032,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     auto build_input = [&](const int t, float* const dst) __attribute__((always_inline)) {
         using T = std::true_type;
         using F = std::false_type;
-        if constexpr (kWide && HIPETS_INPUT_BY_COLUMN) {  // (KSpec static_assert: WIDE instances have the f64 normaliser and no obs preprocessing)
+        if constexpr (kWide) {  // (KSpec static_assert: WIDE instances have the f64 normaliser and no obs preprocessing)
             build_input_cols(t, dst);
             return;
         }
@@ -2244,7 +2058,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     // This thread's column of those (<= 16 action + padding columns, the usual case): column obs_in + (tid & 15), rows tid / 16 + 16 q --
     // no division, the column's normaliser constants and LDS position fixed for the launch.
     const int bac_c = md.obs_in + (tid & 15);
-    const bool bac_fast = kFuse && !kWide && Kp0 - md.obs_in <= 16;
+    const bool bac_fast = S::FUSE && !kWide && Kp0 - md.obs_in <= 16;
     const bool bac_live = bac_fast && bac_c < md.in_dim;  // an action column (else zero padding, or beyond Kp0: nothing to write)
     double bac_nm = 0.0, bac_ns = 0.0;  // read from LDS once the prologue has put the constants there (below)
     const int bac_pos = lds_col(min(bac_c, Kp0 - 1));
@@ -2295,14 +2109,6 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     __syncthreads();
     if (bac_live) { bac_nm = sm.nmean[bac_c]; bac_ns = sm.nstd[bac_c]; }
     if constexpr (kB3) kq = sm.lmeta[0].Kp32 >> 2;
-    Pre pre;      // chunk-0 weight fragments + biases of the NEXT linear op of this wave (kPre kernels)
-    NextOp cur_op;  // ... and that op's descriptor
-    cur_op.valid = false;
-    if constexpr (kPre) {
-        const int m0 = fast ? __builtin_amdgcn_readfirstlane(sm.sched[ra.t_begin]) : member_dom;
-        cur_op = describe_layer<R, S>(md, sm.lmeta, 0, m0, wave);
-        prefetch_issue(cur_op, lane, pre);
-    }
     build_input(ra.t_begin, sm.buf0);
     __syncthreads();
     prof.mark(0);
@@ -2318,11 +2124,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     (void)stamp_seq;
     // Straight persistent form (KSpec::FUSE instances, every launched workgroup serving exactly one logical workgroup, >= 3 hidden
     // layers): see the step loop.  The slot's rows of the current and of the next step live in two LDS arrays that swap roles.
-#ifdef HIPETS_DBG_NOSTRAIGHT
-    const bool straight = false;
-#else
-    const bool straight = kFuse && !kDmaCollect && persist && ra.n_logical == (int)gridDim.x && md.n_layers >= 4;
-#endif
+    const bool straight = S::FUSE && !kWide && persist && ra.n_logical == (int)gridDim.x && md.n_layers >= 4;
     int* const rows_a = sm.rowid;
     int* const rows_b = sm.pend + ROWS;
     // fused hopper termination, persistent DEVICE form: per-row "the state this row arrived with is unhealthy" flags, raised by the
@@ -2519,7 +2321,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
         if (more && !persist) fetch_actions_issue(t + 1, av);  // consumed after the sampling phase: the HBM / L2 latency hides behind the MLP
         unsigned long long* const handover = (more && persist) ? ra.exchange : nullptr;
         const unsigned long long handover_tag = (unsigned long long)(ra.tag_base + (unsigned)t + 1u) << 32;  // tags never repeat across launches
-        if constexpr (kFuse) {
+        if constexpr (S::FUSE) {
             // ---- KSpec::FUSE: hidden layers as usual; the OUTPUT layer's accumulators go straight into the step's tail ----------
             const int member = fast ? __builtin_amdgcn_readfirstlane(sm.sched[t]) : member_dom;  // wave-uniform
             float* cur = step_in;
@@ -2597,8 +2399,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
             // instances with obs preprocessing or a learned reward (pets_halfcheetah, pets_pusher / pets_reacher, pets_mppi_halfcheetah in
             // DEVICE mode) sit at the 256-register limit of two workgroups per CU, and with the pair's exchange they spilt 3-14 registers to
             // scratch memory (the build's resource report; pets_halfcheetah 0.498 -> 0.487 of peak; tests/test_abi.py allows no kernel any).
-            constexpr bool kPairDraws = HIPETS_SHARED_DRAWS != 0 &&
-                                        !(MinWaves<R, S>::value == 2 && R == 2 && S::KMODE != HIPETS_MODE_FAST && (S::OBSP != HIPETS_OBS_NONE || S::REW == HIPETS_REW_LEARNED));
+            constexpr bool kPairDraws = !(MinWaves<R, S>::value == 2 && R == 2 && S::KMODE != HIPETS_MODE_FAST && (S::OBSP != HIPETS_OBS_NONE || S::REW == HIPETS_REW_LEARNED));
             auto unit_draw = [&](const int rid, const int c, float& n0, float& n1) __attribute__((always_inline)) {  // one unit, the whole block per lane
                 const int g = lane >> 4;
                 const bool odd = (g & 1) != 0;
@@ -2814,16 +2615,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                 float* nxt = sm.buf1;
                 for (int l = 0; l < md.n_layers; ++l) {
                     prof.mark(12);
-                    if constexpr (kPre) {
-                        NextOp nop;
-                        nop.valid = false;
-                        if (l + 1 < md.n_layers) nop = describe_layer<R, S>(md, sm.lmeta, l + 1, member, wave);
-                        else if (t + 1 < ra.t_end)  // the next step's first op (its member: the schedule's next entry / the same domain)
-                            nop = describe_layer<R, S>(md, sm.lmeta, 0, fast ? __builtin_amdgcn_readfirstlane(sm.sched[t + 1]) : member_dom, wave);
-                        mlp_layer_pre<R, S>(md, l + 1 == md.n_layers, cur_op, cur, nxt, wave, lane, prof, pre, nop);
-                        cur_op = nop;
-                        lds_barrier();
-                    } else if constexpr (kB3) {
+                    if constexpr (kB3) {
                         mlp_layer_b3<R, S>(md, sm.lmeta, l, member, cur, nxt, wave, lane);
                         __syncthreads();
                     } else {
@@ -3021,7 +2813,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                     sm.tot[s_] = 0.f;
                     sm.term[s_] = 0;
                 }
-            } else if constexpr (kDmaCollect) {
+            } else if constexpr (kWide) {
                 dma_collect((unsigned)(tag >> 32));
             } else
             for (int base = 0; base < ROWS * NVP; base += kGT * kThreads) {
@@ -3049,17 +2841,12 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                 for (int spins = 0;; ++spins) {
                     // issue, issue, wait as straight-line asm (no branch between a load and its wait: the compiler does not know the
                     // destination registers are still in flight); items with nothing to fetch read the table's first pair and ignore it
-                    static_assert(kGT == 2 || kGT == 4 || kGT == 8 || kGT == 16 || kGT == 24, "the wait below names its destinations");
+                    static_assert(kGT == 2 || kGT == 4, "the wait below names its destinations");
                     u32x4g got[kGT];
 #pragma unroll
                     for (int q = 0; q < kGT; ++q) pair_load_issue(got[q], src[q] ? src[q] : ra.exchange);
                     if constexpr (kGT == 2) asm volatile("s_waitcnt vmcnt(0)" : "+v"(got[0]), "+v"(got[1])::"memory");
-                    else if constexpr (kGT == 4) asm volatile("s_waitcnt vmcnt(0)" : "+v"(got[0]), "+v"(got[1]), "+v"(got[2]), "+v"(got[3])::"memory");
-                    else {  // (every 8 destinations one statement; the first is the wait, the others only tie their registers behind it)
-#pragma unroll
-                        for (int q8 = 0; q8 < kGT; q8 += 8)
-                            asm volatile("s_waitcnt vmcnt(0)" : "+v"(got[q8]), "+v"(got[q8 + 1]), "+v"(got[q8 + 2]), "+v"(got[q8 + 3]), "+v"(got[q8 + 4]), "+v"(got[q8 + 5]), "+v"(got[q8 + 6]), "+v"(got[q8 + 7])::"memory");
-                    }
+                    else asm volatile("s_waitcnt vmcnt(0)" : "+v"(got[0]), "+v"(got[1]), "+v"(got[2]), "+v"(got[3])::"memory");
                     bool ready = true;
 #pragma unroll
                     for (int q = 0; q < kGT; ++q)
@@ -3086,7 +2873,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                         if (!soft[q]) {
                             const int d = 2 * gv[q];
                             const float v0 = __uint_as_float(g[q][0]), v1 = __uint_as_float(g[q][2]);
-                            if constexpr (kFuse && S::TERM == HIPETS_TERM_HOPPER) {  // (rows of the padding hold zeros and no row id: never read)
+                            if constexpr (S::FUSE && S::TERM == HIPETS_TERM_HOPPER) {  // (rows of the padding hold zeros and no row id: never read)
                                 if (sm.rowid[gs[q]] >= 0 && hopper_pair_bad(d, v0, v1, true, d + 1 < md.obs_dim)) hop_flags[gs[q]] = 1;
                             }
                             sm.state[gs[q] * md.obs_dim + d] = v0;
@@ -3109,7 +2896,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     }
 
     // ---- write back -------------------------------------------------------------------------------
-    if constexpr (kFuse && S::TERM == HIPETS_TERM_HOPPER) {
+    if constexpr (S::FUSE && S::TERM == HIPETS_TERM_HOPPER) {
         // the fused all-dims termination folds step t's per-row flag into `terminated` one step later (tail_unit): the LAST step's
         // flag is still pending here.  It cannot change a return (model_env.py:186-188: the terminating step's reward counts), but
         // sm.term is what the write-back publishes -- one launch per step in DEVICE mode: the next launch starts from it -- so it is

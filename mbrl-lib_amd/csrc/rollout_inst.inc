@@ -26,42 +26,26 @@
 
 #include "launch.hpp"
 
-// lean shapes instantiated for this R: the per-R tables of launch.hpp
-#if HIPETS_R == 1
-#define HIPETS_LEAN_SHAPES(X) HIPETS_LEAN_SHAPES_R1(X)
-#elif HIPETS_R == 2
-#define HIPETS_LEAN_SHAPES(X) HIPETS_LEAN_SHAPES_R2(X)
-#elif HIPETS_R == 3
-#define HIPETS_LEAN_SHAPES(X) HIPETS_LEAN_SHAPES_R3(X)
-#else
-#define HIPETS_LEAN_SHAPES(X) HIPETS_LEAN_SHAPES_R4(X)
-#endif
-#if HIPETS_R == 1
-#define HIPETS_LEAN_FAST_SHAPES(X) HIPETS_LEAN_FAST_SHAPES_R1(X)
-#elif HIPETS_R == 2
-#define HIPETS_LEAN_FAST_SHAPES(X) HIPETS_LEAN_FAST_SHAPES_R2(X)
-#elif HIPETS_R == 3
-#define HIPETS_LEAN_FAST_SHAPES(X) HIPETS_LEAN_FAST_SHAPES_R3(X)
-#else
-#define HIPETS_LEAN_FAST_SHAPES(X) HIPETS_LEAN_FAST_SHAPES_R4(X)
-#endif
+// lean fp32 and bf16x3 shapes instantiated for this R: the per-R tables of launch.hpp
+#define HIPETS_LEAN_SHAPES(X) HIPETS_CAT2(HIPETS_LEAN_SHAPES_R, HIPETS_R)(X)
+#define HIPETS_B3_SHAPES(X) HIPETS_CAT2(HIPETS_B3_SHAPES_R, HIPETS_R)(X)
 
-// bf16x3 precision instances for this R (launch.hpp)
-#if HIPETS_R == 1
-#define HIPETS_B3_SHAPES(X) HIPETS_B3_SHAPES_R1(X)
-#elif HIPETS_R == 2
-#define HIPETS_B3_SHAPES(X) HIPETS_B3_SHAPES_R2(X)
-#elif HIPETS_R == 3
-#define HIPETS_B3_SHAPES(X) HIPETS_B3_SHAPES_R3(X)
+// The launch mode of the shape-specialised instances of this translation unit, and their launch for a matching model: the lean fp32
+// instances run the output layer's accumulators straight into the step's tail (KSpec::FUSE = 1).  A KSpec::WIDE instance lays the LDS
+// out differently: it runs exactly when the host sized the LDS for it (ra.wide_lds).
+#if HIPETS_PART == 2
+#define HIPETS_LEAN_MODE HIPETS_MODE_FAST
 #else
-#define HIPETS_B3_SHAPES(X) HIPETS_B3_SHAPES_R4(X)
+#define HIPETS_LEAN_MODE HIPETS_MODE_EXACT
 #endif
-
-// the lean fp32 instances run the output layer's accumulators straight into the step's tail (KSpec::FUSE); -DHIPETS_FUSE_TAIL=0
-// builds them with the LDS-based sampling / reward / input phases of the generic kernel instead (A/B measurements)
-#ifndef HIPETS_FUSE_TAIL
-#define HIPETS_FUSE_TAIL 1
-#endif
+#define HIPETS_LEAN_SPEC(HC, OC, RW, TM, OB) KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, OB, RW, TM, HIPETS_LEAN_MODE, HIPETS_PREC_F32, 1>
+#define HIPETS_TRY_SHAPE(HC, OC, RW, TM, OB)                                                                                                   \
+    if (lean_shape_is(md, HC, OC, RW, TM, OB) && (HIPETS_LEAN_SPEC(HC, OC, RW, TM, OB)::WIDE ? 1 : 0) == ra.wide_lds)                         \
+        return launch_one<HIPETS_LEAN_SPEC(HC, OC, RW, TM, OB)>(grid, lds, lds_max, md, ra, st, start, stop);
+#define HIPETS_TRY_B3(HC, OC, RW, TM)                                                                                                          \
+    if (b3_shape_is(md, HC, OC, RW, TM))                                                                                                       \
+        return launch_one<KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, HIPETS_OBS_NONE, RW, TM, HIPETS_LEAN_MODE, HIPETS_PREC_BF16X3>>(      \
+            grid, lds, lds_max, md, ra, st, start, stop);
 
 namespace hipets {
 
@@ -203,31 +187,11 @@ hipError_t HIPETS_FN(_fast)(int grid, unsigned lds, int lds_max, const ModelDev&
                             hipEvent_t stop, bool* found) {
     *found = true;
     if (md.precision == HIPETS_PREC_BF16X3) {
-#define HIPETS_TRY_B3(HC, OC, RW, TM)                                                                                                          \
-    if (md.hidC == HC && md.outC == OC && md.reward_fn == RW && md.term_fn == TM && md.obs_process == HIPETS_OBS_NONE)                       \
-        return launch_one<KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, HIPETS_OBS_NONE, RW, TM, HIPETS_MODE_FAST, HIPETS_PREC_BF16X3>>(       \
-            grid, lds, lds_max, md, ra, st, start, stop);
         HIPETS_B3_SHAPES(HIPETS_TRY_B3)
-#undef HIPETS_TRY_B3
         *found = false;
         return hipErrorNotSupported;
     }
-    // (a KSpec::WIDE instance lays the LDS out differently: it runs exactly when the host sized the LDS for it, ra.wide_lds)
-#define HIPETS_TRY_SHAPE(HC, OC, RW, TM, OB)                                                                                                   \
-    if (md.hidC == HC && md.outC == OC && md.reward_fn == RW && md.term_fn == TM && md.obs_process == OB && md.ld == lean_ld(HC, OC) &&      \
-        (KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, OB, RW, TM, HIPETS_MODE_FAST, HIPETS_PREC_F32, HIPETS_FUSE_TAIL>::WIDE ? 1 : 0) == ra.wide_lds) \
-        return launch_one<KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, OB, RW, TM, HIPETS_MODE_FAST, HIPETS_PREC_F32,                           \
-                                HIPETS_FUSE_TAIL>>(grid, lds, lds_max, md, ra, st, start, stop);
     HIPETS_LEAN_SHAPES(HIPETS_TRY_SHAPE)
-#undef HIPETS_TRY_SHAPE
-    // shapes that exist as FAST instances only
-#define HIPETS_TRY_FAST_SHAPE(HC, OC, RW, TM, OB)                                                                                              \
-    if (md.hidC == HC && md.outC == OC && md.reward_fn == RW && md.term_fn == TM && md.obs_process == OB && md.ld == lean_ld(HC, OC) &&       \
-        !ra.wide_lds) \
-        return launch_one<KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, OB, RW, TM, HIPETS_MODE_FAST, HIPETS_PREC_F32, HIPETS_FUSE_TAIL>>(     \
-            grid, lds, lds_max, md, ra, st, start, stop);
-    HIPETS_LEAN_FAST_SHAPES(HIPETS_TRY_FAST_SHAPE)
-#undef HIPETS_TRY_FAST_SHAPE
     *found = false;
     return hipErrorNotSupported;
 }
@@ -244,12 +208,7 @@ hipError_t HIPETS_FN()(int grid, unsigned lds, int lds_max, const ModelDev& md, 
                 const hipError_t r = HIPETS_FN(_fast)(grid, lds, lds_max, md, ra, st, start, stop, &found);
                 if (found) return r;
             } else {
-#define HIPETS_TRY_B3(HC, OC, RW, TM)                                                                                                          \
-    if (md.hidC == HC && md.outC == OC && md.reward_fn == RW && md.term_fn == TM && md.obs_process == HIPETS_OBS_NONE)                       \
-        return launch_one<KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, HIPETS_OBS_NONE, RW, TM, HIPETS_MODE_EXACT, HIPETS_PREC_BF16X3>>(          \
-            grid, lds, lds_max, md, ra, st, start, stop);
                 HIPETS_B3_SHAPES(HIPETS_TRY_B3)
-#undef HIPETS_TRY_B3
             }
         }
         return hipErrorNotSupported;  // bf16x3 arithmetic exists for the shape-specialised instances only
@@ -260,14 +219,7 @@ hipError_t HIPETS_FN()(int grid, unsigned lds, int lds_max, const ModelDev& md, 
             const hipError_t r = HIPETS_FN(_fast)(grid, lds, lds_max, md, ra, st, start, stop, &found);
             if (found) return r;
         } else {
-    // (a KSpec::WIDE instance lays the LDS out differently: it runs exactly when the host sized the LDS for it, ra.wide_lds)
-#define HIPETS_TRY_SHAPE(HC, OC, RW, TM, OB)                                                                                                   \
-    if (md.hidC == HC && md.outC == OC && md.reward_fn == RW && md.term_fn == TM && md.obs_process == OB && md.ld == lean_ld(HC, OC) &&      \
-        (KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, OB, RW, TM, HIPETS_MODE_EXACT, HIPETS_PREC_F32, HIPETS_FUSE_TAIL>::WIDE ? 1 : 0) == ra.wide_lds) \
-        return launch_one<KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, OB, RW, TM, HIPETS_MODE_EXACT, HIPETS_PREC_F32,                          \
-                                HIPETS_FUSE_TAIL>>(grid, lds, lds_max, md, ra, st, start, stop);
             HIPETS_LEAN_SHAPES(HIPETS_TRY_SHAPE)
-#undef HIPETS_TRY_SHAPE
         }
     }
     if (ra.wide_lds) return hipErrorInvalidConfiguration;  // the LDS was sized for a WIDE instance that does not exist for this R / call: never run another layout in it

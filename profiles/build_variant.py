@@ -3,7 +3,7 @@ object taken from the shipped build (mbrl-lib_amd/build/), linked into profiles/
 to the GPU box with the snapshot).  HIPETS_LIB=<that path> selects it (mbrl-lib_amd/hipets/_lib.py).  The ISA hazard scan of
 __graft_entry__ runs on every recompiled unit: a variant with findings is not linked.
 
-    python profiles/build_variant.py noks rollout_r1.hip -DHIPETS_KSPLIT=0
+    python profiles/build_variant.py leanprof rollout_r1.hip rollout_r3.hip -DHIPETS_LEAN_PROF=1
 """
 import os
 import subprocess
