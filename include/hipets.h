@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define HIPETS_ABI_VERSION 7
+#define HIPETS_ABI_VERSION 8
 #define HIPETS_MAX_LAYERS 8
 
 typedef struct hipets_engine hipets_engine;
@@ -520,6 +520,52 @@ int hipets_plan_planet_icem_batched(hipets_engine* e, const hipets_icem_params* 
                                     const float* upper, float* elite, int32_t has_elite, const int32_t* keep_idx, const float* latent0,
                                     const float* belief0, int32_t num_particles, uint64_t seed, uint64_t plan_id, float* out,
                                     void* stream);
+
+/* ---- GaussianMLP ensemble training: ModelTrainer.train / evaluate (mbrl/models/model_trainer.py:70-262) --------- (ABI v8) */
+/* One GaussianMLP of E members, NLL loss (gaussian_mlp.py:291-305), fixed logvar bounds, torch.optim.Adam with coupled weight
+ * decay (model_trainer.py:63-68).  Parameters and Adam state are caller-owned DEVICE f32 tensors in torch's layout, updated in
+ * place: weights[l] [E, d_l, d_{l+1}], biases[l] [E, 1, d_{l+1}] with d_0 = in_dim, d_1 .. d_{n_layers-1} = hid and
+ * d_{n_layers} = 2 out_dim (mean | raw logvar columns).  Limits: E <= 16, 2 <= n_layers <= 8, in_dim <= 512, hid <= 256,
+ * out_dim <= 512, max_batch <= 256; anything else fails with HIPETS_ERR_INVALID_ARGUMENT.                                   */
+typedef struct {
+    int32_t ensemble_size;   /* E                                                                                    */
+    int32_t n_layers;        /* linear layers = num_layers of GaussianMLP + 1                                        */
+    int32_t in_dim;
+    int32_t hid;
+    int32_t out_dim;         /* target columns (obs dims + learned reward)                                           */
+    int32_t activation;      /* HIPETS_ACT_*                                                                         */
+    float leaky_slope;
+    int32_t max_batch;       /* rows of the widest minibatch of a hipets_train_steps call: sizes the idx rows       */
+    void* const* weights;    /* HOST array [n_layers] of DEVICE f32 pointers                                         */
+    void* const* biases;
+    void* const* exp_avg_w;  /* Adam exp_avg of every weight / bias tensor, same layouts                             */
+    void* const* exp_avg_b;
+    void* const* exp_avg_sq_w; /* Adam exp_avg_sq                                                                   */
+    void* const* exp_avg_sq_b;
+    const float* min_logvar; /* DEVICE [out_dim] (constant: learn_logvar_bounds = False)                              */
+    const float* max_logvar;
+    double lr, beta1, beta2, eps, weight_decay; /* param_groups[0] of the optimizer                                   */
+    int32_t steps_per_launch; /* 0 = the library's choice (launches of at most ~50 ms); else at most this many steps  */
+} hipets_train_desc;
+/* n_steps consecutive minibatch steps (Model.update, model.py:129-167): step s runs member e on dataset rows
+ * idx[s, e, 0 .. rows[s]) of x DEVICE f32 [n_rows, in_dim] (model inputs, normalised) and y DEVICE f32 [n_rows, out_dim]
+ * (targets); idx DEVICE int32 [n_steps, E, max_batch], rows DEVICE int32 [n_steps] (1 .. max_batch; an index outside
+ * [0, n_rows) reads zeros).  step0 = Adam steps taken before the call (torch's state "step"): step s uses t = step0 + s + 1 in
+ * its bias corrections (computed in double, as torch does).  Writes loss DEVICE f32 [n_steps, E] (each member's mean NLL;
+ * the reference's loss is their sum + 0.01 (sum max_logvar - sum min_logvar)) and grad_sq DEVICE f32 [n_steps, E] (sum of
+ * squares of the member's raw gradient, before weight decay: model.py:153-158 sums these over members and tensors).
+ * Members run in parallel, steps in order; the call is cut into launches of steps_per_launch steps (results do not depend
+ * on where the cuts fall).                                                                                                 */
+int hipets_train_steps(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows,
+                       const int32_t* idx, const int32_t* rows, int32_t n_steps, int64_t step0, float* loss, float* grad_sq,
+                       void* stream);
+/* ModelTrainer.evaluate over a whole dataset (GaussianMLP.eval_score, gaussian_mlp.py:337-361, averaged over rows and dims):
+ * score DEVICE f32 [E] = mean over the n_rows rows and out_dim dims of (mean_e(x) - y)^2, the mean columns only.  order
+ * DEVICE int32 [n_rows] or NULL: row r of the pass is dataset row order[r].  row_score DEVICE f32 [E, n_rows] or NULL: the
+ * squared error of pass row r summed over dims (per-batch scores for a batch_callback).  Partial sums are reduced in a
+ * fixed order: the result is deterministic.  The Adam fields of d are not read.                                          */
+int hipets_train_eval(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows,
+                      const int32_t* order, float* score, float* row_score, void* stream);
 
 /* ---- instrumentation (bench.py roofline leg) ----------------------------------------------- */
 /* on = 1: every rollout-kernel launch carries a start / stop hipEvent pair on its dispatch packet; on = k > 1: every

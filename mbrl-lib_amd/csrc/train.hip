@@ -1,0 +1,386 @@
+// train.hip -- GaussianMLP ensemble training kernels (hipets_train_steps / hipets_train_eval, include/hipets.h):
+//   train_step_kernel  Model.update (mbrl/models/model.py:129-167) + torch.optim.Adam for a chunk of consecutive minibatches
+//   train_eval_kernel  GaussianMLP.eval_score over the whole evaluation set (gaussian_mlp.py:337-361), mean columns only
+// Every product runs on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32 accumulate).
+#include <hip/hip_runtime.h>
+
+#include "train.hpp"
+
+namespace hipets {
+
+namespace {
+
+using f32x4 = __attribute__((ext_vector_type(4))) float;
+
+// One 16 x 16 tile of C = A . B (M x K by K x N), element (i, k) of A at A[i * sam + k * sak], (k, j) of B at B[k * sbk + j * sbn].
+// Lane l feeds A[m0 + (l & 15)][k + (l >> 4)] and B[k + (l >> 4)][n0 + (l & 15)]; the result is C[m0 + 4 (l >> 4) + i][n0 + (l & 15)]
+// in element i.  The operands come from L1 / L2 (or LDS) one float per lane, so the loop waits on load latency: kDeep blocks of 4
+// k-steps issue their 8 loads before their 4 MFMAs (forward and dA products), the others blocks of 2 (the dW product: the deeper
+// form there spilt SGPRs to scratch).  Two accumulators over alternate k-steps; out-of-range operands are zeros.
+template <bool kDeep>
+__device__ __forceinline__ f32x4 mm_tile(const float* __restrict__ A, int sam, int sak, int M, const float* __restrict__ B, int sbk, int sbn,
+                                         int N, int K, int m0, int n0, int lane) {
+    const int r = lane & 15, q = lane >> 4;
+    const bool av = m0 + r < M, bv = n0 + r < N;
+    const float* pa = A + (int64_t)(av ? m0 + r : 0) * sam;
+    const float* pb = B + (int64_t)(bv ? n0 + r : 0) * sbn;
+    f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+    int k0 = 0;
+    // per-lane pointers to k-steps 0..3 of the current block of 16 (VGPRs), advanced by 16 rows / columns per block
+    const int64_t sa4 = (int64_t)4 * sak, sb4 = (int64_t)4 * sbk;
+    const float* a0p = pa + (int64_t)q * sak;
+    const float* b0p = pb + (int64_t)q * sbk;
+    const float *a1p = a0p + sa4, *a2p = a0p + 2 * sa4, *a3p = a0p + 3 * sa4;
+    const float *b1p = b0p + sb4, *b2p = b0p + 2 * sb4, *b3p = b0p + 3 * sb4;
+    for (; kDeep && k0 + 16 <= K; k0 += 16) {
+        const float a0 = av ? *a0p : 0.f, a1 = av ? *a1p : 0.f, a2 = av ? *a2p : 0.f, a3 = av ? *a3p : 0.f;
+        const float b0 = bv ? *b0p : 0.f, b1 = bv ? *b1p : 0.f, b2 = bv ? *b2p : 0.f, b3 = bv ? *b3p : 0.f;
+        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, c0, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, c1, 0, 0, 0);
+        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, b2, c0, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a3, b3, c1, 0, 0, 0);
+        a0p += 4 * sa4; a1p += 4 * sa4; a2p += 4 * sa4; a3p += 4 * sa4;
+        b0p += 4 * sb4; b1p += 4 * sb4; b2p += 4 * sb4; b3p += 4 * sb4;
+    }
+    for (; k0 + 8 <= K; k0 += 8) {
+        const int ka = k0 + q, kb = k0 + 4 + q;
+        const float a0 = av ? pa[(int64_t)ka * sak] : 0.f, b0 = bv ? pb[(int64_t)ka * sbk] : 0.f;
+        const float a1 = av ? pa[(int64_t)kb * sak] : 0.f, b1 = bv ? pb[(int64_t)kb * sbk] : 0.f;
+        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, c0, 0, 0, 0);
+        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, c1, 0, 0, 0);
+    }
+    for (; k0 < K; k0 += 4) {
+        const int k = k0 + q;
+        const float a0 = (av && k < K) ? pa[(int64_t)k * sak] : 0.f, b0 = (bv && k < K) ? pb[(int64_t)k * sbk] : 0.f;
+        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, c0, 0, 0, 0);
+    }
+    return c0 + c1;
+}
+
+// the activation modules of GaussianMLP (gaussian_mlp.py:88-96) and their derivatives in terms of the pre-activation z
+__device__ __forceinline__ float act_fwd(int act, float z, float slope) {
+    switch (act) {
+        case HIPETS_ACT_RELU: return z > 0.f ? z : 0.f;
+        case HIPETS_ACT_SILU: return z / (1.f + expf(-z));
+        case HIPETS_ACT_LEAKY_RELU: return z > 0.f ? z : z * slope;
+        case HIPETS_ACT_TANH: return tanhf(z);
+        default: return 1.f / (1.f + expf(-z));
+    }
+}
+
+__device__ __forceinline__ float act_grad(int act, float z, float slope) {
+    switch (act) {
+        case HIPETS_ACT_RELU: return z > 0.f ? 1.f : 0.f;
+        case HIPETS_ACT_SILU: {
+            const float s = 1.f / (1.f + expf(-z));
+            return s * (1.f + z * (1.f - s));
+        }
+        case HIPETS_ACT_LEAKY_RELU: return z > 0.f ? 1.f : slope;
+        case HIPETS_ACT_TANH: {
+            const float t = tanhf(z);
+            return 1.f - t * t;
+        }
+        default: {
+            const float s = 1.f / (1.f + expf(-z));
+            return s * (1.f - s);
+        }
+    }
+}
+
+// torch.nn.functional.softplus (beta 1, threshold 20) and its derivative
+__device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
+__device__ __forceinline__ float softplus_grad(float x) {
+    if (x > 20.f) return 1.f;
+    const float z = expf(x);
+    return z / (z + 1.f);
+}
+
+// torch.optim.Adam, non-fused single-tensor order (weight decay coupled into the gradient); returns the new parameter
+__device__ __forceinline__ float adam(float p, float g, float* m, float* v, const TrainStepArgs& a, float nss, float bc2s) {
+    g = g + a.weight_decay * p;
+    const float mo = *m, w = a.one_minus_beta1;
+    const float mn = w < 0.5f ? mo + w * (g - mo) : g - (g - mo) * (1.f - w);  // Tensor.lerp_
+    const float vn = *v * a.beta2 + a.one_minus_beta2 * g * g;
+    *m = mn;
+    *v = vn;
+    const float denom = sqrtf(vn) / bc2s + a.eps;
+    return p + nss * (mn / denom);
+}
+
+__device__ __forceinline__ float wave_sum(float x) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
+    return x;
+}
+
+__global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainStepArgs a) {
+    __shared__ float red[2][kTrainThreads / 64];
+    const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int kWaves = kTrainThreads / 64;
+    const int E = a.ensemble_size, L = a.n_layers, in = a.dims[0], out = a.out_dim, out2 = 2 * out, bmax = a.max_batch;
+    float* slab = a.slab + (int64_t)e * a.slab_stride;
+    float* A0 = slab + a.off_a[0];
+    float* T = slab + a.off_t;
+    float* O = slab + a.off_o;
+    for (int s = 0; s < a.n_steps; ++s) {
+        const int nb = min(max(a.rows[s], 1), bmax);
+        const int32_t* ix = a.idx + ((int64_t)s * E + e) * bmax;
+        // ---- gather the step's rows (an index outside the dataset reads zeros: never out of bounds) ----
+        for (int t = tid; t < nb * in; t += kTrainThreads) {
+            const int r = t / in, k = t - r * in;
+            const int64_t row = ix[r];
+            A0[t] = (row >= 0 && row < a.n_rows) ? a.x[row * in + k] : 0.f;
+        }
+        for (int t = tid; t < nb * out; t += kTrainThreads) {
+            const int r = t / out, k = t - r * out;
+            const int64_t row = ix[r];
+            T[t] = (row >= 0 && row < a.n_rows) ? a.y[row * out + k] : 0.f;
+        }
+        __syncthreads();
+        // ---- forward: Z_l = A_l W_l + b_l, A_{l+1} = act(Z_l); the output layer's raw columns go to O ----
+        for (int l = 0; l < L; ++l) {
+            const int din = a.dims[l], dout = a.dims[l + 1];
+            const float* Ain = slab + a.off_a[l];
+            const float* W = a.w[l] + (int64_t)e * din * dout;
+            const float* bias = a.b[l] + (int64_t)e * dout;
+            const bool hidden = l < L - 1;
+            float* Z = hidden ? slab + a.off_z[l] : O;
+            float* An = hidden ? slab + a.off_a[l + 1] : nullptr;
+            const int tn = (dout + 15) >> 4, tiles = ((nb + 15) >> 4) * tn;
+            for (int t = wave; t < tiles; t += kWaves) {
+                const int m0 = (t / tn) << 4, n0 = (t % tn) << 4;
+                const f32x4 c = mm_tile<true>(Ain, din, 1, nb, W, dout, 1, dout, din, m0, n0, lane);
+                const int col = n0 + (lane & 15);
+                if (col < dout) {
+                    const float bc = bias[col];
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int row = m0 + 4 * (lane >> 4) + i;
+                        if (row < nb) {
+                            const float z = c[i] + bc;
+                            Z[row * dout + col] = z;
+                            if (hidden) An[row * dout + col] = act_fwd(a.activation, z, a.leaky_slope);
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+        // ---- NLL tail (gaussian_mlp.py:143-153, 291-305; util/math.py:41-64) and its gradient w.r.t. O ----
+        float* D = slab + a.off_d0;
+        float lsum = 0.f;
+        const float scale = 1.f / (float)(nb * out);  // mean over batch and output dims
+        for (int t = tid; t < nb * out; t += kTrainThreads) {
+            const int r = t / out, j = t - r * out;
+            const float mean = O[r * out2 + j], raw = O[r * out2 + out + j];
+            const float mx = a.max_logvar[j], mn = a.min_logvar[j];
+            const float u = mx - raw;
+            const float lv1 = mx - softplus(u);
+            const float w = lv1 - mn;
+            const float lv = mn + softplus(w);
+            const float d = mean - T[t];
+            const float iv = expf(-lv);
+            const float l2iv = d * d * iv;
+            lsum += l2iv + lv;
+            D[r * out2 + j] = 2.f * d * (scale * iv);
+            const float dlv = scale - scale * l2iv;
+            D[r * out2 + out + j] = dlv * softplus_grad(w) * softplus_grad(u);
+        }
+        __syncthreads();
+        // ---- backward, last layer first: dA_l = dZ_l W_l^T (weights before the update), db, dW = A_l^T dZ_l with Adam fused ----
+        float gsq = 0.f;
+        const float nss = a.neg_step_size[s], bc2s = a.bc2_sqrt[s];
+        int cur = 0;
+        for (int l = L - 1; l >= 0; --l) {
+            const int din = a.dims[l], dout = a.dims[l + 1];
+            const float* Dc = slab + (cur ? a.off_d1 : a.off_d0);
+            float* Dn = slab + (cur ? a.off_d0 : a.off_d1);
+            const int64_t wo = (int64_t)e * din * dout;
+            float* W = a.w[l] + wo;
+            float* mW = a.mw[l] + wo;
+            float* vW = a.vw[l] + wo;
+            if (l > 0) {
+                const float* Zp = slab + a.off_z[l - 1];
+                const int tn = (din + 15) >> 4, tiles = ((nb + 15) >> 4) * tn;
+                for (int t = wave; t < tiles; t += kWaves) {
+                    const int m0 = (t / tn) << 4, n0 = (t % tn) << 4;
+                    const f32x4 c = mm_tile<true>(Dc, dout, 1, nb, W, 1, dout, din, dout, m0, n0, lane);
+                    const int col = n0 + (lane & 15);
+                    if (col < din) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int row = m0 + 4 * (lane >> 4) + i;
+                            if (row < nb) Dn[row * din + col] = c[i] * act_grad(a.activation, Zp[row * din + col], a.leaky_slope);
+                        }
+                    }
+                }
+            }
+            {
+                float* bias = a.b[l] + (int64_t)e * dout;
+                float* mB = a.mb[l] + (int64_t)e * dout;
+                float* vB = a.vb[l] + (int64_t)e * dout;
+                for (int j = tid; j < dout; j += kTrainThreads) {
+                    float g = 0.f;
+                    for (int r = 0; r < nb; ++r) g += Dc[r * dout + j];
+                    gsq += g * g;
+                    bias[j] = adam(bias[j], g, mB + j, vB + j, a, nss, bc2s);
+                }
+            }
+            __syncthreads();  // every read of the old W_l (dA above) is done
+            {
+                const float* Ain = slab + a.off_a[l];
+                const int tn = (dout + 15) >> 4, tiles = ((din + 15) >> 4) * tn;
+                for (int t = wave; t < tiles; t += kWaves) {
+                    const int m0 = (t / tn) << 4, n0 = (t % tn) << 4;
+                    const f32x4 c = mm_tile<false>(Ain, 1, din, din, Dc, dout, 1, dout, nb, m0, n0, lane);
+                    const int col = n0 + (lane & 15);
+                    if (col < dout) {
+#pragma unroll
+                        for (int i = 0; i < 4; ++i) {
+                            const int row = m0 + 4 * (lane >> 4) + i;
+                            if (row < din) {
+                                const int64_t o = (int64_t)row * dout + col;
+                                gsq += c[i] * c[i];
+                                W[o] = adam(W[o], c[i], mW + o, vW + o, a, nss, bc2s);
+                            }
+                        }
+                    }
+                }
+            }
+            __syncthreads();  // the next layer's dA reads Dn; the next step's forward reads the new weights
+            cur ^= 1;
+        }
+        // ---- per-member loss and raw-gradient square sum of the step, reduced in a fixed order ----
+        lsum = wave_sum(lsum);
+        gsq = wave_sum(gsq);
+        if (lane == 0) {
+            red[0][wave] = lsum;
+            red[1][wave] = gsq;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            float ls = 0.f, gs = 0.f;
+            for (int w = 0; w < kWaves; ++w) {
+                ls += red[0][w];
+                gs += red[1][w];
+            }
+            a.loss[(int64_t)s * E + e] = ls / (float)(nb * out);
+            a.grad_sq[(int64_t)s * E + e] = gs;
+        }
+        __syncthreads();
+    }
+}
+
+// evaluate: workgroup (tile, member) runs kEvalRows rows through the member with activations in LDS; the output layer computes its
+// first out_dim (mean) columns only.  Writes the tile's squared-error sum to partial[e, tile] (rows in order, one thread).
+__global__ __launch_bounds__(kEvalThreads) void train_eval_kernel(const TrainEvalArgs a) {
+    extern __shared__ float lds[];
+    const int tile = blockIdx.x, e = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    constexpr int kWaves = kEvalThreads / 64;
+    const int L = a.n_layers, in = a.dims[0], out = a.out_dim;
+    const int64_t r0 = (int64_t)tile * kEvalRows;
+    const int nr = (int)min((int64_t)kEvalRows, a.n_rows - r0);
+    float* cur = lds;
+    float* nxt = lds + kEvalRows * a.max_width;
+    __shared__ int64_t rows[kEvalRows];
+    if (tid < nr) {
+        int64_t r = a.order ? (int64_t)a.order[r0 + tid] : r0 + tid;
+        rows[tid] = (r >= 0 && r < a.n_rows) ? r : -1;
+    }
+    __syncthreads();
+    for (int t = tid; t < nr * in; t += kEvalThreads) {
+        const int r = t / in, k = t - r * in;
+        cur[t] = rows[r] >= 0 ? a.x[rows[r] * in + k] : 0.f;
+    }
+    __syncthreads();
+    for (int l = 0; l < L; ++l) {
+        const int din = a.dims[l], ld = a.dims[l + 1];
+        const bool hidden = l < L - 1;
+        const int dout = hidden ? ld : out;
+        const float* W = a.w[l] + (int64_t)e * din * ld;
+        const float* bias = a.b[l] + (int64_t)e * ld;
+        const int tn = (dout + 15) >> 4, tiles = ((nr + 15) >> 4) * tn;
+        for (int t = wave; t < tiles; t += kWaves) {
+            const int m0 = (t / tn) << 4, n0 = (t % tn) << 4;
+            const f32x4 c = mm_tile<true>(cur, din, 1, nr, W, ld, 1, dout, din, m0, n0, lane);
+            const int col = n0 + (lane & 15);
+            if (col < dout) {
+                const float bc = bias[col];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int row = m0 + 4 * (lane >> 4) + i;
+                    if (row < nr) {
+                        const float z = c[i] + bc;
+                        if (hidden) {
+                            nxt[row * dout + col] = act_fwd(a.activation, z, a.leaky_slope);
+                        } else {
+                            const float d = rows[row] >= 0 ? z - a.y[rows[row] * out + col] : 0.f;
+                            nxt[row * dout + col] = d * d;
+                        }
+                    }
+                }
+            }
+        }
+        __syncthreads();
+        float* t = cur;
+        cur = nxt;
+        nxt = t;
+    }
+    // cur = [nr, out] squared errors: per-row sums (dims in order), then the tile's sum (rows in order)
+    __shared__ float rsum[kEvalRows];
+    if (tid < nr) {
+        float s = 0.f;
+        for (int j = 0; j < out; ++j) s += cur[tid * out + j];
+        rsum[tid] = s;
+        if (a.row_score) a.row_score[(int64_t)e * a.n_rows + r0 + tid] = s;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float s = 0.f;
+        for (int r = 0; r < nr; ++r) s += rsum[r];
+        a.partial[(int64_t)e * a.tiles + tile] = s;
+    }
+}
+
+// score[e] = (sum over tiles of partial[e, tile]) / (n_rows * out): every thread sums a fixed strided subset, then a fixed tree
+__global__ __launch_bounds__(256) void train_eval_reduce_kernel(const TrainEvalArgs a) {
+    __shared__ float s[256];
+    const int e = blockIdx.x, tid = threadIdx.x;
+    float acc = 0.f;
+    for (int t = tid; t < a.tiles; t += 256) acc += a.partial[(int64_t)e * a.tiles + t];
+    s[tid] = acc;
+    __syncthreads();
+    for (int h = 128; h > 0; h >>= 1) {
+        if (tid < h) s[tid] += s[tid + h];
+        __syncthreads();
+    }
+    if (tid == 0) a.score[e] = s[0] / ((float)a.n_rows * (float)a.out_dim);
+}
+
+}  // namespace
+
+hipError_t launch_train_steps(const TrainStepArgs& a, hipStream_t st) {
+    hipLaunchKernelGGL(train_step_kernel, dim3(a.ensemble_size), dim3(kTrainThreads), 0, st, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_train_eval(const TrainEvalArgs& a, hipStream_t st) {
+    const size_t lds = (size_t)2 * kEvalRows * a.max_width * sizeof(float);
+    static bool attr_set[64] = {};
+    int dev = 0;
+    hipError_t err = hipGetDevice(&dev);
+    if (err != hipSuccess) return err;
+    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
+        err = hipFuncSetAttribute(reinterpret_cast<const void*>(&train_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  2 * kEvalRows * kTrainMaxIn * (int)sizeof(float));
+        if (err != hipSuccess) return err;
+        if (dev >= 0 && dev < 64) attr_set[dev] = true;
+    }
+    hipLaunchKernelGGL(train_eval_kernel, dim3(a.tiles, a.ensemble_size), dim3(kEvalThreads), lds, st, a);
+    err = hipGetLastError();
+    if (err != hipSuccess) return err;
+    hipLaunchKernelGGL(train_eval_reduce_kernel, dim3(a.ensemble_size), dim3(256), 0, st, a);
+    return hipGetLastError();
+}
+
+}  // namespace hipets

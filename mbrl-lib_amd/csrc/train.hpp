@@ -1,0 +1,73 @@
+// train.hpp -- GaussianMLP ensemble training (ModelTrainer.train / evaluate, mbrl/models/model_trainer.py:70-262): the kernel
+// argument blocks shared by train.hip (kernels + launchers) and hipets.hip (the C ABI: validation, workspace, chunking).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/hipets.h"
+
+namespace hipets {
+
+constexpr int kTrainThreads = 512;        // 8 waves: two per SIMD, so one wave's MFMA chain hides the other's latency
+constexpr int kTrainMaxSteps = 256;       // steps per launch: the per-step Adam scalars travel in the kernel arguments
+constexpr int kTrainMaxMembers = 16;
+constexpr int kTrainMaxHid = 256;
+constexpr int kTrainMaxIn = 512;
+constexpr int kTrainMaxOut = 512;         // target columns; the output layer is 2 x this wide (mean | logvar)
+constexpr int kTrainMaxBatch = 256;
+constexpr int kEvalRows = 32;             // rows per evaluate workgroup
+constexpr int kEvalThreads = 256;
+
+// One launch = n_steps consecutive minibatch steps, one workgroup per member (members never communicate: the loss is a sum
+// over members, Adam is elementwise, the logvar bounds are constants).  Everything a step keeps for its backward pass lives
+// in the member's slab (global, L2-resident): per layer its input A_l and (hidden layers) its pre-activation Z_l, the raw
+// output O, the gathered targets T and two gradient ping-pong buffers D0 / D1.
+struct TrainStepArgs {
+    float* w[HIPETS_MAX_LAYERS];   // [E, d_l, d_{l+1}]  (torch's EnsembleLinearLayer layout)
+    float* b[HIPETS_MAX_LAYERS];   // [E, 1, d_{l+1}]
+    float* mw[HIPETS_MAX_LAYERS];  // Adam exp_avg, same layouts
+    float* mb[HIPETS_MAX_LAYERS];
+    float* vw[HIPETS_MAX_LAYERS];  // Adam exp_avg_sq
+    float* vb[HIPETS_MAX_LAYERS];
+    const float* x;                // [n_rows, in]  model inputs of the whole dataset
+    const float* y;                // [n_rows, out] targets
+    const int32_t* idx;            // [n_steps, E, max_batch] dataset rows of every (step, member)
+    const int32_t* rows;           // [n_steps] rows of every step (the last minibatch of an epoch is ragged)
+    const float* min_logvar;       // [out]
+    const float* max_logvar;
+    float* slab;                   // [E, slab_stride]
+    float* loss;                   // [n_steps, E] mean NLL of every member
+    float* grad_sq;                // [n_steps, E] sum of squares of the raw gradient (before weight decay)
+    int64_t slab_stride;
+    int64_t off_a[HIPETS_MAX_LAYERS];  // slab offsets (floats): layer inputs
+    int64_t off_z[HIPETS_MAX_LAYERS];  //   hidden pre-activations
+    int64_t off_o, off_t, off_d0, off_d1;
+    int64_t n_rows;
+    int32_t dims[HIPETS_MAX_LAYERS + 1];  // in, hid ... hid, 2 out
+    int32_t n_layers, out_dim, ensemble_size, max_batch, n_steps, activation;
+    float leaky_slope;
+    float weight_decay, one_minus_beta1, beta2, one_minus_beta2, eps;
+    float neg_step_size[kTrainMaxSteps];  // -(lr / (1 - beta1^t)) of every step t of the launch, rounded from double
+    float bc2_sqrt[kTrainMaxSteps];       // (1 - beta2^t)^0.5
+};
+
+// evaluate: the mean columns only, many workgroups over (row tile, member); partial sums [E, tiles] reduced in a fixed order
+struct TrainEvalArgs {
+    const float* w[HIPETS_MAX_LAYERS];
+    const float* b[HIPETS_MAX_LAYERS];
+    const float* x;
+    const float* y;
+    const int32_t* order;   // [n_rows] or NULL: row r of the pass is dataset row order[r]
+    float* partial;         // [E, tiles]
+    float* row_score;       // [E, n_rows] or NULL: sum over output dims of the squared error of every row
+    float* score;           // [E]
+    int64_t n_rows;
+    int32_t dims[HIPETS_MAX_LAYERS + 1];
+    int32_t n_layers, out_dim, ensemble_size, activation, max_width, tiles;
+    float leaky_slope;
+};
+
+hipError_t launch_train_steps(const TrainStepArgs& a, hipStream_t st);
+hipError_t launch_train_eval(const TrainEvalArgs& a, hipStream_t st);
+
+}  // namespace hipets

@@ -9,7 +9,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # HIPETS_LIB selects another build of the SAME library (kernel-variant experiments under profiles/); there is no fallback
 LIB_PATH = os.environ.get("HIPETS_LIB") or os.path.join(_HERE, "libhipets.so")
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 MAX_LAYERS = 8
 
 ACT = {"relu": 0, "silu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4}
@@ -98,6 +98,19 @@ class PlanetOpts(C.Structure):
 
 
 # every symbol include/hipets.h declares: name -> (restype, argtypes)
+class TrainDesc(C.Structure):
+    _fields_ = [
+        ("ensemble_size", C.c_int32), ("n_layers", C.c_int32), ("in_dim", C.c_int32), ("hid", C.c_int32), ("out_dim", C.c_int32),
+        ("activation", C.c_int32), ("leaky_slope", C.c_float), ("max_batch", C.c_int32),
+        ("weights", C.POINTER(C.c_void_p)), ("biases", C.POINTER(C.c_void_p)),
+        ("exp_avg_w", C.POINTER(C.c_void_p)), ("exp_avg_b", C.POINTER(C.c_void_p)),
+        ("exp_avg_sq_w", C.POINTER(C.c_void_p)), ("exp_avg_sq_b", C.POINTER(C.c_void_p)),
+        ("min_logvar", C.c_void_p), ("max_logvar", C.c_void_p),
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("weight_decay", C.c_double),
+        ("steps_per_launch", C.c_int32),
+    ]
+
+
 _P = C.c_void_p
 SYMBOLS = {
     "hipets_abi_version": (C.c_int, []),
@@ -154,6 +167,8 @@ SYMBOLS = {
                                                   _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64, _P]),
     "hipets_plan_planet_icem_batched": (C.c_int, [_P, C.POINTER(IcemParams), C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,
                                                   C.c_uint64, C.c_uint64, _P, _P]),
+    "hipets_train_steps": (C.c_int, [_P, C.POINTER(TrainDesc), _P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int64, _P, _P, _P]),
+    "hipets_train_eval": (C.c_int, [_P, C.POINTER(TrainDesc), _P, _P, C.c_int64, _P, _P, _P, _P]),
     "hipets_timing_enable": (C.c_int, [_P, C.c_int32]),
     "hipets_timing_read": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int32]),
 }

@@ -9,7 +9,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import CemParams, HipetsError, ModelDesc, PlanTrace, RolloutOpts
+from ._lib import CemParams, HipetsError, ModelDesc, PlanTrace, RolloutOpts, TrainDesc
 from .model import ModelSpec
 
 
@@ -718,6 +718,98 @@ class Engine:
         return out
 
     # ---- instrumentation ---------------------------------------------------------------------------
+    # ---- GaussianMLP ensemble training (hipets_train_steps / hipets_train_eval) ------------------------------------------
+    def _train_desc(self, weights, biases, activation: str, leaky_slope: float, out_dim: int, max_batch: int, adam=None):
+        """TrainDesc over the caller's DEVICE tensors (weights[l] [E, d_l, d_l+1], biases[l] [E, 1, d_l+1]); ``adam`` =
+        (exp_avg_w, exp_avg_b, exp_avg_sq_w, exp_avg_sq_b, min_logvar, max_logvar, lr, beta1, beta2, eps, weight_decay,
+        steps_per_launch).  The returned keep-alive list holds the ctypes arrays the struct points to."""
+        dev = self.device
+        L = len(weights)
+        if L < 2 or L != len(biases):
+            raise ValueError("weights / biases: one tensor of each per linear layer, at least 2 layers")
+        E, in_dim, hid = int(weights[0].shape[0]), int(weights[0].shape[1]), int(weights[0].shape[2])
+        for li, (w, b) in enumerate(zip(weights, biases)):
+            d_in = in_dim if li == 0 else hid
+            d_out = 2 * out_dim if li == L - 1 else hid
+            _check_dev(w, torch.float32, dev, f"weights[{li}]", shape=(E, d_in, d_out))
+            _check_dev(b, torch.float32, dev, f"biases[{li}]", shape=(E, 1, d_out))
+        if activation not in _lib.ACT:
+            raise ValueError(f"unknown activation {activation!r}")
+        arr = lambda ts: (C.c_void_p * L)(*[t.data_ptr() for t in ts])  # noqa: E731
+        keep = [arr(weights), arr(biases)]
+        d = TrainDesc(ensemble_size=E, n_layers=L, in_dim=in_dim, hid=hid, out_dim=out_dim, activation=_lib.ACT[activation],
+                      leaky_slope=float(leaky_slope), max_batch=int(max_batch))
+        d.weights = C.cast(keep[0], C.POINTER(C.c_void_p))
+        d.biases = C.cast(keep[1], C.POINTER(C.c_void_p))
+        if adam is not None:
+            mw, mb, vw, vb, lo, hi, lr, b1, b2, eps, wd, spl = adam
+            for name, ts, ref in (("exp_avg_w", mw, weights), ("exp_avg_b", mb, biases), ("exp_avg_sq_w", vw, weights), ("exp_avg_sq_b", vb, biases)):
+                if len(ts) != L:
+                    raise ValueError(f"{name}: one tensor per layer")
+                for li, (t, r) in enumerate(zip(ts, ref)):
+                    _check_dev(t, torch.float32, dev, f"{name}[{li}]", shape=tuple(r.shape))
+            _check_dev(lo, torch.float32, dev, "min_logvar", numel=out_dim)
+            _check_dev(hi, torch.float32, dev, "max_logvar", numel=out_dim)
+            keep += [arr(mw), arr(mb), arr(vw), arr(vb), lo, hi]
+            d.exp_avg_w, d.exp_avg_b, d.exp_avg_sq_w, d.exp_avg_sq_b = (C.cast(k, C.POINTER(C.c_void_p)) for k in keep[2:6])
+            d.min_logvar, d.max_logvar = lo.data_ptr(), hi.data_ptr()
+            d.lr, d.beta1, d.beta2, d.eps, d.weight_decay = float(lr), float(b1), float(b2), float(eps), float(wd)
+            d.steps_per_launch = int(spl)
+        return d, keep
+
+    def train_steps(self, weights, biases, exp_avg, exp_avg_sq, min_logvar, max_logvar, x: torch.Tensor, y: torch.Tensor,
+                    idx: torch.Tensor, rows: torch.Tensor, step0: int, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+                    weight_decay: float = 0.0, activation: str = "silu", leaky_slope: float = 0.01, steps_per_launch: int = 0):
+        """``n_steps = idx.shape[0]`` minibatch steps of Model.update + torch.optim.Adam on every member, in place on the DEVICE
+        tensors ``weights`` / ``biases`` and the Adam state ``exp_avg`` / ``exp_avg_sq`` (pairs of per-layer lists (w, b)).
+        x [N, in] / y [N, out] f32 = the dataset's model inputs and targets; idx int32 [n_steps, E, max_batch] its rows per
+        (step, member); rows int32 [n_steps] the rows of each step; step0 = Adam steps taken before.  Returns (loss, grad_sq)
+        DEVICE f32 [n_steps, E] (hipets.h: hipets_train_steps).  Asynchronous on the current stream."""
+        dev = self.device
+        out_dim = int(y.shape[-1]) if y.dim() == 2 else -1
+        _check_dev(x, torch.float32, dev, "x")
+        _check_dev(y, torch.float32, dev, "y")
+        if x.dim() != 2 or y.dim() != 2 or x.shape[0] != y.shape[0]:
+            raise ValueError("x / y must be [N, in] / [N, out] with the same N")
+        _check_dev(idx, torch.int32, dev, "idx")
+        if idx.dim() != 3:
+            raise ValueError("idx must be [n_steps, E, max_batch]")
+        n_steps, E, max_batch = (int(v) for v in idx.shape)
+        if E != int(weights[0].shape[0]):
+            raise ValueError(f"idx has {E} members, the model {int(weights[0].shape[0])}")
+        _check_dev(rows, torch.int32, dev, "rows", numel=n_steps)
+        d, keep = self._train_desc(weights, biases, activation, leaky_slope, out_dim, max_batch,
+                                   adam=(exp_avg[0], exp_avg[1], exp_avg_sq[0], exp_avg_sq[1], min_logvar, max_logvar, lr, betas[0], betas[1],
+                                         eps, weight_decay, steps_per_launch))
+        loss = torch.empty(n_steps, E, dtype=torch.float32, device=dev)
+        gsq = torch.empty(n_steps, E, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.hipets_train_steps(self._h, C.byref(d), _ptr(x), _ptr(y), int(x.shape[0]), _ptr(idx), _ptr(rows), n_steps,
+                                                    int(step0), _ptr(loss), _ptr(gsq), _stream(dev)))
+        del keep
+        return loss, gsq
+
+    def train_eval(self, weights, biases, x: torch.Tensor, y: torch.Tensor, order: Optional[torch.Tensor] = None, *,
+                   activation: str = "silu", leaky_slope: float = 0.01, row_scores: bool = False):
+        """GaussianMLP.eval_score averaged over rows and dims, per member: DEVICE f32 [E] (and, with ``row_scores``, the
+        [E, N] per-row squared-error sums in pass order).  Asynchronous on the current stream."""
+        dev = self.device
+        _check_dev(x, torch.float32, dev, "x")
+        _check_dev(y, torch.float32, dev, "y")
+        if x.dim() != 2 or y.dim() != 2 or x.shape[0] != y.shape[0]:
+            raise ValueError("x / y must be [N, in] / [N, out] with the same N")
+        N = int(x.shape[0])
+        if order is not None:
+            _check_dev(order, torch.int32, dev, "order", numel=N)
+        d, keep = self._train_desc(weights, biases, activation, leaky_slope, int(y.shape[1]), 1)
+        E = int(weights[0].shape[0])
+        score = torch.empty(E, dtype=torch.float32, device=dev)
+        rs = torch.empty(E, N, dtype=torch.float32, device=dev) if row_scores else None
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.hipets_train_eval(self._h, C.byref(d), _ptr(x), _ptr(y), N, _ptr(order), _ptr(score), _ptr(rs), _stream(dev)))
+        del keep
+        return (score, rs) if row_scores else score
+
     def timing_enable(self, on=True):
         """True / 1: time every rollout-kernel launch; k > 1: every k-th launch; False / 0: off."""
         _lib.check(self._lib.hipets_timing_enable(self._h, int(on)))
