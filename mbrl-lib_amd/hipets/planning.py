@@ -42,10 +42,76 @@ def get_engine(device) -> Engine:
     return _ENGINES[idx]
 
 
+def _has_device_mode(spec: ModelSpec) -> bool:
+    """Does the library's DEVICE mode (in-kernel balanced member shuffle) exist for ``spec``?  For GaussianMLP ensembles and for any
+    model under expectation propagation; BasicEnsemble models draw iid members, which the library's DEVICE mode has no variant for."""
+    return spec.ensemble_kind != "basic_ensemble" or spec.propagation == "expectation"
+
+
+def _device_f32(t: torch.Tensor, device) -> torch.Tensor:
+    """``t`` as a contiguous float32 tensor on ``device`` (itself when it already is one)."""
+    if t.device != device or t.dtype != torch.float32 or not t.is_contiguous():
+        t = t.to(device=device, dtype=torch.float32).contiguous()
+    return t
+
+
 # ---------------------------------------------------------------------------------------------
 # objective: ModelEnv.evaluate_action_sequences on the fused kernel
 # ---------------------------------------------------------------------------------------------
-class HipTrajectoryEvalFn:
+class _EnsembleObjective:
+    """What the two ensemble objectives share: the spec, device and model version of a live ``mbrl.models.ModelEnv`` or a
+    ``ModelSpec``, re-packing when the live model changed, binding the spec to the engine shared per GPU, and the reference's
+    batch-size check."""
+
+    _allow_custom_fns = False  # keep unrecognised reward / termination callables in the spec (the unfused objective)
+
+    def __init__(self, model, num_particles: int, engine: Optional[Engine], seed: int, device):
+        self.num_particles, self.seed, self.calls = int(num_particles), int(seed), 0
+        self._model_env, self._version = None, None
+        if isinstance(model, ModelSpec):
+            spec = model
+            dev = device if device is not None else "cuda:0"
+        else:
+            self._model_env = model
+            spec = spec_from_model_env(model, allow_custom_fns=self._allow_custom_fns)
+            dev = device if device is not None else getattr(model, "device", "cuda:0")
+            self._version = model_version(model)
+        self.engine = engine if engine is not None else get_engine(dev)
+        self.device = self.engine.device
+        self.engine.set_model(spec)
+        self.spec = spec
+
+    def refresh(self, force: bool = False):
+        """Re-pack weights if the live model changed (mbrl/models/model_trainer.py:288-296)."""
+        if self._model_env is None:
+            return
+        v = model_version(self._model_env)
+        if force or v != self._version:
+            self.spec = spec_from_model_env(self._model_env, allow_custom_fns=self._allow_custom_fns)
+            self.engine.set_model(self.spec)
+            self._version = v
+
+    def bind_model(self):
+        """Re-pack changed weights and make them the engine's model (engines are shared per GPU)."""
+        self.refresh()
+        if self.engine.spec is not self.spec:
+            self.engine.set_model(self.spec)
+
+    def check_batch(self, pop: int):
+        """The reference's ValueError (gaussian_mlp.py:195-200), raised for every propagation method and kept in
+        FAST mode too so that switching engines never changes which configurations are accepted."""
+        B, M = pop * self.num_particles, len(self.spec.members)
+        if self.spec.ensemble_kind == "basic_ensemble":  # BasicEnsemble.forward has no such rule (basic_ensemble.py:142-196)
+            return
+        if B % M != 0:
+            raise ValueError(
+                f"GaussianMLP ensemble requires batch size to be a multiple of the "
+                f"number of models. Current batch size is {B} for "
+                f"{M} models."
+            )
+
+
+class HipTrajectoryEvalFn(_EnsembleObjective):
     """``trajectory_eval_fn(initial_state, action_sequences) -> Tensor[B]`` (mbrl/types.py:15).
 
     Built from a live ``mbrl.models.ModelEnv`` (weights are re-snapshotted whenever
@@ -71,46 +137,15 @@ class HipTrajectoryEvalFn:
                  seed: int = 0, device=None, rng: Optional[torch.Generator] = None):
         if mode not in ("fast", "device", "exact", "exact_device"):
             raise ValueError("mode must be 'fast', 'device', 'exact' or 'exact_device'")
-        self.num_particles = int(num_particles)
         self.mode = mode
-        self.seed = int(seed)
-        self.calls = 0
-        self._model_env = None
-        self._version = None
-        if isinstance(model, ModelSpec):
-            spec = model
-            dev = device if device is not None else "cuda:0"
-        else:
-            self._model_env = model
-            spec = spec_from_model_env(model)
-            dev = device if device is not None else getattr(model, "device", "cuda:0")
-            self._version = model_version(model)
-            if rng is None:
-                rng = getattr(model, "_rng", None)
-        self.engine = engine if engine is not None else get_engine(dev)
-        self.device = self.engine.device
-        self.engine.set_model(spec)
-        self.spec = spec
+        super().__init__(model, num_particles, engine, seed, device)
+        if rng is None and self._model_env is not None:
+            rng = getattr(model, "_rng", None)
         self._rng = rng
-        # for multi-GPU: evaluate only candidates [lo, hi) (set by dist.ShardedEvalFn)
-
-    def refresh(self, force: bool = False):
-        """Re-pack weights if the live model changed (mbrl/models/model_trainer.py:288-296)."""
-        if self._model_env is None:
-            return
-        v = model_version(self._model_env)
-        if force or v != self._version:
-            self.spec = spec_from_model_env(self._model_env)
-            self.engine.set_model(self.spec)
-            self._version = v
 
     def _prep(self, action_sequences: torch.Tensor) -> torch.Tensor:
-        self.refresh()
-        if self.engine.spec is not self.spec:  # engine shared with another eval fn
-            self.engine.set_model(self.spec)
-        a = action_sequences
-        if a.device != self.device or a.dtype != torch.float32 or not a.is_contiguous():
-            a = a.to(device=self.device, dtype=torch.float32).contiguous()
+        self.bind_model()
+        a = _device_f32(action_sequences, self.device)
         self.check_batch(a.shape[0])
         return a
 
@@ -120,7 +155,7 @@ class HipTrajectoryEvalFn:
         fused plans can run --, else None."""
         if self.mode == "fast":
             return "fast"
-        if self.mode in ("device", "exact_device") and (self.spec.ensemble_kind != "basic_ensemble" or self.spec.propagation == "expectation"):
+        if self.mode in ("device", "exact_device") and _has_device_mode(self.spec):
             return "device"
         return None
 
@@ -184,19 +219,6 @@ class HipTrajectoryEvalFn:
                 eps = torch.stack(e_list).to(self.device)
         return self.engine.rollout(a, initial_state, self.num_particles, mode="exact", perms=perms, eps=eps)
 
-    def check_batch(self, pop: int):
-        """The reference's ValueError (gaussian_mlp.py:195-200), raised for every propagation method and kept in
-        FAST mode too so that switching engines never changes which configurations are accepted."""
-        B, M = pop * self.num_particles, len(self.spec.members)
-        if self.spec.ensemble_kind == "basic_ensemble":  # BasicEnsemble.forward has no such rule (basic_ensemble.py:142-196)
-            return
-        if B % M != 0:
-            raise ValueError(
-                f"GaussianMLP ensemble requires batch size to be a multiple of the "
-                f"number of models. Current batch size is {B} for "
-                f"{M} models."
-            )
-
     def _device_rng(self):
         if not hasattr(self, "_dev_rng"):
             self._dev_rng = torch.Generator(device=self.device).manual_seed(self.seed)
@@ -240,9 +262,7 @@ class ModelEnv:
     def _step_mode(self) -> str:
         """Kernel mode of ``step`` for the in-kernel randomness modes: 'device' where the library has it (GaussianMLP ensembles; any
         model under expectation propagation), else 'fast' (BasicEnsemble: iid member draws per workgroup)."""
-        if self.mode in ("device", "exact_device") and (self.spec.ensemble_kind != "basic_ensemble" or self.spec.propagation == "expectation"):
-            return "device"
-        return "fast"
+        return self._eval.kernel_mode or "fast"
 
     @property
     def spec(self) -> ModelSpec:
@@ -251,9 +271,7 @@ class ModelEnv:
     def reset(self, initial_obs_batch: np.ndarray, return_as_np: bool = True) -> Dict[str, torch.Tensor]:
         """model_env.py:62-85: returns the model state {"obs", "propagation_indices"} (+ ``MAP_STREAM_KEY``, see the class)."""
         assert len(initial_obs_batch.shape) == 2  # batch, obs_dim
-        self._eval.refresh()
-        if self.engine.spec is not self.spec:  # engines are shared per GPU: the maps below are exported for THIS model
-            self.engine.set_model(self.spec)
+        self._eval.bind_model()  # the maps below are exported for THIS model
         obs = torch.as_tensor(np.asarray(initial_obs_batch, dtype=np.float32)).to(self.device).contiguous()
         self._return_as_np = return_as_np
         B = obs.shape[0]
@@ -307,9 +325,7 @@ class ModelEnv:
     def step(self, actions, model_state: Dict[str, torch.Tensor], sample: bool = False):
         """model_env.py:87-140: (next_observs, rewards, dones, next_model_state)."""
         assert len(actions.shape) == 2  # batch, action_dim
-        self._eval.refresh()
-        if self.engine.spec is not self.spec:
-            self.engine.set_model(self.spec)
+        self._eval.bind_model()
         if isinstance(actions, np.ndarray):
             actions = torch.from_numpy(actions)
         actions = actions.to(device=self.device, dtype=torch.float32).contiguous()
@@ -362,7 +378,7 @@ class ModelEnv:
         return self._eval(initial_state, action_sequences)
 
 
-class UnfusedTrajectoryEvalFn:
+class UnfusedTrajectoryEvalFn(_EnsembleObjective):
     """``trajectory_eval_fn`` for models whose ``reward_fn`` / ``termination_fn`` are arbitrary Python callables
     (SURVEY.md section 2.1 row 6 "documented unfused fallback"): the horizon loop of
     ``ModelEnv.evaluate_action_sequences`` (model_env.py:178-191) runs on the host, every model transition is ONE fused
@@ -372,50 +388,19 @@ class UnfusedTrajectoryEvalFn:
     models run: the library's DEVICE mode has no iid-member variant)."""
 
     mode = "unfused"
+    _allow_custom_fns = True
 
     def __init__(self, model, num_particles: int, reward_fn=None, termination_fn=None, engine: Optional[Engine] = None,
                  seed: int = 0, device=None, step_mode: str = "device"):
         if step_mode not in ("device", "fast"):
             raise ValueError("step_mode must be 'device' or 'fast'")
         self.step_mode = step_mode
-        self.num_particles, self.seed, self.calls = int(num_particles), int(seed), 0
-        self._model_env, self._version = None, None
-        if isinstance(model, ModelSpec):
-            spec = model
-            dev = device if device is not None else "cuda:0"
-        else:
-            self._model_env = model
-            spec = spec_from_model_env(model, allow_custom_fns=True)
-            dev = device if device is not None else getattr(model, "device", "cuda:0")
-            self._version = model_version(model)
-        self.reward_fn = reward_fn if reward_fn is not None else spec.custom_reward_fn
-        self.termination_fn = termination_fn if termination_fn is not None else spec.custom_termination_fn
-        self.engine = engine if engine is not None else get_engine(dev)
-        self.device = self.engine.device
-        self.spec = spec
-        self.engine.set_model(spec)
-
-    def refresh(self):
-        if self._model_env is not None and model_version(self._model_env) != self._version:
-            self.spec = spec_from_model_env(self._model_env, allow_custom_fns=True)
-            self.engine.set_model(self.spec)
-            self._version = model_version(self._model_env)
-
-    def check_batch(self, pop: int):
-        B, M = pop * self.num_particles, len(self.spec.members)
-        if self.spec.ensemble_kind == "basic_ensemble":  # BasicEnsemble.forward has no such rule (basic_ensemble.py:142-196)
-            return
-        if B % M != 0:
-            raise ValueError(
-                f"GaussianMLP ensemble requires batch size to be a multiple of the "
-                f"number of models. Current batch size is {B} for "
-                f"{M} models."
-            )
+        super().__init__(model, num_particles, engine, seed, device)
+        self.reward_fn = reward_fn if reward_fn is not None else self.spec.custom_reward_fn
+        self.termination_fn = termination_fn if termination_fn is not None else self.spec.custom_termination_fn
 
     def __call__(self, initial_state: np.ndarray, action_sequences: torch.Tensor) -> torch.Tensor:
-        self.refresh()
-        if self.engine.spec is not self.spec:
-            self.engine.set_model(self.spec)
+        self.bind_model()
         a_seq = action_sequences.to(device=self.device, dtype=torch.float32)
         pop, H, _ = a_seq.shape
         P = self.num_particles
@@ -425,7 +410,7 @@ class UnfusedTrajectoryEvalFn:
         total = torch.zeros(pop * P, 1, device=self.device)
         terminated = torch.zeros(pop * P, 1, dtype=torch.bool, device=self.device)
         schedule = None
-        device_mode = self.step_mode == "device" and (self.spec.ensemble_kind != "basic_ensemble" or self.spec.propagation == "expectation")
+        device_mode = self.step_mode == "device" and _has_device_mode(self.spec)
         fixed = self.spec.propagation == "fixed_model"  # TS-infinity: one member map for the whole horizon (model.py:404-407)
         if fixed and not device_mode:
             nwg, _ = self.engine.fast_geometry(pop * P, 1, 1, -1)  # hipets_step runs the general kernel layout
@@ -522,26 +507,13 @@ class PlaNetTrajectoryEvalFn:
     def evaluate_seeded(self, initial_state, action_sequences: torch.Tensor, seed: int, stream_id: int) -> torch.Tensor:
         """One evaluation with explicit counter-based randomness (what iteration ``stream_id`` of the fused plan runs)."""
         latent0, belief0 = self.prepare()
-        a = action_sequences
-        if a.device != self.device or a.dtype != torch.float32 or not a.is_contiguous():
-            a = a.to(device=self.device, dtype=torch.float32).contiguous()
+        a = _device_f32(action_sequences, self.device)
         return self.engine.planet_rollout(a, latent0, belief0, self.num_particles, seed=seed, stream_id=stream_id)
 
     def __call__(self, initial_state, action_sequences: torch.Tensor) -> torch.Tensor:
-        self.refresh()
-        if self.engine.planet_spec is not self.spec:
-            self.engine.planet_set_model(self.spec)
-        if self._planet is not None:  # planet.py:669-672
-            if self._planet._current_posterior_sample is None or self._planet._current_belief is None:
-                raise RuntimeError("PlaNetModel has no saved posterior: call update_posterior() before planning")
-            self.set_state(self._planet._current_posterior_sample, self._planet._current_belief)
-        if self._state is None:
-            raise RuntimeError("no latent state: call set_state(latent, belief) first")
-        a = action_sequences
-        if a.device != self.device or a.dtype != torch.float32 or not a.is_contiguous():
-            a = a.to(device=self.device, dtype=torch.float32).contiguous()
+        latent0, belief0 = self.prepare()
+        a = _device_f32(action_sequences, self.device)
         self.calls += 1
-        latent0, belief0 = self._state
         if self.mode in ("fast", "device"):
             return self.engine.planet_rollout(a, latent0, belief0, self.num_particles, seed=self.seed, stream_id=self.calls)
         pop, H, _ = a.shape
@@ -590,26 +562,12 @@ class _BoundObjective:
         return self.eval_fn(self.obs, action_sequences)
 
 
-def _fused_target(obj_fun, planet_ok: bool = False):
-    """The hipets objective behind ``obj_fun`` when it draws its randomness in-kernel (so that a whole optimisation can run
-    inside the library), else None.  ``planet_ok``: PlaNet latent objectives count too (CEM has a fused PlaNet plan)."""
-    if isinstance(obj_fun, _BoundObjective):
-        fn = obj_fun.eval_fn
-        if isinstance(fn, HipTrajectoryEvalFn) and fn.kernel_mode is not None:
-            return fn
-        if planet_ok and isinstance(fn, PlaNetTrajectoryEvalFn) and fn.mode in ("fast", "device"):
-            return fn
-    return None
-
-
 def _prepare_fused(fused: HipTrajectoryEvalFn, population_sizes: Sequence[int]):
     """What ``fused.__call__`` would do before a rollout, for plans that run as one library call: re-pack the
     weights if the live model changed, make them the engine's current model, validate every batch size."""
-    fused.refresh()
+    fused.bind_model()
     for n in population_sizes:
         fused.check_batch(int(n))
-    if fused.engine.spec is not fused.spec:
-        fused.engine.set_model(fused.spec)
     if fused.engine.plan_mode != fused.kernel_mode:
         fused.engine.set_plan_mode(fused.kernel_mode)
 
@@ -669,7 +627,42 @@ def _reference_noise(shape, clipped_normal: bool) -> torch.Tensor:
         t[cond] = torch.normal(0.0, 1.0, size=(n,))
 
 
-class CEMOptimizer(Optimizer):
+class _PlanOptimizer(Optimizer):
+    """The front end of the three optimizers: the sampler choice, the engine, the bounds on its device, the seed of the
+    counter-based streams and the plan counter; per ``optimize()`` call, whether and how the plan runs inside the library."""
+
+    def __init__(self, device, lower_bound, upper_bound, seed: Optional[int], sampler: str):
+        super().__init__()
+        if sampler not in ("philox", "torch"):
+            raise ValueError("sampler must be 'philox' (device-side, default) or 'torch' (the reference's draws)")
+        self.sampler = sampler
+        self.engine = get_engine(device)
+        self.device = self.engine.device
+        self.lower_bound = torch.tensor(lower_bound, device=self.device, dtype=torch.float32).contiguous()
+        self.upper_bound = torch.tensor(upper_bound, device=self.device, dtype=torch.float32).contiguous()
+        self.seed = _default_seed(seed)
+        self.calls = 0
+
+    def _fused_objective(self, obj_fun, eligible: bool = True, planet_ok: bool = False):
+        """(fused, seed) of one plan.  ``fused`` is the hipets objective behind ``obj_fun`` when it draws its randomness in-kernel
+        on this optimizer's engine, else None.  With one, iteration i of the plan samples AND rolls out with the counter-based
+        streams of (seed = this seed ^ the objective's seed, the plan's stream of iteration i), whether the loop runs inside the
+        library (one plan call) or here (callback / injected draws / force_generic): both give the same numbers.  ``eligible``:
+        the optimizer's own condition; ``planet_ok``: PlaNet latent objectives count too (CEM has a fused PlaNet plan)."""
+        fn = obj_fun.eval_fn if isinstance(obj_fun, _BoundObjective) else None
+        kinds = (HipTrajectoryEvalFn, PlaNetTrajectoryEvalFn) if planet_ok else HipTrajectoryEvalFn
+        if eligible and self.sampler == "philox" and isinstance(fn, kinds) and fn.kernel_mode is not None and fn.engine is self.engine:
+            return fn, self.seed ^ fn.seed
+        return None, self.seed
+
+    @staticmethod
+    def _whole_plan(fused, callback, injected, kwargs) -> bool:
+        """Does the plan run as one library call?  With a fused objective and no callback, injected draws (parity tests) or
+        ``force_generic``."""
+        return fused is not None and callback is None and injected is None and not kwargs.get("force_generic", False)
+
+
+class CEMOptimizer(_PlanOptimizer):
     """Cross-Entropy Method with device-side sampling and elite refit (trajectory_opt.py:43-188).
 
     Works with ANY ``obj_fun`` (generic path: one sample kernel + ``obj_fun`` + one refit kernel per
@@ -680,27 +673,17 @@ class CEMOptimizer(Optimizer):
                  lower_bound: Sequence[Sequence[float]], upper_bound: Sequence[Sequence[float]], alpha: float,
                  device: torch.device, return_mean_elites: bool = False, clipped_normal: bool = False,
                  seed: Optional[int] = None, sampler: str = "philox"):
-        super().__init__()
-        if sampler not in ("philox", "torch"):
-            raise ValueError("sampler must be 'philox' (device-side, default) or 'torch' (the reference's draws)")
         # sampler='torch': the population noise is drawn exactly like the reference does on a CPU device (torch's GLOBAL
         # generator, redraw-until-inside loop of mbrl.util.math.truncated_normal_, util/math.py:69-92), so that with the
         # same torch.manual_seed an agent reproduces the reference's action selection (a parity aid: it synchronises)
-        self.sampler = sampler
+        super().__init__(device, lower_bound, upper_bound, seed, sampler)
         self.num_iterations = num_iterations
         self.elite_ratio = elite_ratio
         self.population_size = population_size
         self.elite_num = np.ceil(self.population_size * self.elite_ratio).astype(np.int32)  # :89-91
-        self.device = torch.device(device)
-        self.engine = get_engine(self.device)
-        self.device = self.engine.device
-        self.lower_bound = torch.tensor(lower_bound, device=self.device, dtype=torch.float32).contiguous()
-        self.upper_bound = torch.tensor(upper_bound, device=self.device, dtype=torch.float32).contiguous()
         self.alpha = alpha
         self.return_mean_elites = return_mean_elites
         self._clipped_normal = clipped_normal
-        self.seed = _default_seed(seed)
-        self.calls = 0
         # the reference's CEM is shape-generic (notebooks/cem_rosenbrock_ex.ipynb optimises a [2] vector):
         # kernels only see the flattened variable; [H, A] bounds keep their meaning for the fused plan path
         if self.lower_bound.ndim == 2:
@@ -722,15 +705,9 @@ class CEMOptimizer(Optimizer):
                  callback: Optional[Callable[[torch.Tensor, torch.Tensor, int], None]] = None, **kwargs) -> torch.Tensor:
         x0 = x0.to(device=self.device, dtype=torch.float32).contiguous()
         self.calls += 1
-        # a hipets objective that draws its randomness in-kernel: iteration i of this call samples AND rolls out with the
-        # counter-based streams (seed ^ objective seed, calls * iterations + i), whether the loop runs inside the library
-        # (one hipets_plan_cem call) or here (callback / injected noise / force_generic): both give the same numbers
-        fused = _fused_target(obj_fun, planet_ok=True) if (x0.ndim == 2 and self.sampler == "philox") else None
-        if fused is not None and fused.engine is not self.engine:
-            fused = None
-        seed = (self.seed ^ fused.seed) if fused is not None else self.seed
+        fused, seed = self._fused_objective(obj_fun, eligible=x0.ndim == 2, planet_ok=True)
         noise = kwargs.get("noise")  # optional injected z per iteration (parity tests)
-        if fused is not None and callback is None and noise is None and not kwargs.get("force_generic", False):
+        if self._whole_plan(fused, callback, noise, kwargs):
             if isinstance(fused, PlaNetTrajectoryEvalFn):  # the PlaNet latent planner: hipets_plan_planet_cem
                 latent0, belief0 = fused.prepare()
                 return self.engine.plan_planet_cem(self._params, x0, self.lower_bound, self.upper_bound, latent0, belief0,
@@ -756,14 +733,13 @@ class CEMOptimizer(Optimizer):
             values = fused.evaluate_seeded(obj_fun.obs, population, seed, stream) if fused is not None else obj_fun(population)
             if callback is not None:
                 callback(population, values, i)
-            if values.device != self.device or values.dtype != torch.float32 or not values.is_contiguous():
-                values = values.to(device=self.device, dtype=torch.float32).contiguous()
+            values = _device_f32(values, self.device)
             elites = _reference_elites(values, self.elite_num, self.device) if self.sampler == "torch" else None
             self.engine.cem_refit(p, values, population, mu, dispersion, best_value, best_solution, elites=elites)
         return mu if self.return_mean_elites else best_solution
 
 
-class MPPIOptimizer(Optimizer):
+class MPPIOptimizer(_PlanOptimizer):
     """Model Predictive Path Integral optimizer (trajectory_opt.py:191-311) with device-side sampling, smoothing
     recurrence and importance-weighted update.  Reproduces the reference's behaviour including its quirks
     (SURVEY.md Appendix B4-B6): ``self.mean`` persists across calls and is NOT cleared by ``agent.reset()``;
@@ -772,35 +748,24 @@ class MPPIOptimizer(Optimizer):
     def __init__(self, num_iterations: int, population_size: int, gamma: float, sigma: float, beta: float,
                  lower_bound: Sequence[Sequence[float]], upper_bound: Sequence[Sequence[float]], device: torch.device,
                  seed: Optional[int] = None, sampler: str = "philox"):
-        super().__init__()
-        if sampler not in ("philox", "torch"):
-            raise ValueError("sampler must be 'philox' (device-side, default) or 'torch' (the reference's draws)")
-        self.sampler = sampler  # 'torch': noise like the reference (global generator, truncated_normal_, :262-271)
+        # sampler='torch': noise like the reference (global generator, truncated_normal_, :262-271)
+        super().__init__(device, lower_bound, upper_bound, seed, sampler)
         self.planning_horizon = len(lower_bound)
         self.population_size = population_size
         self.action_dimension = len(lower_bound[0])
-        self.engine = get_engine(device)
-        self.device = self.engine.device
         self.mean = torch.zeros((self.planning_horizon, self.action_dimension), device=self.device, dtype=torch.float32)
-        self.lower_bound = torch.tensor(lower_bound, device=self.device, dtype=torch.float32).contiguous()
-        self.upper_bound = torch.tensor(upper_bound, device=self.device, dtype=torch.float32).contiguous()
         self.var = sigma**2 * torch.ones_like(self.lower_bound)  # kept for API parity; dead in the reference too
         self.beta = beta
         self.gamma = gamma
         self.refinements = num_iterations
-        self.seed = _default_seed(seed)
-        self.calls = 0
 
     def optimize(self, obj_fun: Callable[[torch.Tensor], torch.Tensor], x0: Optional[torch.Tensor] = None,
                  callback: Optional[Callable[[torch.Tensor, torch.Tensor, int], None]] = None, **kwargs) -> torch.Tensor:
         H, A, pop = self.planning_horizon, self.action_dimension, self.population_size
         self.calls += 1
-        fused = _fused_target(obj_fun) if self.sampler == "philox" else None  # see CEMOptimizer.optimize
-        if fused is not None and fused.engine is not self.engine:
-            fused = None
-        seed = (self.seed ^ fused.seed) if fused is not None else self.seed
+        fused, seed = self._fused_objective(obj_fun)
         noise = kwargs.get("noise")
-        if fused is not None and callback is None and noise is None and not kwargs.get("force_generic", False):
+        if self._whole_plan(fused, callback, noise, kwargs):
             _prepare_fused(fused, [pop])
             self.mean = self.mean.contiguous()
             if self.engine.comm_world > 1:  # sharded over the engine's communicator; the persistent mean stays replicated bit for bit
@@ -824,8 +789,7 @@ class MPPIOptimizer(Optimizer):
             self.engine.mppi_sample(pop, H, A, self.beta, self.mean, past_action, self.lower_bound, self.upper_bound, population,
                                     z=z, seed=seed, stream_id=stream)
             values = fused.evaluate_seeded(obj_fun.obs, population, seed, stream) if fused is not None else obj_fun(population)
-            if values.device != self.device or values.dtype != torch.float32 or not values.is_contiguous():
-                values = values.to(device=self.device, dtype=torch.float32).contiguous()
+            values = _device_f32(values, self.device)
             if callback is not None:  # the reference calls back after the NaN filter here (:297-300)
                 values[values.isnan()] = -1e-10
                 callback(population, values, k)
@@ -835,7 +799,7 @@ class MPPIOptimizer(Optimizer):
         return self.mean.clone()
 
 
-class ICEMOptimizer(Optimizer):
+class ICEMOptimizer(_PlanOptimizer):
     """Improved CEM (trajectory_opt.py:314-487): decaying population, coloured-noise sampling (device-side inverse
     real DFT), kept / shifted elites, biased variance refit.  ``self.elite`` persists across calls (Appendix B6)."""
 
@@ -843,23 +807,16 @@ class ICEMOptimizer(Optimizer):
                  colored_noise_exponent: float, lower_bound: Sequence[Sequence[float]], upper_bound: Sequence[Sequence[float]],
                  keep_elite_frac: float, alpha: float, device: torch.device, return_mean_elites: bool = False,
                  population_size_module: Optional[int] = None, seed: Optional[int] = None, sampler: str = "philox"):
-        super().__init__()
-        if sampler not in ("philox", "torch"):
-            raise ValueError("sampler must be 'philox' (device-side, default) or 'torch' (the reference's draws)")
         # 'torch': every draw of an iteration comes from torch's global CPU generator in the reference's order -- the two
         # spectrum normals of powerlaw_psd_gaussian (util/math.py:372-377), randperm(elite_num) for the kept elites
         # (trajectory_opt.py:446-448), the tail-action normal of the shifted elites (:451-457)
-        self.sampler = sampler
+        super().__init__(device, lower_bound, upper_bound, seed, sampler)
         self.num_iterations = num_iterations
         self.elite_ratio = elite_ratio
         self.population_size = population_size
         self.population_decay_factor = population_decay_factor
         self.elite_num = np.ceil(self.population_size * self.elite_ratio).astype(np.int32)
         self.colored_noise_exponent = colored_noise_exponent
-        self.engine = get_engine(device)
-        self.device = self.engine.device
-        self.lower_bound = torch.tensor(lower_bound, device=self.device, dtype=torch.float32).contiguous()
-        self.upper_bound = torch.tensor(upper_bound, device=self.device, dtype=torch.float32).contiguous()
         self.initial_var = ((self.upper_bound - self.lower_bound) ** 2) / 16
         self.keep_elite_frac = keep_elite_frac
         self.keep_elite_size = np.ceil(keep_elite_frac * self.elite_num).astype(np.int32)
@@ -869,8 +826,6 @@ class ICEMOptimizer(Optimizer):
         self.population_size_module = population_size_module
         if self.population_size_module:
             self.keep_elite_size = self._round_up_to_module(self.keep_elite_size, self.population_size_module)
-        self.seed = _default_seed(seed)
-        self.calls = 0
 
     @staticmethod
     def _round_up_to_module(value: int, module: int) -> int:  # :385-389
@@ -884,16 +839,19 @@ class ICEMOptimizer(Optimizer):
             n = self._round_up_to_module(n, self.population_size_module)
         return int(n)
 
+    def _extra_rows(self, i: int, has_elite: bool) -> int:
+        """Rows iteration i of a plan evaluates beyond its population (trajectory_opt.py:450-466), ``has_elite``: the plan started
+        with elites.  None in the first iteration of a plan without elites, the mean in the last of several iterations, else the
+        kept elites."""
+        if not (has_elite or i > 0):
+            return 0
+        return 1 if (i == self.num_iterations - 1 and i != 0) else int(self.keep_elite_size)
+
     def _fused_plan(self, H: int, A: int, has_elite: bool):
-        """The fused plan of one optimize(): the rows every iteration evaluates (its population, plus the kept elites or, in
-        the last of several iterations, the mean; trajectory_opt.py:450-466) and the library's IcemParams."""
+        """The fused plan of one optimize(): the rows every iteration evaluates (its population plus its extra rows) and the
+        library's IcemParams."""
         iters, keep = int(self.num_iterations), int(self.keep_elite_size)
-        sizes = []
-        for i in range(iters):
-            extra = 0
-            if has_elite or i > 0:
-                extra = 1 if (i == iters - 1 and i != 0) else keep
-            sizes.append(self._iteration_size(i) + extra)
+        sizes = [self._iteration_size(i) + self._extra_rows(i, has_elite) for i in range(iters)]
         p = IcemParams(population_size=int(self.population_size), horizon=H, act_dim=A, num_iterations=iters, elite_num=int(self.elite_num),
                        keep_elite_size=keep, population_size_module=int(self.population_size_module or 0),
                        return_mean_elites=int(bool(self.return_mean_elites)), alpha=float(self.alpha),
@@ -907,14 +865,12 @@ class ICEMOptimizer(Optimizer):
         H, A = x0.shape
         K, keep = int(self.elite_num), int(self.keep_elite_size)
         self.calls += 1
-        fused = _fused_target(obj_fun) if self.sampler == "philox" else None  # see CEMOptimizer.optimize
-        if fused is not None and fused.engine is not self.engine:
-            fused = None
-        seed = (self.seed ^ fused.seed) if fused is not None else self.seed
-        if fused is not None and callback is None and kwargs.get("inject") is None and not kwargs.get("force_generic", False):
-            sizes, p = self._fused_plan(H, A, self.elite is not None)
-            _prepare_fused(fused, sizes)
+        fused, seed = self._fused_objective(obj_fun)
+        inject = kwargs.get("inject")  # optional injected draws per iteration (parity tests)
+        if self._whole_plan(fused, callback, inject, kwargs):
             has_elite = self.elite is not None
+            sizes, p = self._fused_plan(H, A, has_elite)
+            _prepare_fused(fused, sizes)
             elite = self.elite.contiguous() if has_elite else torch.empty((K, H, A), device=self.device, dtype=torch.float32)
             if eng.comm_world > 1:  # sharded over the engine's communicator; the persistent elites stay replicated bit for bit
                 out = hdist.plan_icem_sharded(eng, p, x0, self.lower_bound, self.upper_bound, elite, has_elite, obj_fun.obs, fused.num_particles,
@@ -930,7 +886,6 @@ class ICEMOptimizer(Optimizer):
         best_solution = torch.zeros_like(mu)
         best_value = torch.full((1,), -float("inf"), device=self.device, dtype=torch.float32)
         elite_idx = torch.empty(K, dtype=torch.int32, device=self.device)
-        inject = kwargs.get("inject")
         for i in range(self.num_iterations):
             n = self._iteration_size(i)
             inj = inject[i] if inject is not None else {}
@@ -942,10 +897,7 @@ class ICEMOptimizer(Optimizer):
                     if i == 0:
                         inj["end_noise"] = torch.empty(keep, A).normal_(0.0, 1.0)
             sid = (self.calls * self.num_iterations + i) * 4
-            extra = 0
-            if self.elite is not None:
-                extra = 1 if (i == self.num_iterations - 1 and i != 0) else keep
-            population = torch.empty((n + extra, H, A), device=self.device, dtype=torch.float32)
+            population = torch.empty((n + self._extra_rows(i, self.elite is not None), H, A), device=self.device, dtype=torch.float32)
             normals = inj.get("normals")
             if normals is not None:
                 normals = normals.to(self.device, torch.float32).contiguous()
@@ -970,8 +922,7 @@ class ICEMOptimizer(Optimizer):
             values = fused.evaluate_seeded(obj_fun.obs, population, seed, sid + 3) if fused is not None else obj_fun(population)
             if callback is not None:
                 callback(population, values, i)
-            if values.device != self.device or values.dtype != torch.float32 or not values.is_contiguous():
-                values = values.to(device=self.device, dtype=torch.float32).contiguous()
+            values = _device_f32(values, self.device)
             p = Engine.cem_params(population.shape[0], H, A, self.num_iterations, K, self.alpha, self.return_mean_elites,
                                   clipped_normal=False, unbiased_var=False)  # biased variance (:479)
             elites = _reference_elites(values, K, self.device) if (self.sampler == "torch" and inject is None) else None
