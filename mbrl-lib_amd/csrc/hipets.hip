@@ -79,8 +79,6 @@ struct DevBuf {
     T* as() const { return reinterpret_cast<T*>(p); }
 };
 
-constexpr int kMaxR = 4;
-
 }  // namespace
 
 struct hipets_engine {
@@ -773,19 +771,16 @@ int hipets_kernel_class(hipets_engine* e, int32_t pop, int32_t P, int32_t horizo
     probe.use_philox = 1;
     Geometry g;
     if (rollout_geometry(e, mode, B, 0, horizon, rows_per_group, GeoCall::query, probe, &g)) return fail("the model does not fit LDS");
-    const bool call_lean = lean_call(md, probe);
+    probe.whole_horizon = g.whole_horizon ? 1 : 0;
+    probe.wide_lds = g.wide ? 1 : 0;
     int cls = HIPETS_KERNEL_GENERIC;
-    if (md.precision == HIPETS_PREC_BF16X3) {
-        if (!(call_lean && b3_shape_exists(md, g.R))) return fail("bf16x3 arithmetic exists for the shape-specialised instances only");
-        cls = HIPETS_KERNEL_FUSED;
-    } else if (g.wide) {
-        cls = HIPETS_KERNEL_WIDE;
-    } else if (call_lean && !wide_model(md) && lean_shape_exists(md, g.R)) {
-        cls = HIPETS_KERNEL_FUSED;
-    } else {
-#define HIPETS_CLASS_HID(HC) if (hid_static_call(md, probe, HC)) cls = HIPETS_KERNEL_HIDDEN_STATIC;
-        HIPETS_HID_STATIC_SHAPES(HIPETS_CLASS_HID)
-#undef HIPETS_CLASS_HID
+    switch (pick_rollout_instance(md, probe, g.R)) {
+        case RolloutInstance::lean: case RolloutInstance::b3: cls = HIPETS_KERNEL_FUSED; break;
+        case RolloutInstance::lean_wide: cls = HIPETS_KERNEL_WIDE; break;
+        case RolloutInstance::hidden_static: cls = HIPETS_KERNEL_HIDDEN_STATIC; break;
+        case RolloutInstance::generic_silu: case RolloutInstance::generic: break;
+        case RolloutInstance::no_b3: return fail("bf16x3 arithmetic exists for the shape-specialised instances only");
+        case RolloutInstance::no_wide: return fail("no WIDE instance of this model's shape for R = %d", g.R);
     }
     if (kernel_class) *kernel_class = cls;
     if (row_tiles) *row_tiles = g.R;

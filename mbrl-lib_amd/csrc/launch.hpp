@@ -8,17 +8,13 @@
 
 namespace hipets {
 
-// Launch rollout_kernel<R, ACT> (ACT = md.activation where a specialised instance exists, else the run-time generic one)
-// with `grid` workgroups and `lds` bytes of dynamic LDS on `st`.  start / stop (both or neither) ride on the dispatch packet.
+// Launch the instance of rollout_kernel<R, ...> that pick_rollout_instance (below) names for this model and call, with `grid`
+// workgroups and `lds` bytes of dynamic LDS on `st`.  start / stop (both or neither) ride on the dispatch packet.
+constexpr int kMaxR = 4;  // row-tile counts 1..kMaxR, one launcher each
 hipError_t launch_rollout_r1(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start, hipEvent_t stop);
 hipError_t launch_rollout_r2(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start, hipEvent_t stop);
 hipError_t launch_rollout_r3(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start, hipEvent_t stop);
 hipError_t launch_rollout_r4(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start, hipEvent_t stop);
-
-// Shapes whose fused fp32 instance is a KSpec::WIDE one (output layer wider than kSplMaxTiles column tiles: no LDS image of the
-// outputs, narrow activation buffers): X(hidden column tiles, output column tiles, reward fn, termination fn).  Instantiated for
-// R = 1 and 2 (rollout_inst.inc); the host sizes the LDS and chooses R for that layout exactly when the launcher will pick it.
-#define HIPETS_WIDE_SHAPES(X) X(13, 47, HIPETS_REW_HALFCHEETAH, HIPETS_TERM_HUMANOID)
 
 // Hidden widths with a KSpec::HID_STATIC instance (hidden layers shape-specialised, everything else generic): X(hidden column tiles).
 // 13 tiles = hidden widths 193..208: the reference's default of 200 (conf/dynamics_model/gaussian_mlp_ensemble.yaml:8), which every
@@ -26,12 +22,6 @@ hipError_t launch_rollout_r4(int grid, unsigned lds, int lds_max, const ModelDev
 // instance, profiles/r4_hidden_widths.json -- for widths no shipped configuration or BASELINE config has; round 6 dropped those eight
 // instances from the build: other widths run the generic instance, same bits.)
 #define HIPETS_HID_STATIC_SHAPES(X) X(13)
-
-// may this model / call run the hidden-static instance for `hc` hidden column tiles?  (SiLU, fp32 arithmetic, the LDS row stride the
-// instance was compiled for -- i.e. no layer wider than the hidden ones; RolloutArgs::generic_only == 1 forbids it, 2 allows it)
-inline bool hid_static_call(const ModelDev& md, const RolloutArgs& ra, const int hc) {
-    return ra.generic_only != 1 && md.precision == HIPETS_PREC_F32 && md.activation == HIPETS_ACT_SILU && md.hidC == hc && md.ld == lean_ld(hc, hc);
-}
 
 // Shape-specialised ("lean") fp32 instances per row-tile count R: X(hidden column tiles, output column tiles, reward fn, termination
 // fn, obs preprocessing); all of them SiLU, f64 normaliser, stochastic GaussianMLP with in-kernel sampling.  R follows the cost
@@ -84,27 +74,45 @@ inline bool fused_term_ok(const ModelDev& md) {
     return true;
 }
 
+// the model-side facts every shape-specialised instance (lean fp32 and bf16x3) was compiled for; the lean ones add fp32 arithmetic
+// (lean_shape), the call adds its own (lean_call)
+inline bool spec_model(const ModelDev& md) {
+    return md.activation == HIPETS_ACT_SILU && md.normalizer == HIPETS_NORM_F64 && !md.deterministic && md.propagation != HIPETS_PROP_EXPECTATION &&
+           md.lv_rows == 1 && fused_term_ok(md);
+}
+
+// does the call use nothing a shape-specialised instance compiled out? (KSpec in rollout.hpp lists what that is; the obs preprocessing
+// is part of an instance's shape since round 4)
+inline bool lean_call(const ModelDev& md, const RolloutArgs& ra) {
+    return !ra.generic_only && spec_model(md) && !ra.eps && ra.use_philox &&
+#if defined(HIPETS_STEP_TRACE) || (defined(HIPETS_LEAN_PROF) && HIPETS_LEAN_PROF)
+           !ra.trace_next_obs && !ra.trace_rewards && ra.pop_env == 0;  // the stamps go to phase_cycles
+#else
+           !ra.trace_next_obs && !ra.trace_rewards && !ra.phase_cycles && ra.pop_env == 0;
+#endif
+}
+
+// the lean fp32 instance X(hc, oc, rw, tm, ob) of the tables above, as rollout_inst.inc instantiates it for launch mode KMODE
+template <int HC, int OC, int RW, int TM, int OB, int KMODE>
+using LeanSpec = KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, OB, RW, TM, KMODE, HIPETS_PREC_F32, 1>;
+
 // does the model have the shape of the lean fp32 instance X(hc, oc, rw, tm, ob) of the tables above (the LDS row stride included)?
 inline bool lean_shape_is(const ModelDev& md, const int hc, const int oc, const int rw, const int tm, const int ob) {
     return md.hidC == hc && md.outC == oc && md.reward_fn == rw && md.term_fn == tm && md.obs_process == ob && md.ld == lean_ld(hc, oc);
 }
-// ... and of the bf16x3 instance X(hc, oc, rw, tm)
+// ... of the bf16x3 instance X(hc, oc, rw, tm)
 inline bool b3_shape_is(const ModelDev& md, const int hc, const int oc, const int rw, const int tm) {
     return md.hidC == hc && md.outC == oc && md.reward_fn == rw && md.term_fn == tm && md.obs_process == HIPETS_OBS_NONE;
 }
+// ... of the hidden-static instance X(hc): the LDS row stride it was compiled for, i.e. no layer wider than the hidden ones
+inline bool hid_static_is(const ModelDev& md, const int hc) { return md.hidC == hc && md.ld == lean_ld(hc, hc); }
 
-// the model-side facts every lean fp32 instance shares (the call-side ones: lean_call below)
-inline bool lean_model(const ModelDev& md) {
-    return md.precision == HIPETS_PREC_F32 && md.activation == HIPETS_ACT_SILU && md.normalizer == HIPETS_NORM_F64 && !md.deterministic &&
-           md.propagation != HIPETS_PROP_EXPECTATION && md.lv_rows == 1 && (md.reward_fn != HIPETS_REW_LEARNED || md.learned_rewards) && fused_term_ok(md);
-}
-
-// is there a lean fp32 instance of this model's shape for R row tiles? (what the launcher of rollout_r<R>.hip will find; the cost
-// model prices a (shape, R) pair with an instance lower than one that runs the hidden-static or the generic kernel)
-inline bool lean_shape_exists(const ModelDev& md, const int R) {
-    if (!lean_model(md)) return false;
+// the lean fp32 instance of this model's shape for R row tiles: none, a plain one, or a KSpec::WIDE one
+enum class LeanShape { none, plain, wide };
+inline LeanShape lean_shape(const ModelDev& md, const int R) {
+    if (md.precision != HIPETS_PREC_F32 || !spec_model(md)) return LeanShape::none;
 #define HIPETS_HAS_SHAPE(HC, OC, RW, TM, OB) \
-    if (lean_shape_is(md, HC, OC, RW, TM, OB)) return true;
+    if (lean_shape_is(md, HC, OC, RW, TM, OB)) return LeanSpec<HC, OC, RW, TM, OB, HIPETS_MODE_EXACT>::WIDE ? LeanShape::wide : LeanShape::plain;
     switch (R) {
         case 1: HIPETS_LEAN_SHAPES_R1(HIPETS_HAS_SHAPE) break;
         case 2: HIPETS_LEAN_SHAPES_R2(HIPETS_HAS_SHAPE) break;
@@ -113,10 +121,21 @@ inline bool lean_shape_exists(const ModelDev& md, const int R) {
         default: break;
     }
 #undef HIPETS_HAS_SHAPE
+    return LeanShape::none;
+}
+
+// is there a lean fp32 instance of this model's shape for R row tiles?  (the cost model prices a (shape, R) pair with an instance lower
+// than one that runs the hidden-static or the generic kernel)
+inline bool lean_shape_exists(const ModelDev& md, const int R) { return lean_shape(md, R) != LeanShape::none; }
+
+// is the model one of the WIDE shapes?  (where the call is lean, hipets.hip rollout_geometry sizes the LDS and chooses R for that layout)
+inline bool wide_model(const ModelDev& md) {
+    for (int R = 1; R <= kMaxR; ++R)
+        if (lean_shape(md, R) == LeanShape::wide) return true;
     return false;
 }
 
-// ... and the same question for the bf16x3 instances (rollout_inst.inc's HIPETS_TRY_B3)
+// is there a bf16x3 instance of this model's shape for R row tiles?
 inline bool b3_shape_exists(const ModelDev& md, const int R) {
 #define HIPETS_HAS_B3(HC, OC, RW, TM) \
     if (b3_shape_is(md, HC, OC, RW, TM)) return true;
@@ -130,28 +149,29 @@ inline bool b3_shape_exists(const ModelDev& md, const int R) {
     return false;
 }
 
-// does the call use nothing a lean instance compiled out? (KSpec in rollout.hpp lists what that is; the obs preprocessing is part
-// of an instance's shape since round 4)
-inline bool lean_call(const ModelDev& md, const RolloutArgs& ra) {
-    return !ra.generic_only && md.activation == HIPETS_ACT_SILU && md.normalizer == HIPETS_NORM_F64 &&
-           !md.deterministic && md.propagation != HIPETS_PROP_EXPECTATION && md.lv_rows == 1 && fused_term_ok(md) && !ra.eps && ra.use_philox &&
-#if defined(HIPETS_STEP_TRACE) || (defined(HIPETS_LEAN_PROF) && HIPETS_LEAN_PROF)
-           !ra.trace_next_obs && !ra.trace_rewards && ra.pop_env == 0;  // the stamps go to phase_cycles
-#else
-           !ra.trace_next_obs && !ra.trace_rewards && !ra.phase_cycles && ra.pop_env == 0;
-#endif
+// may this model / call run a hidden-static instance?  (SiLU, fp32 arithmetic, a hidden width of HIPETS_HID_STATIC_SHAPES;
+// RolloutArgs::generic_only == 1 forbids it, 2 allows it)
+inline bool hid_static_call(const ModelDev& md, const RolloutArgs& ra) {
+    if (ra.generic_only == 1 || md.precision != HIPETS_PREC_F32 || md.activation != HIPETS_ACT_SILU) return false;
+#define HIPETS_HAS_HID(HC) \
+    if (hid_static_is(md, HC)) return true;
+    HIPETS_HID_STATIC_SHAPES(HIPETS_HAS_HID)
+#undef HIPETS_HAS_HID
+    return false;
 }
 
-// is the model one of the WIDE shapes (fp32 arithmetic, the row strides the instance was compiled for)?
-inline bool wide_model(const ModelDev& md) {
-    if (md.precision != HIPETS_PREC_F32 || md.activation != HIPETS_ACT_SILU || md.normalizer != HIPETS_NORM_F64 || md.obs_process != HIPETS_OBS_NONE ||
-        md.deterministic || md.propagation == HIPETS_PROP_EXPECTATION || md.lv_rows != 1)
-        return false;  // (the model-side conditions of lean_call)
-#define HIPETS_IS_WIDE(HC, OC, RW, TM) \
-    if (lean_shape_is(md, HC, OC, RW, TM, HIPETS_OBS_NONE) && md.ld_in > 0) return true;
-    HIPETS_WIDE_SHAPES(HIPETS_IS_WIDE)
-#undef HIPETS_IS_WIDE
-    return false;
+// The instance of rollout_kernel<R, ...> a call runs -- the one selection rule: the launcher of rollout_r<R>.hip dispatches on it,
+// hipets_kernel_class reports it.  lean_wide: a KSpec::WIDE lean instance, which runs exactly where the host sized the LDS for its
+// layout (RolloutArgs::wide_lds); generic_silu: the generic instance with the SiLU epilogue fixed.  Refusals: no_b3 (bf16x3 arithmetic
+// exists in shape-specialised instances only), no_wide (LDS sized for a WIDE instance that does not exist for this R / call).
+enum class RolloutInstance { lean, lean_wide, b3, hidden_static, generic_silu, generic, no_b3, no_wide };
+inline RolloutInstance pick_rollout_instance(const ModelDev& md, const RolloutArgs& ra, const int R) {
+    const bool lean = lean_call(md, ra);
+    if (md.precision == HIPETS_PREC_BF16X3) return lean && b3_shape_exists(md, R) ? RolloutInstance::b3 : RolloutInstance::no_b3;
+    if (lean && lean_shape(md, R) == (ra.wide_lds ? LeanShape::wide : LeanShape::plain)) return ra.wide_lds ? RolloutInstance::lean_wide : RolloutInstance::lean;
+    if (ra.wide_lds) return RolloutInstance::no_wide;
+    if (hid_static_call(md, ra)) return RolloutInstance::hidden_static;
+    return md.activation == HIPETS_ACT_SILU ? RolloutInstance::generic_silu : RolloutInstance::generic;
 }
 
 hipError_t launch_planet_rollout(int grid, unsigned lds, int lds_max, const PlanetDev& pd, const PlanetArgs& ra, hipStream_t st, bool static_shape);

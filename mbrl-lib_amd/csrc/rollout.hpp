@@ -1182,10 +1182,10 @@ __device__ __forceinline__ void linear_op_b3(const uint4* W3, const float* bias,
 // obs preprocessing, reward and termination functions and the launch mode are template arguments, and everything those
 // shapes never use (expectation propagation, injected eps, traces, the phase profiler, batched / per-row initial states,
 // per-member logvar bounds) is compiled out.  The host picks an instance only when the model and the call match ALL of its
-// facts (launch.hpp select_*); anything else runs the generic instance.  Same arithmetic, instruction for instruction, in
+// facts (launch.hpp pick_rollout_instance); anything else runs a generic one.  Same arithmetic, instruction for instruction, in
 // the parts both execute: tests compare the two bit for bit.
 // LDS row stride the host derives for a model whose widest layer has `tiles` column tiles (hipets_set_model: >= the widest
-// activation, == 8 mod 64); a shape-specialised instance runs only when the model's stride is this one (launch: lean_shape_ok)
+// activation, == 8 mod 64); a shape-specialised instance runs only when the model's stride is this one (launch.hpp lean_shape_is)
 // Output layers of up to this many column tiles sum every unit's even / odd k-steps separately (wave_gemm SPL) and, in the
 // shape-specialised fp32 instances, feed the fused tail (KSpec::FUSE).  Wider ones (cfg4': 47) keep the plain order: a wave's share
 // is a dozen units there, and twice the accumulators (or a dozen inlined tails) do not fit the register file.

@@ -1,6 +1,6 @@
 // rollout_inst.inc -- body of rollout_r<R>.hip: instantiates rollout_kernel<HIPETS_R, KSpec<...>> -- the generic instances
 // (activation fixed to SiLU, or read at run time) and the shape-specialised "lean" instances of the BASELINE configurations --
-// and defines the host launcher launch_rollout_r<R> (launch.hpp), which picks the instance that matches the model and the call.
+// and defines the host launcher launch_rollout_r<R> (launch.hpp), which launches the instance launch.hpp pick_rollout_instance names.
 // HIPETS_PART splits an R over four translation units, so that no compile job of the build is longer than its largest single kernel
 // instance (round 6: the two fully generic instances take 40-60 s each, an R's whole set took 85-140 s as one unit):
 //   1  rollout_r<R>.hip       the launcher, the reference-semantics (EXACT / DEVICE) shape-specialised instances, the hidden-static one
@@ -30,22 +30,24 @@
 #define HIPETS_LEAN_SHAPES(X) HIPETS_CAT2(HIPETS_LEAN_SHAPES_R, HIPETS_R)(X)
 #define HIPETS_B3_SHAPES(X) HIPETS_CAT2(HIPETS_B3_SHAPES_R, HIPETS_R)(X)
 
-// The launch mode of the shape-specialised instances of this translation unit, and their launch for a matching model: the lean fp32
-// instances run the output layer's accumulators straight into the step's tail (KSpec::FUSE = 1).  A KSpec::WIDE instance lays the LDS
-// out differently: it runs exactly when the host sized the LDS for it (ra.wide_lds).
+// The launch mode of this unit's shape-specialised instances and the function that launches them (HIPETS_SPEC_FN), and the launch of
+// the instance of a table row that matches the model: the lean fp32 instances run the output layer's accumulators straight into the
+// step's tail (KSpec::FUSE = 1).
 #if HIPETS_PART == 2
 #define HIPETS_LEAN_MODE HIPETS_MODE_FAST
+#define HIPETS_SPEC_FN HIPETS_FN(_fast)
 #else
 #define HIPETS_LEAN_MODE HIPETS_MODE_EXACT
+#define HIPETS_SPEC_FN HIPETS_FN(_exact)
 #endif
-#define HIPETS_LEAN_SPEC(HC, OC, RW, TM, OB) KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, OB, RW, TM, HIPETS_LEAN_MODE, HIPETS_PREC_F32, 1>
-#define HIPETS_TRY_SHAPE(HC, OC, RW, TM, OB)                                                                                                   \
-    if (lean_shape_is(md, HC, OC, RW, TM, OB) && (HIPETS_LEAN_SPEC(HC, OC, RW, TM, OB)::WIDE ? 1 : 0) == ra.wide_lds)                         \
-        return launch_one<HIPETS_LEAN_SPEC(HC, OC, RW, TM, OB)>(grid, lds, lds_max, md, ra, st, start, stop);
+#define HIPETS_TRY_SHAPE(HC, OC, RW, TM, OB) \
+    if (lean_shape_is(md, HC, OC, RW, TM, OB)) return launch_one<LeanSpec<HC, OC, RW, TM, OB, HIPETS_LEAN_MODE>>(grid, lds, lds_max, md, ra, st, start, stop);
 #define HIPETS_TRY_B3(HC, OC, RW, TM)                                                                                                          \
     if (b3_shape_is(md, HC, OC, RW, TM))                                                                                                       \
         return launch_one<KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, HIPETS_OBS_NONE, RW, TM, HIPETS_LEAN_MODE, HIPETS_PREC_BF16X3>>(      \
             grid, lds, lds_max, md, ra, st, start, stop);
+#define HIPETS_TRY_HID(HC) \
+    if (hid_static_is(md, HC)) return launch_one<KSpec<HIPETS_ACT_SILU, HC>>(grid, lds, lds_max, md, ra, st, start, stop);
 
 namespace hipets {
 
@@ -166,8 +168,8 @@ hipError_t launch_one(int grid, unsigned lds, int lds_max, const ModelDev& md, c
 }  // namespace
 
 // the other translation units of this R
-hipError_t HIPETS_FN(_fast)(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start,
-                            hipEvent_t stop, bool* found);  // *found = an instance matched
+hipError_t HIPETS_FN(_fast)(RolloutInstance pick, int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st,
+                            hipEvent_t start, hipEvent_t stop);
 hipError_t HIPETS_FN(_gen)(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start, hipEvent_t stop);
 hipError_t HIPETS_FN(_gens)(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start, hipEvent_t stop);
 
@@ -182,54 +184,35 @@ hipError_t HIPETS_FN(_gens)(int grid, unsigned lds, int lds_max, const ModelDev&
 }
 #endif
 
-#if HIPETS_PART == 2
-hipError_t HIPETS_FN(_fast)(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start,
-                            hipEvent_t stop, bool* found) {
-    *found = true;
-    if (md.precision == HIPETS_PREC_BF16X3) {
+#if HIPETS_PART <= 2
+// the shape-specialised instance that the pick names, in this unit's launch mode: a bf16x3 one, or a lean fp32 one (KSpec::WIDE or not)
+hipError_t HIPETS_SPEC_FN(const RolloutInstance pick, int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st,
+                          hipEvent_t start, hipEvent_t stop) {
+    if (pick == RolloutInstance::b3) {
         HIPETS_B3_SHAPES(HIPETS_TRY_B3)
-        *found = false;
-        return hipErrorNotSupported;
+    } else {
+        HIPETS_LEAN_SHAPES(HIPETS_TRY_SHAPE)
     }
-    HIPETS_LEAN_SHAPES(HIPETS_TRY_SHAPE)
-    *found = false;
-    return hipErrorNotSupported;
+    return hipErrorNotSupported;  // (not reached: the pick found the model's row in this table)
 }
-#endif  // HIPETS_PART == 2
+#endif
 
 #if HIPETS_PART == 1
 hipError_t HIPETS_FN()(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start,
                             hipEvent_t stop) {
-    const bool fast = ra.whole_horizon != 0;
-    if (md.precision == HIPETS_PREC_BF16X3) {
-        if (lean_call(md, ra)) {
-            if (fast) {
-                bool found = false;
-                const hipError_t r = HIPETS_FN(_fast)(grid, lds, lds_max, md, ra, st, start, stop, &found);
-                if (found) return r;
-            } else {
-                HIPETS_B3_SHAPES(HIPETS_TRY_B3)
-            }
-        }
-        return hipErrorNotSupported;  // bf16x3 arithmetic exists for the shape-specialised instances only
+    const RolloutInstance pick = pick_rollout_instance(md, ra, HIPETS_R);
+    switch (pick) {
+        case RolloutInstance::lean:
+        case RolloutInstance::lean_wide:
+        case RolloutInstance::b3:
+            return (ra.whole_horizon ? HIPETS_FN(_fast) : HIPETS_FN(_exact))(pick, grid, lds, lds_max, md, ra, st, start, stop);
+        case RolloutInstance::hidden_static: HIPETS_HID_STATIC_SHAPES(HIPETS_TRY_HID) break;
+        case RolloutInstance::generic_silu: return HIPETS_FN(_gens)(grid, lds, lds_max, md, ra, st, start, stop);
+        case RolloutInstance::generic: return HIPETS_FN(_gen)(grid, lds, lds_max, md, ra, st, start, stop);
+        case RolloutInstance::no_b3: return hipErrorNotSupported;            // (hipets.hip launch_rollout reports it)
+        case RolloutInstance::no_wide: return hipErrorInvalidConfiguration;  // never run another layout in LDS sized for a WIDE instance
     }
-    if (lean_call(md, ra)) {
-        if (fast) {
-            bool found = false;
-            const hipError_t r = HIPETS_FN(_fast)(grid, lds, lds_max, md, ra, st, start, stop, &found);
-            if (found) return r;
-        } else {
-            HIPETS_LEAN_SHAPES(HIPETS_TRY_SHAPE)
-        }
-    }
-    if (ra.wide_lds) return hipErrorInvalidConfiguration;  // the LDS was sized for a WIDE instance that does not exist for this R / call: never run another layout in it
-    // hidden-static instances: any SiLU model of the reference's default hidden width, whatever else it and the call use
-#define HIPETS_TRY_HID(HC) \
-    if (hid_static_call(md, ra, HC)) return launch_one<KSpec<HIPETS_ACT_SILU, HC>>(grid, lds, lds_max, md, ra, st, start, stop);
-    HIPETS_HID_STATIC_SHAPES(HIPETS_TRY_HID)
-#undef HIPETS_TRY_HID
-    if (md.activation == HIPETS_ACT_SILU) return HIPETS_FN(_gens)(grid, lds, lds_max, md, ra, st, start, stop);  // the PETS default
-    return HIPETS_FN(_gen)(grid, lds, lds_max, md, ra, st, start, stop);
+    return hipErrorNotSupported;
 }
 #endif  // HIPETS_PART == 1
 
