@@ -1718,6 +1718,34 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     const int NVP = (md.obs_dim + 1) / 2 + 1;  // pairs per row
     const int NV = 2 * NVP;                    // granules per row
     const unsigned nvp_magic = (unsigned)(0x100000000ull / (unsigned)NVP) + 1u;  // NVP >= 2
+    // The give-up rule of every hand-over poll (true: the caller leaves its loop).  A hand-over takes microseconds; 0.2 s (poll_ticks)
+    // without the producer means it is not running at all (the grid is not co-resident: another process or stream holds CUs) -- give up
+    // loudly instead of spinning on; a flag that is already up (another workgroup, or an earlier poll, gave up) ends the wait after
+    // 64 spins: the results of the launch are void anyway and the host re-runs the call (hipets_check_async_error)
+    auto poll_gave_up = [&](const int spins, const long long t_poll) __attribute__((always_inline)) {
+        if ((poll_every || (spins & 63) == 63) && (wall_clock64() - t_poll > ra.poll_ticks || *(volatile int*)ra.error_flag)) {
+            *ra.error_flag = 1;
+            return true;
+        }
+        return false;
+    };
+    // sm.pend[s] was set: the row's {running total, flag} pair was late at the collect -- its previous owner published it after ITS
+    // output layer / reward phase (normally long arrived).  Poll the row's last pair until its tags are step t's.
+    auto fetch_late_total = [&](const int rid, const int t, float& tot, int& trm) __attribute__((always_inline)) {
+        const unsigned long long* const src = ra.exchange + (size_t)rid * NV + (NV - 2);
+        const unsigned want = ra.tag_base + (unsigned)t;
+        const long long t_poll = wall_clock64();
+        u32x4g g = {0u, 0u, 0u, 0u};
+        for (int spins = 0;; ++spins) {
+            pair_load_issue(g, src);
+            asm volatile("s_waitcnt vmcnt(0)" : "+v"(g)::"memory");
+            if (g[1] == want && g[3] == want) break;
+            if (poll_gave_up(spins, t_poll)) break;
+            __builtin_amdgcn_s_sleep(8);
+        }
+        tot = __uint_as_float(g[0]);
+        trm = (int)g[2];
+    };
     // rows wider than a few pairs (cfg4: 24 pairs per row, cfg4': 189) are collected in rounds of kGT pairs per thread, each round one
     // round trip to the table (>= 1 us even when the rows are long there: the later turns of a step): 4 / 8 in flight instead of 2
     // cut cfg4''s 12 rounds per turn to 3.  (Only the collect phase holds these registers; the straight form's cfg2 needs one round.)
@@ -2176,10 +2204,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                         else if (!soft[q]) ready = false;
                     }
                 if (ready) break;
-                if ((poll_every || (spins & 63) == 63) && (wall_clock64() - t_poll > ra.poll_ticks || *(volatile int*)ra.error_flag)) {
-                    *ra.error_flag = 1;
-                    break;
-                }
+                if (poll_gave_up(spins, t_poll)) break;
                 __builtin_amdgcn_s_sleep(8);
             }
 #pragma unroll
@@ -2299,8 +2324,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
             }
             pending = still;
             if (!pending) break;
-            if ((poll_every || (spins & 63) == 63) && (wall_clock64() - t_poll > ra.poll_ticks || *(volatile int*)ra.error_flag)) {
-                *ra.error_flag = 1;
+            if (poll_gave_up(spins, t_poll)) {
                 vmem_drain();  // nothing of this wave may still be landing in the activation buffers when the flow goes on
                 break;
             }
@@ -2508,24 +2532,9 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                     if (g == g_rew && rid >= 0) {
                         float tot = sm.tot[s];
                         int trm = sm.term[s];
-                        if (persist && sm.pend[s]) {  // collected late: the previous owner published them after ITS output layer (normally long arrived)
+                        if (persist && sm.pend[s]) {  // collected late
                             sm.pend[s] = 0;
-                            const unsigned long long* const src = ra.exchange + (size_t)rid * NV + (NV - 2);
-                            const unsigned want = ra.tag_base + (unsigned)t;
-                            const long long t_poll = wall_clock64();
-                            u32x4g gq = {0u, 0u, 0u, 0u};
-                            for (int spins = 0;; ++spins) {
-                                pair_load_issue(gq, src);
-                                asm volatile("s_waitcnt vmcnt(0)" : "+v"(gq)::"memory");
-                                if (gq[1] == want && gq[3] == want) break;
-                                if ((poll_every || (spins & 63) == 63) && (wall_clock64() - t_poll > ra.poll_ticks || *(volatile int*)ra.error_flag)) {
-                                    *ra.error_flag = 1;
-                                    break;
-                                }
-                                __builtin_amdgcn_s_sleep(8);
-                            }
-                            tot = __uint_as_float(gq[0]);
-                            trm = (int)gq[2];
+                            fetch_late_total(rid, t, tot, trm);
                         }
                         float rwd;
                         if constexpr (kLearnedRew) rwd = lrew;
@@ -2742,24 +2751,9 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                     const float* ac = sm.actn + (t & 1) * ROWS * md.act_dim + s * md.act_dim;
                     float tot = sm.tot[s];
                     int trm = sm.term[s];
-                    if (persist && sm.pend[s]) {  // collected late: the previous owner published them after ITS reward phase (normally long arrived)
+                    if (persist && sm.pend[s]) {  // collected late
                         sm.pend[s] = 0;
-                        const unsigned long long* const src = ra.exchange + (size_t)rid * NV + (NV - 2);
-                        const unsigned want = ra.tag_base + (unsigned)t;
-                        const long long t_poll = wall_clock64();
-                        u32x4g g = {0u, 0u, 0u, 0u};
-                        for (int spins = 0;; ++spins) {
-                            pair_load_issue(g, src);
-                            asm volatile("s_waitcnt vmcnt(0)" : "+v"(g)::"memory");
-                            if (g[1] == want && g[3] == want) break;
-                            if ((poll_every || (spins & 63) == 63) && (wall_clock64() - t_poll > ra.poll_ticks || *(volatile int*)ra.error_flag)) {
-                                *ra.error_flag = 1;
-                                break;
-                            }
-                            __builtin_amdgcn_s_sleep(8);
-                        }
-                        tot = __uint_as_float(g[0]);
-                        trm = (int)g[2];
+                        fetch_late_total(rid, t, tot, trm);
                     }
                     float r = reward_eval(st, ac, md.obs_dim, md.act_dim, reward_fn, sm.lrew[s]);
                     const bool done = term_eval(st, md.obs_dim, term_fn);
@@ -2856,14 +2850,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                             else if (!soft[q]) ready = false;
                         }
                     if (ready) break;
-                    // a hand-over takes microseconds; 0.2 s (poll_ticks) without the producer means it is not running at all (the grid is
-                    // not co-resident: another process or stream holds CUs) -- give up loudly instead of spinning on; a flag that is
-                    // already up (another workgroup, or an earlier poll, gave up) ends the wait after 64 spins: the results of the
-                    // launch are void anyway and the host re-runs the call (hipets_check_async_error)
-                    if ((poll_every || (spins & 63) == 63) && (wall_clock64() - t_poll > ra.poll_ticks || *(volatile int*)ra.error_flag)) {
-                        *ra.error_flag = 1;
-                        break;
-                    }
+                    if (poll_gave_up(spins, t_poll)) break;
                     __builtin_amdgcn_s_sleep(8);
                 }
 #pragma unroll
