@@ -64,9 +64,17 @@ enum { HIPETS_NORM_NONE = 0, HIPETS_NORM_F32 = 1, HIPETS_NORM_F64 = 2 };
 enum { HIPETS_ENSEMBLE_GAUSSIAN_MLP = 0, HIPETS_ENSEMBLE_BASIC = 1 };
 /* arithmetic of the ensemble MLP's linear layers */
 enum { HIPETS_PREC_F32 = 0,    /* v_mfma_f32_16x16x4_f32: fp32 operands, fp32 accumulate (the graded mode)              */
-       HIPETS_PREC_BF16X3 = 1  /* fp32 operands carried as three bf16 pieces, six exact partial products per product     */
+       HIPETS_PREC_BF16X3 = 1, /* fp32 operands carried as three bf16 pieces, six exact partial products per product     */
                                /* on v_mfma_f32_16x16x32_bf16, fp32 accumulate: fp32-accurate to a few product ulps      */
-                               /* (|error| <= 2^-22 |a||b| per product), reported SEPARATELY from the fp32-MFMA mode     */ };
+                               /* (|error| <= 2^-22 |a||b| per product), reported SEPARATELY from the fp32-MFMA mode     */
+       HIPETS_PREC_BF16 = 2    /* reduced precision, reported SEPARATELY with its own parity tolerance: for every linear  */
+                               /* layer both operands are rounded to bf16 (round-to-nearest-even), products are exact,   */
+                               /* accumulation is fp32 on v_mfma_f32_16x16x32_bf16 (ONE MFMA per 16x16x32 block), bias   */
+                               /* is added in fp32, SiLU is computed in fp32.  A hidden layer's activated result is     */
+                               /* stored as one bf16 per value: that store is the rounding of the next layer's operand; */
+                               /* the output layer's results stay fp32.  Everything outside the linear layers (f64      */
+                               /* normaliser, logvar clamps, sampling, delta add, reward / termination, totals, the     */
+                               /* fp32 state and its hand-over, Philox streams and permutations) is the fp32 mode's.    */ };
 /* randomness source of a rollout */
 enum { HIPETS_MODE_EXACT = 0,  /* reference semantics, injected perms / eps (parity mode)                              */
        HIPETS_MODE_FAST = 1,   /* whole-horizon kernel, block-balanced member schedule, in-kernel Philox             */
@@ -110,7 +118,7 @@ typedef struct {
     const void* const* weights; /* HOST array [n_layers] of DEVICE float [E, in_l, out_l]         */
     const void* const* biases;  /* HOST array [n_layers] of DEVICE float [E, 1, out_l]            */
     int32_t ensemble_kind;   /* HIPETS_ENSEMBLE_*                                                 */
-    int32_t precision;       /* HIPETS_PREC_*: BF16X3 runs only where a shape-specialised kernel instance   */
+    int32_t precision;       /* HIPETS_PREC_*: BF16X3 / BF16 run only where a shape-specialised kernel instance */
                              /*   exists for the model and the call (else the rollout call fails)           */
 } hipets_model_desc;
 
@@ -213,8 +221,10 @@ int hipets_fast_geometry(hipets_engine* e, int32_t pop, int32_t num_particles, i
  *                  the BASELINE.json configurations and the conf/overrides/pets_*.yaml workloads without a termination function
  *                  that reads every state dim)
  *   WIDE           FUSED for output layers wider than 8 column tiles (Humanoid-v4)
+ *   BF16           a shape-specialised instance in HIPETS_PREC_BF16 arithmetic (launch.hpp HIPETS_BF16_SHAPES_R*)
  * Diagnostic only -- nothing needs to call it; a profile (rocprofv3 --kernel-trace) shows the same thing as a kernel name.      */
-enum { HIPETS_KERNEL_GENERIC = 0, HIPETS_KERNEL_HIDDEN_STATIC = 1, HIPETS_KERNEL_FUSED = 2, HIPETS_KERNEL_WIDE = 3 };
+enum { HIPETS_KERNEL_GENERIC = 0, HIPETS_KERNEL_HIDDEN_STATIC = 1, HIPETS_KERNEL_FUSED = 2, HIPETS_KERNEL_WIDE = 3,
+       HIPETS_KERNEL_BF16 = 4 /* a shape-specialised instance in HIPETS_PREC_BF16 arithmetic */ };
 int hipets_kernel_class(hipets_engine* e, int32_t pop, int32_t num_particles, int32_t horizon, int32_t mode, int32_t rows_per_group,
                         int32_t* kernel_class, int32_t* row_tiles);
 

@@ -88,7 +88,7 @@ struct hipets_engine {
     bool has_model = false;
     ModelDev md{};
     int ensemble_size = 0;
-    DevBuf w3pack;  // bf16x3 precision mode: weight pieces
+    DevBuf w3pack;  // bf16x3 / bf16 precision modes: weight pieces (three bf16 planes / one)
     DevBuf wpack, bpack, layer_meta, norm_mean, norm_std, min_lv, max_lv, no_delta, members;
     // rollout workspace
     DevBuf s0, state, totals, term;
@@ -165,6 +165,9 @@ int launch_rollout(hipets_engine* e, int R, int grid, size_t lds, const RolloutA
         default: return fail("unsupported rows_per_group %d (1..%d)", R, kMaxR);
     }
     if (timed) e->events.emplace_back(a, b);  // recorded (or leaked to the pool) either way
+    if (err == hipErrorNotSupported && e->md.precision == HIPETS_PREC_BF16)
+        return fail("precision bf16: no shape-specialised kernel instance for this model / call (SiLU, f64 normaliser, no obs "
+                    "preprocessing, in-kernel sampling, one of the two bf16 layer shapes, R = %d); use precision f32", R);
     if (err == hipErrorNotSupported && e->md.precision == HIPETS_PREC_BF16X3)
         return fail("precision bf16x3: no shape-specialised kernel instance for this model / call (SiLU, f64 normaliser, no obs "
                     "preprocessing, in-kernel sampling, one of the BASELINE layer shapes, R = %d); use precision f32", R);
@@ -211,9 +214,9 @@ int choose_R(const hipets_engine* e, long long tiles_total_per_slice, int slices
     const double a = (wide ? (drift ? 6.45 : 2.67) : 1.77) * (double)C / 13.0;
     int best = 1;
     double best_cost = 1e300;
-    // bf16x3 arithmetic exists in shape-specialised instances only: among the R that have one (if any has: else the launch reports it)
+    // bf16x3 / bf16 arithmetic exists in shape-specialised instances only: among the R that have one (if any has: else the launch reports it)
     bool b3_only = false;
-    if (e->md.precision == HIPETS_PREC_BF16X3)
+    if (e->md.precision != HIPETS_PREC_F32)
         for (int R = 1; R <= kMaxR; ++R) b3_only = b3_only || b3_shape_exists(e->md, R);
     for (int R = 1; R <= kMaxR; ++R) {
         if (lds_for(e, R, horizon, wide) > e->lds_max) break;
@@ -635,14 +638,15 @@ int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream)
         boff += out.Np;
     }
     md.precision = d->precision;
-    if (d->precision != HIPETS_PREC_F32 && d->precision != HIPETS_PREC_BF16X3) return fail("unknown precision %d", d->precision);
+    if (d->precision != HIPETS_PREC_F32 && d->precision != HIPETS_PREC_BF16X3 && d->precision != HIPETS_PREC_BF16) return fail("unknown precision %d", d->precision);
+    const int pieces = d->precision == HIPETS_PREC_BF16 ? 1 : 3;  // bf16 planes per weight (bf16: piece 0 of the split alone)
     long long w3off = 0;  // 16-byte units
     int max_kc32 = 1;
     for (int l = 0; l < d->n_layers; ++l) {
         lms[l].Kp32 = (Ks[l] + 31) / 32 * 32;
         lms[l].pad_ = 0;
         lms[l].woff3 = w3off;
-        w3off += (long long)(lms[l].Np / 16) * (lms[l].Kp32 / 32) * 3 * 64;
+        w3off += (long long)(lms[l].Np / 16) * (lms[l].Kp32 / 32) * pieces * 64;
         max_kc32 = std::max(max_kc32, lms[l].Kp32 / 32);
     }
     md.w3member = w3off;
@@ -654,10 +658,10 @@ int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream)
     // row stride: >= widest activation, == 8 (mod 64) floats => conflict-free ds_read_b128 A fragments
     int ld = maxK;
     while (ld % 64 != 8) ld += 4;
-    if (d->precision == HIPETS_PREC_BF16X3) {
-        // activation rows hold [k chunk of 32][3 pieces][32 x bf16] = 192 bytes per chunk; the last layer's fp32 results share the
+    if (d->precision != HIPETS_PREC_F32) {
+        // activation rows hold [k chunk of 32][3 pieces][32 x bf16] = 192 bytes per chunk (bf16: one piece, 64 bytes); the last layer's fp32 results share the
         // rows; a byte stride that is an ODD multiple of 16 keeps the ds_read_b128 of 16 consecutive rows on distinct slots
-        int ldb = std::max(max_kc32 * 192, lms[d->n_layers - 1].Np * 4);
+        int ldb = std::max(max_kc32 * 64 * pieces, lms[d->n_layers - 1].Np * 4);
         ldb = (ldb + 15) / 16 * 16;
         if ((ldb / 16) % 2 == 0) ldb += 16;
         ld = ldb / 4;
@@ -669,7 +673,7 @@ int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream)
                            md.propagation == HIPETS_PROP_EXPECTATION, md.lv_rows) > e->lds_max)
         return fail("model too wide for LDS (ld=%d)", md.ld);
 
-    if (d->precision == HIPETS_PREC_BF16X3 && e->w3pack.ensure((size_t)md.w3member * md.M * 16)) return 1;
+    if (d->precision != HIPETS_PREC_F32 && e->w3pack.ensure((size_t)md.w3member * md.M * 16)) return 1;
     if (e->wpack.ensure((size_t)md.wmember * md.M * 4)) return 1;
     if (e->bpack.ensure((size_t)md.bmember * md.M * 4)) return 1;
     if (e->members.ensure((size_t)md.M * 4)) return 1;
@@ -682,11 +686,11 @@ int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream)
                            reinterpret_cast<const float*>(d->weights[l]), e->members.as<int>(), md.M, Ks[l], Ns[l], lms[l].Kp,
                            lms[l].Np, md.wmember, lms[l].woff, l < d->n_layers - 1 ? 1 : 0, 0);
         HCHECK(hipGetLastError());
-        if (d->precision == HIPETS_PREC_BF16X3) {
-            const long long n3 = (long long)(lms[l].Np / 16) * (lms[l].Kp32 / 32) * 3 * 64 * md.M;
+        if (d->precision != HIPETS_PREC_F32) {
+            const long long n3 = (long long)(lms[l].Np / 16) * (lms[l].Kp32 / 32) * pieces * 64 * md.M;
             hipLaunchKernelGGL(pack_weights_b3_kernel, dim3((unsigned)((n3 + 255) / 256)), dim3(256), 0, st, e->w3pack.as<uint4>(),
                                reinterpret_cast<const float*>(d->weights[l]), e->members.as<int>(), md.M, Ks[l], Ns[l], lms[l].Kp32, lms[l].Np,
-                               md.w3member, lms[l].woff3, 0);
+                               md.w3member, lms[l].woff3, 0, pieces);
             HCHECK(hipGetLastError());
         }
         const int nb = md.M * lms[l].Np;
@@ -776,10 +780,12 @@ int hipets_kernel_class(hipets_engine* e, int32_t pop, int32_t P, int32_t horizo
     int cls = HIPETS_KERNEL_GENERIC;
     switch (pick_rollout_instance(md, probe, g.R)) {
         case RolloutInstance::lean: case RolloutInstance::b3: cls = HIPETS_KERNEL_FUSED; break;
+        case RolloutInstance::bf16: cls = HIPETS_KERNEL_BF16; break;
         case RolloutInstance::lean_wide: cls = HIPETS_KERNEL_WIDE; break;
         case RolloutInstance::hidden_static: cls = HIPETS_KERNEL_HIDDEN_STATIC; break;
         case RolloutInstance::generic_silu: case RolloutInstance::generic: break;
         case RolloutInstance::no_b3: return fail("bf16x3 arithmetic exists for the shape-specialised instances only");
+        case RolloutInstance::no_bf16: return fail("bf16 arithmetic exists for the shape-specialised instances only");
         case RolloutInstance::no_wide: return fail("no WIDE instance of this model's shape for R = %d", g.R);
     }
     if (kernel_class) *kernel_class = cls;

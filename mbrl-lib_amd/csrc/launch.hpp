@@ -64,6 +64,13 @@ hipError_t launch_rollout_r4(int grid, unsigned lds, int lds_max, const ModelDev
 #define HIPETS_B3_SHAPES_R3(X) X(13, 3, HIPETS_REW_HALFCHEETAH, HIPETS_TERM_NONE) X(13, 6, HIPETS_REW_HALFCHEETAH, HIPETS_TERM_HUMANOID)
 #define HIPETS_B3_SHAPES_R4(X)
 
+// bf16 precision instances per R (HIPETS_PREC_BF16: one bf16 piece per operand, one MFMA per block), same row format; the two shapes
+// bf16x3 has, at R = 3.  (One-plane rows make R = 4 fit in LDS and R = 2 the register file: no such instance until a measurement asks for it.)
+#define HIPETS_BF16_SHAPES_R1(X)
+#define HIPETS_BF16_SHAPES_R2(X)
+#define HIPETS_BF16_SHAPES_R3(X) X(13, 3, HIPETS_REW_HALFCHEETAH, HIPETS_TERM_NONE) X(13, 6, HIPETS_REW_HALFCHEETAH, HIPETS_TERM_HUMANOID)
+#define HIPETS_BF16_SHAPES_R4(X)
+
 // what the fused tail's reward / termination lane can see of THIS model: termination functions that test every state dim need all of them
 // among the four it holds; a learned reward next to a termination function comes from another lane of the same accumulator (column
 // tile 0 holds output columns 0..7)
@@ -74,7 +81,7 @@ inline bool fused_term_ok(const ModelDev& md) {
     return true;
 }
 
-// the model-side facts every shape-specialised instance (lean fp32 and bf16x3) was compiled for; the lean ones add fp32 arithmetic
+// the model-side facts every shape-specialised instance (lean fp32, bf16x3 and bf16) was compiled for; the lean ones add fp32 arithmetic
 // (lean_shape), the call adds its own (lean_call)
 inline bool spec_model(const ModelDev& md) {
     return md.activation == HIPETS_ACT_SILU && md.normalizer == HIPETS_NORM_F64 && !md.deterministic && md.propagation != HIPETS_PROP_EXPECTATION &&
@@ -100,7 +107,7 @@ using LeanSpec = KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, OB, RW, TM, KMO
 inline bool lean_shape_is(const ModelDev& md, const int hc, const int oc, const int rw, const int tm, const int ob) {
     return md.hidC == hc && md.outC == oc && md.reward_fn == rw && md.term_fn == tm && md.obs_process == ob && md.ld == lean_ld(hc, oc);
 }
-// ... of the bf16x3 instance X(hc, oc, rw, tm)
+// ... of the bf16x3 or bf16 instance X(hc, oc, rw, tm)
 inline bool b3_shape_is(const ModelDev& md, const int hc, const int oc, const int rw, const int tm) {
     return md.hidC == hc && md.outC == oc && md.reward_fn == rw && md.term_fn == tm && md.obs_process == HIPETS_OBS_NONE;
 }
@@ -135,15 +142,26 @@ inline bool wide_model(const ModelDev& md) {
     return false;
 }
 
-// is there a bf16x3 instance of this model's shape for R row tiles?
+// is there an instance of this model's shape for R row tiles in the model's own bf16x3 / bf16 arithmetic?  (fp32 models: no)
 inline bool b3_shape_exists(const ModelDev& md, const int R) {
 #define HIPETS_HAS_B3(HC, OC, RW, TM) \
     if (b3_shape_is(md, HC, OC, RW, TM)) return true;
-    switch (R) {
-        case 1: HIPETS_B3_SHAPES_R1(HIPETS_HAS_B3) break;
-        case 2: HIPETS_B3_SHAPES_R2(HIPETS_HAS_B3) break;
-        case 3: HIPETS_B3_SHAPES_R3(HIPETS_HAS_B3) break;
-        default: break;
+    if (md.precision == HIPETS_PREC_BF16X3) {
+        switch (R) {
+            case 1: HIPETS_B3_SHAPES_R1(HIPETS_HAS_B3) break;
+            case 2: HIPETS_B3_SHAPES_R2(HIPETS_HAS_B3) break;
+            case 3: HIPETS_B3_SHAPES_R3(HIPETS_HAS_B3) break;
+            case 4: HIPETS_B3_SHAPES_R4(HIPETS_HAS_B3) break;
+            default: break;
+        }
+    } else if (md.precision == HIPETS_PREC_BF16) {
+        switch (R) {
+            case 1: HIPETS_BF16_SHAPES_R1(HIPETS_HAS_B3) break;
+            case 2: HIPETS_BF16_SHAPES_R2(HIPETS_HAS_B3) break;
+            case 3: HIPETS_BF16_SHAPES_R3(HIPETS_HAS_B3) break;
+            case 4: HIPETS_BF16_SHAPES_R4(HIPETS_HAS_B3) break;
+            default: break;
+        }
     }
 #undef HIPETS_HAS_B3
     return false;
@@ -162,12 +180,14 @@ inline bool hid_static_call(const ModelDev& md, const RolloutArgs& ra) {
 
 // The instance of rollout_kernel<R, ...> a call runs -- the one selection rule: the launcher of rollout_r<R>.hip dispatches on it,
 // hipets_kernel_class reports it.  lean_wide: a KSpec::WIDE lean instance, which runs exactly where the host sized the LDS for its
-// layout (RolloutArgs::wide_lds); generic_silu: the generic instance with the SiLU epilogue fixed.  Refusals: no_b3 (bf16x3 arithmetic
-// exists in shape-specialised instances only), no_wide (LDS sized for a WIDE instance that does not exist for this R / call).
-enum class RolloutInstance { lean, lean_wide, b3, hidden_static, generic_silu, generic, no_b3, no_wide };
+// layout (RolloutArgs::wide_lds); generic_silu: the generic instance with the SiLU epilogue fixed.  Refusals: no_b3 / no_bf16 (bf16x3 and
+// bf16 arithmetic exist in shape-specialised instances only: a model or call without one fails, it never runs another arithmetic),
+// no_wide (LDS sized for a WIDE instance that does not exist for this R / call).
+enum class RolloutInstance { lean, lean_wide, b3, bf16, hidden_static, generic_silu, generic, no_b3, no_bf16, no_wide };
 inline RolloutInstance pick_rollout_instance(const ModelDev& md, const RolloutArgs& ra, const int R) {
     const bool lean = lean_call(md, ra);
     if (md.precision == HIPETS_PREC_BF16X3) return lean && b3_shape_exists(md, R) ? RolloutInstance::b3 : RolloutInstance::no_b3;
+    if (md.precision == HIPETS_PREC_BF16) return lean && b3_shape_exists(md, R) ? RolloutInstance::bf16 : RolloutInstance::no_bf16;
     if (lean && lean_shape(md, R) == (ra.wide_lds ? LeanShape::wide : LeanShape::plain)) return ra.wide_lds ? RolloutInstance::lean_wide : RolloutInstance::lean;
     if (ra.wide_lds) return RolloutInstance::no_wide;
     if (hid_static_call(md, ra)) return RolloutInstance::hidden_static;

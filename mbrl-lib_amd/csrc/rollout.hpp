@@ -31,7 +31,7 @@ struct LayerMeta {
     int boff;            // float offset of the layer's bias inside a member block
     int tail_steps;      // MFMA k-steps (of 4) of the last chunk that hold real weights: ceil((K - (Kp - 16)) / 4)
     long long woff;      // float offset of the layer's packed weights inside a member block
-    // bf16x3 precision mode (fp32 operands as three bf16 pieces on the bf16 matrix pipe):
+    // bf16x3 / bf16 precision modes (operands as three bf16 pieces, or one, on the bf16 matrix pipe):
     int Kp32;            // K padded to a multiple of 32 (one v_mfma_f32_16x16x32_bf16 k-chunk)
     int pad_;
     long long woff3;     // 16-byte-unit offset of the layer's packed bf16 planes inside a member block
@@ -81,8 +81,8 @@ struct ModelDev {
     int iid_members;      // BasicEnsemble: members are drawn independently (no balanced shuffle, no batch % M rule)
     const unsigned char* no_delta;  // [obs_dim]
     int precision;            // HIPETS_PREC_*
-    long long w3member;       // 16-byte units per member (bf16x3 planes)
-    const uint4* w3;          // packed bf16 planes: [member][layer][col tile][k chunk of 32][plane 0..2][lane][8 x bf16]
+    long long w3member;       // 16-byte units per member (bf16 planes: three in bf16x3, one in bf16)
+    const uint4* w3;          // packed bf16 planes: [member][layer][col tile][k chunk of 32][plane 0..NP-1][lane][8 x bf16]
 };
 
 struct RolloutArgs {
@@ -967,6 +967,8 @@ __device__ __forceinline__ void linear_op(const float* W, const float* bias, con
 // Layouts: weights packed per (column tile, 32-wide k chunk, piece) as one A-operand fragment (lane l: output column
 // l & 15, k = 8 (l >> 4) .. + 7); activations in LDS per row as [k chunk][piece][4 groups][8 x bf16] so that a lane's
 // B-operand fragment of a piece is ONE ds_read_b128.  The last layer's results stay fp32 (sampling reads them).
+// Precision bf16 (HIPETS_PREC_BF16) is the one-piece form of the same code (template parameter NP = 1): piece 0 alone, i.e. both
+// operands rounded to bf16 (nearest-even), exact products, fp32 accumulation, ONE MFMA per block; bias and SiLU in fp32.
 // ---------------------------------------------------------------------------------------------------------------------
 using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
@@ -994,19 +996,21 @@ __host__ __device__ __forceinline__ void split3(float x, unsigned (&h)[3]) {
 // four consecutive values -> per piece one 8-byte word pair (4 x bf16, little endian: value 0 in the low half of word 0).
 // v_cvt_pk_bf16_f32 rounds two floats to nearest-even and packs them in exactly that order: one conversion, two bit
 // operations and one packed subtract per pair and piece (the host-side split3 above states the same arithmetic bit by bit).
-__device__ __forceinline__ void split3x4(const f32x4 v, u32x2 (&out)[3]) {
+// NP = 1 keeps piece 0 alone: the plain bf16 rounding of precision bf16 (HIPETS_PREC_BF16).
+template <int NP>
+__device__ __forceinline__ void split_x4(const f32x4 v, u32x2 (&out)[NP]) {
     using f32p = __attribute__((ext_vector_type(2))) float;
     using bf16p = __attribute__((ext_vector_type(2))) __bf16;
     f32p lo = {v[0], v[1]}, hi = {v[2], v[3]};
 #pragma unroll
-    for (int p = 0; p < 3; ++p) {
+    for (int p = 0; p < NP; ++p) {
         const bf16p hl = __builtin_convertvector(lo, bf16p), hh = __builtin_convertvector(hi, bf16p);
         unsigned ul, uh;
         __builtin_memcpy(&ul, &hl, 4);
         __builtin_memcpy(&uh, &hh, 4);
         out[p][0] = ul;
         out[p][1] = uh;
-        if (p < 2) {
+        if (p + 1 < NP) {
             lo = lo - f32p{bits_to_float(ul << 16), bits_to_float(ul & 0xFFFF0000u)};
             hi = hi - f32p{bits_to_float(uh << 16), bits_to_float(uh & 0xFFFF0000u)};
         }
@@ -1017,21 +1021,28 @@ __device__ __forceinline__ bf16x8 as_bf16x8(const u32x4 v) {
     __builtin_memcpy(&r, &v, 16);
     return r;
 }
-// byte offset inside an activation row of the 4 consecutive columns k0 .. k0 + 3 (k0 % 4 == 0) of piece p
-__device__ __forceinline__ int b3_offset(int k0, int p) { return (k0 >> 5) * 192 + p * 64 + ((k0 & 31) >> 3) * 16 + (k0 & 7) * 2; }
+// byte offset inside an activation row of the 4 consecutive columns k0 .. k0 + 3 (k0 % 4 == 0) of piece p of NP
+template <int NP>
+__device__ __forceinline__ int b3_offset(int k0, int p) { return (k0 >> 5) * (64 * NP) + p * 64 + ((k0 & 31) >> 3) * 16 + (k0 & 7) * 2; }
 
-template <int R, int CT, int EX>
+template <int R, int CT, int EX, int NP>
 struct GemmFragsB3 {
-    u32x4 w[CT > 0 ? CT : 1][3];   // weight pieces (A operand) of the strided column tiles
-    u32x4 wx[EX > 0 ? EX : 1][3];  // ... of the extra units
-    u32x4 a[R][3];                 // activation pieces (B operand) of the row tiles
-    u32x4 ax[EX > 0 ? EX : 1][3];
+    u32x4 w[CT > 0 ? CT : 1][NP];   // weight pieces (A operand) of the strided column tiles
+    u32x4 wx[EX > 0 ? EX : 1][NP];  // ... of the extra units
+    u32x4 a[R][NP];                 // activation pieces (B operand) of the row tiles
+    u32x4 ax[EX > 0 ? EX : 1][NP];
 };
 
 // One wave's share of a linear op in bf16x3 arithmetic: same unit decomposition as wave_gemm (CT strided column tiles x R row
 // tiles + EX extra units).  `in`: LDS activation pieces (byte stride ldb); hidden ops write the activated result as pieces into
 // `out`, the last op writes fp32 (float stride ldb / 4) for the sampling phase.
-template <int R, int CT, int EX, int ACT>
+// NP = 3: precision bf16x3.  NP = 1: precision bf16 -- one weight and one activation fragment per unit, ONE MFMA per unit and k
+// chunk, activation rows of 64 bytes per chunk; the bf16 store of a hidden layer's activated result IS the rounding of the next
+// layer's operand.  Its k loop is paced by the fragment loads, not by the MFMAs: fragments are requested kBf16Ahead chunks ahead
+// (measured per cfg2 rollout, DEVICE / FAST: 2 ahead 0.443 / 0.362 ms, 4 ahead 0.437 / 0.356 ms, all 7 chunks of a hidden layer
+// 0.450 / 0.375 ms -- profiles/bf16_rollout.json).
+constexpr int kBf16Ahead = 4;
+template <int R, int CT, int EX, int ACT, int NP>
 __device__ __forceinline__ void wave_gemm_b3(const char* __restrict__ in, char* __restrict__ out, const int ldb, const uint4* __restrict__ W3,
                                              const float* __restrict__ bias, const int KC32, const int c_first, const Extras ex,
                                              const bool last_op, const int lane) {
@@ -1041,14 +1052,15 @@ __device__ __forceinline__ void wave_gemm_b3(const char* __restrict__ in, char* 
     f32x4 accx[EXn];
     const int exc[kMaxExtras] = {ex.c0, ex.c1, ex.c2, ex.c3};
     const int exr[kMaxExtras] = {ex.r0, ex.r1, ex.r2, ex.r3};
-    // weights: 16-byte units; (column tile c, chunk kk, piece p, lane) -> ((c * KC32 + kk) * 3 + p) * 64 + lane
+    // weights: 16-byte units; (column tile c, chunk kk, piece p, lane) -> ((c * KC32 + kk) * NP + p) * 64 + lane
+    constexpr int kCh = 64 * NP;  // 16-byte weight units per (column tile, chunk) -- and bytes per chunk of an activation row
     unsigned woff[CTn], wxoff[EXn];
     int axoff[EXn];
 #pragma unroll
-    for (int ct = 0; ct < CT; ++ct) woff[ct] = (unsigned)((c_first + kWaves * ct) * KC32 * 192 + lane);
+    for (int ct = 0; ct < CT; ++ct) woff[ct] = (unsigned)((c_first + kWaves * ct) * KC32 * kCh + lane);
 #pragma unroll
     for (int e = 0; e < EX; ++e) {
-        wxoff[e] = (unsigned)(exc[e] * KC32 * 192 + lane);
+        wxoff[e] = (unsigned)(exc[e] * KC32 * kCh + lane);
         axoff[e] = exr[e] * 16 * ldb;
     }
     const char* ap = in + (lane & 15) * ldb + (lane >> 4) * 16;
@@ -1069,35 +1081,37 @@ __device__ __forceinline__ void wave_gemm_b3(const char* __restrict__ in, char* 
 #pragma unroll
     for (int e = 0; e < EXn; ++e) accx[e] = EX > 0 ? bias4(exc[e]) : f32x4{0.f, 0.f, 0.f, 0.f};
 
-    auto load = [&](GemmFragsB3<R, CT, EX>& f, const int kk) __attribute__((always_inline)) {
-        const uint4* Wk = W3 + (size_t)kk * 192;
+    auto load = [&](GemmFragsB3<R, CT, EX, NP>& f, const int kk) __attribute__((always_inline)) {
+        const uint4* Wk = W3 + (size_t)kk * kCh;
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) f.w[ct][p] = *reinterpret_cast<const u32x4*>(Wk + woff[ct] + p * 64);
+            for (int p = 0; p < NP; ++p) f.w[ct][p] = *reinterpret_cast<const u32x4*>(Wk + woff[ct] + p * 64);
 #pragma unroll
         for (int e = 0; e < EX; ++e)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) f.wx[e][p] = *reinterpret_cast<const u32x4*>(Wk + wxoff[e] + p * 64);
+            for (int p = 0; p < NP; ++p) f.wx[e][p] = *reinterpret_cast<const u32x4*>(Wk + wxoff[e] + p * 64);
 #pragma unroll
         for (int r = 0; r < R; ++r)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) f.a[r][p] = *reinterpret_cast<const u32x4*>(ap + r * 16 * ldb + kk * 192 + p * 64);
+            for (int p = 0; p < NP; ++p) f.a[r][p] = *reinterpret_cast<const u32x4*>(ap + r * 16 * ldb + kk * kCh + p * 64);
 #pragma unroll
         for (int e = 0; e < EX; ++e)
 #pragma unroll
-            for (int p = 0; p < 3; ++p) f.ax[e][p] = *reinterpret_cast<const u32x4*>(ap + axoff[e] + kk * 192 + p * 64);
+            for (int p = 0; p < NP; ++p) f.ax[e][p] = *reinterpret_cast<const u32x4*>(ap + axoff[e] + kk * kCh + p * 64);
     };
-    // the six partial products of one unit, smallest weights first
-    auto unit = [&](const u32x4 (&w)[3], const u32x4 (&a)[3], f32x4& c) __attribute__((always_inline)) {
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[2]), as_bf16x8(a[0]), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[1]), as_bf16x8(a[1]), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[0]), as_bf16x8(a[2]), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[1]), as_bf16x8(a[0]), c, 0, 0, 0);
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[0]), as_bf16x8(a[1]), c, 0, 0, 0);
+    // the six partial products of one unit, smallest weights first (NP = 1: the one product)
+    auto unit = [&](const u32x4 (&w)[NP], const u32x4 (&a)[NP], f32x4& c) __attribute__((always_inline)) {
+        if constexpr (NP == 3) {
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[2]), as_bf16x8(a[0]), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[1]), as_bf16x8(a[1]), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[0]), as_bf16x8(a[2]), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[1]), as_bf16x8(a[0]), c, 0, 0, 0);
+            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[0]), as_bf16x8(a[1]), c, 0, 0, 0);
+        }
         c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[0]), as_bf16x8(a[0]), c, 0, 0, 0);
     };
-    auto compute = [&](const GemmFragsB3<R, CT, EX>& f) __attribute__((always_inline)) {
+    auto compute = [&](const GemmFragsB3<R, CT, EX, NP>& f) __attribute__((always_inline)) {
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
@@ -1105,20 +1119,40 @@ __device__ __forceinline__ void wave_gemm_b3(const char* __restrict__ in, char* 
 #pragma unroll
         for (int e = 0; e < EX; ++e) unit(f.wx[e], f.ax[e], accx[e]);
     };
-    GemmFragsB3<R, CT, EX> f0, f1;
-    load(f0, 0);
-    int kk = 0;
-    for (; kk + 1 < KC32; kk += 2) {
-        load(f1, kk + 1);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(f0);
-        __builtin_amdgcn_sched_barrier(0);
-        if (kk + 2 < KC32) load(f0, kk + 2);
-        __builtin_amdgcn_sched_barrier(0);
-        compute(f1);
-        __builtin_amdgcn_sched_barrier(0);
+    if constexpr (NP == 1) {
+        // a ring of kBf16Ahead fragment sets (32 registers each at R = 3): slot i holds chunks i, i + kBf16Ahead, ...; a slot is
+        // refilled as soon as its MFMAs are issued, so kBf16Ahead - 1 chunks of loads are in flight behind every compute
+        GemmFragsB3<R, CT, EX, NP> f[kBf16Ahead];
+#pragma unroll
+        for (int i = 0; i < kBf16Ahead; ++i)
+            if (i < KC32) load(f[i], i);
+        for (int kk = 0; kk < KC32; kk += kBf16Ahead) {
+#pragma unroll
+            for (int i = 0; i < kBf16Ahead; ++i) {
+                if (kk + i < KC32) {
+                    __builtin_amdgcn_sched_barrier(0);
+                    compute(f[i]);
+                    __builtin_amdgcn_sched_barrier(0);
+                    if (kk + i + kBf16Ahead < KC32) load(f[i], kk + i + kBf16Ahead);
+                }
+            }
+        }
+    } else {
+        GemmFragsB3<R, CT, EX, NP> f0, f1;
+        load(f0, 0);
+        int kk = 0;
+        for (; kk + 1 < KC32; kk += 2) {
+            load(f1, kk + 1);
+            __builtin_amdgcn_sched_barrier(0);
+            compute(f0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (kk + 2 < KC32) load(f0, kk + 2);
+            __builtin_amdgcn_sched_barrier(0);
+            compute(f1);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+        if (kk < KC32) compute(f0);
     }
-    if (kk < KC32) compute(f0);
 
     const int j = lane & 15, g4 = 4 * (lane >> 4);
     auto silu4 = [](const f32x4 a) {
@@ -1134,15 +1168,15 @@ __device__ __forceinline__ void wave_gemm_b3(const char* __restrict__ in, char* 
         const f32x2 yl = lo * tl, yh = hi * th;
         return f32x4{yl[0], yl[1], yh[0], yh[1]};
     };
-    static_assert(ACT == HIPETS_ACT_SILU, "bf16x3 instances exist for SiLU models");
+    static_assert(ACT == HIPETS_ACT_SILU, "bf16x3 / bf16 instances exist for SiLU models");
     auto store = [&](const f32x4 v, const int row, const int col0) __attribute__((always_inline)) {
         if (last_op) {
             *reinterpret_cast<f32x4*>(out + (size_t)row * ldb + col0 * 4) = v;  // fp32, natural columns (float stride ldb / 4)
         } else {
-            u32x2 pc[3];
-            split3x4(silu4(v), pc);
+            u32x2 pc[NP];
+            split_x4<NP>(silu4(v), pc);
 #pragma unroll
-            for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x2*>(out + (size_t)row * ldb + b3_offset(col0, p)) = pc[p];
+            for (int p = 0; p < NP; ++p) *reinterpret_cast<u32x2*>(out + (size_t)row * ldb + b3_offset<NP>(col0, p)) = pc[p];
         }
     };
 #pragma unroll
@@ -1153,13 +1187,13 @@ __device__ __forceinline__ void wave_gemm_b3(const char* __restrict__ in, char* 
     for (int e = 0; e < EX; ++e) store(accx[e], exr[e] * 16 + j, exc[e] * 16 + g4);
 }
 
-// linear op with CS column tiles in bf16x3 arithmetic (static shapes only: the lean instances)
-template <int R, int ACT, int CS>
+// linear op with CS column tiles in bf16x3 (NP = 3) or bf16 (NP = 1) arithmetic (static shapes only: the lean instances)
+template <int R, int ACT, int CS, int NP>
 __device__ __forceinline__ void linear_op_b3(const uint4* W3, const float* bias, const int KC32, const int ldb, const bool last_op, const char* in,
                                              char* out, const int wave, const int lane) {
     constexpr int kMaxCT = 3;
     constexpr int full = CS / kWaves, rem = CS % kWaves, nu = rem * R;
-    static_assert(full <= kMaxCT, "bf16x3 instances cover ops of at most 15 column tiles");
+    static_assert(full <= kMaxCT, "bf16x3 / bf16 instances cover ops of at most 15 column tiles");
     Extras ex;
     ex.c0 = kWaves * full + wave / R;                ex.r0 = wave % R;
     ex.c1 = kWaves * full + (wave + kWaves) / R;     ex.r1 = (wave + kWaves) % R;
@@ -1167,12 +1201,12 @@ __device__ __forceinline__ void linear_op_b3(const uint4* W3, const float* bias,
     ex.c3 = kWaves * full + (wave + 3 * kWaves) / R; ex.r3 = (wave + 3 * kWaves) % R;
     constexpr int lo = nu / kWaves, hi = (nu + kWaves - 1) / kWaves;
     if constexpr (lo == hi) {
-        if constexpr (full > 0 || lo > 0) wave_gemm_b3<R, full, lo, ACT>(in, out, ldb, W3, bias, KC32, wave, ex, last_op, lane);
+        if constexpr (full > 0 || lo > 0) wave_gemm_b3<R, full, lo, ACT, NP>(in, out, ldb, W3, bias, KC32, wave, ex, last_op, lane);
     } else {
         if (wave < nu % kWaves) {
-            wave_gemm_b3<R, full, hi, ACT>(in, out, ldb, W3, bias, KC32, wave, ex, last_op, lane);
+            wave_gemm_b3<R, full, hi, ACT, NP>(in, out, ldb, W3, bias, KC32, wave, ex, last_op, lane);
         } else {
-            if constexpr (full > 0 || lo > 0) wave_gemm_b3<R, full, lo, ACT>(in, out, ldb, W3, bias, KC32, wave, ex, last_op, lane);
+            if constexpr (full > 0 || lo > 0) wave_gemm_b3<R, full, lo, ACT, NP>(in, out, ldb, W3, bias, KC32, wave, ex, last_op, lane);
         }
     }
 }
@@ -1207,7 +1241,8 @@ struct KSpec {
     static constexpr bool WIDE = FUSE_ != 0 && HIDC_ >= 0 && PREC_ == HIPETS_PREC_F32 && OUTC_ > kSplMaxTiles;
     static constexpr int LD = (HIDC_ >= 0 && PREC_ == HIPETS_PREC_F32) ? lean_ld(HIDC_, WIDE ? HIDC_ : OUTC_) : -1;  // compile-time LDS row stride (fp32 lean instances)
     static constexpr int ACT = ACT_, HIDC = HIDC_, OUTC = OUTC_, NORM = NORM_, OBSP = OBSP_, REW = REW_, TERM = TERM_, KMODE = KMODE_;
-    static constexpr int PREC = PREC_;  // HIPETS_PREC_F32 (fp32 MFMA) or HIPETS_PREC_BF16X3 (lean instances only)
+    static constexpr int PREC = PREC_;  // HIPETS_PREC_F32 (fp32 MFMA), or HIPETS_PREC_BF16X3 / HIPETS_PREC_BF16 (lean instances only)
+    static constexpr int PIECES = PREC_ == HIPETS_PREC_BF16X3 ? 3 : (PREC_ == HIPETS_PREC_BF16 ? 1 : 0);  // bf16 pieces per operand on the bf16 matrix pipe
     static constexpr bool LEAN = HIDC_ >= 0 && OUTC_ >= 0;
     // HIDDEN-STATIC instances (HIDC_ >= 0, everything else decided at run time): what ANY model with that hidden width gets --
     // the reference's default is 200 = 13 column tiles (conf/dynamics_model/gaussian_mlp_ensemble.yaml:8), whatever its
@@ -1255,7 +1290,7 @@ struct KSpec {
     static_assert(!FUSE || OBSP_ == HIPETS_OBS_NONE || OBSP_ == HIPETS_OBS_HALFCHEETAH || OBSP_ == HIPETS_OBS_CARTPOLE_PETS, "unknown obs preprocessing");
 };
 
-// Layer l in bf16x3 arithmetic
+// Layer l in bf16x3 / bf16 arithmetic
 template <int R, class S>
 __device__ __forceinline__ void mlp_layer_b3(const ModelDev& md, const LayerMeta* lmeta, const int l, const int member, const float* in, float* out,
                                              const int wave, const int lane) {
@@ -1264,8 +1299,8 @@ __device__ __forceinline__ void mlp_layer_b3(const ModelDev& md, const LayerMeta
     const float* bias = md.b + (size_t)member * md.bmember + lm.boff;
     const char* inb = reinterpret_cast<const char*>(in);
     char* outb = reinterpret_cast<char*>(out);
-    if (l < md.n_layers - 1) linear_op_b3<R, S::ACT, S::HIDC>(W3, bias, lm.Kp32 / 32, md.ld * 4, false, inb, outb, wave, lane);
-    else linear_op_b3<R, S::ACT, S::OUTC>(W3, bias, lm.Kp32 / 32, md.ld * 4, true, inb, outb, wave, lane);
+    if (l < md.n_layers - 1) linear_op_b3<R, S::ACT, S::HIDC, S::PIECES>(W3, bias, lm.Kp32 / 32, md.ld * 4, false, inb, outb, wave, lane);
+    else linear_op_b3<R, S::ACT, S::OUTC, S::PIECES>(W3, bias, lm.Kp32 / 32, md.ld * 4, true, inb, outb, wave, lane);
 }
 
 // Layer l of the ensemble MLP with member `member`'s weights.
@@ -1526,8 +1561,9 @@ template <int R, class S>
 __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_kernel(const ModelDev md, const RolloutArgs ra) {
     constexpr int ROWS = kTile * R;
     constexpr bool kLean = S::LEAN;
-    constexpr bool kB3 = S::PREC == HIPETS_PREC_BF16X3;  // operands as three bf16 pieces on the bf16 matrix pipe (lean instances)
-    static_assert(!kB3 || kLean, "bf16x3 arithmetic exists for the shape-specialised instances");
+    constexpr bool kB3 = S::PIECES > 0;  // operands as three bf16 pieces (bf16x3) or one (bf16) on the bf16 matrix pipe (lean instances)
+    constexpr int kNP = kB3 ? S::PIECES : 1;
+    static_assert(!kB3 || kLean, "bf16x3 / bf16 arithmetic exists for the shape-specialised instances");
     // (no cross-layer weight prefetch: the next op's chunk-0 fragments requested behind this op's k loop measured slower -- 56 more live
     // VGPRs and the scalar work between layers outweigh the latency it hides)
     // facts that are template arguments in a lean instance and model / call fields in the generic one
@@ -1940,7 +1976,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     // An item is therefore (row, chunk kk, group g) with those four columns (round 4): ONE ds_write_b128 instead of four scattered
     // ds_write_b32, and consecutive threads read consecutive state floats / normaliser doubles (conflict free) where the old item
     // (four CONSECUTIVE columns) read with a stride of four (measured on cfg4', 393 columns x 32 rows: 8.3 us per turn in the step
-    // trace, profiles/turn_trace.py).  Same arithmetic per element.  bf16x3 images keep consecutive columns (split3x4's layout).
+    // trace, profiles/turn_trace.py).  Same arithmetic per element.  bf16x3 / bf16 images keep consecutive columns (split_x4's layout).
     auto build_input_impl = [&](const int t, float* const dst, auto norm_tag, auto plain_tag) __attribute__((always_inline)) {
         constexpr int NORM = decltype(norm_tag)::value;
         constexpr bool PLAIN = decltype(plain_tag)::value;
@@ -2010,12 +2046,12 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                 v[q] = (c < md.in_dim && valid) ? x : 0.f;
             }
             HIPETS_BOUND(s >= 0 && s < ROWS && 4 * cq + 3 < ld_in);
-            if constexpr (kB3) {  // three bf16 pieces per value, in the B-operand layout of wave_gemm_b3
-                u32x2 pc[3];
-                split3x4(f32x4{v[0], v[1], v[2], v[3]}, pc);
+            if constexpr (kB3) {  // three bf16 pieces per value (bf16: the one), in the B-operand layout of wave_gemm_b3
+                u32x2 pc[kNP];
+                split_x4<kNP>(f32x4{v[0], v[1], v[2], v[3]}, pc);
                 char* row = reinterpret_cast<char*>(dst) + (size_t)s * ld_in * 4;
 #pragma unroll
-                for (int p = 0; p < 3; ++p) *reinterpret_cast<u32x2*>(row + b3_offset(4 * cq, p)) = pc[p];
+                for (int p = 0; p < kNP; ++p) *reinterpret_cast<u32x2*>(row + b3_offset<kNP>(4 * cq, p)) = pc[p];
             } else if constexpr (kByGroup) {  // columns 16 kk + 4 q + g live at positions 16 kk + 4 g + q: item cq = 4 kk + g writes [4 cq, 4 cq + 3]
                 *reinterpret_cast<f32x4*>(dst + s * ld_in + 4 * cq) = f32x4{v[0], v[1], v[2], v[3]};
             } else {

@@ -102,17 +102,19 @@ __global__ void pack_weights_kernel(float* dst, const float* src, const int* mem
 
 // bf16x3 precision mode: the same weights as three bf16 pieces, one A-operand fragment of v_mfma_f32_16x16x32_bf16 per
 // (column tile c, 32-wide k chunk kk, piece p): dst unit (16 bytes) index ((c * KC32 + kk) * 3 + p) * 64 + lane holds
-// piece p of W[members[m]][32 kk + 8 (lane >> 4) + j][16 c + (lane & 15)], j = 0..7 (zero outside K x N; natural columns)
+// piece p of W[members[m]][32 kk + 8 (lane >> 4) + j][16 c + (lane & 15)], j = 0..7 (zero outside K x N; natural columns).
+// bf16 precision mode: pieces = 1 -- ONE plane per (member, layer, column tile, k chunk, lane), piece 0 of the same split, i.e. the
+// weight rounded to bf16 (nearest-even); unit index (c * KC32 + kk) * 64 + lane
 __global__ void pack_weights_b3_kernel(uint4* dst, const float* src, const int* members, int M, int K, int N, int Kp32, int Np,
-                                       long long member_stride, long long layer_off, int src_nk) {
+                                       long long member_stride, long long layer_off, int src_nk, int pieces) {
     const int KC32 = Kp32 / 32, C = Np / 16;
-    const long long per_member = (long long)C * KC32 * 3 * 64;
+    const long long per_member = (long long)C * KC32 * pieces * 64;
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= per_member * M) return;
     const int m = (int)(i / per_member);
     long long r = i % per_member;
     const int lane = (int)(r & 63); r >>= 6;
-    const int p = (int)(r % 3); r /= 3;
+    const int p = (int)(r % pieces); r /= pieces;
     const int kk = (int)(r % KC32);
     const int c = (int)(r / KC32);
     const int n = 16 * c + (lane & 15);

@@ -26,9 +26,10 @@
 
 #include "launch.hpp"
 
-// lean fp32 and bf16x3 shapes instantiated for this R: the per-R tables of launch.hpp
+// lean fp32, bf16x3 and bf16 shapes instantiated for this R: the per-R tables of launch.hpp
 #define HIPETS_LEAN_SHAPES(X) HIPETS_CAT2(HIPETS_LEAN_SHAPES_R, HIPETS_R)(X)
 #define HIPETS_B3_SHAPES(X) HIPETS_CAT2(HIPETS_B3_SHAPES_R, HIPETS_R)(X)
+#define HIPETS_BF16_SHAPES(X) HIPETS_CAT2(HIPETS_BF16_SHAPES_R, HIPETS_R)(X)
 
 // The launch mode of this unit's shape-specialised instances and the function that launches them (HIPETS_SPEC_FN), and the launch of
 // the instance of a table row that matches the model: the lean fp32 instances run the output layer's accumulators straight into the
@@ -42,10 +43,12 @@
 #endif
 #define HIPETS_TRY_SHAPE(HC, OC, RW, TM, OB) \
     if (lean_shape_is(md, HC, OC, RW, TM, OB)) return launch_one<LeanSpec<HC, OC, RW, TM, OB, HIPETS_LEAN_MODE>>(grid, lds, lds_max, md, ra, st, start, stop);
-#define HIPETS_TRY_B3(HC, OC, RW, TM)                                                                                                          \
-    if (b3_shape_is(md, HC, OC, RW, TM))                                                                                                       \
-        return launch_one<KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, HIPETS_OBS_NONE, RW, TM, HIPETS_LEAN_MODE, HIPETS_PREC_BF16X3>>(      \
+#define HIPETS_TRY_PREC(PREC, HC, OC, RW, TM)                                                                                 \
+    if (b3_shape_is(md, HC, OC, RW, TM))                                                                                      \
+        return launch_one<KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, HIPETS_OBS_NONE, RW, TM, HIPETS_LEAN_MODE, PREC>>( \
             grid, lds, lds_max, md, ra, st, start, stop);
+#define HIPETS_TRY_B3(HC, OC, RW, TM) HIPETS_TRY_PREC(HIPETS_PREC_BF16X3, HC, OC, RW, TM)
+#define HIPETS_TRY_BF16(HC, OC, RW, TM) HIPETS_TRY_PREC(HIPETS_PREC_BF16, HC, OC, RW, TM)
 #define HIPETS_TRY_HID(HC) \
     if (hid_static_is(md, HC)) return launch_one<KSpec<HIPETS_ACT_SILU, HC>>(grid, lds, lds_max, md, ra, st, start, stop);
 
@@ -185,11 +188,13 @@ hipError_t HIPETS_FN(_gens)(int grid, unsigned lds, int lds_max, const ModelDev&
 #endif
 
 #if HIPETS_PART <= 2
-// the shape-specialised instance that the pick names, in this unit's launch mode: a bf16x3 one, or a lean fp32 one (KSpec::WIDE or not)
+// the shape-specialised instance that the pick names, in this unit's launch mode: a bf16x3 one, a bf16 one, or a lean fp32 one (KSpec::WIDE or not)
 hipError_t HIPETS_SPEC_FN(const RolloutInstance pick, int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st,
                           hipEvent_t start, hipEvent_t stop) {
     if (pick == RolloutInstance::b3) {
         HIPETS_B3_SHAPES(HIPETS_TRY_B3)
+    } else if (pick == RolloutInstance::bf16) {
+        HIPETS_BF16_SHAPES(HIPETS_TRY_BF16)
     } else {
         HIPETS_LEAN_SHAPES(HIPETS_TRY_SHAPE)
     }
@@ -205,11 +210,13 @@ hipError_t HIPETS_FN()(int grid, unsigned lds, int lds_max, const ModelDev& md, 
         case RolloutInstance::lean:
         case RolloutInstance::lean_wide:
         case RolloutInstance::b3:
+        case RolloutInstance::bf16:
             return (ra.whole_horizon ? HIPETS_FN(_fast) : HIPETS_FN(_exact))(pick, grid, lds, lds_max, md, ra, st, start, stop);
         case RolloutInstance::hidden_static: HIPETS_HID_STATIC_SHAPES(HIPETS_TRY_HID) break;
         case RolloutInstance::generic_silu: return HIPETS_FN(_gens)(grid, lds, lds_max, md, ra, st, start, stop);
         case RolloutInstance::generic: return HIPETS_FN(_gen)(grid, lds, lds_max, md, ra, st, start, stop);
-        case RolloutInstance::no_b3: return hipErrorNotSupported;            // (hipets.hip launch_rollout reports it)
+        case RolloutInstance::no_b3:
+        case RolloutInstance::no_bf16: return hipErrorNotSupported;          // (hipets.hip launch_rollout reports it)
         case RolloutInstance::no_wide: return hipErrorInvalidConfiguration;  // never run another layout in LDS sized for a WIDE instance
     }
     return hipErrorNotSupported;

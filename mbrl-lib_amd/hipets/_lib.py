@@ -19,10 +19,10 @@ REW = {None: 0, "learned": 0, "cartpole": 1, "cartpole_pets": 2, "inverted_pendu
 TERM = {"no_termination": 0, "cartpole": 1, "inverted_pendulum": 2, "hopper": 3, "walker2d": 4, "ant": 5, "humanoid": 6}
 NORM = {"none": 0, "f32": 1, "f64": 2}
 ENSEMBLE = {"gaussian_mlp": 0, "basic_ensemble": 1}
-PREC = {"f32": 0, "bf16x3": 1}
+PREC = {"f32": 0, "bf16x3": 1, "bf16": 2}
 MODE_EXACT, MODE_FAST, MODE_DEVICE = 0, 1, 2
 MODES = {"exact": MODE_EXACT, "fast": MODE_FAST, "device": MODE_DEVICE}
-KERNEL_CLASSES = ("generic", "hidden_static", "fused", "wide")  # HIPETS_KERNEL_*
+KERNEL_CLASSES = ("generic", "hidden_static", "fused", "wide", "bf16")  # HIPETS_KERNEL_*
 
 
 class ModelDesc(C.Structure):

@@ -276,7 +276,8 @@ class Engine:
 
     def kernel_class(self, pop: int, num_particles: int, horizon: int, mode: str = "device", rows_per_group: int = 0):
         """(class name, row tiles per workgroup) of the rollout-kernel instance a default rollout / fused plan of this size runs on
-        the engine's model: "generic", "hidden_static", "fused" or "wide" (include/hipets.h, hipets_kernel_class); ``rows_per_group``
+        the engine's model: "generic", "hidden_static", "fused", "wide" or "bf16" (the instances of precision="bf16") (include/hipets.h,
+        hipets_kernel_class); ``rows_per_group``
         > 0: the answer for a call that forces that row-tile count.  Diagnostic."""
         cls, r = C.c_int32(), C.c_int32()
         _lib.check(self._lib.hipets_kernel_class(self._h, pop, num_particles, horizon, _lib.MODES[mode], int(rows_per_group), C.byref(cls),

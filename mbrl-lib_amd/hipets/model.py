@@ -56,7 +56,10 @@ class ModelSpec:
     ensemble_kind: str = "gaussian_mlp"
     # arithmetic of the linear layers: "f32" (fp32 MFMA, the default and the graded mode) or "bf16x3" (fp32 operands as three
     # bf16 pieces on the bf16 matrix pipe: fp32-accurate to a few product ulps, ~1.5x faster; available for the shapes that have
-    # a shape-specialised kernel instance -- anything else fails loudly at the rollout call)
+    # a shape-specialised kernel instance -- anything else fails loudly at the rollout call), or "bf16" (reduced precision, reported
+    # separately with its own parity tolerance: both operands of every linear layer rounded to bf16 nearest-even, exact products,
+    # fp32 accumulation, bias and SiLU in fp32, hidden activations stored as bf16; the state, sampling, rewards and everything else
+    # stay fp32 -- same availability and refusal rule as "bf16x3")
     precision: str = "f32"
 
     # ---- derived ---------------------------------------------------------------------------
@@ -88,8 +91,8 @@ class ModelSpec:
         return 2 * sum(int(w.shape[1]) * int(w.shape[2]) for w in self.weights)
 
     def validate(self):
-        if self.precision not in ("f32", "bf16x3"):
-            raise ValueError(f"precision must be 'f32' or 'bf16x3', got {self.precision!r}")
+        if self.precision not in ("f32", "bf16x3", "bf16"):
+            raise ValueError(f"precision must be 'f32', 'bf16x3' or 'bf16', got {self.precision!r}")
         if self.ensemble_kind not in ("gaussian_mlp", "basic_ensemble"):
             raise UnsupportedModelError(f"ensemble kind {self.ensemble_kind!r} has no fused implementation")
         if self.activation not in _ACT_BY_CLASS.values():
