@@ -1,0 +1,141 @@
+// closed_forms.hpp -- the elementwise closed forms around the MLP: observation preprocessing (ObsMap, processed_obs), termination
+// and reward functions (term_eval, reward_eval, hopper_pair_bad), the standard normals of a (row, step, dim block)
+// (rollout_normals4) and the hardware transcendentals behind the log-variance clamp (exp_hw, log_hw, softplus_fast).  Replaces
+// mbrl/env/termination_fns.py, mbrl/env/reward_fns.py, the obs_process_fn of mbrl/env/pets_halfcheetah.py:91-113 and
+// pets_cartpole.py:78-101, the torch.randn of Ensemble.sample_1d (mbrl/models/model.py:471-473) and F.softplus
+// (gaussian_mlp.py:152-153).
+#pragma once
+#include "common.hpp"
+
+namespace hipets {
+
+// obs_process_fn seen from the PRODUCER of an observation dim (the fused tail, the straight form's collect phase: both hold a pair
+// of raw dims in registers and write the next step's input image themselves): which input column does dim d feed, and which dim
+// enters as sin / cos?  halfcheetah (env/pets_halfcheetah.py:91-113): [s1, sin s2, cos s2, s3:] -- dim 0 feeds nothing;
+// cartpole_pets (env/pets_cartpole.py:78-101): [sin s1, cos s1, s0, s2:] -- one column more than dims.
+template <int OBSP>
+struct ObsMap {
+    static constexpr int kTrigDim = OBSP == HIPETS_OBS_HALFCHEETAH ? 2 : (OBSP == HIPETS_OBS_CARTPOLE_PETS ? 1 : -1);  // enters as sin and cos
+    static constexpr int kSinCol = OBSP == HIPETS_OBS_HALFCHEETAH ? 1 : 0;
+    static constexpr int kCosCol = OBSP == HIPETS_OBS_HALFCHEETAH ? 2 : 1;
+    // column of dim d (the sin column for the trig dim), -1 = the dim is not a model input
+    __device__ static __forceinline__ int col(const int d) {
+        if constexpr (OBSP == HIPETS_OBS_HALFCHEETAH) return d == 0 ? -1 : (d == 1 ? 0 : (d == 2 ? 1 : d));
+        else if constexpr (OBSP == HIPETS_OBS_CARTPOLE_PETS) return d == 0 ? 2 : (d == 1 ? 0 : d + 1);
+        else return d;
+    }
+};
+
+// obs_process_fn(obs)[i] (mbrl/env/pets_halfcheetah.py:91-113, pets_cartpole.py:78-101)
+__device__ __forceinline__ float processed_obs(const float* s, int i, int mode) {
+    if (mode == HIPETS_OBS_HALFCHEETAH) {  // [s1, sin s2, cos s2, s3:]
+        if (i == 0) return s[1];
+        if (i == 1) return sinf(s[2]);
+        if (i == 2) return cosf(s[2]);
+        return s[i];
+    }
+    if (mode == HIPETS_OBS_CARTPOLE_PETS) {  // [sin s1, cos s1, s0, s2:]
+        if (i == 0) return sinf(s[1]);
+        if (i == 1) return cosf(s[1]);
+        if (i == 2) return s[0];
+        return s[i - 1];
+    }
+    return s[i];
+}
+
+__device__ __forceinline__ bool term_eval(const float* s, int obs_dim, int fn) {
+    switch (fn) {
+        case HIPETS_TERM_CARTPOLE: {  // termination_fns.py:29-44
+            const float x = s[0], th = s[2], thr = (float)(12.0 * 2.0 * 3.14159265358979323846 / 360.0);
+            return !((x > -2.4f) && (x < 2.4f) && (th > -thr) && (th < thr));
+        }
+        case HIPETS_TERM_INVERTED_PENDULUM: {  // :47-55
+            bool fin = true;
+            for (int d = 0; d < obs_dim; ++d) fin = fin && isfinite(s[d]);
+            return !(fin && (fabsf(s[1]) <= 0.2f));
+        }
+        case HIPETS_TERM_HOPPER: {  // :12-26
+            bool ok = true;
+            for (int d = 0; d < obs_dim; ++d) ok = ok && isfinite(s[d]);
+            for (int d = 1; d < obs_dim; ++d) ok = ok && (fabsf(s[d]) < 100.0f);
+            return !(ok && (s[0] > 0.7f) && (fabsf(s[1]) < 0.2f));
+        }
+        case HIPETS_TERM_WALKER2D:  // :66-74
+            return !((s[0] > 0.8f) && (s[0] < 2.0f) && (s[1] > -1.0f) && (s[1] < 1.0f));
+        case HIPETS_TERM_ANT: {  // :77-85
+            bool fin = true;
+            for (int d = 0; d < obs_dim; ++d) fin = fin && isfinite(s[d]);
+            return !(fin && (s[0] >= 0.2f) && (s[0] <= 1.0f));
+        }
+        case HIPETS_TERM_HUMANOID:  // :88-95
+            return (s[0] < 1.0f) || (s[0] > 2.0f);
+        default: return false;  // no_termination :58-63
+    }
+}
+
+__device__ __forceinline__ float reward_eval(const float* s, const float* a, int obs_dim, int act_dim, int fn,
+                                             float learned) {
+    switch (fn) {
+        case HIPETS_REW_CARTPOLE: return term_eval(s, obs_dim, HIPETS_TERM_CARTPOLE) ? 0.0f : 1.0f;  // reward_fns.py:10-13
+        case HIPETS_REW_INVERTED_PENDULUM: return term_eval(s, obs_dim, HIPETS_TERM_INVERTED_PENDULUM) ? 0.0f : 1.0f;
+        case HIPETS_REW_CARTPOLE_PETS: {  // :16-24
+            const float e0 = (s[0] - 0.6f * sinf(s[1])) - 0.0f, e1 = (-0.6f * cosf(s[1])) - 0.6f;
+            const float obs_cost = expf(-(e0 * e0 + e1 * e1) / (float)(0.6 * 0.6));
+            float sq = 0.f;
+            for (int i = 0; i < act_dim; ++i) sq += a[i] * a[i];
+            return obs_cost + (-0.01f * sq);
+        }
+        case HIPETS_REW_HALFCHEETAH: {  // :33-38
+            float sq = 0.f;
+            for (int i = 0; i < act_dim; ++i) sq += a[i] * a[i];
+            const float run = s[0] - 0.0f * (s[2] * s[2]);
+            return run + (-0.1f * sq);
+        }
+        case HIPETS_REW_PUSHER: {  // :41-53
+            const float g0 = 0.45f, g1 = -0.05f, g2 = -0.323f;
+            const float tip_obj = fabsf(s[14] - s[17]) + fabsf(s[15] - s[18]) + fabsf(s[16] - s[19]);
+            const float obj_goal = fabsf(g0 - s[17]) + fabsf(g1 - s[18]) + fabsf(g2 - s[19]);
+            const float obs_cost = 0.5f * tip_obj + 1.25f * obj_goal;
+            float sq = 0.f;
+            for (int i = 0; i < act_dim; ++i) sq += a[i] * a[i];
+            return -(obs_cost + 0.1f * sq);
+        }
+        case HIPETS_REW_NONE: return 0.0f;  // the caller evaluates its own reward_fn on the returned next_obs
+        default: return learned;  // model_env.py:124-128 with reward_fn None
+    }
+}
+
+// the 4 standard normals of (row, step, dim block): counter = (row, step, block, stream), key = seed
+__device__ __forceinline__ void rollout_normals4(int rid, int t, int blk, unsigned long long seed,
+                                                 unsigned long long stream_id, float (&nrm)[4]) {
+    const Philox4 r4 = philox4x32_10((uint32_t)rid, (uint32_t)t, (uint32_t)blk, (uint32_t)stream_id, (uint32_t)seed,
+                                     (uint32_t)(seed >> 32) ^ (uint32_t)(stream_id >> 32));
+    box_muller(r4.x, r4.y, nrm[0], nrm[1]);
+    box_muller(r4.z, r4.w, nrm[2], nrm[3]);
+}
+
+// termination_fns.hopper (:12-26) seen from ONE pair of state dims (d, d + 1): all finite, |dims 1..| < 100, height (dim 0) > 0.7,
+// |angle (dim 1)| < 0.2.  The row is unhealthy iff any of its pairs says so (fused tail lanes / the collecting threads of the
+// persistent DEVICE form, kspec.hpp KSpec).
+__device__ __forceinline__ bool hopper_pair_bad(const int d, const float vA, const float vB, const bool hasA, const bool hasB) {
+    bool bad = false;
+    if (hasA) bad = !isfinite(vA) || (d >= 1 ? !(fabsf(vA) < 100.0f) : !(vA > 0.7f));
+    if (hasB) bad = bad || !isfinite(vB) || !(fabsf(vB) < 100.0f) || (d == 0 && !(fabsf(vB) < 0.2f));
+    return bad;
+}
+
+// Raw hardware transcendentals (v_exp_f32 / v_log_f32 are base 2, ~1 ulp, no denormal fix-up sequences).
+__device__ __forceinline__ float exp_hw(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
+__device__ __forceinline__ float log_hw(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994530942f; }
+// log(1 + e^x) (abs error ~1e-7; F.softplus' threshold-20 branch kept as a select)
+__device__ __forceinline__ float softplus_fast(float x) {
+    const float y = log_hw(1.0f + exp_hw(fminf(x, 20.0f)));
+    return x > 20.0f ? x : y;
+}
+// the log-variance clamp of GaussianMLP._default_forward (gaussian_mlp.py:152-153) between the bounds mn / mx
+__device__ __forceinline__ float clamp_logvar(float lv, const float mn, const float mx) {
+    lv = mx - softplus_fast(mx - lv);
+    return mn + softplus_fast(lv - mn);
+}
+
+}  // namespace hipets

@@ -18,6 +18,7 @@
 #include "launch.hpp"
 #include "optim.hpp"
 #include "rollout_helpers.hpp"
+#include "rollout_smem.hpp"
 #include "train.hpp"
 
 using namespace hipets;
@@ -630,7 +631,7 @@ int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream)
         boff += lms[l].Np;
         maxK = std::max(maxK, std::max(lms[l].Kp, lms[l].Np));
     }
-    if (!d->deterministic) {  // second pack of the mean / logvar head in "head pair" column order (rollout.hpp head_pair_col, KSpec::FUSE)
+    if (!d->deterministic) {  // second pack of the mean / logvar head in "head pair" column order (rollout_types.hpp head_pair_col, KSpec::FUSE)
         LayerMeta& out = lms[d->n_layers - 1];
         out.woff_pairs = woff;
         out.boff_pairs = boff;
@@ -1718,7 +1719,7 @@ int hipets_planet_set_model(hipets_engine* e, const hipets_planet_desc* d, void*
     const int widB = up16(std::max(Hb, F)), widC = up16(std::max(3 * Hb, F)), widD = up16(std::max(std::max(3 * Hb, 2 * L), 16));
     pd.segA = 0; pd.segB = pd.widA; pd.segC = pd.segB + widB; pd.segD = pd.segC + widC; pd.segE = pd.segD + widD;
     int ld = pd.segE + pd.widE;
-    while (ld % 64 != 8) ld += 4;  // conflict-free ds_read_b128 A fragments (see rollout.hpp)
+    while (ld % 64 != 8) ld += 4;  // conflict-free ds_read_b128 A fragments (rollout.hpp header; gemm_f32.hpp lds_col)
     pd.ld = ld;
     if (planet_smem_bytes(ld) > e->lds_max) return fail("PlaNet model too wide for LDS (row of %d floats)", ld);
     // op table: K, N, source tensors, whether the output feeds another GEMM (chunk-transposed columns)

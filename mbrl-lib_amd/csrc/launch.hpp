@@ -3,8 +3,9 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include "kspec.hpp"
 #include "planet_types.hpp"
-#include "rollout.hpp"
+#include "rollout_types.hpp"
 
 namespace hipets {
 
@@ -88,7 +89,7 @@ inline bool spec_model(const ModelDev& md) {
            md.lv_rows == 1 && fused_term_ok(md);
 }
 
-// does the call use nothing a shape-specialised instance compiled out? (KSpec in rollout.hpp lists what that is; the obs preprocessing
+// does the call use nothing a shape-specialised instance compiled out? (KSpec in kspec.hpp lists what that is; the obs preprocessing
 // is part of an instance's shape since round 4)
 inline bool lean_call(const ModelDev& md, const RolloutArgs& ra) {
     return !ra.generic_only && spec_model(md) && !ra.eps && ra.use_philox &&

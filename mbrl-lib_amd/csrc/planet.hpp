@@ -18,8 +18,9 @@
 // The linear ops are the rollout kernel's wave_gemm (fp32 MFMA 16x16x4, weights pre-packed as fragments); segments that
 // feed a GEMM are kept in its chunk-transposed column order (lds_col), segments read elementwise in natural order.
 #pragma once
+#include "closed_forms.hpp"
+#include "gemm_f32.hpp"
 #include "planet_types.hpp"
-#include "rollout.hpp"
 
 namespace hipets {
 
@@ -38,7 +39,7 @@ __global__ __launch_bounds__(kThreads) void planet_rollout_kernel(const PlanetDe
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int ld = pd.ld;
-    // phase profiler (rollout.hpp Prof; the marks inside the linear ops are wave_gemm's own): profiling builds only, workgroup 0.
+    // phase profiler (gemm_f32.hpp Prof; the marks inside the linear ops are wave_gemm's own): profiling builds only, workgroup 0.
     // (Its accumulators sit at the end of the DYNAMIC LDS: the kernel opts in to the full 160 KB of dynamic LDS, and a static array on
     // top of that made the launch fail with "invalid argument".)
     long long* const prof_slots = reinterpret_cast<long long*>(smem_raw + planet_smem_bytes(pd.ld) - kWaves * 16 * sizeof(long long));

@@ -19,182 +19,24 @@
 //   FAST  mode: one launch for the whole horizon; workgroup (particle p, candidate group g) owns
 //               its rows for all H steps, state stays in LDS, the member is drawn per
 //               (workgroup, step) from a balanced schedule, eps comes from Philox.
+//
+// This file holds the kernel and what only the kernel uses (the hand-over primitives, MinWaves, HIPETS_STAMP).  Its layers:
+//   rollout_types.hpp  argument structs          gemm_f32.hpp / gemm_bf16.hpp  the linear ops          kspec.hpp  instance facts, layer dispatch
+//   closed_forms.hpp   reward / termination / sampling forms                   rollout_smem.hpp        the LDS layout
 #pragma once
-#include <type_traits>
-
+#include "closed_forms.hpp"
 #include "common.hpp"
+#include "gemm_f32.hpp"
+#include "kspec.hpp"
+#include "rollout_smem.hpp"
+#include "rollout_types.hpp"
 
 namespace hipets {
-
-struct LayerMeta {
-    int Kp, Np;          // K, N padded to multiples of 16
-    int boff;            // float offset of the layer's bias inside a member block
-    int tail_steps;      // MFMA k-steps (of 4) of the last chunk that hold real weights: ceil((K - (Kp - 16)) / 4)
-    long long woff;      // float offset of the layer's packed weights inside a member block
-    // bf16x3 / bf16 precision modes (operands as three bf16 pieces, or one, on the bf16 matrix pipe):
-    int Kp32;            // K padded to a multiple of 32 (one v_mfma_f32_16x16x32_bf16 k-chunk)
-    int pad_;
-    long long woff3;     // 16-byte-unit offset of the layer's packed bf16 planes inside a member block
-    // output layer of a stochastic model only: a SECOND pack of its weights / biases with the columns in "head pair" order
-    // (head_pair_col below) for the kernel instances that sample straight from the accumulators (KSpec::FUSE); -1 = none
-    long long woff_pairs;
-    int boff_pairs;
-    int pad2_;
-};
-
-// "Head pair" column order of the output layer (mean_and_logvar, gaussian_mlp.py:107-112): packed column p = 16 c + 4 g + i
-// holds, for the output dim d = 8 c + 2 g + (i & 1), its mean (i < 2) or its log-variance (i >= 2).  Formed transposed, the
-// product leaves lane group g of column tile c with {mean d, mean d+1, logvar d, logvar d+1} of one batch row in ONE
-// accumulator: everything the sampling of those two dims needs (model.py:471-473), no LDS round trip.  -1 = zero padding.
-__host__ __device__ __forceinline__ int head_pair_col(int p, int out_dim) {
-    const int c = p >> 4, g = (p >> 2) & 3, i = p & 3;
-    const int d = 8 * c + 2 * g + (i & 1);
-    if (d >= out_dim) return -1;
-    return i < 2 ? d : out_dim + d;
-}
-
-struct Extras {  // up to kMaxExtras leftover (column tile, row tile) units of one wave
-    int c0, c1, c2, c3, r0, r1, r2, r3;
-};
-
-struct ModelDev {
-    int obs_dim, act_dim, in_dim, out_dim, out_total, hid, n_layers, M;
-    int obs_in;  // width of obs_process_fn(obs) = in_dim - act_dim
-    int activation;
-    float slope;
-    int propagation, deterministic, obs_process, reward_fn, term_fn, target_is_delta, learned_rewards, normalizer;
-    const LayerMeta* layers;  // DEVICE [n_layers] (a table in memory: runtime-indexed kernargs would go to scratch)
-    int Kp0;                  // padded input width of layer 0
-    int hidC;                 // column tiles of a hidden layer (cost model; shape of the lean kernel instances)
-    int outC;                 // column tiles of the output layer
-    long long wmember;  // floats per member (packed weights)
-    int bmember;        // floats per member (padded biases)
-    int ld;             // LDS activation row stride in floats (== 8 mod 64)
-    int ld_in;          // KSpec::WIDE instances: row stride of the model-input image (>= Kp0, == 8 mod 64); the hidden activations use KSpec::LD
-    const float* w;
-    const float* b;
-    const double* norm_mean;
-    const double* norm_std;
-    const float* min_lv;  // [lv_rows][out_dim]
-    const float* max_lv;
-    int lv_rows;          // 1 (bounds shared by the members) or M (BasicEnsemble: one row per member)
-    int iid_members;      // BasicEnsemble: members are drawn independently (no balanced shuffle, no batch % M rule)
-    const unsigned char* no_delta;  // [obs_dim]
-    int precision;            // HIPETS_PREC_*
-    long long w3member;       // 16-byte units per member (bf16 planes: three in bf16x3, one in bf16)
-    const uint4* w3;          // packed bf16 planes: [member][layer][col tile][k chunk of 32][plane 0..NP-1][lane][8 x bf16]
-};
-
-struct RolloutArgs {
-    int pop, P, H, B;
-    int whole_horizon;  // the kernel form: 1 = FAST (one launch for the horizon, rows tiled from s0, state in LDS); 0 = step-synchronous
-                        //   (rows by identity / permutation, state in HBM around the launch, or handed over in the persistent form)
-    int t_begin, t_end;
-    int groups;           // FAST: candidate groups per particle; EXACT: workgroups per member domain
-    int rows_per_domain;  // EXACT: B / M (or B for expectation)
-    const float* actions;  // [pop,H,A]
-    const float* s0;       // [obs]
-    float* state;          // EXACT: [B,obs] in/out
-    float* totals;         // [B] (EXACT in/out; FAST out)
-    unsigned char* term;   // EXACT: [B] in/out
-    const long long* perm; // EXACT: [H,B] / [B] / null
-    long long perm_step;   // stride between steps (0 for fixed_model)
-    unsigned perm_n, perm_a, perm_b;  // DEVICE mode: row of slot j = perm_apply(j) over [0, perm_n), radices a x b (perm_n = 0: none)
-    PermKeys perm_keys;    // DEVICE mode: round keys of THIS launch's permutation (perm_round_keys(perm_key(seed, stream, step)), host side)
-    const float* eps;      // [H,B,out] or null
-    int use_philox;        // FAST without eps override
-    unsigned long long seed, stream_id;
-    const int* schedule;   // FAST: [H, nWG] member slot per (step, workgroup), injected by the caller; null = every workgroup draws its own
-                           //   entries in its prologue (common.hpp fast_member, radices fm_a x fm_b = perm_radices(gridDim.x))
-    unsigned fm_a, fm_b;
-    int fast_members;      // the step-synchronous form (whole_horizon = 0) with the workgroup's member chosen as in FAST mode (`schedule`,
-                           //   or the in-kernel draw for step t_begin): hipets_step in FAST mode -- for one step that form IS the FAST form,
-                           //   and it exists in every shape-specialised instance
-    float* trace_next_obs;
-    float* trace_rewards;
-    long long* phase_cycles;  // optional [kWaves][16 phases] cycle counters of workgroup 0 (profiling aid)
-    int pop_env;               // FAST batched planning: candidates per environment (candidate c starts from s0[c / pop_env]); 0 = one env
-    int generic_only;          // hipets_rollout_opts.generic_kernel: 1 = only the fully generic kernel instance; 2 = no shape-specialised
-                               // (lean) instance, but the hidden-static one (KSpec::HID_STATIC) where the model has its width
-    int wide_lds;              // the host sized the LDS (and chose R) for the KSpec::WIDE layout: the launcher runs that instance or fails
-    // DEVICE mode, persistent form (all workgroups co-resident, ONE launch for the horizon): rows change workgroups every step
-    // through `exchange`, a [B][obs_dim + 2] table of 8-byte {value bits, step tag} granules (state dims, running total,
-    // terminated flag).  A granule is written by ONE write-through (sc1) 8-byte store and polled with sc1 loads until its
-    // tag is the awaited step: self-validating, so no fence, flag or grid barrier is involved (MI355X_MICROARCH.md R2).
-    unsigned long long* exchange;  // null: per-step launches
-    unsigned tag_base;             // step t's hand-over carries tag tag_base + t + 1 (the engine advances it by H per launch: no clearing)
-    int* capacity_out;             // HOST pointer, launcher only: when set, no launch -- the resident capacity (workgroups) is stored here
-    int n_logical;                 // persistent form: logical workgroups (member domain x row group); a launched workgroup serves the
-                                   // logical ones wg, wg + gridDim.x, ... one after the other within every step (batches larger than the chip)
-    int ragged_last_turn;          // persistent form, KSpec::WIDE two-tile instances: when the row tiles the LAST turn of a step would serve
-                                   // fit one per launched workgroup, that turn is dealt in ONE-tile logical workgroups (rollout_kernel:
-                                   // "ragged last turn"); 0 = always two-tile turns (A/B measurements: HIPETS_RAGGED_LAST_TURN=0)
-    const PermKeys* step_keys;     // DEVICE [H]: round keys of every step's permutation
-    int* error_flag;               // HOST-mapped: set to 1 when a poll exceeds its bound (another workgroup was not resident); once it is
-                                   // set every later poll of the launch gives up after <= 64 spins, so a stranded grid drains in
-                                   // milliseconds instead of waiting out the bound at every step and turn
-    long long poll_ticks;          // bound of one hand-over poll in 100 MHz wall-clock ticks (hipets_set_handover_timeout; default 0.2 s)
-    unsigned lds_bytes;            // the dynamic LDS size the launch was given (debug builds check every LDS section against it: HIPETS_DEBUG_BOUNDS)
-    int* census;                   // DEVICE [2], launcher only: when set the launch is the co-residency SELF-TEST of this kernel instance at
-                                   // this grid, not a rollout -- every workgroup arrives at census[0] and waits (bounded by poll_ticks)
-                                   // until all gridDim.x have; those that saw everybody count themselves in census[1]
-};
-
-// D = A(16x4) * B(4x16) + C, exact f32.  Issued through inline asm with the accumulator tied in place
-// ("+v"): with the builtin, hipcc's register allocator rotates the accumulators through fresh registers in
-// the unrolled k loop and pays ~45 v_accvgpr_mov/read/write per iteration to undo it at the back edge.
-// Hazards: A/B come from loads (the compiler's s_waitcnt covers asm inputs); back-to-back MFMAs that take
-// the previous D whole as C need no wait states; the first non-MFMA reader of D is fenced by mfma_drain().
-__device__ __forceinline__ void mfma16x16x4(const float a, const float b, f32x4& c) {
-    asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
-}
-// >= 12 wait states between the last 8-pass MFMA and a VALU read of its result (cdna4 ISA, XDL write -> VALU read)
-__device__ __forceinline__ void mfma_drain() { asm volatile("s_nop 15" ::: "memory"); }
-
-// Column c of an activation row lives at LDS position lds_col(c): inside every 16-wide k chunk the 4x4 block
-// (k-step s, lane group g) is stored transposed, so the lane group g of the A fragment reads its 4 k-steps
-// {16kk + 4s + g : s = 0..3} with ONE ds_read_b128 at [16kk + 4g, +3].
-__device__ __forceinline__ int lds_col(int c) { return (c & ~15) | ((c & 3) << 2) | ((c >> 2) & 3); }
-
-// phase profiler: lane 0 of every wave of workgroup 0 accumulates s_memtime deltas per phase in LDS (a mark is one LDS
-// read-modify-write on one lane, ~100 cycles; accumulating straight into global memory cost a ~800-cycle round trip per
-// mark and dominated the short phases it measured) and flushes them into RolloutArgs::phase_cycles[wave][phase] at the end
-// of the launch (a profiling aid, off unless the caller passes a buffer).  An accumulator holds the cycles in its low 44 bits and
-// the NUMBER of marks that fed it above them (round 6): a reader divides both by the step count and can subtract what the marks
-// themselves cost (profiles/one_tile_phase_profile.py calibrates that against the unprofiled launch duration).
-constexpr int kProfCountShift = 44;
-struct Prof {
-    long long* slot;  // LDS: this wave's 16 accumulators
-    long long t;
-    bool on;
-    __device__ __forceinline__ void mark(int phase) {
-        if (on) {
-            const long long now = clock64();
-            slot[phase] += (now - t) + (1ll << kProfCountShift);
-            t = now;
-        }
-    }
-};
-
-// One wave's share of a layer: CT strided column tiles (c_first + kWaves*ct) for all R row tiles, plus EX
-// "extra" (column tile, row tile) units taken from the C % 4 leftover column tiles, all accumulated
-// in the same k loop so the MFMA pipe always has >= 2 independent accumulators in flight.
-// The k loop is software pipelined by hand with two register buffers: the B fragments (global, L2
-// resident) and A fragments (LDS) of chunk kk+1 are in flight while the 4*(CT*R+EX) MFMAs of chunk kk
-// issue (one wave per SIMD, so nothing else hides the load latency).
-template <int R, int CT, int EX>
-struct GemmFrags {
-    f32x4 b[CT > 0 ? CT : 1];
-    f32x4 bx[EX > 0 ? EX : 1];
-    f32x4 a[R];
-    f32x4 ax[EX > 0 ? EX : 1];
-};
 
 // 16-byte write-through store / load of a PAIR of hand-over granules {value, tag, value, tag} (persistent DEVICE form).  sc1 =
 // device scope: the store leaves the XCD's L2, the load never returns a stale L1 line (MI355X_MICROARCH.md: 8-byte sc1 stores
 // cost 2.7x the 16-byte ones per byte, and a workgroup's polls queue behind its own stores).  The load is asynchronous:
 // pair_wait() is the s_waitcnt, tied to the destination registers so nothing reads them earlier.
-using u32x4g = __attribute__((ext_vector_type(4))) unsigned;
 // (s_nop 1 behind the store: a VMEM store of more than 8 bytes reads its data registers late, and on gfx940+ a VALU write of one
 // of them needs TWO wait states behind it.  The compiler keeps that distance for its own stores; inside an asm statement it does not
 // know there is a store.  Round 5: after an unrelated change the next instruction but one rewrote the first data register, and under
@@ -220,1326 +62,6 @@ __device__ __forceinline__ void pair_dma_issue(const unsigned long long* gsrc, c
                  : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
 }
 __device__ __forceinline__ void vmem_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
-
-// Minimum waves per SIMD the register allocation must leave room for (= workgroups of 4 waves per CU).  R <= 2 keeps two
-// workgroups per CU resident (their barrier / latency phases overlap); R = 3, 4 need the registers.
-template <int R> struct MinWavesOf { static constexpr int value = R <= 2 ? 2 : 1; };
-
-// Debug build (__graft_entry__.build_debug: -O1 -g -DHIPETS_DEBUG_BOUNDS=1, host side under AddressSanitizer): every LDS section of
-// the rollout kernel is checked against the dynamic LDS size of the launch, and the indexed LDS accesses of the elementwise phases
-// against their section.  A violated bound aborts the kernel (device assert -> the next HIP call reports it).  Off in the shipped
-// library: the checks cost registers in kernels that sit at the limit.
-#ifndef HIPETS_DEBUG_BOUNDS
-#define HIPETS_DEBUG_BOUNDS 0
-#endif
-#if HIPETS_DEBUG_BOUNDS
-// (not <cassert>'s assert: the generic lambdas of wave_gemm are implicitly __host__ __device__, where the host's __assert_fail is not callable)
-__host__ __device__ inline void hipets_bound_fail(const int line) {
-#if defined(__HIP_DEVICE_COMPILE__)
-    printf("hipets: bound violated at rollout.hpp:%d (workgroup %d, thread %d)\n", line, (int)blockIdx.x, (int)threadIdx.x);
-    __builtin_trap();
-#else
-    (void)line;
-#endif
-}
-#define HIPETS_BOUND(cond) do { if (!(cond)) hipets_bound_fail(__LINE__); } while (0)
-#else
-#define HIPETS_BOUND(cond) ((void)0)
-#endif
-
-struct NoTail {};  // wave_gemm's TL: the ordinary epilogue (activation, store as the next op's LDS image)
-// A fused tail = four stages over the accumulators (units) a wave finished: prep(slot, c, r) for EVERY unit of a group first -- it
-// only loads (LDS) what the unit will need into its slot, so the round trips of all units overlap --, then draw(slot a, slot b, c_a,
-// c_b, two) for every PAIR of units (the pair's standard normals: one Philox block per lane for the two units together, see
-// rollout_kernel's tail_draw), then unit(slot, acc, c, r) for every unit (arithmetic + stores), then finish() once per wave.
-struct FusedSlot {  // what one unit's lane reads from LDS (rollout_kernel, KSpec::FUSE)
-    float mxA, mxB, mnA, mnB, pA, pB;
-    double nmA, nmB, nsA, nsB;
-    int rid, ndA, ndB;
-    float n0, n1;  // the two standard normals of the lane's dims (draw stage)
-};
-template <class P, class D, class F, class G>
-struct TailStages {
-    P prep;
-    D draw;
-    F unit;
-    G finish;
-};
-template <class P, class D, class F, class G>
-__device__ __forceinline__ TailStages<P, D, F, G> make_tail(P p, D d, F f, G g) { return TailStages<P, D, F, G>{p, d, f, g}; }
-
-// ACT >= 0: the activation is a compile-time fact (one epilogue in the code); ACT < 0: `act` selects it at run time.
-// TL != NoTail: instead of the epilogue every finished accumulator is handed to (*tl)(acc, column tile, row tile) -- the fused
-// per-step tail of the output layer (KSpec::FUSE: sampling, next state, reward, next input straight from the registers).
-// LD > 0: the LDS row stride is a compile-time fact (shape-specialised instances): the A-fragment reads of the R row tiles become
-// ONE base register + immediate offsets (ds_read_b128 ... offset:r * 16 * LD * 4), no per-row address arithmetic in the k loop.
-// SPL: every unit sums its even and its odd k-steps in two accumulators and adds them at the end -- the order a wave whose whole
-// share is ONE unit uses anyway (hazard (2) below).  The OUTPUT layer runs with SPL in every instance: its columns are dealt to
-// the waves differently by the natural and the head-pair packs, and with SPL a column's sum does not depend on whether its wave
-// holds one unit or several -- shape-specialised and generic instances keep returning the same bits.
-// KCS > 0: the number of k chunks is a compile-time fact (ops whose K is the hidden width of a shape-specialised instance): the
-// k loop is fully unrolled -- straight-line code, no loop control, no accumulator copies where blocks meet.
-// x * rcp(1 + exp2(-x log2 e)) on the 4 accumulator values of a lane: the two multiplies and the add as packed 2 x f32 ops
-__device__ __forceinline__ f32x4 silu4(const f32x4 a) {
-    using f32x2 = __attribute__((ext_vector_type(2))) float;
-    const f32x2 k = {-1.44269504088896340736f, -1.44269504088896340736f}, one = {1.0f, 1.0f};
-    const f32x2 lo = {a[0], a[1]}, hi = {a[2], a[3]};
-    f32x2 tl = lo * k, th = hi * k;
-    tl[0] = __builtin_amdgcn_exp2f(tl[0]); tl[1] = __builtin_amdgcn_exp2f(tl[1]);
-    th[0] = __builtin_amdgcn_exp2f(th[0]); th[1] = __builtin_amdgcn_exp2f(th[1]);
-    tl = tl + one; th = th + one;
-    tl[0] = __builtin_amdgcn_rcpf(tl[0]); tl[1] = __builtin_amdgcn_rcpf(tl[1]);
-    th[0] = __builtin_amdgcn_rcpf(th[0]); th[1] = __builtin_amdgcn_rcpf(th[1]);
-    const f32x2 yl = lo * tl, yh = hi * th;
-    return f32x4{yl[0], yl[1], yh[0], yh[1]};
-}
-
-// K-SPLIT of the leftover column tile (one-tile workgroups, round 5; KSpec::KSPLIT).  A hidden layer of 13 column tiles deals 4-3-3-3
-// tiles to the four waves: the wave with four sets the pace of every layer (200 of its 4 x 50 MFMA k-steps against 150 of the
-// others), and at R = 1 nothing else runs on the CU.  Instead the 13th tile's K RANGE is dealt to the waves -- wave w takes the k
-// chunks [w KC / 4, (w + 1) KC / 4) of it, at most kKsSlots -- so every wave issues 3 x 50 + 16 k-steps, and the four partial sums
-// meet LAZILY: a wave leaves its partial (pre-activation; wave 0's starts at the bias) in LDS as the f32x4 its lanes hold -- which,
-// formed transposed, is exactly the B-operand fragment layout of the NEXT op's last k chunk (`lds_col`) -- and after the layer's
-// ordinary barrier every wave of the next op reads the four partials of its lane, adds them in one fixed order ((P0 + P1) + (P2 + P3))
-// and applies the activation: that IS its fragment of the last chunk.  No extra barrier, no extra pass; 4 ds_read_b128 + ~20 VALU
-// instructions per wave and layer against 34 k-steps (~1.1 k cycles) fewer on the critical wave.  The hidden columns 192..207 are
-// summed in another order than in the other instances: KSPLIT instances agree with them to rounding (tests: T2 against the oracle),
-// not bit for bit.  Two partial buffers alternate by layer parity (a fast wave may finish layer l + 1 while a slow one still reads
-// layer l's partials).
-constexpr int kKsSlots = 4;  // k chunks of the split tile per wave (KC <= 16: hidden widths up to 256, inputs up to 256 columns)
-struct KsArgs {
-    const float* part_in;  // KSI: [kWaves][64][4] the producer's partial sums of this op's LAST k chunk
-    float* part_out;       // KSO: [kWaves][64][4] this op's partial sums of its split column tile
-    int tile;              // KSO: the split column tile (the op's last)
-    int k0, n;             // KSO: this wave's chunks [k0, k0 + n) of it
-    int wave;
-};
-
-// KS bit 0 (KSI): the input image's last k chunk is NOT in LDS -- it is rebuilt from ks->part_in; bit 1 (KSO): see above;
-// bit 2: no k-split, only the one-tile k loop that fetches two chunks ahead (kTriple: ops with a static chunk count, planet.hpp)
-template <int R, int CT, int EX, int ACT, class TL = NoTail, int LD = -1, bool SPL = false, int KCS = -1, int KS = 0>
-__device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* __restrict__ out, const int ld_rt,
-                                          const float* __restrict__ W, const float* __restrict__ bias, const int KC_rt,
-                                          const int tail_steps, const int c_first, const Extras ex,
-                                          const bool apply_act, const int act, const float slope, const int lane,
-                                          Prof& prof, const TL* tl = nullptr, const int ldi_rt = 0, const KsArgs* ks = nullptr) {
-    constexpr int CTn = CT > 0 ? CT : 1;
-    constexpr int EXn = EX > 0 ? EX : 1;
-    constexpr bool KSI = (KS & 1) != 0, KSO = (KS & 2) != 0;
-    static_assert(!KS || (R == 1 && LD > 0), "k-split: one-tile shape-specialised instances, rolled k loop");
-    static_assert(!KSO || (std::is_same<TL, NoTail>::value && EX == 0 && !SPL), "k-split producer: a hidden op");
-    f32x4 acc[CTn][R];
-    f32x4 accx[EXn];
-    const int ld = LD > 0 ? LD : ld_rt;
-    const int ldi = ldi_rt > 0 ? ldi_rt : ld;  // row stride of `in` when it differs from the output's (KSpec::WIDE: the model-input image)
-    const int KC = KCS > 0 ? KCS : KC_rt;
-
-    const int exc[kMaxExtras] = {ex.c0, ex.c1, ex.c2, ex.c3};
-    const int exr[kMaxExtras] = {ex.r0, ex.r1, ex.r2, ex.r3};
-    // per-lane BYTE offsets from the (wave-uniform) chunk base W + 256 kk floats: loop invariant, unsigned 32 bit, so the
-    // loads take the scalar-base form (global_load v, v_off, s[base]) and the k loop carries no 64-bit address VALU work
-    // (a wave's own VALU instructions do not overlap its MFMAs, profiles/microbench)
-    unsigned woff[CTn], wxoff[EXn];
-    int axoff[EXn];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) woff[ct] = (unsigned)(((c_first + kWaves * ct) * KC * 64 + lane) * 16);
-#pragma unroll
-    for (int e = 0; e < EX; ++e) {
-        wxoff[e] = (unsigned)((exc[e] * KC * 64 + lane) * 16);
-        axoff[e] = exr[e] * 16 * ldi;
-    }
-    const float* ap = in + (lane & 15) * ldi + 4 * (lane >> 4);
-    // biases of this lane's columns: loaded before the k loop so their latency hides behind it
-    f32x4 bv[CTn], bvx[EXn];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) bv[ct] = *reinterpret_cast<const f32x4*>(bias + (c_first + kWaves * ct) * 16 + 4 * (lane >> 4));
-#pragma unroll
-    for (int e = 0; e < EX; ++e) bvx[e] = *reinterpret_cast<const f32x4*>(bias + exc[e] * 16 + 4 * (lane >> 4));
-    // The weight block of this op as a raw buffer (base = W, wave-uniform): a fragment load is buffer_load_dwordx4 v, v_off, s[rsrc],
-    // s_chunk offen -- the loop-invariant per-lane offset in a VGPR, the chunk offset (kk KiB) in an SGPR, NO address VALU work in
-    // the k loop (fp32 MFMAs and VALU instructions exclude each other on a SIMD: every v_lshl_add_u64 there is MFMA-pipe idle time)
-    // (W is wave-uniform by construction -- member and layer are -- but parts of it came through LDS, which the compiler's divergence
-    // analysis cannot see: without the readfirstlane it wraps every buffer_load in a waterfall loop)
-    const unsigned long long wbits = reinterpret_cast<unsigned long long>(W);
-    const unsigned long long wuni = ((unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(wbits >> 32)) << 32) |
-                                    (unsigned long long)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)wbits);
-    const __amdgpu_buffer_rsrc_t wrsrc = __builtin_amdgcn_make_buffer_rsrc(reinterpret_cast<float*>(wuni), 0, 0x7FFFFFFF, 0x00020000);
-    auto wload = [&](const unsigned voff, const int kk) __attribute__((always_inline)) {
-        const u32x4g v = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (int)voff, kk * 1024, 0);
-        f32x4 r;
-        __builtin_memcpy(&r, &v, 16);
-        return r;
-    };
-    auto load = [&](GemmFrags<R, CT, EX>& f, const int kk) __attribute__((always_inline)) {
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) f.b[ct] = wload(woff[ct], kk);
-#pragma unroll
-        for (int e = 0; e < EX; ++e) f.bx[e] = wload(wxoff[e], kk);
-#pragma unroll
-        for (int r = 0; r < R; ++r) f.a[r] = *reinterpret_cast<const f32x4*>(ap + r * 16 * ldi + kk * 16);
-#pragma unroll
-        for (int e = 0; e < EX; ++e) f.ax[e] = *reinterpret_cast<const f32x4*>(ap + axoff[e] + kk * 16);
-    };
-    // Hazards the compiler cannot see inside asm: (1) a VALU write (e.g. a phi copy of an accumulator) must be
-    // >= 2 wait states ahead of the MFMA that reads it -> s_nop 1 opens every k-step; (2) an MFMA that takes the
-    // previous MFMA's D as C back-to-back (issue interval 32 < dependent latency 40 cycles) reads a stale C on
-    // VGPR accumulators -> a wave whose whole share is ONE unit alternates two accumulators (even / odd k-steps).
-    constexpr bool kSplit = (CT * R + EX) == 1;
-    constexpr bool kSplitAll = SPL && !kSplit;
-    f32x4 acc_odd = f32x4{0.f, 0.f, 0.f, 0.f};
-    f32x4 acco[CTn][R], accxo[EXn];  // kSplitAll: the odd k-steps of every unit
-#pragma unroll
-    for (int ct = 0; ct < CTn; ++ct)
-#pragma unroll
-        for (int r = 0; r < R; ++r) acco[ct][r] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int e = 0; e < EXn; ++e) accxo[e] = f32x4{0.f, 0.f, 0.f, 0.f};
-    auto kstep = [&](const GemmFrags<R, CT, EX>& f, const int s) __attribute__((always_inline)) {
-        asm volatile("s_nop 1");
-        if constexpr (kSplit) {
-            f32x4& dst = (s & 1) ? acc_odd : (CT ? acc[0][0] : accx[0]);
-            if constexpr (CT) mfma16x16x4(f.b[0][s], f.a[0][s], dst);
-            else mfma16x16x4(f.bx[0][s], f.ax[0][s], dst);
-        } else if constexpr (kSplitAll) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int r = 0; r < R; ++r) mfma16x16x4(f.b[ct][s], f.a[r][s], (s & 1) ? acco[ct][r] : acc[ct][r]);
-#pragma unroll
-            for (int e = 0; e < EX; ++e) mfma16x16x4(f.bx[e][s], f.ax[e][s], (s & 1) ? accxo[e] : accx[e]);
-        } else {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int r = 0; r < R; ++r) mfma16x16x4(f.b[ct][s], f.a[r][s], acc[ct][r]);
-#pragma unroll
-            for (int e = 0; e < EX; ++e) mfma16x16x4(f.bx[e][s], f.ax[e][s], accx[e]);
-        }
-    };
-    auto compute = [&](const GemmFrags<R, CT, EX>& f) __attribute__((always_inline)) {
-#pragma unroll
-        for (int s = 0; s < 4; ++s) kstep(f, s);
-    };
-    // Interleaved form of "load the next chunk, then compute this one": the kNL fragment loads of chunk
-    // kk_next are issued ONE AT A TIME, evenly spread behind the MFMAs of the current chunk, instead of as a clump in front of it.
-    // Measured stand-alone (profiles/microbench/kloop_probe.hip, this wave's 3 x 3 + 1 tiling, 220 workgroups): a VMEM / LDS
-    // instruction issued while no MFMA is executing costs ~12 cycles of matrix-pipe idle time (8 per 40 MFMAs: 34.46 cycles per
-    // MFMA); issued inside an MFMA's 32-cycle shadow it is free (32.98).  Weight fragments first: they have the L2 round trip
-    // ahead of them and are needed >= 30 MFMAs (~1 000 cycles) later; the LDS fragments follow in the order the next chunk's first
-    // MFMAs consume them.  sched_barrier(0) on both sides pins each load where it is written.
-    constexpr bool kIL = LD > 0;  // shape-specialised instances only: in the generic ones (every shape x activation in one kernel, at the
-                                  // 256-VGPR limit) the longer live ranges spill 16-20 VGPRs to scratch
-    constexpr int kNU = CT * R + EX;                              // MFMA units of this wave
-    constexpr int kNL = CT + EX + (CT > 0 ? R : 0) + EX;          // fragment loads per chunk
-    static_assert(4 * kNU >= kNL + 1, "every load needs its own slot behind an MFMA");
-    auto load_one = [&](GemmFrags<R, CT, EX>& g, const int kk, const int i) __attribute__((always_inline)) {
-        __builtin_amdgcn_sched_barrier(0);
-        if (i < CT) g.b[i < CT ? i : 0] = wload(woff[i < CT ? i : 0], kk);
-        else if (i < CT + EX) g.bx[i - CT] = wload(wxoff[i - CT], kk);
-        else if (CT > 0 && i < CT + EX + R) g.a[i - CT - EX] = *reinterpret_cast<const f32x4*>(ap + (i - CT - EX) * 16 * ldi + kk * 16);
-        else {
-            const int e = i - CT - EX - (CT > 0 ? R : 0);
-            g.ax[e] = *reinterpret_cast<const f32x4*>(ap + axoff[e] + kk * 16);
-        }
-        __builtin_amdgcn_sched_barrier(0);
-    };
-    auto mfma_unit = [&](const GemmFrags<R, CT, EX>& f, const int s, const int u) __attribute__((always_inline)) {
-        if constexpr (kSplit) {
-            f32x4& dst = (s & 1) ? acc_odd : (CT ? acc[0][0] : accx[0]);
-            if constexpr (CT) mfma16x16x4(f.b[0][s], f.a[0][s], dst);
-            else mfma16x16x4(f.bx[0][s], f.ax[0][s], dst);
-        } else if (u < CT * R) {
-            const int ct = u / R, r = u - ct * R;
-            if constexpr (kSplitAll) mfma16x16x4(f.b[ct][s], f.a[r][s], (s & 1) ? acco[ct][r] : acc[ct][r]);
-            else mfma16x16x4(f.b[ct][s], f.a[r][s], acc[ct][r]);
-        } else {
-            const int e = u - CT * R;
-            if constexpr (kSplitAll) mfma16x16x4(f.bx[e][s], f.ax[e][s], (s & 1) ? accxo[e] : accx[e]);
-            else mfma16x16x4(f.bx[e][s], f.ax[e][s], accx[e]);
-        }
-    };
-    // after MFMA number m1 (1-based) of the chunk: the loads whose slot this is.  Load j goes behind MFMA (j + 1) * total / (kNL + 1):
-    // evenly spread, the last one still several MFMAs ahead of the chunk's end (the next chunk's first MFMAs want its data).
-    // Plain nested loops with compile-time bounds and an explicit `#pragma unroll` each: every array index must be a constant
-    // after unrolling (a dynamically indexed fragment array is demoted to scratch memory -- measured: 28 ms per rollout).
-    auto loads_behind = [&](GemmFrags<R, CT, EX>& g, const int kk_next, const int m1) __attribute__((always_inline)) {
-#pragma unroll
-        for (int j = 0; j < kNL; ++j)
-            if (((j + 1) * 4 * kNU) / (kNL + 1) == m1) load_one(g, kk_next, j);
-    };
-    auto compute_il = [&](const GemmFrags<R, CT, EX>& f, GemmFrags<R, CT, EX>& g, const int kk_next) __attribute__((always_inline)) {
-#pragma unroll
-        for (int ks = 0; ks < 4; ++ks) {
-            asm volatile("s_nop 1");  // hazard guard of kstep above
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int r = 0; r < R; ++r) {
-                    mfma_unit(f, ks, ct * R + r);
-                    loads_behind(g, kk_next, ks * kNU + ct * R + r + 1);
-                }
-#pragma unroll
-            for (int e = 0; e < EX; ++e) {
-                mfma_unit(f, ks, CT * R + e);
-                loads_behind(g, kk_next, ks * kNU + CT * R + e + 1);
-            }
-        }
-    };
-    // The compiler models an asm MFMA as an ordinary instruction whose result is ready immediately, so any VALU
-    // copy of an accumulator it places right behind one (phi copies where control flow merges) would read the
-    // register before the matrix pipe has written it.  drain_all() = wait out the pipe, then re-define every
-    // accumulator through an empty asm so such copies can only be scheduled after the wait.  It ends every
-    // conditional arm below and follows the main loop; the loop body itself is branch-free and in place.
-    auto drain_all = [&]() __attribute__((always_inline)) {
-        mfma_drain();
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int r = 0; r < R; ++r) asm volatile("" : "+v"(acc[ct][r]));
-#pragma unroll
-        for (int e = 0; e < EX; ++e) asm volatile("" : "+v"(accx[e]));
-        asm volatile("" : "+v"(acc_odd));
-        if constexpr (kSplitAll) {
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-                for (int r = 0; r < R; ++r) asm volatile("" : "+v"(acco[ct][r]));
-#pragma unroll
-            for (int e = 0; e < EX; ++e) asm volatile("" : "+v"(accxo[e]));
-        }
-    };
-    // last chunk: only the k-steps that hold real (non-padding) weights, e.g. 2 of 4 for K = 200
-    auto compute_tail = [&](const GemmFrags<R, CT, EX>& f) __attribute__((always_inline)) {
-        switch (tail_steps) {
-            case 1: kstep(f, 0); drain_all(); break;
-            case 2: kstep(f, 0); kstep(f, 1); drain_all(); break;
-            case 3: kstep(f, 0); kstep(f, 1); kstep(f, 2); drain_all(); break;
-            default: kstep(f, 0); kstep(f, 1); kstep(f, 2); kstep(f, 3); drain_all(); break;
-        }
-    };
-
-    // sched_barrier(0) pins "issue the next chunk's loads, THEN this chunk's MFMAs": without it the machine
-    // scheduler sinks each load group down to its first use and the pipeline degenerates to load->wait->compute.
-    // k-split: the partials of the input's last chunk (KSI) and this wave's share of the split tile (KSO: its weight and activation
-    // fragments, ALL requested up front -- unused slots read chunk 0 and are zeroed below: straight-line code, no branch around an MFMA)
-    f32x4 ks_p[kWaves], ks_b[kKsSlots], ks_a[kKsSlots], ks_bias = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (KSI) {
-#pragma unroll
-        for (int w = 0; w < kWaves; ++w) ks_p[w] = *reinterpret_cast<const f32x4*>(ks->part_in + (w * 64 + lane) * 4);
-    }
-    if constexpr (KSO) {
-        const unsigned xoff = (unsigned)((ks->tile * KC * 64 + lane) * 16);
-        ks_bias = *reinterpret_cast<const f32x4*>(bias + ks->tile * 16 + 4 * (lane >> 4));
-#pragma unroll
-        for (int j = 0; j < kKsSlots; ++j) {
-            const int c = j < ks->n ? ks->k0 + j : 0;
-            ks_b[j] = wload(xoff, c);
-            ks_a[j] = *reinterpret_cast<const f32x4*>(ap + c * 16);
-        }
-    }
-    GemmFrags<R, CT, EX> f0, f1;
-    load(f0, 0);
-    // One-tile k-split instances fetch TWO chunks ahead (kTriple below): a wave's 12 MFMAs per chunk (384 cycles) are no cover for an
-    // L2 round trip issued somewhere inside the previous chunk
-    // (ops whose chunk count is a compile-time fact -- KCS: everything fed by a hidden layer -- so that the loop's remainder is no run-time
-    // branch: the allocator copies accumulators where such arms begin and sinks the copies to just in front of their first MFMA)
-    constexpr bool kTriple = KS != 0 && KCS > 0 && LD > 0;
-    static_assert(!KS || KCS <= 0 || kTriple, "k-split ops with a static chunk count run the three-set loop");
-    if constexpr (kTriple) load(f1, KCS > 1 ? 1 : 0);
-    // accumulators start at the bias (C input of the first MFMA) instead of zero: no add in the epilogue.  Initialised AFTER
-    // chunk 0's fragment loads were issued: the bias loads are older, so waiting for them leaves the fragments in flight
-    // (initialising first serialised two L2 round trips per layer: ~1.2k cycles of "set-up" per layer in the phase profile)
-#pragma unroll
-    for (int ct = 0; ct < CTn; ++ct)
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[ct][r] = CT > 0 ? bv[ct] : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int e = 0; e < EXn; ++e) accx[e] = EX > 0 ? bvx[e] : f32x4{0.f, 0.f, 0.f, 0.f};
-    // Pin every accumulator's initial value HERE: to the compiler an asm MFMA is an ordinary reader of its C operand, so it may
-    // sink the (VALU) initialisation -- a copy of the bias, the zeros of the odd-k-step accumulators -- down to just in front of
-    // the first MFMA that uses the register, inside a k-step, behind that k-step's s_nop: a VALU write followed at once by an MFMA
-    // reading it as SrcC (hazard (1) below; found in the ISA of the cfg4 instances by __graft_entry__.scan_isa_hazards (tests/test_abi.py), where it returned
-    // wrong sums).  An empty asm that "modifies" the register makes the value opaque: it must be complete before this point.
-    auto pin = [](f32x4& v) __attribute__((always_inline)) { asm volatile("" : "+v"(v)); };
-#pragma unroll
-    for (int ct = 0; ct < CTn; ++ct)
-#pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if constexpr (CT > 0) pin(acc[ct][r]);
-            if constexpr (CT > 0 && kSplitAll) pin(acco[ct][r]);
-        }
-#pragma unroll
-    for (int e = 0; e < EXn; ++e) {
-        if constexpr (EX > 0) pin(accx[e]);
-        if constexpr (EX > 0 && kSplitAll) pin(accxo[e]);
-    }
-    if constexpr (kSplit) pin(acc_odd);
-    prof.mark(14);
-    f32x4 a_last = f32x4{0.f, 0.f, 0.f, 0.f};
-    if constexpr (KSI) {  // this lane's fragment of the input's last chunk: the activation of the four partial sums, in ONE fixed order
-        static_assert(ACT == HIPETS_ACT_SILU, "k-split instances are SiLU instances");
-        a_last = silu4((ks_p[0] + ks_p[1]) + (ks_p[2] + ks_p[3]));
-    }
-    f32x4 ks_e = f32x4{0.f, 0.f, 0.f, 0.f}, ks_o = f32x4{0.f, 0.f, 0.f, 0.f};  // even / odd k-steps of the split tile (hazard (2) above)
-    if constexpr (KSO) {
-        // Wave-uniform choices as ARITHMETIC (a multiply by 1.0f or 0.0f from an SGPR: exact on finite values), never as control flow:
-        // written as `if`s the compiler built a web of ~40 scalar branches around these 20 register writes
-        ks_e = ks_bias * (ks->wave == 0 ? 1.0f : 0.0f);  // the sum of the four partials carries the bias once
-#pragma unroll
-        for (int j = 0; j < kKsSlots; ++j) ks_b[j] = ks_b[j] * (j < ks->n ? 1.0f : 0.0f);  // unused slot: 0 x (a valid activation of chunk 0)
-        if constexpr (KSI) {
-            // the input's last chunk lives in registers (a_last), not in LDS.  In an op fed by a hidden layer it is the LAST slot of the
-            // LAST wave (KC = 13 .. 16: wave 3 holds chunks [3 KC / 4, KC), four of them); on the other waves that slot is unused (zero
-            // weights), so it may hold the same finite values there: no selection at all
-            HIPETS_BOUND(KC >= 13 && KC <= 16);
-            ks_a[kKsSlots - 1] = a_last;
-        }
-        pin(ks_e);
-        pin(ks_o);
-#pragma unroll
-        for (int j = 0; j < kKsSlots; ++j) {
-            pin(ks_b[j]);
-            pin(ks_a[j]);
-        }
-#pragma unroll
-        for (int j = 0; j < kKsSlots; ++j)
-#pragma unroll
-            for (int s_ = 0; s_ < 4; ++s_) {
-                asm volatile("s_nop 1");
-                mfma16x16x4(ks_b[j][s_], ks_a[j][s_], (s_ & 1) ? ks_o : ks_e);
-            }
-        prof.mark(7);  // (profiling builds) the k-split share: its loads' round trip + 16 MFMAs
-    }
-    if constexpr (KCS > 0 && !kTriple) {
-        constexpr int kEnd = KCS >= 2 ? ((KCS - 1) / 2) * 2 : 0;  // the loop below leaves kk at the smallest even number >= KCS - 2
-#pragma unroll
-        for (int kk = 0; kk + 2 < KCS; kk += 2) {
-            if constexpr (kIL) {
-                compute_il(f0, f1, kk + 1);
-                compute_il(f1, f0, kk + 2);
-            } else {
-                load(f1, kk + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                compute(f0);
-                __builtin_amdgcn_sched_barrier(0);
-                load(f0, kk + 2);
-                __builtin_amdgcn_sched_barrier(0);
-                compute(f1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        if constexpr (kEnd + 1 < KCS) {
-            if constexpr (kIL) {
-                compute_il(f0, f1, kEnd + 1);
-            } else {
-                load(f1, kEnd + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                compute(f0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            compute_tail(f1);
-        } else {
-            compute_tail(f0);
-        }
-    } else if constexpr (kTriple) {
-        // three fragment sets in rotation: chunk kk is computed from one while chunk kk + 2 is being fetched into another (measured
-        // on MI355X, one-tile workgroups, round 5: with one chunk of lead the k loop of a wave with 3 column tiles ran at the pace of
-        // the L2 round trips, not of its MFMAs -- profiles/r5_small_batches.json)
-        GemmFrags<R, CT, EX> f2;
-        auto last_frag = [&](GemmFrags<R, CT, EX>& f) __attribute__((always_inline)) {  // KSI: see the two-set loop below
-            if constexpr (KSI) {
-                if constexpr (CT > 0) f.a[0] = a_last;
-#pragma unroll
-                for (int e = 0; e < EX; ++e) f.ax[e] = a_last;
-                if constexpr (CT > 0) pin(f.a[0]);
-#pragma unroll
-                for (int e = 0; e < EX; ++e) pin(f.ax[e]);
-            }
-        };
-        constexpr int kEnd3 = KCS >= 3 ? ((KCS - 1) / 3) * 3 : 0;  // where the loop below leaves kk
-        constexpr int kRem = KCS - kEnd3;                          // 1 .. 3 chunks left then, the last of them the tail chunk
-#pragma nounroll
-        for (int kk = 0; kk + 3 < KCS; kk += 3) {  // chunks kk .. kk + 2 are full ones; f0 = chunk kk, f1 = chunk kk + 1 on entry
-            compute_il(f0, f2, kk + 2);
-            compute_il(f1, f0, kk + 3);
-            compute_il(f2, f1, min(kk + 4, KCS - 1));  // (past the end: the last chunk once more, never used)
-        }
-        drain_all();
-        if constexpr (kRem == 1) {
-            last_frag(f0);
-            compute_tail(f0);
-        } else if constexpr (kRem == 2) {
-            compute(f0);
-            drain_all();
-            last_frag(f1);
-            compute_tail(f1);
-        } else {
-            compute_il(f0, f2, kEnd3 + 2);
-            compute(f1);
-            drain_all();
-            last_frag(f2);
-            compute_tail(f2);
-        }
-    } else {
-        int kk = 0;
-        for (; kk + 2 < KC; kk += 2) {  // chunks kk, kk+1 are not the last one
-            if constexpr (kIL) {
-                compute_il(f0, f1, kk + 1);
-                compute_il(f1, f0, kk + 2);
-            } else {
-                load(f1, kk + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                compute(f0);
-                __builtin_amdgcn_sched_barrier(0);
-                load(f0, kk + 2);
-                __builtin_amdgcn_sched_barrier(0);
-                compute(f1);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-        }
-        // (k-split instances drain unconditionally: their register allocation copies the accumulators where the tail's arms begin, and
-        // the build's ISA scan cannot know that the path "loop left with results in flight AND kk == 0" does not exist)
-        if (KS != 0 || kk > 0) drain_all();
-        // KSI: the last chunk's activation fragment is a_last (what the loads above fetched from that LDS position is unwritten space)
-        auto last_frag = [&](GemmFrags<R, CT, EX>& f) __attribute__((always_inline)) {
-            if constexpr (KSI) {
-                if constexpr (CT > 0) f.a[0] = a_last;
-#pragma unroll
-                for (int e = 0; e < EX; ++e) f.ax[e] = a_last;
-                if constexpr (CT > 0) pin(f.a[0]);
-#pragma unroll
-                for (int e = 0; e < EX; ++e) pin(f.ax[e]);
-            }
-        };
-        if (kk + 1 < KC) {  // two chunks left: kk (full) and kk+1 (tail)
-            if constexpr (kIL) {
-                compute_il(f0, f1, kk + 1);
-            } else {
-                load(f1, kk + 1);
-                __builtin_amdgcn_sched_barrier(0);
-                compute(f0);
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            if constexpr (KS != 0) drain_all();  // (the allocator copies the accumulators where the tail's arms begin: see above)
-            last_frag(f1);
-            compute_tail(f1);
-        } else {  // one chunk left
-            last_frag(f0);
-            compute_tail(f0);
-        }
-    }
-    // the fused tail runs over the wave's units in groups of at most kTailGroup: within a group the LDS loads of ALL its units are
-    // issued first (prep), then the arithmetic (unit); the slots of one group are dead before the next starts (a wave of a
-    // 47-tile output layer holds 6-8 units per pass: all their slots at once would not fit the arch VGPRs)
-    constexpr int kNUt = CT * R + EX;
-    constexpr int kTailGroup = 4;
-    FusedSlot slots[kTailGroup];
-    auto unit_c = [&](const int u) __attribute__((always_inline)) { return u < CT * R ? c_first + kWaves * (u / R) : exc[(u >= CT * R && u < kNUt) ? u - CT * R : 0]; };
-    auto unit_r = [&](const int u) __attribute__((always_inline)) { return u < CT * R ? u % R : exr[(u >= CT * R && u < kNUt) ? u - CT * R : 0]; };
-    if constexpr (!std::is_same<TL, NoTail>::value) {  // the first group's LDS loads: in flight while the matrix pipe drains
-#pragma unroll
-        for (int k = 0; k < kTailGroup; ++k)
-            if (k < kNUt) tl->prep(slots[k < kNUt ? k : 0], unit_c(k), unit_r(k));
-    }
-    if constexpr (kSplit) {
-        mfma_drain();
-        if constexpr (CT) acc[0][0] += acc_odd;
-        else accx[0] += acc_odd;
-    }
-    if constexpr (kSplitAll) {
-        drain_all();
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int r = 0; r < R; ++r) acc[ct][r] += acco[ct][r];
-#pragma unroll
-        for (int e = 0; e < EX; ++e) accx[e] += accxo[e];
-    }
-    mfma_drain();
-    __builtin_amdgcn_sched_barrier(0);
-    prof.mark(11);
-    if constexpr (!std::is_same<TL, NoTail>::value) {
-        // (constant trip counts on both levels: every slot / accumulator index must be a constant after unrolling)
-#pragma unroll
-        for (int g = 0; g < (kNUt + kTailGroup - 1) / kTailGroup; ++g) {
-            if (g > 0) {
-#pragma unroll
-                for (int k = 0; k < kTailGroup; ++k) {
-                    const int u = g * kTailGroup + k;
-                    if (u < kNUt) tl->prep(slots[k], unit_c(u), unit_r(u));
-                }
-            }
-            static_assert(kTailGroup % 2 == 0, "the draw stage pairs the units of a group");
-            // (pair by pair -- draw, unit, unit -- so that only one pair's normals are live at a time: with the whole group's drawn up front
-            // three two-workgroups-per-CU instances spilt to scratch memory)
-#pragma unroll
-            for (int k = 0; k < kTailGroup; k += 2) {
-                const int u = g * kTailGroup + k;
-                if (u + 1 < kNUt) tl->draw(slots[k], slots[k + 1], unit_c(u), unit_c(u + 1), true);
-                else if (u < kNUt) tl->draw(slots[k], slots[k], unit_c(u), unit_c(u), false);
-#pragma unroll
-                for (int kk = k; kk < k + 2; ++kk) {
-                    const int uu = g * kTailGroup + kk;
-                    if (uu < CT * R) tl->unit(slots[kk], acc[(uu < CT * R ? uu : 0) / R][(uu < CT * R ? uu : 0) % R], unit_c(uu), unit_r(uu));
-                    else if (uu < kNUt) tl->unit(slots[kk], accx[(uu >= CT * R && uu < kNUt) ? uu - CT * R : 0], unit_c(uu), unit_r(uu));
-                }
-            }
-        }
-        tl->finish();
-        prof.mark(9);  // the fused tail is booked as the "sample" phase
-        return;
-    }
-
-    if constexpr (KSO) {
-        // this wave's partial sum of the split tile -> LDS, as the f32x4 the lane holds (= the next op's fragment layout).  The two
-        // accumulators are re-defined behind the drain above: to the compiler an asm MFMA's result is ready at once, and it would
-        // otherwise be free to form this sum right behind the mini-loop, while the matrix pipe still writes the registers
-        asm volatile("" : "+v"(ks_e));
-        asm volatile("" : "+v"(ks_o));
-        *reinterpret_cast<f32x4*>(ks->part_out + (ks->wave * 64 + lane) * 4) = ks_e + ks_o;
-    }
-    // epilogue: D[row = 4*(lane>>4)+i][col = lane&15] -> bias, activation, next layer's A image.
-    // The activation switch is hoisted OUT of the element loops: one compact straight-line body per
-    // activation (a per-element switch made the hot path stream ~12 KB of mostly-skipped code per layer
-    // through the instruction cache: 11k cycles per epilogue instead of ~2k).
-    // The product is formed transposed (weights are the MFMA A operand, activations the B operand), so a lane's
-    // accumulator holds 4 CONSECUTIVE LDS columns (16c + 4g .. +3; the weight / bias packing pre-permutes the real
-    // columns so that this holds in the chunk-transposed layout too) of batch row 16r + (lane & 15): one
-    // ds_write_b128 per accumulator instead of four ds_write_b32.
-    // actfn maps the 4 accumulator values of a lane at once (lets an activation use packed 2 x f32 VALU instructions:
-    // a wave's VALU work is not hidden behind anything here, so the instruction count is the cost)
-    auto store = [&](auto actfn) __attribute__((always_inline)) {
-        const int j = lane & 15, g4 = 4 * (lane >> 4);
-        HIPETS_BOUND(c_first >= 0 && (CT == 0 || (c_first + kWaves * (CT - 1)) * 16 + g4 + 3 < ld) && KC >= 1 && KC * 16 <= ldi);
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            const int col = (c_first + kWaves * ct) * 16 + g4;
-#pragma unroll
-            for (int r = 0; r < R; ++r) *reinterpret_cast<f32x4*>(out + (r * 16 + j) * ld + col) = actfn(acc[ct][r]);
-        }
-#pragma unroll
-        for (int e = 0; e < EX; ++e) *reinterpret_cast<f32x4*>(out + (exr[e] * 16 + j) * ld + exc[e] * 16 + g4) = actfn(accx[e]);
-    };
-    auto each = [](auto f) {  // lift a scalar activation to the 4 values
-        return [f](const f32x4 a) {
-            f32x4 v;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) v[i] = f(a[i]);
-            return v;
-        };
-    };
-    if (!apply_act) {
-        store([](const f32x4 a) { return a; });
-    } else {
-        switch (ACT >= 0 ? ACT : act) {
-            case HIPETS_ACT_SILU: store([](const f32x4 a) { return silu4(a); }); break;
-            case HIPETS_ACT_RELU: store(each([](float x) { return x < 0.0f ? 0.0f : x; })); break;  // NOT fmaxf: v_max_f32 returns 0 for a NaN input, torch.relu returns NaN
-            case HIPETS_ACT_LEAKY_RELU: store(each([slope](float x) { return x > 0.0f ? x : slope * x; })); break;
-            case HIPETS_ACT_TANH: store(each([](float x) { return tanhf(x); })); break;
-            default: store(each([](float x) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(x * -1.44269504088896340736f)); })); break;
-        }
-    }
-    prof.mark(13);
-}
-
-template <int R, int CT, int ACT, bool SPL = false>
-__device__ __forceinline__ void wave_gemm_ex(int nex, const float* in, float* out, int ld, const float* W,
-                                             const float* bias, int KC, int tail_steps, int c_first, const Extras ex,
-                                             bool apply_act, int act, float slope, int lane, Prof& prof) {
-    // a wave holds at most ceil(3 R / 4) leftover units (C % 4 <= 3 leftover column tiles x R row tiles dealt to 4 waves): only those
-    // counts are instantiated (every instance adds to the kernel's register maximum, and the generic kernels sit at the limit)
-    constexpr int kMaxEx = (3 * R + kWaves - 1) / kWaves;
-    switch (nex) {
-        case 0:
-            if constexpr (CT > 0) wave_gemm<R, CT, 0, ACT, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof);
-            break;
-        case 1: wave_gemm<R, CT, 1, ACT, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof); break;
-        case 2:
-            if constexpr (kMaxEx >= 2) wave_gemm<R, CT, 2, ACT, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof);
-            break;
-        default:
-            if constexpr (kMaxEx >= 3) wave_gemm<R, CT, 3, ACT, NoTail, -1, SPL>(in, out, ld, W, bias, KC, tail_steps, c_first, ex, apply_act, act, slope, lane, prof);
-            break;
-    }
-}
-
-// One linear op (+activation) for the workgroup's 16*R rows: in (LDS) -> out (LDS), both with row stride ld.
-// W / bias point at the packed fragments / padded biases of this op (pack_weights_kernel / pack_bias_kernel).
-// CS >= 0: the number of column tiles is a compile-time fact (shape-specialised kernels): every wave's (CT, EX) follows
-// from it and the wave index through ONE branch, and only the two wave_gemm instances the shape needs are compiled;
-// CS < 0: it is read from the layer table and dispatched through the (full, nex) switches.
-// KS (shape-specialised ops of one-tile workgroups): wave_gemm's k-split bits; part_in / part_out: the partial-sum buffers (KsArgs)
-template <int R, int ACT = -1, int CS = -1, class TL = NoTail, int LD = -1, bool SPL = false, int KCS = -1, int KS = 0>
-__device__ __forceinline__ void linear_op(const float* W, const float* bias, const LayerMeta lm, const int ld, const bool apply_act,
-                                          const int activation, const float slope, const float* in, float* out, const int wave,
-                                          const int lane, Prof& prof, const TL* tl = nullptr, const int ldi = 0,
-                                          const float* part_in = nullptr, float* part_out = nullptr) {
-    static_assert(std::is_same<TL, NoTail>::value || CS >= 0, "a fused tail needs a shape-specialised op");
-    static_assert(!KS || CS >= 0, "k-split needs a shape-specialised op");
-    const int KC = lm.Kp / kKChunk;
-    if constexpr ((KS & 2) != 0) {
-        // k-split producer: the CS - 1 strided tiles as usual (CS / 4 per wave, no leftover units), the last tile's k range dealt to the waves
-        static_assert(CS % kWaves == 1 && CS / kWaves >= 1 && CS / kWaves <= 3, "k-split: one leftover column tile");
-        KsArgs ks;
-        ks.part_in = part_in; ks.part_out = part_out; ks.tile = CS - 1; ks.wave = wave;
-        ks.k0 = (wave * KC) / kWaves;
-        ks.n = ((wave + 1) * KC) / kWaves - ks.k0;
-        Extras ex0;
-        ex0.c0 = ex0.c1 = ex0.c2 = ex0.c3 = 0; ex0.r0 = ex0.r1 = ex0.r2 = ex0.r3 = 0;
-        wave_gemm<R, CS / kWaves, 0, ACT, NoTail, LD, false, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, wave, ex0, apply_act, activation, slope, lane, prof,
-                                                                     nullptr, ldi, &ks);
-    } else {
-    KsArgs ks;  // (KS == 1: a consumer only -- the output layer)
-    ks.part_in = part_in; ks.part_out = nullptr; ks.tile = 0; ks.k0 = 0; ks.n = 0; ks.wave = wave;
-    // a wave's strided column tiles go through in passes of at most kMaxCT tiles (accumulator + double-buffered
-    // fragment registers must fit the 256 VGPRs two waves per SIMD leave each wave)
-    constexpr int kMaxCT = kWaves >= 8 ? 2 : 3;
-    if constexpr (CS >= 0) {
-        constexpr int full = CS / kWaves, rem = CS % kWaves, nu = rem * R;
-        Extras ex;
-        ex.c0 = kWaves * full + wave / R;                ex.r0 = wave % R;
-        ex.c1 = kWaves * full + (wave + kWaves) / R;     ex.r1 = (wave + kWaves) % R;
-        ex.c2 = kWaves * full + (wave + 2 * kWaves) / R; ex.r2 = (wave + 2 * kWaves) % R;
-        ex.c3 = kWaves * full + (wave + 3 * kWaves) / R; ex.r3 = (wave + 3 * kWaves) % R;
-        constexpr int passes = full > kMaxCT ? (full - 1) / kMaxCT : 0;  // whole passes of kMaxCT tiles before the last one
-        constexpr int last = full - passes * kMaxCT;                      // 0 .. kMaxCT column tiles ride with the extras
-        if constexpr (std::is_same<TL, NoTail>::value) {
-#pragma unroll
-            for (int p = 0; p < passes; ++p)
-                wave_gemm<R, kMaxCT, 0, ACT, TL, LD, SPL, KCS, (KS & 4)>(in, out, ld, W, bias, KC, lm.tail_steps, wave + kWaves * kMaxCT * p, ex, apply_act, activation, slope, lane, prof, tl, ldi);
-        } else {  // with a fused tail inlined per unit the body is large: ONE copy, a real loop over the passes
-#pragma nounroll
-            for (int p = 0; p < passes; ++p)
-                wave_gemm<R, kMaxCT, 0, ACT, TL, LD, SPL, KCS, (KS & 4)>(in, out, ld, W, bias, KC, lm.tail_steps, wave + kWaves * kMaxCT * p, ex, apply_act, activation, slope, lane, prof, tl, ldi);
-        }
-        const int c_first = wave + kWaves * kMaxCT * passes;
-        // the nu leftover units are dealt round-robin: waves below nu % kWaves hold one more than the others
-        constexpr int lo = nu / kWaves, hi = (nu + kWaves - 1) / kWaves;
-        if constexpr (lo == hi) {
-            if constexpr (last > 0 || lo > 0)
-                wave_gemm<R, last, lo, ACT, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks);
-        } else {
-            if (wave < nu % kWaves) {
-                wave_gemm<R, last, hi, ACT, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks);
-            } else {
-                if constexpr (last > 0 || lo > 0)
-                    wave_gemm<R, last, lo, ACT, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks);
-            }
-        }
-    } else {
-        const int C = lm.Np / kTile;
-        const int full = C / kWaves, rem = C % kWaves;
-        // leftover units u = (column tile kWaves*full + u / R, row tile u % R), dealt round-robin to waves
-        const int nu = rem * R;
-        Extras ex;
-        ex.c0 = kWaves * full + wave / R;                ex.r0 = wave % R;
-        ex.c1 = kWaves * full + (wave + kWaves) / R;     ex.r1 = (wave + kWaves) % R;
-        ex.c2 = kWaves * full + (wave + 2 * kWaves) / R; ex.r2 = (wave + 2 * kWaves) % R;
-        ex.c3 = kWaves * full + (wave + 3 * kWaves) / R; ex.r3 = (wave + 3 * kWaves) % R;
-        const int nex = wave < nu ? (nu - wave + kWaves - 1) / kWaves : 0;  // <= kMaxExtras since rem < kWaves, R <= 4
-        int done = 0;
-        while (full - done > kMaxCT) {
-            wave_gemm<R, kMaxCT, 0, ACT, NoTail, -1, SPL>(in, out, ld, W, bias, KC, lm.tail_steps, wave + kWaves * done, ex, apply_act, activation, slope, lane, prof);
-            done += kMaxCT;
-        }
-        const int c_first = wave + kWaves * done;
-        switch (full - done) {
-            case 0: wave_gemm_ex<R, 0, ACT, SPL>(nex, in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof); break;
-            case 1: wave_gemm_ex<R, 1, ACT, SPL>(nex, in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof); break;
-            case 2: wave_gemm_ex<R, 2, ACT, SPL>(nex, in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof); break;
-            default:
-                // (SPL ops have at most 8 column tiles, i.e. at most 2 strided tiles per wave: mlp_layer)
-                if constexpr (kMaxCT >= 3 && !SPL)
-                    wave_gemm_ex<R, 3, ACT, SPL>(nex, in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof);
-                break;
-        }
-    }
-    }  // (not a k-split producer)
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
-// bf16x3 precision mode ("f32 on the bf16 matrix pipe").  An fp32 operand x is carried as three bf16 pieces x0 + x1 + x2
-// (x0 = bf16(x), x1 = bf16(x - x0), x2 = bf16(x - x0 - x1): |x - x0 - x1 - x2| <= 2^-24 |x|), and a product a b is formed from
-// the six partial products of weight <= 2^-16: a0 b0 + (a0 b1 + a1 b0) + (a0 b2 + a1 b1 + a2 b0), each EXACT in fp32
-// (8 x 8 significand bits), accumulated in fp32 by v_mfma_f32_16x16x32_bf16.  The dropped terms (a1 b2, a2 b1, a2 b2) are
-// <= 2^-23 |a b|: the result is fp32-accurate to a few ulps of the products, at 6 x 17 cycles per 16x16x32 block instead of
-// 8 x 32 cycles for the fp32 MFMAs -- and the bf16 matrix pipe, unlike the fp32 one, runs beside the VALU.
-// Layouts: weights packed per (column tile, 32-wide k chunk, piece) as one A-operand fragment (lane l: output column
-// l & 15, k = 8 (l >> 4) .. + 7); activations in LDS per row as [k chunk][piece][4 groups][8 x bf16] so that a lane's
-// B-operand fragment of a piece is ONE ds_read_b128.  The last layer's results stay fp32 (sampling reads them).
-// Precision bf16 (HIPETS_PREC_BF16) is the one-piece form of the same code (template parameter NP = 1): piece 0 alone, i.e. both
-// operands rounded to bf16 (nearest-even), exact products, fp32 accumulation, ONE MFMA per block; bias and SiLU in fp32.
-// ---------------------------------------------------------------------------------------------------------------------
-using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
-
-// round-to-nearest-even bf16 of x as the upper 16 bits of a word (finite x)
-__host__ __device__ __forceinline__ unsigned bf16_rne_bits(float x) {
-    unsigned u;
-    __builtin_memcpy(&u, &x, 4);
-    return (u + 0x7FFFu + ((u >> 16) & 1u)) & 0xFFFF0000u;
-}
-__host__ __device__ __forceinline__ float bits_to_float(unsigned u) {
-    float f;
-    __builtin_memcpy(&f, &u, 4);
-    return f;
-}
-// the three pieces of x as bf16 bit patterns (in the UPPER halves of h[0..2])
-__host__ __device__ __forceinline__ void split3(float x, unsigned (&h)[3]) {
-    h[0] = bf16_rne_bits(x);
-    const float r1 = x - bits_to_float(h[0]);
-    h[1] = bf16_rne_bits(r1);
-    const float r2 = r1 - bits_to_float(h[1]);
-    h[2] = bf16_rne_bits(r2);
-}
-// four consecutive values -> per piece one 8-byte word pair (4 x bf16, little endian: value 0 in the low half of word 0).
-// v_cvt_pk_bf16_f32 rounds two floats to nearest-even and packs them in exactly that order: one conversion, two bit
-// operations and one packed subtract per pair and piece (the host-side split3 above states the same arithmetic bit by bit).
-// NP = 1 keeps piece 0 alone: the plain bf16 rounding of precision bf16 (HIPETS_PREC_BF16).
-template <int NP>
-__device__ __forceinline__ void split_x4(const f32x4 v, u32x2 (&out)[NP]) {
-    using f32p = __attribute__((ext_vector_type(2))) float;
-    using bf16p = __attribute__((ext_vector_type(2))) __bf16;
-    f32p lo = {v[0], v[1]}, hi = {v[2], v[3]};
-#pragma unroll
-    for (int p = 0; p < NP; ++p) {
-        const bf16p hl = __builtin_convertvector(lo, bf16p), hh = __builtin_convertvector(hi, bf16p);
-        unsigned ul, uh;
-        __builtin_memcpy(&ul, &hl, 4);
-        __builtin_memcpy(&uh, &hh, 4);
-        out[p][0] = ul;
-        out[p][1] = uh;
-        if (p + 1 < NP) {
-            lo = lo - f32p{bits_to_float(ul << 16), bits_to_float(ul & 0xFFFF0000u)};
-            hi = hi - f32p{bits_to_float(uh << 16), bits_to_float(uh & 0xFFFF0000u)};
-        }
-    }
-}
-__device__ __forceinline__ bf16x8 as_bf16x8(const u32x4 v) {
-    bf16x8 r;
-    __builtin_memcpy(&r, &v, 16);
-    return r;
-}
-// byte offset inside an activation row of the 4 consecutive columns k0 .. k0 + 3 (k0 % 4 == 0) of piece p of NP
-template <int NP>
-__device__ __forceinline__ int b3_offset(int k0, int p) { return (k0 >> 5) * (64 * NP) + p * 64 + ((k0 & 31) >> 3) * 16 + (k0 & 7) * 2; }
-
-template <int R, int CT, int EX, int NP>
-struct GemmFragsB3 {
-    u32x4 w[CT > 0 ? CT : 1][NP];   // weight pieces (A operand) of the strided column tiles
-    u32x4 wx[EX > 0 ? EX : 1][NP];  // ... of the extra units
-    u32x4 a[R][NP];                 // activation pieces (B operand) of the row tiles
-    u32x4 ax[EX > 0 ? EX : 1][NP];
-};
-
-// One wave's share of a linear op in bf16x3 arithmetic: same unit decomposition as wave_gemm (CT strided column tiles x R row
-// tiles + EX extra units).  `in`: LDS activation pieces (byte stride ldb); hidden ops write the activated result as pieces into
-// `out`, the last op writes fp32 (float stride ldb / 4) for the sampling phase.
-// NP = 3: precision bf16x3.  NP = 1: precision bf16 -- one weight and one activation fragment per unit, ONE MFMA per unit and k
-// chunk, activation rows of 64 bytes per chunk; the bf16 store of a hidden layer's activated result IS the rounding of the next
-// layer's operand.  Its k loop is paced by the fragment loads, not by the MFMAs: fragments are requested kBf16Ahead chunks ahead
-// (measured per cfg2 rollout, DEVICE / FAST: 2 ahead 0.443 / 0.362 ms, 4 ahead 0.437 / 0.356 ms, all 7 chunks of a hidden layer
-// 0.450 / 0.375 ms -- profiles/bf16_rollout.json).
-constexpr int kBf16Ahead = 4;
-template <int R, int CT, int EX, int ACT, int NP>
-__device__ __forceinline__ void wave_gemm_b3(const char* __restrict__ in, char* __restrict__ out, const int ldb, const uint4* __restrict__ W3,
-                                             const float* __restrict__ bias, const int KC32, const int c_first, const Extras ex,
-                                             const bool last_op, const int lane) {
-    constexpr int CTn = CT > 0 ? CT : 1;
-    constexpr int EXn = EX > 0 ? EX : 1;
-    f32x4 acc[CTn][R];
-    f32x4 accx[EXn];
-    const int exc[kMaxExtras] = {ex.c0, ex.c1, ex.c2, ex.c3};
-    const int exr[kMaxExtras] = {ex.r0, ex.r1, ex.r2, ex.r3};
-    // weights: 16-byte units; (column tile c, chunk kk, piece p, lane) -> ((c * KC32 + kk) * NP + p) * 64 + lane
-    constexpr int kCh = 64 * NP;  // 16-byte weight units per (column tile, chunk) -- and bytes per chunk of an activation row
-    unsigned woff[CTn], wxoff[EXn];
-    int axoff[EXn];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) woff[ct] = (unsigned)((c_first + kWaves * ct) * KC32 * kCh + lane);
-#pragma unroll
-    for (int e = 0; e < EX; ++e) {
-        wxoff[e] = (unsigned)(exc[e] * KC32 * kCh + lane);
-        axoff[e] = exr[e] * 16 * ldb;
-    }
-    const char* ap = in + (lane & 15) * ldb + (lane >> 4) * 16;
-    // biases: the packed bias arrays serve the fp32 kernels, where hidden layers keep their columns permuted inside every group
-    // of 16 (position lds_col(n) holds column n; lds_col is an involution); here columns are natural
-    auto bias4 = [&](const int c) __attribute__((always_inline)) {
-        const int g = lane >> 4;
-        if (last_op) return *reinterpret_cast<const f32x4*>(bias + c * 16 + 4 * g);
-        const float* bp = bias + c * 16 + g;  // natural column 4 g + i sits at position 4 i + g
-        return f32x4{bp[0], bp[4], bp[8], bp[12]};
-    };
-#pragma unroll
-    for (int ct = 0; ct < CTn; ++ct) {
-        const f32x4 b = CT > 0 ? bias4(c_first + kWaves * ct) : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[ct][r] = b;
-    }
-#pragma unroll
-    for (int e = 0; e < EXn; ++e) accx[e] = EX > 0 ? bias4(exc[e]) : f32x4{0.f, 0.f, 0.f, 0.f};
-
-    auto load = [&](GemmFragsB3<R, CT, EX, NP>& f, const int kk) __attribute__((always_inline)) {
-        const uint4* Wk = W3 + (size_t)kk * kCh;
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int p = 0; p < NP; ++p) f.w[ct][p] = *reinterpret_cast<const u32x4*>(Wk + woff[ct] + p * 64);
-#pragma unroll
-        for (int e = 0; e < EX; ++e)
-#pragma unroll
-            for (int p = 0; p < NP; ++p) f.wx[e][p] = *reinterpret_cast<const u32x4*>(Wk + wxoff[e] + p * 64);
-#pragma unroll
-        for (int r = 0; r < R; ++r)
-#pragma unroll
-            for (int p = 0; p < NP; ++p) f.a[r][p] = *reinterpret_cast<const u32x4*>(ap + r * 16 * ldb + kk * kCh + p * 64);
-#pragma unroll
-        for (int e = 0; e < EX; ++e)
-#pragma unroll
-            for (int p = 0; p < NP; ++p) f.ax[e][p] = *reinterpret_cast<const u32x4*>(ap + axoff[e] + kk * kCh + p * 64);
-    };
-    // the six partial products of one unit, smallest weights first (NP = 1: the one product)
-    auto unit = [&](const u32x4 (&w)[NP], const u32x4 (&a)[NP], f32x4& c) __attribute__((always_inline)) {
-        if constexpr (NP == 3) {
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[2]), as_bf16x8(a[0]), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[1]), as_bf16x8(a[1]), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[0]), as_bf16x8(a[2]), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[1]), as_bf16x8(a[0]), c, 0, 0, 0);
-            c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[0]), as_bf16x8(a[1]), c, 0, 0, 0);
-        }
-        c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(as_bf16x8(w[0]), as_bf16x8(a[0]), c, 0, 0, 0);
-    };
-    auto compute = [&](const GemmFragsB3<R, CT, EX, NP>& f) __attribute__((always_inline)) {
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-            for (int r = 0; r < R; ++r) unit(f.w[ct], f.a[r], acc[ct][r]);
-#pragma unroll
-        for (int e = 0; e < EX; ++e) unit(f.wx[e], f.ax[e], accx[e]);
-    };
-    if constexpr (NP == 1) {
-        // a ring of kBf16Ahead fragment sets (32 registers each at R = 3): slot i holds chunks i, i + kBf16Ahead, ...; a slot is
-        // refilled as soon as its MFMAs are issued, so kBf16Ahead - 1 chunks of loads are in flight behind every compute
-        GemmFragsB3<R, CT, EX, NP> f[kBf16Ahead];
-#pragma unroll
-        for (int i = 0; i < kBf16Ahead; ++i)
-            if (i < KC32) load(f[i], i);
-        for (int kk = 0; kk < KC32; kk += kBf16Ahead) {
-#pragma unroll
-            for (int i = 0; i < kBf16Ahead; ++i) {
-                if (kk + i < KC32) {
-                    __builtin_amdgcn_sched_barrier(0);
-                    compute(f[i]);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (kk + i + kBf16Ahead < KC32) load(f[i], kk + i + kBf16Ahead);
-                }
-            }
-        }
-    } else {
-        GemmFragsB3<R, CT, EX, NP> f0, f1;
-        load(f0, 0);
-        int kk = 0;
-        for (; kk + 1 < KC32; kk += 2) {
-            load(f1, kk + 1);
-            __builtin_amdgcn_sched_barrier(0);
-            compute(f0);
-            __builtin_amdgcn_sched_barrier(0);
-            if (kk + 2 < KC32) load(f0, kk + 2);
-            __builtin_amdgcn_sched_barrier(0);
-            compute(f1);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-        if (kk < KC32) compute(f0);
-    }
-
-    const int j = lane & 15, g4 = 4 * (lane >> 4);
-    auto silu4 = [](const f32x4 a) {
-        using f32x2 = __attribute__((ext_vector_type(2))) float;
-        const f32x2 k = {-1.44269504088896340736f, -1.44269504088896340736f}, one = {1.0f, 1.0f};
-        const f32x2 lo = {a[0], a[1]}, hi = {a[2], a[3]};
-        f32x2 tl = lo * k, th = hi * k;
-        tl[0] = __builtin_amdgcn_exp2f(tl[0]); tl[1] = __builtin_amdgcn_exp2f(tl[1]);
-        th[0] = __builtin_amdgcn_exp2f(th[0]); th[1] = __builtin_amdgcn_exp2f(th[1]);
-        tl = tl + one; th = th + one;
-        tl[0] = __builtin_amdgcn_rcpf(tl[0]); tl[1] = __builtin_amdgcn_rcpf(tl[1]);
-        th[0] = __builtin_amdgcn_rcpf(th[0]); th[1] = __builtin_amdgcn_rcpf(th[1]);
-        const f32x2 yl = lo * tl, yh = hi * th;
-        return f32x4{yl[0], yl[1], yh[0], yh[1]};
-    };
-    static_assert(ACT == HIPETS_ACT_SILU, "bf16x3 / bf16 instances exist for SiLU models");
-    auto store = [&](const f32x4 v, const int row, const int col0) __attribute__((always_inline)) {
-        if (last_op) {
-            *reinterpret_cast<f32x4*>(out + (size_t)row * ldb + col0 * 4) = v;  // fp32, natural columns (float stride ldb / 4)
-        } else {
-            u32x2 pc[NP];
-            split_x4<NP>(silu4(v), pc);
-#pragma unroll
-            for (int p = 0; p < NP; ++p) *reinterpret_cast<u32x2*>(out + (size_t)row * ldb + b3_offset<NP>(col0, p)) = pc[p];
-        }
-    };
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int r = 0; r < R; ++r) store(acc[ct][r], r * 16 + j, (c_first + kWaves * ct) * 16 + g4);
-#pragma unroll
-    for (int e = 0; e < EX; ++e) store(accx[e], exr[e] * 16 + j, exc[e] * 16 + g4);
-}
-
-// linear op with CS column tiles in bf16x3 (NP = 3) or bf16 (NP = 1) arithmetic (static shapes only: the lean instances)
-template <int R, int ACT, int CS, int NP>
-__device__ __forceinline__ void linear_op_b3(const uint4* W3, const float* bias, const int KC32, const int ldb, const bool last_op, const char* in,
-                                             char* out, const int wave, const int lane) {
-    constexpr int kMaxCT = 3;
-    constexpr int full = CS / kWaves, rem = CS % kWaves, nu = rem * R;
-    static_assert(full <= kMaxCT, "bf16x3 / bf16 instances cover ops of at most 15 column tiles");
-    Extras ex;
-    ex.c0 = kWaves * full + wave / R;                ex.r0 = wave % R;
-    ex.c1 = kWaves * full + (wave + kWaves) / R;     ex.r1 = (wave + kWaves) % R;
-    ex.c2 = kWaves * full + (wave + 2 * kWaves) / R; ex.r2 = (wave + 2 * kWaves) % R;
-    ex.c3 = kWaves * full + (wave + 3 * kWaves) / R; ex.r3 = (wave + 3 * kWaves) % R;
-    constexpr int lo = nu / kWaves, hi = (nu + kWaves - 1) / kWaves;
-    if constexpr (lo == hi) {
-        if constexpr (full > 0 || lo > 0) wave_gemm_b3<R, full, lo, ACT, NP>(in, out, ldb, W3, bias, KC32, wave, ex, last_op, lane);
-    } else {
-        if (wave < nu % kWaves) {
-            wave_gemm_b3<R, full, hi, ACT, NP>(in, out, ldb, W3, bias, KC32, wave, ex, last_op, lane);
-        } else {
-            if constexpr (full > 0 || lo > 0) wave_gemm_b3<R, full, lo, ACT, NP>(in, out, ldb, W3, bias, KC32, wave, ex, last_op, lane);
-        }
-    }
-}
-
-// Compile-time facts of a rollout-kernel instance; -1 = decided at run time.  Instances with HIDC >= 0 are the
-// SHAPE-SPECIALISED ("lean") kernels of the BASELINE configurations: hidden / output column-tile counts, normaliser kind,
-// obs preprocessing, reward and termination functions and the launch mode are template arguments, and everything those
-// shapes never use (expectation propagation, injected eps, traces, the phase profiler, batched / per-row initial states,
-// per-member logvar bounds) is compiled out.  The host picks an instance only when the model and the call match ALL of its
-// facts (launch.hpp pick_rollout_instance); anything else runs a generic one.  Same arithmetic, instruction for instruction, in
-// the parts both execute: tests compare the two bit for bit.
-// LDS row stride the host derives for a model whose widest layer has `tiles` column tiles (hipets_set_model: >= the widest
-// activation, == 8 mod 64); a shape-specialised instance runs only when the model's stride is this one (launch.hpp lean_shape_is)
-// Output layers of up to this many column tiles sum every unit's even / odd k-steps separately (wave_gemm SPL) and, in the
-// shape-specialised fp32 instances, feed the fused tail (KSpec::FUSE).  Wider ones (cfg4': 47) keep the plain order: a wave's share
-// is a dozen units there, and twice the accumulators (or a dozen inlined tails) do not fit the register file.
-constexpr int kSplMaxTiles = 8;
-
-constexpr int lean_ld(int hidc, int outc) {
-    int m = (hidc > outc ? hidc : outc) * 16;
-    while (m % 64 != 8) m += 4;
-    return m;
-}
-
-template <int ACT_, int HIDC_ = -1, int OUTC_ = -1, int NORM_ = -1, int OBSP_ = -1, int REW_ = -1, int TERM_ = -1, int KMODE_ = -1, int PREC_ = 0,
-          int FUSE_ = 0>
-struct KSpec {
-    // WIDE (fused fp32 instances whose output layer is wider than kSplMaxTiles column tiles -- cfg4': 47): no LDS image of the outputs
-    // exists at all, so the two activation buffers hold hidden activations only (row stride for HIDC tiles) and the model-input
-    // image -- wider than a hidden layer there: 393 columns -- lives in buf0 with its own run-time stride (ModelDev::ld_in).
-    // 4.4 KB of LDS per row instead of 7.6: two row tiles per workgroup fit where one did.
-    static constexpr bool WIDE = FUSE_ != 0 && HIDC_ >= 0 && PREC_ == HIPETS_PREC_F32 && OUTC_ > kSplMaxTiles;
-    static constexpr int LD = (HIDC_ >= 0 && PREC_ == HIPETS_PREC_F32) ? lean_ld(HIDC_, WIDE ? HIDC_ : OUTC_) : -1;  // compile-time LDS row stride (fp32 lean instances)
-    static constexpr int ACT = ACT_, HIDC = HIDC_, OUTC = OUTC_, NORM = NORM_, OBSP = OBSP_, REW = REW_, TERM = TERM_, KMODE = KMODE_;
-    static constexpr int PREC = PREC_;  // HIPETS_PREC_F32 (fp32 MFMA), or HIPETS_PREC_BF16X3 / HIPETS_PREC_BF16 (lean instances only)
-    static constexpr int PIECES = PREC_ == HIPETS_PREC_BF16X3 ? 3 : (PREC_ == HIPETS_PREC_BF16 ? 1 : 0);  // bf16 pieces per operand on the bf16 matrix pipe
-    static constexpr bool LEAN = HIDC_ >= 0 && OUTC_ >= 0;
-    // HIDDEN-STATIC instances (HIDC_ >= 0, everything else decided at run time): what ANY model with that hidden width gets --
-    // the reference's default is 200 = 13 column tiles (conf/dynamics_model/gaussian_mlp_ensemble.yaml:8), whatever its
-    // environment's obs preprocessing, reward / termination functions, normaliser, output width or propagation method.  The ops
-    // that carry > 90 % of a step's FLOPs (every op whose N is the hidden width) run exactly like in the shape-specialised
-    // instances: per-wave (CT, EX) through one branch, compile-time LDS stride, interleaved fragment loads, unrolled k loops where
-    // the register file allows; the output layer and every elementwise phase stay the generic kernel's.
-    static constexpr bool HID_STATIC = HIDC_ >= 0 && OUTC_ < 0;
-    // FUSE (lean fp32 instances): the output layer runs on the "head pair" pack and its accumulators go straight into the
-    // step's tail -- sampling, delta, next state, hand-over publication, reward / termination / totals and the next step's
-    // normalised model input happen in registers in the output layer's own barrier interval (5 barriers per step instead
-    // of 7, no LDS round trip of the 2 x out_dim outputs).  Needs reward / termination forms that read state dims 0..3 only.
-    // (output layers of up to 8 column tiles: beyond that -- cfg4' has 47 -- a wave's tail covers a dozen units and the instance spills)
-    static constexpr bool FUSE = FUSE_ != 0 && LEAN && PREC_ == HIPETS_PREC_F32 && (OUTC_ <= kSplMaxTiles || WIDE);
-    static constexpr bool SPL_OUT = OUTC_ >= 0 && OUTC_ <= kSplMaxTiles;  // the output layer sums even / odd k-steps separately (wave_gemm SPL)
-    // K-split of the leftover hidden column tile (KsArgs above): the fused fp32 instances whose hidden layers leave ONE column tile over
-    // (13 = 3 x 4 + 1), used by the kernel for ONE-TILE workgroups only (R = 1: rollout_kernel's kKS)
-    // (13 column tiles only: the consumer side, wave_gemm KSI inside KSO, rebuilds the last k chunk from slot kKsSlots - 1 of the last wave,
-    // which is where a 13-chunk range -- 3 + 3 + 3 + 4 chunks -- ends; a 5- or 9-tile shape would end in another slot and read unwritten LDS)
-    static constexpr bool KSPLIT = FUSE && !WIDE && kWaves == 4 && HIDC_ == 13;
-    // termination functions that test EVERY state dim (inverted_pendulum: isfinite(next_obs).all(), termination_fns.py:47-55) are fused for
-    // models with obs_dim <= 4 only -- then dims 0..3 ARE every dim (launch.hpp fused_term_ok checks the model)
-    static_assert(!FUSE || ((REW_ == HIPETS_REW_HALFCHEETAH || REW_ == HIPETS_REW_CARTPOLE || REW_ == HIPETS_REW_CARTPOLE_PETS || REW_ == HIPETS_REW_LEARNED) &&
-                            (TERM_ == HIPETS_TERM_NONE || TERM_ == HIPETS_TERM_CARTPOLE || TERM_ == HIPETS_TERM_HUMANOID || TERM_ == HIPETS_TERM_INVERTED_PENDULUM ||
-                             TERM_ == HIPETS_TERM_HOPPER)),
-                  "fused tail: the reward / termination lane sees dims 0..3 of its row");
-    // hopper (termination_fns.py:12-26) tests EVERY state dim of a model whose dims span several column tiles, i.e. several waves: every
-    // tail lane judges its own two dims and raises a per-row flag in LDS; the flag of step t is complete at the barrier that ends the
-    // step and is folded into the row's `terminated` by the tail of step t + 1 -- which is when it first matters (model_env.py:186-188:
-    // the reward of the terminating step itself still counts).  The row must still be HERE then: FAST instances only (in the persistent
-    // DEVICE form it has moved to another workgroup, which would need the flag through the hand-over table); learned rewards only.
-    // Round 5: DEVICE-mode instances too.  One launch per step: the flag of the launch's step is folded into `terminated` behind the
-    // step loop, before the write-back.  Persistent form: the row has moved on -- and its NEXT owner holds every dim of the state it
-    // receives: the threads that collect a pair of dims judge them exactly like the tail lanes would have and raise the flag in the
-    // new owner's LDS (hop_flags below); nothing more travels through the hand-over table.
-    static_assert(!FUSE || TERM_ != HIPETS_TERM_HOPPER || (REW_ == HIPETS_REW_LEARNED && !WIDE),
-                  "fused tail with an all-dims termination function: instances with a learned reward");
-    // learned rewards (round 4): the reward is the sampled LAST output column.  Without a termination function (pets_pusher / pets_reacher /
-    // pets_mppi_halfcheetah) the lane that holds that column keeps the row's running total and needs no state dim at all; with one
-    // (pets_inv_pendulum) the lane with dims 0, 1 keeps it and fetches the reward from the column's lane of the SAME accumulator, i.e. the
-    // column must sit in column tile 0: obs_dim < 8 (fused_term_ok)
-    static_assert(!FUSE || REW_ != HIPETS_REW_LEARNED || !WIDE, "fused tail with learned rewards: no WIDE instance");
-    // obs preprocessing in the fused tail (round 4): the lane that holds the trig dim writes its sin and cos columns (ObsMap)
-    static_assert(!FUSE || (NORM_ == HIPETS_NORM_F64 && (OBSP_ == HIPETS_OBS_NONE || !WIDE)), "fused tail: f64 normaliser; WIDE instances: no obs preprocessing");
-    static_assert(!FUSE || OBSP_ == HIPETS_OBS_NONE || OBSP_ == HIPETS_OBS_HALFCHEETAH || OBSP_ == HIPETS_OBS_CARTPOLE_PETS, "unknown obs preprocessing");
-};
-
-// Layer l in bf16x3 / bf16 arithmetic
-template <int R, class S>
-__device__ __forceinline__ void mlp_layer_b3(const ModelDev& md, const LayerMeta* lmeta, const int l, const int member, const float* in, float* out,
-                                             const int wave, const int lane) {
-    const LayerMeta lm = lmeta[l];
-    const uint4* W3 = md.w3 + (size_t)member * md.w3member + lm.woff3;
-    const float* bias = md.b + (size_t)member * md.bmember + lm.boff;
-    const char* inb = reinterpret_cast<const char*>(in);
-    char* outb = reinterpret_cast<char*>(out);
-    if (l < md.n_layers - 1) linear_op_b3<R, S::ACT, S::HIDC, S::PIECES>(W3, bias, lm.Kp32 / 32, md.ld * 4, false, inb, outb, wave, lane);
-    else linear_op_b3<R, S::ACT, S::OUTC, S::PIECES>(W3, bias, lm.Kp32 / 32, md.ld * 4, true, inb, outb, wave, lane);
-}
-
-// Layer l of the ensemble MLP with member `member`'s weights.
-// part: the two k-split partial-sum buffers of a KSpec::KSPLIT one-tile workgroup ([2][kWaves][64][4] floats, alternating by layer)
-template <int R, class S>
-__device__ __forceinline__ void mlp_layer(const ModelDev& md, const LayerMeta* lmeta, const int l, const int member,
-                                          const float* in, float* out, const int wave, const int lane, Prof& prof, float* part = nullptr) {
-    const LayerMeta lm = lmeta[l];  // staged in LDS once per launch (a global scalar load here cost ~400 cycles per layer)
-    const float* W = md.w + (size_t)member * md.wmember + lm.woff;
-    const float* bias = md.b + (size_t)member * md.bmember + lm.boff;
-    if constexpr (S::KSPLIT && R == 1) {
-        // hidden ops of a one-tile workgroup: every wave 3 column tiles + its quarter of the 13th tile's k range (wave_gemm KSO); ops fed
-        // by a hidden layer rebuild their last k chunk from the previous op's partial sums (KSI)
-        float* const po = part + (l & 1) * (kWaves * 64 * 4);
-        const float* const pi = part + ((l & 1) ^ 1) * (kWaves * 64 * 4);
-        if (l == 0) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD, false, -1, 2>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, 0, nullptr, po);
-        else linear_op<R, S::ACT, S::HIDC, NoTail, S::LD, false, S::HIDC, 3>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, 0, pi, po);
-    } else if constexpr (S::LEAN) {
-        // ops fed by a hidden layer have K = hid: HIDC chunks, a compile-time count (the input layer's K is the model's input width)
-        // Unrolled only where the register file is not the constraint (R >= 3: one workgroup per CU, 512 registers per lane).  At R = 2
-        // (two workgroups per CU, 256-register cap) the allocator splits accumulator live ranges inside the unrolled stream and
-        // puts v_mov copies straight behind asm MFMAs -- which it believes complete at once (wave_gemm, "drain_all") -- and the
-        // interleaved + unrolled build returned wrong sums (caught by the cfg5 parity tests); R = 1 measured 1 % slower unrolled.
-        constexpr int kHidChunks = MinWavesOf<R>::value == 1 ? S::HIDC : -1;
-        if (l == 0) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, S::WIDE ? md.ld_in : 0);
-        else if (l < md.n_layers - 1) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD, false, kHidChunks>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof);
-        else linear_op<R, S::ACT, S::OUTC, NoTail, S::LD, (S::OUTC <= kSplMaxTiles), kHidChunks>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
-    } else if constexpr (S::HID_STATIC) {
-        // (unrolled up to 13 MFMA units per wave -- the widest the shape-specialised instances run: at 16 units, hid 256 with R = 4,
-        // the allocator splits accumulator live ranges inside the unrolled stream again and the build's ISA scan finds a v_mov of an
-        // accumulator behind an MFMA still in flight; the rolled loop ends every block with drain_all)
-        constexpr int kHidChunks = (MinWavesOf<R>::value == 1 && ((S::HIDC + kWaves - 1) / kWaves) * R <= 13) ? S::HIDC : -1;
-        if (l == 0) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof);
-        else if (l < md.n_layers - 1) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD, false, kHidChunks>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof);
-        else if (lm.Np / kTile <= kSplMaxTiles)  // the output layer: the generic instance's dispatch, the SAME summation rule (SPL)
-            linear_op<R, S::ACT, -1, NoTail, -1, true>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
-        else linear_op<R, S::ACT>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
-    } else {
-        // the output layer of up to kSplMaxTiles column tiles: SPL (the SAME rule in the shape-specialised branch above)
-        if (l == md.n_layers - 1 && lm.Np / kTile <= kSplMaxTiles)
-            linear_op<R, S::ACT, -1, NoTail, -1, true>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
-        else linear_op<R, S::ACT>(W, bias, lm, md.ld, l < md.n_layers - 1, md.activation, md.slope, in, out, wave, lane, prof);
-    }
-}
-
-// The OUTPUT layer of a KSpec::FUSE instance: the "head pair" pack, accumulators handed to `tl` (no LDS image of the outputs)
-template <int R, class S, class TL>
-__device__ __forceinline__ void mlp_output_layer_fused(const ModelDev& md, const LayerMeta* lmeta, const int member, const float* in,
-                                                       const int wave, const int lane, Prof& prof, const TL& tl, const float* part = nullptr) {
-    const LayerMeta lm = lmeta[md.n_layers - 1];
-    const float* W = md.w + (size_t)member * md.wmember + lm.woff_pairs;
-    const float* bias = md.b + (size_t)member * md.bmember + lm.boff_pairs;
-    if constexpr (S::KSPLIT && R == 1) {  // the last hidden layer (index n_layers - 2) left its 13th tile as partial sums
-        const float* const pi = part + ((md.n_layers - 2) & 1) * (kWaves * 64 * 4);
-        linear_op<R, S::ACT, S::OUTC, TL, S::LD, S::SPL_OUT, S::HIDC, 1>(W, bias, lm, md.ld, false, md.activation, md.slope, in, nullptr, wave, lane, prof, &tl, 0, pi);
-    } else {
-        linear_op<R, S::ACT, S::OUTC, TL, S::LD, S::SPL_OUT, MinWavesOf<R>::value == 1 ? S::HIDC : -1>(W, bias, lm, md.ld, false, md.activation, md.slope, in, nullptr, wave, lane, prof, &tl);
-    }
-}
-
-// obs_process_fn seen from the PRODUCER of an observation dim (the fused tail, the straight form's collect phase: both hold a pair
-// of raw dims in registers and write the next step's input image themselves): which input column does dim d feed, and which dim
-// enters as sin / cos?  halfcheetah (env/pets_halfcheetah.py:91-113): [s1, sin s2, cos s2, s3:] -- dim 0 feeds nothing;
-// cartpole_pets (env/pets_cartpole.py:78-101): [sin s1, cos s1, s0, s2:] -- one column more than dims.
-template <int OBSP>
-struct ObsMap {
-    static constexpr int kTrigDim = OBSP == HIPETS_OBS_HALFCHEETAH ? 2 : (OBSP == HIPETS_OBS_CARTPOLE_PETS ? 1 : -1);  // enters as sin and cos
-    static constexpr int kSinCol = OBSP == HIPETS_OBS_HALFCHEETAH ? 1 : 0;
-    static constexpr int kCosCol = OBSP == HIPETS_OBS_HALFCHEETAH ? 2 : 1;
-    // column of dim d (the sin column for the trig dim), -1 = the dim is not a model input
-    __device__ static __forceinline__ int col(const int d) {
-        if constexpr (OBSP == HIPETS_OBS_HALFCHEETAH) return d == 0 ? -1 : (d == 1 ? 0 : (d == 2 ? 1 : d));
-        else if constexpr (OBSP == HIPETS_OBS_CARTPOLE_PETS) return d == 0 ? 2 : (d == 1 ? 0 : d + 1);
-        else return d;
-    }
-};
-
-// obs_process_fn(obs)[i] (mbrl/env/pets_halfcheetah.py:91-113, pets_cartpole.py:78-101)
-__device__ __forceinline__ float processed_obs(const float* s, int i, int mode) {
-    if (mode == HIPETS_OBS_HALFCHEETAH) {  // [s1, sin s2, cos s2, s3:]
-        if (i == 0) return s[1];
-        if (i == 1) return sinf(s[2]);
-        if (i == 2) return cosf(s[2]);
-        return s[i];
-    }
-    if (mode == HIPETS_OBS_CARTPOLE_PETS) {  // [sin s1, cos s1, s0, s2:]
-        if (i == 0) return sinf(s[1]);
-        if (i == 1) return cosf(s[1]);
-        if (i == 2) return s[0];
-        return s[i - 1];
-    }
-    return s[i];
-}
-
-__device__ __forceinline__ bool term_eval(const float* s, int obs_dim, int fn) {
-    switch (fn) {
-        case HIPETS_TERM_CARTPOLE: {  // termination_fns.py:29-44
-            const float x = s[0], th = s[2], thr = (float)(12.0 * 2.0 * 3.14159265358979323846 / 360.0);
-            return !((x > -2.4f) && (x < 2.4f) && (th > -thr) && (th < thr));
-        }
-        case HIPETS_TERM_INVERTED_PENDULUM: {  // :47-55
-            bool fin = true;
-            for (int d = 0; d < obs_dim; ++d) fin = fin && isfinite(s[d]);
-            return !(fin && (fabsf(s[1]) <= 0.2f));
-        }
-        case HIPETS_TERM_HOPPER: {  // :12-26
-            bool ok = true;
-            for (int d = 0; d < obs_dim; ++d) ok = ok && isfinite(s[d]);
-            for (int d = 1; d < obs_dim; ++d) ok = ok && (fabsf(s[d]) < 100.0f);
-            return !(ok && (s[0] > 0.7f) && (fabsf(s[1]) < 0.2f));
-        }
-        case HIPETS_TERM_WALKER2D:  // :66-74
-            return !((s[0] > 0.8f) && (s[0] < 2.0f) && (s[1] > -1.0f) && (s[1] < 1.0f));
-        case HIPETS_TERM_ANT: {  // :77-85
-            bool fin = true;
-            for (int d = 0; d < obs_dim; ++d) fin = fin && isfinite(s[d]);
-            return !(fin && (s[0] >= 0.2f) && (s[0] <= 1.0f));
-        }
-        case HIPETS_TERM_HUMANOID:  // :88-95
-            return (s[0] < 1.0f) || (s[0] > 2.0f);
-        default: return false;  // no_termination :58-63
-    }
-}
-
-__device__ __forceinline__ float reward_eval(const float* s, const float* a, int obs_dim, int act_dim, int fn,
-                                             float learned) {
-    switch (fn) {
-        case HIPETS_REW_CARTPOLE: return term_eval(s, obs_dim, HIPETS_TERM_CARTPOLE) ? 0.0f : 1.0f;  // reward_fns.py:10-13
-        case HIPETS_REW_INVERTED_PENDULUM: return term_eval(s, obs_dim, HIPETS_TERM_INVERTED_PENDULUM) ? 0.0f : 1.0f;
-        case HIPETS_REW_CARTPOLE_PETS: {  // :16-24
-            const float e0 = (s[0] - 0.6f * sinf(s[1])) - 0.0f, e1 = (-0.6f * cosf(s[1])) - 0.6f;
-            const float obs_cost = expf(-(e0 * e0 + e1 * e1) / (float)(0.6 * 0.6));
-            float sq = 0.f;
-            for (int i = 0; i < act_dim; ++i) sq += a[i] * a[i];
-            return obs_cost + (-0.01f * sq);
-        }
-        case HIPETS_REW_HALFCHEETAH: {  // :33-38
-            float sq = 0.f;
-            for (int i = 0; i < act_dim; ++i) sq += a[i] * a[i];
-            const float run = s[0] - 0.0f * (s[2] * s[2]);
-            return run + (-0.1f * sq);
-        }
-        case HIPETS_REW_PUSHER: {  // :41-53
-            const float g0 = 0.45f, g1 = -0.05f, g2 = -0.323f;
-            const float tip_obj = fabsf(s[14] - s[17]) + fabsf(s[15] - s[18]) + fabsf(s[16] - s[19]);
-            const float obj_goal = fabsf(g0 - s[17]) + fabsf(g1 - s[18]) + fabsf(g2 - s[19]);
-            const float obs_cost = 0.5f * tip_obj + 1.25f * obj_goal;
-            float sq = 0.f;
-            for (int i = 0; i < act_dim; ++i) sq += a[i] * a[i];
-            return -(obs_cost + 0.1f * sq);
-        }
-        case HIPETS_REW_NONE: return 0.0f;  // the caller evaluates its own reward_fn on the returned next_obs
-        default: return learned;  // model_env.py:124-128 with reward_fn None
-    }
-}
-
-// the 4 standard normals of (row, step, dim block): counter = (row, step, block, stream), key = seed
-__device__ __forceinline__ void rollout_normals4(int rid, int t, int blk, unsigned long long seed,
-                                                 unsigned long long stream_id, float (&nrm)[4]) {
-    const Philox4 r4 = philox4x32_10((uint32_t)rid, (uint32_t)t, (uint32_t)blk, (uint32_t)stream_id, (uint32_t)seed,
-                                     (uint32_t)(seed >> 32) ^ (uint32_t)(stream_id >> 32));
-    box_muller(r4.x, r4.y, nrm[0], nrm[1]);
-    box_muller(r4.z, r4.w, nrm[2], nrm[3]);
-}
-
-// termination_fns.hopper (:12-26) seen from ONE pair of state dims (d, d + 1): all finite, |dims 1..| < 100, height (dim 0) > 0.7,
-// |angle (dim 1)| < 0.2.  The row is unhealthy iff any of its pairs says so (fused tail lanes / the collecting threads of the
-// persistent DEVICE form, KSpec above).
-__device__ __forceinline__ bool hopper_pair_bad(const int d, const float vA, const float vB, const bool hasA, const bool hasB) {
-    bool bad = false;
-    if (hasA) bad = !isfinite(vA) || (d >= 1 ? !(fabsf(vA) < 100.0f) : !(vA > 0.7f));
-    if (hasB) bad = bad || !isfinite(vB) || !(fabsf(vB) < 100.0f) || (d == 0 && !(fabsf(vB) < 0.2f));
-    return bad;
-}
-
-struct RolloutSmem {
-    float* buf0;
-    float* buf1;
-    float* state;    // [ROWS][obs_dim]
-    float* actn;     // [2][ROWS][act_dim]  (double buffered: reward(t) reads while input(t+1) is built)
-    float* tot;      // [ROWS]
-    float* lrew;     // [ROWS] learned reward of the current step
-    int* term;       // [ROWS]
-    int* rowid;      // [ROWS] global row id (candidate*P + particle) or -1
-    int* pend;       // [2][ROWS] persistent DEVICE form: running total / flag granule of the row not yet collected
-    double* nmean;   // [in_dim] normaliser stats (f64 like the reference)
-    double* nstd;    // [in_dim] (f64 normaliser: holds 1 / std)
-    float* minlv;    // [lv_rows][out_dim]
-    float* maxlv;    // [lv_rows][out_dim]
-    int* nodelta;    // [obs_dim]
-    int* sched;      // [H] member slot of this workgroup per step (FAST)
-    LayerMeta* lmeta;  // [HIPETS_MAX_LAYERS]
-    long long* prof;   // [kWaves][16] phase-cycle accumulators (profiling aid)
-    float* dump;     // [4] sink of the fused tail's masked-off LDS stores (branch-free: an inactive lane stores here)
-    float* part;     // one-tile workgroups: [2][kWaves][64][4] k-split partial sums (KsArgs)
-    float* expacc;   // [ROWS][out_total] (expectation propagation only)
-    char* stage_x;   // KSpec::WIDE: the chunks of the hand-over staging area that do not fit buf0 + buf1 (dma_stage_extra_bytes; last section)
-};
-
-__host__ __device__ inline size_t align16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// ld0 > 0: buf0 has its own row stride (KSpec::WIDE: the model-input image), buf1 uses `ld`
-// KSpec::WIDE instances collect a turn's rows by LDS-DMA (rollout_kernel, "dma_collect"): rows x pairs 16-byte hand-over pairs staged
-// in 1 KiB chunks of 64.  The two activation buffers are idle then and hold most of them; what does not fit gets a section of its own.
-__host__ __device__ inline size_t dma_stage_extra_bytes(int rows, int ld, int ld0, int obs_dim) {
-    const size_t nvp = (size_t)(obs_dim + 1) / 2 + 1;          // pairs per row
-    const size_t need = (size_t)rows * ((nvp + 63) / 64) * 1024;  // every row's pairs in whole chunks of 64 (dma_collect)
-    const size_t have = ((size_t)rows * ld0 * 4 + 15) / 16 * 16 + ((size_t)rows * ld * 4 + 15) / 16 * 16;
-    return need > have ? need - have : 0;
-}
-
-__host__ __device__ inline size_t rollout_smem_bytes(int rows, int ld, int obs_dim, int act_dim, int in_dim, int out_dim,
-                                                     int out_total, int horizon, bool expectation, int lv_rows = 1, int ld0 = 0) {
-    size_t n = 0;
-    if (ld0 > 0) n += dma_stage_extra_bytes(rows, ld, ld0, obs_dim);  // (ld0 > 0: the KSpec::WIDE layout)
-    n += align16((size_t)rows * (ld0 > 0 ? ld0 : ld) * 4) + align16((size_t)rows * ld * 4);
-    n += align16((size_t)rows * obs_dim * 4);
-    n += align16((size_t)2 * rows * act_dim * 4);
-    n += 4 * align16((size_t)rows * 4) + align16((size_t)2 * rows * 4);
-    n += 2 * align16((size_t)in_dim * 8);
-    n += 2 * align16((size_t)lv_rows * out_dim * 4);
-    n += align16((size_t)obs_dim * 4);
-    n += align16((size_t)horizon * 4);
-    n += align16(sizeof(LayerMeta) * HIPETS_MAX_LAYERS);
-    n += align16((size_t)kWaves * 16 * 8);
-    n += 16;  // dump slot
-    if (rows == kTile) n += (size_t)2 * kWaves * 64 * 16;  // one-tile workgroups: the k-split partial sums (RolloutSmem::part)
-    if (expectation) n += align16((size_t)rows * out_total * 4);
-    return n;
-}
-
-// Raw hardware transcendentals (v_exp_f32 / v_log_f32 are base 2, ~1 ulp, no denormal fix-up sequences).
-__device__ __forceinline__ float exp_hw(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
-__device__ __forceinline__ float log_hw(float x) { return __builtin_amdgcn_logf(x) * 0.69314718055994530942f; }
-// log(1 + e^x) (abs error ~1e-7; F.softplus' threshold-20 branch kept as a select)
-__device__ __forceinline__ float softplus_fast(float x) {
-    const float y = log_hw(1.0f + exp_hw(fminf(x, 20.0f)));
-    return x > 20.0f ? x : y;
-}
 
 template <int R, class S> struct MinWaves { static constexpr int value = S::WIDE ? 1 : MinWavesOf<R>::value; };  // (WIDE: the LDS admits one workgroup per CU anyway)
 
@@ -1581,44 +103,27 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     extern __shared__ __attribute__((aligned(16))) char smem[];
     RolloutSmem sm;
     {
-        // sections whose size follows from ROWS and the row stride first: in a shape-specialised instance (compile-time stride) their
-        // addresses are constants -- immediate offsets in the LDS instructions instead of a live SGPR each (the DEVICE instance
-        // of cfg2 spills > 200 scalars); the sections sized by the model's run-time dimensions follow
+        // the layout of rollout_smem.hpp, carved.  Its last two sections (rollout_smem.hpp: no kernel has both, nothing follows them)
+        // start at the same address and are not sized here: the host's total covers them (rollout_smem_bytes, checked below in debug
+        // builds), and their sizes computed here ahead of their real uses moved every rollout kernel's register allocation.
         char* p = smem;
-        sm.buf0 = reinterpret_cast<float*>(p); p += align16((size_t)ROWS * (kWide ? md.ld_in : ld_k) * 4);
-        sm.buf1 = reinterpret_cast<float*>(p); p += align16((size_t)ROWS * ld_k * 4);
-        sm.tot = reinterpret_cast<float*>(p); p += align16((size_t)ROWS * 4);
-        sm.lrew = reinterpret_cast<float*>(p); p += align16((size_t)ROWS * 4);
-        sm.term = reinterpret_cast<int*>(p); p += align16((size_t)ROWS * 4);
-        sm.rowid = reinterpret_cast<int*>(p); p += align16((size_t)ROWS * 4);
-        sm.pend = reinterpret_cast<int*>(p); p += align16((size_t)2 * ROWS * 4);
-        sm.lmeta = reinterpret_cast<LayerMeta*>(p); p += align16(sizeof(LayerMeta) * HIPETS_MAX_LAYERS);
-        sm.prof = reinterpret_cast<long long*>(p); p += align16((size_t)kWaves * 16 * 8);
-        sm.dump = reinterpret_cast<float*>(p); p += 16;
-        sm.part = reinterpret_cast<float*>(p); p += (ROWS == kTile) ? (size_t)2 * kWaves * 64 * 16 : 0;
-        sm.state = reinterpret_cast<float*>(p); p += align16((size_t)ROWS * md.obs_dim * 4);
-        sm.actn = reinterpret_cast<float*>(p); p += align16((size_t)2 * ROWS * md.act_dim * 4);
-        sm.nmean = reinterpret_cast<double*>(p); p += align16((size_t)md.in_dim * 8);
-        sm.nstd = reinterpret_cast<double*>(p); p += align16((size_t)md.in_dim * 8);
-        sm.minlv = reinterpret_cast<float*>(p); p += align16((size_t)md.lv_rows * md.out_dim * 4);
-        sm.maxlv = reinterpret_cast<float*>(p); p += align16((size_t)md.lv_rows * md.out_dim * 4);
-        sm.nodelta = reinterpret_cast<int*>(p); p += align16((size_t)md.obs_dim * 4);
-        sm.sched = reinterpret_cast<int*>(p); p += align16((size_t)ra.H * 4);
-        sm.expacc = reinterpret_cast<float*>(p);
-        sm.stage_x = p;  // (KSpec::WIDE instances have no expectation accumulator: the extra staging chunks are the last section)
+#define HIPETS_CARVE(T, name, bytes)   \
+    sm.name = reinterpret_cast<T*>(p); \
+    p += (bytes);
+        HIPETS_ROLLOUT_SECTIONS(HIPETS_CARVE, ROWS, ld_in, ld_k, md.obs_dim, md.act_dim, md.in_dim, md.lv_rows, md.out_dim, md.out_total, ra.H, false, false)
+#undef HIPETS_CARVE
 #if HIPETS_DEBUG_BOUNDS
-        {   // every section starts inside the launch's dynamic LDS, 16-byte aligned, in layout order; the last one ends inside it
-            const char* const secs[] = {(char*)sm.buf0, (char*)sm.buf1, (char*)sm.tot, (char*)sm.lrew, (char*)sm.term, (char*)sm.rowid, (char*)sm.pend,
-                                        (char*)sm.lmeta, (char*)sm.prof, (char*)sm.dump, (char*)sm.part, (char*)sm.state, (char*)sm.actn, (char*)sm.nmean, (char*)sm.nstd,
-                                        (char*)sm.minlv, (char*)sm.maxlv, (char*)sm.nodelta, (char*)sm.sched, (char*)sm.expacc};
-            constexpr int kSecs = (int)(sizeof(secs) / sizeof(secs[0]));
-            for (int i = 0; i < kSecs; ++i) {
+        {   // every section starts inside the launch's dynamic LDS, 16-byte aligned, in layout order; the whole layout fits the launch's size
+#define HIPETS_SECTION_START(T, name, bytes) (char*)sm.name,
+            const char* const secs[] = {HIPETS_ROLLOUT_SECTION_NAMES(HIPETS_SECTION_START)};
+#undef HIPETS_SECTION_START
+            for (int i = 0; i < kRolloutSections; ++i) {
                 HIPETS_BOUND(secs[i] >= smem && secs[i] <= smem + ra.lds_bytes);
                 HIPETS_BOUND(((size_t)(secs[i] - smem) & 15) == 0);
                 HIPETS_BOUND(i == 0 || secs[i] >= secs[i - 1]);
             }
             const bool expect = !S::LEAN && md.propagation == HIPETS_PROP_EXPECTATION;
-            HIPETS_BOUND((char*)sm.expacc + (expect ? align16((size_t)ROWS * md.out_total * 4) : 0) <= smem + ra.lds_bytes);
+            HIPETS_BOUND(rollout_smem_bytes(ROWS, ld_k, md.obs_dim, md.act_dim, md.in_dim, md.out_dim, md.out_total, ra.H, expect, md.lv_rows, kWide ? ld_in : 0) <= ra.lds_bytes);
             HIPETS_BOUND(md.Kp0 <= (kWide ? md.ld_in : ld_k) && md.obs_in + md.act_dim == md.in_dim && md.in_dim <= md.Kp0);
         }
 #endif
@@ -1782,6 +287,19 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
         tot = __uint_as_float(g[0]);
         trm = (int)g[2];
     };
+    // The masked accumulation that ends a step for row `rid` in slot s (model_env.py:186-188): a terminated row earns nothing more; the
+    // running total and flag stay in LDS and are published to the row's next owner (`handover`, tag `tag`) or, on the last step of the
+    // persistent form, the total is the row's return
+    auto end_step_for_row = [&](const int s, const int rid, float tot, int trm, float r, const bool done, unsigned long long* const handover,
+                                const unsigned tag) __attribute__((always_inline)) {
+        if (trm) r = 0.f;
+        trm = trm | (done ? 1 : 0);
+        tot += r;
+        sm.term[s] = trm;
+        sm.tot[s] = tot;
+        if (handover) pair_store(handover + (size_t)rid * NV + (NV - 2), __float_as_uint(tot), (unsigned)trm, tag);
+        else if (persist) ra.totals[rid] = tot;  // last step: the row's return
+    };
     // rows wider than a few pairs (cfg4: 24 pairs per row, cfg4': 189) are collected in rounds of kGT pairs per thread, each round one
     // round trip to the table (>= 1 us even when the rows are long there: the later turns of a step): 4 / 8 in flight instead of 2
     // cut cfg4''s 12 rounds per turn to 3.  (Only the collect phase holds these registers; the straight form's cfg2 needs one round.)
@@ -1808,7 +326,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
         // bf16x3: the k chunks are 32 wide, the column tiles 16: the last chunk of a 13-tile layer ends in 16 columns no epilogue
         // ever writes.  Their weights are zero, but 0 x (whatever bits LDS holds) may be NaN: clear both activation buffers once.
         f32x4* z = reinterpret_cast<f32x4*>(sm.buf0);
-        const int n16 = (int)(2 * align16((size_t)ROWS * ld_k * 4) / 16);
+        const int n16 = (int)(2 * act_buf_bytes(ROWS, ld_k) / 16);
         for (int i = tid; i < n16; i += kThreads) z[i] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     // ---- per-dimension constants -> LDS, and the rows' initial state / totals / flags / first actions: EVERY global load of the
@@ -1899,9 +417,6 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     const int nblk = (md.out_dim + 3) / 4;
     const int Kp0 = md.Kp0;
     Prof prof;
-#ifndef HIPETS_LEAN_PROF
-#define HIPETS_LEAN_PROF 0  // profiling builds: the phase profiler also in the shape-specialised instances (profiles/kernel_variants.py)
-#endif
     prof.on = (!kLean || HIPETS_LEAN_PROF) && ra.phase_cycles != nullptr && wg == 0 && lane == 0;
     prof.slot = sm.prof + wave * 16;
     if (prof.on) {
@@ -2294,9 +809,9 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
         constexpr int CPR = kWide ? (((S::OUTC > 0 ? S::OUTC : 1) * 8 + 1) / 2 + 1 + 63) / 64 : 1;
         constexpr int kRowsPerWave = ROWS / kWaves;
         static_assert(ROWS % kWaves == 0 && kRowsPerWave * CPR <= 32, "row slots are dealt to the waves; one pending bit per (row, chunk)");
-        const int n_main = (int)((align16((size_t)ROWS * ld_in * 4) + align16((size_t)ROWS * ld_k * 4)) >> 10);  // chunks that fit buf0 + buf1 (contiguous)
+        const int n_main = (int)(act_bytes(ROWS, ld_in, ld_k) >> 10);  // chunks that fit buf0 + buf1 (contiguous)
         char* const stage0 = reinterpret_cast<char*>(sm.buf0);
-        HIPETS_BOUND(CPR == (NVP + 63) / 64 && (size_t)max(ROWS * CPR - n_main, 0) * 1024 <= dma_stage_extra_bytes(ROWS, ld_k, ld_in, md.obs_dim));
+        HIPETS_BOUND(CPR == (NVP + 63) / 64 && (size_t)max(ROWS * CPR - n_main, 0) * 1024 <= stage_extra_bytes(ROWS, ld_in, ld_k, md.obs_dim));
         auto chunk_ptr = [&](const int c) __attribute__((always_inline)) { return c < n_main ? stage0 + ((size_t)c << 10) : sm.stage_x + ((size_t)(c - n_main) << 10); };
         auto lds_of = [&](const int c) __attribute__((always_inline)) { return (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(size_t)chunk_ptr(c)); };
         unsigned pending = 0;  // bit j CPR + k: chunk k of this wave's j-th row still has a lane waiting
@@ -2588,13 +1103,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                         } else {
                             done = term_eval(st, 4, S::TERM);
                         }
-                        if (trm) rwd = 0.f;
-                        trm = trm | (done ? 1 : 0);
-                        tot += rwd;
-                        sm.term[s] = trm;
-                        sm.tot[s] = tot;
-                        if (handover) pair_store(handover + (size_t)rid * NV + (NV - 2), __float_as_uint(tot), (unsigned)trm, handover_tg);
-                        else if (persist) ra.totals[rid] = tot;  // last step: the row's return
+                        end_step_for_row(s, rid, tot, trm, rwd, done, handover, handover_tg);
                     }
                 }
             };
@@ -2679,8 +1188,8 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                         if (!deterministic && c >= md.out_dim) {
                             const int d = c - md.out_dim;
                             const int bd = (lv_rows > 1 ? member * md.out_dim : 0) + d;
-                            v = sm.maxlv[bd] - softplus_fast(sm.maxlv[bd] - v);
-                            v = sm.minlv[bd] + softplus_fast(v - sm.minlv[bd]);
+                            const float mx = sm.maxlv[bd], mn = sm.minlv[bd];
+                            v = clamp_logvar(v, mn, mx);
                         }
                         sm.expacc[i] = mi == 0 ? v : sm.expacc[i] + v;
                     }
@@ -2726,8 +1235,8 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                             mean = result[s * ld_k + d];
                             if constexpr (MODE != 0) {
                                 lv = result[s * ld_k + md.out_dim + d];
-                                lv = lvmax[d] - softplus_fast(lvmax[d] - lv);  // gaussian_mlp.py:152
-                                lv = lvmin[d] + softplus_fast(lv - lvmin[d]);  // :153
+                                const float mx = lvmax[d], mn = lvmin[d];
+                                lv = clamp_logvar(lv, mn, mx);  // gaussian_mlp.py:152-153
                             }
                         }
                         if constexpr (MODE != 0) pred[q] = mean + __builtin_amdgcn_sqrtf(exp_hw(lv)) * nrm[q];  // model.py:471-473
@@ -2794,16 +1303,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                     float r = reward_eval(st, ac, md.obs_dim, md.act_dim, reward_fn, sm.lrew[s]);
                     const bool done = term_eval(st, md.obs_dim, term_fn);
                     if (trace_rewards) trace_rewards[(size_t)t * ra.B + rid] = r;
-                    if (trm) r = 0.f;
-                    trm = trm | (done ? 1 : 0);
-                    tot += r;
-                    sm.term[s] = trm;
-                    sm.tot[s] = tot;
-                    if (handover) {
-                        pair_store(handover + (size_t)rid * NV + (NV - 2), __float_as_uint(tot), (unsigned)trm, (unsigned)(handover_tag >> 32));
-                    } else if (persist) {
-                        ra.totals[rid] = tot;  // last step: the row's return
-                    }
+                    end_step_for_row(s, rid, tot, trm, r, done, handover, (unsigned)(handover_tag >> 32));
                 }
                 if (persist && has_next) {  // the slot's row in the next turn (only this thread reads rowid[s] between the two barriers around here)
                     const int j = (v_next % ra.groups) * ROWS + s;

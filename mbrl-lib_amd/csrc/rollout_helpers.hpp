@@ -1,7 +1,11 @@
 // rollout_helpers.hpp -- the small kernels around the rollout kernel (state init, particle mean, member schedules, exports of
 // the device-side randomness, weight / bias packing).  Included by hipets.hip only (non-template kernels: one definition).
 #pragma once
-#include "rollout.hpp"
+#include "closed_forms.hpp"
+#include "common.hpp"
+#include "gemm_bf16.hpp"
+#include "gemm_f32.hpp"
+#include "rollout_types.hpp"
 
 namespace hipets {
 

@@ -25,6 +25,7 @@
 #include <utility>
 
 #include "launch.hpp"
+#include "rollout.hpp"
 
 // lean fp32, bf16x3 and bf16 shapes instantiated for this R: the per-R tables of launch.hpp
 #define HIPETS_LEAN_SHAPES(X) HIPETS_CAT2(HIPETS_LEAN_SHAPES_R, HIPETS_R)(X)

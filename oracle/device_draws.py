@@ -2,7 +2,7 @@
 GPU (hipets_fast_normals, hipets_fast_schedule; hipets_device_perms has oracle/feistel_perm.py) can be re-derived where there is no
 GPU -- tests/test_oracle_memo_pinned.py replays the memoised FAST / DEVICE entries of tests/golden/oracle_cache/ with them.
 
-Restated from mbrl-lib_amd/csrc/common.hpp (philox4x32_10, u01, box_muller, fast_member / fast_member_key), csrc/rollout.hpp
+Restated from mbrl-lib_amd/csrc/common.hpp (philox4x32_10, u01, box_muller, fast_member / fast_member_key), csrc/closed_forms.hpp
 (rollout_normals4: counter = (row, step, block of four output dims, stream), key = seed) and csrc/rollout_helpers.hpp
 (member_schedule_kernel, export_normals_kernel).  The integer parts (Philox, the schedule) are exact; Box-Muller runs on the CPU's float32 log2 / sqrt /
 sin / cos where the device uses v_log_f32 / v_sqrt_f32 / v_sin_f32 / v_cos_f32 (about 1 ulp each): the normals agree to ~1e-6

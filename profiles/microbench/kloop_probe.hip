@@ -1,6 +1,6 @@
 // What keeps the rollout kernel's k loop above 32 cycles per v_mfma_f32_16x16x4_f32?  (round 3: 36.5 cycles per MFMA inside
 // wave_gemm<3,3,1> by the in-kernel phase profile, with buffer-load weight fragments and immediate-offset LDS reads.)
-// The loop body of rollout.hpp wave_gemm<R=3,CT=3,EX=1> rebuilt stand-alone -- 10 accumulators, per 16-wide k chunk 4 weight
+// The loop body of gemm_f32.hpp wave_gemm<R=3,CT=3,EX=1> rebuilt stand-alone -- 10 accumulators, per 16-wide k chunk 4 weight
 // fragments (buffer_load_dwordx4 ... s_off offen from an L2-resident array) + 4 activation fragments (ds_read_b128) feeding
 // 4 k-steps x 10 MFMAs, double buffered, sched_barrier pinned like the original -- with its ingredients switchable:
 //   bit 0: s_nop 1 in front of every k-step      bit 1: the LDS fragment reads      bit 2: the weight fragment loads

@@ -6,7 +6,7 @@ one-tile heading: the shape-specialised instances compile the profiler out unles
     HIPETS_LIB=profiles/variants/leanprof.so python profiles/one_tile_phase_profile.py > gpurun_out/r6_one_tile_phase_profile.json
 
 Per workload and mode: (1) the UNPROFILED launch duration of this very build (no phase buffer passed: the marks are dead branches),
-(2) one launch with the phase buffer: per phase and wave the cycles and the NUMBER of marks (rollout.hpp Prof: count in the upper
+(2) one launch with the phase buffer: per phase and wave the cycles and the NUMBER of marks (gemm_f32.hpp Prof: count in the upper
 bits), (3) the cost of a mark, calibrated as (profiled - unprofiled duration) / marks of wave 0, subtracted per phase.  Workgroup 0 is
 the only one that stamps; in the profiled launch it is the slowest workgroup, so the launch duration is its timeline."""
 import json

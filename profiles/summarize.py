@@ -40,7 +40,7 @@ def rollout_row(stats_csv, names=("rollout_kernel",)):
     out = {"kernels": [r["Name"][:120] for r in rows], "calls": calls, "avg_ns": total / calls, "min_ns": min(float(r["MinNs"]) for r in rows),
            "max_ns": max(float(r["MaxNs"]) for r in rows), "pct_of_gpu_time": sum(float(r["Percentage"]) for r in rows)}
     # The persistent DEVICE form validates co-residency ONCE per process with a self-test launch of the very same kernel (a few
-    # microseconds: every workgroup arrives at a counter and returns; rollout.hpp RolloutArgs::census).  rocprofv3 files it under
+    # microseconds: every workgroup arrives at a counter and returns; rollout_types.hpp RolloutArgs::census).  rocprofv3 files it under
     # the rollout kernel's name; bench.py's hipEvents do not cover it.  Reported separately, so that the two averages compare.
     if len(rows) == 1 and out["min_ns"] < 0.05 * out["avg_ns"] and calls > 2:
         out["self_test_launches_excluded"] = 1

@@ -12,7 +12,7 @@ from test_gpu_rollout import _random_case
 
 
 def bf16_rne_bits(x):
-    """numpy restatement of csrc/rollout.hpp bf16_rne_bits: the bf16 nearest-even rounding of finite fp32 values, as fp32."""
+    """numpy restatement of csrc/gemm_bf16.hpp bf16_rne_bits: the bf16 nearest-even rounding of finite fp32 values, as fp32."""
     u = np.asarray(x, np.float32).view(np.uint32).astype(np.uint64)
     r = (u + 0x7FFF + ((u >> 16) & 1)) & 0xFFFF0000
     return r.astype(np.uint32).view(np.float32)

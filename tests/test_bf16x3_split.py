@@ -1,4 +1,4 @@
-"""The operand split of precision='bf16x3' (csrc/rollout.hpp split3), restated in numpy: three bf16 pieces reproduce an fp32 value to
+"""The operand split of precision='bf16x3' (csrc/gemm_bf16.hpp split3), restated in numpy: three bf16 pieces reproduce an fp32 value to
 2^-24 relative, and the six kept partial products reproduce an fp32 product to a few 2^-24."""
 import numpy as np
 

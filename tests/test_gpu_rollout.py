@@ -500,7 +500,7 @@ def test_gaussian_mlp_with_explicit_member_maps(engine, prop):
 def assert_same_arithmetic(a, b, kernel_class):
     """Two instances of the rollout kernel on the same call.  Bit for bit -- except where one of them is a K-SPLIT instance: the
     FUSED (not WIDE) instances with ONE row tile per workgroup deal the k range of the 13th hidden column tile to the four waves
-    (rollout.hpp KSpec::KSPLIT, round 5), i.e. sum hidden columns 192..207 in another order; they agree with every other instance to
+    (kspec.hpp KSpec::KSPLIT, round 5), i.e. sum hidden columns 192..207 in another order; they agree with every other instance to
     rounding, which is held to a tenth of the tolerance the same returns get against the oracle (T2).  `kernel_class` =
     Engine.kernel_class(...) of the shape-specialised side: (class name, row tiles).  Everything else -- WIDE, hidden-static and
     generic instances at any row-tile count, fused ones at R >= 2 -- must be bit for bit (round-5 advice: a blanket tolerance for
