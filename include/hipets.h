@@ -26,7 +26,7 @@
  *     pinned staging buffers owned by the engine and uploaded asynchronously from there; model descriptors are
  *     uploaded inside hipets_set_model, which synchronises.
  *   - one engine per device; an engine is not thread-safe (the reference is single-threaded).  Engines of DIFFERENT devices may
- *     be driven from different host threads (the library's per-kernel residency table is locked).
+ *     be driven from different host threads (the library's per-device residency table is locked).
  */
 #ifndef HIPETS_H
 #define HIPETS_H
@@ -261,7 +261,9 @@ int hipets_device_perms(hipets_engine* e, int32_t horizon, int32_t batch, uint64
  *     the library launches that very instance in a self-test mode in which every workgroup waits for all the others (one extra
  *     launch and ONE synchronisation of `stream`, once per instance, LDS size (model / horizon) and grid size -- so the first plan
  *     of a new shape is not capturable into a hipGraph, later ones are); if they cannot meet, the runtime's smaller
- *     occupancy answer is tried, and failing that the engine launches per step;
+ *     occupancy answer is tried, and failing that the engine launches per step.  What the self-tests found is kept per device,
+ *     kernel instance and LDS size behind one lock per device: engines on one device driven from two host threads serialise the
+ *     enqueue of their persistent launches there, and a persistent launch never exceeds the grid that was validated;
  *   - every poll is bounded (hipets_set_handover_timeout, default 0.2 s): if a producer never shows up (another process or
  *     stream took CUs after the self-test) the kernel raises a host-visible flag and drains in milliseconds.  The results of
  *     that launch, and everything computed from them, are INVALID;

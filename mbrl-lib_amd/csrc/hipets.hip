@@ -5,7 +5,6 @@
 #include <dlfcn.h>
 
 #include <algorithm>
-#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -17,6 +16,7 @@
 #include "cem.hpp"
 #include "launch.hpp"
 #include "optim.hpp"
+#include "residency.hpp"
 #include "rollout_helpers.hpp"
 #include "rollout_smem.hpp"
 #include "train.hpp"
@@ -107,7 +107,7 @@ struct hipets_engine {
     int* error_flag = nullptr;
     bool persistent_ok = true;
     long long poll_ticks = 20000000ll;  // bound of one hand-over poll, 100 MHz ticks (hipets_set_handover_timeout; default 0.2 s)
-    DevBuf census;                      // [2] ints of the co-residency self-test (rollout_inst.inc launch_one)
+    DevBuf census;                      // [2] ints of the co-residency self-test (residency.hpp census_ok)
     // The workspace (state / totals / schedules / plan buffers), the hand-over table, its tags and the key tables are
     // engine-global: the work of two calls must execute in the order the calls were made.  A call on another stream than the
     // previous call's first makes its stream wait for that one (an event, device side only), so "any stream per call"
@@ -142,9 +142,27 @@ struct hipets_engine {
 
 namespace {
 
+// the kernel instance a call with R row tiles runs (launch.hpp pick_rollout_instance); nullptr: there is none, and fail() has said why
+KernelRec* rollout_instance(const hipets_engine* e, int R, const RolloutArgs& ra) {
+    static constexpr decltype(&rollout_instance_r1) resolvers[kMaxR] = {rollout_instance_r1, rollout_instance_r2, rollout_instance_r3, rollout_instance_r4};
+    if (R < 1 || R > kMaxR) return fail("unsupported rows_per_group %d (1..%d)", R, kMaxR), nullptr;
+    hipError_t why = hipSuccess;
+    KernelRec* k = resolvers[R - 1](e->md, ra, &why);
+    const bool b3 = e->md.precision == HIPETS_PREC_BF16X3;
+    if (!k && why == hipErrorNotSupported && (b3 || e->md.precision == HIPETS_PREC_BF16))
+        fail("precision %s: no shape-specialised kernel instance for this model / call (SiLU, f64 normaliser, no obs preprocessing, in-kernel "
+             "sampling, one of the %s layer shapes, R = %d); use precision f32", b3 ? "bf16x3" : "bf16", b3 ? "BASELINE" : "two bf16", R);
+    else if (!k) fail_kind(HIPETS_ERR_RUNTIME, "rollout kernel launch failed: %s", hipGetErrorString(why));
+    return k;
+}
+
 int launch_rollout(hipets_engine* e, int R, int grid, size_t lds, const RolloutArgs& ra, hipStream_t st) {
+    RolloutArgs rl = ra;
+    rl.lds_bytes = (unsigned)lds;  // (debug builds check every LDS section against it)
+    KernelRec* k = rollout_instance(e, R, rl);
+    if (!k) return 1;
     hipEvent_t a = nullptr, b = nullptr;
-    const bool timed = !ra.capacity_out && e->timing && (e->launch_counter++ % (unsigned long long)e->timing_stride) == 0;
+    const bool timed = e->timing && (e->launch_counter++ % (unsigned long long)e->timing_stride) == 0;
     if (timed) {
         if (!e->event_pool.empty()) {
             a = e->event_pool.back().first;
@@ -155,24 +173,18 @@ int launch_rollout(hipets_engine* e, int R, int grid, size_t lds, const RolloutA
             HCHECK(hipEventCreate(&b));
         }
     }
-    hipError_t err;
-    RolloutArgs rl = ra;
-    rl.lds_bytes = (unsigned)lds;  // (debug builds check every LDS section against it)
-    switch (R) {
-        case 1: err = launch_rollout_r1(grid, (unsigned)lds, (int)e->lds_max, e->md, rl, st, a, b); break;
-        case 2: err = launch_rollout_r2(grid, (unsigned)lds, (int)e->lds_max, e->md, rl, st, a, b); break;
-        case 3: err = launch_rollout_r3(grid, (unsigned)lds, (int)e->lds_max, e->md, rl, st, a, b); break;
-        case 4: err = launch_rollout_r4(grid, (unsigned)lds, (int)e->lds_max, e->md, rl, st, a, b); break;
-        default: return fail("unsupported rows_per_group %d (1..%d)", R, kMaxR);
-    }
+    const hipError_t err = launch_rollout_kernel(*k, grid, (unsigned)lds, (int)e->lds_max, e->md, rl, st, a, b);
     if (timed) e->events.emplace_back(a, b);  // recorded (or leaked to the pool) either way
-    if (err == hipErrorNotSupported && e->md.precision == HIPETS_PREC_BF16)
-        return fail("precision bf16: no shape-specialised kernel instance for this model / call (SiLU, f64 normaliser, no obs "
-                    "preprocessing, in-kernel sampling, one of the two bf16 layer shapes, R = %d); use precision f32", R);
-    if (err == hipErrorNotSupported && e->md.precision == HIPETS_PREC_BF16X3)
-        return fail("precision bf16x3: no shape-specialised kernel instance for this model / call (SiLU, f64 normaliser, no obs "
-                    "preprocessing, in-kernel sampling, one of the BASELINE layer shapes, R = %d); use precision f32", R);
     if (err != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "rollout kernel launch failed: %s", hipGetErrorString(err));
+    return 0;
+}
+
+// persistent form or one launch per step, for a DEVICE rollout of `logical` workgroups (residency.hpp decide_launch_form)
+int launch_form(hipets_engine* e, int R, int logical, size_t lds, RolloutArgs ra, hipStream_t st, bool* persistent) {
+    ra.lds_bytes = (unsigned)lds;
+    KernelRec* k = rollout_instance(e, R, ra);
+    if (!k) return 1;
+    HCHECK(decide_launch_form(*k, logical, (unsigned)lds, (int)e->lds_max, e->num_cu, e->md, ra, e->census.as<int>(), e->poll_ticks, st, &e->persistent_ok, persistent));
     return 0;
 }
 
@@ -328,13 +340,9 @@ int launch_mppi_sample(int n_env, int pop, int H, int A, float beta, const float
 // MPPI update (optim.hpp): the weighted sum stages the population through LDS tiles as large as the CU holds -- the kernel opts in to the
 // full LDS once per device, like the rollout kernels
 int launch_mppi_update(hipets_engine* e, int n_env, int pop, int D, float gamma, float* values, const float* population, float* mean, hipStream_t st) {
-    static std::atomic<bool> attr_set[64] = {};
-    const int dev = e->device;
-    if (dev < 0 || dev >= 64 || !attr_set[dev].load(std::memory_order_acquire)) {
-        HCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_update_kernel<kMppiTileMax / 16>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_max));
-        HCHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(&mppi_update_kernel<kMppiTileMax / 32>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)e->lds_max));
-        if (dev >= 0 && dev < 64) attr_set[dev].store(true, std::memory_order_release);
-    }
+    static LdsOptIn once[2];
+    HCHECK(full_lds_once(once[0], reinterpret_cast<const void*>(&mppi_update_kernel<kMppiTileMax / 16>), (int)e->lds_max));
+    HCHECK(full_lds_once(once[1], reinterpret_cast<const void*>(&mppi_update_kernel<kMppiTileMax / 32>), (int)e->lds_max));
     const int tile_c = mppi_update_tile(pop, e->lds_max);
     const dim3 grid(mppi_update_blocks(D), n_env);
     if (tile_c == kMppiTileMax)
@@ -891,28 +899,7 @@ int rollout_impl(hipets_engine* e, const float* actions, const float* s0, int32_
         // table.  Only as many workgroups as are resident at once are launched; a batch with more logical workgroups (cfg4: 435)
         // is served in turns, workgroup b taking b, b + grid, ... every step.
         bool persistent = device && per_step && e->persistent_ok && H > 1;
-        if (persistent) {
-            // How many workgroups of this kernel instance can wait for each other (be resident at once)?  The launcher answers
-            // from the occupancy arithmetic AND a one-time self-test of the instance at this grid size (a census launch + one
-            // stream synchronisation the first time a larger grid is asked for); 0 = the self-test failed (CUs held by another
-            // process, a masked device, an occupancy estimate that does not hold on this ROCm build): launch per step then.
-            int capacity = 0;
-            RolloutArgs q = ra;
-            q.exchange = reinterpret_cast<unsigned long long*>(&capacity);  // marks the persistent form for the launcher; never dereferenced
-            q.capacity_out = &capacity;
-            q.census = e->census.as<int>();
-            q.poll_ticks = std::max(e->poll_ticks, 20000000ll);  // the self-test keeps its 0.2 s whatever bound the hand-over polls were given
-            if (launch_rollout(e, R, domains * groups, lds, q, st)) return 1;
-            if (capacity <= 0) {
-                e->persistent_ok = false;  // stays off until hipets_set_persistent(e, 1)
-                persistent = false;
-            } else {
-                // Turns pay off when a CU holds ONE workgroup of this instance (cfg4: 4.51 -> 4.11 ms per rollout, cfg4' 16.4 -> 15.0).
-                // Where two are resident, one launch per step lets the hardware deal 1 250 workgroups to 512 slots as they free up;
-                // fixed turns (3 for some workgroups, 2 for the rest) measured slower there (cfg5: 7.3 vs 6.6 ms).
-                persistent = domains * groups <= capacity || capacity <= e->num_cu;
-            }
-        }
+        if (persistent && launch_form(e, R, domains * groups, lds, ra, st, &persistent)) return 1;
         if (!persistent) {  // the persistent form starts from s0 itself and writes every row's total at the end
             hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((B * md.obs_dim + 255) / 256)), dim3(256), 0, st,
                                e->state.as<float>(), e->totals.as<float>(), e->term.as<unsigned char>(), e->s0.as<float>(), (int)B,

@@ -4,18 +4,24 @@
 #include <hip/hip_runtime.h>
 
 #include "kspec.hpp"
+#include "lds_optin.hpp"
 #include "planet_types.hpp"
 #include "rollout_types.hpp"
 
 namespace hipets {
 
-// Launch the instance of rollout_kernel<R, ...> that pick_rollout_instance (below) names for this model and call, with `grid`
-// workgroups and `lds` bytes of dynamic LDS on `st`.  start / stop (both or neither) ride on the dispatch packet.
-constexpr int kMaxR = 4;  // row-tile counts 1..kMaxR, one launcher each
-hipError_t launch_rollout_r1(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start, hipEvent_t stop);
-hipError_t launch_rollout_r2(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start, hipEvent_t stop);
-hipError_t launch_rollout_r3(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start, hipEvent_t stop);
-hipError_t launch_rollout_r4(int grid, unsigned lds, int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st, hipEvent_t start, hipEvent_t stop);
+// One instance of rollout_kernel<R, ...> as the host sees it: the address hipLaunchKernel takes and the instance's LDS opt-in flags
+// (residency.hpp launches it and keeps what is known about its residency), and per row-tile count R the resolver that hands out the record
+// of the instance pick_rollout_instance (below) names: nullptr with *why = hipErrorNotSupported / hipErrorInvalidConfiguration for a refusal.
+struct KernelRec {
+    const void* fn;
+    LdsOptIn lds;
+};
+constexpr int kMaxR = 4;  // row-tile counts 1..kMaxR
+KernelRec* rollout_instance_r1(const ModelDev& md, const RolloutArgs& ra, hipError_t* why);
+KernelRec* rollout_instance_r2(const ModelDev& md, const RolloutArgs& ra, hipError_t* why);
+KernelRec* rollout_instance_r3(const ModelDev& md, const RolloutArgs& ra, hipError_t* why);
+KernelRec* rollout_instance_r4(const ModelDev& md, const RolloutArgs& ra, hipError_t* why);
 
 // Hidden widths with a KSpec::HID_STATIC instance (hidden layers shape-specialised, everything else generic): X(hidden column tiles).
 // 13 tiles = hidden widths 193..208: the reference's default of 200 (conf/dynamics_model/gaussian_mlp_ensemble.yaml:8), which every
@@ -179,7 +185,7 @@ inline bool hid_static_call(const ModelDev& md, const RolloutArgs& ra) {
     return false;
 }
 
-// The instance of rollout_kernel<R, ...> a call runs -- the one selection rule: the launcher of rollout_r<R>.hip dispatches on it,
+// The instance of rollout_kernel<R, ...> a call runs -- the one selection rule: the resolver of rollout_r<R>.hip dispatches on it,
 // hipets_kernel_class reports it.  lean_wide: a KSpec::WIDE lean instance, which runs exactly where the host sized the LDS for its
 // layout (RolloutArgs::wide_lds); generic_silu: the generic instance with the SiLU epilogue fixed.  Refusals: no_b3 / no_bf16 (bf16x3 and
 // bf16 arithmetic exist in shape-specialised instances only: a model or call without one fails, it never runs another arithmetic),

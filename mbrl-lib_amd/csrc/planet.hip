@@ -9,15 +9,9 @@ namespace hipets {
 namespace {
 template <bool STATIC>
 hipError_t launch_planet(int grid, unsigned lds, int lds_max, const PlanetDev& pd, const PlanetArgs& ra, hipStream_t st) {
-    static bool attr_set[64] = {};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
+    static LdsOptIn once;
+    const hipError_t e = full_lds_once(once, reinterpret_cast<const void*>(&planet_rollout_kernel<STATIC>), lds_max);
     if (e != hipSuccess) return e;
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(&planet_rollout_kernel<STATIC>), hipFuncAttributeMaxDynamicSharedMemorySize, lds_max);
-        if (e != hipSuccess) return e;
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
     hipLaunchKernelGGL(planet_rollout_kernel<STATIC>, dim3(grid), dim3(kThreads), lds, st, pd, ra);
     return hipGetLastError();
 }

@@ -4,6 +4,7 @@
 // Every product runs on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32 accumulate).
 #include <hip/hip_runtime.h>
 
+#include "lds_optin.hpp"
 #include "train.hpp"
 
 namespace hipets {
@@ -366,16 +367,9 @@ hipError_t launch_train_steps(const TrainStepArgs& a, hipStream_t st) {
 
 hipError_t launch_train_eval(const TrainEvalArgs& a, hipStream_t st) {
     const size_t lds = (size_t)2 * kEvalRows * a.max_width * sizeof(float);
-    static bool attr_set[64] = {};
-    int dev = 0;
-    hipError_t err = hipGetDevice(&dev);
+    static LdsOptIn once;
+    hipError_t err = full_lds_once(once, reinterpret_cast<const void*>(&train_eval_kernel), 2 * kEvalRows * kTrainMaxIn * (int)sizeof(float));
     if (err != hipSuccess) return err;
-    if (dev < 0 || dev >= 64 || !attr_set[dev]) {
-        err = hipFuncSetAttribute(reinterpret_cast<const void*>(&train_eval_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  2 * kEvalRows * kTrainMaxIn * (int)sizeof(float));
-        if (err != hipSuccess) return err;
-        if (dev >= 0 && dev < 64) attr_set[dev] = true;
-    }
     hipLaunchKernelGGL(train_eval_kernel, dim3(a.tiles, a.ensemble_size), dim3(kEvalThreads), lds, st, a);
     err = hipGetLastError();
     if (err != hipSuccess) return err;

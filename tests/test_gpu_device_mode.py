@@ -189,6 +189,49 @@ def test_every_shipped_device_instance_persistent_equals_per_step(engine, name, 
     assert torch.isfinite(a).all() and torch.equal(a, b)
 
 
+# (R, population, persistent form allowed, logical workgroups, rollout-kernel launches on 256 CUs): M = 5, P = 20, H = 4 at the cfg2 shape
+LAUNCH_FORMS = {
+    "one_per_cu_fits": (3, 480, True, 200, 1),
+    "turns": (3, 1080, True, 450, 1),             # one workgroup of the R = 3 instance per CU: 256 launched, the rest in turns
+    "two_per_cu": (1, 360, True, 450, 1),         # two workgroups of the R = 1 instance per CU hold all 450
+    "beyond_two_per_cu": (1, 600, True, 750, 4),  # more than the 512 resident: one launch per step
+    "persistent_off": (3, 480, False, 200, 4),
+}
+
+
+@pytest.mark.parametrize("form", list(LAUNCH_FORMS))
+def test_launch_form_of_device_rollouts(engine, form):
+    """The bitwise persistent-vs-per-step tests above pass just as well when every rollout silently runs per step (a residency rule
+    that answers "capacity 0"): this pins the launch FORM of plain DEVICE rollouts by counting rollout-kernel launches (the
+    co-residency self-test is none, and has run in the warm-up call).  The counts are what the capacity rule (residency_rule.hpp;
+    the same rule the per-instance launcher applied before) gives on 256 CUs; profiles/one_launch_path.json records whether and
+    what a GPU returned for them."""
+    R, pop, persistent, logical, launches = LAUNCH_FORMS[form]
+    obs, act, P, H, M = 17, 6, 20, 4, 5
+    om, actions, s0, _, _ = _random_case(obs, act, pop, P, H, ensemble_size=M, hid=200)
+    engine.set_model(to_spec(om, obs, act))
+    assert M * -(-(pop * P // M) // (16 * R)) == logical
+    kw = dict(mode="device", seed=77, stream_id=9, rows_per_group=R)
+    try:
+        engine.set_persistent(persistent)
+        engine.rollout(actions.to(DEV), s0, P, **kw)  # warm-up: the self-test of this instance and grid
+        engine.timing_enable(True)
+        engine.timing_read(reset=True)
+        a = engine.rollout(actions.to(DEV), s0, P, **kw)
+        n, _ = engine.timing_read(reset=True)
+        engine.set_persistent(False)
+        b = engine.rollout(actions.to(DEV), s0, P, **kw)
+        n_per_step, _ = engine.timing_read(reset=True)
+    finally:
+        engine.timing_enable(False)
+        engine.set_persistent(True)
+    print(f"launch form {form}: {n} launches, {n_per_step} with the persistent form off")
+    assert torch.isfinite(a).all() and torch.equal(a, b)
+    assert n_per_step == H
+    if torch.cuda.get_device_properties(0).multi_processor_count == 256:
+        assert n == launches
+
+
 def ragged_last_turn(pop, P, M, grid=256):
     """rollout.hpp 'Ragged last turn', restated: (turns, row tiles behind the full two-tile turns, dealt one per workgroup?)"""
     tpd = -(-(pop * P // M) // 16)
