@@ -32,7 +32,7 @@ KernelRec* rollout_instance_r4(const ModelDev& md, const RolloutArgs& ra, hipErr
 
 // Shape-specialised ("lean") fp32 instances per row-tile count R: X(hidden column tiles, output column tiles, reward fn, termination
 // fn, obs preprocessing); all of them SiLU, f64 normaliser, stochastic GaussianMLP with in-kernel sampling.  R follows the cost
-// model's choice for the configuration (hipets.hip choose_R, which in turn knows this table: lean_shape_exists):
+// model's choice for the configuration (rollout.hip choose_R, which in turn knows this table: lean_shape_exists):
 //   BASELINE.json: cfg1 cartpole R = 1, cfg2 / cfg3 R = 3 (a rank's shard of a strong-scaled plan: 1, 2), cfg4 R = 3 at its first
 //   iteration and 2 / 4 as the iCEM population decays, cfg4' Humanoid-v4 R = 2 (small batches 1; KSpec::WIDE), cfg5 (2500 row tiles) 2;
 //   the workloads the reference ships (round 4): pets_halfcheetah (conf/overrides/pets_halfcheetah.yaml: obs 18 through
@@ -66,7 +66,7 @@ KernelRec* rollout_instance_r4(const ModelDev& md, const RolloutArgs& ra, hipErr
 #define HIPETS_B3_SHAPES_R1(X)
 // (round 5: the R = 2 instances are gone -- two workgroups per CU cap a wave at 256 registers, the three-piece fragments did not fit and
 // the two instances spilt 6 / 41 VGPRs to scratch, the only rollout kernels that did; the row-tile rule chooses among R = 1 and 3 for
-// this arithmetic mode, hipets.hip choose_R)
+// this arithmetic mode, rollout.hip choose_R)
 #define HIPETS_B3_SHAPES_R2(X)
 #define HIPETS_B3_SHAPES_R3(X) X(13, 3, HIPETS_REW_HALFCHEETAH, HIPETS_TERM_NONE) X(13, 6, HIPETS_REW_HALFCHEETAH, HIPETS_TERM_HUMANOID)
 #define HIPETS_B3_SHAPES_R4(X)
@@ -142,7 +142,7 @@ inline LeanShape lean_shape(const ModelDev& md, const int R) {
 // than one that runs the hidden-static or the generic kernel)
 inline bool lean_shape_exists(const ModelDev& md, const int R) { return lean_shape(md, R) != LeanShape::none; }
 
-// is the model one of the WIDE shapes?  (where the call is lean, hipets.hip rollout_geometry sizes the LDS and chooses R for that layout)
+// is the model one of the WIDE shapes?  (where the call is lean, rollout.hip rollout_geometry sizes the LDS and chooses R for that layout)
 inline bool wide_model(const ModelDev& md) {
     for (int R = 1; R <= kMaxR; ++R)
         if (lean_shape(md, R) == LeanShape::wide) return true;

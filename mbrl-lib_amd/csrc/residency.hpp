@@ -1,4 +1,4 @@
-// residency.hpp -- host only (hipets.hip): the ONE launcher of every rollout kernel instance and everything that decides whether the
+// residency.hpp -- host only (rollout.hip): the ONE launcher of every rollout kernel instance and everything that decides whether the
 // persistent DEVICE form is safe to run: occupancy estimate, co-residency self-test, table of validated grids, capacity query, choice of
 // launch form.  It works on a KernelRec (launch.hpp): hipLaunchKernel takes the kernel's host address, so nothing here is a template
 // over the instance.
@@ -116,7 +116,7 @@ inline hipError_t decide_launch_form(KernelRec& k, const int logical, const unsi
     return e;
 }
 
-// Launch k.  A persistent launch (ra.exchange set: hipets.hip rollout_impl) is cut to the resident capacity -- the kernel serves the rest of
+// Launch k.  A persistent launch (ra.exchange set: rollout.hip rollout_impl) is cut to the resident capacity -- the kernel serves the rest of
 // the `grid` logical workgroups in turns -- and refused if that grid was never validated; every other launch goes straight out: one
 // acquire load in full_lds_once, no lock.
 inline hipError_t launch_rollout_kernel(KernelRec& k, int grid, const unsigned lds, const int lds_max, const ModelDev& md, const RolloutArgs& ra, hipStream_t st,

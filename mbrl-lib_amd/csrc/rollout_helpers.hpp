@@ -1,5 +1,6 @@
 // rollout_helpers.hpp -- the small kernels around the rollout kernel (state init, particle mean, member schedules, exports of
-// the device-side randomness, weight / bias packing).  Included by hipets.hip only (non-template kernels: one definition).
+// the device-side randomness, weight / bias packing).  Included by rollout.hip only (non-template kernels: one definition);
+// model.hip and plan.hip launch them through the functions rollout.hip offers in engine.hpp.
 #pragma once
 #include "closed_forms.hpp"
 #include "common.hpp"

@@ -2,7 +2,7 @@
 // (activation fixed to SiLU, or read at run time) and the shape-specialised "lean" instances of the BASELINE configurations --
 // and defines rollout_instance_r<R> (launch.hpp), which RESOLVES the instance launch.hpp pick_rollout_instance names to its KernelRec (host
 // address + LDS opt-in flags).  Nothing here launches: the one launcher, the occupancy estimate, the co-residency self-test and the table
-// of validated grids live in residency.hpp (host only, compiled with hipets.hip).
+// of validated grids live in residency.hpp (host only, compiled with rollout.hip).
 // HIPETS_PART splits an R over four translation units, so that no compile job of the build is longer than its largest single kernel
 // instance (round 6: the two fully generic instances take 40-60 s each, an R's whole set took 85-140 s as one unit):
 //   1  rollout_r<R>.hip       the resolver, the reference-semantics (EXACT / DEVICE) shape-specialised instances, the hidden-static one
@@ -94,7 +94,7 @@ KernelRec* HIPETS_FN()(const ModelDev& md, const RolloutArgs& ra, hipError_t* wh
         case RolloutInstance::generic_silu: return HIPETS_FN(_gens)();
         case RolloutInstance::generic: return HIPETS_FN(_gen)();
         case RolloutInstance::no_b3:
-        case RolloutInstance::no_bf16: break;                                        // (hipets.hip launch_rollout reports it)
+        case RolloutInstance::no_bf16: break;                                        // (rollout.hip launch_rollout reports it)
         case RolloutInstance::no_wide: *why = hipErrorInvalidConfiguration; break;  // never run another layout in LDS sized for a WIDE instance
     }
     return nullptr;

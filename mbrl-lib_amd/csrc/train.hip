@@ -1,9 +1,13 @@
-// train.hip -- GaussianMLP ensemble training kernels (hipets_train_steps / hipets_train_eval, include/hipets.h):
+// train.hip -- GaussianMLP ensemble training (hipets_train_steps / hipets_train_eval, include/hipets.h): the kernels, then the entry points.
 //   train_step_kernel  Model.update (mbrl/models/model.py:129-167) + torch.optim.Adam for a chunk of consecutive minibatches
 //   train_eval_kernel  GaussianMLP.eval_score over the whole evaluation set (gaussian_mlp.py:337-361), mean columns only
 // Every product runs on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32 accumulate).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cmath>
+
+#include "engine.hpp"
 #include "lds_optin.hpp"
 #include "train.hpp"
 
@@ -358,6 +362,39 @@ __global__ __launch_bounds__(256) void train_eval_reduce_kernel(const TrainEvalA
     if (tid == 0) a.score[e] = s[0] / ((float)a.n_rows * (float)a.out_dim);
 }
 
+// ---- the C ABI's argument checks (hipets_train_steps / hipets_train_eval below) ----
+
+int train_check(const hipets_train_desc* d, bool adam) {
+    if (!d) return fail("null train desc");
+    if (d->ensemble_size < 1 || d->ensemble_size > kTrainMaxMembers) return fail("ensemble_size %d outside [1, %d]", d->ensemble_size, kTrainMaxMembers);
+    if (d->n_layers < 2 || d->n_layers > HIPETS_MAX_LAYERS) return fail("n_layers %d outside [2, %d]", d->n_layers, HIPETS_MAX_LAYERS);
+    if (d->in_dim < 1 || d->in_dim > kTrainMaxIn) return fail("in_dim %d outside [1, %d]", d->in_dim, kTrainMaxIn);
+    if (d->hid < 1 || d->hid > kTrainMaxHid) return fail("hid %d outside [1, %d]", d->hid, kTrainMaxHid);
+    if (d->out_dim < 1 || d->out_dim > kTrainMaxOut) return fail("out_dim %d outside [1, %d]", d->out_dim, kTrainMaxOut);
+    if (d->activation < HIPETS_ACT_RELU || d->activation > HIPETS_ACT_SIGMOID) return fail("unknown activation %d", d->activation);
+    if (d->max_batch < 1 || d->max_batch > kTrainMaxBatch) return fail("max_batch %d outside [1, %d]", d->max_batch, kTrainMaxBatch);
+    if (!d->weights || !d->biases) return fail("null parameter arrays");
+    for (int l = 0; l < d->n_layers; ++l)
+        if (!d->weights[l] || !d->biases[l]) return fail("null parameter of layer %d", l);
+    if (adam) {
+        if (!d->exp_avg_w || !d->exp_avg_b || !d->exp_avg_sq_w || !d->exp_avg_sq_b || !d->min_logvar || !d->max_logvar)
+            return fail("null Adam state or logvar bounds");
+        for (int l = 0; l < d->n_layers; ++l)
+            if (!d->exp_avg_w[l] || !d->exp_avg_b[l] || !d->exp_avg_sq_w[l] || !d->exp_avg_sq_b[l]) return fail("null Adam state of layer %d", l);
+        // torch.optim.Adam's own argument checks (torch/optim/adam.py)
+        if (!(d->lr >= 0.0) || !(d->eps >= 0.0) || !(d->weight_decay >= 0.0)) return fail("invalid lr / eps / weight_decay");
+        if (!(d->beta1 >= 0.0 && d->beta1 < 1.0) || !(d->beta2 >= 0.0 && d->beta2 < 1.0)) return fail("invalid betas");
+        if (d->steps_per_launch < 0) return fail("steps_per_launch %d < 0", d->steps_per_launch);
+    }
+    return 0;
+}
+
+void train_dims(const hipets_train_desc* d, int32_t* dims) {
+    dims[0] = d->in_dim;
+    for (int l = 1; l < d->n_layers; ++l) dims[l] = d->hid;
+    dims[d->n_layers] = 2 * d->out_dim;
+}
+
 }  // namespace
 
 hipError_t launch_train_steps(const TrainStepArgs& a, hipStream_t st) {
@@ -378,3 +415,127 @@ hipError_t launch_train_eval(const TrainEvalArgs& a, hipStream_t st) {
 }
 
 }  // namespace hipets
+
+// ---- the C ABI: validation, workspace, chunking ----
+using namespace hipets;
+
+extern "C" {
+
+int hipets_train_steps(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows, const int32_t* idx,
+                       const int32_t* rows, int32_t n_steps, int64_t step0, float* loss, float* grad_sq, void* stream) {
+    if (!e) return fail("null engine");
+    if (train_check(d, true)) return 1;
+    if (!x || !y || !idx || !rows || !loss || !grad_sq) return fail("null argument");
+    if (n_rows < 1 || n_rows > INT32_MAX) return fail("n_rows %lld outside [1, 2^31)", (long long)n_rows);
+    if (n_steps < 0) return fail("n_steps %d < 0", n_steps);
+    if (step0 < 0) return fail("step0 %lld < 0", (long long)step0);
+    if (n_steps == 0) return 0;
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HCHECK(hipSetDevice(e->device));
+    ENTER_STREAM(e, st);
+    TrainStepArgs a{};
+    const int L = d->n_layers, E = d->ensemble_size, Bm = d->max_batch;
+    train_dims(d, a.dims);
+    int64_t off = 0, widest = 0;
+    auto take = [&](int64_t n) { const int64_t o = off; off += (n + 63) / 64 * 64; return o; };
+    for (int l = 0; l < L; ++l) a.off_a[l] = take((int64_t)Bm * a.dims[l]);
+    for (int l = 0; l + 1 < L; ++l) a.off_z[l] = take((int64_t)Bm * a.dims[l + 1]);
+    for (int l = 1; l <= L; ++l) widest = std::max<int64_t>(widest, a.dims[l]);
+    a.off_o = take((int64_t)Bm * a.dims[L]);
+    a.off_t = take((int64_t)Bm * d->out_dim);
+    a.off_d0 = take((int64_t)Bm * widest);
+    a.off_d1 = take((int64_t)Bm * widest);
+    a.slab_stride = off;
+    if (e->train_slab.ensure((size_t)E * off * sizeof(float))) return 1;
+    a.slab = e->train_slab.as<float>();
+    for (int l = 0; l < L; ++l) {
+        a.w[l] = static_cast<float*>(d->weights[l]);
+        a.b[l] = static_cast<float*>(d->biases[l]);
+        a.mw[l] = static_cast<float*>(d->exp_avg_w[l]);
+        a.mb[l] = static_cast<float*>(d->exp_avg_b[l]);
+        a.vw[l] = static_cast<float*>(d->exp_avg_sq_w[l]);
+        a.vb[l] = static_cast<float*>(d->exp_avg_sq_b[l]);
+    }
+    a.x = x;
+    a.y = y;
+    a.min_logvar = d->min_logvar;
+    a.max_logvar = d->max_logvar;
+    a.n_rows = n_rows;
+    a.n_layers = L;
+    a.out_dim = d->out_dim;
+    a.ensemble_size = E;
+    a.max_batch = Bm;
+    a.activation = d->activation;
+    a.leaky_slope = d->leaky_slope;
+    // torch passes these python floats to float32 tensor ops: one rounding each
+    a.weight_decay = (float)d->weight_decay;
+    a.one_minus_beta1 = (float)(1.0 - d->beta1);
+    a.beta2 = (float)d->beta2;
+    a.one_minus_beta2 = (float)(1.0 - d->beta2);
+    a.eps = (float)d->eps;
+    // launches of ~50 ms at most: a step costs ~ 6 B P flops per member at the ~50 GFLOP/s per CU the kernel reaches
+    // (measured at both halfcheetah shapes)
+    int chunk = d->steps_per_launch;
+    if (chunk == 0) {
+        double params = 0.0;
+        for (int l = 0; l < L; ++l) params += (double)a.dims[l] * a.dims[l + 1];
+        const double step_us = 20.0 + 6.0 * Bm * params / 5.0e4;
+        chunk = (int)std::max(1.0, std::min((double)kTrainMaxSteps, 50000.0 / step_us));
+    }
+    chunk = std::min(chunk, kTrainMaxSteps);
+    for (int s0 = 0; s0 < n_steps; s0 += chunk) {
+        const int n = std::min(chunk, n_steps - s0);
+        for (int i = 0; i < n; ++i) {  // torch.optim.Adam (_single_tensor_adam): python-float bias corrections
+            const double t = (double)(step0 + s0 + i + 1);
+            const double bc1 = 1.0 - std::pow(d->beta1, t), bc2 = 1.0 - std::pow(d->beta2, t);
+            a.neg_step_size[i] = (float)(-(d->lr / bc1));
+            a.bc2_sqrt[i] = (float)std::pow(bc2, 0.5);
+        }
+        a.n_steps = n;
+        a.idx = idx + (int64_t)s0 * E * Bm;
+        a.rows = rows + s0;
+        a.loss = loss + (int64_t)s0 * E;
+        a.grad_sq = grad_sq + (int64_t)s0 * E;
+        hipError_t err = launch_train_steps(a, st);
+        if (err != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "train step kernel launch failed: %s", hipGetErrorString(err));
+    }
+    return 0;
+}
+
+int hipets_train_eval(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows, const int32_t* order,
+                      float* score, float* row_score, void* stream) {
+    if (!e) return fail("null engine");
+    if (train_check(d, false)) return 1;
+    if (!x || !y || !score) return fail("null argument");
+    if (n_rows < 1 || n_rows > INT32_MAX) return fail("n_rows %lld outside [1, 2^31)", (long long)n_rows);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HCHECK(hipSetDevice(e->device));
+    ENTER_STREAM(e, st);
+    TrainEvalArgs a{};
+    const int L = d->n_layers, E = d->ensemble_size;
+    train_dims(d, a.dims);
+    for (int l = 0; l < L; ++l) {
+        a.w[l] = static_cast<const float*>(d->weights[l]);
+        a.b[l] = static_cast<const float*>(d->biases[l]);
+    }
+    a.tiles = (int)((n_rows + kEvalRows - 1) / kEvalRows);
+    if (e->train_partial.ensure((size_t)E * a.tiles * sizeof(float))) return 1;
+    a.partial = e->train_partial.as<float>();
+    a.x = x;
+    a.y = y;
+    a.order = order;
+    a.row_score = row_score;
+    a.score = score;
+    a.n_rows = n_rows;
+    a.n_layers = L;
+    a.out_dim = d->out_dim;
+    a.ensemble_size = E;
+    a.activation = d->activation;
+    a.leaky_slope = d->leaky_slope;
+    a.max_width = std::max(std::max(d->in_dim, d->hid), d->out_dim);
+    hipError_t err = launch_train_eval(a, st);
+    if (err != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "train eval kernel launch failed: %s", hipGetErrorString(err));
+    return 0;
+}
+
+}  // extern "C"

@@ -1,5 +1,5 @@
 // train.hpp -- GaussianMLP ensemble training (ModelTrainer.train / evaluate, mbrl/models/model_trainer.py:70-262): the kernel
-// argument blocks shared by train.hip (kernels + launchers) and hipets.hip (the C ABI: validation, workspace, chunking).
+// argument blocks of train.hip: its kernels and launchers, and its entry points of the C ABI (validation, workspace, chunking).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,4 +1,4 @@
-"""Python restatement of the library's row-tile rule (mbrl-lib_amd/csrc/hipets.hip choose_R + wave_units, launch.hpp's instance tables) for
+"""Python restatement of the library's row-tile rule (mbrl-lib_amd/csrc/rollout.hip choose_R + wave_units, launch.hpp's instance tables) for
 hid-200 models on a 256-CU chip -- test infrastructure: lets the calibration claim of DESIGN.md section 4 ("the fastest R in 23 of the 24
 measured cases") be checked on CPU against the committed sweeps, and the restatement itself be checked against the library on the GPU
 (tests/test_gpu_cost_model.py)."""

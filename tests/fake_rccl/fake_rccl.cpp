@@ -1,6 +1,6 @@
 // fake_rccl.cpp -- TEST INFRASTRUCTURE, never linked or loaded by the product unless a test says HIPETS_RCCL_LIB=<this .so>.
 //
-// A stand-in for the five RCCL entry points libhipets binds through dlopen (hipets.hip rccl_load: ncclGetUniqueId,
+// A stand-in for the five RCCL entry points libhipets binds through dlopen (comm.hip rccl_load: ncclGetUniqueId,
 // ncclCommInitRank, ncclAllGather, ncclCommDestroy, ncclGetErrorString, + the optional ncclCommCount / ncclCommUserRank), for
 // N ranks that are N PROCESSES SHARING ONE GPU.  It exists so that hipets_plan_cem_sharded's world > 1 path -- uneven candidate
 // shards, the padded all-gather, the unpad kernel, the rank-offset rollout seeds, the error path -- executes on the one-GPU

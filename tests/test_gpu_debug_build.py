@@ -3,7 +3,7 @@ rebuilt here only if they do not match the sources).
   libhipets_debug.so  -O1 -g, every LDS section of the rollout kernel and the indexed LDS accesses of its elementwise phases
                       bound-checked on the device (gemm_f32.hpp HIPETS_BOUND: a violated bound prints and traps the kernel):
                       runs the driver's smoke() -- EXACT-mode rollout against the oracle + a fused CEM plan.
-  libhipets_asan.so   the same, with the host side of the C ABI (hipets.hip) under AddressSanitizer: runs the plain-C client of
+  libhipets_asan.so   the same, with the host side of the C ABI (the HOST_UNITS of __graft_entry__.py) under AddressSanitizer: runs the plain-C client of
                       the ABI (create / set_model / EXACT + FAST rollouts / fused plan / destroy) compiled with the sanitizer too.
 (The sanitizer runtime intercepts HSA allocations and fails inside the HIP runtime PyTorch bundles -- measured on the GPU box --
 so the Python host runs the bounds-checked library, the C host the sanitized one.)"""
