@@ -37,8 +37,10 @@
 extern "C" {
 #endif
 
-#define HIPETS_ABI_VERSION 8
+#define HIPETS_ABI_VERSION 9
 #define HIPETS_MAX_LAYERS 8
+#define HIPETS_MAX_REWARD_TERMS 64   /* entries of a reward term table (HIPETS_REW_TERMS)  */
+#define HIPETS_MAX_TERM_INTERVALS 64 /* interval tests of a healthy box (HIPETS_TERM_BOX)     */
 
 typedef struct hipets_engine hipets_engine;
 
@@ -51,10 +53,12 @@ enum { HIPETS_OBS_NONE = 0, HIPETS_OBS_HALFCHEETAH = 1, HIPETS_OBS_CARTPOLE_PETS
 /* reward_fn (mbrl/env/reward_fns.py:10-53); LEARNED = last model output (model_env.py:124-128) */
 enum { HIPETS_REW_LEARNED = 0, HIPETS_REW_CARTPOLE = 1, HIPETS_REW_CARTPOLE_PETS = 2, HIPETS_REW_INVERTED_PENDULUM = 3,
        HIPETS_REW_HALFCHEETAH = 4, HIPETS_REW_PUSHER = 5,
-       HIPETS_REW_NONE = 6 /* rewards are computed by the caller (arbitrary Python reward_fn on hipets_step's next_obs) */ };
+       HIPETS_REW_NONE = 6, /* rewards are computed by the caller (arbitrary Python reward_fn on hipets_step's next_obs) */
+       HIPETS_REW_TERMS = 7 /* ABI v9: the model's own term table (hipets_reward_term below), no mbrl.env counterpart   */ };
 /* termination_fn (mbrl/env/termination_fns.py:12-95) */
 enum { HIPETS_TERM_NONE = 0, HIPETS_TERM_CARTPOLE = 1, HIPETS_TERM_INVERTED_PENDULUM = 2, HIPETS_TERM_HOPPER = 3,
-       HIPETS_TERM_WALKER2D = 4, HIPETS_TERM_ANT = 5, HIPETS_TERM_HUMANOID = 6 };
+       HIPETS_TERM_WALKER2D = 4, HIPETS_TERM_ANT = 5, HIPETS_TERM_HUMANOID = 6,
+       HIPETS_TERM_BOX = 7 /* ABI v9: the model's own healthy box (hipets_term_interval below) */ };
 /* Normalizer dtype (mbrl/util/math.py:108-111; normalize_double_precision, one_dim_tr_model.py:87-92) */
 enum { HIPETS_NORM_NONE = 0, HIPETS_NORM_F32 = 1, HIPETS_NORM_F64 = 2 };
 /* Ensemble container: GAUSSIAN_MLP = one GaussianMLP with E members: balanced random shuffles and the batch % members
@@ -83,6 +87,38 @@ enum { HIPETS_MODE_EXACT = 0,  /* reference semantics, injected perms / eps (par
                                /* drawn in-kernel from (seed, stream_id): a keyed bijection of [0, B) and Philox     */
                                /* normals.  No input tensors; exportable through hipets_device_perms /              */
                                /* hipets_fast_normals for replay through a reference implementation.                 */ };
+
+/* ---- parametric closed forms (ABI v9): rewards and terminations of environments mbrl.env does not ship ----------------
+ * Both are defined op by op in fp32 (no fused multiply-add), on the step's next_obs s' and its action a:
+ *
+ * HIPETS_REW_TERMS   r = reward_bias + sum_k w_k * f_k(e_k)  [+ alive_bonus * (done ? 0 : 1)]
+ *     accumulated in table order starting from reward_bias; e_k = v[i_k] - (j_k >= 0 ? v[j_k] : c_k) with v = s' (source
+ *     OBS) or a (source ACT); f = identity, square or absolute value.  The alive bonus is added last, and only when it is
+ *     non-zero; `done` is the model's own termination test on the same s' (reward_fns.cartpole: (~termination_fn).float()).
+ *     NaN and inf propagate as IEEE arithmetic does.
+ * HIPETS_TERM_BOX    healthy = every interval test holds (lo < or <= s'[dim] < or <= hi, each bound open or closed by its
+ *     flag, +-inf allowed; a NaN fails every test) and, with term_require_finite, all obs_dim dims of s' are finite;
+ *     done = !healthy.  Restates termination_fns.cartpole / inverted_pendulum / hopper / walker2d / ant exactly, and
+ *     humanoid on finite rows only (the reference's humanoid leaves a NaN row alive; a box ends it).
+ * The parametric forms run on the GENERIC and HIDDEN_STATIC kernel instances (hipets_kernel_class): a model that uses one
+ * has no shape-specialised instance, and is therefore refused under HIPETS_PREC_BF16X3 / HIPETS_PREC_BF16.               */
+enum { HIPETS_TERM_FN_LINEAR = 0, HIPETS_TERM_FN_SQUARE = 1, HIPETS_TERM_FN_ABS = 2 };
+enum { HIPETS_TERM_SRC_OBS = 0, HIPETS_TERM_SRC_ACT = 1 };
+enum { HIPETS_BOX_LO_OPEN = 1, HIPETS_BOX_HI_OPEN = 2 }; /* hipets_term_interval.flags: the bound is strict (0 = closed) */
+typedef struct {
+    int32_t fn;     /* HIPETS_TERM_FN_*                                                  */
+    int32_t source; /* HIPETS_TERM_SRC_*: the vector i and j index                       */
+    int32_t i;      /* dim of the minuend                                                */
+    int32_t j;      /* dim of the subtrahend, or < 0: the constant c                     */
+    float c;
+    float w;        /* weight of the term                                                */
+} hipets_reward_term;
+typedef struct {
+    int32_t dim;    /* observation dim                                                   */
+    int32_t flags;  /* HIPETS_BOX_LO_OPEN | HIPETS_BOX_HI_OPEN                           */
+    float lo;       /* lo <= hi; -INFINITY / INFINITY = no bound on that side            */
+    float hi;
+} hipets_term_interval;
 
 /*
  * Snapshot of what ModelEnv.evaluate_action_sequences reads from the live objects
@@ -120,6 +156,15 @@ typedef struct {
     int32_t ensemble_kind;   /* HIPETS_ENSEMBLE_*                                                 */
     int32_t precision;       /* HIPETS_PREC_*: BF16X3 / BF16 run only where a shape-specialised kernel instance */
                              /*   exists for the model and the call (else the rollout call fails)           */
+    /* ABI v9: the tables of the parametric closed forms above.  A zeroed tail = none (reward_fn / termination_fn then  */
+    /* must not ask for them); present exactly when the enum does.  Copied into engine-owned device memory.            */
+    const hipets_reward_term* reward_terms;     /* HOST [n_reward_terms] for HIPETS_REW_TERMS, else NULL                */
+    const hipets_term_interval* term_intervals; /* HOST [n_term_intervals] for HIPETS_TERM_BOX, else NULL               */
+    int32_t n_reward_terms;    /* 0 .. HIPETS_MAX_REWARD_TERMS (0 with HIPETS_REW_TERMS: bias and alive bonus only)     */
+    int32_t n_term_intervals;  /* 0 .. HIPETS_MAX_TERM_INTERVALS (0 with HIPETS_TERM_BOX: the finite test only)         */
+    float reward_bias;         /* HIPETS_REW_TERMS: the sum starts here                                                 */
+    float alive_bonus;         /* HIPETS_REW_TERMS: != 0 needs a termination_fn other than HIPETS_TERM_NONE             */
+    int32_t term_require_finite; /* HIPETS_TERM_BOX: every observation dim must be finite                               */
 } hipets_model_desc;
 
 /* options of one evaluate_action_sequences call */

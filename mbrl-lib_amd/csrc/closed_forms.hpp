@@ -6,6 +6,7 @@
 // (gaussian_mlp.py:152-153).
 #pragma once
 #include "common.hpp"
+#include "rollout_types.hpp"
 
 namespace hipets {
 
@@ -43,8 +44,22 @@ __device__ __forceinline__ float processed_obs(const float* s, int i, int mode) 
     return s[i];
 }
 
-__device__ __forceinline__ bool term_eval(const float* s, int obs_dim, int fn) {
+// `forms`: the model's tables for the parametric forms (HIPETS_TERM_BOX here, HIPETS_REW_TERMS below); the shape-specialised instances,
+// whose fn is a compile-time enum, pass none
+__device__ __forceinline__ bool term_eval(const float* s, int obs_dim, int fn, const FormTables* forms = nullptr) {
     switch (fn) {
+        case HIPETS_TERM_BOX: {  // include/hipets.h: every interval test holds, and (require_finite) every dim is finite; a NaN fails every test
+            bool ok = true;
+            if (forms->require_finite)
+                for (int d = 0; d < obs_dim; ++d) ok = ok && isfinite(s[d]);
+            const int n = forms->n_intervals;
+            for (int k = 0; k < n; ++k) {  // (table address and k are wave-uniform)
+                const hipets_term_interval iv = forms->intervals[k];
+                const float x = s[iv.dim];
+                ok = ok && ((iv.flags & HIPETS_BOX_LO_OPEN) ? x > iv.lo : x >= iv.lo) && ((iv.flags & HIPETS_BOX_HI_OPEN) ? x < iv.hi : x <= iv.hi);
+            }
+            return !ok;
+        }
         case HIPETS_TERM_CARTPOLE: {  // termination_fns.py:29-44
             const float x = s[0], th = s[2], thr = (float)(12.0 * 2.0 * 3.14159265358979323846 / 360.0);
             return !((x > -2.4f) && (x < 2.4f) && (th > -thr) && (th < thr));
@@ -73,9 +88,22 @@ __device__ __forceinline__ bool term_eval(const float* s, int obs_dim, int fn) {
     }
 }
 
+// (HIPETS_REW_TERMS: without the alive bonus, which needs the step's `done`: reward_alive_bonus below)
 __device__ __forceinline__ float reward_eval(const float* s, const float* a, int obs_dim, int act_dim, int fn,
-                                             float learned) {
+                                             float learned, const FormTables* forms = nullptr) {
     switch (fn) {
+        case HIPETS_REW_TERMS: {  // include/hipets.h: bias + sum_k w_k f_k(e_k), accumulated in table order (fp32, no contraction)
+            float r = forms->bias;
+            const int n = forms->n_terms;
+            for (int k = 0; k < n; ++k) {  // (table address and k are wave-uniform)
+                const hipets_reward_term tm = forms->terms[k];
+                const float* v = tm.source == HIPETS_TERM_SRC_ACT ? a : s;
+                const float e = v[tm.i] - (tm.j >= 0 ? v[tm.j] : tm.c);
+                const float f = tm.fn == HIPETS_TERM_FN_SQUARE ? e * e : (tm.fn == HIPETS_TERM_FN_ABS ? fabsf(e) : e);
+                r = r + tm.w * f;
+            }
+            return r;
+        }
         case HIPETS_REW_CARTPOLE: return term_eval(s, obs_dim, HIPETS_TERM_CARTPOLE) ? 0.0f : 1.0f;  // reward_fns.py:10-13
         case HIPETS_REW_INVERTED_PENDULUM: return term_eval(s, obs_dim, HIPETS_TERM_INVERTED_PENDULUM) ? 0.0f : 1.0f;
         case HIPETS_REW_CARTPOLE_PETS: {  // :16-24
@@ -103,6 +131,13 @@ __device__ __forceinline__ float reward_eval(const float* s, const float* a, int
         case HIPETS_REW_NONE: return 0.0f;  // the caller evaluates its own reward_fn on the returned next_obs
         default: return learned;  // model_env.py:124-128 with reward_fn None
     }
+}
+
+// HIPETS_REW_TERMS, last op: + alive_bonus * (1 - done) with the step's own termination test (reward_fns.cartpole: (~termination_fn).float());
+// a zero bonus adds nothing, so a non-finite sum keeps its bits
+__device__ __forceinline__ float reward_alive_bonus(const float r, const bool done, const FormTables* forms) {
+    const float bonus = forms->alive_bonus;
+    return bonus != 0.0f ? r + bonus * (done ? 0.0f : 1.0f) : r;
 }
 
 // the 4 standard normals of (row, step, dim block): counter = (row, step, block, stream), key = seed

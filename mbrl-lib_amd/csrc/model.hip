@@ -7,6 +7,56 @@
 
 using namespace hipets;
 
+namespace {
+
+// The parametric closed forms of the descriptor (include/hipets.h HIPETS_REW_TERMS / HIPETS_TERM_BOX), checked entry by entry and laid
+// out as the kernels read them (all zero: the model has neither).
+int read_form_tables(const hipets_model_desc* d, FormTables* ft) {
+    const bool terms = d->reward_fn == HIPETS_REW_TERMS, box = d->termination_fn == HIPETS_TERM_BOX;
+    if (d->reward_fn < HIPETS_REW_LEARNED || d->reward_fn > HIPETS_REW_TERMS) return fail("unknown reward_fn %d", d->reward_fn);
+    if (d->termination_fn < HIPETS_TERM_NONE || d->termination_fn > HIPETS_TERM_BOX) return fail("unknown termination_fn %d", d->termination_fn);
+    if (!terms && (d->reward_terms || d->n_reward_terms || d->reward_bias != 0.0f || d->alive_bonus != 0.0f))
+        return fail("reward_terms / n_reward_terms / reward_bias / alive_bonus are set but reward_fn %d is not HIPETS_REW_TERMS", d->reward_fn);
+    if (!box && (d->term_intervals || d->n_term_intervals || d->term_require_finite))
+        return fail("term_intervals / n_term_intervals / term_require_finite are set but termination_fn %d is not HIPETS_TERM_BOX", d->termination_fn);
+    if (terms) {
+        if (d->n_reward_terms < 0 || d->n_reward_terms > HIPETS_MAX_REWARD_TERMS)
+            return fail("n_reward_terms %d outside [0, %d]", d->n_reward_terms, HIPETS_MAX_REWARD_TERMS);
+        if (d->n_reward_terms > 0 && !d->reward_terms) return fail("reward_fn TERMS: reward_terms is null for n_reward_terms %d", d->n_reward_terms);
+        if (d->alive_bonus != 0.0f && d->termination_fn == HIPETS_TERM_NONE) return fail("alive_bonus %g needs a termination_fn other than NONE", (double)d->alive_bonus);
+        for (int k = 0; k < d->n_reward_terms; ++k) {
+            const hipets_reward_term& t = d->reward_terms[k];
+            if (t.fn != HIPETS_TERM_FN_LINEAR && t.fn != HIPETS_TERM_FN_SQUARE && t.fn != HIPETS_TERM_FN_ABS) return fail("reward term %d: unknown fn %d", k, t.fn);
+            if (t.source != HIPETS_TERM_SRC_OBS && t.source != HIPETS_TERM_SRC_ACT) return fail("reward term %d: unknown source %d", k, t.source);
+            const int width = t.source == HIPETS_TERM_SRC_ACT ? d->act_dim : d->obs_dim;
+            if (t.i < 0 || t.i >= width) return fail("reward term %d: dim i = %d outside [0, %d)", k, t.i, width);
+            if (t.j >= width) return fail("reward term %d: dim j = %d outside [0, %d)", k, t.j, width);
+            ft->terms[k] = t;
+            if (t.j < 0) ft->terms[k].j = -1;
+        }
+        ft->n_terms = d->n_reward_terms;
+        ft->bias = d->reward_bias;
+        ft->alive_bonus = d->alive_bonus;
+    }
+    if (box) {
+        if (d->n_term_intervals < 0 || d->n_term_intervals > HIPETS_MAX_TERM_INTERVALS)
+            return fail("n_term_intervals %d outside [0, %d]", d->n_term_intervals, HIPETS_MAX_TERM_INTERVALS);
+        if (d->n_term_intervals > 0 && !d->term_intervals) return fail("termination_fn BOX: term_intervals is null for n_term_intervals %d", d->n_term_intervals);
+        for (int k = 0; k < d->n_term_intervals; ++k) {
+            const hipets_term_interval& iv = d->term_intervals[k];
+            if (iv.dim < 0 || iv.dim >= d->obs_dim) return fail("term interval %d: dim %d outside [0, %d)", k, iv.dim, d->obs_dim);
+            if (iv.flags & ~(HIPETS_BOX_LO_OPEN | HIPETS_BOX_HI_OPEN)) return fail("term interval %d: unknown flags 0x%x", k, (unsigned)iv.flags);
+            if (!(iv.lo <= iv.hi)) return fail("term interval %d: lo %g is not <= hi %g", k, (double)iv.lo, (double)iv.hi);
+            ft->intervals[k] = iv;
+        }
+        ft->n_intervals = d->n_term_intervals;
+        ft->require_finite = d->term_require_finite ? 1 : 0;
+    }
+    return 0;
+}
+
+}  // namespace
+
 extern "C" {
 
 int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream) {
@@ -36,6 +86,8 @@ int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream)
     if (d->normalizer != HIPETS_NORM_NONE && (!d->norm_mean || !d->norm_std)) return fail("normalizer stats missing");
     for (int i = 0; i < d->n_members; ++i)
         if (d->members[i] < 0 || d->members[i] >= d->ensemble_size) return fail("member index %d out of range", d->members[i]);
+    FormTables forms{};
+    if (read_form_tables(d, &forms)) return 1;
 
     ModelDev md{};
     md.obs_dim = d->obs_dim; md.act_dim = d->act_dim; md.in_dim = d->in_dim; md.out_dim = d->out_dim;
@@ -115,8 +167,11 @@ int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream)
     if (e->bpack.ensure((size_t)md.bmember * md.M * 4)) return 1;
     if (e->members.ensure((size_t)md.M * 4)) return 1;
     HCHECK(hipMemcpyAsync(e->members.p, d->members, (size_t)md.M * 4, hipMemcpyHostToDevice, st));
-    if (e->layer_meta.ensure(sizeof(LayerMeta) * d->n_layers)) return 1;
+    // one block: the layer table, then the tables of the parametric closed forms (rollout_types.hpp form_tables)
+    static_assert(sizeof(LayerMeta) % alignof(FormTables) == 0, "FormTables follow the layer table");
+    if (e->layer_meta.ensure(sizeof(LayerMeta) * d->n_layers + sizeof(FormTables))) return 1;
     HCHECK(hipMemcpyAsync(e->layer_meta.p, lms.data(), sizeof(LayerMeta) * d->n_layers, hipMemcpyHostToDevice, st));
+    HCHECK(hipMemcpyAsync(e->layer_meta.as<char>() + sizeof(LayerMeta) * d->n_layers, &forms, sizeof(FormTables), hipMemcpyHostToDevice, st));
     for (int l = 0; l < d->n_layers; ++l) {
         const float* w = reinterpret_cast<const float*>(d->weights[l]);
         const float* b = reinterpret_cast<const float*>(d->biases[l]);

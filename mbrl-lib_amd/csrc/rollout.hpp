@@ -1292,16 +1292,21 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
             for (int s = tid; s < ROWS; s += kThreads) {
                 const int rid = sm.rowid[s];
                 if (rid >= 0) {
-                    const float* st = sm.state + s * md.obs_dim;
-                    const float* ac = sm.actn + (t & 1) * ROWS * md.act_dim + s * md.act_dim;
+                    int so = s;  // (generic instances: the row's state / action addresses are formed here, every step -- as loop invariants they
+                    if constexpr (!kLean) asm volatile("" : "+v"(so));  // were carried through the layer loops, where no register is free)
+                    const float* st = sm.state + so * md.obs_dim;
+                    const float* ac = sm.actn + (t & 1) * ROWS * md.act_dim + so * md.act_dim;
                     float tot = sm.tot[s];
                     int trm = sm.term[s];
                     if (persist && sm.pend[s]) {  // collected late
                         sm.pend[s] = 0;
                         fetch_late_total(rid, t, tot, trm);
                     }
-                    float r = reward_eval(st, ac, md.obs_dim, md.act_dim, reward_fn, sm.lrew[s]);
-                    const bool done = term_eval(st, md.obs_dim, term_fn);
+                    const FormTables* forms = kLean ? nullptr : form_tables(md);  // (read only by the parametric forms, which a lean instance never has)
+                    if constexpr (!kLean) asm volatile("" : "+s"(forms));  // (likewise: the table address and what is loaded through it stay inside the step)
+                    float r = reward_eval(st, ac, md.obs_dim, md.act_dim, reward_fn, sm.lrew[s], forms);
+                    const bool done = term_eval(st, md.obs_dim, term_fn, forms);
+                    if (reward_fn == HIPETS_REW_TERMS) r = reward_alive_bonus(r, done, forms);
                     if (trace_rewards) trace_rewards[(size_t)t * ra.B + rid] = r;
                     end_step_for_row(s, rid, tot, trm, r, done, handover, (unsigned)(handover_tag >> 32));
                 }

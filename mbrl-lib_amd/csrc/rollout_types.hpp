@@ -39,13 +39,25 @@ struct Extras {  // up to kMaxExtras leftover (column tile, row tile) units of o
     int c0, c1, c2, c3, r0, r1, r2, r3;
 };
 
+// The parametric closed forms of a model (include/hipets.h HIPETS_REW_TERMS / HIPETS_TERM_BOX), as hipets_set_model leaves them in
+// engine-owned device memory: one block, read with plain loads at wave-uniform addresses by the one thread per row that evaluates
+// reward and termination in the non-lean tail (closed_forms.hpp).  Never staged in LDS: the LDS layout does not know them.
+struct FormTables {
+    int n_terms, n_intervals, require_finite;
+    float bias, alive_bonus;
+    int pad_[3];
+    hipets_reward_term terms[HIPETS_MAX_REWARD_TERMS];
+    hipets_term_interval intervals[HIPETS_MAX_TERM_INTERVALS];
+};
+
 struct ModelDev {
     int obs_dim, act_dim, in_dim, out_dim, out_total, hid, n_layers, M;
     int obs_in;  // width of obs_process_fn(obs) = in_dim - act_dim
     int activation;
     float slope;
     int propagation, deterministic, obs_process, reward_fn, term_fn, target_is_delta, learned_rewards, normalizer;
-    const LayerMeta* layers;  // DEVICE [n_layers] (a table in memory: runtime-indexed kernargs would go to scratch)
+    const LayerMeta* layers;  // DEVICE [n_layers] (a table in memory: runtime-indexed kernargs would go to scratch), followed by the model's
+                              // FormTables where reward_fn is HIPETS_REW_TERMS or term_fn HIPETS_TERM_BOX (form_tables below)
     int Kp0;                  // padded input width of layer 0
     int hidC;                 // column tiles of a hidden layer (cost model; shape of the lean kernel instances)
     int outC;                 // column tiles of the output layer
@@ -66,6 +78,12 @@ struct ModelDev {
     long long w3member;       // 16-byte units per member (bf16 planes: three in bf16x3, one in bf16)
     const uint4* w3;          // packed bf16 planes: [member][layer][col tile][k chunk of 32][plane 0..NP-1][lane][8 x bf16]
 };
+
+// The model's FormTables: hipets_set_model stores them right behind the layer table, in the same device block.  (No pointer of their own
+// in ModelDev: the kernel-argument layout of every rollout-kernel instance stays what it was.)
+__host__ __device__ __forceinline__ const FormTables* form_tables(const ModelDev& md) {
+    return reinterpret_cast<const FormTables*>(md.layers + md.n_layers);
+}
 
 struct RolloutArgs {
     int pop, P, H, B;

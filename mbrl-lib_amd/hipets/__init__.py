@@ -6,8 +6,12 @@ Public names follow mbrl-lib so the stock Hydra configs only swap ``_target_``:
 """
 from ._lib import ERR_INVALID_ARGUMENT, ERR_NONE, ERR_RUNTIME, ERR_TIMEOUT, HipetsError, LIB_PATH  # noqa: F401
 from .model import (  # noqa: F401
+    BoxTermination,
+    Interval,
     ModelSpec,
     PlaNetSpec,
+    RewardTerm,
+    RewardTerms,
     UnsupportedModelError,
     model_version,
     spec_from_checkpoint,

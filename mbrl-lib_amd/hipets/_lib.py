@@ -9,20 +9,34 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # HIPETS_LIB selects another build of the SAME library (kernel-variant experiments under profiles/); there is no fallback
 LIB_PATH = os.environ.get("HIPETS_LIB") or os.path.join(_HERE, "libhipets.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 MAX_LAYERS = 8
 
 ACT = {"relu": 0, "silu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4}
 PROP = {"random_model": 0, "fixed_model": 1, "expectation": 2}
 OBS = {"none": 0, "halfcheetah": 1, "cartpole_pets": 2}
-REW = {None: 0, "learned": 0, "cartpole": 1, "cartpole_pets": 2, "inverted_pendulum": 3, "halfcheetah": 4, "pusher": 5, "none": 6}
-TERM = {"no_termination": 0, "cartpole": 1, "inverted_pendulum": 2, "hopper": 3, "walker2d": 4, "ant": 5, "humanoid": 6}
+REW = {None: 0, "learned": 0, "cartpole": 1, "cartpole_pets": 2, "inverted_pendulum": 3, "halfcheetah": 4, "pusher": 5, "none": 6,
+       "terms": 7}  # (terms: a hipets.RewardTerms table, HIPETS_REW_TERMS)
+TERM = {"no_termination": 0, "cartpole": 1, "inverted_pendulum": 2, "hopper": 3, "walker2d": 4, "ant": 5, "humanoid": 6,
+        "box": 7}  # (box: a hipets.BoxTermination, HIPETS_TERM_BOX)
 NORM = {"none": 0, "f32": 1, "f64": 2}
 ENSEMBLE = {"gaussian_mlp": 0, "basic_ensemble": 1}
 PREC = {"f32": 0, "bf16x3": 1, "bf16": 2}
 MODE_EXACT, MODE_FAST, MODE_DEVICE = 0, 1, 2
 MODES = {"exact": MODE_EXACT, "fast": MODE_FAST, "device": MODE_DEVICE}
+TERM_FN = {"linear": 0, "square": 1, "abs": 2}  # HIPETS_TERM_FN_*
+TERM_SRC = {"obs": 0, "act": 1}  # HIPETS_TERM_SRC_*
+BOX_LO_OPEN, BOX_HI_OPEN = 1, 2  # hipets_term_interval.flags
+MAX_REWARD_TERMS, MAX_TERM_INTERVALS = 64, 64
 KERNEL_CLASSES = ("generic", "hidden_static", "fused", "wide", "bf16")  # HIPETS_KERNEL_*
+
+
+class RewardTermC(C.Structure):  # hipets_reward_term
+    _fields_ = [("fn", C.c_int32), ("source", C.c_int32), ("i", C.c_int32), ("j", C.c_int32), ("c", C.c_float), ("w", C.c_float)]
+
+
+class TermIntervalC(C.Structure):  # hipets_term_interval
+    _fields_ = [("dim", C.c_int32), ("flags", C.c_int32), ("lo", C.c_float), ("hi", C.c_float)]
 
 
 class ModelDesc(C.Structure):
@@ -39,6 +53,9 @@ class ModelDesc(C.Structure):
         ("weights", C.POINTER(C.c_void_p)), ("biases", C.POINTER(C.c_void_p)),
         ("ensemble_kind", C.c_int32),
         ("precision", C.c_int32),
+        ("reward_terms", C.POINTER(RewardTermC)), ("term_intervals", C.POINTER(TermIntervalC)),
+        ("n_reward_terms", C.c_int32), ("n_term_intervals", C.c_int32),
+        ("reward_bias", C.c_float), ("alive_bonus", C.c_float), ("term_require_finite", C.c_int32),
     ]
 
 

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import CemParams, HipetsError, ModelDesc, PlanTrace, RolloutOpts, TrainDesc
-from .model import ModelSpec
+from .model import BoxTermination, ModelSpec, RewardTerms
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -102,8 +102,27 @@ class Engine:
         d.propagation = _lib.PROP[spec.propagation]
         d.deterministic = int(spec.deterministic)
         d.obs_process = _lib.OBS[spec.obs_process]
-        d.reward_fn = _lib.REW[spec.reward]
-        d.termination_fn = _lib.TERM[spec.termination]
+        keep = []  # the ctypes tables of the parametric forms: alive until the call has copied them
+        if isinstance(spec.reward, RewardTerms):
+            rt = spec.reward
+            terms = (_lib.RewardTermC * max(1, len(rt.terms)))(*[
+                _lib.RewardTermC(_lib.TERM_FN[t.fn], _lib.TERM_SRC[t.source], int(t.i), -1 if t.j is None else int(t.j), float(t.c), float(t.w))
+                for t in rt.terms])
+            keep.append(terms)
+            d.reward_fn, d.reward_terms, d.n_reward_terms = _lib.REW["terms"], terms, len(rt.terms)
+            d.reward_bias, d.alive_bonus = rt.bias, rt.alive_bonus
+        else:
+            d.reward_fn = _lib.REW[spec.reward]
+        if isinstance(spec.termination, BoxTermination):
+            box = spec.termination
+            ivs = (_lib.TermIntervalC * max(1, len(box.intervals)))(*[
+                _lib.TermIntervalC(int(iv.dim), (_lib.BOX_LO_OPEN if iv.lo_open else 0) | (_lib.BOX_HI_OPEN if iv.hi_open else 0), float(iv.lo), float(iv.hi))
+                for iv in box.intervals])
+            keep.append(ivs)
+            d.termination_fn, d.term_intervals, d.n_term_intervals = _lib.TERM["box"], ivs, len(box.intervals)
+            d.term_require_finite = int(box.require_finite)
+        else:
+            d.termination_fn = _lib.TERM[spec.termination]
         d.target_is_delta = int(spec.target_is_delta)
         d.learned_rewards = int(spec.learned_rewards)
         nd = [int(i) for i in spec.no_delta_list]
@@ -134,6 +153,7 @@ class Engine:
         d.weights, d.biases = w_arr, b_arr
         with torch.cuda.device(dev):
             _lib.check(self._lib.hipets_set_model(self._h, C.byref(d), _stream(dev)))
+        del keep
         self.spec = spec
 
     # ---- ModelEnv.evaluate_action_sequences ------------------------------------------------------

@@ -10,11 +10,14 @@ the reference path instead of silently approximating.
 """
 from __future__ import annotations
 
+import math
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 import torch
+
+from ._lib import MAX_REWARD_TERMS, MAX_TERM_INTERVALS
 
 
 class UnsupportedModelError(ValueError):
@@ -24,6 +27,126 @@ class UnsupportedModelError(ValueError):
 _ACT_BY_CLASS = {"SiLU": "silu", "ReLU": "relu", "LeakyReLU": "leaky_relu", "Tanh": "tanh", "Sigmoid": "sigmoid"}
 _KNOWN_REWARDS = ("cartpole", "cartpole_pets", "inverted_pendulum", "halfcheetah", "pusher", "none")
 _KNOWN_TERMS = ("no_termination", "cartpole", "inverted_pendulum", "hopper", "walker2d", "ant", "humanoid")
+
+
+# ---------------------------------------------------------------------------------------------
+# Parametric closed forms: rewards and terminations of environments mbrl.env does not ship
+# (include/hipets.h HIPETS_REW_TERMS / HIPETS_TERM_BOX).  Torch callables with the reference's signature
+# ``(act, next_obs) -> [B, 1]``: one object is the reward_fn / termination_fn of a stock ``mbrl.models.ModelEnv``, the
+# callable of the unfused path, the oracle of a test, and -- as ``ModelSpec.reward`` / ``.termination`` -- what the fused
+# kernels evaluate, op by op in the same order in fp32.
+# ---------------------------------------------------------------------------------------------
+@dataclass(frozen=True)
+class Interval:
+    """One test of a healthy box: ``lo <= s'[dim] <= hi``, each bound strict when its ``*_open`` flag is set; ``-inf`` /
+    ``inf`` = no bound on that side.  A NaN fails it."""
+
+    dim: int
+    lo: float = -math.inf
+    hi: float = math.inf
+    lo_open: bool = False
+    hi_open: bool = False
+
+
+@dataclass(frozen=True)
+class RewardTerm:
+    """One term ``w * f(e)`` of a reward table: ``e = v[i] - (v[j] if j is not None else c)`` with ``v`` the step's
+    ``next_obs`` (``source='obs'``) or its action (``'act'``); ``fn``: ``'linear'`` (e), ``'square'`` (e * e) or ``'abs'``."""
+
+    fn: str
+    i: int
+    w: float = 1.0
+    j: Optional[int] = None
+    c: float = 0.0
+    source: str = "obs"
+
+
+TERM_FNS = ("linear", "square", "abs")  # HIPETS_TERM_FN_*
+TERM_SOURCES = ("obs", "act")  # HIPETS_TERM_SRC_*
+
+
+@dataclass(frozen=True)
+class BoxTermination:
+    """``termination_fn`` of a "healthy box": a row is healthy iff every :class:`Interval` test holds and, with
+    ``require_finite``, all of its observation dims are finite; ``done = ~healthy``.  Restates mbrl.env.termination_fns'
+    cartpole, inverted_pendulum, hopper, walker2d and ant exactly; humanoid on finite rows only (the reference's humanoid
+    leaves a NaN row alive, a box ends it).  At most 64 intervals."""
+
+    intervals: Tuple[Interval, ...] = ()
+    require_finite: bool = False
+
+    def __post_init__(self):
+        object.__setattr__(self, "intervals", tuple(iv if isinstance(iv, Interval) else Interval(*iv) for iv in self.intervals))
+        object.__setattr__(self, "require_finite", bool(self.require_finite))
+        self.validate()
+
+    def validate(self, obs_dim: Optional[int] = None):
+        if len(self.intervals) > MAX_TERM_INTERVALS:
+            raise UnsupportedModelError(f"BoxTermination: {len(self.intervals)} intervals, at most {MAX_TERM_INTERVALS}")
+        for k, iv in enumerate(self.intervals):
+            if int(iv.dim) != iv.dim or iv.dim < 0 or (obs_dim is not None and iv.dim >= obs_dim):
+                raise UnsupportedModelError(f"BoxTermination interval {k}: dim {iv.dim} outside [0, {obs_dim if obs_dim is not None else 'obs_dim'})")
+            if not float(iv.lo) <= float(iv.hi):
+                raise UnsupportedModelError(f"BoxTermination interval {k}: lo {iv.lo} is not <= hi {iv.hi}")
+
+    def __call__(self, act: torch.Tensor, next_obs: torch.Tensor) -> torch.Tensor:
+        s = next_obs.float()
+        ok = torch.isfinite(s).all(-1) if self.require_finite else torch.ones(len(s), dtype=torch.bool, device=s.device)
+        for iv in self.intervals:
+            x = s[:, iv.dim]
+            ok = ok & ((x > iv.lo) if iv.lo_open else (x >= iv.lo)) & ((x < iv.hi) if iv.hi_open else (x <= iv.hi))
+        return (~ok)[:, None]
+
+
+@dataclass(frozen=True)
+class RewardTerms:
+    """``reward_fn`` as a term table: ``r = bias + sum_k w_k f_k(e_k) [+ alive_bonus * (1 - done)]``, accumulated in table
+    order in fp32 starting from ``bias`` (:class:`RewardTerm`); the alive bonus is added last and only when it is non-zero,
+    with ``done = termination_fn(act, next_obs)`` -- the step's own termination test, which must then be the
+    :class:`BoxTermination` the model terminates with (``mbrl.env.reward_fns.cartpole`` is ``alive_bonus=1`` over the
+    cartpole box).  NaN and inf propagate as IEEE arithmetic does.  At most 64 terms."""
+
+    terms: Tuple[RewardTerm, ...] = ()
+    bias: float = 0.0
+    alive_bonus: float = 0.0
+    termination_fn: Optional[BoxTermination] = None
+
+    def __post_init__(self):
+        object.__setattr__(self, "terms", tuple(t if isinstance(t, RewardTerm) else RewardTerm(*t) for t in self.terms))
+        object.__setattr__(self, "bias", float(self.bias))
+        object.__setattr__(self, "alive_bonus", float(self.alive_bonus))
+        self.validate()
+
+    def validate(self, obs_dim: Optional[int] = None, act_dim: Optional[int] = None):
+        if len(self.terms) > MAX_REWARD_TERMS:
+            raise UnsupportedModelError(f"RewardTerms: {len(self.terms)} terms, at most {MAX_REWARD_TERMS}")
+        for k, t in enumerate(self.terms):
+            if t.fn not in TERM_FNS:
+                raise UnsupportedModelError(f"RewardTerms term {k}: fn {t.fn!r} is not one of {TERM_FNS}")
+            if t.source not in TERM_SOURCES:
+                raise UnsupportedModelError(f"RewardTerms term {k}: source {t.source!r} is not one of {TERM_SOURCES}")
+            width = act_dim if t.source == "act" else obs_dim
+            for name, v in (("i", t.i), ("j", t.j)):
+                if v is None and name == "j":
+                    continue
+                if v is None or int(v) != v or v < 0 or (width is not None and v >= width):
+                    raise UnsupportedModelError(f"RewardTerms term {k}: dim {name} = {v} outside [0, {width if width is not None else t.source + '_dim'})")
+        if self.alive_bonus != 0.0 and not isinstance(self.termination_fn, BoxTermination):
+            raise UnsupportedModelError("RewardTerms: alive_bonus != 0 needs termination_fn=BoxTermination(...), the model's own termination")
+        if self.termination_fn is not None and isinstance(self.termination_fn, BoxTermination):
+            self.termination_fn.validate(obs_dim)
+
+    def __call__(self, act: torch.Tensor, next_obs: torch.Tensor) -> torch.Tensor:
+        s, a = next_obs.float(), act.float()
+        r = torch.full((len(s),), self.bias, dtype=torch.float32, device=s.device)
+        for t in self.terms:
+            v = a if t.source == "act" else s
+            e = v[:, t.i] - (v[:, t.j] if t.j is not None else t.c)
+            f = e * e if t.fn == "square" else (e.abs() if t.fn == "abs" else e)
+            r = r + t.w * f
+        if self.alive_bonus != 0.0:
+            r = r + self.alive_bonus * (~self.termination_fn(act, next_obs))[:, 0].float()
+        return r.view(-1, 1)
 
 
 @dataclass
@@ -45,8 +168,9 @@ class ModelSpec:
     no_delta_list: Sequence[int] = field(default_factory=list)
     learned_rewards: bool = False
     obs_process: str = "none"
-    reward: Optional[str] = "halfcheetah"  # None => learned reward (last model output); "none" => caller's callable
-    termination: str = "no_termination"
+    # None => learned reward (last model output); "none" => caller's callable; a RewardTerms => the model's own term table
+    reward: Union[str, None, RewardTerms] = "halfcheetah"
+    termination: Union[str, BoxTermination] = "no_termination"  # (a BoxTermination => the model's own healthy box)
     custom_reward_fn: Optional[object] = None  # arbitrary torch callables (act, next_obs) -> [B,1]; UNFUSED path only
     custom_termination_fn: Optional[object] = None
     # "gaussian_mlp": one GaussianMLP with E members (balanced shuffles, batch % members rule, elites).
@@ -99,12 +223,20 @@ class ModelSpec:
             raise UnsupportedModelError(f"activation {self.activation!r} has no fused implementation")
         if self.propagation not in ("random_model", "fixed_model", "expectation"):
             raise ValueError(f"Invalid propagation method {self.propagation}.")  # gaussian_mlp.py:216
-        if self.reward is not None and self.reward not in _KNOWN_REWARDS:
+        if isinstance(self.termination, BoxTermination):
+            self.termination.validate(self.obs_dim)
+        elif self.termination not in _KNOWN_TERMS:
+            raise UnsupportedModelError(f"termination_fn {self.termination!r} has no fused implementation")
+        if isinstance(self.reward, RewardTerms):
+            self.reward.validate(self.obs_dim, self.act_dim)
+            # the kernel's alive bonus uses the step's own `done`: the table's termination_fn must BE the model's termination
+            if self.reward.alive_bonus != 0.0 and not (isinstance(self.termination, BoxTermination) and self.reward.termination_fn == self.termination):
+                raise UnsupportedModelError("RewardTerms.alive_bonus != 0 needs RewardTerms.termination_fn to equal the model's termination "
+                                            "(a BoxTermination)")
+        elif self.reward is not None and self.reward not in _KNOWN_REWARDS:
             raise UnsupportedModelError(f"reward_fn {self.reward!r} has no fused implementation")
         if self.reward is None and not self.learned_rewards:
             raise UnsupportedModelError("reward_fn is None but the model does not learn rewards")
-        if self.termination not in _KNOWN_TERMS:
-            raise UnsupportedModelError(f"termination_fn {self.termination!r} has no fused implementation")
         if self.obs_process not in ("none", "halfcheetah", "cartpole_pets"):
             raise UnsupportedModelError(f"obs_process_fn {self.obs_process!r} has no fused implementation")
         if len(self.weights) < 2 or len(self.weights) > 8:
@@ -217,16 +349,19 @@ def spec_from_model_env(model_env, obs_dim: Optional[int] = None, act_dim: Optio
     rew, term = model_env.reward_fn, model_env.termination_fn
     # model_env.py:124-128: a reward_fn that is not None ALWAYS wins over the learned reward, so an unrecognised callable
     # is never mapped to "learned" -- it is either kept for the unfused path or rejected
-    rew_name = None if rew is None else _closed_form(rew, "reward", _KNOWN_REWARDS)
-    term_name = _closed_form(term, "termination", _KNOWN_TERMS)
+    # (the parametric forms are recognised by type and enter the spec as themselves: the fused kernels evaluate their tables)
+    rew_name = None if rew is None else (rew if isinstance(rew, RewardTerms) else _closed_form(rew, "reward", _KNOWN_REWARDS))
+    term_name = term if isinstance(term, BoxTermination) else _closed_form(term, "termination", _KNOWN_TERMS)
     custom_rew = custom_term = None
     if rew is not None and rew_name is None:
         if not allow_custom_fns:
-            raise UnsupportedModelError(f"reward_fn {getattr(rew, '__qualname__', rew)!r} is not one of mbrl.env.reward_fns' closed forms")
+            raise UnsupportedModelError(f"reward_fn {getattr(rew, '__qualname__', rew)!r} is not one of mbrl.env.reward_fns' closed forms "
+                                        "(a sum of linear / square / abs terms runs fused as a hipets.RewardTerms)")
         custom_rew, rew_name = rew, "none"
     if term_name is None:
         if not allow_custom_fns:
-            raise UnsupportedModelError(f"termination_fn {getattr(term, '__qualname__', term)!r} is not one of mbrl.env.termination_fns' closed forms")
+            raise UnsupportedModelError(f"termination_fn {getattr(term, '__qualname__', term)!r} is not one of mbrl.env.termination_fns' closed forms "
+                                        "(interval tests on state dims run fused as a hipets.BoxTermination)")
         custom_term, term_name = term, "no_termination"
     spec = ModelSpec(
         weights=ws, biases=bs, obs_dim=od, act_dim=ad,
