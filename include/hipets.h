@@ -619,8 +619,11 @@ int hipets_train_steps(hipets_engine* e, const hipets_train_desc* d, const float
 /* ModelTrainer.evaluate over a whole dataset (GaussianMLP.eval_score, gaussian_mlp.py:337-361, averaged over rows and dims):
  * score DEVICE f32 [E] = mean over the n_rows rows and out_dim dims of (mean_e(x) - y)^2, the mean columns only.  order
  * DEVICE int32 [n_rows] or NULL: row r of the pass is dataset row order[r].  row_score DEVICE f32 [E, n_rows] or NULL: the
- * squared error of pass row r summed over dims (per-batch scores for a batch_callback).  Partial sums are reduced in a
- * fixed order: the result is deterministic.  The Adam fields of d are not read.                                          */
+ * squared error of pass row r summed over dims (per-batch scores for a batch_callback).  As in training, an order entry
+ * outside [0, n_rows) is never read out of bounds: that pass row contributes exactly zero to row_score and to the sum,
+ * while the divisor of score stays n_rows * out_dim.  A row's arithmetic does not depend on its position in the pass
+ * (row_score under order = a permutation is the permuted row_score, bit for bit).  Partial sums are reduced in a fixed
+ * order: the result is deterministic.  The Adam fields of d are not read.                                                */
 int hipets_train_eval(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows,
                       const int32_t* order, float* score, float* row_score, void* stream);
 

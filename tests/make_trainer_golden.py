@@ -6,7 +6,12 @@ through oracle.ref_bridge and write tests/golden/trainer_*.npz for tests/test_gp
 Each case: a replay buffer of 517 random transitions, mbrl.util.common.get_basic_buffer_iterators (bootstrap, shuffling),
 a GaussianMLP in a OneDTransitionRewardModel (delta targets, no normaliser), 3 epochs of ModelTrainer.train.  Stored: the
 initial weights, the transitions and the split, every batch's loss and grad_norm, per-epoch losses and validation scores,
-epochs run, final weights, elites, the weights / Adam state / RNG state after epoch 1, and the RNG state afterwards."""
+epochs run, final weights, elites, the weights / Adam state / RNG state after epoch 1, and the RNG state afterwards.
+
+trainer_c_two_calls: the same tiny model trained as a PETS loop trains it, by ONE ModelTrainer on a growing buffer: 300 stored
+transitions, new iterators, 2 epochs; the other 217 added, new iterators, 2 more epochs.  Stored per call: the split, the member
+indices, the RNG states, every batch's loss and grad_norm, per-epoch losses and scores, the weights and elites afterwards; and
+the optimizer's step count at the end."""
 import json
 import os
 import sys
@@ -92,6 +97,66 @@ def record(name, act, val_ratio, patience, seed):
     print(f"{path}: {os.path.getsize(path)} bytes, epochs {len(losses)}, elites {mlp.elite_models}")
 
 
+TWO_CALLS = ("trainer_c_two_calls", "silu", 0.2, 7, (300, N), 2)  # name, activation, validation ratio, seed, stored per call, epochs per call
+
+
+def record_two_calls(name, act, val_ratio, seed, stored, epochs):
+    ref_bridge.import_reference()
+    import mbrl.models as models
+    import mbrl.util.common as common
+    from mbrl.util.replay_buffer import ReplayBuffer
+
+    torch.manual_seed(seed)
+    gen = np.random.default_rng(seed + 100)
+    obs = gen.standard_normal((N, OBS)).astype(np.float32)
+    acts = gen.uniform(-1, 1, (N, ACT)).astype(np.float32)
+    next_obs = (obs + 0.1 * np.tanh(obs @ gen.standard_normal((OBS, OBS)) + acts @ gen.standard_normal((ACT, OBS)))).astype(np.float32)
+    rb = ReplayBuffer(N, (OBS,), (ACT,), rng=np.random.default_rng(seed))
+    row_of = {obs[i].tobytes(): i for i in range(N)}
+    mlp = models.GaussianMLP(OBS + ACT, OBS, "cpu", num_layers=NUM_LAYERS, ensemble_size=E, hid_size=HID,
+                             activation_fn_cfg={"_target_": TARGETS[act]})
+    dm = models.OneDTransitionRewardModel(mlp, target_is_delta=True, normalize=False, learned_rewards=False, num_elites=3)
+    layers = [l[0] for l in mlp.hidden_layers] + [mlp.mean_and_logvar]
+    arrays = dict(obs=obs, act=acts, next_obs=next_obs)
+    for i, l in enumerate(layers):
+        arrays[f"w0_{i}"] = l.weight.detach().numpy().copy()
+        arrays[f"b0_{i}"] = l.bias.detach().numpy().copy()
+    trainer = models.ModelTrainer(dm, optim_lr=LR, weight_decay=WD)  # one trainer (one optimizer) for both calls, as pets.train
+    calls, added = [], 0
+    for c, n_stored in enumerate(stored):
+        for i in range(added, n_stored):
+            rb.add(obs[i], acts[i], next_obs[i], 0.0, False, False)
+        added = n_stored
+        train_it, val_it = common.get_basic_buffer_iterators(rb, BATCH, val_ratio, ensemble_size=E, shuffle_each_epoch=True, bootstrap_permutes=False)
+        m = {"rng_state_after_split": json.dumps(rb.rng.bit_generator.state)}
+        arrays[f"c{c}_train_rows"] = np.array([row_of[o.tobytes()] for o in train_it.transitions.obs], np.int64)
+        arrays[f"c{c}_val_rows"] = np.array([row_of[o.tobytes()] for o in val_it.transitions.obs], np.int64)
+        arrays[f"c{c}_member_indices"] = np.asarray(train_it.member_indices)
+        batches = []
+        losses, scores = trainer.train(train_it, val_it, num_epochs=epochs, patience=None,
+                                       batch_callback=lambda ep, loss, meta, mode: batches.append((float(loss), float(meta["grad_norm"])))
+                                       if mode == "train" else None)
+        m["rng_state_after"] = json.dumps(rb.rng.bit_generator.state)
+        m["epochs_run"] = len(losses)
+        arrays[f"c{c}_batch_losses"] = np.array([b[0] for b in batches])
+        arrays[f"c{c}_batch_grad_norms"] = np.array([b[1] for b in batches])
+        arrays[f"c{c}_train_losses"], arrays[f"c{c}_val_scores"] = np.array(losses), np.array(scores)
+        arrays[f"c{c}_elites"] = np.array(mlp.elite_models, np.int64)
+        for i, l in enumerate(layers):
+            arrays[f"c{c}_w1_{i}"] = l.weight.detach().numpy().copy()
+            arrays[f"c{c}_b1_{i}"] = l.bias.detach().numpy().copy()
+        calls.append(m)
+    sd = trainer.optimizer.state_dict()
+    steps = sorted({float(st["step"]) for st in sd["state"].values()})
+    assert len(steps) == 1
+    meta = dict(E=E, n_layers=NUM_LAYERS + 1, in_dim=OBS + ACT, hid=HID, out=OBS, act=act, num_elites=dm.num_elites, batch_size=BATCH,
+                lr=LR, weight_decay=WD, num_epochs=epochs, patience=None, stored=list(stored), calls=calls, adam_step=steps[0],
+                val_ratio=val_ratio, seed=seed)
+    path = os.path.join(OUT, name + ".npz")
+    np.savez_compressed(path, meta_json=np.frombuffer(json.dumps(meta).encode(), np.uint8), **arrays)
+    print(f"{path}: {os.path.getsize(path)} bytes, Adam step {steps[0]}, elites {mlp.elite_models}")
+
+
 def record_host_cases():
     """train_host_cases.npz: (1) one and two float64 Model.update + torch.optim.Adam steps of a small GaussianMLP for every
     activation; (2) the dataset rows of every batch the reference's iterators yield over 3 epochs, for both bootstrap_permutes
@@ -162,4 +227,5 @@ def record_host_cases():
 if __name__ == "__main__":
     for case in CASES:
         record(*case)
+    record_two_calls(*TWO_CALLS)
     record_host_cases()

@@ -16,54 +16,8 @@ from conftest import GOLDEN
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
-LR, WD = 1e-3, 1e-5
-
-
-def _dist(a, b):
-    return (a.double().cpu() - b.double().cpu()).abs().max().item()
-
-
-def _check(hip, f32, f64, what):
-    d_hip, d_32 = _dist(hip, f64), _dist(f32, f64)
-    assert d_hip <= 4 * d_32 + 1e-7, f"{what}: |hip - f64| = {d_hip:.3e} > 4 |f32 - f64| = {4 * d_32:.3e} + 1e-7"
-
-
-def _state(ws, bs, dtype, device):
-    w = [t.to(device, dtype).clone() for t in ws]
-    b = [t.to(device, dtype).clone() for t in bs]
-    return w, b, ([torch.zeros_like(t) for t in w], [torch.zeros_like(t) for t in b]), ([torch.zeros_like(t) for t in w], [torch.zeros_like(t) for t in b])
-
-
-def _run(engine, E, B, in_dim, hid, out, n_layers, act, n_steps, N=None, seed=0, steps_per_launch=0, ragged_last=False):
-    """n_steps steps on the GPU and in the float32 / float64 restatements; returns the three final states and per-step losses."""
-    g = torch.Generator().manual_seed(seed + 1)
-    N = N or max(3 * B, 64)
-    x = torch.randn(N, in_dim, generator=g, dtype=torch.float64)
-    y = torch.randn(N, out, generator=g, dtype=torch.float64) * 0.3
-    ws, bs = tr.random_model(E, in_dim, hid, out, n_layers, seed)
-    lo, hi = -10 * torch.ones(1, out, dtype=torch.float64), 0.5 * torch.ones(1, out, dtype=torch.float64)
-    lo[0, 0], hi[0, 0] = -2.0, -1.0  # one column whose bounds are active
-    idx = torch.stack([torch.stack([torch.randperm(N, generator=g)[:B] for _ in range(E)]) for _ in range(n_steps)]).to(torch.int32)
-    rows = torch.full((n_steps,), B, dtype=torch.int32)
-    if ragged_last:
-        rows[-1] = max(1, B // 3)
-    res = {}
-    for name, dtype in (("f64", torch.float64), ("f32", torch.float32)):
-        w, b, m, v = _state(ws, bs, dtype, "cpu")
-        losses, gsqs = [], []
-        for s in range(n_steps):
-            sel = idx[s, :, :rows[s]].long()
-            l, gq = tr.train_step(w, b, m, v, x.to(dtype)[sel], y.to(dtype)[sel], lo.to(dtype), hi.to(dtype), act, s + 1, LR, WD)
-            losses.append(l)
-            gsqs.append(gq)
-        res[name] = (w, b, m, v, torch.stack(losses), torch.stack(gsqs))
-    w, b, m, v = _state(ws, bs, torch.float32, DEV)
-    loss, gsq = engine.train_steps(w, b, m, v, lo.float().reshape(-1).to(DEV), hi.float().reshape(-1).to(DEV), x.float().to(DEV),
-                                   y.float().to(DEV), idx.to(DEV), rows.to(DEV), 0, lr=LR, weight_decay=WD, activation=act,
-                                   steps_per_launch=steps_per_launch)
-    torch.cuda.synchronize()
-    res["hip"] = (w, b, m, v, loss, gsq)
-    return res
+LR, WD = tr.LR, tr.WD
+_dist, _check, _state, _run = tr.dist, tr.check, tr.fresh_state, tr.run_steps  # shared with tests/test_gpu_trainer_edges.py
 
 
 SHAPES = {  # (E, B, in, hid, out, n_layers)
@@ -151,7 +105,30 @@ def _setup(meta, arr, device="cpu"):
     return mlp, model, train, val, rng
 
 
-GOLDENS = sorted(glob.glob(os.path.join(GOLDEN, "trainer_*.npz")))
+TWO_CALLS = os.path.join(GOLDEN, "trainer_c_two_calls.npz")  # two train() calls of one trainer: its own layout and tests
+GOLDENS = sorted(p for p in glob.glob(os.path.join(GOLDEN, "trainer_*.npz")) if p != TWO_CALLS)
+
+
+def _setup_two_calls(meta, arr):
+    """The model of tests/golden/trainer_c_two_calls.npz at its initial weights, and iterators(c) -> (train, val, rng) of call c:
+    the reference's split and member indices of that call over the transitions stored by then, the RNG where the reference's
+    stood after building them."""
+    E, L = meta["E"], meta["n_layers"]
+    mlp = tr.TinyGaussianMLP(E, meta["in_dim"], meta["hid"], meta["out"], L, act=meta["act"])
+    tr.load_params(mlp, [arr[f"w0_{i}"] for i in range(L)], [arr[f"b0_{i}"] for i in range(L)])
+    model = tr.TinyDynamicsModel(mlp, num_elites=meta["num_elites"])
+    data = tr.Batch(obs=arr["obs"], act=arr["act"], next_obs=arr["next_obs"])
+
+    def iterators(c):
+        assert max(arr[f"c{c}_train_rows"].max(), arr[f"c{c}_val_rows"].max()) < meta["stored"][c]
+        rng = np.random.default_rng()
+        rng.bit_generator.state = json.loads(meta["calls"][c]["rng_state_after_split"])
+        train = tr.BootstrapIterator(data[arr[f"c{c}_train_rows"]], meta["batch_size"], E, shuffle_each_epoch=True, rng=rng,
+                                     member_indices=arr[f"c{c}_member_indices"])
+        val = tr.TransitionIterator(data[arr[f"c{c}_val_rows"]], meta["batch_size"], shuffle_each_epoch=False, rng=rng)
+        return train, val, rng
+
+    return mlp, model, iterators
 
 
 @pytest.mark.parametrize("path", GOLDENS, ids=[os.path.basename(p) for p in GOLDENS])

@@ -13,7 +13,7 @@ import torch
 import hipets
 import train_restatement as tr
 from conftest import GOLDEN
-from test_gpu_trainer import GOLDENS, _golden, _setup
+from test_gpu_trainer import GOLDENS, TWO_CALLS, _golden, _setup, _setup_two_calls
 
 HOST = os.path.join(GOLDEN, "train_host_cases.npz")
 
@@ -109,6 +109,27 @@ def test_train_host_logic_and_rng_match_reference_trainer(path):
     assert np.allclose(losses, arr["train_losses"], rtol=1e-5) and np.allclose(scores, arr["val_scores"], rtol=1e-5)
     assert sorted(int(i) for i in mlp.elite_models) == sorted(int(i) for i in arr["elites"])
     assert trainer._train_iteration == 1
+
+
+def test_two_train_calls_on_a_growing_buffer_host_logic():
+    """One trainer, two train() calls (300 stored transitions, then 517, new iterators each time: a PETS loop), the device steps
+    replaced by the float32 restatement: Adam's moments and step count carry over, the dataset of the second call replaces the
+    first's, and after each call the RNG, epochs, elites and (to float32 noise) losses and scores are the reference trainer's."""
+    meta, arr = _golden(TWO_CALLS)
+    mlp, model, iterators = _setup_two_calls(meta, arr)
+    trainer = hipets.ModelTrainer(model, optim_lr=meta["lr"], weight_decay=meta["weight_decay"], engine=CpuEngine())
+    for c, m in enumerate(meta["calls"]):
+        train, val, rng = iterators(c)
+        losses, scores = trainer.train(train, val, num_epochs=meta["num_epochs"], patience=meta["patience"])
+        assert json.dumps(rng.bit_generator.state, sort_keys=True) == json.dumps(json.loads(m["rng_state_after"]), sort_keys=True)
+        assert len(losses) == m["epochs_run"]
+        assert np.allclose(losses, arr[f"c{c}_train_losses"], rtol=1e-5) and np.allclose(scores, arr[f"c{c}_val_scores"], rtol=1e-5)
+        assert sorted(int(i) for i in mlp.elite_models) == sorted(int(i) for i in arr[f"c{c}_elites"])
+        for i, lin in enumerate(mlp.layers()):
+            assert np.abs(lin.weight.detach().numpy() - arr[f"c{c}_w1_{i}"]).max() < 2e-5
+        assert trainer._train_iteration == c + 1
+    assert trainer._step == int(meta["adam_step"])
+    assert float(next(iter(trainer.optimizer.state_dict()["state"].values()))["step"]) == meta["adam_step"]
 
 
 def test_optimizer_state_dict_round_trips_through_torch_adam():

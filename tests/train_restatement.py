@@ -8,7 +8,8 @@ written out by hand in torch (no autograd, no torch.optim), in float64 or float3
 plus small stand-ins for the live objects the trainer reads (a GaussianMLP-shaped module in a OneDTransitionRewardModel-shaped
 wrapper, and the replay buffer's two iterators), so the GPU tests run where mbrl is not installed.  The stand-in iterators
 make their random draws in the same calls as mbrl.util.replay_buffer's; tests/test_trainer_host.py checks that against the
-reference where it is available.
+reference where it is available.  At the end: what the GPU trainer tests share (run_steps: the same steps on the GPU and in
+both restatements; check: the self-calibrated rule).
 """
 from __future__ import annotations
 
@@ -262,3 +263,108 @@ def load_params(mlp, ws, bs):
         for lin, w, b in zip(mlp.layers(), ws, bs):
             lin.weight.copy_(torch.as_tensor(w))
             lin.bias.copy_(torch.as_tensor(b))
+
+
+# ---- shared by the GPU trainer tests (tests/test_gpu_trainer.py, tests/test_gpu_trainer_edges.py) ------------------------
+LR, WD = 1e-3, 1e-5
+
+
+def dist(a, b):
+    return (a.double().cpu() - b.double().cpu()).abs().max().item()
+
+
+def check(hip, f32, f64, what, f32_others=()):
+    """The suite's self-calibrated rule: the HIP result may lie at most 4x as far from the float64 restatement as the float32
+    restatement does, plus a 1e-7 floor.  Prints the distances.  f32_others = further float32 restatements in other summation
+    orders: where the float32 orders are themselves further apart than the rule allows (one's distance from float64 is more than
+    4x another's + 1e-7), float32 rounding decides the quantity and the yardstick is the largest of their distances."""
+    d_hip, d_32 = dist(hip, f64), dist(f32, f64)
+    d_all = [d_32] + [dist(t, f64) for t in f32_others]
+    print(f"{what}: |hip - f64| = {d_hip:.3e}, |f32 - f64| = {d_32:.3e}" + "".join(f", other order {d:.3e}" for d in d_all[1:]))
+    if max(d_all) > 4 * min(d_all) + 1e-7:
+        d_32 = max(d_all)
+    assert d_hip <= 4 * d_32 + 1e-7, f"{what}: |hip - f64| = {d_hip:.3e} > 4 |f32 - f64| = {4 * d_32:.3e} + 1e-7"
+
+
+def mirrored(ws, bs):
+    """The same network with its input features and hidden units in reverse order (apply twice to get the original back): with
+    mirrored inputs, every contraction of a step sums the same terms in the other order."""
+    L = len(ws)
+    ws = [w.flip(1, 2) if l < L - 1 else w.flip(1) for l, w in enumerate(ws)]
+    bs = [b.flip(2) if l < L - 1 else b for l, b in enumerate(bs)]
+    return ws, bs
+
+
+def fresh_state(ws, bs, dtype, device):
+    """(weights, biases, exp_avg, exp_avg_sq) copies of a model in ``dtype`` on ``device``, the moments zero."""
+    w = [t.to(device, dtype).clone() for t in ws]
+    b = [t.to(device, dtype).clone() for t in bs]
+    return w, b, ([torch.zeros_like(t) for t in w], [torch.zeros_like(t) for t in b]), ([torch.zeros_like(t) for t in w], [torch.zeros_like(t) for t in b])
+
+
+def run_steps(engine, E, B, in_dim, hid, out, n_layers, act, n_steps, N=None, seed=0, steps_per_launch=0, ragged_last=False, *,
+              bounds=None, edit_params=None, rows=None, edit_idx=None, step0=0, calls=None, restate=True, f32_orders=False, device="cuda:0"):
+    """n_steps steps on the GPU and in the float32 / float64 restatements; returns the three final states and per-step losses
+    ({"hip" | "f32" | "f64": (w, b, m, v, loss [S, E], grad_sq [S, E])}) and, under "inputs", what the run was fed.
+
+    bounds(lo, hi) edits the logvar bounds [1, out] in place; edit_params(ws, bs) the float64 initial parameters; rows is an
+    explicit per-step row count (n_steps = len(rows)); edit_idx(idx) edits the int32 schedule [S, E, B] in place (an index
+    outside [0, N) stands for a row of zeros, in the restatement too); step0 = Adam steps taken before; calls = step counts
+    of consecutive train_steps calls the run is split into; restate=False skips the CPU restatements; f32_orders adds two float32
+    restatements of the same sums in other orders: "f32r" with every minibatch's rows reversed (the contractions over the batch),
+    "f32m" with the rows reversed and the network mirrored (every contraction)."""
+    g = torch.Generator().manual_seed(seed + 1)
+    N = N or max(3 * B, 64)
+    x = torch.randn(N, in_dim, generator=g, dtype=torch.float64)
+    y = torch.randn(N, out, generator=g, dtype=torch.float64) * 0.3
+    ws, bs = random_model(E, in_dim, hid, out, n_layers, seed)
+    if edit_params is not None:
+        edit_params(ws, bs)
+    lo, hi = -10 * torch.ones(1, out, dtype=torch.float64), 0.5 * torch.ones(1, out, dtype=torch.float64)
+    lo[0, 0], hi[0, 0] = -2.0, -1.0  # one column whose bounds are active
+    if bounds is not None:
+        bounds(lo, hi)
+    if rows is not None:
+        n_steps = len(rows)
+    idx = torch.stack([torch.stack([torch.randperm(N, generator=g)[:B] for _ in range(E)]) for _ in range(n_steps)]).to(torch.int32)
+    if edit_idx is not None:
+        edit_idx(idx)
+    if rows is None:
+        rows = torch.full((n_steps,), B, dtype=torch.int32)
+        if ragged_last:
+            rows[-1] = max(1, B // 3)
+    rows = torch.as_tensor(rows, dtype=torch.int32)
+    res = {"inputs": dict(x=x, y=y, ws=ws, bs=bs, lo=lo, hi=hi, idx=idx, rows=rows)}
+    # dataset row N of the restatement is the row of zeros an outside index reads
+    sel_all = torch.where((idx >= 0) & (idx < N), idx.long(), torch.full_like(idx, N, dtype=torch.int64))
+    x0, y0 = torch.cat([x, torch.zeros(1, in_dim, dtype=x.dtype)]), torch.cat([y, torch.zeros(1, out, dtype=y.dtype)])
+    kinds = (("f64", torch.float64), ("f32", torch.float32)) + ((("f32r", torch.float32), ("f32m", torch.float32)) if f32_orders else ())
+    for name, dtype in kinds if restate else ():
+        w, b, m, v = fresh_state(*(mirrored(ws, bs) if name == "f32m" else (ws, bs)), dtype, "cpu")
+        xd, yd = (x0.flip(1) if name == "f32m" else x0).to(dtype), y0.to(dtype)
+        losses, gsqs = [], []
+        for s in range(n_steps):
+            sel = sel_all[s, :, :rows[s]]
+            if name in ("f32r", "f32m"):
+                sel = sel.flip(-1)
+            l, gq = train_step(w, b, m, v, xd[sel], yd[sel], lo.to(dtype), hi.to(dtype), act, step0 + s + 1, LR, WD)
+            losses.append(l)
+            gsqs.append(gq)
+        if name == "f32m":
+            (w, b), m, v = mirrored(w, b), mirrored(*m), mirrored(*v)
+        res[name] = (w, b, m, v, torch.stack(losses), torch.stack(gsqs))
+    w, b, m, v = fresh_state(ws, bs, torch.float32, device)
+    lo_d, hi_d = lo.float().reshape(-1).to(device), hi.float().reshape(-1).to(device)
+    x_d, y_d, idx_d, rows_d = x.float().to(device), y.float().to(device), idx.to(device), rows.to(device)
+    loss, gsq, done = [], [], 0
+    for n in calls or [n_steps]:
+        l, gq = engine.train_steps(w, b, m, v, lo_d, hi_d, x_d, y_d, idx_d[done:done + n].contiguous(), rows_d[done:done + n].contiguous(),
+                                   step0 + done, lr=LR, weight_decay=WD, activation=act, steps_per_launch=steps_per_launch)
+        loss.append(l)
+        gsq.append(gq)
+        done += n
+    assert done == n_steps
+    if device != "cpu":
+        torch.cuda.synchronize()
+    res["hip"] = (w, b, m, v, torch.cat(loss), torch.cat(gsq))
+    return res
