@@ -41,6 +41,7 @@ extern "C" {
 #define HIPETS_MAX_LAYERS 8
 #define HIPETS_MAX_REWARD_TERMS 64   /* entries of a reward term table (HIPETS_REW_TERMS)  */
 #define HIPETS_MAX_TERM_INTERVALS 64 /* interval tests of a healthy box (HIPETS_TERM_BOX)     */
+#define HIPETS_MAX_OBS_COLUMNS 512   /* columns of an observation column table (HIPETS_OBS_COLUMNS) */
 
 typedef struct hipets_engine hipets_engine;
 
@@ -49,7 +50,8 @@ enum { HIPETS_ACT_RELU = 0, HIPETS_ACT_SILU = 1, HIPETS_ACT_LEAKY_RELU = 2, HIPE
 /* Ensemble.propagation_method (mbrl/models/gaussian_mlp.py:201-216) */
 enum { HIPETS_PROP_RANDOM_MODEL = 0, HIPETS_PROP_FIXED_MODEL = 1, HIPETS_PROP_EXPECTATION = 2 };
 /* obs_process_fn (mbrl/env/pets_halfcheetah.py:91-113, mbrl/env/pets_cartpole.py:78-101) */
-enum { HIPETS_OBS_NONE = 0, HIPETS_OBS_HALFCHEETAH = 1, HIPETS_OBS_CARTPOLE_PETS = 2 };
+enum { HIPETS_OBS_NONE = 0, HIPETS_OBS_HALFCHEETAH = 1, HIPETS_OBS_CARTPOLE_PETS = 2,
+       HIPETS_OBS_COLUMNS = 3 /* the model's own column table (hipets_obs_column below, hipets_set_model_columns) */ };
 /* reward_fn (mbrl/env/reward_fns.py:10-53); LEARNED = last model output (model_env.py:124-128) */
 enum { HIPETS_REW_LEARNED = 0, HIPETS_REW_CARTPOLE = 1, HIPETS_REW_CARTPOLE_PETS = 2, HIPETS_REW_INVERTED_PENDULUM = 3,
        HIPETS_REW_HALFCHEETAH = 4, HIPETS_REW_PUSHER = 5,
@@ -119,6 +121,19 @@ typedef struct {
     float lo;       /* lo <= hi; -INFINITY / INFINITY = no bound on that side            */
     float hi;
 } hipets_term_interval;
+
+/* ---- parametric observation preprocessing: obs_process_fn of environments mbrl.env does not ship -----------------------
+ * HIPETS_OBS_COLUMNS   column k of obs_process_fn(obs) is fn_k(obs[dim_k]), fn = identity, sinf or cosf in fp32 -- the form of both
+ *     shipped preprocessors (halfcheetah: [s1, sin s2, cos s2, s3:]; cartpole_pets: [sin s1, cos s1, s0, s2:]) and of any
+ *     environment that feeds joint angles to its model as sin / cos.  A dim may enter several columns, in any order, or none; the
+ *     table has in_dim - act_dim entries, whatever obs_dim is.  NaN and inf propagate as sinf / cosf do (sin(inf) = NaN).
+ * Runs on the GENERIC and HIDDEN_STATIC kernel instances, like the parametric forms above, and is refused under
+ * HIPETS_PREC_BF16X3 / HIPETS_PREC_BF16 likewise.                                                                         */
+enum { HIPETS_COL_ID = 0, HIPETS_COL_SIN = 1, HIPETS_COL_COS = 2 };
+typedef struct {
+    int32_t dim; /* observation dim the column reads                                  */
+    int32_t fn;  /* HIPETS_COL_*                                                      */
+} hipets_obs_column;
 
 /*
  * Snapshot of what ModelEnv.evaluate_action_sequences reads from the live objects
@@ -228,6 +243,11 @@ void hipets_destroy(hipets_engine* e);
 /* Re-snapshot weights / normaliser / elite set (call after ModelTrainer.train,
  * mbrl/models/model_trainer.py:288-296).  Packs into the MFMA fragment layout. */
 int hipets_set_model(hipets_engine* e, const hipets_model_desc* desc, void* stream);
+/* hipets_set_model for a model whose obs_process is HIPETS_OBS_COLUMNS: column k of obs_process_fn(obs) is fn_k(obs[dim_k]);
+ * desc->in_dim must equal n_cols + act_dim (1 <= n_cols <= HIPETS_MAX_OBS_COLUMNS).  cols is HOST memory, copied.  (An entry point
+ * of its own, not a field of hipets_model_desc: the descriptor's layout and HIPETS_ABI_VERSION stay what they were; plain
+ * hipets_set_model refuses HIPETS_OBS_COLUMNS.)                                                                               */
+int hipets_set_model_columns(hipets_engine* e, const hipets_model_desc* desc, const hipets_obs_column* cols, int32_t n_cols, void* stream);
 
 /* ---- ModelEnv.evaluate_action_sequences (mbrl/models/model_env.py:145-191) ---------------- */
 /* actions DEVICE [pop,H,A] f32; s0 HOST [obs_dim] f32; returns DEVICE [pop] f32.              */

@@ -28,7 +28,16 @@ struct ObsMap {
 };
 
 // obs_process_fn(obs)[i] (mbrl/env/pets_halfcheetah.py:91-113, pets_cartpole.py:78-101)
-__device__ __forceinline__ float processed_obs(const float* s, int i, int mode) {
+// `cols`: the model's column table (HIPETS_OBS_COLUMNS: column i is fn_i(s[dim_i]), the same sinf / cosf as the enum forms -- a table that
+// restates one of them gives its bits); the shape-specialised instances, whose mode is a compile-time enum, pass none
+__device__ __forceinline__ float processed_obs(const float* s, int i, int mode, const hipets_obs_column* cols = nullptr) {
+    if (mode == HIPETS_OBS_COLUMNS) {
+        const hipets_obs_column col = cols[i];
+        const float x = s[col.dim];
+        if (col.fn == HIPETS_COL_SIN) return sinf(x);
+        if (col.fn == HIPETS_COL_COS) return cosf(x);
+        return x;
+    }
     if (mode == HIPETS_OBS_HALFCHEETAH) {  // [s1, sin s2, cos s2, s3:]
         if (i == 0) return s[1];
         if (i == 1) return sinf(s[2]);

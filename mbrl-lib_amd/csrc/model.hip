@@ -55,12 +55,20 @@ int read_form_tables(const hipets_model_desc* d, FormTables* ft) {
     return 0;
 }
 
-}  // namespace
+// The column table of a HIPETS_OBS_COLUMNS model (include/hipets.h hipets_set_model_columns), checked entry by entry.
+int read_obs_columns(const hipets_model_desc* d, const hipets_obs_column* cols, const int n_cols) {
+    if (!cols) return fail("obs_process COLUMNS: cols is null");
+    if (n_cols < 1 || n_cols > HIPETS_MAX_OBS_COLUMNS) return fail("n_cols %d outside [1, %d]", n_cols, HIPETS_MAX_OBS_COLUMNS);
+    for (int k = 0; k < n_cols; ++k) {
+        if (cols[k].dim < 0 || cols[k].dim >= d->obs_dim) return fail("obs column %d: dim %d outside [0, %d)", k, cols[k].dim, d->obs_dim);
+        if (cols[k].fn != HIPETS_COL_ID && cols[k].fn != HIPETS_COL_SIN && cols[k].fn != HIPETS_COL_COS) return fail("obs column %d: unknown fn %d", k, cols[k].fn);
+    }
+    return 0;
+}
 
-extern "C" {
-
-int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream) {
-    if (!e || !d) return fail("null argument");
+// hipets_set_model and hipets_set_model_columns: one body.  cols = the column table of a HIPETS_OBS_COLUMNS model, null for every other
+// obs_process (the entry points have checked which of the two the descriptor asks for).
+int set_model(hipets_engine* e, const hipets_model_desc* d, const hipets_obs_column* cols, const int n_cols, void* stream) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
@@ -69,7 +77,9 @@ int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream)
     if (d->obs_dim < 1 || d->act_dim < 1 || d->in_dim < d->act_dim + 1 || d->hid < 1) return fail("bad dimensions");
     if (d->out_dim != d->obs_dim + (d->learned_rewards ? 1 : 0)) return fail("out_dim %d != obs_dim %d + learned_rewards %d", d->out_dim, d->obs_dim, d->learned_rewards);
     const int obs_in = d->in_dim - d->act_dim;
-    const int expect_in = d->obs_process == HIPETS_OBS_CARTPOLE_PETS ? d->obs_dim + 1 : d->obs_dim;
+    if (d->obs_process < HIPETS_OBS_NONE || d->obs_process > HIPETS_OBS_COLUMNS) return fail("unknown obs_process %d", d->obs_process);
+    if (cols && obs_in != n_cols) return fail("in_dim %d != n_cols %d + act_dim %d", d->in_dim, n_cols, d->act_dim);
+    const int expect_in = cols ? n_cols : (d->obs_process == HIPETS_OBS_CARTPOLE_PETS ? d->obs_dim + 1 : d->obs_dim);
     if (obs_in != expect_in) return fail("in_dim %d inconsistent with obs_dim %d / obs_process %d / act_dim %d", d->in_dim, d->obs_dim, d->obs_process, d->act_dim);
     if (d->reward_fn == HIPETS_REW_LEARNED && !d->learned_rewards) return fail("reward_fn LEARNED needs learned_rewards");
     if (d->reward_fn == HIPETS_REW_HALFCHEETAH && d->obs_dim < 3) return fail("halfcheetah reward needs obs_dim >= 3");
@@ -167,11 +177,15 @@ int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream)
     if (e->bpack.ensure((size_t)md.bmember * md.M * 4)) return 1;
     if (e->members.ensure((size_t)md.M * 4)) return 1;
     HCHECK(hipMemcpyAsync(e->members.p, d->members, (size_t)md.M * 4, hipMemcpyHostToDevice, st));
-    // one block: the layer table, then the tables of the parametric closed forms (rollout_types.hpp form_tables)
+    // one block: the layer table, then the tables of the parametric closed forms (rollout_types.hpp form_tables), then the column table of
+    // a HIPETS_OBS_COLUMNS model (obs_columns)
     static_assert(sizeof(LayerMeta) % alignof(FormTables) == 0, "FormTables follow the layer table");
-    if (e->layer_meta.ensure(sizeof(LayerMeta) * d->n_layers + sizeof(FormTables))) return 1;
-    HCHECK(hipMemcpyAsync(e->layer_meta.p, lms.data(), sizeof(LayerMeta) * d->n_layers, hipMemcpyHostToDevice, st));
-    HCHECK(hipMemcpyAsync(e->layer_meta.as<char>() + sizeof(LayerMeta) * d->n_layers, &forms, sizeof(FormTables), hipMemcpyHostToDevice, st));
+    static_assert(sizeof(FormTables) % alignof(hipets_obs_column) == 0, "the column table follows the FormTables");
+    const size_t forms_at = sizeof(LayerMeta) * d->n_layers, cols_at = forms_at + sizeof(FormTables), cols_bytes = cols ? sizeof(hipets_obs_column) * n_cols : 0;
+    if (e->layer_meta.ensure(cols_at + cols_bytes)) return 1;
+    HCHECK(hipMemcpyAsync(e->layer_meta.p, lms.data(), forms_at, hipMemcpyHostToDevice, st));
+    HCHECK(hipMemcpyAsync(e->layer_meta.as<char>() + forms_at, &forms, sizeof(FormTables), hipMemcpyHostToDevice, st));
+    if (cols) HCHECK(hipMemcpyAsync(e->layer_meta.as<char>() + cols_at, cols, cols_bytes, hipMemcpyHostToDevice, st));
     for (int l = 0; l < d->n_layers; ++l) {
         const float* w = reinterpret_cast<const float*>(d->weights[l]);
         const float* b = reinterpret_cast<const float*>(d->biases[l]);
@@ -221,6 +235,24 @@ int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream)
     e->ensemble_size = d->ensemble_size;
     e->has_model = true;
     return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int hipets_set_model(hipets_engine* e, const hipets_model_desc* d, void* stream) {
+    if (!e || !d) return fail("null argument");
+    if (d->obs_process == HIPETS_OBS_COLUMNS) return fail("obs_process COLUMNS comes with its column table: call hipets_set_model_columns");
+    return set_model(e, d, nullptr, 0, stream);
+}
+
+int hipets_set_model_columns(hipets_engine* e, const hipets_model_desc* d, const hipets_obs_column* cols, int32_t n_cols, void* stream) {
+    if (!e || !d) return fail("null argument");
+    if (d->obs_process != HIPETS_OBS_COLUMNS) return fail("hipets_set_model_columns: obs_process %d is not HIPETS_OBS_COLUMNS", d->obs_process);
+    if (d->obs_dim < 1) return fail("bad dimensions");
+    if (read_obs_columns(d, cols, n_cols)) return 1;
+    return set_model(e, d, cols, n_cols, stream);
 }
 
 int hipets_planet_set_model(hipets_engine* e, const hipets_planet_desc* d, void* stream) {

@@ -548,7 +548,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                 float x;
                 if (cc < md.obs_in) {
                     if constexpr (PLAIN) x = sm.state[s * md.obs_dim + cc];
-                    else x = processed_obs(sm.state + s * md.obs_dim, cc, obs_process);
+                    else x = processed_obs(sm.state + s * md.obs_dim, cc, obs_process, kLean ? nullptr : obs_columns(md));  // (the table: read only by HIPETS_OBS_COLUMNS, which a lean instance never is)
                 } else {
                     x = actn_t[s * md.act_dim + (cc - md.obs_in)];
                 }

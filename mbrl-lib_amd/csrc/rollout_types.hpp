@@ -57,7 +57,8 @@ struct ModelDev {
     float slope;
     int propagation, deterministic, obs_process, reward_fn, term_fn, target_is_delta, learned_rewards, normalizer;
     const LayerMeta* layers;  // DEVICE [n_layers] (a table in memory: runtime-indexed kernargs would go to scratch), followed by the model's
-                              // FormTables where reward_fn is HIPETS_REW_TERMS or term_fn HIPETS_TERM_BOX (form_tables below)
+                              // FormTables where reward_fn is HIPETS_REW_TERMS or term_fn HIPETS_TERM_BOX (form_tables below), and by its
+                              // column table where obs_process is HIPETS_OBS_COLUMNS (obs_columns below)
     int Kp0;                  // padded input width of layer 0
     int hidC;                 // column tiles of a hidden layer (cost model; shape of the lean kernel instances)
     int outC;                 // column tiles of the output layer
@@ -83,6 +84,13 @@ struct ModelDev {
 // in ModelDev: the kernel-argument layout of every rollout-kernel instance stays what it was.)
 __host__ __device__ __forceinline__ const FormTables* form_tables(const ModelDev& md) {
     return reinterpret_cast<const FormTables*>(md.layers + md.n_layers);
+}
+
+// The column table of a HIPETS_OBS_COLUMNS model ([obs_in] entries: column k of obs_process_fn(obs) is fn_k(obs[dim_k])):
+// hipets_set_model_columns stores it behind the FormTables, in the same device block, for the same reason.  Read with plain global
+// loads by build_input_impl (at most 4 KB, hot in cache); never staged in LDS: the LDS layout does not know it.
+__host__ __device__ __forceinline__ const hipets_obs_column* obs_columns(const ModelDev& md) {
+    return reinterpret_cast<const hipets_obs_column*>(form_tables(md) + 1);
 }
 
 struct RolloutArgs {

@@ -9,6 +9,8 @@ from .model import (  # noqa: F401
     BoxTermination,
     Interval,
     ModelSpec,
+    ObsColumn,
+    ObsColumns,
     PlaNetSpec,
     RewardTerm,
     RewardTerms,

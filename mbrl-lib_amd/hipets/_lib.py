@@ -14,7 +14,7 @@ MAX_LAYERS = 8
 
 ACT = {"relu": 0, "silu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4}
 PROP = {"random_model": 0, "fixed_model": 1, "expectation": 2}
-OBS = {"none": 0, "halfcheetah": 1, "cartpole_pets": 2}
+OBS = {"none": 0, "halfcheetah": 1, "cartpole_pets": 2, "columns": 3}  # (columns: a hipets.ObsColumns table, HIPETS_OBS_COLUMNS)
 REW = {None: 0, "learned": 0, "cartpole": 1, "cartpole_pets": 2, "inverted_pendulum": 3, "halfcheetah": 4, "pusher": 5, "none": 6,
        "terms": 7}  # (terms: a hipets.RewardTerms table, HIPETS_REW_TERMS)
 TERM = {"no_termination": 0, "cartpole": 1, "inverted_pendulum": 2, "hopper": 3, "walker2d": 4, "ant": 5, "humanoid": 6,
@@ -28,6 +28,8 @@ TERM_FN = {"linear": 0, "square": 1, "abs": 2}  # HIPETS_TERM_FN_*
 TERM_SRC = {"obs": 0, "act": 1}  # HIPETS_TERM_SRC_*
 BOX_LO_OPEN, BOX_HI_OPEN = 1, 2  # hipets_term_interval.flags
 MAX_REWARD_TERMS, MAX_TERM_INTERVALS = 64, 64
+COL_FN = {"id": 0, "sin": 1, "cos": 2}  # HIPETS_COL_*
+MAX_OBS_COLUMNS = 512
 KERNEL_CLASSES = ("generic", "hidden_static", "fused", "wide", "bf16")  # HIPETS_KERNEL_*
 
 
@@ -37,6 +39,10 @@ class RewardTermC(C.Structure):  # hipets_reward_term
 
 class TermIntervalC(C.Structure):  # hipets_term_interval
     _fields_ = [("dim", C.c_int32), ("flags", C.c_int32), ("lo", C.c_float), ("hi", C.c_float)]
+
+
+class ObsColumnC(C.Structure):  # hipets_obs_column
+    _fields_ = [("dim", C.c_int32), ("fn", C.c_int32)]
 
 
 class ModelDesc(C.Structure):
@@ -136,6 +142,7 @@ SYMBOLS = {
     "hipets_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
     "hipets_destroy": (None, [_P]),
     "hipets_set_model": (C.c_int, [_P, C.POINTER(ModelDesc), _P]),
+    "hipets_set_model_columns": (C.c_int, [_P, C.POINTER(ModelDesc), C.POINTER(ObsColumnC), C.c_int32, _P]),
     "hipets_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RolloutOpts), _P, _P]),
     "hipets_step": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(RolloutOpts), _P, _P, _P, _P]),
     "hipets_fast_geometry": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),

@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import CemParams, HipetsError, ModelDesc, PlanTrace, RolloutOpts, TrainDesc
-from .model import BoxTermination, ModelSpec, RewardTerms
+from .model import BoxTermination, ModelSpec, ObsColumns, RewardTerms
 
 
 def _ptr(t: Optional[torch.Tensor]):
@@ -101,8 +101,14 @@ class Engine:
         d.leaky_slope = float(spec.leaky_slope)
         d.propagation = _lib.PROP[spec.propagation]
         d.deterministic = int(spec.deterministic)
-        d.obs_process = _lib.OBS[spec.obs_process]
         keep = []  # the ctypes tables of the parametric forms: alive until the call has copied them
+        cols = None
+        if isinstance(spec.obs_process, ObsColumns):
+            cols = (_lib.ObsColumnC * len(spec.obs_process.columns))(*[_lib.ObsColumnC(int(c.dim), _lib.COL_FN[c.fn]) for c in spec.obs_process.columns])
+            keep.append(cols)
+            d.obs_process = _lib.OBS["columns"]
+        else:
+            d.obs_process = _lib.OBS[spec.obs_process]
         if isinstance(spec.reward, RewardTerms):
             rt = spec.reward
             terms = (_lib.RewardTermC * max(1, len(rt.terms)))(*[
@@ -152,7 +158,10 @@ class Engine:
         b_arr = (C.c_void_p * n)(*[b.data_ptr() for b in bs])
         d.weights, d.biases = w_arr, b_arr
         with torch.cuda.device(dev):
-            _lib.check(self._lib.hipets_set_model(self._h, C.byref(d), _stream(dev)))
+            if cols is not None:
+                _lib.check(self._lib.hipets_set_model_columns(self._h, C.byref(d), cols, len(cols), _stream(dev)))
+            else:
+                _lib.check(self._lib.hipets_set_model(self._h, C.byref(d), _stream(dev)))
         del keep
         self.spec = spec
 

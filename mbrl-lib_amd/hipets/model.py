@@ -17,7 +17,7 @@ from typing import List, Optional, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from ._lib import MAX_REWARD_TERMS, MAX_TERM_INTERVALS
+from ._lib import MAX_OBS_COLUMNS, MAX_REWARD_TERMS, MAX_TERM_INTERVALS
 
 
 class UnsupportedModelError(ValueError):
@@ -149,6 +149,59 @@ class RewardTerms:
         return r.view(-1, 1)
 
 
+# ---------------------------------------------------------------------------------------------
+# Parametric observation preprocessing (include/hipets.h HIPETS_OBS_COLUMNS): the obs_process_fn of environments mbrl.env does
+# not ship.  A callable with the signature of HalfCheetahEnv.preprocess_fn / CartPoleEnv.preprocess_fn, on torch tensors and
+# numpy arrays alike: one object is the ``obs_process_fn`` of a stock ``OneDTransitionRewardModel`` (the reference trains with
+# it), the oracle of a test, and -- as ``ModelSpec.obs_process`` -- what the fused kernels evaluate.
+# ---------------------------------------------------------------------------------------------
+COL_FNS = ("id", "sin", "cos")  # HIPETS_COL_*
+
+
+@dataclass(frozen=True)
+class ObsColumn:
+    """One model-input column ``fn(obs[dim])``; ``fn``: ``'id'``, ``'sin'`` or ``'cos'``."""
+
+    dim: int
+    fn: str = "id"
+
+
+@dataclass(frozen=True)
+class ObsColumns:
+    """``obs_process_fn`` as a column table: column ``k`` of the processed observation is ``fn_k(obs[..., dim_k])``
+    (:class:`ObsColumn`).  A dim may enter several columns, in any order, or none.  Restates both shipped preprocessors:
+    halfcheetah ``[s1, sin s2, cos s2, s3:]`` and cartpole_pets ``[sin s1, cos s1, s0, s2:]``.  1 .. 512 columns."""
+
+    columns: Tuple[ObsColumn, ...] = ()
+
+    def __post_init__(self):
+        object.__setattr__(self, "columns", tuple(c if isinstance(c, ObsColumn) else ObsColumn(*c) for c in self.columns))
+        self.validate()
+
+    def validate(self, obs_dim: Optional[int] = None):
+        if not 1 <= len(self.columns) <= MAX_OBS_COLUMNS:
+            raise UnsupportedModelError(f"ObsColumns: {len(self.columns)} columns, 1 .. {MAX_OBS_COLUMNS} are supported")
+        for k, c in enumerate(self.columns):
+            if isinstance(c.dim, bool) or not isinstance(c.dim, (int, np.integer)) or c.dim < 0 or (obs_dim is not None and c.dim >= obs_dim):
+                raise UnsupportedModelError(f"ObsColumns column {k}: dim {c.dim!r} outside [0, {obs_dim if obs_dim is not None else 'obs_dim'})")
+            if c.fn not in COL_FNS:
+                raise UnsupportedModelError(f"ObsColumns column {k}: fn {c.fn!r} is not one of {COL_FNS}")
+
+    def __call__(self, obs):
+        dims = [int(c.dim) for c in self.columns]
+        sin = [k for k, c in enumerate(self.columns) if c.fn == "sin"]
+        cos = [k for k, c in enumerate(self.columns) if c.fn == "cos"]
+        # (advanced indexing: a new tensor / array of obs's dtype, on obs's device; a numpy array goes through torch's sin / cos on a
+        # view of the result, so that the normaliser statistics the reference computes on numpy batches see the bits the model sees)
+        res = obs[..., dims] if isinstance(obs, torch.Tensor) else np.asarray(obs)[..., dims]
+        out = res if isinstance(obs, torch.Tensor) else torch.from_numpy(res)
+        if sin:
+            out[..., sin] = torch.sin(out[..., sin])
+        if cos:
+            out[..., cos] = torch.cos(out[..., cos])
+        return res
+
+
 @dataclass
 class ModelSpec:
     weights: List[torch.Tensor]  # per linear layer [E, in_l, out_l] f32
@@ -167,7 +220,7 @@ class ModelSpec:
     target_is_delta: bool = True
     no_delta_list: Sequence[int] = field(default_factory=list)
     learned_rewards: bool = False
-    obs_process: str = "none"
+    obs_process: Union[str, ObsColumns] = "none"  # (an ObsColumns => the model's own column table)
     # None => learned reward (last model output); "none" => caller's callable; a RewardTerms => the model's own term table
     reward: Union[str, None, RewardTerms] = "halfcheetah"
     termination: Union[str, BoxTermination] = "no_termination"  # (a BoxTermination => the model's own healthy box)
@@ -237,14 +290,19 @@ class ModelSpec:
             raise UnsupportedModelError(f"reward_fn {self.reward!r} has no fused implementation")
         if self.reward is None and not self.learned_rewards:
             raise UnsupportedModelError("reward_fn is None but the model does not learn rewards")
-        if self.obs_process not in ("none", "halfcheetah", "cartpole_pets"):
+        if isinstance(self.obs_process, ObsColumns):
+            self.obs_process.validate(self.obs_dim)
+        elif self.obs_process not in ("none", "halfcheetah", "cartpole_pets"):
             raise UnsupportedModelError(f"obs_process_fn {self.obs_process!r} has no fused implementation")
         if len(self.weights) < 2 or len(self.weights) > 8:
             raise UnsupportedModelError("need 2..8 linear layers")
         for li in range(1, len(self.weights) - 1):
             if tuple(self.weights[li].shape[1:]) != (self.hid, self.hid):
                 raise UnsupportedModelError("hidden layers must share one width")
-        exp_in = self.obs_dim + (1 if self.obs_process == "cartpole_pets" else 0) + self.act_dim
+        if isinstance(self.obs_process, ObsColumns):
+            exp_in = len(self.obs_process.columns) + self.act_dim
+        else:
+            exp_in = self.obs_dim + (1 if self.obs_process == "cartpole_pets" else 0) + self.act_dim
         if self.in_dim != exp_in:
             raise UnsupportedModelError(f"model in_size {self.in_dim} != obs'+act = {exp_in}")
         if self.out_dim != self.obs_dim + (1 if self.learned_rewards else 0):
@@ -272,7 +330,9 @@ def _closed_form(fn, kind: str, known) -> Optional[str]:
     return None
 
 
-def _obs_process_name(fn) -> Optional[str]:
+def _obs_process_name(fn) -> Union[str, ObsColumns, None]:
+    if isinstance(fn, ObsColumns):  # recognised by type, enters the spec as itself: the fused kernels evaluate its table
+        return fn
     tag = getattr(fn, "hipets_closed_form", None)
     if tag is not None:
         return tag if tag in ("halfcheetah", "cartpole_pets") else None
@@ -343,7 +403,8 @@ def spec_from_model_env(model_env, obs_dim: Optional[int] = None, act_dim: Optio
     if obs_fn is not None:
         obs_process = _obs_process_name(obs_fn)
         if obs_process is None:
-            raise UnsupportedModelError(f"obs_process_fn {getattr(obs_fn, '__qualname__', obs_fn)!r} has no fused implementation")
+            raise UnsupportedModelError(f"obs_process_fn {getattr(obs_fn, '__qualname__', obs_fn)!r} has no fused implementation "
+                                        "(columns of the form id / sin / cos of one observation dim run fused as a hipets.ObsColumns)")
     od = obs_dim if obs_dim is not None else int(model_env.observation_space.shape[0])
     ad = act_dim if act_dim is not None else int(model_env.action_space.shape[0])
     rew, term = model_env.reward_fn, model_env.termination_fn
