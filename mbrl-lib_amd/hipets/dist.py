@@ -87,7 +87,7 @@ def init_engine_comm(engine, group=None):
     box = [engine.comm_unique_id() if rank == 0 else None]
     dist.broadcast_object_list(box, src=dist.get_global_rank(group, 0) if group is not None else 0, group=group)
     engine.comm_init(box[0], rank, world)
-    engine.comm_group = group  # the process group the ranks agree over (plan_*_sharded below)
+    engine.comm_group = group  # the process group the ranks agree over (_plan_sharded below)
     return engine
 
 
@@ -154,33 +154,33 @@ def run_sharded(engine, sharded_call: Callable, single_call: Callable, group=Non
     return single_call(), True
 
 
+def _plan_sharded(engine, sharded_plan: Callable, single_plan: Callable, args, group=None, in_place: Optional[torch.Tensor] = None, **kw):
+    """``sharded_plan(*args, **kw)`` -- an ``Engine.plan_*_sharded`` method -- under :func:`run_sharded`'s failure policy (fallback:
+    ``single_plan``, the ``Engine.plan_*`` of the whole population, with the same arguments).  ``in_place``: the persistent tensor
+    among ``args`` that the plan overwrites (MPPI's mean, iCEM's elite set); a failed sharded attempt is undone before the single-GPU
+    plan runs.  Returns ``(result, used_fallback)``."""
+    before = in_place.clone() if in_place is not None else None
+    return run_sharded(engine, lambda: sharded_plan(*args, **kw), lambda: single_plan(*args, **kw), group,
+                       restore=(lambda: in_place.copy_(before)) if in_place is not None else None)
+
+
 def plan_cem_sharded(engine, params, x0, lower, upper, s0, num_particles: int, seed: int = 0, plan_id: int = 0, group=None):
-    """``Engine.plan_cem_sharded`` under :func:`run_sharded`'s failure policy (fallback: ``Engine.plan_cem`` of the whole
-    population).  Returns ``(plan, used_fallback)``."""
-    return run_sharded(engine,
-                       lambda: engine.plan_cem_sharded(params, x0, lower, upper, s0, num_particles, seed=seed, plan_id=plan_id),
-                       lambda: engine.plan_cem(params, x0, lower, upper, s0, num_particles, seed=seed, plan_id=plan_id), group)
+    """``Engine.plan_cem_sharded`` (hipets_plan_cem_sharded), fallback ``Engine.plan_cem``.  Returns ``(plan, used_fallback)``."""
+    return _plan_sharded(engine, engine.plan_cem_sharded, engine.plan_cem, (params, x0, lower, upper, s0, num_particles), group,
+                         seed=seed, plan_id=plan_id)
 
 
 def plan_mppi_sharded(engine, pop: int, H: int, A: int, num_iterations: int, gamma: float, beta: float, mean: torch.Tensor, lower, upper, s0,
                       num_particles: int, seed: int = 0, plan_id: int = 0, group=None):
-    """``Engine.plan_mppi_sharded`` (hipets_plan_mppi_sharded) under :func:`run_sharded`'s failure policy.  ``mean`` -- the
-    optimizer's persistent mean -- is shifted and refined IN PLACE; a failed sharded attempt is undone before the single-GPU plan
-    runs.  Returns ``(mean, used_fallback)``."""
-    before = mean.clone()
-    return run_sharded(engine,
-                       lambda: engine.plan_mppi_sharded(pop, H, A, num_iterations, gamma, beta, mean, lower, upper, s0, num_particles, seed=seed, plan_id=plan_id),
-                       lambda: engine.plan_mppi(pop, H, A, num_iterations, gamma, beta, mean, lower, upper, s0, num_particles, seed=seed, plan_id=plan_id),
-                       group, restore=lambda: mean.copy_(before))
+    """``Engine.plan_mppi_sharded`` (hipets_plan_mppi_sharded): ``mean`` -- the optimizer's persistent mean -- is shifted and refined
+    IN PLACE.  Returns ``(mean, used_fallback)``."""
+    return _plan_sharded(engine, engine.plan_mppi_sharded, engine.plan_mppi,
+                         (pop, H, A, num_iterations, gamma, beta, mean, lower, upper, s0, num_particles), group, mean, seed=seed, plan_id=plan_id)
 
 
 def plan_icem_sharded(engine, params, x0, lower, upper, elite: torch.Tensor, has_elite: bool, s0, num_particles: int, seed: int = 0,
                       plan_id: int = 0, keep_idx=None, group=None):
-    """``Engine.plan_icem_sharded`` (hipets_plan_icem_sharded) under :func:`run_sharded`'s failure policy.  ``elite`` -- the
-    optimizer's persistent elite set -- is overwritten by every iteration; a failed sharded attempt is undone before the single-GPU
-    plan runs.  Returns ``(plan, used_fallback)``."""
-    before = elite.clone()
-    return run_sharded(engine,
-                       lambda: engine.plan_icem_sharded(params, x0, lower, upper, elite, has_elite, s0, num_particles, seed=seed, plan_id=plan_id, keep_idx=keep_idx),
-                       lambda: engine.plan_icem(params, x0, lower, upper, elite, has_elite, s0, num_particles, seed=seed, plan_id=plan_id, keep_idx=keep_idx),
-                       group, restore=lambda: elite.copy_(before))
+    """``Engine.plan_icem_sharded`` (hipets_plan_icem_sharded): ``elite`` -- the optimizer's persistent elite set -- is overwritten
+    by every iteration.  Returns ``(plan, used_fallback)``."""
+    return _plan_sharded(engine, engine.plan_icem_sharded, engine.plan_icem, (params, x0, lower, upper, elite, has_elite, s0, num_particles),
+                         group, elite, seed=seed, plan_id=plan_id, keep_idx=keep_idx)

@@ -3,7 +3,7 @@ device memory and streams; every computation is a libhipets call."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Optional
+from typing import Dict, Optional
 
 import numpy as np
 import torch
@@ -69,7 +69,7 @@ class Engine:
         self.planet_spec = None
         self.comm_world, self.comm_rank = 1, 0
         self.comm_group = None  # torch.distributed group of the communicator's ranks (hipets.dist.init_engine_comm)
-        self.plan_mode = "fast"  # (the library's initial value; every fused plan sets its objective's mode: planning._prepare_fused)
+        self.plan_mode = "fast"  # (the library's initial value; every fused plan sets its objective's mode: optimizers._prepare_fused)
         self._trace = None
         self._keep = []  # device tensors that must outlive async set_model work
 
@@ -848,3 +848,17 @@ class Engine:
         n, ms = C.c_int64(), C.c_double()
         _lib.check(self._lib.hipets_timing_read(self._h, C.byref(n), C.byref(ms), int(reset)))
         return n.value, ms.value
+
+
+_ENGINES: Dict[int, Engine] = {}
+
+
+def get_engine(device) -> Engine:
+    """One Engine per GPU (the reference is single-device, single-threaded)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise HipetsError(f"hipets needs a GPU device, got {device} (there is no CPU fallback)")
+    idx = device.index if device.index is not None else torch.cuda.current_device()
+    if idx not in _ENGINES:
+        _ENGINES[idx] = Engine(torch.device("cuda", idx))
+    return _ENGINES[idx]

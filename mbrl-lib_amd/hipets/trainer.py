@@ -143,7 +143,7 @@ class ModelTrainer:
 
     def __init__(self, model, optim_lr: float = 1e-4, weight_decay: float = 1e-5, optim_eps: float = 1e-8, logger=None, *,
                  engine=None, device=None, steps_per_launch: int = 0):
-        from .planning import get_engine
+        from .engine import get_engine
 
         self.model = model
         self._mlp, self._live, self._act, self._slope = _read_model(model)

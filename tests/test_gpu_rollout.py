@@ -703,3 +703,27 @@ def test_wide_output_instance_equals_the_generic_kernel_bitwise(engine, case):
     a = engine.rollout(actions.to(DEV), s0, P, mode="fast", seed=11, stream_id=3, rows_per_group=1)
     b = engine.rollout(actions.to(DEV), s0, P, mode="fast", seed=11, stream_id=3, rows_per_group=1, generic_kernel=True)
     assert torch.equal(a, b) and torch.isfinite(a).all()
+
+
+@pytest.mark.parametrize("propagation", ["random_model", "fixed_model"])
+@pytest.mark.parametrize("kind,pop,P", [("gaussian_mlp", 6, 2), ("basic_ensemble", 5, 3)])  # (15 rows: no multiple of the 4 members)
+def test_exact_objective_equals_the_exact_rollout_fed_the_reference_draws(engine, kind, pop, P, propagation):
+    """HipTrajectoryEvalFn(mode='exact') keeps no draw code of its own: it returns, bit for bit, what Engine.rollout(mode='exact')
+    returns for hipets.reference_draws.rollout_draws of identically seeded generators."""
+    import hipets
+    from hipets import reference_draws as rd
+
+    obs, act, H, E = 5, 2, 3, 4
+    om = po.make_synthetic_model(obs, act, ensemble_size=E, hid=8, ensemble_kind=kind, propagation=propagation)
+    spec = to_spec(om, obs, act)
+    g = torch.Generator().manual_seed(5)
+    actions = (torch.rand(pop, H, act, generator=g) * 2 - 1).to(DEV)
+    s0 = (np.random.default_rng(2).standard_normal(obs) * 0.1).astype(np.float32)
+    fn = hipets.HipTrajectoryEvalFn(spec, P, engine=engine, mode="exact", rng=torch.Generator().manual_seed(31))
+    torch.manual_seed(17)
+    out = fn(s0, actions)
+    torch.manual_seed(17)
+    perms, members, eps = rd.rollout_draws(spec, pop * P, H, torch.Generator().manual_seed(31))
+    assert (perms is None) == (kind == "basic_ensemble") and (members is None) == (kind == "gaussian_mlp") and eps is not None
+    ref = engine.rollout(actions, s0, P, mode="exact", perms=None if perms is None else perms.to(DEV), members=members, eps=eps.to(DEV))
+    assert torch.equal(out, ref) and torch.isfinite(out).all()
