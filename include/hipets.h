@@ -103,13 +103,35 @@ enum { HIPETS_MODE_EXACT = 0,  /* reference semantics, injected perms / eps (par
  *     done = !healthy.  Restates termination_fns.cartpole / inverted_pendulum / hopper / walker2d / ant exactly, and
  *     humanoid on finite rows only (the reference's humanoid leaves a NaN row alive; a box ends it).
  * The parametric forms run on the GENERIC and HIDDEN_STATIC kernel instances (hipets_kernel_class): a model that uses one
- * has no shape-specialised instance, and is therefore refused under HIPETS_PREC_BF16X3 / HIPETS_PREC_BF16.               */
-enum { HIPETS_TERM_FN_LINEAR = 0, HIPETS_TERM_FN_SQUARE = 1, HIPETS_TERM_FN_ABS = 2 };
-enum { HIPETS_TERM_SRC_OBS = 0, HIPETS_TERM_SRC_ACT = 1 };
+ * has no shape-specialised instance, and is therefore refused under HIPETS_PREC_BF16X3 / HIPETS_PREC_BF16.
+ *
+ * Grouped terms (additive to ABI v9: no struct changed, a v9 table means what it meant).  The table is a small expression form
+ * over three accumulators: A0 starts at reward_bias, A1 and A2 at 0.  Entries run in table order, op by op in fp32:
+ *     e = v[i] - (j >= 0 ? v[j] : c)          source OBS (v = s') or ACT (v = a)
+ *     e = c                                   source CONST
+ *     e = A[level + 1] - c;  A[level + 1] = 0 source GROUP: consumes the finished deeper group (level 0 or 1 only)
+ *     t = w * f(e)                            f: linear | square | abs | sinf | cosf | expf | sqrtf
+ *     A[level] = A[level] + t | A[level] * t | A[level] / t          op: ADD | MUL | DIV
+ *     r = A0, then the alive bonus as above.  sqrt of a negative is NaN, x / 0 is +-inf; NaN and inf propagate.
+ * `level` and `op` travel in the upper bits of hipets_reward_term.fn, which a v9 client leaves zero (level 0, ADD):
+ * HIPETS_TERM_WORD below.  A table is well formed, and hipets_set_model refuses it otherwise naming the entry, when level is in
+ * 0..2, GROUP is not at level 2 and does not consume an empty group (no entry since its last consumption or the table start),
+ * MUL / DIV do not go into an empty group at level 1 or 2, no group is left open at the end of the table, and GROUP / CONST
+ * entries have j < 0.  i and j of a GROUP / CONST entry are not read.                                                       */
+enum { HIPETS_TERM_FN_LINEAR = 0, HIPETS_TERM_FN_SQUARE = 1, HIPETS_TERM_FN_ABS = 2,
+       HIPETS_TERM_FN_SIN = 3, HIPETS_TERM_FN_COS = 4, HIPETS_TERM_FN_EXP = 5, HIPETS_TERM_FN_SQRT = 6 };
+enum { HIPETS_TERM_SRC_OBS = 0, HIPETS_TERM_SRC_ACT = 1, HIPETS_TERM_SRC_GROUP = 2, HIPETS_TERM_SRC_CONST = 3 };
+enum { HIPETS_TERM_OP_ADD = 0, HIPETS_TERM_OP_MUL = 1, HIPETS_TERM_OP_DIV = 2 };
+#define HIPETS_TERM_MAX_LEVEL 2
+/* hipets_reward_term.fn: fn | op << 8 | level << 16 (bits 24..31 zero) */
+#define HIPETS_TERM_WORD(fn, op, level) ((int32_t)((fn) | ((op) << 8) | ((level) << 16)))
+#define HIPETS_TERM_WORD_FN(word) ((int32_t)((word) & 0xff))
+#define HIPETS_TERM_WORD_OP(word) ((int32_t)(((word) >> 8) & 0xff))
+#define HIPETS_TERM_WORD_LEVEL(word) ((int32_t)(((uint32_t)(word)) >> 16))
 enum { HIPETS_BOX_LO_OPEN = 1, HIPETS_BOX_HI_OPEN = 2 }; /* hipets_term_interval.flags: the bound is strict (0 = closed) */
 typedef struct {
-    int32_t fn;     /* HIPETS_TERM_FN_*                                                  */
-    int32_t source; /* HIPETS_TERM_SRC_*: the vector i and j index                       */
+    int32_t fn;     /* HIPETS_TERM_WORD(HIPETS_TERM_FN_*, HIPETS_TERM_OP_*, level); a bare HIPETS_TERM_FN_* = level 0, ADD */
+    int32_t source; /* HIPETS_TERM_SRC_*: the vector i and j index, the deeper group, or the constant c */
     int32_t i;      /* dim of the minuend                                                */
     int32_t j;      /* dim of the subtrahend, or < 0: the constant c                     */
     float c;

@@ -101,17 +101,65 @@ __device__ __forceinline__ bool term_eval(const float* s, int obs_dim, int fn, c
 __device__ __forceinline__ float reward_eval(const float* s, const float* a, int obs_dim, int act_dim, int fn,
                                              float learned, const FormTables* forms = nullptr) {
     switch (fn) {
-        case HIPETS_REW_TERMS: {  // include/hipets.h: bias + sum_k w_k f_k(e_k), accumulated in table order (fp32, no contraction)
-            float r = forms->bias;
-            const int n = forms->n_terms;
-            for (int k = 0; k < n; ++k) {  // (table address and k are wave-uniform)
-                const hipets_reward_term tm = forms->terms[k];
-                const float* v = tm.source == HIPETS_TERM_SRC_ACT ? a : s;
-                const float e = v[tm.i] - (tm.j >= 0 ? v[tm.j] : tm.c);
-                const float f = tm.fn == HIPETS_TERM_FN_SQUARE ? e * e : (tm.fn == HIPETS_TERM_FN_ABS ? fabsf(e) : e);
-                r = r + tm.w * f;
+        case HIPETS_REW_TERMS: {  // include/hipets.h: the table's expression form, entry by entry in table order (fp32, no contraction)
+            // three accumulators in three named registers (a run-time-indexed array would go to scratch).  The table address and k are
+            // wave-uniform, but the entry arrives through a vector load (the kernel stores to global memory, so the compiler may not use
+            // the scalar cache): the first lane's copy of every field goes to a scalar register, and fn / op / level / source select by
+            // scalar branches.  A flat v9 table (every entry level 0, add, source OBS / ACT, fn <= abs: FormTables::grouped is 0) does not
+            // enter the machine at all: it keeps its own short loop, so that it costs what it cost before the machine existed.
+            if (!__builtin_amdgcn_readfirstlane(forms->grouped)) {  // a flat v9 table: bias + sum_k w_k f_k(e_k), the loop it always ran
+                float r = forms->bias;
+                const int n = forms->n_terms;
+                for (int k = 0; k < n; ++k) {
+                    const hipets_reward_term tm = forms->terms[k];
+                    const float* v = tm.source == HIPETS_TERM_SRC_ACT ? a : s;
+                    const float e = v[tm.i] - (tm.j >= 0 ? v[tm.j] : tm.c);
+                    const float f = tm.fn == HIPETS_TERM_FN_SQUARE ? e * e : (tm.fn == HIPETS_TERM_FN_ABS ? fabsf(e) : e);
+                    r = r + tm.w * f;
+                }
+                return r;
             }
-            return r;
+            float a0 = forms->bias, a1 = 0.0f, a2 = 0.0f;
+            const int n = __builtin_amdgcn_readfirstlane(forms->n_terms);
+            for (int k = 0; k < n; ++k) {
+                const hipets_reward_term tv = forms->terms[k];
+                hipets_reward_term tm;
+                tm.fn = __builtin_amdgcn_readfirstlane(tv.fn);
+                tm.source = __builtin_amdgcn_readfirstlane(tv.source);
+                tm.i = __builtin_amdgcn_readfirstlane(tv.i);
+                tm.j = __builtin_amdgcn_readfirstlane(tv.j);
+                tm.c = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, tv.c)));
+                tm.w = __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, tv.w)));
+                const int fn = HIPETS_TERM_WORD_FN(tm.fn), op = HIPETS_TERM_WORD_OP(tm.fn), level = HIPETS_TERM_WORD_LEVEL(tm.fn);
+                float e;
+                if (tm.source <= HIPETS_TERM_SRC_ACT) {
+                    const float* v = tm.source == HIPETS_TERM_SRC_ACT ? a : s;
+                    e = v[tm.i] - (tm.j >= 0 ? v[tm.j] : tm.c);
+                } else if (tm.source == HIPETS_TERM_SRC_CONST) {
+                    e = tm.c;
+                } else if (level == 0) {  // HIPETS_TERM_SRC_GROUP: the finished deeper group, which starts over
+                    e = a1 - tm.c;
+                    a1 = 0.0f;
+                } else {
+                    e = a2 - tm.c;
+                    a2 = 0.0f;
+                }
+                float f;
+                if (fn <= HIPETS_TERM_FN_ABS) f = fn == HIPETS_TERM_FN_SQUARE ? e * e : (fn == HIPETS_TERM_FN_ABS ? fabsf(e) : e);
+                else if (fn == HIPETS_TERM_FN_SIN) f = sinf(e);
+                else if (fn == HIPETS_TERM_FN_COS) f = cosf(e);
+                else if (fn == HIPETS_TERM_FN_EXP) f = expf(e);
+                else f = sqrtf(e);
+                const float t = tm.w * f;
+                float acc = level == 0 ? a0 : (level == 1 ? a1 : a2);
+                if (op == HIPETS_TERM_OP_ADD) acc = acc + t;
+                else if (op == HIPETS_TERM_OP_MUL) acc = acc * t;
+                else acc = acc / t;
+                if (level == 0) a0 = acc;
+                else if (level == 1) a1 = acc;
+                else a2 = acc;
+            }
+            return a0;
         }
         case HIPETS_REW_CARTPOLE: return term_eval(s, obs_dim, HIPETS_TERM_CARTPOLE) ? 0.0f : 1.0f;  // reward_fns.py:10-13
         case HIPETS_REW_INVERTED_PENDULUM: return term_eval(s, obs_dim, HIPETS_TERM_INVERTED_PENDULUM) ? 0.0f : 1.0f;

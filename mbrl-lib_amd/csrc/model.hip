@@ -24,16 +24,36 @@ int read_form_tables(const hipets_model_desc* d, FormTables* ft) {
             return fail("n_reward_terms %d outside [0, %d]", d->n_reward_terms, HIPETS_MAX_REWARD_TERMS);
         if (d->n_reward_terms > 0 && !d->reward_terms) return fail("reward_fn TERMS: reward_terms is null for n_reward_terms %d", d->n_reward_terms);
         if (d->alive_bonus != 0.0f && d->termination_fn == HIPETS_TERM_NONE) return fail("alive_bonus %g needs a termination_fn other than NONE", (double)d->alive_bonus);
+        int open[HIPETS_TERM_MAX_LEVEL + 1] = {0, 0, 0}, last[HIPETS_TERM_MAX_LEVEL + 1] = {0, 0, 0};  // entries of the open group of a level since it was consumed, its latest entry
         for (int k = 0; k < d->n_reward_terms; ++k) {
             const hipets_reward_term& t = d->reward_terms[k];
-            if (t.fn != HIPETS_TERM_FN_LINEAR && t.fn != HIPETS_TERM_FN_SQUARE && t.fn != HIPETS_TERM_FN_ABS) return fail("reward term %d: unknown fn %d", k, t.fn);
-            if (t.source != HIPETS_TERM_SRC_OBS && t.source != HIPETS_TERM_SRC_ACT) return fail("reward term %d: unknown source %d", k, t.source);
-            const int width = t.source == HIPETS_TERM_SRC_ACT ? d->act_dim : d->obs_dim;
-            if (t.i < 0 || t.i >= width) return fail("reward term %d: dim i = %d outside [0, %d)", k, t.i, width);
-            if (t.j >= width) return fail("reward term %d: dim j = %d outside [0, %d)", k, t.j, width);
+            const int fn = HIPETS_TERM_WORD_FN(t.fn), op = HIPETS_TERM_WORD_OP(t.fn), level = HIPETS_TERM_WORD_LEVEL(t.fn);
+            if (fn > HIPETS_TERM_FN_SQRT) return fail("reward term %d: unknown fn %d", k, fn);
+            if (op > HIPETS_TERM_OP_DIV) return fail("reward term %d: unknown op %d", k, op);
+            if (level > HIPETS_TERM_MAX_LEVEL) return fail("reward term %d: level %d outside [0, %d]", k, level, HIPETS_TERM_MAX_LEVEL);
+            if (t.source < HIPETS_TERM_SRC_OBS || t.source > HIPETS_TERM_SRC_CONST) return fail("reward term %d: unknown source %d", k, t.source);
             ft->terms[k] = t;
+            if (t.source == HIPETS_TERM_SRC_GROUP || t.source == HIPETS_TERM_SRC_CONST) {
+                if (t.j >= 0) return fail("reward term %d: j = %d is set on a GROUP / CONST entry", k, t.j);
+                if (t.source == HIPETS_TERM_SRC_GROUP) {
+                    if (level == HIPETS_TERM_MAX_LEVEL) return fail("reward term %d: GROUP at level %d has no deeper group to consume", k, level);
+                    if (!open[level + 1]) return fail("reward term %d: GROUP consumes an empty group (level %d has no entry since it was last consumed)", k, level + 1);
+                    open[level + 1] = 0;
+                }
+                ft->terms[k].i = 0;  // (not read)
+            } else {
+                const int width = t.source == HIPETS_TERM_SRC_ACT ? d->act_dim : d->obs_dim;
+                if (t.i < 0 || t.i >= width) return fail("reward term %d: dim i = %d outside [0, %d)", k, t.i, width);
+                if (t.j >= width) return fail("reward term %d: dim j = %d outside [0, %d)", k, t.j, width);
+            }
             if (t.j < 0) ft->terms[k].j = -1;
+            if (op != HIPETS_TERM_OP_ADD && level > 0 && !open[level]) return fail("reward term %d: mul / div into an empty group (level %d starts at 0)", k, level);
+            ++open[level];
+            last[level] = k;
+            if (t.fn > HIPETS_TERM_FN_ABS || t.source > HIPETS_TERM_SRC_ACT) ft->grouped = 1;  // (t.fn: the whole word)
         }
+        for (int level = 1; level <= HIPETS_TERM_MAX_LEVEL; ++level)
+            if (open[level]) return fail("reward term %d: the group at level %d is left open at the end of the table", last[level], level);
         ft->n_terms = d->n_reward_terms;
         ft->bias = d->reward_bias;
         ft->alive_bonus = d->alive_bonus;

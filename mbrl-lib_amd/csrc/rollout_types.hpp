@@ -45,7 +45,8 @@ struct Extras {  // up to kMaxExtras leftover (column tile, row tile) units of o
 struct FormTables {
     int n_terms, n_intervals, require_finite;
     float bias, alive_bonus;
-    int pad_[3];
+    int grouped;  // HIPETS_REW_TERMS: some entry has a level, an op, a source or a function beyond the flat sum of ABI v9 (reward_eval picks its loop by it)
+    int pad_[2];
     hipets_reward_term terms[HIPETS_MAX_REWARD_TERMS];
     hipets_term_interval intervals[HIPETS_MAX_TERM_INTERVALS];
 };

@@ -24,8 +24,20 @@ ENSEMBLE = {"gaussian_mlp": 0, "basic_ensemble": 1}
 PREC = {"f32": 0, "bf16x3": 1, "bf16": 2}
 MODE_EXACT, MODE_FAST, MODE_DEVICE = 0, 1, 2
 MODES = {"exact": MODE_EXACT, "fast": MODE_FAST, "device": MODE_DEVICE}
-TERM_FN = {"linear": 0, "square": 1, "abs": 2}  # HIPETS_TERM_FN_*
-TERM_SRC = {"obs": 0, "act": 1}  # HIPETS_TERM_SRC_*
+TERM_FN = {"linear": 0, "square": 1, "abs": 2, "sin": 3, "cos": 4, "exp": 5, "sqrt": 6}  # HIPETS_TERM_FN_*
+TERM_SRC = {"obs": 0, "act": 1, "group": 2, "const": 3}  # HIPETS_TERM_SRC_*
+TERM_OP = {"add": 0, "mul": 1, "div": 2}  # HIPETS_TERM_OP_*
+TERM_MAX_LEVEL = 2
+
+
+def term_word(fn: int, op: int = 0, level: int = 0) -> int:
+    """hipets_reward_term.fn (HIPETS_TERM_WORD): fn | op << 8 | level << 16; a bare fn code is level 0, add -- the v9 meaning"""
+    return int(fn) | (int(op) << 8) | (int(level) << 16)
+
+
+def term_word_fields(word: int):
+    """(fn, op, level) of a packed word (HIPETS_TERM_WORD_FN / _OP / _LEVEL)"""
+    return word & 0xFF, (word >> 8) & 0xFF, (word & 0xFFFFFFFF) >> 16
 BOX_LO_OPEN, BOX_HI_OPEN = 1, 2  # hipets_term_interval.flags
 MAX_REWARD_TERMS, MAX_TERM_INTERVALS = 64, 64
 COL_FN = {"id": 0, "sin": 1, "cos": 2}  # HIPETS_COL_*

@@ -52,6 +52,15 @@ def member_slots(members: torch.Tensor, n_members: int, device) -> tuple:
     return slots.to(device).contiguous(), max(rpm, 1)
 
 
+def pack_reward_terms(rt: RewardTerms):
+    """The ``hipets_reward_term`` array of a table: ``level`` and ``op`` go into the upper bits of ``fn`` (``_lib.term_word``), so a
+    plain term -- level 0, add -- packs to the bare fn code an ABI v9 client writes."""
+    return (_lib.RewardTermC * max(1, len(rt.terms)))(*[
+        _lib.RewardTermC(_lib.term_word(_lib.TERM_FN[t.fn], _lib.TERM_OP[t.op], t.level), _lib.TERM_SRC[t.source], int(t.i),
+                         -1 if t.j is None else int(t.j), float(t.c), float(t.w))
+        for t in rt.terms])
+
+
 class Engine:
     """One fused planning engine bound to ``device`` (a gfx950 GPU).  Not thread-safe."""
 
@@ -111,9 +120,7 @@ class Engine:
             d.obs_process = _lib.OBS[spec.obs_process]
         if isinstance(spec.reward, RewardTerms):
             rt = spec.reward
-            terms = (_lib.RewardTermC * max(1, len(rt.terms)))(*[
-                _lib.RewardTermC(_lib.TERM_FN[t.fn], _lib.TERM_SRC[t.source], int(t.i), -1 if t.j is None else int(t.j), float(t.c), float(t.w))
-                for t in rt.terms])
+            terms = pack_reward_terms(rt)
             keep.append(terms)
             d.reward_fn, d.reward_terms, d.n_reward_terms = _lib.REW["terms"], terms, len(rt.terms)
             d.reward_bias, d.alive_bonus = rt.bias, rt.alive_bonus

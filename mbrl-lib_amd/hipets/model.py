@@ -50,8 +50,12 @@ class Interval:
 
 @dataclass(frozen=True)
 class RewardTerm:
-    """One term ``w * f(e)`` of a reward table: ``e = v[i] - (v[j] if j is not None else c)`` with ``v`` the step's
-    ``next_obs`` (``source='obs'``) or its action (``'act'``); ``fn``: ``'linear'`` (e), ``'square'`` (e * e) or ``'abs'``."""
+    """One entry ``t = w * f(e)`` of a reward table, combined into accumulator ``level`` (0, 1 or 2) by ``op``: ``A += t``
+    (``'add'``), ``A *= t`` (``'mul'``) or ``A /= t`` (``'div'``).  ``e = v[i] - (v[j] if j is not None else c)`` with ``v`` the
+    step's ``next_obs`` (``source='obs'``) or its action (``'act'``); ``e = c`` (``'const'``); or ``e = A[level + 1] - c``
+    (``'group'``), which consumes the finished deeper group: that accumulator starts over at 0 (``i`` is not read for the last two:
+    pass 0).  ``fn``: ``'linear'`` (e), ``'square'`` (e * e), ``'abs'``, ``'sin'``, ``'cos'``, ``'exp'`` or ``'sqrt'``.  The
+    defaults -- level 0, add -- are a plain term of the sum."""
 
     fn: str
     i: int
@@ -59,10 +63,16 @@ class RewardTerm:
     j: Optional[int] = None
     c: float = 0.0
     source: str = "obs"
+    level: int = 0
+    op: str = "add"
 
 
-TERM_FNS = ("linear", "square", "abs")  # HIPETS_TERM_FN_*
-TERM_SOURCES = ("obs", "act")  # HIPETS_TERM_SRC_*
+TERM_FNS = ("linear", "square", "abs", "sin", "cos", "exp", "sqrt")  # HIPETS_TERM_FN_*
+TERM_SOURCES = ("obs", "act", "group", "const")  # HIPETS_TERM_SRC_*
+TERM_OPS = ("add", "mul", "div")  # HIPETS_TERM_OP_*
+TERM_MAX_LEVEL = 2
+_TERM_FN_TORCH = {"linear": lambda e: e, "square": lambda e: e * e, "abs": torch.abs, "sin": torch.sin, "cos": torch.cos, "exp": torch.exp,
+                  "sqrt": torch.sqrt}
 
 
 @dataclass(frozen=True)
@@ -104,7 +114,13 @@ class RewardTerms:
     order in fp32 starting from ``bias`` (:class:`RewardTerm`); the alive bonus is added last and only when it is non-zero,
     with ``done = termination_fn(act, next_obs)`` -- the step's own termination test, which must then be the
     :class:`BoxTermination` the model terminates with (``mbrl.env.reward_fns.cartpole`` is ``alive_bonus=1`` over the
-    cartpole box).  NaN and inf propagate as IEEE arithmetic does.  At most 64 terms."""
+    cartpole box).  NaN and inf propagate as IEEE arithmetic does.  At most 64 terms.
+
+    With ``level`` / ``op`` / the ``'group'`` and ``'const'`` sources (:class:`RewardTerm`) the table is a small expression form
+    over three accumulators -- ``A0`` starts at ``bias``, ``A1`` and ``A2`` at 0, ``r = A0`` -- evaluated entry by entry in table
+    order: products, quotients, ``sqrt`` of a sum of squares, ``exp`` of a group, ``sin`` / ``cos`` of a dim.  Well formed when a
+    ``'group'`` entry sits at level 0 or 1 and consumes a non-empty group, ``'mul'`` / ``'div'`` do not go into an empty group at
+    level 1 or 2, no group is left open at the end, and ``'group'`` / ``'const'`` entries leave ``j`` unset."""
 
     terms: Tuple[RewardTerm, ...] = ()
     bias: float = 0.0
@@ -120,17 +136,39 @@ class RewardTerms:
     def validate(self, obs_dim: Optional[int] = None, act_dim: Optional[int] = None):
         if len(self.terms) > MAX_REWARD_TERMS:
             raise UnsupportedModelError(f"RewardTerms: {len(self.terms)} terms, at most {MAX_REWARD_TERMS}")
+        open_, last = [0] * (TERM_MAX_LEVEL + 1), [0] * (TERM_MAX_LEVEL + 1)  # entries of a level's open group since it was consumed; its latest entry
         for k, t in enumerate(self.terms):
             if t.fn not in TERM_FNS:
                 raise UnsupportedModelError(f"RewardTerms term {k}: fn {t.fn!r} is not one of {TERM_FNS}")
             if t.source not in TERM_SOURCES:
                 raise UnsupportedModelError(f"RewardTerms term {k}: source {t.source!r} is not one of {TERM_SOURCES}")
-            width = act_dim if t.source == "act" else obs_dim
-            for name, v in (("i", t.i), ("j", t.j)):
-                if v is None and name == "j":
-                    continue
-                if v is None or int(v) != v or v < 0 or (width is not None and v >= width):
-                    raise UnsupportedModelError(f"RewardTerms term {k}: dim {name} = {v} outside [0, {width if width is not None else t.source + '_dim'})")
+            if t.op not in TERM_OPS:
+                raise UnsupportedModelError(f"RewardTerms term {k}: op {t.op!r} is not one of {TERM_OPS}")
+            if isinstance(t.level, bool) or not isinstance(t.level, (int, np.integer)) or not 0 <= t.level <= TERM_MAX_LEVEL:
+                raise UnsupportedModelError(f"RewardTerms term {k}: level {t.level!r} outside [0, {TERM_MAX_LEVEL}]")
+            if t.source in ("group", "const"):
+                if t.j is not None:
+                    raise UnsupportedModelError(f"RewardTerms term {k}: j = {t.j} is set on a {t.source!r} entry")
+                if t.source == "group":
+                    if t.level == TERM_MAX_LEVEL:
+                        raise UnsupportedModelError(f"RewardTerms term {k}: 'group' at level {t.level} has no deeper group to consume")
+                    if not open_[t.level + 1]:
+                        raise UnsupportedModelError(f"RewardTerms term {k}: 'group' consumes an empty group (level {t.level + 1} has no entry since it was last consumed)")
+                    open_[t.level + 1] = 0
+            else:
+                width = act_dim if t.source == "act" else obs_dim
+                for name, v in (("i", t.i), ("j", t.j)):
+                    if v is None and name == "j":
+                        continue
+                    if v is None or int(v) != v or v < 0 or (width is not None and v >= width):
+                        raise UnsupportedModelError(f"RewardTerms term {k}: dim {name} = {v} outside [0, {width if width is not None else t.source + '_dim'})")
+            if t.op != "add" and t.level > 0 and not open_[t.level]:
+                raise UnsupportedModelError(f"RewardTerms term {k}: {t.op!r} into an empty group (level {t.level} starts at 0)")
+            open_[t.level] += 1
+            last[t.level] = k
+        for level in range(1, TERM_MAX_LEVEL + 1):
+            if open_[level]:
+                raise UnsupportedModelError(f"RewardTerms term {last[level]}: the group at level {level} is left open at the end of the table")
         if self.alive_bonus != 0.0 and not isinstance(self.termination_fn, BoxTermination):
             raise UnsupportedModelError("RewardTerms: alive_bonus != 0 needs termination_fn=BoxTermination(...), the model's own termination")
         if self.termination_fn is not None and isinstance(self.termination_fn, BoxTermination):
@@ -138,12 +176,21 @@ class RewardTerms:
 
     def __call__(self, act: torch.Tensor, next_obs: torch.Tensor) -> torch.Tensor:
         s, a = next_obs.float(), act.float()
-        r = torch.full((len(s),), self.bias, dtype=torch.float32, device=s.device)
+        zero = torch.zeros(len(s), dtype=torch.float32, device=s.device)
+        acc = [torch.full((len(s),), self.bias, dtype=torch.float32, device=s.device), zero, zero]  # A0, A1, A2
         for t in self.terms:
-            v = a if t.source == "act" else s
-            e = v[:, t.i] - (v[:, t.j] if t.j is not None else t.c)
-            f = e * e if t.fn == "square" else (e.abs() if t.fn == "abs" else e)
-            r = r + t.w * f
+            if t.source == "const":
+                e = zero + t.c
+            elif t.source == "group":
+                e = acc[t.level + 1] - t.c
+                acc[t.level + 1] = zero
+            else:
+                v = a if t.source == "act" else s
+                e = v[:, t.i] - (v[:, t.j] if t.j is not None else t.c)
+            f = _TERM_FN_TORCH[t.fn](e)
+            term = t.w * f
+            acc[t.level] = acc[t.level] + term if t.op == "add" else (acc[t.level] * term if t.op == "mul" else acc[t.level] / term)
+        r = acc[0]
         if self.alive_bonus != 0.0:
             r = r + self.alive_bonus * (~self.termination_fn(act, next_obs))[:, 0].float()
         return r.view(-1, 1)
