@@ -594,6 +594,10 @@ typedef struct {
  * eps, the traces and the in-kernel draws are indexed by the launch-global row (candidate * P + particle).          */
 int hipets_planet_rollout(hipets_engine* e, const float* actions, const float* latent0, const float* belief0, int32_t pop,
                           int32_t horizon, int32_t num_particles, const hipets_planet_opts* opts, float* returns, void* stream);
+/* Diagnostic: which instance of the PlaNet rollout kernel the next hipets_planet_rollout (and every PlaNet plan) launches for the
+ * model set last: *is_static = 1 the instance specialised for the tile counts of conf/dynamics_model/planet.yaml, 0 the run-time
+ * generic one (always with HIPETS_PLANET_GENERIC=1 in the environment).  The same bits either way.                              */
+int hipets_planet_kernel_class(hipets_engine* e, int32_t* is_static);
 
 /* The PlaNet planner as one call: CEMOptimizer.optimize (trajectory_opt.py:142-188; the PlaNet configs use the clipped-normal
  * branch :116-120, conf/overrides/planet_cheetah_run.yaml:29-35) with hipets_planet_rollout as objective, no host round trip.

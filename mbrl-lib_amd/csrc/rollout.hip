@@ -398,6 +398,14 @@ int rollout_impl(hipets_engine* e, const float* actions, const float* s0, int32_
     return 0;
 }
 
+// Which PlaNet kernel instance a launch on this engine runs: the STATIC one for models with conf's tile counts (planet_static_shape, decided
+// at hipets_planet_set_model), unless HIPETS_PLANET_GENERIC=1 asks for the run-time generic instance whatever the shapes -- tests compare
+// the two bit for bit.  The one rule of planet_rollout_impl's launch and of hipets_planet_kernel_class.
+static bool planet_launches_static(const hipets_engine* e) {
+    const char* pg = std::getenv("HIPETS_PLANET_GENERIC");
+    return e->planet_static && !(pg && pg[0] == '1');
+}
+
 int planet_rollout_impl(hipets_engine* e, const float* actions, const float* latent0, const float* belief0, int32_t pop, int32_t H,
                         int32_t P, const hipets_planet_opts* o, float* returns, hipStream_t st) {
     const int n_env = std::max(o->n_env, 1);
@@ -424,9 +432,7 @@ int planet_rollout_impl(hipets_engine* e, const float* actions, const float* lat
     ra.phase_cycles = reinterpret_cast<long long*>(o->phase_cycles);
     const size_t lds = planet_smem_bytes(e->pd.ld);
     const int nwg = (int)((B + kTile - 1) / kTile);
-    // (HIPETS_PLANET_GENERIC=1: the run-time generic instance whatever the shapes -- tests compare the two bit for bit)
-    const char* pg = std::getenv("HIPETS_PLANET_GENERIC");
-    HCHECK(launch_planet_rollout(nwg, (unsigned)lds, (int)e->lds_max, e->pd, ra, st, e->planet_static && !(pg && pg[0] == '1')));
+    HCHECK(launch_planet_rollout(nwg, (unsigned)lds, (int)e->lds_max, e->pd, ra, st, planet_launches_static(e)));
     if (!returns) return 0;
     hipLaunchKernelGGL(particle_mean_kernel, dim3((pop + 255) / 256), dim3(256), 0, st, e->totals.as<float>(), returns, pop, P);
     HCHECK(hipGetLastError());
@@ -584,6 +590,13 @@ int hipets_planet_rollout(hipets_engine* e, const float* actions, const float* l
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
     return planet_rollout_impl(e, actions, latent0, belief0, pop, H, P, o, returns, st);
+}
+
+int hipets_planet_kernel_class(hipets_engine* e, int32_t* is_static) {
+    if (!e || !e->has_planet) return fail("engine has no PlaNet model (call hipets_planet_set_model)");
+    if (!is_static) return fail("null argument");
+    *is_static = planet_launches_static(e) ? 1 : 0;
+    return 0;
 }
 
 }  // extern "C"

@@ -196,6 +196,7 @@ SYMBOLS = {
                                            _P, _P]),
     "hipets_planet_set_model": (C.c_int, [_P, C.POINTER(PlanetDesc), _P]),
     "hipets_planet_rollout": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlanetOpts), _P, _P]),
+    "hipets_planet_kernel_class": (C.c_int, [_P, C.POINTER(C.c_int32)]),
     "hipets_plan_planet_cem": (C.c_int, [_P, C.POINTER(CemParams), _P, _P, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64, _P, _P]),
     "hipets_plan_planet_cem_batched": (C.c_int, [_P, C.POINTER(CemParams), C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64,
                                                  _P, _P]),

@@ -707,6 +707,13 @@ class Engine:
                                                        C.byref(o), _ptr(out), _stream(dev)))
         return out
 
+    def planet_kernel_class(self) -> str:
+        """Which instance of the PlaNet rollout kernel the next launch runs for the model set last: "static" (specialised for the tile
+        counts of conf/dynamics_model/planet.yaml) or "generic" (every other model, and every model under HIPETS_PLANET_GENERIC=1)."""
+        is_static = C.c_int32(-1)
+        _lib.check(self._lib.hipets_planet_kernel_class(self._h, C.byref(is_static)))
+        return "static" if is_static.value else "generic"
+
     def plan_planet_cem(self, p: CemParams, x0, lower, upper, latent0: torch.Tensor, belief0: torch.Tensor, num_particles: int,
                         seed: int = 0, plan_id: int = 0, out: Optional[torch.Tensor] = None, n_env: int = 1) -> torch.Tensor:
         """Whole CEM plan over the PlaNet latent model on the device.  x0 [H, A] with n_env = 1: hipets_plan_planet_cem; else

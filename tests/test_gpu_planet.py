@@ -56,16 +56,25 @@ def test_planet_rollout_matches_oracle(engine, latent, action, belief, hidden, p
     latent0, belief0 = torch.randn(1, latent, generator=g) * 0.3, torch.randn(1, belief, generator=g) * 0.3
     actions = torch.rand(pop, H, action, generator=g) * 2 - 1
     eps = torch.randn(H, pop * P, latent, generator=g)
-    ref = pl.planet_rollout(pm, actions, latent0, belief0, P, eps=eps)
-    out = engine.planet_rollout(actions.to(DEV), latent0.to(DEV), belief0.to(DEV), P, eps=eps.to(DEV))
+    trace = {}
+    ref = pl.planet_rollout(pm, actions, latent0, belief0, P, eps=eps, trace=trace)
+    B = pop * P
+    tl, tb, tr = torch.zeros(H, B, latent, device=DEV), torch.zeros(H, B, belief, device=DEV), torch.zeros(H, B, device=DEV)
+    out = engine.planet_rollout(actions.to(DEV), latent0.to(DEV), belief0.to(DEV), P, eps=eps.to(DEV), trace_latent=tl, trace_belief=tb,
+                                trace_rewards=tr)
     close(out, ref)
+    # all three traces at EVERY step under T1 (tests/test_gpu_step.py), not the returns alone
+    for name, got, want in (("latent", tl, torch.stack(trace["latent"])), ("belief", tb, torch.stack(trace["belief"])),
+                            ("rewards", tr, torch.stack(trace["rewards"]).squeeze(-1))):
+        assert torch.isfinite(got).all(), name
+        assert torch.allclose(got.cpu(), want, rtol=1e-5, atol=2e-6), (name, (got.cpu() - want).abs().max().item())
     # deterministic rollouts (sample(deterministic=True)): latent = prior mean
     ref_det = pl.planet_rollout(pm, actions, latent0, belief0, P, eps=torch.zeros_like(eps))
     close(engine.planet_rollout(actions.to(DEV), latent0.to(DEV), belief0.to(DEV), P, sample=False), ref_det)
 
 
 @pytest.mark.parametrize("pop,P,H", [(1000, 1, 12), (37, 3, 4)])
-def test_planet_static_instance_equals_the_generic_kernel_bitwise(engine, pop, P, H):
+def test_planet_static_instance_equals_the_generic_kernel_bitwise(engine, monkeypatch, pop, P, H):
     """Models with conf/dynamics_model/planet.yaml's shapes (latent 30, belief 200, hidden 200, action 6: what every planet_*.yaml override
     plans on) run a kernel instance with every op's tile / chunk counts and the LDS row stride as compile-time facts (planet.hpp STATIC,
     round 5); HIPETS_PLANET_GENERIC=1 forces the run-time generic instance.  Same tile -> wave deal, same k order: the same bits, with
@@ -81,12 +90,11 @@ def test_planet_static_instance_equals_the_generic_kernel_bitwise(engine, pop, P
         return (engine.planet_rollout(actions, latent0, belief0, P, eps=eps).clone(), engine.planet_rollout(actions, latent0, belief0, P, seed=4, stream_id=2).clone(),
                 engine.planet_rollout(actions, latent0, belief0, P, sample=False).clone())
 
+    assert engine.planet_kernel_class() == "static"  # (or the comparison below is the generic kernel with itself)
     static = three()
-    os.environ["HIPETS_PLANET_GENERIC"] = "1"
-    try:
-        generic = three()
-    finally:
-        del os.environ["HIPETS_PLANET_GENERIC"]
+    monkeypatch.setenv("HIPETS_PLANET_GENERIC", "1")
+    assert engine.planet_kernel_class() == "generic"
+    generic = three()
     for a, b in zip(static, generic):
         assert torch.isfinite(a).all() and torch.equal(a, b)
     ref = pl.planet_rollout(pm, actions.cpu(), latent0.cpu(), belief0.cpu(), P, eps=eps.cpu())
@@ -105,6 +113,12 @@ def test_planet_fast_mode_replayed_and_seeded(engine):
     c = engine.planet_rollout(actions, latent0, belief0, 2, seed=5, stream_id=8)
     assert torch.equal(a, b) and not torch.equal(a, c)
     assert torch.isfinite(a).all()
+    # the replay: the oracle fed the normals the kernel drew for (seed 5, stream 7) and for (5, 8)
+    for out, stream in ((a, 7), (c, 8)):
+        out = out.cpu()
+        eps = engine_normals(engine, 6, 50 * 2, 12, 5, stream)
+        assert eps.shape == (6, 100, 12)
+        close(out, pl.planet_rollout(pm, actions.cpu(), latent0.cpu(), belief0.cpu(), 2, eps=eps))
 
 
 def test_planet_eval_fn_and_cem_agent(engine):

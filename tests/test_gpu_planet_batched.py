@@ -60,6 +60,8 @@ def test_batched_planet_rollout_injected_eps(engine, monkeypatch, dims, pop_env,
         out = engine.planet_rollout(actions, lat_d, bel_d, P, eps=eps, trace_latent=tl, trace_belief=tb, trace_rewards=tr, n_env=n_env)
         return out.clone(), tl, tb, tr
 
+    # conf runs the STATIC instance, so the comparison with the generic one at the end is between two kernels
+    assert engine.planet_kernel_class() == ("static" if dims == CONF else "generic")
     static = batched()
     assert torch.isfinite(static[0]).all()
     for e_ in range(n_env):
@@ -74,6 +76,7 @@ def test_batched_planet_rollout_injected_eps(engine, monkeypatch, dims, pop_env,
     if n_env > 1:  # the environments really start from different states
         assert not torch.equal(static[0][:pop_env], static[0][pop_env:2 * pop_env])
     monkeypatch.setenv("HIPETS_PLANET_GENERIC", "1")
+    assert engine.planet_kernel_class() == "generic"
     generic = batched()
     for a, b in zip(static, generic):
         assert torch.equal(a, b)
