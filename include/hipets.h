@@ -285,6 +285,19 @@ int hipets_rollout(hipets_engine* e, const float* actions, const float* s0, int3
 int hipets_step(hipets_engine* e, const float* obs, const float* actions, int32_t batch, const hipets_rollout_opts* opts,
                 float* next_obs, float* rewards, uint8_t* dones, void* stream);
 
+/* ---- model_env.py:186-191 over a finished trajectory: masked returns for rewards / terminations evaluated outside the kernel ----
+ * For rollouts whose reward_fn / termination_fn are the caller's own code: run hipets_rollout once with opts->trace_next_obs (and
+ * trace_rewards), evaluate the callables over all H * B traced rows, and reduce here.  rewards DEVICE [H,B] f32 and dones DEVICE [H,B]
+ * uint8 (non-zero = the row terminates at that step), B = pop * num_particles, row c * num_particles + p = particle p of candidate c.
+ * Per row, for t = 0 .. H-1 in order:  r = terminated ? 0 : rewards[t][row];  terminated |= dones[t][row] != 0;  total += r  -- the
+ * zeroing is a select (the reference assigns rewards[terminated] = 0): a NaN or inf reward after termination adds exactly 0, one before
+ * it propagates, and the reward of the terminating step itself counts.  returns DEVICE [pop] = the mean of a candidate's
+ * num_particles row totals, the same sequential f32 sum and division as hipets_rollout's own (bit-identical to it on the same
+ * rewards).  Optional outputs (NULL = not wanted): row_totals DEVICE [B] f32; first_done DEVICE [B] int32 = the first step with
+ * dones != 0, horizon if none.  Needs no model.  (An entry point of its own: no struct changes, HIPETS_ABI_VERSION stays.)          */
+int hipets_trajectory_returns(hipets_engine* e, const float* rewards, const uint8_t* dones, int32_t pop, int32_t horizon,
+                              int32_t num_particles, float* returns, float* row_totals, int32_t* first_done, void* stream);
+
 /* geometry the FAST kernel will use for (pop, P): workgroups and rows per group (for member_schedule).  rows_per_group 0: the
  * library's own choice for a DEFAULT call (hipets_rollout without injected eps / traces, the fused plans); > 0: forced.
  * rows_per_group -1: the choice for calls that run the general kernel layout whatever the model -- hipets_step, rollouts with

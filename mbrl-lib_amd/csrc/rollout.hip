@@ -1,5 +1,5 @@
 // rollout.hip -- rollouts of the C ABI (include/hipets.h): launch geometry, the binding from a call's mode to the kernel's arguments,
-// hipets_rollout / hipets_step / hipets_planet_rollout, the geometry queries and the exports of the device-side randomness.  The one
+// hipets_rollout / hipets_step / hipets_planet_rollout / hipets_trajectory_returns, the geometry queries and the exports of the device-side randomness.  The one
 // unit that includes residency.hpp (the launcher of every rollout kernel instance) and rollout_helpers.hpp (the small kernels around it).
 #include <hip/hip_ext.h>
 
@@ -538,6 +538,35 @@ int hipets_step(hipets_engine* e, const float* obs, const float* actions, int32_
     HCHECK(hipMemsetAsync(rewards, 0, (size_t)B * 4, st));
     HCHECK(hipMemsetAsync(dones, 0, (size_t)B, st));
     return launch_rollout(e, g.R, g.domains * g.groups, g.lds, ra, st);
+}
+
+int hipets_trajectory_returns(hipets_engine* e, const float* rewards, const uint8_t* dones, int32_t pop, int32_t H, int32_t P, float* returns,
+                              float* row_totals, int32_t* first_done, void* stream) {
+    if (!e || !rewards || !dones || !returns) return fail("null argument");
+    if (pop < 1 || H < 1 || P < 1) return fail("bad pop/horizon/particles");
+    const long long B = (long long)pop * P;
+    if (B > 0x7FFFFFFF) return fail("batch too large");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HCHECK(hipSetDevice(e->device));
+    ENTER_STREAM(e, st);  // (the two-pass form below may run on the engine's row totals)
+    if (P <= kReturnsThreads) {
+        const int cpb = kReturnsThreads / P;  // whole candidates per workgroup
+        hipLaunchKernelGGL(trajectory_returns_kernel, dim3((unsigned)((pop + cpb - 1) / cpb)), dim3(kReturnsThreads), 0, st, rewards, dones, pop, H, P, cpb,
+                           returns, row_totals, first_done);
+        HCHECK(hipGetLastError());
+        return 0;
+    }
+    // a candidate's particles do not fit one workgroup: the row pass, then the particle means
+    if (!row_totals) {
+        if (e->totals.ensure((size_t)B * 4)) return 1;
+        row_totals = e->totals.as<float>();
+    }
+    hipLaunchKernelGGL(trajectory_returns_kernel, dim3((unsigned)((B + kReturnsThreads - 1) / kReturnsThreads)), dim3(kReturnsThreads), 0, st, rewards, dones,
+                       pop, H, P, 0, static_cast<float*>(nullptr), row_totals, first_done);
+    HCHECK(hipGetLastError());
+    hipLaunchKernelGGL(particle_mean_kernel, dim3((pop + 255) / 256), dim3(256), 0, st, row_totals, returns, pop, P);
+    HCHECK(hipGetLastError());
+    return 0;
 }
 
 int hipets_fast_schedule(hipets_engine* e, int32_t H, int32_t nwg, uint64_t seed, uint64_t stream_id, int32_t* schedule,

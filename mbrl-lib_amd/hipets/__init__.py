@@ -27,6 +27,7 @@ from .planning import (  # noqa: F401
     BatchedICEMAgent,
     BatchedMPPIAgent,
     CEMOptimizer,
+    CallableTrajectoryEvalFn,
     HipTrajectoryEvalFn,
     ICEMOptimizer,
     MPPIOptimizer,

@@ -304,6 +304,31 @@ class Engine:
                                              _ptr(dones), _stream(dev)))
         return next_obs, rewards.view(B, 1), dones.view(B, 1).bool()
 
+    def trajectory_returns(self, rewards: torch.Tensor, dones: torch.Tensor, pop: int, num_particles: int, *, row_totals: bool = False,
+                           first_done: bool = False):
+        """model_env.py:186-191 over a finished trajectory (hipets_trajectory_returns): ``rewards`` f32 [H, B] and ``dones`` bool or
+        uint8 [H, B] (B = pop * num_particles, row c * P + p) -> ``returns`` f32 [pop]: per row the rewards up to and including the
+        first step whose ``dones`` is set, summed in step order, then the particle mean of ``Engine.rollout``'s own returns.  With
+        ``row_totals`` / ``first_done`` the result is the tuple (returns, row totals f32 [B] or None, first terminating step int32 [B]
+        -- H where a row never terminates -- or None)."""
+        dev = self.device
+        if not isinstance(rewards, torch.Tensor) or rewards.ndim != 2:
+            raise ValueError("rewards must be a [H, B] tensor")
+        H, B = (int(v) for v in rewards.shape)
+        if pop < 1 or num_particles < 1 or pop * num_particles != B:
+            raise ValueError(f"rewards holds {B} rows per step, pop x num_particles = {pop} x {num_particles}")
+        _check_dev(rewards, torch.float32, dev, "rewards")
+        if isinstance(dones, torch.Tensor) and dones.dtype == torch.bool:
+            dones = dones.view(torch.uint8)  # (one byte per element, 0 / 1)
+        _check_dev(dones, torch.uint8, dev, "dones", (H, B))
+        out = torch.empty(pop, dtype=torch.float32, device=dev)
+        tot = torch.empty(B, dtype=torch.float32, device=dev) if row_totals else None
+        first = torch.empty(B, dtype=torch.int32, device=dev) if first_done else None
+        with torch.cuda.device(dev):
+            _lib.check(self._lib.hipets_trajectory_returns(self._h, _ptr(rewards), _ptr(dones), int(pop), H, int(num_particles), _ptr(out),
+                                                           _ptr(tot), _ptr(first), _stream(dev)))
+        return (out, tot, first) if (row_totals or first_done) else out
+
     def fast_geometry(self, pop: int, num_particles: int, horizon: int, rows_per_group: int = 0):
         nwg, r = C.c_int32(), C.c_int32()
         _lib.check(self._lib.hipets_fast_geometry(self._h, pop, num_particles, horizon, rows_per_group, C.byref(nwg),

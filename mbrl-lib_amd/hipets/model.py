@@ -271,7 +271,7 @@ class ModelSpec:
     # None => learned reward (last model output); "none" => caller's callable; a RewardTerms => the model's own term table
     reward: Union[str, None, RewardTerms] = "halfcheetah"
     termination: Union[str, BoxTermination] = "no_termination"  # (a BoxTermination => the model's own healthy box)
-    custom_reward_fn: Optional[object] = None  # arbitrary torch callables (act, next_obs) -> [B,1]; UNFUSED path only
+    custom_reward_fn: Optional[object] = None  # arbitrary torch callables (act, next_obs) -> [B,1]; the unfused / callable objectives only
     custom_termination_fn: Optional[object] = None
     # "gaussian_mlp": one GaussianMLP with E members (balanced shuffles, batch % members rule, elites).
     # "basic_ensemble": mbrl.models.BasicEnsemble of E single-member GaussianMLPs: every row draws its member

@@ -14,7 +14,7 @@ import torch
 
 from . import reference_draws as rd
 from .engine import Engine, get_engine
-from .model import (ModelSpec, PlaNetSpec, UnsupportedModelError, is_planet_model, model_version, planet_version,
+from .model import (BoxTermination, ModelSpec, PlaNetSpec, UnsupportedModelError, is_planet_model, model_version, planet_version,
                     spec_from_model_env, spec_from_planet_model)
 
 
@@ -100,7 +100,129 @@ class _EnsembleObjective(_Objective):
             )
 
 
-class HipTrajectoryEvalFn(_EnsembleObjective):
+def closed_form_dones(spec: ModelSpec, states: torch.Tensor) -> torch.Tensor:
+    """The spec's closed-form termination over ``states`` [N, obs] -> bool [N]: the torch restatement of the kernels' ``term_eval``
+    (csrc/closed_forms.hpp; mbrl/env/termination_fns.py).  Comparisons of the same float32 values against the same float32
+    constants, so the flags are the kernel's own."""
+    s, term = states, spec.termination
+    finite = lambda: torch.isfinite(s).all(dim=1)  # noqa: E731
+    if isinstance(term, BoxTermination):
+        ok = finite() if term.require_finite else torch.ones(s.shape[0], dtype=torch.bool, device=s.device)
+        for iv in term.intervals:
+            x = s[:, iv.dim]
+            ok = ok & ((x > iv.lo) if iv.lo_open else (x >= iv.lo)) & ((x < iv.hi) if iv.hi_open else (x <= iv.hi))
+        return ~ok
+    if term == "cartpole":
+        thr = 12.0 * 2.0 * 3.14159265358979323846 / 360.0
+        return ~((s[:, 0] > -2.4) & (s[:, 0] < 2.4) & (s[:, 2] > -thr) & (s[:, 2] < thr))
+    if term == "inverted_pendulum":
+        return ~(finite() & (s[:, 1].abs() <= 0.2))
+    if term == "hopper":
+        return ~(finite() & (s[:, 1:].abs() < 100.0).all(dim=1) & (s[:, 0] > 0.7) & (s[:, 1].abs() < 0.2))
+    if term == "walker2d":
+        return ~((s[:, 0] > 0.8) & (s[:, 0] < 2.0) & (s[:, 1] > -1.0) & (s[:, 1] < 1.0))
+    if term == "ant":
+        return ~(finite() & (s[:, 0] >= 0.2) & (s[:, 0] <= 1.0))
+    if term == "humanoid":
+        return (s[:, 0] < 1.0) | (s[:, 0] > 2.0)
+    if term == "no_termination":
+        return torch.zeros(s.shape[0], dtype=torch.bool, device=s.device)
+    raise UnsupportedModelError(f"no restatement of termination {term!r}")
+
+
+class _RolloutObjective(_EnsembleObjective):
+    """What the objectives that run a whole horizon per ``hipets_rollout`` call share: the randomness modes and their draws
+    (``_rollout``), and the predicted trajectory of one call read off the rollout kernel's taps (``_traced_rollout``, ``_trajectory``)."""
+
+    max_trajectory_bytes = 2 << 30
+
+    def __init__(self, model, num_particles: int, engine: Optional[Engine] = None, mode: str = "device",
+                 seed: int = 0, device=None, rng: Optional[torch.Generator] = None):
+        if mode not in ("fast", "device", "exact", "exact_device"):
+            raise ValueError("mode must be 'fast', 'device', 'exact' or 'exact_device'")
+        self.mode = mode
+        self.rollout_kw = {}  # extra Engine.rollout arguments of every call (tests pin rows_per_group / generic_kernel)
+        self._taps = None
+        super().__init__(model, num_particles, engine, seed, device)
+        if rng is None and self._live is not None:
+            rng = getattr(model, "_rng", None)
+        self._rng = rng
+
+    def _prep(self, action_sequences: torch.Tensor) -> torch.Tensor:
+        self.bind_model()
+        a = _device_f32(action_sequences, self.device)
+        self.check_batch(a.shape[0])
+        return a
+
+    @property
+    def _rollout_mode(self) -> Optional[str]:
+        """'fast' / 'device' when the rollouts draw their randomness in-kernel from (seed, stream_id), else None."""
+        if self.mode == "fast":
+            return "fast"
+        if self.mode in ("device", "exact_device") and _has_device_mode(self.spec):
+            return "device"
+        return None
+
+    def _rollout(self, a: torch.Tensor, initial_state: np.ndarray, **kw) -> torch.Tensor:
+        """One ``Engine.rollout`` of this call's stream (``self.calls``) in the objective's mode; ``kw``: the taps."""
+        kw = {**self.rollout_kw, **kw}
+        if self._rollout_mode is not None:
+            return self.engine.rollout(a, initial_state, self.num_particles, mode=self._rollout_mode, seed=self.seed, stream_id=self.calls, **kw)
+        pop, H, _ = a.shape
+        B = pop * self.num_particles
+        if self.mode in ("device", "exact_device"):  # BasicEnsemble models only: torch's device generator, not reference order
+            members, eps = rd.device_generator_draws(self.spec, B, H, self._device_rng())
+            return self.engine.rollout(a, initial_state, self.num_particles, mode="exact", members=members, eps=eps, **kw)
+        perms, members, eps = rd.rollout_draws(self.spec, B, H, self._cpu_rng())
+        if perms is not None:
+            perms = perms.to(self.device)
+        if eps is not None:
+            eps = eps.to(self.device)
+        return self.engine.rollout(a, initial_state, self.num_particles, mode="exact", perms=perms, members=members, eps=eps, **kw)
+
+    def _device_rng(self):
+        if not hasattr(self, "_dev_rng"):
+            self._dev_rng = torch.Generator(device=self.device).manual_seed(self.seed)
+        return self._dev_rng
+
+    def _cpu_rng(self):
+        if self._rng is not None and self._rng.device.type == "cpu":
+            return self._rng
+        if not hasattr(self, "_own_rng"):
+            self._own_rng = torch.Generator().manual_seed(self.seed)
+        return self._own_rng
+
+    # ---- the predicted trajectory of one call ----
+    def _traced_rollout(self, a: torch.Tensor, initial_state: np.ndarray):
+        """This call's rollout with both taps set: (next_obs [H, B, obs], rewards [H, B]) -- every row's predicted states and the
+        kernel's own reward (learned or closed form) before termination masking --, in buffers the objective owns and reuses
+        across calls of the same (H, B)."""
+        pop, H, _ = a.shape
+        B, obs = pop * self.num_particles, self.spec.obs_dim
+        nbytes = H * B * (obs + 1) * 4
+        if nbytes > self.max_trajectory_bytes:
+            raise ValueError(f"the trajectory of this call -- horizon {H} x {B} rows x ({obs} + 1) floats = {nbytes} bytes -- exceeds "
+                             f"max_trajectory_bytes = {self.max_trajectory_bytes}")
+        if self._taps is None or tuple(self._taps[0].shape) != (H, B, obs) or self._taps[0].device != self.device:
+            self._taps = (torch.empty(H, B, obs, dtype=torch.float32, device=self.device),
+                          torch.empty(H, B, dtype=torch.float32, device=self.device))
+        next_obs, rewards = self._taps
+        self._rollout(a, initial_state, trace_next_obs=next_obs, trace_rewards=rewards)
+        return next_obs, rewards
+
+    def _trajectory(self, initial_state: np.ndarray, action_sequences: torch.Tensor, details: bool):
+        """One evaluation through the taps (the hook of a kind of objective: rewards / dones of the traced states)."""
+        raise NotImplementedError
+
+    def trajectories(self, initial_state: np.ndarray, action_sequences: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """The predicted trajectories of ONE evaluation (the model side of ``mbrl.util.common.rollout_model_env``): ``next_obs``
+        [H, B, obs], ``rewards`` [H, B] (before termination masking), ``dones`` bool [H, B], ``first_done`` int32 [B] (the first
+        terminating step, H if none), ``row_totals`` [B], ``returns`` [pop]; B = pop * num_particles, row c * P + p.  Counts as
+        a call (it consumes the next stream, and returns what ``__call__`` would have); the views are valid until the next call."""
+        return self._trajectory(initial_state, action_sequences, True)
+
+
+class HipTrajectoryEvalFn(_RolloutObjective):
     """``trajectory_eval_fn(initial_state, action_sequences) -> Tensor[B]`` (mbrl/types.py:15).
 
     Built from a live ``mbrl.models.ModelEnv`` (weights are re-snapshotted whenever
@@ -122,31 +244,11 @@ class HipTrajectoryEvalFn(_EnsembleObjective):
       member maps with torch's device generator).
     """
 
-    def __init__(self, model, num_particles: int, engine: Optional[Engine] = None, mode: str = "device",
-                 seed: int = 0, device=None, rng: Optional[torch.Generator] = None):
-        if mode not in ("fast", "device", "exact", "exact_device"):
-            raise ValueError("mode must be 'fast', 'device', 'exact' or 'exact_device'")
-        self.mode = mode
-        super().__init__(model, num_particles, engine, seed, device)
-        if rng is None and self._live is not None:
-            rng = getattr(model, "_rng", None)
-        self._rng = rng
-
-    def _prep(self, action_sequences: torch.Tensor) -> torch.Tensor:
-        self.bind_model()
-        a = _device_f32(action_sequences, self.device)
-        self.check_batch(a.shape[0])
-        return a
-
     @property
     def kernel_mode(self) -> Optional[str]:
         """'fast' / 'device' when the objective draws its randomness in-kernel from (seed, stream_id) -- the modes the
         fused plans can run --, else None."""
-        if self.mode == "fast":
-            return "fast"
-        if self.mode in ("device", "exact_device") and _has_device_mode(self.spec):
-            return "device"
-        return None
+        return self._rollout_mode
 
     def evaluate_seeded(self, initial_state: np.ndarray, action_sequences: torch.Tensor, seed: int, stream_id: int) -> torch.Tensor:
         """One objective evaluation with explicit counter-based randomness: what iteration ``stream_id`` of a fused plan
@@ -157,31 +259,18 @@ class HipTrajectoryEvalFn(_EnsembleObjective):
     def __call__(self, initial_state: np.ndarray, action_sequences: torch.Tensor) -> torch.Tensor:
         a = self._prep(action_sequences)
         self.calls += 1
-        if self.kernel_mode is not None:
-            return self.engine.rollout(a, initial_state, self.num_particles, mode=self.kernel_mode, seed=self.seed, stream_id=self.calls)
+        return self._rollout(a, initial_state)
+
+    def _trajectory(self, initial_state, action_sequences, details):
+        """The kernel's own rewards off the tap, the spec's closed-form termination restated over the traced states, reduced by
+        hipets_trajectory_returns: ``returns`` are the bits of the untapped call of the same stream."""
+        a = self._prep(action_sequences)
+        self.calls += 1
         pop, H, _ = a.shape
-        B = pop * self.num_particles
-        if self.mode in ("device", "exact_device"):  # BasicEnsemble models only: torch's device generator, not reference order
-            members, eps = rd.device_generator_draws(self.spec, B, H, self._device_rng())
-            return self.engine.rollout(a, initial_state, self.num_particles, mode="exact", members=members, eps=eps)
-        perms, members, eps = rd.rollout_draws(self.spec, B, H, self._cpu_rng())
-        if perms is not None:
-            perms = perms.to(self.device)
-        if eps is not None:
-            eps = eps.to(self.device)
-        return self.engine.rollout(a, initial_state, self.num_particles, mode="exact", perms=perms, members=members, eps=eps)
-
-    def _device_rng(self):
-        if not hasattr(self, "_dev_rng"):
-            self._dev_rng = torch.Generator(device=self.device).manual_seed(self.seed)
-        return self._dev_rng
-
-    def _cpu_rng(self):
-        if self._rng is not None and self._rng.device.type == "cpu":
-            return self._rng
-        if not hasattr(self, "_own_rng"):
-            self._own_rng = torch.Generator().manual_seed(self.seed)
-        return self._own_rng
+        next_obs, rewards = self._traced_rollout(a, initial_state)
+        dones = closed_form_dones(self.spec, next_obs.view(-1, self.spec.obs_dim)).view(H, -1)
+        returns, row_totals, first_done = self.engine.trajectory_returns(rewards, dones, pop, self.num_particles, row_totals=True, first_done=True)
+        return {"next_obs": next_obs, "rewards": rewards, "dones": dones, "first_done": first_done, "row_totals": row_totals, "returns": returns}
 
 
 class ModelEnv:
@@ -380,6 +469,99 @@ class UnfusedTrajectoryEvalFn(_EnsembleObjective):
         return total.reshape(-1, P).mean(dim=1)
 
 
+def _rowwise_output(out, n_rows: int, what: str, boolean: bool) -> torch.Tensor:
+    """A callable's result over ``n_rows`` rows as a flat [n_rows] tensor: [N] or [N, 1], floats for a reward, bool for a termination."""
+    if not isinstance(out, torch.Tensor) or tuple(out.shape) not in ((n_rows,), (n_rows, 1)):
+        got = tuple(out.shape) if isinstance(out, torch.Tensor) else type(out).__name__
+        raise ValueError(f"{what} must return a tensor of shape [{n_rows}] or [{n_rows}, 1] for {n_rows} rows, got {got}")
+    if boolean and out.dtype != torch.bool:
+        raise ValueError(f"{what} must return a bool tensor, got {out.dtype}")
+    if not boolean and not out.dtype.is_floating_point:
+        raise ValueError(f"{what} must return a floating-point tensor, got {out.dtype}")
+    return out.reshape(n_rows)
+
+
+def _same_values(a: torch.Tensor, b: torch.Tensor) -> bool:
+    """torch.equal with NaNs at equal positions counting as equal."""
+    if a.dtype == torch.bool:
+        return torch.equal(a, b)
+    return torch.equal(torch.isnan(a), torch.isnan(b)) and torch.equal(torch.nan_to_num(a, nan=0.0), torch.nan_to_num(b, nan=0.0))
+
+
+class CallableTrajectoryEvalFn(_RolloutObjective):
+    """``trajectory_eval_fn`` for models whose ``reward_fn`` / ``termination_fn`` are arbitrary Python callables, in ONE rollout
+    launch per evaluation.  In ``ModelEnv.evaluate_action_sequences`` (model_env.py:178-191) the dynamics never read the reward or
+    the ``terminated`` mask -- terminated rows keep rolling, only their rewards are zeroed -- so the horizon runs as one
+    ``hipets_rollout`` that writes every row's predicted states (the kernel's taps), the callables run ONCE over all ``H * B`` rows,
+    and ``hipets_trajectory_returns`` applies lines 186-191.  :class:`UnfusedTrajectoryEvalFn` runs the same evaluation as ``H``
+    ``hipets_step`` launches with the callables in between.
+
+    THE CALLABLES MUST BE ROW-WISE: ``fn(act [N, A], next_obs [N, obs])`` returns, for every row, a value that depends on that row
+    only, for any N.  They are called once per evaluation with ``N = H * B`` rows, time-major -- row ``t * B + c * P + p`` is step t
+    of particle p of candidate c, its action ``action_sequences[c, t]`` -- not ``H`` times with ``B`` rows.  A reward returns ``[N]``
+    or ``[N, 1]`` floats, a termination ``[N]`` or ``[N, 1]`` bool.  ``check_rowwise`` (default): the objective's FIRST call also
+    evaluates both callables on step 0's ``B`` rows alone and compares with the first ``B`` rows of the batched result (that one
+    call synchronises with the host); a callable that fails it -- one that normalises over the batch, say -- belongs to
+    :class:`UnfusedTrajectoryEvalFn`.  Otherwise a call never synchronises in the in-kernel modes.
+
+    ``reward_fn`` / ``termination_fn``: the arguments, else the spec's ``custom_reward_fn`` / ``custom_termination_fn`` (what
+    ``spec_from_model_env(allow_custom_fns=True)`` kept).  Without a reward callable the rewards are the kernel's own (a learned
+    reward, or the spec's closed form); without a termination callable the spec's closed-form termination is restated over the
+    traced states (:func:`closed_form_dones`).  ``mode``, seed and streams as for :class:`HipTrajectoryEvalFn` (call k runs stream
+    k of ``seed``).  The trajectory of a call takes ``H * B * (obs + 1) * 4`` bytes; a call beyond ``max_trajectory_bytes`` raises."""
+
+    _allow_custom_fns = True
+    kernel_mode = None  # not a fused-plan target: the optimizers run their per-iteration loops and call it; batched agents refuse it
+
+    def __init__(self, model, num_particles: int, reward_fn=None, termination_fn=None, engine: Optional[Engine] = None,
+                 mode: str = "device", seed: int = 0, device=None, rng: Optional[torch.Generator] = None, check_rowwise: bool = True,
+                 max_trajectory_bytes: int = 2 << 30):
+        super().__init__(model, num_particles, engine, mode, seed, device, rng)
+        self.reward_fn = reward_fn if reward_fn is not None else self.spec.custom_reward_fn
+        self.termination_fn = termination_fn if termination_fn is not None else self.spec.custom_termination_fn
+        if self.reward_fn is None and self.termination_fn is None:
+            raise ValueError("neither a reward nor a termination callable: this model's objective is fully fused, use HipTrajectoryEvalFn")
+        self.check_rowwise, self.max_trajectory_bytes = bool(check_rowwise), int(max_trajectory_bytes)
+        self._rowwise_checked = False
+
+    def _evaluate_callables(self, act_rows: torch.Tensor, obs_rows: torch.Tensor):
+        """(rewards [N] or None, dones bool [N] or None) of the callables that are set, shapes and dtypes checked."""
+        n = act_rows.shape[0]
+        rew = done = None
+        if self.reward_fn is not None:
+            rew = _rowwise_output(self.reward_fn(act_rows, obs_rows), n, "reward_fn", boolean=False)
+        if self.termination_fn is not None:
+            done = _rowwise_output(self.termination_fn(act_rows, obs_rows), n, "termination_fn", boolean=True)
+        return rew, done
+
+    def _trajectory(self, initial_state, action_sequences, details):
+        a = self._prep(action_sequences)
+        self.calls += 1
+        pop, H, A = a.shape
+        P = self.num_particles
+        B = pop * P
+        next_obs, rewards = self._traced_rollout(a, initial_state)
+        obs_rows = next_obs.view(H * B, self.spec.obs_dim)
+        act_rows = a.transpose(0, 1).unsqueeze(2).expand(H, pop, P, A).reshape(H * B, A)  # model_env.py:179-182, all steps at once
+        rew, done = self._evaluate_callables(act_rows, obs_rows)
+        if self.check_rowwise and not self._rowwise_checked:
+            for name, batched, alone in zip(("reward_fn", "termination_fn"), (rew, done), self._evaluate_callables(act_rows[:B], obs_rows[:B])):
+                if batched is not None and not _same_values(batched[:B], alone):
+                    raise ValueError(f"{name} is not row-wise: evaluated on step 0's {B} rows alone it returns other values than for the "
+                                     f"same rows inside the batch of {H * B}.  CallableTrajectoryEvalFn calls it once per evaluation over "
+                                     "all steps; use UnfusedTrajectoryEvalFn (one call per step) for such a callable")
+            self._rowwise_checked = True
+        rewards = rewards if rew is None else rew.to(torch.float32).reshape(H, B).contiguous()
+        dones = (closed_form_dones(self.spec, obs_rows) if done is None else done).reshape(H, B).contiguous()
+        if not details:
+            return self.engine.trajectory_returns(rewards, dones, pop, P)
+        returns, row_totals, first_done = self.engine.trajectory_returns(rewards, dones, pop, P, row_totals=True, first_done=True)
+        return {"next_obs": next_obs, "rewards": rewards, "dones": dones, "first_done": first_done, "row_totals": row_totals, "returns": returns}
+
+    def __call__(self, initial_state: np.ndarray, action_sequences: torch.Tensor) -> torch.Tensor:
+        return self._trajectory(initial_state, action_sequences, False)
+
+
 class PlaNetTrajectoryEvalFn(_Objective):
     """``trajectory_eval_fn`` for a PlaNet latent model: ``ModelEnv.evaluate_action_sequences`` with
     ``PlaNetModel.sample`` as the transition (mbrl/models/planet.py:531-581, mbrl/algorithms/planet.py), the whole horizon in
@@ -454,12 +636,16 @@ class PlaNetTrajectoryEvalFn(_Objective):
         return self.engine.planet_rollout(a, latent0, belief0, self.num_particles, eps=eps.contiguous())
 
 
-def make_eval_fn(model, num_particles: int, **kw):
+def make_eval_fn(model, num_particles: int, callables: str = "steps", **kw):
     """``agent.set_trajectory_eval_fn(hipets.make_eval_fn(model_env, num_particles))`` on a stock or a
     hipets agent (seam 3 of SURVEY.md section 8b).  Returns the fully fused objective when reward / termination are
-    mbrl.env closed forms, the unfused one (fused model step + Python callables) when they are arbitrary callables.
+    mbrl.env closed forms; when they are arbitrary callables, ``callables='steps'`` (default) returns the unfused objective (one fused
+    model step per launch, the callables between the steps) and ``callables='trajectory'`` the one-launch
+    :class:`CallableTrajectoryEvalFn` (the callables must be row-wise: they run once over all steps' rows).
     Without a ``mode=`` argument the objective runs ``mode='device'``: the reference's TS1 semantics (one balanced permutation
     of all rows per step, gaussian_mlp.py:201-211), every draw made in-kernel; ``mode='fast'`` is the opt-in block-balanced variant."""
+    if callables not in ("steps", "trajectory"):
+        raise ValueError(f"callables must be 'steps' or 'trajectory', got {callables!r}")
     if isinstance(model, PlaNetSpec) or is_planet_model(getattr(model, "dynamics_model", model)):
         return PlaNetTrajectoryEvalFn(model, num_particles, **kw)
     try:
@@ -470,6 +656,8 @@ def make_eval_fn(model, num_particles: int, **kw):
         spec = spec_from_model_env(model, allow_custom_fns=True)  # raises again if something else is unsupported
         if spec.custom_reward_fn is None and spec.custom_termination_fn is None:
             raise
+        if callables == "trajectory":
+            return CallableTrajectoryEvalFn(model, num_particles, **kw)
         kw2 = {k: v for k, v in kw.items() if k in ("engine", "seed", "device")}
         if kw.get("mode") in ("fast", "device"):
             kw2["step_mode"] = kw["mode"]

@@ -5,7 +5,7 @@ from .agents import (Agent, BatchedCEMAgent, BatchedICEMAgent, BatchedMPPIAgent,
                      TrajectoryOptimizerAgent, _instantiate, _OptimizerSnapshot, complete_agent_cfg,
                      create_trajectory_optim_agent_for_model)
 from .engine import get_engine  # noqa: F401
-from .objectives import (HipTrajectoryEvalFn, ModelEnv, PlaNetTrajectoryEvalFn, UnfusedTrajectoryEvalFn, _BoundObjective,  # noqa: F401
+from .objectives import (CallableTrajectoryEvalFn, HipTrajectoryEvalFn, ModelEnv, PlaNetTrajectoryEvalFn, UnfusedTrajectoryEvalFn, _BoundObjective,  # noqa: F401
                          make_eval_fn)
 from .optimizers import CEMOptimizer, ICEMOptimizer, MPPIOptimizer, Optimizer  # noqa: F401
 from .reference_draws import population_noise as _reference_noise  # noqa: F401
