@@ -38,6 +38,8 @@ def term_word(fn: int, op: int = 0, level: int = 0) -> int:
 def term_word_fields(word: int):
     """(fn, op, level) of a packed word (HIPETS_TERM_WORD_FN / _OP / _LEVEL)"""
     return word & 0xFF, (word >> 8) & 0xFF, (word & 0xFFFFFFFF) >> 16
+
+
 BOX_LO_OPEN, BOX_HI_OPEN = 1, 2  # hipets_term_interval.flags
 MAX_REWARD_TERMS, MAX_TERM_INTERVALS = 64, 64
 COL_FN = {"id": 0, "sin": 1, "cos": 2}  # HIPETS_COL_*
@@ -132,7 +134,6 @@ class PlanetOpts(C.Structure):
                 ("n_env", C.c_int32)]
 
 
-# every symbol include/hipets.h declares: name -> (restype, argtypes)
 class TrainDesc(C.Structure):
     _fields_ = [
         ("ensemble_size", C.c_int32), ("n_layers", C.c_int32), ("in_dim", C.c_int32), ("hid", C.c_int32), ("out_dim", C.c_int32),
@@ -146,69 +147,82 @@ class TrainDesc(C.Structure):
     ]
 
 
-_P = C.c_void_p
+_CTYPES = {"": C.c_void_p, "i32": C.c_int32, "i64": C.c_int64, "u64": C.c_uint64, "f64": C.c_double, "int": C.c_int, "ptr": C.c_void_p}
+
+
+def _sig(params: str, restype=C.c_int):
+    """'e p:CemParams* seed:u64 out' -> (restype, [("e", c_void_p), ("p", POINTER(CemParams)), ("seed", c_uint64), ("out", c_void_p)]):
+    a bare name is a void* (any pointer to caller-owned memory), 'T*' a pointer to the scalar or struct T"""
+    out = []
+    for name, _, t in (p.partition(":") for p in params.split()):
+        base = _CTYPES[t.rstrip("*")] if t.rstrip("*") in _CTYPES else globals()[t.rstrip("*")]  # (a struct of this module)
+        out.append((name, C.POINTER(base) if t.endswith("*") else base))
+    return restype, out
+
+
+# every symbol include/hipets.h declares: name -> (restype, [(parameter name, ctype), ...]), names and order exactly the header's
+# (tests/test_abi.py compares them with its prototypes); Engine calls by these names
 SYMBOLS = {
-    "hipets_abi_version": (C.c_int, []),
-    "hipets_last_error": (C.c_char_p, []),
-    "hipets_last_error_kind": (C.c_int, []),
-    "hipets_create": (C.c_int, [C.c_int, C.POINTER(_P)]),
-    "hipets_destroy": (None, [_P]),
-    "hipets_set_model": (C.c_int, [_P, C.POINTER(ModelDesc), _P]),
-    "hipets_set_model_columns": (C.c_int, [_P, C.POINTER(ModelDesc), C.POINTER(ObsColumnC), C.c_int32, _P]),
-    "hipets_rollout": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(RolloutOpts), _P, _P]),
-    "hipets_step": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(RolloutOpts), _P, _P, _P, _P]),
-    "hipets_trajectory_returns": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
-    "hipets_fast_geometry": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "hipets_kernel_class": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "hipets_fast_schedule": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_fast_normals": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_device_perms": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_set_plan_mode": (C.c_int, [_P, C.c_int32]),
-    "hipets_set_persistent": (C.c_int, [_P, C.c_int32]),
-    "hipets_set_handover_timeout": (C.c_int, [_P, C.c_double]),
-    "hipets_check_async_error": (C.c_int, [_P, C.POINTER(C.c_int32)]),
-    "hipets_set_plan_trace": (C.c_int, [_P, C.POINTER(PlanTrace)]),
-    "hipets_cem_sample": (C.c_int, [_P, C.POINTER(CemParams), _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_cem_refit": (C.c_int, [_P, C.POINTER(CemParams), _P, _P, _P, _P, _P, _P, _P, _P]),
-    "hipets_cem_refit_elites": (C.c_int, [_P, C.POINTER(CemParams), _P, _P, _P, _P, _P, _P, _P, _P]),
-    "hipets_gather_rows": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P]),
-    "hipets_mppi_sample": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_mppi_update": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P]),
-    "hipets_icem_sample": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_double, _P, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_icem_shift": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_plan_cem": (C.c_int, [_P, C.POINTER(CemParams), _P, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_plan_cem_batched": (C.c_int, [_P, C.POINTER(CemParams), C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_plan_mppi": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P, C.c_int32,
-                                   C.c_uint64, C.c_uint64, _P]),
-    "hipets_plan_mppi_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P,
-                                           C.c_int32, C.c_uint64, C.c_uint64, _P]),
-    "hipets_plan_icem_batched": (C.c_int, [_P, C.POINTER(IcemParams), C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_uint64,
-                                           C.c_uint64, _P, _P]),
-    "hipets_plan_icem": (C.c_int, [_P, C.POINTER(IcemParams), _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_uint64, C.c_uint64,
-                                   _P, _P]),
-    "hipets_comm_unique_id": (C.c_int, [_P]),
-    "hipets_comm_init": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),
-    "hipets_comm_destroy": (C.c_int, [_P]),
-    "hipets_comm_info": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
-    "hipets_plan_cem_sharded": (C.c_int, [_P, C.POINTER(CemParams), _P, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_plan_mppi_sharded": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, _P, _P, _P, _P, C.c_int32,
-                                           C.c_uint64, C.c_uint64, _P]),
-    "hipets_plan_icem_sharded": (C.c_int, [_P, C.POINTER(IcemParams), _P, _P, _P, _P, C.c_int32, _P, _P, C.c_int32, C.c_uint64, C.c_uint64,
-                                           _P, _P]),
-    "hipets_planet_set_model": (C.c_int, [_P, C.POINTER(PlanetDesc), _P]),
-    "hipets_planet_rollout": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.POINTER(PlanetOpts), _P, _P]),
-    "hipets_planet_kernel_class": (C.c_int, [_P, C.POINTER(C.c_int32)]),
-    "hipets_plan_planet_cem": (C.c_int, [_P, C.POINTER(CemParams), _P, _P, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_plan_planet_cem_batched": (C.c_int, [_P, C.POINTER(CemParams), C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64,
-                                                 _P, _P]),
-    "hipets_plan_planet_mppi_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_int32, _P, _P,
-                                                  _P, _P, _P, C.c_int32, C.c_uint64, C.c_uint64, _P]),
-    "hipets_plan_planet_icem_batched": (C.c_int, [_P, C.POINTER(IcemParams), C.c_int32, _P, _P, _P, _P, C.c_int32, _P, _P, _P, C.c_int32,
-                                                  C.c_uint64, C.c_uint64, _P, _P]),
-    "hipets_train_steps": (C.c_int, [_P, C.POINTER(TrainDesc), _P, _P, C.c_int64, _P, _P, C.c_int32, C.c_int64, _P, _P, _P]),
-    "hipets_train_eval": (C.c_int, [_P, C.POINTER(TrainDesc), _P, _P, C.c_int64, _P, _P, _P, _P]),
-    "hipets_timing_enable": (C.c_int, [_P, C.c_int32]),
-    "hipets_timing_read": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_double), C.c_int32]),
+    "hipets_abi_version": _sig(""),
+    "hipets_last_error": _sig("", C.c_char_p),
+    "hipets_last_error_kind": _sig(""),
+    "hipets_create": _sig("device:int out:ptr*"),
+    "hipets_destroy": _sig("e", None),
+    "hipets_set_model": _sig("e desc:ModelDesc* stream"),
+    "hipets_set_model_columns": _sig("e desc:ModelDesc* cols:ObsColumnC* n_cols:i32 stream"),
+    "hipets_rollout": _sig("e actions s0 pop:i32 horizon:i32 num_particles:i32 opts:RolloutOpts* returns stream"),
+    "hipets_step": _sig("e obs actions batch:i32 opts:RolloutOpts* next_obs rewards dones stream"),
+    "hipets_trajectory_returns": _sig("e rewards dones pop:i32 horizon:i32 num_particles:i32 returns row_totals first_done stream"),
+    "hipets_fast_geometry": _sig("e pop:i32 num_particles:i32 horizon:i32 rows_per_group:i32 n_workgroups:i32* row_tiles:i32*"),
+    "hipets_kernel_class": _sig("e pop:i32 num_particles:i32 horizon:i32 mode:i32 rows_per_group:i32 kernel_class:i32* row_tiles:i32*"),
+    "hipets_fast_schedule": _sig("e horizon:i32 n_workgroups:i32 seed:u64 stream_id:u64 schedule stream"),
+    "hipets_fast_normals": _sig("e horizon:i32 batch:i32 seed:u64 stream_id:u64 normals stream"),
+    "hipets_device_perms": _sig("e horizon:i32 batch:i32 seed:u64 stream_id:u64 perms stream"),
+    "hipets_set_plan_mode": _sig("e mode:i32"),
+    "hipets_set_persistent": _sig("e on:i32"),
+    "hipets_set_handover_timeout": _sig("e seconds:f64"),
+    "hipets_check_async_error": _sig("e timed_out:i32*"),
+    "hipets_set_plan_trace": _sig("e trace:PlanTrace*"),
+    "hipets_cem_sample": _sig("e p:CemParams* mu dispersion lower upper z seed:u64 stream_id:u64 population stream"),
+    "hipets_cem_refit": _sig("e p:CemParams* values population mu dispersion best_value best_solution elite_idx stream"),
+    "hipets_cem_refit_elites": _sig("e p:CemParams* values population elites mu dispersion best_value best_solution stream"),
+    "hipets_gather_rows": _sig("e rows:i32 dim:i32 src index dst stream"),
+    "hipets_mppi_sample": _sig("e pop:i32 horizon:i32 act_dim:i32 beta:f64 mean past_action lower upper z seed:u64 stream_id:u64 population stream"),
+    "hipets_mppi_update": _sig("e pop:i32 horizon:i32 act_dim:i32 gamma:f64 values population mean stream"),
+    "hipets_icem_sample": _sig("e n:i32 horizon:i32 act_dim:i32 exponent:f64 mu var lower upper normals seed:u64 stream_id:u64 population stream"),
+    "hipets_icem_shift": _sig("e keep:i32 horizon:i32 act_dim:i32 kept mu var end_noise seed:u64 stream_id:u64 out stream"),
+    "hipets_plan_cem": _sig("e p:CemParams* x0 lower upper s0 num_particles:i32 seed:u64 plan_id:u64 out stream"),
+    "hipets_plan_cem_batched": _sig("e p:CemParams* n_env:i32 x0 lower upper s0 num_particles:i32 seed:u64 plan_id:u64 out stream"),
+    "hipets_plan_mppi": _sig("e population_size:i32 horizon:i32 act_dim:i32 num_iterations:i32 gamma:f64 beta:f64 mean lower upper s0 "
+                             "num_particles:i32 seed:u64 plan_id:u64 stream"),
+    "hipets_plan_mppi_batched": _sig("e population_size:i32 horizon:i32 act_dim:i32 num_iterations:i32 gamma:f64 beta:f64 n_env:i32 mean lower "
+                                     "upper s0 num_particles:i32 seed:u64 plan_id:u64 stream"),
+    "hipets_plan_icem": _sig("e p:IcemParams* x0 lower upper elite has_elite:i32 keep_idx s0 num_particles:i32 seed:u64 plan_id:u64 out stream"),
+    "hipets_plan_icem_batched": _sig("e p:IcemParams* n_env:i32 x0 lower upper elite has_elite:i32 keep_idx s0 num_particles:i32 seed:u64 "
+                                     "plan_id:u64 out stream"),
+    "hipets_comm_unique_id": _sig("id_out"),
+    "hipets_comm_init": _sig("e unique_id rank:i32 world_size:i32"),
+    "hipets_comm_destroy": _sig("e"),
+    "hipets_comm_info": _sig("e rank:i32* world_size:i32*"),
+    "hipets_plan_cem_sharded": _sig("e p:CemParams* x0 lower upper s0 num_particles:i32 seed:u64 plan_id:u64 out stream"),
+    "hipets_plan_mppi_sharded": _sig("e population_size:i32 horizon:i32 act_dim:i32 num_iterations:i32 gamma:f64 beta:f64 mean lower upper s0 "
+                                     "num_particles:i32 seed:u64 plan_id:u64 stream"),
+    "hipets_plan_icem_sharded": _sig("e p:IcemParams* x0 lower upper elite has_elite:i32 keep_idx s0 num_particles:i32 seed:u64 plan_id:u64 "
+                                     "out stream"),
+    "hipets_planet_set_model": _sig("e d:PlanetDesc* stream"),
+    "hipets_planet_rollout": _sig("e actions latent0 belief0 pop:i32 horizon:i32 num_particles:i32 opts:PlanetOpts* returns stream"),
+    "hipets_planet_kernel_class": _sig("e is_static:i32*"),
+    "hipets_plan_planet_cem": _sig("e p:CemParams* x0 lower upper latent0 belief0 num_particles:i32 seed:u64 plan_id:u64 out stream"),
+    "hipets_plan_planet_cem_batched": _sig("e p:CemParams* n_env:i32 x0 lower upper latent0 belief0 num_particles:i32 seed:u64 plan_id:u64 "
+                                           "out stream"),
+    "hipets_plan_planet_mppi_batched": _sig("e population_size:i32 horizon:i32 act_dim:i32 num_iterations:i32 gamma:f64 beta:f64 n_env:i32 mean "
+                                            "lower upper latent0 belief0 num_particles:i32 seed:u64 plan_id:u64 stream"),
+    "hipets_plan_planet_icem_batched": _sig("e p:IcemParams* n_env:i32 x0 lower upper elite has_elite:i32 keep_idx latent0 belief0 "
+                                            "num_particles:i32 seed:u64 plan_id:u64 out stream"),
+    "hipets_train_steps": _sig("e d:TrainDesc* x y n_rows:i64 idx rows n_steps:i32 step0:i64 loss grad_sq stream"),
+    "hipets_train_eval": _sig("e d:TrainDesc* x y n_rows:i64 order score row_score stream"),
+    "hipets_timing_enable": _sig("e on:i32"),
+    "hipets_timing_read": _sig("e launches:i64* total_ms:f64* reset:i32"),
 }
 
 _lib = None
@@ -245,7 +259,7 @@ def load():
     for name, (res, args) in SYMBOLS.items():
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.restype = res
-        fn.argtypes = args
+        fn.argtypes = [t for _, t in args]
     if lib.hipets_abi_version() != ABI_VERSION:
         raise HipetsError(f"libhipets ABI {lib.hipets_abi_version()} != binding ABI {ABI_VERSION}")
     _lib = lib

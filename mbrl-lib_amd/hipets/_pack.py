@@ -1,0 +1,222 @@
+"""The descriptors of include/hipets.h, packed from specs and tensors.  Pure functions: no library call and no device API, so that
+every one of them runs in a host test (tests/test_engine_binding_host.py).  Each returns the filled struct and a keep-alive list: what
+the struct points to and nothing else references, to be held until the library call that reads the struct has returned."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+import torch
+
+from . import _lib
+from .model import BoxTermination, ModelSpec, ObsColumns, RewardTerms
+
+
+def _ptr(t: Optional[torch.Tensor]):
+    return None if t is None else t.data_ptr()
+
+
+def _check_dev(t: torch.Tensor, dtype, device, name: str, shape=None, numel=None):
+    if not isinstance(t, torch.Tensor) or t.device != device:
+        raise ValueError(f"{name} must be a tensor on {device}")
+    if t.dtype != dtype:
+        raise ValueError(f"{name} must have dtype {dtype}, got {t.dtype}")
+    if not t.is_contiguous():
+        raise ValueError(f"{name} must be contiguous")
+    if shape is not None and tuple(t.shape) != tuple(shape):
+        raise ValueError(f"{name} must have shape {tuple(shape)}, got {tuple(t.shape)}")
+    if numel is not None and t.numel() != numel:
+        raise ValueError(f"{name} must have {numel} elements, got {t.numel()}")
+
+
+def member_slots(members: torch.Tensor, n_members: int, device) -> tuple:
+    """Row -> member map(s) ``members`` int64 [T, B] -> (slots int64 [T, M * rpm] on ``device``, rpm): slot m * rpm + j holds
+    the j-th row (ascending) of member m, -1 pads the tail (hipets_rollout_opts.rows_per_member).  Pure index plumbing
+    with torch ops on whichever device ``members`` lives: a CPU map gets the tight rpm = largest member count; a device
+    map uses rpm = B so that no count has to travel to the host (all-padding workgroups exit immediately)."""
+    T, B = members.shape
+    members = members.to(torch.int64)
+    counts = torch.zeros(T, n_members, dtype=torch.int64, device=members.device).scatter_add_(1, members, torch.ones_like(members))
+    rpm = int(counts.max()) if members.device.type == "cpu" else B
+    order = members.argsort(dim=1, stable=True)
+    sorted_m = members.gather(1, order)
+    starts = counts.cumsum(1) - counts
+    pos = torch.arange(B, device=members.device).unsqueeze(0) - starts.gather(1, sorted_m)
+    slots = torch.full((T, n_members * rpm), -1, dtype=torch.int64, device=members.device)
+    slots.scatter_(1, sorted_m * rpm + pos, order)
+    return slots.to(device).contiguous(), max(rpm, 1)
+
+
+def pack_reward_terms(rt: RewardTerms):
+    """The ``hipets_reward_term`` array of a table: ``level`` and ``op`` go into the upper bits of ``fn`` (``_lib.term_word``), so a
+    plain term -- level 0, add -- packs to the bare fn code an ABI v9 client writes."""
+    return (_lib.RewardTermC * max(1, len(rt.terms)))(*[
+        _lib.RewardTermC(_lib.term_word(_lib.TERM_FN[t.fn], _lib.TERM_OP[t.op], t.level), _lib.TERM_SRC[t.source], int(t.i),
+                         -1 if t.j is None else int(t.j), float(t.c), float(t.w))
+        for t in rt.terms])
+
+
+def pack_model_desc(spec: ModelSpec, ws, bs):
+    """hipets_model_desc of ``spec`` over its converted (device, f32, contiguous) weights ``ws`` / biases ``bs`` -> (desc, the
+    hipets_obs_column table of an ObsColumns model -- hipets_set_model_columns' own argument -- or None, keep-alive list)."""
+    members, n = spec.members, len(ws)
+    d = _lib.ModelDesc(obs_dim=spec.obs_dim, act_dim=spec.act_dim, in_dim=spec.in_dim, out_dim=spec.out_dim, hid=spec.hid, n_layers=n,
+                       ensemble_size=spec.ensemble_size, n_members=len(members), activation=_lib.ACT[spec.activation],
+                       leaky_slope=float(spec.leaky_slope), propagation=_lib.PROP[spec.propagation], deterministic=int(spec.deterministic),
+                       target_is_delta=int(spec.target_is_delta), learned_rewards=int(spec.learned_rewards),
+                       n_no_delta=len(spec.no_delta_list), ensemble_kind=_lib.ENSEMBLE[spec.ensemble_kind], precision=_lib.PREC[spec.precision])
+    d.members = (C.c_int32 * len(members))(*members)
+    d.no_delta = (C.c_int32 * max(1, len(spec.no_delta_list)))(*[int(i) for i in spec.no_delta_list])
+    d.weights = (C.c_void_p * n)(*[w.data_ptr() for w in ws])
+    d.biases = (C.c_void_p * n)(*[b.data_ptr() for b in bs])
+    keep, cols = [ws, bs], None  # (the ctypes arrays assigned to pointer fields are referenced by the struct itself)
+    if isinstance(spec.obs_process, ObsColumns):
+        cols = (_lib.ObsColumnC * len(spec.obs_process.columns))(*[_lib.ObsColumnC(int(c.dim), _lib.COL_FN[c.fn]) for c in spec.obs_process.columns])
+        d.obs_process = _lib.OBS["columns"]
+    else:
+        d.obs_process = _lib.OBS[spec.obs_process]
+    if isinstance(spec.reward, RewardTerms):
+        rt = spec.reward
+        d.reward_fn, d.reward_terms, d.n_reward_terms = _lib.REW["terms"], pack_reward_terms(rt), len(rt.terms)
+        d.reward_bias, d.alive_bonus = rt.bias, rt.alive_bonus
+    else:
+        d.reward_fn = _lib.REW[spec.reward]
+    if isinstance(spec.termination, BoxTermination):
+        box = spec.termination
+        d.term_intervals = (_lib.TermIntervalC * max(1, len(box.intervals)))(*[
+            _lib.TermIntervalC(int(iv.dim), (_lib.BOX_LO_OPEN if iv.lo_open else 0) | (_lib.BOX_HI_OPEN if iv.hi_open else 0), float(iv.lo), float(iv.hi))
+            for iv in box.intervals])
+        d.termination_fn, d.n_term_intervals, d.term_require_finite = _lib.TERM["box"], len(box.intervals), int(box.require_finite)
+    else:
+        d.termination_fn = _lib.TERM[spec.termination]
+
+    def host(t, np_type, c_type):  # a HOST array behind a typed pointer
+        arr = np.ascontiguousarray(t.numpy().reshape(-1), dtype=np_type)
+        keep.append(arr)
+        return arr.ctypes.data_as(C.POINTER(c_type))
+
+    if spec.norm_mean is not None:
+        d.normalizer = _lib.NORM["f64" if spec.norm_mean.dtype == torch.float64 else "f32"]
+        d.norm_mean = host(spec.norm_mean.detach().cpu().double(), np.float64, C.c_double)
+        d.norm_std = host(spec.norm_std.detach().cpu().double(), np.float64, C.c_double)
+    else:
+        d.normalizer = _lib.NORM["none"]
+    if not spec.deterministic:
+        lo, hi = spec.min_logvar.detach().cpu().float(), spec.max_logvar.detach().cpu().float()
+        if spec.ensemble_kind == "basic_ensemble":  # every member owns its bounds: [M, out] (a shared [1, out] is broadcast)
+            lo = lo.reshape(-1, spec.out_dim).expand(len(members), spec.out_dim)
+            hi = hi.reshape(-1, spec.out_dim).expand(len(members), spec.out_dim)
+        d.min_logvar, d.max_logvar = host(lo, np.float32, C.c_float), host(hi, np.float32, C.c_float)
+    return d, cols, keep
+
+
+def pack_planet_desc(spec, tensors):
+    """hipets_planet_desc of a ``PlaNetSpec`` over its converted tensors (``_lib._PLANET_TENSORS`` order) -> (desc, keep-alive list)"""
+    d = _lib.PlanetDesc(latent_size=spec.latent_size, action_size=spec.action_size, belief_size=spec.belief_size, hidden_size=spec.hidden_size,
+                        min_std=float(spec.min_std), **{n: t.data_ptr() for n, t in zip(_lib._PLANET_TENSORS, tensors)})
+    return d, list(tensors)
+
+
+def pack_train_desc(device, weights, biases, activation: str, leaky_slope: float, out_dim: int, max_batch: int, adam=None):
+    """TrainDesc over the caller's DEVICE tensors (weights[l] [E, d_l, d_l+1], biases[l] [E, 1, d_l+1]); ``adam`` =
+    (exp_avg_w, exp_avg_b, exp_avg_sq_w, exp_avg_sq_b, min_logvar, max_logvar, lr, beta1, beta2, eps, weight_decay,
+    steps_per_launch).  The returned keep-alive list holds the ctypes arrays the struct points to."""
+    L = len(weights)
+    if L < 2 or L != len(biases):
+        raise ValueError("weights / biases: one tensor of each per linear layer, at least 2 layers")
+    E, in_dim, hid = int(weights[0].shape[0]), int(weights[0].shape[1]), int(weights[0].shape[2])
+    for li, (w, b) in enumerate(zip(weights, biases)):
+        d_in = in_dim if li == 0 else hid
+        d_out = 2 * out_dim if li == L - 1 else hid
+        _check_dev(w, torch.float32, device, f"weights[{li}]", shape=(E, d_in, d_out))
+        _check_dev(b, torch.float32, device, f"biases[{li}]", shape=(E, 1, d_out))
+    if activation not in _lib.ACT:
+        raise ValueError(f"unknown activation {activation!r}")
+    arr = lambda ts: (C.c_void_p * L)(*[t.data_ptr() for t in ts])  # noqa: E731
+    keep = [arr(weights), arr(biases)]
+    d = _lib.TrainDesc(ensemble_size=E, n_layers=L, in_dim=in_dim, hid=hid, out_dim=out_dim, activation=_lib.ACT[activation],
+                       leaky_slope=float(leaky_slope), max_batch=int(max_batch))
+    d.weights = C.cast(keep[0], C.POINTER(C.c_void_p))
+    d.biases = C.cast(keep[1], C.POINTER(C.c_void_p))
+    if adam is not None:
+        mw, mb, vw, vb, lo, hi, lr, b1, b2, eps, wd, spl = adam
+        for name, ts, ref in (("exp_avg_w", mw, weights), ("exp_avg_b", mb, biases), ("exp_avg_sq_w", vw, weights), ("exp_avg_sq_b", vb, biases)):
+            if len(ts) != L:
+                raise ValueError(f"{name}: one tensor per layer")
+            for li, (t, r) in enumerate(zip(ts, ref)):
+                _check_dev(t, torch.float32, device, f"{name}[{li}]", shape=tuple(r.shape))
+        _check_dev(lo, torch.float32, device, "min_logvar", numel=out_dim)
+        _check_dev(hi, torch.float32, device, "max_logvar", numel=out_dim)
+        keep += [arr(mw), arr(mb), arr(vw), arr(vb), lo, hi]
+        d.exp_avg_w, d.exp_avg_b, d.exp_avg_sq_w, d.exp_avg_sq_b = (C.cast(k, C.POINTER(C.c_void_p)) for k in keep[2:6])
+        d.min_logvar, d.max_logvar = lo.data_ptr(), hi.data_ptr()
+        d.lr, d.beta1, d.beta2, d.eps, d.weight_decay = float(lr), float(b1), float(b2), float(eps), float(wd)
+        d.steps_per_launch = int(spl)
+    return d, keep
+
+
+def pack_rollout_opts(spec: ModelSpec, device, mode: str, B: int, H: Optional[int], perms, members, eps, seed: int, stream_id: int,
+                      member_schedule, rows_per_group: int, generic_kernel, *, sample: bool = True, perm_stream_id: int = 0, n_workgroups=None,
+                      n_env: int = 0, trace_next_obs=None, trace_rewards=None, phase_cycles=None):
+    """hipets_rollout_opts of a rollout of B rows over H steps, or -- ``H`` None -- of one step (hipets_step) -> (opts, keep-alive
+    list).  The two differ in what they are given: a rollout's row -> member maps are [H, B] ([B] for fixed_model), its eps is [H, B,
+    out_dim] and its member schedule [H, ``n_workgroups()``]; a step's maps are [B] and read in EXACT mode only, its eps has B * out_dim
+    elements and is read only where the step samples, its schedule has any length."""
+    step = H is None
+    if mode not in _lib.MODES:
+        raise ValueError("mode must be 'exact', 'fast' or 'device'")
+    # (generic_kernel: False / True (1: fully generic instance only) / 2 (hidden-static allowed, shape-specialised not))
+    o = _lib.RolloutOpts()
+    o.mode, o.seed, o.stream_id, o.perm_stream_id = _lib.MODES[mode], int(seed), int(stream_id), int(perm_stream_id)
+    o.rows_per_group, o.no_sample, o.generic_kernel, o.n_env = int(rows_per_group), int(not sample), int(generic_kernel), int(n_env)
+    if mode == "device" and (perms is not None or eps is not None or members is not None):
+        raise ValueError("mode='device' draws its permutation and eps in-kernel" if step else
+                         "mode='device' draws its permutations and eps in-kernel: perms / eps / members must be None")
+    if step and mode != "exact":
+        perms = members = None
+    if members is not None or perms is not None:
+        want = (B,) if step or spec.propagation == "fixed_model" else (H, B)
+    if members is not None:
+        if step:
+            if perms is not None or tuple(members.shape) != want:
+                raise ValueError("members= must be int64 [B], exclusive with perm=")
+        elif mode != "exact" or perms is not None:
+            raise ValueError("members= (explicit per-row member maps) is an EXACT-mode input, exclusive with perms=")
+        elif tuple(members.shape) != want:
+            raise ValueError(f"members must have shape {want}")
+        perms, o.rows_per_member = member_slots(members.reshape(-1, B), len(spec.members), device)
+    elif perms is not None:
+        _check_dev(perms, torch.int64, device, "perm" if step else "perms", want if step else None)
+        if tuple(perms.shape) != want:
+            raise ValueError(f"perms must have shape {want}")
+    if step and mode == "exact":
+        if not sample or spec.deterministic:
+            eps = None  # (the mean: no draw is read)
+        elif eps is None:
+            raise ValueError("EXACT step with sample=True needs eps [B, out_dim]")
+    if eps is not None:
+        _check_dev(eps, torch.float32, device, "eps", **({"numel": B * spec.out_dim} if step else {"shape": (H, B, spec.out_dim)}))
+    if mode == "exact":
+        o.perms, o.eps = _ptr(perms), _ptr(eps)
+    elif mode == "fast":
+        o.fast_eps = _ptr(eps)
+        if member_schedule is not None:
+            _check_dev(member_schedule, torch.int32, device, "member_schedule", None if step else (H, n_workgroups()))
+            o.member_schedule, o.member_schedule_len = member_schedule.data_ptr(), int(member_schedule.numel())
+    if trace_next_obs is not None:
+        _check_dev(trace_next_obs, torch.float32, device, "trace_next_obs", (H, B, spec.obs_dim))
+        o.trace_next_obs = trace_next_obs.data_ptr()
+    if trace_rewards is not None:
+        _check_dev(trace_rewards, torch.float32, device, "trace_rewards", (H, B))
+        o.trace_rewards = trace_rewards.data_ptr()
+    if phase_cycles is not None:
+        _check_dev(phase_cycles, torch.int64, device, "phase_cycles", (8, 16))
+        o.phase_cycles = phase_cycles.data_ptr()
+    return o, [perms]  # (member_slots' map has no other owner)
+
+
+def pack_plan_trace(buffers: dict, max_rows: int):
+    """hipets_plan_trace over the device tensors ``buffers`` (one per pointer field) -> (trace, keep-alive list)"""
+    t = _lib.PlanTrace(max_rows=int(max_rows), **{name: buf.data_ptr() for name, buf in buffers.items()})
+    return t, list(buffers.values())

@@ -17,6 +17,56 @@ def header_functions():
     return sorted(set(re.findall(r"\b(hipets_[a-z_]+)\s*\(", src)))
 
 
+def header_prototypes():
+    """name -> (return type, [(parameter type, parameter name), ...]) of every function the header declares, in declaration order;
+    types without ``const`` and without blanks (``const hipets_cem_params* p`` -> ``("hipets_cem_params*", "p")``)."""
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    ctype = lambda text: re.sub(r"\bconst\b|\s+", "", text)  # noqa: E731
+    protos = {}
+    for ret, name, params in re.findall(r"^([a-z_0-9 ]+?\**)\s*(hipets_[a-z_]+)\s*\(([^()]*)\)\s*;", src, flags=re.M):
+        plist = []
+        for decl in ([] if params.strip() == "void" else params.split(",")):
+            m = re.fullmatch(r"(.*?)([A-Za-z_0-9]+)", decl.strip(), flags=re.S)
+            plist.append((ctype(m.group(1)), m.group(2)))
+        assert name not in protos, name
+        protos[name] = (ctype(ret), plist)
+    return protos
+
+
+HEADER_SCALARS = {"int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64, "uint64_t": ctypes.c_uint64, "double": ctypes.c_double,
+                  "int": ctypes.c_int, "float": ctypes.c_float, "uint8_t": ctypes.c_uint8}
+HEADER_STRUCTS = {"hipets_model_desc": "ModelDesc", "hipets_obs_column": "ObsColumnC", "hipets_rollout_opts": "RolloutOpts",
+                  "hipets_cem_params": "CemParams", "hipets_icem_params": "IcemParams", "hipets_plan_trace": "PlanTrace",
+                  "hipets_planet_desc": "PlanetDesc", "hipets_planet_opts": "PlanetOpts", "hipets_train_desc": "TrainDesc"}
+
+
+def test_binding_prototypes_match_the_header():
+    """_lib.SYMBOLS against every prototype of include/hipets.h: parameter count, names in order, scalar types, and a pointer ctype
+    for every pointer (void* / char*, or POINTER(X) with X the header's pointee).  A prototype that gains an argument in the header
+    alone would shift every later argument of the call."""
+    from hipets import _lib
+
+    protos = header_prototypes()
+    assert sorted(protos) == header_functions() == sorted(_lib.SYMBOLS)
+
+    def pointee(t):  # ctypes type a POINTER(...) binding of ``t*`` must point to
+        if t.endswith("*") or t == "hipets_engine":
+            return ctypes.c_void_p
+        return getattr(_lib, HEADER_STRUCTS[t]) if t in HEADER_STRUCTS else HEADER_SCALARS.get(t)
+
+    for name, (ret, params) in protos.items():
+        res, bound = _lib.SYMBOLS[name]
+        assert res is {"int": ctypes.c_int, "char*": ctypes.c_char_p, "void": None}[ret], name
+        assert [n for n, _ in bound] == [n for _, n in params], f"{name}: parameter names / count differ from the header"
+        for (t, pname), (_, ct) in zip(params, bound):
+            where = f"{name}({pname}): header {t}, binding {ct}"
+            if not t.endswith("*"):
+                assert ct is HEADER_SCALARS[t], where
+            elif ct not in (ctypes.c_void_p, ctypes.c_char_p):
+                assert issubclass(ct, ctypes._Pointer) and pointee(t[:-1]) is not None and ct._type_ is pointee(t[:-1]), where
+
+
 def test_header_declares_expected_entry_points():
     fns = header_functions()
     for must in ("hipets_create", "hipets_destroy", "hipets_set_model", "hipets_rollout", "hipets_cem_sample",

@@ -199,7 +199,8 @@ def test_the_new_entry_point_comes_without_a_new_abi_version():
     assert re.search(r"int hipets_set_model_columns\(hipets_engine\* e, const hipets_model_desc\* desc, const hipets_obs_column\* cols, int32_t n_cols, void\* stream\);", plain)
     assert "hipets_set_model_columns" in _lib.SYMBOLS
     res, args = _lib.SYMBOLS["hipets_set_model_columns"]
-    assert res is ctypes.c_int and args[1:4] == [ctypes.POINTER(_lib.ModelDesc), ctypes.POINTER(_lib.ObsColumnC), ctypes.c_int32]
+    assert res is ctypes.c_int and args[1:4] == [("desc", ctypes.POINTER(_lib.ModelDesc)), ("cols", ctypes.POINTER(_lib.ObsColumnC)),
+                                                 ("n_cols", ctypes.c_int32)]
     # the descriptor has not changed: the fields and the size it had (what tests/test_reward_terms_host.py pins, restated)
     assert [f[0] for f in _lib.ModelDesc._fields_][-7:] == ["reward_terms", "term_intervals", "n_reward_terms", "n_term_intervals", "reward_bias", "alive_bonus",
                                                           "term_require_finite"]
