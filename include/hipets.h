@@ -293,10 +293,29 @@ int hipets_step(hipets_engine* e, const float* obs, const float* actions, int32_
  * zeroing is a select (the reference assigns rewards[terminated] = 0): a NaN or inf reward after termination adds exactly 0, one before
  * it propagates, and the reward of the terminating step itself counts.  returns DEVICE [pop] = the mean of a candidate's
  * num_particles row totals, the same sequential f32 sum and division as hipets_rollout's own (bit-identical to it on the same
- * rewards).  Optional outputs (NULL = not wanted): row_totals DEVICE [B] f32; first_done DEVICE [B] int32 = the first step with
+ * rewards) -- or the engine's other reduction over the particles (hipets_set_particle_reduce below).  Optional outputs (NULL = not wanted): row_totals DEVICE [B] f32; first_done DEVICE [B] int32 = the first step with
  * dones != 0, horizon if none.  Needs no model.  (An entry point of its own: no struct changes, HIPETS_ABI_VERSION stays.)          */
 int hipets_trajectory_returns(hipets_engine* e, const float* rewards, const uint8_t* dones, int32_t pop, int32_t horizon,
                               int32_t num_particles, float* returns, float* row_totals, int32_t* first_done, void* stream);
+
+/* ---- the reduction over a candidate's particles (risk-aware planning) ----
+ * A candidate is rolled out as num_particles rows (row c * P + p = particle p of candidate c); its value is ONE rule over the P row
+ * totals t[0..P), fp32 op by op, the same in every entry point that reduces particles -- hipets_rollout, hipets_planet_rollout,
+ * hipets_trajectory_returns, hipets_particle_reduce and every hipets_plan_* (batched, sharded and PlaNet plans included):
+ *   MEAN      s = 0; for p: s += t[p]; v = s / P                        (model_env.py:190-191; the state of a new engine)
+ *   MEAN_STD  m as MEAN; q = 0; for p: q += (t[p] - m)^2; v = m - kappa * sqrtf(q / P)   (kappa > 0 risk-averse, < 0 optimistic)
+ *   MIN, MAX  the lowest / highest total; NaN if any total is NaN
+ *   WORST_K   the mean of the worst_k lowest totals (CVaR): NaN if any total is NaN; else the totals are ranked ascending, ties to the
+ *             lower particle, those of rank < worst_k summed in particle order, / worst_k.  worst_k = P gives MEAN's bits.
+ *             Needs 1 <= worst_k <= P <= 256.
+ * The optimizers' NaN filter, best values, MPPI's weights and the plan traces all see the reduced value.                        */
+enum { HIPETS_REDUCE_MEAN = 0, HIPETS_REDUCE_MEAN_STD = 1, HIPETS_REDUCE_MIN = 2, HIPETS_REDUCE_MAX = 3, HIPETS_REDUCE_WORST_K = 4 };
+/* Engine state, like hipets_set_plan_mode; host only.  kappa is read for MEAN_STD (finite), worst_k for WORST_K (>= 1; checked against
+ * num_particles by the call that knows it: worst_k > num_particles or num_particles > 256 fail there).  Anything else fails with
+ * HIPETS_ERR_INVALID_ARGUMENT and leaves the engine's reduction as it was.                                                      */
+int hipets_set_particle_reduce(hipets_engine* e, int32_t kind, float kappa, int32_t worst_k);
+/* totals DEVICE f32 [pop * num_particles] -> returns DEVICE f32 [pop] under the engine's reduction.  Needs no model.           */
+int hipets_particle_reduce(hipets_engine* e, const float* totals, int32_t pop, int32_t num_particles, float* returns, void* stream);
 
 /* geometry the FAST kernel will use for (pop, P): workgroups and rows per group (for member_schedule).  rows_per_group 0: the
  * library's own choice for a DEFAULT call (hipets_rollout without injected eps / traces, the fused plans); > 0: forced.

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "common.hpp"
+#include "particle_reduce.hpp"
 
 namespace hipets {
 
@@ -16,11 +17,12 @@ struct CemDev {
     int K;             // elite_num
     float alpha, one_minus_alpha;
     int return_mean, clipped, unbiased;
-    // refit only: when set, values[i] is first formed as the mean over the P particle totals of candidate i (model_env.py:190-191;
-    // the same sequential sum and division as particle_mean_kernel, so the same bits) -- the fused plan's rollouts leave their
+    // refit only: when set, values[i] is first formed from the P particle totals of candidate i under `reduce` (model_env.py:190-191 for
+    // the mean; particle_value, the rule of particle_mean_kernel, so the same bits) -- the fused plan's rollouts leave their
     // per-row totals and this kernel reduces them, instead of a kernel launch of its own in between
     const float* totals = nullptr;
     int P = 0;
+    ParticleReduce reduce{};
     // refit only: when set, the caller has chosen the elites (DEVICE [n_env][K] candidate indices, best first) and the kernel's own
     // selection is skipped.  For the reference-order parity mode of the optimizer classes (sampler='torch'): torch.topk's order
     // among EQUAL values is whatever its partial sort leaves (trajectory_opt.py:179), and the 0 / 1 rewards of the cartpole family
@@ -103,18 +105,8 @@ __global__ __launch_bounds__(kRefitThreads) void cem_refit_kernel(const CemDev p
         values += (size_t)env * p.pop;
         if (p.totals && !(HIPETS_REFIT_SKIP & 1)) {
             const float* tot = p.totals + (size_t)env * p.pop * p.P;
-            for (int i = threadIdx.x; i < p.pop; i += kRefitThreads) {
-                float s = 0.f;  // the same sequential sum; a candidate's particle totals fetched eight at a time
-                for (int q0 = 0; q0 < p.P; q0 += 8) {
-                    float tv[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) tv[u] = tot[(size_t)i * p.P + min(q0 + u, p.P - 1)];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u)
-                        if (q0 + u < p.P) s += tv[u];
-                }
-                values[i] = s / (float)p.P;
-            }
+            // (every workgroup of the environment forms every value: a deterministic rule, the same bits from each)
+            for (int i = threadIdx.x; i < p.pop; i += kRefitThreads) values[i] = particle_value(tot + (size_t)i * p.P, 1, p.P, p.reduce);
         }
         population += (size_t)env * p.pop * p.D;
         mu += (size_t)env * p.D;

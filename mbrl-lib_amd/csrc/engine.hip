@@ -33,6 +33,13 @@ int fail_kind(const int kind, const char* fmt, ...) {
     return 1;
 }
 
+int check_reduce(const hipets_engine* e, const int P) {
+    if (e->reduce.kind != HIPETS_REDUCE_WORST_K) return 0;
+    if (P > kWorstKMaxP) return fail("particle reduction WORST_K: %d particles (max %d)", P, kWorstKMaxP);
+    if (e->reduce.k > P) return fail("particle reduction WORST_K: worst_k %d > %d particles", e->reduce.k, P);
+    return 0;
+}
+
 int stage_h2d(hipets_engine* e, void* dst, const void* src, size_t bytes, hipStream_t st) {
     hipets_engine::HostStage& sl = e->stage[e->stage_next];
     e->stage_next = (e->stage_next + 1) % 4;
@@ -128,6 +135,17 @@ int hipets_set_plan_mode(hipets_engine* e, int32_t mode) {
     if (!e) return fail("null engine");
     if (mode != HIPETS_MODE_FAST && mode != HIPETS_MODE_DEVICE) return fail("plan mode must be HIPETS_MODE_FAST or HIPETS_MODE_DEVICE");
     e->plan_mode = mode;
+    return 0;
+}
+
+int hipets_set_particle_reduce(hipets_engine* e, int32_t kind, float kappa, int32_t worst_k) {
+    if (!e) return fail("null engine");
+    if (kind < HIPETS_REDUCE_MEAN || kind > HIPETS_REDUCE_WORST_K) return fail("unknown particle reduction %d (HIPETS_REDUCE_MEAN .. HIPETS_REDUCE_WORST_K)", kind);
+    if (!std::isfinite(kappa)) return fail("particle reduction: kappa must be finite");
+    if (kind == HIPETS_REDUCE_WORST_K && worst_k < 1) return fail("particle reduction WORST_K: worst_k %d < 1", worst_k);
+    e->reduce.kind = kind;
+    e->reduce.kappa = kind == HIPETS_REDUCE_MEAN_STD ? kappa : 0.f;
+    e->reduce.k = kind == HIPETS_REDUCE_WORST_K ? worst_k : 0;
     return 0;
 }
 

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/hipets.h"
+#include "particle_reduce.hpp"
 #include "planet_types.hpp"
 #include "rollout_types.hpp"
 
@@ -112,6 +113,8 @@ struct hipets_engine {
     DevBuf planet_w, planet_b, planet_member, planet_ops;
     // fused plans: randomness mode of their rollouts, optional per-iteration trace
     int plan_mode = HIPETS_MODE_FAST;
+    // how every entry point that reduces a candidate's particles forms its value (hipets_set_particle_reduce; particle_reduce.hpp)
+    hipets::ParticleReduce reduce{};
     bool has_trace = false;
     hipets_plan_trace trace{};
     // timing: every timing_stride-th rollout-kernel launch carries a start / stop event pair on its dispatch packet
@@ -168,7 +171,14 @@ struct LocalErr {
     }
 };
 
+// the engine's reduction against the particle count of a call (WORST_K: worst_k <= P <= 256); every call that reduces particles asks
+// before it enqueues anything, a sharded plan on every rank alike
+int check_reduce(const hipets_engine* e, int P);
+
 // ---- rollout.hip (the one unit that includes rollout_helpers.hpp: its small kernels are launched from there) ----
+
+// returns [pop] = the engine's reduction of totals [pop * P] (particle_mean_kernel); the caller has passed check_reduce
+int launch_particle_reduce(const hipets_engine* e, const float* totals, float* returns, int pop, int P, hipStream_t st);
 
 // hipets_rollout with a plan-level shortcut: s0 == nullptr means the initial state(s) are already staged in e->s0 (the observation
 // is the same for every iteration of a plan); returns == nullptr: the caller reduces e->totals over the particles itself (the CEM /

@@ -175,12 +175,13 @@ struct PlanObjective {
         if (is_sharded()) HCHECK(hipMemsetAsync(e->shard_values.p, 0, shard_width(e, max_rows) * 4, st));
         return 0;
     }
-    // a local rollout left its per-row totals: the refit kernel forms the particle means (same sum, same bits).  A sharded plan's
-    // values come from the all-gather.
+    // a local rollout left its per-row totals: the refit kernel reduces them over the particles under the engine's reduction (the rule of
+    // particle_mean_kernel: same bits).  A sharded plan's values come from the all-gather.
     void refit_from_totals(hipets_engine* e, CemDev* c, int P) const {
         if (is_sharded()) return;
         c->totals = e->totals.as<float>();
         c->P = P;
+        c->reduce = e->reduce;
     }
     // `rows` candidates of ro->n_env environments (environment after environment), iteration ro->stream_id, into `returns` (nullptr:
     // the per-row totals stay in e->totals for the refit; a sharded objective always fills e->values).  Returns non-zero only when a
@@ -226,7 +227,7 @@ int check_plan(const hipets_engine* e, const PlanObjective& obj, bool args, int 
     if (!planet && A != e->md.act_dim) return fail("act_dim %d != model act_dim %d", A, e->md.act_dim);
     if (n_env < 1 || n_env > 4096) return fail("n_env %d outside [1, 4096]", n_env);
     if (planet && P < 1) return fail("bad pop/horizon/particles");
-    return 0;
+    return check_reduce(e, P);  // (a sharded plan: on every rank alike, before the first collective)
 }
 
 // CEM refit (cem.hpp): one row of workgroups per environment; the elite selection sorts the next power of two >= c.pop values in LDS

@@ -1,5 +1,5 @@
 // rollout.hip -- rollouts of the C ABI (include/hipets.h): launch geometry, the binding from a call's mode to the kernel's arguments,
-// hipets_rollout / hipets_step / hipets_planet_rollout / hipets_trajectory_returns, the geometry queries and the exports of the device-side randomness.  The one
+// hipets_rollout / hipets_step / hipets_planet_rollout / hipets_trajectory_returns / hipets_particle_reduce, the geometry queries and the exports of the device-side randomness.  The one
 // unit that includes residency.hpp (the launcher of every rollout kernel instance) and rollout_helpers.hpp (the small kernels around it).
 #include <hip/hip_ext.h>
 
@@ -261,6 +261,12 @@ int pack_bias(hipStream_t st, float* dst, const float* src, const int* members, 
     return 0;
 }
 
+int launch_particle_reduce(const hipets_engine* e, const float* totals, float* returns, int pop, int P, hipStream_t st) {
+    hipLaunchKernelGGL(particle_mean_kernel, dim3((pop + 255) / 256), dim3(256), 0, st, totals, returns, pop, P, e->reduce);
+    HCHECK(hipGetLastError());
+    return 0;
+}
+
 int plan_step_keys(hipets_engine* e, int H, int iters, uint64_t seed, uint64_t first_stream, hipStream_t st) {
     if (e->md.propagation != HIPETS_PROP_RANDOM_MODEL || iters < 1 || e->plan_mode != HIPETS_MODE_DEVICE || !e->persistent_ok) return 0;
     if (e->plan_keys.ensure((size_t)iters * H * sizeof(PermKeys))) return 1;
@@ -276,6 +282,7 @@ int rollout_impl(hipets_engine* e, const float* actions, const float* s0, int32_
     if (!e || !e->has_model) return fail("engine has no model (call hipets_set_model)");
     if (!actions || !o) return fail("null argument");  // (returns == nullptr: internal callers that fold the particle mean)
     if (pop < 1 || H < 1 || P < 1) return fail("bad pop/horizon/particles");
+    if (check_reduce(e, P)) return 1;
     if (e->error_flag && *e->error_flag) {  // raised by an EARLIER launch: its returns were garbage
         *e->error_flag = 0;
         e->persistent_ok = false;  // fall back to one launch per step from now on
@@ -393,9 +400,7 @@ int rollout_impl(hipets_engine* e, const float* actions, const float* s0, int32_
         if (launch_rollout(e, g.R, nwg, g.lds, ra, st)) return 1;
     }
     if (!returns) return 0;  // the caller reduces e->totals over the particles itself (hipets_plan_cem: inside the refit kernel)
-    hipLaunchKernelGGL(particle_mean_kernel, dim3((pop + 255) / 256), dim3(256), 0, st, e->totals.as<float>(), returns, pop, P);
-    HCHECK(hipGetLastError());
-    return 0;
+    return launch_particle_reduce(e, e->totals.as<float>(), returns, pop, P, st);
 }
 
 // Which PlaNet kernel instance a launch on this engine runs: the STATIC one for models with conf's tile counts (planet_static_shape, decided
@@ -408,6 +413,7 @@ static bool planet_launches_static(const hipets_engine* e) {
 
 int planet_rollout_impl(hipets_engine* e, const float* actions, const float* latent0, const float* belief0, int32_t pop, int32_t H,
                         int32_t P, const hipets_planet_opts* o, float* returns, hipStream_t st) {
+    if (check_reduce(e, P)) return 1;
     const int n_env = std::max(o->n_env, 1);
     if (o->n_env < 0 || n_env > 4096) return fail("n_env %d outside [0, 4096]", o->n_env);
     if (pop % n_env) return fail("PlaNet rollout: population %d is not divisible by n_env %d", pop, n_env);
@@ -434,9 +440,7 @@ int planet_rollout_impl(hipets_engine* e, const float* actions, const float* lat
     const int nwg = (int)((B + kTile - 1) / kTile);
     HCHECK(launch_planet_rollout(nwg, (unsigned)lds, (int)e->lds_max, e->pd, ra, st, planet_launches_static(e)));
     if (!returns) return 0;
-    hipLaunchKernelGGL(particle_mean_kernel, dim3((pop + 255) / 256), dim3(256), 0, st, e->totals.as<float>(), returns, pop, P);
-    HCHECK(hipGetLastError());
-    return 0;
+    return launch_particle_reduce(e, e->totals.as<float>(), returns, pop, P, st);
 }
 
 }  // namespace hipets
@@ -546,13 +550,14 @@ int hipets_trajectory_returns(hipets_engine* e, const float* rewards, const uint
     if (pop < 1 || H < 1 || P < 1) return fail("bad pop/horizon/particles");
     const long long B = (long long)pop * P;
     if (B > 0x7FFFFFFF) return fail("batch too large");
+    if (check_reduce(e, P)) return 1;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);  // (the two-pass form below may run on the engine's row totals)
     if (P <= kReturnsThreads) {
         const int cpb = kReturnsThreads / P;  // whole candidates per workgroup
         hipLaunchKernelGGL(trajectory_returns_kernel, dim3((unsigned)((pop + cpb - 1) / cpb)), dim3(kReturnsThreads), 0, st, rewards, dones, pop, H, P, cpb,
-                           returns, row_totals, first_done);
+                           e->reduce, returns, row_totals, first_done);
         HCHECK(hipGetLastError());
         return 0;
     }
@@ -562,11 +567,18 @@ int hipets_trajectory_returns(hipets_engine* e, const float* rewards, const uint
         row_totals = e->totals.as<float>();
     }
     hipLaunchKernelGGL(trajectory_returns_kernel, dim3((unsigned)((B + kReturnsThreads - 1) / kReturnsThreads)), dim3(kReturnsThreads), 0, st, rewards, dones,
-                       pop, H, P, 0, static_cast<float*>(nullptr), row_totals, first_done);
+                       pop, H, P, 0, e->reduce, static_cast<float*>(nullptr), row_totals, first_done);
     HCHECK(hipGetLastError());
-    hipLaunchKernelGGL(particle_mean_kernel, dim3((pop + 255) / 256), dim3(256), 0, st, row_totals, returns, pop, P);
-    HCHECK(hipGetLastError());
-    return 0;
+    return launch_particle_reduce(e, row_totals, returns, pop, P, st);
+}
+
+int hipets_particle_reduce(hipets_engine* e, const float* totals, int32_t pop, int32_t num_particles, float* returns, void* stream) {
+    if (!e || !totals || !returns) return fail("null argument");
+    if (pop < 1 || num_particles < 1) return fail("bad pop/particles");
+    if ((long long)pop * num_particles > 0x7FFFFFFF) return fail("batch too large");
+    if (check_reduce(e, num_particles)) return 1;
+    HCHECK(hipSetDevice(e->device));
+    return launch_particle_reduce(e, totals, returns, pop, num_particles, reinterpret_cast<hipStream_t>(stream));
 }
 
 int hipets_fast_schedule(hipets_engine* e, int32_t H, int32_t nwg, uint64_t seed, uint64_t stream_id, int32_t* schedule,

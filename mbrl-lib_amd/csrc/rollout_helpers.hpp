@@ -6,6 +6,7 @@
 #include "common.hpp"
 #include "gemm_bf16.hpp"
 #include "gemm_f32.hpp"
+#include "particle_reduce.hpp"
 #include "rollout_types.hpp"
 
 namespace hipets {
@@ -23,13 +24,12 @@ __global__ void init_state_kernel(float* state, float* totals, unsigned char* te
     if (i < B) { totals[i] = 0.f; term[i] = 0; }
 }
 
-// model_env.py:190-191: total_rewards.reshape(-1, P).mean(dim=1)
-__global__ void particle_mean_kernel(const float* totals, float* returns, int pop, int P) {
+// model_env.py:190-191: total_rewards.reshape(-1, P).mean(dim=1) -- or the engine's other reduction over the particles (particle_reduce.hpp;
+// the kernel keeps the name of its default)
+__global__ void particle_mean_kernel(const float* totals, float* returns, int pop, int P, const ParticleReduce r) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= pop) return;
-    float s = 0.f;
-    for (int p = 0; p < P; ++p) s += totals[(size_t)c * P + p];
-    returns[c] = s / (float)P;
+    returns[c] = particle_value(totals + (size_t)c * P, 1, P, r);
 }
 
 // model_env.py:186-191 over a finished trajectory (hipets_trajectory_returns): rewards / dones [H, B] of rollouts whose reward and
@@ -38,13 +38,14 @@ __global__ void particle_mean_kernel(const float* totals, float* returns, int po
 //     r = term ? 0 : rewards[t][row];  term |= dones[t][row] != 0;  tot += r
 // (a select, like the reference's rewards[terminated] = 0: whatever a terminated row's reward holds, NaN included, adds exactly 0).
 // cand_per_block > 0: the workgroup owns candidates [blockIdx.x * cand_per_block, + cand_per_block) = cand_per_block * P consecutive
-// rows (<= kReturnsThreads); their totals go through LDS to the thread that runs candidate c's chain of particle_mean_kernel above (the
-// same sequential sum and division: the same bits).  cand_per_block == 0 (P > kReturnsThreads): rows only, blockDim.x per workgroup,
+// rows (<= kReturnsThreads); their totals go through LDS to the thread that runs candidate c's particle_value, as particle_mean_kernel
+// above does (the same rule: the same bits).  cand_per_block == 0 (P > kReturnsThreads): rows only, blockDim.x per workgroup,
 // into row_totals (never null then); the launcher runs particle_mean_kernel behind it.
 constexpr int kReturnsThreads = 256;
 __global__ __launch_bounds__(kReturnsThreads) void trajectory_returns_kernel(const float* __restrict__ rewards, const unsigned char* __restrict__ dones,
-                                                                             int pop, int H, int P, int cand_per_block, float* __restrict__ returns,
-                                                                             float* __restrict__ row_totals, int* __restrict__ first_done) {
+                                                                             int pop, int H, int P, int cand_per_block, const ParticleReduce r,
+                                                                             float* __restrict__ returns, float* __restrict__ row_totals,
+                                                                             int* __restrict__ first_done) {
     __shared__ float tot_s[kReturnsThreads];
     const long long B = (long long)pop * P;
     const int tid = threadIdx.x;
@@ -71,11 +72,7 @@ __global__ __launch_bounds__(kReturnsThreads) void trajectory_returns_kernel(con
     if (cand_per_block == 0) return;
     __syncthreads();
     const long long c = (long long)blockIdx.x * cand_per_block + tid;
-    if (tid < cand_per_block && c < pop) {
-        float s = 0.f;
-        for (int p = 0; p < P; ++p) s += tot_s[tid * P + p];
-        returns[c] = s / (float)P;
-    }
+    if (tid < cand_per_block && c < pop) returns[c] = particle_value(tot_s + tid * P, 1, P, r);
 }
 
 // Export of the FAST-mode member schedule (hipets_fast_schedule): sched[t][w] = the member slot workgroup w of nwg draws for step t

@@ -21,6 +21,7 @@ from .model import (  # noqa: F401
     spec_from_planet_model,
 )
 from .engine import Engine  # noqa: F401
+from .reduce import ParticleReduce  # noqa: F401
 from .planning import (  # noqa: F401
     Agent,
     BatchedCEMAgent,

@@ -45,6 +45,7 @@ MAX_REWARD_TERMS, MAX_TERM_INTERVALS = 64, 64
 COL_FN = {"id": 0, "sin": 1, "cos": 2}  # HIPETS_COL_*
 MAX_OBS_COLUMNS = 512
 KERNEL_CLASSES = ("generic", "hidden_static", "fused", "wide", "bf16")  # HIPETS_KERNEL_*
+REDUCE = {"mean": 0, "mean_std": 1, "min": 2, "max": 3, "worst_k": 4}  # HIPETS_REDUCE_*
 
 
 class RewardTermC(C.Structure):  # hipets_reward_term
@@ -147,7 +148,8 @@ class TrainDesc(C.Structure):
     ]
 
 
-_CTYPES = {"": C.c_void_p, "i32": C.c_int32, "i64": C.c_int64, "u64": C.c_uint64, "f64": C.c_double, "int": C.c_int, "ptr": C.c_void_p}
+_CTYPES = {"": C.c_void_p, "i32": C.c_int32, "i64": C.c_int64, "u64": C.c_uint64, "f32": C.c_float, "f64": C.c_double, "int": C.c_int,
+           "ptr": C.c_void_p}
 
 
 def _sig(params: str, restype=C.c_int):
@@ -173,6 +175,8 @@ SYMBOLS = {
     "hipets_rollout": _sig("e actions s0 pop:i32 horizon:i32 num_particles:i32 opts:RolloutOpts* returns stream"),
     "hipets_step": _sig("e obs actions batch:i32 opts:RolloutOpts* next_obs rewards dones stream"),
     "hipets_trajectory_returns": _sig("e rewards dones pop:i32 horizon:i32 num_particles:i32 returns row_totals first_done stream"),
+    "hipets_set_particle_reduce": _sig("e kind:i32 kappa:f32 worst_k:i32"),
+    "hipets_particle_reduce": _sig("e totals pop:i32 num_particles:i32 returns stream"),
     "hipets_fast_geometry": _sig("e pop:i32 num_particles:i32 horizon:i32 rows_per_group:i32 n_workgroups:i32* row_tiles:i32*"),
     "hipets_kernel_class": _sig("e pop:i32 num_particles:i32 horizon:i32 mode:i32 rows_per_group:i32 kernel_class:i32* row_tiles:i32*"),
     "hipets_fast_schedule": _sig("e horizon:i32 n_workgroups:i32 seed:u64 stream_id:u64 schedule stream"),

@@ -13,6 +13,7 @@ from ._lib import CemParams, HipetsError
 from ._pack import (_check_dev, member_slots, pack_model_desc, pack_plan_trace, pack_planet_desc, pack_reward_terms,  # noqa: F401
                     pack_rollout_opts, pack_train_desc)
 from .model import ModelSpec
+from .reduce import ParticleReduce
 
 
 def _address(v):
@@ -59,6 +60,7 @@ class Engine:
         self.comm_world, self.comm_rank = 1, 0
         self.comm_group = None  # torch.distributed group of the communicator's ranks (hipets.dist.init_engine_comm)
         self.plan_mode = "fast"  # (the library's initial value; every fused plan sets its objective's mode: optimizers._prepare_fused)
+        self.reduce = ParticleReduce()  # (the library's initial value, the mean; every objective sets its own: _Objective.bind_model)
         self._trace = None
 
     def close(self):
@@ -232,6 +234,19 @@ class Engine:
             raise ValueError("plan mode must be 'fast' or 'device'")
         self._query("hipets_set_plan_mode", mode=_lib.MODES[mode])
         self.plan_mode = mode
+
+    def set_particle_reduce(self, reduce: ParticleReduce):
+        """How every call that reduces a candidate's particles forms its value from now on (hipets_set_particle_reduce): rollouts,
+        ``trajectory_returns``, ``particle_reduce`` and every fused plan.  ``reduce``: a resolved reduction (``ParticleReduce.resolve``)."""
+        self._query("hipets_set_particle_reduce", **reduce.abi_args())
+        self.reduce = reduce
+
+    def particle_reduce(self, totals: torch.Tensor, pop: int, num_particles: int) -> torch.Tensor:
+        """``totals`` f32 [pop * num_particles] (row c * P + p) -> f32 [pop] under the engine's reduction (hipets_particle_reduce)."""
+        _check_dev(totals, torch.float32, self.device, "totals", numel=int(pop) * int(num_particles))
+        out = torch.empty(int(pop), dtype=torch.float32, device=self.device)
+        self._call("hipets_particle_reduce", totals=totals, pop=int(pop), num_particles=int(num_particles), returns=out)
+        return out
 
     def set_persistent(self, on: bool = True):
         """Allow (default) or forbid the persistent one-launch form of DEVICE-mode rollouts (hipets_set_persistent)."""

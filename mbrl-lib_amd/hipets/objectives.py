@@ -16,6 +16,7 @@ from . import reference_draws as rd
 from .engine import Engine, get_engine
 from .model import (BoxTermination, ModelSpec, PlaNetSpec, UnsupportedModelError, is_planet_model, model_version, planet_version,
                     spec_from_model_env, spec_from_planet_model)
+from .reduce import ParticleReduce
 
 
 def _has_device_mode(spec: ModelSpec) -> bool:
@@ -37,10 +38,12 @@ def _device_f32(t: torch.Tensor, device) -> torch.Tensor:
 class _Objective:
     """What every objective shares: the spec, device and version token of a live model or of a spec (``_spec_type``) handed in
     as it is, re-packing when the live model changed, binding the spec to the engine shared per GPU, and the seed and call
-    counter of its counter-based streams.  A kind of objective supplies three hooks: ``_read_spec(live)``,
-    ``_read_version(live)`` and ``_set_engine_model(only_if_other)``."""
+    counter of its counter-based streams, and its reduction over the particles (``particle_reduce``: a :class:`ParticleReduce` or
+    'mean' / 'min' / 'max').  A kind of objective supplies three hooks: ``_read_spec(live)``, ``_read_version(live)`` and
+    ``_set_engine_model(only_if_other)``."""
 
-    def __init__(self, model, num_particles: int, engine: Optional[Engine], seed: int, device):
+    def __init__(self, model, num_particles: int, engine: Optional[Engine], seed: int, device, particle_reduce=None):
+        self.particle_reduce = ParticleReduce.coerce(particle_reduce)  # (a bad one raises before anything touches the engine)
         self.num_particles, self.seed, self.calls = int(num_particles), int(seed), 0
         self._live, self._version = None, None
         if isinstance(model, self._spec_type):
@@ -66,9 +69,13 @@ class _Objective:
             self._version = v
 
     def bind_model(self):
-        """Re-pack changed weights and make them the engine's model (engines are shared per GPU)."""
+        """Re-pack changed weights and make them the engine's model, and this objective's reduction over the particles the engine's
+        (engines are shared per GPU: a default objective that follows a risk-aware one sets the mean back)."""
         self.refresh()
         self._set_engine_model(only_if_other=True)
+        reduce = self.particle_reduce.resolve(self.num_particles)
+        if getattr(self.engine, "reduce", ParticleReduce()) != reduce:  # (an engine that mirrors none is at the library's initial mean)
+            self.engine.set_particle_reduce(reduce)
 
 
 class _EnsembleObjective(_Objective):
@@ -137,13 +144,13 @@ class _RolloutObjective(_EnsembleObjective):
     max_trajectory_bytes = 2 << 30
 
     def __init__(self, model, num_particles: int, engine: Optional[Engine] = None, mode: str = "device",
-                 seed: int = 0, device=None, rng: Optional[torch.Generator] = None):
+                 seed: int = 0, device=None, rng: Optional[torch.Generator] = None, particle_reduce=None):
         if mode not in ("fast", "device", "exact", "exact_device"):
             raise ValueError("mode must be 'fast', 'device', 'exact' or 'exact_device'")
         self.mode = mode
         self.rollout_kw = {}  # extra Engine.rollout arguments of every call (tests pin rows_per_group / generic_kernel)
         self._taps = None
-        super().__init__(model, num_particles, engine, seed, device)
+        super().__init__(model, num_particles, engine, seed, device, particle_reduce)
         if rng is None and self._live is not None:
             rng = getattr(model, "_rng", None)
         self._rng = rng
@@ -217,7 +224,8 @@ class _RolloutObjective(_EnsembleObjective):
     def trajectories(self, initial_state: np.ndarray, action_sequences: torch.Tensor) -> Dict[str, torch.Tensor]:
         """The predicted trajectories of ONE evaluation (the model side of ``mbrl.util.common.rollout_model_env``): ``next_obs``
         [H, B, obs], ``rewards`` [H, B] (before termination masking), ``dones`` bool [H, B], ``first_done`` int32 [B] (the first
-        terminating step, H if none), ``row_totals`` [B], ``returns`` [pop]; B = pop * num_particles, row c * P + p.  Counts as
+        terminating step, H if none), ``row_totals`` [B], ``returns`` [pop] (the objective's reduction of ``row_totals`` over the
+        particles); B = pop * num_particles, row c * P + p.  Counts as
         a call (it consumes the next stream, and returns what ``__call__`` would have); the views are valid until the next call."""
         return self._trajectory(initial_state, action_sequences, True)
 
@@ -242,6 +250,10 @@ class HipTrajectoryEvalFn(_RolloutObjective):
       to ``ModelEnv.evaluate_action_sequences`` (a parity aid: it synchronises with the host).
     * ``'exact_device'``: alias of ``'device'`` (kept for round-1 callers; BasicEnsemble models draw their iid
       member maps with torch's device generator).
+
+    ``particle_reduce``: how a candidate's ``num_particles`` totals become its value -- the mean (default, model_env.py:190-191), or
+    a :class:`ParticleReduce` (worst case, mean - kappa * std, the mean of the worst k / CVaR, best case) for planning under the
+    model's own uncertainty; the fused plans reduce the same way, inside their launches.
     """
 
     @property
@@ -405,11 +417,17 @@ class ModelEnv:
             return nobs.cpu().numpy(), rew.cpu().numpy(), done.cpu().numpy(), next_state
         return nobs, rew, done, next_state
 
-    def evaluate_action_sequences(self, action_sequences: torch.Tensor, initial_state: np.ndarray, num_particles: int) -> torch.Tensor:
-        """model_env.py:145-191."""
+    def evaluate_action_sequences(self, action_sequences: torch.Tensor, initial_state: np.ndarray, num_particles: int,
+                                  particle_reduce=None) -> torch.Tensor:
+        """model_env.py:145-191.  ``particle_reduce`` (this call only): a :class:`ParticleReduce` or 'mean' / 'min' / 'max' in place
+        of the mean over the particles."""
         assert len(action_sequences.shape) == 3
         self._eval.num_particles = int(num_particles)
-        return self._eval(initial_state, action_sequences)
+        self._eval.particle_reduce = ParticleReduce.coerce(particle_reduce)
+        try:
+            return self._eval(initial_state, action_sequences)
+        finally:
+            self._eval.particle_reduce = ParticleReduce()  # (reset / step bind the model too: they leave the engine at the mean)
 
 
 class UnfusedTrajectoryEvalFn(_EnsembleObjective):
@@ -425,11 +443,11 @@ class UnfusedTrajectoryEvalFn(_EnsembleObjective):
     _allow_custom_fns = True
 
     def __init__(self, model, num_particles: int, reward_fn=None, termination_fn=None, engine: Optional[Engine] = None,
-                 seed: int = 0, device=None, step_mode: str = "device"):
+                 seed: int = 0, device=None, step_mode: str = "device", particle_reduce=None):
         if step_mode not in ("device", "fast"):
             raise ValueError("step_mode must be 'device' or 'fast'")
         self.step_mode = step_mode
-        super().__init__(model, num_particles, engine, seed, device)
+        super().__init__(model, num_particles, engine, seed, device, particle_reduce)
         self.reward_fn = reward_fn if reward_fn is not None else self.spec.custom_reward_fn
         self.termination_fn = termination_fn if termination_fn is not None else self.spec.custom_termination_fn
 
@@ -466,7 +484,9 @@ class UnfusedTrajectoryEvalFn(_EnsembleObjective):
             terminated |= done  # :187
             total += rew  # :188
             obs = nobs
-        return total.reshape(-1, P).mean(dim=1)
+        if self.particle_reduce.kind == "mean":
+            return total.reshape(-1, P).mean(dim=1)
+        return self.engine.particle_reduce(total.reshape(-1).contiguous(), pop, P)  # (bind_model made the reduction the engine's)
 
 
 def _rowwise_output(out, n_rows: int, what: str, boolean: bool) -> torch.Tensor:
@@ -515,8 +535,8 @@ class CallableTrajectoryEvalFn(_RolloutObjective):
 
     def __init__(self, model, num_particles: int, reward_fn=None, termination_fn=None, engine: Optional[Engine] = None,
                  mode: str = "device", seed: int = 0, device=None, rng: Optional[torch.Generator] = None, check_rowwise: bool = True,
-                 max_trajectory_bytes: int = 2 << 30):
-        super().__init__(model, num_particles, engine, mode, seed, device, rng)
+                 max_trajectory_bytes: int = 2 << 30, particle_reduce=None):
+        super().__init__(model, num_particles, engine, mode, seed, device, rng, particle_reduce)
         self.reward_fn = reward_fn if reward_fn is not None else self.spec.custom_reward_fn
         self.termination_fn = termination_fn if termination_fn is not None else self.spec.custom_termination_fn
         if self.reward_fn is None and self.termination_fn is None:
@@ -579,7 +599,7 @@ class PlaNetTrajectoryEvalFn(_Objective):
     _read_version = staticmethod(planet_version)
 
     def __init__(self, model, num_particles: int = 1, engine: Optional[Engine] = None, mode: str = "device", seed: int = 0,
-                 device=None, rng: Optional[torch.Generator] = None):
+                 device=None, rng: Optional[torch.Generator] = None, particle_reduce=None):
         if mode not in ("device", "fast", "exact"):
             raise ValueError("mode must be 'device' (= 'fast': in-kernel draws) or 'exact'")
         self.mode, self._state = mode, None
@@ -587,7 +607,7 @@ class PlaNetTrajectoryEvalFn(_Objective):
             if rng is None:
                 rng = getattr(model, "_rng", None)
             model = getattr(model, "dynamics_model", model)  # a ModelEnv or the PlaNetModel itself
-        super().__init__(model, num_particles, engine, seed, device)
+        super().__init__(model, num_particles, engine, seed, device, particle_reduce)
         self._rng = rng
 
     def _set_engine_model(self, only_if_other: bool = False):
@@ -643,7 +663,8 @@ def make_eval_fn(model, num_particles: int, callables: str = "steps", **kw):
     model step per launch, the callables between the steps) and ``callables='trajectory'`` the one-launch
     :class:`CallableTrajectoryEvalFn` (the callables must be row-wise: they run once over all steps' rows).
     Without a ``mode=`` argument the objective runs ``mode='device'``: the reference's TS1 semantics (one balanced permutation
-    of all rows per step, gaussian_mlp.py:201-211), every draw made in-kernel; ``mode='fast'`` is the opt-in block-balanced variant."""
+    of all rows per step, gaussian_mlp.py:201-211), every draw made in-kernel; ``mode='fast'`` is the opt-in block-balanced variant.
+    ``particle_reduce=`` (every objective): a :class:`ParticleReduce` or 'mean' / 'min' / 'max', the reduction over the particles."""
     if callables not in ("steps", "trajectory"):
         raise ValueError(f"callables must be 'steps' or 'trajectory', got {callables!r}")
     if isinstance(model, PlaNetSpec) or is_planet_model(getattr(model, "dynamics_model", model)):
@@ -658,7 +679,7 @@ def make_eval_fn(model, num_particles: int, callables: str = "steps", **kw):
             raise
         if callables == "trajectory":
             return CallableTrajectoryEvalFn(model, num_particles, **kw)
-        kw2 = {k: v for k, v in kw.items() if k in ("engine", "seed", "device")}
+        kw2 = {k: v for k, v in kw.items() if k in ("engine", "seed", "device", "particle_reduce")}
         if kw.get("mode") in ("fast", "device"):
             kw2["step_mode"] = kw["mode"]
         return UnfusedTrajectoryEvalFn(model, num_particles, **kw2)
