@@ -704,6 +704,26 @@ int hipets_train_steps(hipets_engine* e, const hipets_train_desc* d, const float
  * order: the result is deterministic.  The Adam fields of d are not read.                                                */
 int hipets_train_eval(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows,
                       const int32_t* order, float* score, float* row_score, void* stream);
+/* Loss kinds of hipets_train_steps_loss / hipets_train_eval_loss (additive entry points: hipets_train_desc keeps its layout and
+ * HIPETS_ABI_VERSION its value; the new parameters travel as scalars). */
+#define HIPETS_TRAIN_LOSS_NLL 0 /* GaussianMLP._nll_loss (gaussian_mlp.py:291-305): what hipets_train_steps trains               */
+#define HIPETS_TRAIN_LOSS_MSE 1 /* GaussianMLP._mse_loss (gaussian_mlp.py:283-289) of a deterministic model                       */
+/* hipets_train_steps with a loss kind, per-member logvar bounds and a gradient scale; (HIPETS_TRAIN_LOSS_NLL, 0, 1.0f) IS
+ * hipets_train_steps.  Under HIPETS_TRAIN_LOSS_MSE the descriptor is read differently: the last layer is out_dim wide
+ * (d_{n_layers} = out_dim, no logvar columns), min_logvar / max_logvar are ignored and may be NULL, and loss[s, e] is the
+ * member's plain SUM over the step's rows and dims of the squared error (a sum, not a mean).  bounds_per_member != 0 (NLL): the
+ * bounds are DEVICE [E, out_dim], member e reads row e -- a BasicEnsemble (mbrl/models/basic_ensemble.py) of one-member
+ * GaussianMLPs stacked into one descriptor.  grad_scale (finite, > 0) multiplies the gradient of the loss before Adam and
+ * is therefore part of grad_sq, but not of loss: BasicEnsemble.loss divides the sum of the member losses by E, so each of
+ * its members trains with grad_scale = 1 / E.  1.0f changes no bit.  An unknown loss_kind, a grad_scale that is not finite or
+ * is <= 0, and NULL bounds under NLL fail with HIPETS_ERR_INVALID_ARGUMENT before anything is launched.                     */
+int hipets_train_steps_loss(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows,
+                            const int32_t* idx, const int32_t* rows, int32_t n_steps, int64_t step0, float* loss,
+                            float* grad_sq, void* stream, int32_t loss_kind, int32_t bounds_per_member, float grad_scale);
+/* hipets_train_eval for either loss kind: under HIPETS_TRAIN_LOSS_MSE the last layer is out_dim wide (all of its columns are
+ * means), under HIPETS_TRAIN_LOSS_NLL 2 out_dim wide (the first out_dim are).  The score is the same squared error.          */
+int hipets_train_eval_loss(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows,
+                           const int32_t* order, float* score, float* row_score, void* stream, int32_t loss_kind);
 
 /* ---- instrumentation (bench.py roofline leg) ----------------------------------------------- */
 /* on = 1: every rollout-kernel launch carries a start / stop hipEvent pair on its dispatch packet; on = k > 1: every

@@ -1,11 +1,14 @@
-// train.hip -- GaussianMLP ensemble training (hipets_train_steps / hipets_train_eval, include/hipets.h): the kernels, then the entry points.
-//   train_step_kernel  Model.update (mbrl/models/model.py:129-167) + torch.optim.Adam for a chunk of consecutive minibatches
+// train.hip -- GaussianMLP ensemble training (hipets_train_steps[_loss] / hipets_train_eval[_loss], include/hipets.h): the kernels, then the
+// entry points.
+//   train_step_kernel  Model.update (mbrl/models/model.py:129-167) + torch.optim.Adam for a chunk of consecutive minibatches, one
+//                      instantiation per loss kind (NLL, MSE); a BasicEnsemble is per-member bounds and grad_scale = 1 / E
 //   train_eval_kernel  GaussianMLP.eval_score over the whole evaluation set (gaussian_mlp.py:337-361), mean columns only
 // Every product runs on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32 accumulate).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
+#include <type_traits>
 
 #include "engine.hpp"
 #include "lds_optin.hpp"
@@ -112,14 +115,20 @@ __device__ __forceinline__ float adam(float p, float g, float* m, float* v, cons
     return p + nss * (mn / denom);
 }
 
-__device__ __forceinline__ float wave_sum(float x) {
+template <class T>
+__device__ __forceinline__ T wave_sum(T x) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
     return x;
 }
 
+// kLoss = the loss tail: kTrainLossNLL (output layer 2 out wide, mean | raw logvar) or kTrainLossMSE (output layer out wide).
+// The MSE loss is a sum, not a mean: the loss and the gradient are not scaled down by rows x dims, so loss[s, e] and grad_sq[s, e]
+// are large numbers whose float32 rounding shows; under MSE both are accumulated in double (same fixed order) and rounded once.
+template <int kLoss>
 __global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainStepArgs a) {
-    __shared__ float red[2][kTrainThreads / 64];
+    using acc_t = std::conditional_t<kLoss == kTrainLossMSE, double, float>;
+    __shared__ acc_t red[2][kTrainThreads / 64];
     const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int kWaves = kTrainThreads / 64;
     const int E = a.ensemble_size, L = a.n_layers, in = a.dims[0], out = a.out_dim, out2 = 2 * out, bmax = a.max_batch;
@@ -171,29 +180,40 @@ __global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainSt
             }
             __syncthreads();
         }
-        // ---- NLL tail (gaussian_mlp.py:143-153, 291-305; util/math.py:41-64) and its gradient w.r.t. O ----
         float* D = slab + a.off_d0;
-        float lsum = 0.f;
-        const float scale = 1.f / (float)(nb * out);  // mean over batch and output dims
-        for (int t = tid; t < nb * out; t += kTrainThreads) {
-            const int r = t / out, j = t - r * out;
-            const float mean = O[r * out2 + j], raw = O[r * out2 + out + j];
-            const float mx = a.max_logvar[j], mn = a.min_logvar[j];
-            const float u = mx - raw;
-            const float lv1 = mx - softplus(u);
-            const float w = lv1 - mn;
-            const float lv = mn + softplus(w);
-            const float d = mean - T[t];
-            const float iv = expf(-lv);
-            const float l2iv = d * d * iv;
-            lsum += l2iv + lv;
-            D[r * out2 + j] = 2.f * d * (scale * iv);
-            const float dlv = scale - scale * l2iv;
-            D[r * out2 + out + j] = dlv * softplus_grad(w) * softplus_grad(u);
+        acc_t lsum = 0;
+        if constexpr (kLoss == kTrainLossMSE) {
+            // ---- MSE tail (gaussian_mlp.py:283-289): the plain sum of squared errors; O and D are [nb, out] ----
+            for (int t = tid; t < nb * out; t += kTrainThreads) {
+                const float d = O[t] - T[t];
+                lsum += (acc_t)d * (acc_t)d;
+                D[t] = 2.f * d * a.grad_scale;
+            }
+        } else {
+            // ---- NLL tail (gaussian_mlp.py:143-153, 291-305; util/math.py:41-64) and its gradient w.r.t. O ----
+            const float scale = 1.f / (float)(nb * out) * a.grad_scale;  // mean over batch and output dims (times 1 / E: BasicEnsemble.loss)
+            const float* mxv = a.max_logvar + (int64_t)e * a.bounds_stride;
+            const float* mnv = a.min_logvar + (int64_t)e * a.bounds_stride;
+            for (int t = tid; t < nb * out; t += kTrainThreads) {
+                const int r = t / out, j = t - r * out;
+                const float mean = O[r * out2 + j], raw = O[r * out2 + out + j];
+                const float mx = mxv[j], mn = mnv[j];
+                const float u = mx - raw;
+                const float lv1 = mx - softplus(u);
+                const float w = lv1 - mn;
+                const float lv = mn + softplus(w);
+                const float d = mean - T[t];
+                const float iv = expf(-lv);
+                const float l2iv = d * d * iv;
+                lsum += l2iv + lv;
+                D[r * out2 + j] = 2.f * d * (scale * iv);
+                const float dlv = scale - scale * l2iv;
+                D[r * out2 + out + j] = dlv * softplus_grad(w) * softplus_grad(u);
+            }
         }
         __syncthreads();
         // ---- backward, last layer first: dA_l = dZ_l W_l^T (weights before the update), db, dW = A_l^T dZ_l with Adam fused ----
-        float gsq = 0.f;
+        acc_t gsq = 0;
         const float nss = a.neg_step_size[s], bc2s = a.bc2_sqrt[s];
         int cur = 0;
         for (int l = L - 1; l >= 0; --l) {
@@ -226,8 +246,20 @@ __global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainSt
                 float* vB = a.vb[l] + (int64_t)e * dout;
                 for (int j = tid; j < dout; j += kTrainThreads) {
                     float g = 0.f;
-                    for (int r = 0; r < nb; ++r) g += Dc[r * dout + j];
-                    gsq += g * g;
+                    if constexpr (kLoss == kTrainLossMSE) {
+                        // the MSE loss is a sum, not a mean: gradients are not scaled down by rows x dims, a bias gradient sums rows of both
+                        // signs, and its square is most of grad_sq -- so the rows are summed compensated (Kahan), to one rounding
+                        float comp = 0.f;
+                        for (int r = 0; r < nb; ++r) {
+                            const float yk = Dc[r * dout + j] - comp;
+                            const float tk = g + yk;
+                            comp = (tk - g) - yk;
+                            g = tk;
+                        }
+                    } else {
+                        for (int r = 0; r < nb; ++r) g += Dc[r * dout + j];
+                    }
+                    gsq += (acc_t)g * (acc_t)g;
                     bias[j] = adam(bias[j], g, mB + j, vB + j, a, nss, bc2s);
                 }
             }
@@ -245,7 +277,7 @@ __global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainSt
                             const int row = m0 + 4 * (lane >> 4) + i;
                             if (row < din) {
                                 const int64_t o = (int64_t)row * dout + col;
-                                gsq += c[i] * c[i];
+                                gsq += (acc_t)c[i] * (acc_t)c[i];
                                 W[o] = adam(W[o], c[i], mW + o, vW + o, a, nss, bc2s);
                             }
                         }
@@ -264,13 +296,13 @@ __global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainSt
         }
         __syncthreads();
         if (tid == 0) {
-            float ls = 0.f, gs = 0.f;
+            acc_t ls = 0, gs = 0;
             for (int w = 0; w < kWaves; ++w) {
                 ls += red[0][w];
                 gs += red[1][w];
             }
-            a.loss[(int64_t)s * E + e] = ls / (float)(nb * out);
-            a.grad_sq[(int64_t)s * E + e] = gs;
+            a.loss[(int64_t)s * E + e] = kLoss == kTrainLossMSE ? (float)ls : (float)ls / (float)(nb * out);
+            a.grad_sq[(int64_t)s * E + e] = (float)gs;
         }
         __syncthreads();
     }
@@ -364,8 +396,9 @@ __global__ __launch_bounds__(256) void train_eval_reduce_kernel(const TrainEvalA
 
 // ---- the C ABI's argument checks (hipets_train_steps / hipets_train_eval below) ----
 
-int train_check(const hipets_train_desc* d, bool adam) {
+int train_check(const hipets_train_desc* d, bool adam, int loss_kind) {
     if (!d) return fail("null train desc");
+    if (loss_kind != HIPETS_TRAIN_LOSS_NLL && loss_kind != HIPETS_TRAIN_LOSS_MSE) return fail("unknown loss kind %d", loss_kind);
     if (d->ensemble_size < 1 || d->ensemble_size > kTrainMaxMembers) return fail("ensemble_size %d outside [1, %d]", d->ensemble_size, kTrainMaxMembers);
     if (d->n_layers < 2 || d->n_layers > HIPETS_MAX_LAYERS) return fail("n_layers %d outside [2, %d]", d->n_layers, HIPETS_MAX_LAYERS);
     if (d->in_dim < 1 || d->in_dim > kTrainMaxIn) return fail("in_dim %d outside [1, %d]", d->in_dim, kTrainMaxIn);
@@ -377,8 +410,8 @@ int train_check(const hipets_train_desc* d, bool adam) {
     for (int l = 0; l < d->n_layers; ++l)
         if (!d->weights[l] || !d->biases[l]) return fail("null parameter of layer %d", l);
     if (adam) {
-        if (!d->exp_avg_w || !d->exp_avg_b || !d->exp_avg_sq_w || !d->exp_avg_sq_b || !d->min_logvar || !d->max_logvar)
-            return fail("null Adam state or logvar bounds");
+        if (!d->exp_avg_w || !d->exp_avg_b || !d->exp_avg_sq_w || !d->exp_avg_sq_b) return fail("null Adam state or logvar bounds");
+        if (loss_kind == HIPETS_TRAIN_LOSS_NLL && (!d->min_logvar || !d->max_logvar)) return fail("null Adam state or logvar bounds");
         for (int l = 0; l < d->n_layers; ++l)
             if (!d->exp_avg_w[l] || !d->exp_avg_b[l] || !d->exp_avg_sq_w[l] || !d->exp_avg_sq_b[l]) return fail("null Adam state of layer %d", l);
         // torch.optim.Adam's own argument checks (torch/optim/adam.py)
@@ -389,16 +422,19 @@ int train_check(const hipets_train_desc* d, bool adam) {
     return 0;
 }
 
-void train_dims(const hipets_train_desc* d, int32_t* dims) {
+void train_dims(const hipets_train_desc* d, int loss_kind, int32_t* dims) {
     dims[0] = d->in_dim;
     for (int l = 1; l < d->n_layers; ++l) dims[l] = d->hid;
-    dims[d->n_layers] = 2 * d->out_dim;
+    dims[d->n_layers] = loss_kind == HIPETS_TRAIN_LOSS_MSE ? d->out_dim : 2 * d->out_dim;
 }
 
 }  // namespace
 
-hipError_t launch_train_steps(const TrainStepArgs& a, hipStream_t st) {
-    hipLaunchKernelGGL(train_step_kernel, dim3(a.ensemble_size), dim3(kTrainThreads), 0, st, a);
+hipError_t launch_train_steps(const TrainStepArgs& a, int loss_kind, hipStream_t st) {
+    if (loss_kind == kTrainLossMSE)
+        hipLaunchKernelGGL(train_step_kernel<kTrainLossMSE>, dim3(a.ensemble_size), dim3(kTrainThreads), 0, st, a);
+    else
+        hipLaunchKernelGGL(train_step_kernel<kTrainLossNLL>, dim3(a.ensemble_size), dim3(kTrainThreads), 0, st, a);
     return hipGetLastError();
 }
 
@@ -423,8 +459,15 @@ extern "C" {
 
 int hipets_train_steps(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows, const int32_t* idx,
                        const int32_t* rows, int32_t n_steps, int64_t step0, float* loss, float* grad_sq, void* stream) {
+    return hipets_train_steps_loss(e, d, x, y, n_rows, idx, rows, n_steps, step0, loss, grad_sq, stream, HIPETS_TRAIN_LOSS_NLL, 0, 1.0f);
+}
+
+int hipets_train_steps_loss(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows, const int32_t* idx,
+                            const int32_t* rows, int32_t n_steps, int64_t step0, float* loss, float* grad_sq, void* stream, int32_t loss_kind,
+                            int32_t bounds_per_member, float grad_scale) {
     if (!e) return fail("null engine");
-    if (train_check(d, true)) return 1;
+    if (train_check(d, true, loss_kind)) return 1;
+    if (!std::isfinite(grad_scale) || !(grad_scale > 0.f)) return fail("grad_scale %g is not a finite positive number", (double)grad_scale);
     if (!x || !y || !idx || !rows || !loss || !grad_sq) return fail("null argument");
     if (n_rows < 1 || n_rows > INT32_MAX) return fail("n_rows %lld outside [1, 2^31)", (long long)n_rows);
     if (n_steps < 0) return fail("n_steps %d < 0", n_steps);
@@ -435,7 +478,7 @@ int hipets_train_steps(hipets_engine* e, const hipets_train_desc* d, const float
     ENTER_STREAM(e, st);
     TrainStepArgs a{};
     const int L = d->n_layers, E = d->ensemble_size, Bm = d->max_batch;
-    train_dims(d, a.dims);
+    train_dims(d, loss_kind, a.dims);
     int64_t off = 0, widest = 0;
     auto take = [&](int64_t n) { const int64_t o = off; off += (n + 63) / 64 * 64; return o; };
     for (int l = 0; l < L; ++l) a.off_a[l] = take((int64_t)Bm * a.dims[l]);
@@ -460,6 +503,8 @@ int hipets_train_steps(hipets_engine* e, const hipets_train_desc* d, const float
     a.y = y;
     a.min_logvar = d->min_logvar;
     a.max_logvar = d->max_logvar;
+    a.bounds_stride = bounds_per_member ? d->out_dim : 0;
+    a.grad_scale = grad_scale;
     a.n_rows = n_rows;
     a.n_layers = L;
     a.out_dim = d->out_dim;
@@ -496,7 +541,7 @@ int hipets_train_steps(hipets_engine* e, const hipets_train_desc* d, const float
         a.rows = rows + s0;
         a.loss = loss + (int64_t)s0 * E;
         a.grad_sq = grad_sq + (int64_t)s0 * E;
-        hipError_t err = launch_train_steps(a, st);
+        hipError_t err = launch_train_steps(a, loss_kind, st);
         if (err != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "train step kernel launch failed: %s", hipGetErrorString(err));
     }
     return 0;
@@ -504,8 +549,13 @@ int hipets_train_steps(hipets_engine* e, const hipets_train_desc* d, const float
 
 int hipets_train_eval(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows, const int32_t* order,
                       float* score, float* row_score, void* stream) {
+    return hipets_train_eval_loss(e, d, x, y, n_rows, order, score, row_score, stream, HIPETS_TRAIN_LOSS_NLL);
+}
+
+int hipets_train_eval_loss(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows, const int32_t* order,
+                           float* score, float* row_score, void* stream, int32_t loss_kind) {
     if (!e) return fail("null engine");
-    if (train_check(d, false)) return 1;
+    if (train_check(d, false, loss_kind)) return 1;
     if (!x || !y || !score) return fail("null argument");
     if (n_rows < 1 || n_rows > INT32_MAX) return fail("n_rows %lld outside [1, 2^31)", (long long)n_rows);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -513,7 +563,7 @@ int hipets_train_eval(hipets_engine* e, const hipets_train_desc* d, const float*
     ENTER_STREAM(e, st);
     TrainEvalArgs a{};
     const int L = d->n_layers, E = d->ensemble_size;
-    train_dims(d, a.dims);
+    train_dims(d, loss_kind, a.dims);
     for (int l = 0; l < L; ++l) {
         a.w[l] = static_cast<const float*>(d->weights[l]);
         a.b[l] = static_cast<const float*>(d->biases[l]);

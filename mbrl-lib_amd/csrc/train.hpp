@@ -17,11 +17,16 @@ constexpr int kTrainMaxOut = 512;         // target columns; the output layer is
 constexpr int kTrainMaxBatch = 256;
 constexpr int kEvalRows = 32;             // rows per evaluate workgroup
 constexpr int kEvalThreads = 256;
+constexpr int kTrainLossNLL = HIPETS_TRAIN_LOSS_NLL;  // the loss tail train_step_kernel is instantiated for
+constexpr int kTrainLossMSE = HIPETS_TRAIN_LOSS_MSE;
 
 // One launch = n_steps consecutive minibatch steps, one workgroup per member (members never communicate: the loss is a sum
 // over members, Adam is elementwise, the logvar bounds are constants).  Everything a step keeps for its backward pass lives
 // in the member's slab (global, L2-resident): per layer its input A_l and (hidden layers) its pre-activation Z_l, the raw
 // output O, the gathered targets T and two gradient ping-pong buffers D0 / D1.
+// Loss kinds: NLL (GaussianMLP._nll_loss: the output layer is 2 out wide, mean | raw logvar) and MSE (GaussianMLP._mse_loss of a
+// deterministic model: the output layer is out wide, the loss a plain sum of squared errors, no logvar columns anywhere).
+// A BasicEnsemble of one-member GaussianMLPs is the same launch with per-member bounds (bounds_stride = out) and grad_scale = 1 / E.
 struct TrainStepArgs {
     float* w[HIPETS_MAX_LAYERS];   // [E, d_l, d_{l+1}]  (torch's EnsembleLinearLayer layout)
     float* b[HIPETS_MAX_LAYERS];   // [E, 1, d_{l+1}]
@@ -33,25 +38,27 @@ struct TrainStepArgs {
     const float* y;                // [n_rows, out] targets
     const int32_t* idx;            // [n_steps, E, max_batch] dataset rows of every (step, member)
     const int32_t* rows;           // [n_steps] rows of every step (the last minibatch of an epoch is ragged)
-    const float* min_logvar;       // [out]
+    const float* min_logvar;       // [out], or [E, out] with bounds_stride = out; not read under MSE
     const float* max_logvar;
     float* slab;                   // [E, slab_stride]
-    float* loss;                   // [n_steps, E] mean NLL of every member
-    float* grad_sq;                // [n_steps, E] sum of squares of the raw gradient (before weight decay)
+    float* loss;                   // [n_steps, E] mean NLL (MSE: sum of squared errors) of every member, without grad_scale
+    float* grad_sq;                // [n_steps, E] sum of squares of the raw gradient (before weight decay; grad_scale included)
     int64_t slab_stride;
     int64_t off_a[HIPETS_MAX_LAYERS];  // slab offsets (floats): layer inputs
     int64_t off_z[HIPETS_MAX_LAYERS];  //   hidden pre-activations
     int64_t off_o, off_t, off_d0, off_d1;
     int64_t n_rows;
-    int32_t dims[HIPETS_MAX_LAYERS + 1];  // in, hid ... hid, 2 out
+    int32_t dims[HIPETS_MAX_LAYERS + 1];  // in, hid ... hid, 2 out (MSE: out)
     int32_t n_layers, out_dim, ensemble_size, max_batch, n_steps, activation;
+    int32_t bounds_stride;         // member stride of min_logvar / max_logvar: 0 = shared [out], out = per member [E, out]
     float leaky_slope;
+    float grad_scale;              // multiplied into the loss gradient (1 / E of BasicEnsemble.loss); 1.0f is exact
     float weight_decay, one_minus_beta1, beta2, one_minus_beta2, eps;
     float neg_step_size[kTrainMaxSteps];  // -(lr / (1 - beta1^t)) of every step t of the launch, rounded from double
     float bc2_sqrt[kTrainMaxSteps];       // (1 - beta2^t)^0.5
 };
 
-// evaluate: the mean columns only, many workgroups over (row tile, member); partial sums [E, tiles] reduced in a fixed order
+// evaluate: the mean columns only (the first out_dim of the dims[n_layers] the output layer has), many workgroups over (row tile, member); partial sums [E, tiles] reduced in a fixed order
 struct TrainEvalArgs {
     const float* w[HIPETS_MAX_LAYERS];
     const float* b[HIPETS_MAX_LAYERS];
@@ -67,7 +74,7 @@ struct TrainEvalArgs {
     float leaky_slope;
 };
 
-hipError_t launch_train_steps(const TrainStepArgs& a, hipStream_t st);
+hipError_t launch_train_steps(const TrainStepArgs& a, int loss_kind, hipStream_t st);
 hipError_t launch_train_eval(const TrainEvalArgs& a, hipStream_t st);
 
 }  // namespace hipets

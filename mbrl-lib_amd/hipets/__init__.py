@@ -50,7 +50,7 @@ from .propagation import (  # noqa: F401
     propagate_from_indices,
     propagate_random_model,
 )
-from .trainer import ModelTrainer  # noqa: F401
+from .trainer import ModelTrainer, make_model_trainer  # noqa: F401
 from . import dist  # noqa: F401
 
 __version__ = "0.1.0"

@@ -13,6 +13,7 @@ ABI_VERSION = 9
 MAX_LAYERS = 8
 
 ACT = {"relu": 0, "silu": 1, "leaky_relu": 2, "tanh": 3, "sigmoid": 4}
+TRAIN_LOSS = {"nll": 0, "mse": 1}  # HIPETS_TRAIN_LOSS_*
 PROP = {"random_model": 0, "fixed_model": 1, "expectation": 2}
 OBS = {"none": 0, "halfcheetah": 1, "cartpole_pets": 2, "columns": 3}  # (columns: a hipets.ObsColumns table, HIPETS_OBS_COLUMNS)
 REW = {None: 0, "learned": 0, "cartpole": 1, "cartpole_pets": 2, "inverted_pendulum": 3, "halfcheetah": 4, "pusher": 5, "none": 6,
@@ -225,6 +226,9 @@ SYMBOLS = {
                                             "num_particles:i32 seed:u64 plan_id:u64 out stream"),
     "hipets_train_steps": _sig("e d:TrainDesc* x y n_rows:i64 idx rows n_steps:i32 step0:i64 loss grad_sq stream"),
     "hipets_train_eval": _sig("e d:TrainDesc* x y n_rows:i64 order score row_score stream"),
+    "hipets_train_steps_loss": _sig("e d:TrainDesc* x y n_rows:i64 idx rows n_steps:i32 step0:i64 loss grad_sq stream loss_kind:i32 "
+                                    "bounds_per_member:i32 grad_scale:f32"),
+    "hipets_train_eval_loss": _sig("e d:TrainDesc* x y n_rows:i64 order score row_score stream loss_kind:i32"),
     "hipets_timing_enable": _sig("e on:i32"),
     "hipets_timing_read": _sig("e launches:i64* total_ms:f64* reset:i32"),
 }

@@ -118,17 +118,21 @@ def pack_planet_desc(spec, tensors):
     return d, list(tensors)
 
 
-def pack_train_desc(device, weights, biases, activation: str, leaky_slope: float, out_dim: int, max_batch: int, adam=None):
+def pack_train_desc(device, weights, biases, activation: str, leaky_slope: float, out_dim: int, max_batch: int, adam=None, *,
+                    loss: str = "nll", bounds_per_member: bool = False):
     """TrainDesc over the caller's DEVICE tensors (weights[l] [E, d_l, d_l+1], biases[l] [E, 1, d_l+1]); ``adam`` =
     (exp_avg_w, exp_avg_b, exp_avg_sq_w, exp_avg_sq_b, min_logvar, max_logvar, lr, beta1, beta2, eps, weight_decay,
-    steps_per_launch).  The returned keep-alive list holds the ctypes arrays the struct points to."""
+    steps_per_launch).  The returned keep-alive list holds the ctypes arrays the struct points to.  ``loss`` "mse": the last
+    layer is out_dim wide and the bounds may be None (NULL in the descriptor); ``bounds_per_member``: the bounds are [E, out_dim]."""
+    if loss not in _lib.TRAIN_LOSS:
+        raise ValueError(f"unknown loss {loss!r}")
     L = len(weights)
     if L < 2 or L != len(biases):
         raise ValueError("weights / biases: one tensor of each per linear layer, at least 2 layers")
     E, in_dim, hid = int(weights[0].shape[0]), int(weights[0].shape[1]), int(weights[0].shape[2])
     for li, (w, b) in enumerate(zip(weights, biases)):
         d_in = in_dim if li == 0 else hid
-        d_out = 2 * out_dim if li == L - 1 else hid
+        d_out = (out_dim if loss == "mse" else 2 * out_dim) if li == L - 1 else hid
         _check_dev(w, torch.float32, device, f"weights[{li}]", shape=(E, d_in, d_out))
         _check_dev(b, torch.float32, device, f"biases[{li}]", shape=(E, 1, d_out))
     if activation not in _lib.ACT:
@@ -146,11 +150,13 @@ def pack_train_desc(device, weights, biases, activation: str, leaky_slope: float
                 raise ValueError(f"{name}: one tensor per layer")
             for li, (t, r) in enumerate(zip(ts, ref)):
                 _check_dev(t, torch.float32, device, f"{name}[{li}]", shape=tuple(r.shape))
-        _check_dev(lo, torch.float32, device, "min_logvar", numel=out_dim)
-        _check_dev(hi, torch.float32, device, "max_logvar", numel=out_dim)
+        for name, t in (("min_logvar", lo), ("max_logvar", hi)):
+            if t is not None:  # (None = NULL: the library refuses it under NLL)
+                _check_dev(t, torch.float32, device, name, numel=E * out_dim if bounds_per_member else out_dim)
         keep += [arr(mw), arr(mb), arr(vw), arr(vb), lo, hi]
         d.exp_avg_w, d.exp_avg_b, d.exp_avg_sq_w, d.exp_avg_sq_b = (C.cast(k, C.POINTER(C.c_void_p)) for k in keep[2:6])
-        d.min_logvar, d.max_logvar = lo.data_ptr(), hi.data_ptr()
+        d.min_logvar = lo.data_ptr() if lo is not None else None
+        d.max_logvar = hi.data_ptr() if hi is not None else None
         d.lr, d.beta1, d.beta2, d.eps, d.weight_decay = float(lr), float(b1), float(b2), float(eps), float(wd)
         d.steps_per_launch = int(spl)
     return d, keep

@@ -589,12 +589,16 @@ class Engine:
     # ---- GaussianMLP ensemble training (hipets_train_steps / hipets_train_eval) ------------------------------------------
     def train_steps(self, weights, biases, exp_avg, exp_avg_sq, min_logvar, max_logvar, x: torch.Tensor, y: torch.Tensor,
                     idx: torch.Tensor, rows: torch.Tensor, step0: int, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
-                    weight_decay: float = 0.0, activation: str = "silu", leaky_slope: float = 0.01, steps_per_launch: int = 0):
+                    weight_decay: float = 0.0, activation: str = "silu", leaky_slope: float = 0.01, steps_per_launch: int = 0,
+                    loss: str = "nll", grad_scale: float = 1.0, bounds_per_member: bool = False):
         """``n_steps = idx.shape[0]`` minibatch steps of Model.update + torch.optim.Adam on every member, in place on the DEVICE
         tensors ``weights`` / ``biases`` and the Adam state ``exp_avg`` / ``exp_avg_sq`` (pairs of per-layer lists (w, b)).
         x [N, in] / y [N, out] f32 = the dataset's model inputs and targets; idx int32 [n_steps, E, max_batch] its rows per
         (step, member); rows int32 [n_steps] the rows of each step; step0 = Adam steps taken before.  Returns (loss, grad_sq)
-        DEVICE f32 [n_steps, E] (hipets.h: hipets_train_steps).  Asynchronous on the current stream."""
+        DEVICE f32 [n_steps, E] (hipets.h: hipets_train_steps).  Asynchronous on the current stream.
+        ``loss`` "mse": a deterministic model (last layer out wide, bounds None, loss = the member's sum of squared errors);
+        ``bounds_per_member``: min_logvar / max_logvar are [E, out]; ``grad_scale`` multiplies the loss gradient (1 / E for a
+        BasicEnsemble).  Any of them off its default goes through hipets_train_steps_loss."""
         dev = self.device
         out_dim = int(y.shape[-1]) if y.dim() == 2 else -1
         _check_dev(x, torch.float32, dev, "x")
@@ -610,18 +614,23 @@ class Engine:
         _check_dev(rows, torch.int32, dev, "rows", numel=n_steps)
         d, keep = pack_train_desc(dev, weights, biases, activation, leaky_slope, out_dim, max_batch,
                                   adam=(exp_avg[0], exp_avg[1], exp_avg_sq[0], exp_avg_sq[1], min_logvar, max_logvar, lr, betas[0], betas[1],
-                                        eps, weight_decay, steps_per_launch))
-        loss = torch.empty(n_steps, E, dtype=torch.float32, device=dev)
+                                        eps, weight_decay, steps_per_launch), loss=loss, bounds_per_member=bounds_per_member)
+        losses = torch.empty(n_steps, E, dtype=torch.float32, device=dev)
         gsq = torch.empty(n_steps, E, dtype=torch.float32, device=dev)
-        self._call("hipets_train_steps", d=d, x=x, y=y, n_rows=int(x.shape[0]), idx=idx, rows=rows, n_steps=n_steps, step0=int(step0), loss=loss,
-                   grad_sq=gsq)
+        kw = dict(d=d, x=x, y=y, n_rows=int(x.shape[0]), idx=idx, rows=rows, n_steps=n_steps, step0=int(step0), loss=losses, grad_sq=gsq)
+        if loss == "nll" and not bounds_per_member and float(grad_scale) == 1.0:
+            self._call("hipets_train_steps", **kw)
+        else:
+            self._call("hipets_train_steps_loss", loss_kind=_lib.TRAIN_LOSS[loss], bounds_per_member=int(bool(bounds_per_member)),
+                       grad_scale=float(grad_scale), **kw)
         del keep
-        return loss, gsq
+        return losses, gsq
 
     def train_eval(self, weights, biases, x: torch.Tensor, y: torch.Tensor, order: Optional[torch.Tensor] = None, *,
-                   activation: str = "silu", leaky_slope: float = 0.01, row_scores: bool = False):
+                   activation: str = "silu", leaky_slope: float = 0.01, row_scores: bool = False, loss: str = "nll"):
         """GaussianMLP.eval_score averaged over rows and dims, per member: DEVICE f32 [E] (and, with ``row_scores``, the
-        [E, N] per-row squared-error sums in pass order).  Asynchronous on the current stream."""
+        [E, N] per-row squared-error sums in pass order).  Asynchronous on the current stream.  ``loss`` "mse": the last layer is
+        out wide (a deterministic model), through hipets_train_eval_loss."""
         dev = self.device
         _check_dev(x, torch.float32, dev, "x")
         _check_dev(y, torch.float32, dev, "y")
@@ -630,11 +639,14 @@ class Engine:
         N = int(x.shape[0])
         if order is not None:
             _check_dev(order, torch.int32, dev, "order", numel=N)
-        d, keep = pack_train_desc(dev, weights, biases, activation, leaky_slope, int(y.shape[1]), 1)
+        d, keep = pack_train_desc(dev, weights, biases, activation, leaky_slope, int(y.shape[1]), 1, loss=loss)
         E = int(weights[0].shape[0])
         score = torch.empty(E, dtype=torch.float32, device=dev)
         rs = torch.empty(E, N, dtype=torch.float32, device=dev) if row_scores else None
-        self._call("hipets_train_eval", d=d, x=x, y=y, n_rows=N, order=order, score=score, row_score=rs)
+        if loss == "nll":
+            self._call("hipets_train_eval", d=d, x=x, y=y, n_rows=N, order=order, score=score, row_score=rs)
+        else:
+            self._call("hipets_train_eval_loss", d=d, x=x, y=y, n_rows=N, order=order, score=score, row_score=rs, loss_kind=_lib.TRAIN_LOSS[loss])
         del keep
         return (score, rs) if row_scores else score
 

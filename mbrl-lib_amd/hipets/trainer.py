@@ -6,10 +6,17 @@ evaluation passes run in libhipets (hipets_train_steps / hipets_train_eval):
 Supported: a ``OneDTransitionRewardModel`` over one ``GaussianMLP`` (NLL loss, fixed logvar bounds).  Anything else raises
 ``UnsupportedModelError`` at construction: keep ``mbrl.models.ModelTrainer`` for it.  Torch is used for data preparation
 and copies only; the update (forward, backward, Adam) never touches torch.autograd or torch.optim.
+
+With ``extended=True`` (what ``hipets.make_model_trainer`` passes) two further kinds train in HIP: a ``GaussianMLP`` with
+``deterministic=True`` (MSE loss) and a ``BasicEnsemble`` of one-member ``GaussianMLP``s of one shape (all NLL with fixed bounds, or
+all deterministic).  ``learn_logvar_bounds=True``, mixed member kinds and members that are ensembles stay refused.
+
+    model_trainer = hipets.make_model_trainer(dynamics_model, optim_lr=..., weight_decay=..., logger=...)
 """
 from __future__ import annotations
 
 import itertools
+import warnings
 from typing import Callable, Dict, List, Optional, Tuple
 
 import numpy as np
@@ -32,18 +39,67 @@ MAX_MEMBERS, MAX_HID, MAX_IN, MAX_OUT, MAX_BATCH = 16, 256, 512, 512, 256
 _KEEP_STOCK = "; keep mbrl.models.ModelTrainer for this model"
 
 
-def _read_model(model):
-    """(GaussianMLP, [(weight, bias) live parameters per linear layer], activation, slope) or UnsupportedModelError."""
+class _Kind:
+    """What _read_model found: ``mlps`` = the GaussianMLPs that own the parameters (one vectorised model, or the E one-member
+    members of a BasicEnsemble, ``basic``); ``layers[li]`` = the (weight, bias, member) live parameters that make up row ``member``
+    of the stacked device tensor of linear layer li (member None: the whole [E, ., .] tensor); ``loss`` "nll" / "mse"."""
+
+    def __init__(self, mlps, basic, layers, act, slope, loss):
+        self.mlps, self.basic, self.layers, self.act, self.slope, self.loss = mlps, basic, layers, act, slope, loss
+
+
+def _read_model(model, extended: bool = False) -> _Kind:
+    """The model's kind and live parameters, or UnsupportedModelError.  ``extended``: deterministic GaussianMLPs (MSE loss) and
+    BasicEnsembles of one-member GaussianMLPs are accepted as well."""
     mlp = getattr(model, "model", None)
     if mlp is None or not hasattr(model, "_process_batch"):
         raise UnsupportedModelError("hipets.ModelTrainer trains a OneDTransitionRewardModel" + _KEEP_STOCK)
     if hasattr(mlp, "members") and not hasattr(mlp, "hidden_layers"):
-        raise UnsupportedModelError("BasicEnsemble is not supported" + _KEEP_STOCK)
+        if not extended:
+            raise UnsupportedModelError("BasicEnsemble is not supported" + _KEEP_STOCK)
+        return _read_basic_ensemble(mlp)
+    layers, act, slope, loss = _read_mlp(mlp, extended)
+    return _Kind([mlp], False, [[(lin.weight, lin.bias, None)] for lin in layers], act, slope, loss)
+
+
+def _read_basic_ensemble(ens) -> _Kind:
+    """A BasicEnsemble (mbrl/models/basic_ensemble.py) whose members are one-member GaussianMLPs of one shape, activation and loss."""
+    members = list(ens.members)
+    if not members:
+        raise UnsupportedModelError("BasicEnsemble without members" + _KEEP_STOCK)
+    if len(members) > MAX_MEMBERS:
+        raise UnsupportedModelError(f"BasicEnsemble of {len(members)} members exceeds the trained shapes (E <= {MAX_MEMBERS})" + _KEEP_STOCK)
+    read = []
+    for i, m in enumerate(members):
+        if hasattr(m, "members"):
+            raise UnsupportedModelError(f"BasicEnsemble member {i} is an ensemble itself" + _KEEP_STOCK)
+        try:
+            read.append(_read_mlp(m, True))
+        except UnsupportedModelError as exc:
+            raise UnsupportedModelError(f"BasicEnsemble member {i}: {exc}") from None
+        if int(read[-1][0][0].weight.shape[0]) != 1 or int(getattr(m, "num_members", 1)) != 1:
+            raise UnsupportedModelError(f"BasicEnsemble member {i} is an ensemble itself (num_members != 1)" + _KEEP_STOCK)
+    layers0, act, slope, loss = read[0]
+    shapes0 = [tuple(lin.weight.shape) for lin in layers0]
+    for i, (layers, a, s, l) in enumerate(read[1:], 1):
+        if l != loss:
+            raise UnsupportedModelError(f"BasicEnsemble mixes member kinds (member 0 trains with {loss}, member {i} with {l})" + _KEEP_STOCK)
+        if [tuple(lin.weight.shape) for lin in layers] != shapes0:
+            raise UnsupportedModelError(f"BasicEnsemble member {i} has other layer shapes than member 0" + _KEEP_STOCK)
+        if a != act or s != slope:
+            raise UnsupportedModelError(f"BasicEnsemble member {i} has another activation than member 0" + _KEEP_STOCK)
+    stacked = [[(layers[li].weight, layers[li].bias, e) for e, (layers, _, _, _) in enumerate(read)] for li in range(len(layers0))]
+    return _Kind(members, True, stacked, act, slope, loss)
+
+
+def _read_mlp(mlp, extended: bool):
+    """([linear layers], activation, slope, loss kind) of one GaussianMLP or UnsupportedModelError."""
     if not hasattr(mlp, "hidden_layers") or not hasattr(mlp, "mean_and_logvar"):
         raise UnsupportedModelError("dynamics_model.model is not a GaussianMLP" + _KEEP_STOCK)
-    if bool(getattr(mlp, "deterministic", False)):
+    deterministic = bool(getattr(mlp, "deterministic", False))
+    if deterministic and not extended:
         raise UnsupportedModelError("deterministic GaussianMLP (MSE loss) is not supported" + _KEEP_STOCK)
-    if mlp.min_logvar.requires_grad or mlp.max_logvar.requires_grad:
+    if not deterministic and (mlp.min_logvar.requires_grad or mlp.max_logvar.requires_grad):
         raise UnsupportedModelError("learn_logvar_bounds=True is not supported (its gradient couples the members)" + _KEEP_STOCK)
     layers, act, slope = [], None, 0.01
     for layer in mlp.hidden_layers:
@@ -62,10 +118,11 @@ def _read_model(model):
         raise UnsupportedModelError("expected 1..7 hidden ensemble layers of weights [E, in, out]" + _KEEP_STOCK)
     E, in_dim, hid = (int(v) for v in w0.shape)
     out2 = int(layers[-1].weight.shape[2])
-    if E > MAX_MEMBERS or hid > MAX_HID or in_dim > MAX_IN or out2 > 2 * MAX_OUT:
+    max_cols = MAX_OUT if deterministic else 2 * MAX_OUT
+    if E > MAX_MEMBERS or hid > MAX_HID or in_dim > MAX_IN or out2 > max_cols:
         raise UnsupportedModelError(f"ensemble {E} x in {in_dim} x hid {hid} x out {out2} exceeds the trained shapes (E <= {MAX_MEMBERS}, "
-                                    f"in <= {MAX_IN}, hid <= {MAX_HID}, out <= {2 * MAX_OUT} columns)" + _KEEP_STOCK)
-    return mlp, [(lin.weight, lin.bias) for lin in layers], act or "relu", slope
+                                    f"in <= {MAX_IN}, hid <= {MAX_HID}, out <= {max_cols} columns)" + _KEEP_STOCK)
+    return layers, act or "relu", slope, "mse" if deterministic else "nll"
 
 
 def _iterator_kind(ds) -> Optional[str]:
@@ -97,10 +154,9 @@ class _AdamState:
         state = {}
         if t._step > 0:
             pos = {id(p): i for i, p in enumerate(params)}
-            for li, (w, b) in enumerate(t._live):
-                for k, p in enumerate((w, b)):
-                    state[pos[id(p)]] = {"step": torch.tensor(float(t._step)), "exp_avg": t._m[k][li].detach().to(p.device).clone(),
-                                         "exp_avg_sq": t._v[k][li].detach().to(p.device).clone()}
+            for li, e, k, p in t._slots():
+                state[pos[id(p)]] = {"step": torch.tensor(float(t._step)), "exp_avg": t._rows(t._m[k][li], e).detach().to(p.device).clone(),
+                                     "exp_avg_sq": t._rows(t._v[k][li], e).detach().to(p.device).clone()}
         group = {k: v for k, v in self.param_groups[0].items() if k != "params"}
         group["params"] = list(range(len(params)))
         return {"state": dict(sorted(state.items())), "param_groups": [group]}
@@ -116,17 +172,16 @@ class _AdamState:
                 self.param_groups[0][k] = v
         pos = {id(p): i for i, p in enumerate(params)}
         steps = set()
-        for li, (w, b) in enumerate(t._live):
-            for k, p in enumerate((w, b)):
-                st = sd["state"].get(groups[0]["params"][pos[id(p)]])
-                if st is None:
-                    t._m[k][li].zero_()
-                    t._v[k][li].zero_()
-                    steps.add(0)
-                    continue
-                t._m[k][li].copy_(st["exp_avg"])
-                t._v[k][li].copy_(st["exp_avg_sq"])
-                steps.add(int(float(st["step"])))
+        for li, e, k, p in t._slots():
+            st = sd["state"].get(groups[0]["params"][pos[id(p)]])
+            if st is None:
+                t._rows(t._m[k][li], e).zero_()
+                t._rows(t._v[k][li], e).zero_()
+                steps.add(0)
+                continue
+            t._rows(t._m[k][li], e).copy_(st["exp_avg"])
+            t._rows(t._v[k][li], e).copy_(st["exp_avg_sq"])
+            steps.add(int(float(st["step"])))
         if len(steps) != 1:
             raise ValueError("hipets.ModelTrainer keeps one Adam step count for all parameters")
         t._step = steps.pop()
@@ -142,11 +197,12 @@ class ModelTrainer:
     _LOG_GROUP_NAME = "model_train"
 
     def __init__(self, model, optim_lr: float = 1e-4, weight_decay: float = 1e-5, optim_eps: float = 1e-8, logger=None, *,
-                 engine=None, device=None, steps_per_launch: int = 0):
+                 engine=None, device=None, steps_per_launch: int = 0, extended: bool = False):
         from .engine import get_engine
 
         self.model = model
-        self._mlp, self._live, self._act, self._slope = _read_model(model)
+        self._kind = _read_model(model, extended)
+        self._act, self._slope = self._kind.act, self._kind.slope
         self._train_iteration = 0
         self.logger = logger
         if self.logger:
@@ -154,9 +210,21 @@ class ModelTrainer:
         self.engine = engine if engine is not None else get_engine(device if device is not None else f"cuda:{torch.cuda.current_device()}")
         self.steps_per_launch = int(steps_per_launch)
         dev = self.engine.device
-        self._out = int(self._live[-1][0].shape[2]) // 2
-        self._w = [[w.detach().to(dev, torch.float32).contiguous().clone() for w, _ in self._live],
-                   [b.detach().to(dev, torch.float32).contiguous().clone() for _, b in self._live]]
+        layers = self._kind.layers
+        self._param_device = layers[0][0][0].device
+        mse = self._kind.loss == "mse"
+        self._out = int(layers[-1][0][0].shape[2]) // (1 if mse else 2)
+        E = len(self._kind.mlps) if self._kind.basic else int(layers[0][0][0].shape[0])
+        # what the engine is told beyond today's arguments (nothing for one NLL GaussianMLP): the loss kind, per-member bounds and
+        # the 1 / E of BasicEnsemble.loss, computed in float32 as torch's backward of `loss / E` computes it
+        self._engine_kw = {"loss": "mse"} if mse else {}
+        if self._kind.basic and not mse:
+            self._engine_kw["bounds_per_member"] = True
+        if self._kind.basic and E > 1:
+            self._engine_kw["grad_scale"] = float(np.float32(1.0) / np.float32(E))
+        # the device copies: a BasicEnsemble's [1, in, out] member tensors stacked into [E, in, out]
+        self._w = [[torch.cat([slot[k].detach().to(dev, torch.float32) for slot in slots]).contiguous().clone() for slots in layers]
+                   for k in (0, 1)]
         self._m = [[torch.zeros_like(t) for t in ts] for ts in self._w]
         self._v = [[torch.zeros_like(t) for t in ts] for ts in self._w]
         self._step = 0
@@ -164,23 +232,55 @@ class ModelTrainer:
         self._data: Dict[int, Tuple] = {}
 
     # ---- device copies of the parameters ------------------------------------------------------------------------------
+    def _slots(self):
+        """(layer, member or None, 0 weight / 1 bias, live parameter) of every trained parameter"""
+        for li, slots in enumerate(self._kind.layers):
+            for w, b, e in slots:
+                yield li, e, 0, w
+                yield li, e, 1, b
+
+    @staticmethod
+    def _rows(stacked, e):
+        """the part of a stacked device tensor one live parameter owns: all of it, or member e's [1, ., .]"""
+        return stacked if e is None else stacked[e:e + 1]
+
     def _pull(self):
         with torch.no_grad():
-            for li, (w, b) in enumerate(self._live):
-                self._w[0][li].copy_(w.detach())
-                self._w[1][li].copy_(b.detach())
+            for li, e, k, p in self._slots():
+                self._rows(self._w[k][li], e).copy_(p.detach())
 
     def _push(self):
         with torch.no_grad():
-            for li, (w, b) in enumerate(self._live):
-                w.copy_(self._w[0][li])
-                b.copy_(self._w[1][li])
+            for li, e, k, p in self._slots():
+                p.copy_(self._rows(self._w[k][li], e))
 
     def _bounds(self):
+        """DEVICE (min_logvar, max_logvar): [out] of one GaussianMLP, [E, out] of a BasicEnsemble's members, (None, None) under MSE"""
+        if self._kind.loss == "mse":
+            return None, None
         dev = self.engine.device
-        lo = self._mlp.min_logvar.detach().reshape(-1).to(dev, torch.float32).contiguous()
-        hi = self._mlp.max_logvar.detach().reshape(-1).to(dev, torch.float32).contiguous()
-        return lo, hi
+        lo = torch.cat([m.min_logvar.detach().reshape(1, -1) for m in self._kind.mlps]).to(dev, torch.float32)
+        hi = torch.cat([m.max_logvar.detach().reshape(1, -1) for m in self._kind.mlps]).to(dev, torch.float32)
+        if not self._kind.basic:
+            lo, hi = lo.reshape(-1), hi.reshape(-1)
+        return lo.contiguous(), hi.contiguous()
+
+    def _batch_losses(self, loss_h):
+        """The reference's loss of every batch from the per-member losses [S, E] of the device (float32, summed in its order):
+        GaussianMLP: sum_e nll_e + 0.01 (sum max_logvar - sum min_logvar) (gaussian_mlp.py:299-304), or sum_e sse_e (:289);
+        BasicEnsemble: (sum_e member loss_e) / E with every NLL member's own bound term (basic_ensemble.py:214-221)."""
+        mse = self._kind.loss == "mse"
+        terms = [np.float32(0.0) if mse else np.float32((0.01 * (m.max_logvar.detach().float().cpu().sum() - m.min_logvar.detach().float().cpu().sum())).item())
+                 for m in self._kind.mlps]
+        if not self._kind.basic:
+            return [float(np.float32(r.sum(dtype=np.float32)) + terms[0]) for r in loss_h]
+        out = []
+        for r in loss_h:
+            acc = np.float32(0.0)
+            for e, t in enumerate(terms):
+                acc = np.float32(acc + (r[e] if mse else np.float32(r[e] + t)))
+            out.append(float(acc / np.float32(len(terms))))
+        return out
 
     def _processed(self, ds):
         """(x [N, in], y [N, out]) on the engine's GPU: the model's own _process_batch over the whole dataset, once per train()."""
@@ -224,7 +324,7 @@ class ModelTrainer:
             self._w[0], self._w[1], (self._m[0], self._m[1]), (self._v[0], self._v[1]), lo, hi, x, y,
             torch.from_numpy(np.ascontiguousarray(idx)).to(dev), torch.from_numpy(np.ascontiguousarray(rows)).to(dev), self._step,
             lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], activation=self._act, leaky_slope=self._slope,
-            steps_per_launch=self.steps_per_launch)
+            steps_per_launch=self.steps_per_launch, **self._engine_kw)
         self._step += int(idx.shape[0])
         return loss, gsq
 
@@ -277,15 +377,13 @@ class ModelTrainer:
         epoch_iter = range(num_epochs) if num_epochs else itertools.count()
         epochs_since_update = 0
         best_val_score = self._evaluate(eval_dataset) if evaluate else None
-        lo, hi = self._mlp.min_logvar.detach().float().cpu(), self._mlp.max_logvar.detach().float().cpu()
-        bound_term = np.float32((0.01 * (hi.sum() - lo.sum())).item())  # gaussian_mlp.py:304, a constant here
         for epoch in epoch_iter:
             loss, gsq = self._epoch(dataset_train)
             if loss is None:
                 batch_losses, grad_norms = [], []
             else:
                 loss_h, gsq_h = loss.cpu().numpy(), gsq.cpu().numpy()  # the epoch's one synchronisation
-                batch_losses = [float(np.float32(r.sum(dtype=np.float32)) + bound_term) for r in loss_h]
+                batch_losses = self._batch_losses(loss_h)
                 grad_norms = [float(r.astype(np.float64).sum()) for r in gsq_h]
             if batch_callback:
                 for bl, gn in zip(batch_losses, grad_norms):
@@ -366,7 +464,7 @@ class ModelTrainer:
             y = torch.cat(ys).to(dev, torch.float32).contiguous()
             order = None
         res = self.engine.train_eval(self._w[0], self._w[1], x, y, order, activation=self._act, leaky_slope=self._slope,
-                                     row_scores=batch_callback is not None)
+                                     row_scores=batch_callback is not None, **({"loss": "mse"} if self._kind.loss == "mse" else {}))
         score, rs = res if batch_callback is not None else (res, None)
         if batch_callback is not None:
             rs_h = rs.cpu().numpy()
@@ -376,7 +474,7 @@ class ModelTrainer:
                 start += n
         if kind == "bootstrap":
             dataset.toggle_bootstrap()
-        return score.to(self._live[0][0].device)
+        return score.to(self._param_device)
 
     def maybe_get_best_weights(self, best_val_score: torch.Tensor, val_score: torch.Tensor, threshold: float = 0.01) -> Optional[Dict]:
         """As the reference (model_trainer.py:264-286), with the snapshot a device copy of the trained parameters."""
@@ -386,10 +484,26 @@ class ModelTrainer:
 
     def _maybe_set_best_weights_and_elite(self, best_weights: Optional[Dict], best_val_score: torch.Tensor):
         if best_weights is not None:
-            for li in range(len(self._live)):
+            for li in range(len(self._kind.layers)):
                 self._w[0][li].copy_(best_weights["weights"][li])
                 self._w[1][li].copy_(best_weights["biases"][li])
         if len(best_val_score) > 1 and hasattr(self.model, "num_elites"):
             sorted_indices = np.argsort(best_val_score.tolist())
             elite_models = sorted_indices[: self.model.num_elites]
             self.model.set_elite(elite_models)
+
+
+def make_model_trainer(model, optim_lr: float = 1e-4, weight_decay: float = 1e-5, optim_eps: float = 1e-8, logger=None, **kw):
+    """The trainer's analogue of ``make_eval_fn``: ``hipets.ModelTrainer(model, ..., extended=True, **kw)`` where the model trains
+    in HIP (one GaussianMLP, NLL or deterministic; a BasicEnsemble of one-member GaussianMLPs); for any other model
+    ``mbrl.models.ModelTrainer(model, ...)`` with one warning that names the reason, or, where mbrl cannot be imported, the
+    UnsupportedModelError itself."""
+    try:
+        return ModelTrainer(model, optim_lr=optim_lr, weight_decay=weight_decay, optim_eps=optim_eps, logger=logger, extended=True, **kw)
+    except UnsupportedModelError as exc:
+        try:
+            import mbrl.models as stock
+        except ImportError:
+            raise exc from None
+        warnings.warn(f"hipets.make_model_trainer: training with mbrl.models.ModelTrainer ({str(exc).replace(_KEEP_STOCK, '')})", stacklevel=2)
+        return stock.ModelTrainer(model, optim_lr=optim_lr, weight_decay=weight_decay, optim_eps=optim_eps, logger=logger)

@@ -1,0 +1,327 @@
+"""hipets.ModelTrainer(..., extended=True) and hipets.make_model_trainer without a GPU: the kinds that stay refused by default, the
+factory's two fall-back branches, the trainer's host logic (batches consumed, RNG, loss and grad_norm composition, optimizer
+state_dict, elites) for a BasicEnsemble (NLL / deterministic) and a deterministic GaussianMLP against the reference ModelTrainer's
+recordings (tests/golden/trainerx_*.npz, tests/make_trainer_loss_golden.py) with the device steps on a CPU stand-in of the engine,
+the additive C ABI, and the restatements (tests/train_loss_restatement.py) against the reference's own Model.update in float64."""
+import json
+import os
+import re
+import sys
+import types
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+import hipets
+import train_loss_restatement as tlr
+import train_restatement as tr
+from conftest import GOLDEN
+from hipets import _lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+KINDS = ("trainerx_basic_nll", "trainerx_gmlp_mse", "trainerx_basic_mse")
+
+
+def _golden(name):
+    z = np.load(os.path.join(GOLDEN, name + ".npz"))
+    return json.loads(bytes(z["meta_json"]).decode()), {k: z[k] for k in z.files if k != "meta_json"}
+
+
+def _models():
+    """name -> a fresh dynamics model of each new kind (E 3, in 5, hid 8, out 4, 3 linear layers)"""
+    return {"basic_nll": tr.TinyDynamicsModel(tlr.TinyBasicEnsemble(3, 5, 8, 4, 3)),
+            "gmlp_mse": tr.TinyDynamicsModel(tr.TinyGaussianMLP(3, 5, 8, 4, 3, deterministic=True)),
+            "basic_mse": tr.TinyDynamicsModel(tlr.TinyBasicEnsemble(3, 5, 8, 4, 3, deterministic=True))}
+
+
+# ---- what is accepted, and by whom -------------------------------------------------------------------------------------------
+def test_new_kinds_are_refused_by_default_and_construct_when_extended():
+    for name, model in _models().items():
+        with pytest.raises(hipets.UnsupportedModelError, match="keep mbrl.models.ModelTrainer"):
+            hipets.ModelTrainer(model, engine=tlr.CpuEngineKinds())
+        trainer = hipets.ModelTrainer(model, engine=tlr.CpuEngineKinds(), extended=True)
+        assert trainer._out == 4 and [tuple(t.shape) for t in trainer._w[0]] == [(3, 5, 8), (3, 8, 8), (3, 8, 4 if "mse" in name else 8)], name
+    with pytest.raises(TypeError):
+        hipets.ModelTrainer(_models()["gmlp_mse"], 1e-3, 1e-5, 1e-8, None, True)  # extended is keyword-only
+
+
+def test_still_refused_when_extended_with_the_reason():
+    E = tlr.CpuEngineKinds
+    cases = {
+        "learn_logvar_bounds": tr.TinyGaussianMLP(3, 5, 8, 4, 3, learn_logvar_bounds=True),
+        "member 1: learn_logvar_bounds": tlr.TinyBasicEnsemble(3, 5, 8, 4, 3, learn_logvar_bounds=True),
+    }
+    cases["member 1: learn_logvar_bounds"].members[0].min_logvar.requires_grad_(False)
+    cases["member 1: learn_logvar_bounds"].members[0].max_logvar.requires_grad_(False)
+    mixed = tlr.TinyBasicEnsemble(3, 5, 8, 4, 3)
+    mixed.members[2] = tr.TinyGaussianMLP(1, 5, 8, 4, 3, deterministic=True)
+    cases["mixes member kinds"] = mixed
+    nested = tlr.TinyBasicEnsemble(3, 5, 8, 4, 3)
+    nested.members[1] = tr.TinyGaussianMLP(2, 5, 8, 4, 3)
+    cases["member 1 is an ensemble itself"] = nested
+    nested2 = tlr.TinyBasicEnsemble(2, 5, 8, 4, 3)
+    nested2.members[0] = tlr.TinyBasicEnsemble(2, 5, 8, 4, 3)
+    cases["member 0 is an ensemble itself"] = nested2
+    shapes = tlr.TinyBasicEnsemble(3, 5, 8, 4, 3)
+    shapes.members[1] = tr.TinyGaussianMLP(1, 5, 9, 4, 3)
+    cases["member 1 has other layer shapes"] = shapes
+    acts = tlr.TinyBasicEnsemble(3, 5, 8, 4, 3)
+    acts.members[2] = tr.TinyGaussianMLP(1, 5, 8, 4, 3, act="tanh")
+    cases["member 2 has another activation"] = acts
+    for reason, mlp in cases.items():
+        with pytest.raises(hipets.UnsupportedModelError, match=reason) as ei:
+            hipets.ModelTrainer(tr.TinyDynamicsModel(mlp, num_elites=2), engine=E(), extended=True)
+        assert "keep mbrl.models.ModelTrainer" in str(ei.value), reason
+
+
+def test_factory_returns_the_hip_trainer_for_every_trainable_kind():
+    models = dict(_models(), gmlp_nll=tr.TinyDynamicsModel(tr.TinyGaussianMLP(3, 5, 8, 4, 3)))
+    for name, model in models.items():
+        with warnings.catch_warnings():
+            warnings.simplefilter("error")
+            trainer = hipets.make_model_trainer(model, optim_lr=3e-4, weight_decay=2e-5, optim_eps=1e-7, engine=tlr.CpuEngineKinds())
+        assert type(trainer) is hipets.ModelTrainer, name
+        g = trainer.optimizer.param_groups[0]
+        assert (g["lr"], g["weight_decay"], g["eps"]) == (3e-4, 2e-5, 1e-7)
+
+
+def test_factory_falls_back_to_the_stock_trainer_with_one_warning(monkeypatch):
+    made = []
+
+    class StockTrainer:
+        def __init__(self, model, optim_lr=1e-4, weight_decay=1e-5, optim_eps=1e-8, logger=None):
+            made.append((model, optim_lr, weight_decay, optim_eps, logger))
+
+    pkg, models = types.ModuleType("mbrl"), types.ModuleType("mbrl.models")
+    models.ModelTrainer = StockTrainer
+    pkg.models = models
+    monkeypatch.setitem(sys.modules, "mbrl", pkg)
+    monkeypatch.setitem(sys.modules, "mbrl.models", models)
+    model = tr.TinyDynamicsModel(tr.TinyGaussianMLP(3, 5, 8, 4, 3, learn_logvar_bounds=True))
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        trainer = hipets.make_model_trainer(model, optim_lr=3e-4, weight_decay=2e-5, optim_eps=1e-7, logger="L", engine=tlr.CpuEngineKinds())
+    assert type(trainer) is StockTrainer and made == [(model, 3e-4, 2e-5, 1e-7, "L")]
+    assert len(caught) == 1 and "learn_logvar_bounds=True" in str(caught[0].message)
+
+
+def test_factory_reraises_where_the_stock_trainer_cannot_be_imported(monkeypatch):
+    monkeypatch.setitem(sys.modules, "mbrl", None)  # `import mbrl.models` raises ImportError
+    monkeypatch.setitem(sys.modules, "mbrl.models", None)
+    model = tr.TinyDynamicsModel(tr.TinyGaussianMLP(3, 5, 8, 4, 3, learn_logvar_bounds=True))
+    with pytest.raises(hipets.UnsupportedModelError, match="learn_logvar_bounds=True"):
+        hipets.make_model_trainer(model, engine=tlr.CpuEngineKinds())
+
+
+def test_todays_kind_calls_the_engine_with_todays_arguments_only():
+    """The stand-in engine of tests/test_trainer_host.py knows today's keywords only: extended or not, a GaussianMLP with the NLL
+    loss must not be handed a new one."""
+    from test_trainer_host import CpuEngine
+
+    rng = np.random.default_rng(3)
+    obs = rng.standard_normal((60, 6)).astype(np.float32)
+    data = tr.Batch(obs=obs, act=rng.uniform(-1, 1, (60, 2)).astype(np.float32), next_obs=obs * 1.1)
+    for extended in (False, True):
+        trainer = hipets.ModelTrainer(tr.TinyDynamicsModel(tr.TinyGaussianMLP(5, 8, 16, 6, 3)), engine=CpuEngine(), extended=extended)
+        losses, scores = trainer.train(tr.BootstrapIterator(data, 16, 5, shuffle_each_epoch=True, rng=rng), num_epochs=1)
+        assert len(losses) == len(scores) == 1
+
+
+# ---- host logic of a whole train() against the reference trainer's recordings -----------------------------------------------
+@pytest.fixture(scope="module", params=KINDS)
+def trained(request):
+    """One train() per golden with the device steps on the CPU stand-in, shared by the tests below (which only read it)."""
+    meta, arr = _golden(request.param)
+    mlp, model, train, val, rng = tlr.golden_setup(meta, arr)
+    engine = tlr.CpuEngineKinds()
+    trainer = hipets.ModelTrainer(model, optim_lr=meta["lr"], weight_decay=meta["weight_decay"], engine=engine, extended=True)
+    batches = []
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        losses, scores = trainer.train(train, val, num_epochs=meta["num_epochs"], patience=meta["patience"],
+                                       batch_callback=lambda ep, l, m, mode: batches.append((ep, float(l), m.get("grad_norm"), mode)))
+    return dict(meta=meta, arr=arr, mlp=mlp, model=model, rng=rng, engine=engine, trainer=trainer, losses=losses, scores=scores,
+                batches=[b for b in batches if b[3] == "train"], warnings=[str(w.message) for w in caught])
+
+
+def test_batches_consumed_and_rng_match_reference_trainer(trained):
+    """Every step's rows are the reference's: epoch k's order is the k-th permutation drawn from the RNG where the reference's stood
+    after the split, member e's rows are its bootstrap indices of that order; the RNG ends bit for bit where the reference's did."""
+    meta, arr = trained["meta"], trained["arr"]
+    rng = np.random.default_rng()
+    rng.bit_generator.state = json.loads(meta["rng_state_after_split"])
+    n, B = len(arr["train_rows"]), meta["batch_size"]
+    steps = [c for c in trained["engine"].calls if c["fn"] == "train_steps"]
+    assert len(steps) == meta["epochs_run"]
+    self_eval = len(arr["val_rows"]) == 0  # no validation set: every evaluation pass iterates (and reshuffles) the training iterator
+    if self_eval:
+        rng.permutation(n)  # the evaluation before the first epoch
+    for k, call in enumerate(steps):
+        if self_eval and k > 0:
+            rng.permutation(n)  # the evaluation after the epoch before
+        order = rng.permutation(n)
+        nb = (n - 1) // B + 1
+        assert call["idx"].shape == (nb, meta["E"], B) and call["rows"].tolist() == [min(B, n - i * B) for i in range(nb)]
+        for i in range(nb):
+            sel = order[i * B:(i + 1) * B]
+            assert np.array_equal(call["idx"][i, :, :len(sel)].numpy(), arr["member_indices"][:, sel])
+    assert json.dumps(trained["rng"].bit_generator.state, sort_keys=True) == json.dumps(json.loads(meta["rng_state_after"]), sort_keys=True)
+    assert len(trained["losses"]) == meta["epochs_run"] and trained["trainer"]._train_iteration == 1
+
+
+def test_engine_is_told_the_kind(trained):
+    meta = trained["meta"]
+    for call in trained["engine"].calls:
+        assert call["loss"] == ("mse" if meta["deterministic"] else "nll")
+        if call["fn"] == "train_steps":
+            assert call["bounds_per_member"] == (meta["basic"] and not meta["deterministic"])
+            assert call["grad_scale"] == (float(np.float32(1.0) / np.float32(meta["E"])) if meta["basic"] else 1.0)
+            if not meta["deterministic"]:
+                assert np.array_equal(call["lo"].numpy(), trained["arr"]["min_logvar"]) and np.array_equal(call["hi"].numpy(), trained["arr"]["max_logvar"])
+
+
+def test_loss_and_grad_norm_composition(trained):
+    """The reported batch loss and grad_norm are the reference's compositions of the per-member results the engine returned,
+    (sum_e (loss_e + bound term_e)) [/ E for a BasicEnsemble] and sum_e grad_sq_e, evaluated in float64 (the loss sum to its float32
+    rounding bound; the grad_norm sum is taken in float64: exact), and they are the reference's figures to float32 noise."""
+    meta, arr = trained["meta"], trained["arr"]
+    E = meta["E"]
+    steps = [c for c in trained["engine"].calls if c["fn"] == "train_steps"]
+    member_loss = torch.cat([c["loss_out"] for c in steps]).double().numpy()
+    gsq = torch.cat([c["gsq_out"] for c in steps]).double().numpy()
+    terms = np.zeros(E)
+    if not meta["deterministic"]:
+        terms = 0.01 * (arr["max_logvar"].astype(np.float64).sum(1) - arr["min_logvar"].astype(np.float64).sum(1))
+    expect = (member_loss + terms[None, :]).sum(1) / (E if meta["basic"] else 1)
+    got = np.array([b[1] for b in trained["batches"]])
+    assert got.shape == expect.shape == arr["batch_losses"].shape
+    # the trainer composes in float32, as torch does: 2 E + 1 roundings (E bound-term additions, E accumulations, one division), each
+    # at most 2^-24 of a partial sum no larger than S = sum_e (|loss_e| + |term_e|): the NLL members' losses and bound terms cancel
+    partial = (np.abs(member_loss) + np.abs(terms)[None, :]).sum(1).max()
+    assert np.abs(got - expect).max() <= (2 * E + 1) * 2.0 ** -24 * partial
+    assert np.allclose([b[2] for b in trained["batches"]], gsq.sum(1), rtol=1e-12, atol=0)
+    assert np.allclose(got, arr["batch_losses"], rtol=1e-4, atol=1e-6)
+    assert np.allclose([b[2] for b in trained["batches"]], arr["batch_grad_norms"], rtol=1e-3, atol=1e-9)
+    assert np.allclose(trained["losses"], arr["train_losses"], rtol=1e-5) and np.allclose(trained["scores"], arr["val_scores"], rtol=1e-5)
+
+
+def test_final_weights_land_in_the_live_member_parameters(trained):
+    meta, arr = trained["meta"], trained["arr"]
+    ws, bs = tlr.stacked_params(trained["mlp"])
+    for i in range(meta["n_layers"]):
+        assert tuple(ws[i].shape) == arr[f"w1_{i}"].shape
+        assert np.abs(ws[i].numpy() - arr[f"w1_{i}"]).max() < 2e-5 and np.abs(bs[i].numpy() - arr[f"b1_{i}"]).max() < 2e-5
+        assert np.abs(ws[i].numpy() - arr[f"w0_{i}"]).max() > 1e-3  # and they moved
+    if meta["basic"]:  # the write-back is member by member, in place: every live parameter was bumped
+        assert all(p._version > 0 for m in trained["mlp"].members for p in m.parameters() if p.ndim == 3)
+
+
+def test_set_elite_is_the_live_models(trained):
+    """A BasicEnsemble's set_elite warns and keeps every member (elite_models stays None); a GaussianMLP gets the reference's elites."""
+    meta, arr, mlp = trained["meta"], trained["arr"], trained["mlp"]
+    if meta["basic"]:
+        assert mlp.elite_models is None and not meta["elites_set"]
+        assert sum("does not support elite models" in w for w in trained["warnings"]) == 1
+    else:
+        assert sorted(int(i) for i in mlp.elite_models) == sorted(int(i) for i in arr["elites"])
+
+
+def test_optimizer_state_dict_follows_the_live_parameter_order(trained):
+    """state_dict: the reference's key set (the bounds, requires_grad False, get no entry), every entry shaped as its live parameter
+    ([1, in, out] for a BasicEnsemble's members); it round-trips through torch.optim.Adam and through load_state_dict of a second
+    trainer, where member e's moments land in row e of the stacked device tensors."""
+    meta, arr, trainer = trained["meta"], trained["arr"], trained["trainer"]
+    sd = trainer.optimizer.state_dict()
+    params = list(trained["model"].parameters())
+    assert [list(p.shape) for p in params] == meta["param_shapes"]
+    assert sorted(sd["state"]) == meta["adam_state_keys"] and sd["param_groups"][0]["params"] == list(range(len(params)))
+    steps = meta["epochs_run"] * ((len(arr["train_rows"]) - 1) // meta["batch_size"] + 1)
+    for k, st in sd["state"].items():
+        assert tuple(st["exp_avg"].shape) == tuple(st["exp_avg_sq"].shape) == tuple(params[k].shape) == arr[f"m_{k}"].shape
+        assert float(st["step"]) == steps
+    opt = torch.optim.Adam(params, lr=meta["lr"])
+    opt.load_state_dict(sd)
+    back = opt.state_dict()
+    _, model2, _, _, _ = tlr.golden_setup(meta, arr)
+    trainer2 = hipets.ModelTrainer(model2, optim_lr=meta["lr"], engine=tlr.CpuEngineKinds(), extended=True)
+    trainer2.optimizer.load_state_dict(back)
+    assert trainer2._step == steps
+    for k in (0, 1):
+        for li in range(meta["n_layers"]):
+            assert torch.equal(trainer2._m[k][li], trainer._m[k][li]) and torch.equal(trainer2._v[k][li], trainer._v[k][li])
+    sd2 = trainer2.optimizer.state_dict()
+    for k, st in sd["state"].items():
+        assert torch.equal(sd2["state"][k]["exp_avg"], st["exp_avg"]) and torch.equal(sd2["state"][k]["exp_avg_sq"], st["exp_avg_sq"])
+
+
+@pytest.mark.parametrize("name", KINDS)
+def test_adam_state_from_epoch_1_lands_in_member_rows(name):
+    """load_state_dict of the reference optimizer's state after epoch 1: entry k of the live parameter order is member e's
+    [1, ., .] moments, which must land in row e of the stacked tensors (and come back out at k)."""
+    meta, arr = _golden(name)
+    _, model, _, _, _ = tlr.golden_setup(meta, arr)
+    trainer = hipets.ModelTrainer(model, optim_lr=meta["lr"], engine=tlr.CpuEngineKinds(), extended=True)
+    n = len(meta["param_shapes"])
+    group = dict(trainer.optimizer.state_dict()["param_groups"][0], params=list(range(n)))
+    trainer.optimizer.load_state_dict({"state": {int(k): {"step": torch.tensor(float(meta["adam_step_epoch1"])), "exp_avg": torch.from_numpy(arr[f"m_{k}"]),
+                                                          "exp_avg_sq": torch.from_numpy(arr[f"v_{k}"])} for k in meta["adam_state_keys"]},
+                                       "param_groups": [group]})
+    assert trainer._step == int(meta["adam_step_epoch1"])
+    pos = {id(p): i for i, p in enumerate(model.parameters())}
+    seen = 0
+    for li, e, k, p in trainer._slots():
+        key = pos[id(p)]
+        rows = trainer._m[k][li] if e is None else trainer._m[k][li][e:e + 1]
+        assert np.array_equal(rows.numpy(), arr[f"m_{key}"])
+        seen += 1
+    assert seen == len(meta["adam_state_keys"])
+
+
+# ---- the additive C ABI --------------------------------------------------------------------------------------------------------
+def test_header_and_binding_carry_the_new_entry_points():
+    src = open(os.path.join(ROOT, "include", "hipets.h")).read()
+    assert re.search(r"^#define HIPETS_ABI_VERSION 9$", src, flags=re.M)
+    assert re.search(r"^#define HIPETS_TRAIN_LOSS_NLL 0\b", src, flags=re.M) and re.search(r"^#define HIPETS_TRAIN_LOSS_MSE 1\b", src, flags=re.M)
+    for name, tail in (("hipets_train_steps_loss", r"void\* stream, int32_t loss_kind, int32_t bounds_per_member, float grad_scale"),
+                       ("hipets_train_eval_loss", r"void\* stream, int32_t loss_kind")):
+        proto = re.search(r"^int " + name + r"\(([^()]*)\);", src, flags=re.M)
+        assert proto and re.search(tail + r"$", " ".join(proto.group(1).split())), name
+        assert name in _lib.SYMBOLS
+    assert [n for n, _ in _lib.SYMBOLS["hipets_train_steps_loss"][1]][:12] == [n for n, _ in _lib.SYMBOLS["hipets_train_steps"][1]]
+    assert [n for n, _ in _lib.SYMBOLS["hipets_train_eval_loss"][1]][:9] == [n for n, _ in _lib.SYMBOLS["hipets_train_eval"][1]]
+    assert _lib.ABI_VERSION == 9 and _lib.TRAIN_LOSS == {"nll": 0, "mse": 1}
+
+
+# ---- the restatements against the reference's own update ------------------------------------------------------------------------
+@pytest.mark.parametrize("kind", ["basic_nll", "gmlp_mse", "basic_mse"])
+def test_restatement_equals_reference_update_float64(kind):
+    """mse_step and the 1 / E NLL step with per-member bounds, then Adam, against Model.update + torch.optim.Adam of the reference in
+    float64 (tests/golden/trainerx_host_cases.npz): loss, grad_norm, weights and both moments after one and two steps."""
+    meta, a = _golden("trainerx_host_cases")
+    m = meta["update"][kind]
+    L, E = 3, 3
+    ws = [torch.from_numpy(a[f"u_{kind}_w0_{i}"]).clone() for i in range(L)]
+    bs = [torch.from_numpy(a[f"u_{kind}_b0_{i}"]).clone() for i in range(L)]
+    ms = ([torch.zeros_like(w) for w in ws], [torch.zeros_like(b) for b in bs])
+    vs = ([torch.zeros_like(w) for w in ws], [torch.zeros_like(b) for b in bs])
+    loss_kind = "mse" if m["deterministic"] else "nll"
+    lo = hi = None
+    terms = torch.zeros(E, dtype=torch.float64)
+    if loss_kind == "nll":
+        lo, hi = torch.from_numpy(a[f"u_{kind}_min_logvar"]), torch.from_numpy(a[f"u_{kind}_max_logvar"])
+        assert lo.shape == (E, 3) and not torch.equal(lo[0], lo[1])  # per-member bounds that differ
+        terms = 0.01 * (hi.sum(1) - lo.sum(1))
+    scale = 1.0 / E if m["basic"] else 1.0
+    for step in range(2):
+        x, y = torch.from_numpy(a[f"u_{kind}_x{step}"]), torch.from_numpy(a[f"u_{kind}_y{step}"])
+        loss, gsq = tlr.train_step_kind(loss_kind, ws, bs, ms, vs, x, y, lo, hi, m["act"], step + 1, 1e-2, 1e-3, grad_scale=scale)
+        total = ((loss + terms).sum() * scale).item()
+        assert abs(total - m["loss"][step]) < 1e-12 * max(1.0, abs(total))
+        assert abs(gsq.sum().item() - m["grad_norm"][step]) < 1e-12 * max(1.0, gsq.sum().item())
+        for i in range(L):
+            assert (ws[i] - torch.from_numpy(a[f"u_{kind}_w{step + 1}_{i}"])).abs().max().item() < 1e-12
+            assert (bs[i] - torch.from_numpy(a[f"u_{kind}_b{step + 1}_{i}"])).abs().max().item() < 1e-12
+            assert (ms[0][i] - torch.from_numpy(a[f"u_{kind}_m{step + 1}_{i}"])).abs().max().item() < 1e-12
+            assert (vs[0][i] - torch.from_numpy(a[f"u_{kind}_v{step + 1}_{i}"])).abs().max().item() < 1e-12
