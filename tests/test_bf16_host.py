@@ -4,13 +4,15 @@ GPU parity tests (tests/test_gpu_bf16.py) to tell bf16 from fp32.
 Packing: the weight packer (csrc/rollout_helpers.hpp pack_weights_b3_kernel, pieces = 1) is a device kernel and is not reachable
 from a host build; the plane it writes is piece 0 of split3, i.e. bf16_rne_bits of the weight -- the rounding this file restates and
 checks against torch.  The packed layout itself is covered on the GPU: a misplaced or mis-rounded weight fails the replay tests."""
+import json
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from bf16_restatement import CFG2, T1_ATOL, T2_REL, bf16_rne_bits, emulated_rollout, scaled_case
+from bf16_restatement import (CASES_OF, CFG2, EDGE_CASES, EDGE_CASES_B3, MUTATIONS, T1_ATOL, T2_REL, bf16_rne_bits, edge_figures, emulated_rollout,
+                               scaled_case)
 from conftest import ROOT, to_spec
 from oracle import pets_oracle as po
 
@@ -62,3 +64,60 @@ def test_scaled_case_tells_bf16_from_fp32(monkeypatch, H, bound):
     assert fig >= 10 * bound, fig
     # the restatement is no longer installed: the oracle is the fp32 one again
     assert torch.equal(po.rollout(om, actions, s0, P, perms=perms, eps=eps), f32)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The edge probes of the two instance families (tests/bf16_restatement.py EDGE_CASES): what the GPU tests of every case can see,
+# measured on the CPU before a GPU is touched
+# ---------------------------------------------------------------------------------------------------------------------
+_EDGE = [(prec, c) for prec in ("bf16", "bf16x3") for c in CASES_OF[prec]]
+
+
+@pytest.mark.parametrize("mode", ["device", "fast"])
+@pytest.mark.parametrize("prec,case", _EDGE, ids=[f"{p}-{c.name}" for p, c in _EDGE])
+def test_edge_case_cpu_conditions(monkeypatch, prec, case, mode):
+    """Against the reference of `prec` (bf16: the emulation, tol_i = max(T2_i, D / 4); bf16x3: the fp32 oracle, T2), on the CPU
+    restatement of the draws the GPU test replays:
+    (a) power: zeroing the last input row of layer 0, the last hidden row of layer 1 (where a hidden -> hidden layer exists), the last
+        mean column or the last log-variance column moves some candidate's reference return by >= 4 x its tolerance (the device may
+        itself use up to 1 x);
+    (b) spread: the same restatement accumulated in f64 stays within tol / 4 of the reference for every candidate -- the kernel's own
+        fp32 summation order, which neither restates, has four times the room the reference's needs;
+    (c) the reference returns are finite, and no row's height is within 1e-4 of the humanoid thresholds 1.0 / 2.0;
+    (d) bf16: some candidate's |emu - f32| is >= 4 x its T2 tolerance: the mode is told apart from fp32;
+    (e) bf16, flip room: with every activation moved by -2, -1, 1 or 2 fp32 ulps before its rounding to bf16 the emulation stays within
+        tol / 2 of itself for every candidate.  The device's elementwise functions are not torch's (its SiLU, x rcp(1 + exp2(-x log2 e)),
+        is off by 0.3 ulp on average and <= 2.6 on [-3, 10]), so some activations land on the other side of a bf16 boundary there: a
+        case in which one such flip is worth a tolerance tests the draw of the flips, not the kernel.  (b) and (e) together leave the
+        device a quarter of the tolerance."""
+    f = edge_figures(monkeypatch, case, prec, mode)
+    print("EDGE_CPU " + json.dumps({"case": case.name, "precision": prec, "mode": mode, **f}))
+    assert f["finite"]
+    want = [m for m in MUTATIONS if m != "hid_row" or case.mkw.get("num_layers", 4) > 1]
+    assert sorted(f["power"]) == sorted(want)
+    assert min(f["power"].values()) >= 4.0, f["power"]
+    assert f["spread"] <= 0.25, f["spread"]
+    assert f["margin"] >= 1e-4, f["margin"]
+    if prec == "bf16":
+        assert f["told"] >= 4.0, f["told"]
+        assert sorted(f["flip"]) == [-2, -1, 1, 2] and max(f["flip"].values()) <= 0.5, f["flip"]
+
+
+def test_edge_case_table_covers_the_family_edges():
+    """Every edge the table claims, stated on the shapes: input widths on both sides of the 32-wide k chunks up to the first ring
+    refill (kBf16Ahead = 4 chunks), full and nearly empty last output tiles, both hidden-width limits, both depths, a non-prefix
+    member subset and single-tile batches; bf16x3 runs the same table up to the widest input its three-plane rows leave LDS for."""
+    ins = {c.name: c.obs + c.act for c in EDGE_CASES}
+    assert [ins[n] for n in ("A_in18", "A_in32", "A_in33", "A_in64", "A_in65", "A_in97", "A_in129")] == [18, 32, 33, 64, 65, 97, 129]
+    assert [ins[n] for n in ("B_in42", "B_in64", "B_in65", "B_in97")] == [42, 64, 65, 97]
+    assert {-(-i // 32) for i in ins.values()} >= {1, 2, 3, 4, 5}
+    for cases in (EDGE_CASES, EDGE_CASES_B3):
+        fam_a = [c for c in cases if c.mkw.get("termination") is None]
+        fam_b = [c for c in cases if c.mkw.get("termination") == "humanoid"]
+        assert {c.obs for c in fam_a} >= {17, 24} and all(17 <= c.obs <= 24 for c in fam_a)
+        assert {c.obs for c in fam_b} >= {41, 48} and all(41 <= c.obs <= 48 for c in fam_b)
+        assert {c.mkw["hid"] for c in cases} == {193, 200, 208}
+        assert {c.mkw.get("num_layers", 4) for c in cases} == {1, 4, 7}
+        assert any(c.mkw.get("elite") == [0, 2, 3, 5, 6] for c in cases) and {c.pop for c in cases} == {1, 7, 40}
+        assert all((c.P, c.H) == (5, 4) for c in cases)
+    assert [c.name for c in EDGE_CASES_B3 if c not in EDGE_CASES] == ["A_in88", "B_in96"] and len(EDGE_CASES_B3) == len(EDGE_CASES) - 1

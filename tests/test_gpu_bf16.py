@@ -19,7 +19,8 @@ import pytest
 import torch
 
 import hipets
-from bf16_restatement import CFG2, T1_ATOL, T2_REL, emulated_rollout, scaled_case
+from bf16_restatement import (CFG2, EDGE_CASES, T1_ATOL, T2_REL, edge_case, emulated_rollout, reference_rollout, scaled_case, threshold_margin,
+                               tolerance)
 from conftest import to_spec
 from hipets.planning import _BoundObjective
 from oracle import device_draws
@@ -64,7 +65,10 @@ def _run(engine, monkeypatch, case, H, mode):
 def test_bf16_rollouts_replayed_through_the_bf16_emulation(engine, monkeypatch, case, H, mode):
     """|hip_i - emu_i| <= tol_i, all values finite.  cfg4 (humanoid termination: the thresholds at heights 1.0 and 2.0 are
     discontinuities): candidates with any row whose EMULATED height is within 1e-4 of a threshold are not compared, and at most 2 % of
-    the candidates may be dropped -- a kernel whose heights differ from the emulation by more than 1e-4 fails here, by design."""
+    the candidates may be dropped -- a kernel whose heights differ from the emulation by more than 1e-4 fails here, by design.
+    cfg2_H1: at H = 1 the return sees output columns 0 and obs only (the mean and log-variance of state dim 0); on the CPU, zeroing the
+    last mean or log-variance column moves no emulated return, the last input row moves one by 26 x tol and the last hidden row of
+    layer 1 by 10 x tol.  The other output columns are pinned by the edge cases below (H = 4, gained edge columns)."""
     pop, P = case[2], case[3]
     hip, emu, f32, tr = _run(engine, monkeypatch, case, H, mode)
     assert torch.isfinite(hip).all() and torch.isfinite(emu).all()
@@ -100,7 +104,8 @@ def test_bf16_keeps_the_elites_of_a_cfg2_iteration(engine, monkeypatch, mode):
 @pytest.mark.parametrize("mode", ["device", "fast"])
 def test_bf16_is_really_bf16(engine, monkeypatch, mode):
     """cfg2, H = 1: the kernel differs from the fp32 oracle by more than 10 x the fp32 mode's one-step tolerance, and the instance
-    that runs is the bf16 one at R = 3."""
+    that runs is the bf16 one at R = 3.  (At H = 1 the return sees output columns 0 and obs only -- the mean and log-variance of state
+    dim 0: no other output column can move it.)"""
     obs, act, pop, P, mkw = CFG2
     hip, emu, f32, _ = _run(engine, monkeypatch, CFG2, 1, mode)
     assert (hip - f32).abs().max().item() > 10 * T1_ATOL
@@ -137,3 +142,88 @@ def test_bf16_rollouts_are_deterministic(engine, mode):
     a = engine.rollout(actions.to(DEV), s0, P, mode=mode, seed=7, stream_id=2).clone()
     b = engine.rollout(actions.to(DEV), s0, P, mode=mode, seed=7, stream_id=2).clone()
     assert torch.equal(a, b)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The edges of the two instance families (tests/bf16_restatement.py EDGE_CASES; tests/test_bf16_host.py holds the CPU conditions of
+# every case: each single-column loss moves a return by >= 4 tol, the reference's own summation order uses <= tol / 4)
+# ---------------------------------------------------------------------------------------------------------------------
+KERNEL_CLASS = {"bf16": "bf16", "bf16x3": "fused"}
+
+
+def edge_replay(engine, monkeypatch, case, prec, mode):
+    """One edge case in arithmetic `prec`: (hip, ref, D, tol, om, actions, s0) -- the kernel's returns, the reference of `prec` on the
+    draws the engine exports, D = max |emu - f32| and the tolerance (bf16_restatement.tolerance).  Asserts what does not depend on the
+    arithmetic: the instance is the mode's own at three row tiles, everything is finite, no height is within 1e-4 of a threshold."""
+    om, actions, s0, _, _ = edge_case(case.obs, case.act, case.pop, case.P, case.H, seed=case.seed, gain=case.gain, g_in=case.g_in,
+                                      g_lv=case.g_lv, **case.mkw)
+    engine.set_model(to_spec(om, case.obs, case.act, precision=prec))
+    assert engine.kernel_class(case.pop, case.P, case.H, mode=mode) == (KERNEL_CLASS[prec], 3)
+    hip = engine.rollout(actions.to(DEV), s0, case.P, mode=mode, seed=SEED, stream_id=SID).cpu()
+    kw = _draws(engine, case.pop, case.P, case.H, mode)
+    tr = {}
+    ref = reference_rollout(monkeypatch, prec, om, actions, s0, case.P, trace=tr, **kw)
+    f32 = po.rollout(om, actions, s0, case.P, **kw)
+    emu = ref if prec == "bf16" else reference_rollout(monkeypatch, "bf16", om, actions, s0, case.P, **kw)
+    assert torch.isfinite(hip).all() and torch.isfinite(ref).all()
+    # the keep-mask of the replay tests above is empty here (cap: 0 candidates dropped)
+    assert threshold_margin(om, tr) >= 1e-4, threshold_margin(om, tr)
+    D = (emu - f32).abs().max().item()
+    return hip, ref, D, tolerance(prec, ref, D), om, actions, s0
+
+
+def edge_parity_line(tag, case, prec, mode, err, D, tol):
+    print(tag + " " + json.dumps({"case": case.name, "precision": prec, "mode": mode, "max_hip_minus_ref": err.max().item(), "D": D,
+                                  "ratio": err.max().item() / D, "of_tol": (err / tol).max().item()}))
+
+
+@pytest.mark.parametrize("mode", ["device", "fast"])
+@pytest.mark.parametrize("case", EDGE_CASES, ids=lambda c: c.name)
+def test_bf16_edge_cases_replayed_through_the_bf16_emulation(engine, monkeypatch, case, mode):
+    """|hip_i - emu_i| <= tol_i = max(1e-4 max(1, |emu_i|), D / 4) for EVERY candidate (no candidate is masked), all values finite,
+    the bf16 instance at three row tiles."""
+    hip, emu, D, tol, *_ = edge_replay(engine, monkeypatch, case, "bf16", mode)
+    err = (hip - emu).abs()
+    edge_parity_line("BF16_PARITY", case, "bf16", mode, err, D, tol)
+    bad = err > tol
+    assert not bad.any(), f"max |hip - emu| {err.max():.3e} (D {D:.3e}, {(err / tol).max():.2f} x tol) at candidate {int(bad.nonzero()[0])}"
+
+
+# models next to the two families: (obs, act, model kwargs).  None has an instance in this arithmetic
+REFUSED = {
+    "obs16": (16, 6, dict(hid=200)), "obs25": (25, 6, dict(hid=200)),
+    "obs40_humanoid": (40, 17, dict(hid=200, termination="humanoid")), "obs49_humanoid": (49, 17, dict(hid=200, termination="humanoid")),
+    "hid192": (17, 6, dict(hid=192)), "hid209": (17, 6, dict(hid=209)),
+    "obs17_humanoid": (17, 6, dict(hid=200, termination="humanoid")),
+    "obs_process": (17, 6, dict(hid=200, obs_process="halfcheetah")),
+    "learned_rewards": (17, 6, dict(hid=200, learned_rewards=True, reward=None)),
+    "relu": (17, 6, dict(hid=200, activation="relu")),
+    "normalizer_f32": (17, 6, dict(hid=200, normalizer="f32")),
+    "expectation": (17, 6, dict(hid=200, propagation="expectation")),
+    "deterministic": (17, 6, dict(hid=200, deterministic=True)),
+}
+ACCEPTED = next(c for c in EDGE_CASES if c.name == "A_pop7")
+
+
+def assert_refused_then_accepted(engine, prec, match, obs, act, mkw):
+    """A model without an instance raises in both launch modes -- it never runs another arithmetic --, and the accepted model set
+    right after it returns what it returned before."""
+    c = ACCEPTED
+    good, actions, s0, _, _ = edge_case(c.obs, c.act, c.pop, c.P, c.H, seed=c.seed, gain=c.gain, g_in=c.g_in, g_lv=c.g_lv, **c.mkw)
+    engine.set_model(to_spec(good, c.obs, c.act, precision=prec))
+    before = {m: engine.rollout(actions.to(DEV), s0, c.P, mode=m, seed=SEED, stream_id=SID).clone() for m in ("device", "fast")}
+    om = po.make_synthetic_model(obs, act, ensemble_size=5, seed=3, **mkw)
+    for m in ("device", "fast"):
+        with pytest.raises(hipets.HipetsError, match=match):
+            engine.set_model(to_spec(om, obs, act, precision=prec))
+            engine.rollout(torch.zeros(40, 4, act, device=DEV), np.zeros(obs, np.float32), 5, mode=m, seed=SEED, stream_id=SID)
+    engine.set_model(to_spec(good, c.obs, c.act, precision=prec))
+    for m in ("device", "fast"):
+        after = engine.rollout(actions.to(DEV), s0, c.P, mode=m, seed=SEED, stream_id=SID)
+        assert torch.isfinite(after).all() and torch.equal(after, before[m])
+        assert engine.kernel_class(c.pop, c.P, c.H, mode=m) == (KERNEL_CLASS[prec], 3)
+
+
+@pytest.mark.parametrize("name", list(REFUSED))
+def test_bf16_refuses_models_next_to_its_families(engine, name):
+    assert_refused_then_accepted(engine, "bf16", "precision bf16:", *REFUSED[name])

@@ -7,10 +7,12 @@ import pytest
 import torch
 
 import hipets
+from bf16_restatement import B3_TOO_WIDE, EDGE_CASES_B3, SEED, SID
 from conftest import to_spec
 from hipets.planning import _BoundObjective
 from oracle import pets_oracle as po
 from oracle import device_draws
+from test_gpu_bf16 import REFUSED, assert_refused_then_accepted, edge_parity_line, edge_replay
 from test_gpu_rollout import SIZES, _random_case, assert_returns_close
 
 pytestmark = pytest.mark.gpu
@@ -22,6 +24,10 @@ B3_CASES = [SIZES[0], SIZES[3], SIZES[4], (17, 6, 7, 5, 4, dict(ensemble_size=5,
 @pytest.mark.parametrize("mode", ["fast", "device"])
 @pytest.mark.parametrize("case", B3_CASES, ids=lambda c: f"obs{c[0]}_pop{c[2]}x{c[3]}_H{c[4]}")
 def test_bf16x3_rollouts_replayed_through_the_oracle(engine, case, mode):
+    """Stock synthetic weights: returns within T2 of the oracle.  What this comparison cannot see: on the small case (17, 6, 7, 5, 4)
+    zeroing the last input row, the last hidden row of layer 1, the last mean column or the last log-variance column moves the oracle's
+    returns by at most 3.0 / 1.9 / 0.01 / 0.00 x T2 (DEVICE; FAST 1.7 / 1.6 / 0.01 / 0.00) -- the reward reads state dim 0 alone.  Its
+    gained variant, on which each of the four moves a return by >= 34 x T2, is EDGE_CASES_B3's A_pop7 below."""
     obs, act, pop, P, H, mkw = case
     om, actions, s0, _, _ = _random_case(obs, act, pop, P, H, **mkw)
     engine.set_model(to_spec(om, obs, act, precision="bf16x3"))
@@ -57,7 +63,9 @@ def test_bf16x3_rollouts_replayed_through_the_oracle(engine, case, mode):
 
 def test_bf16x3_one_step_accuracy(engine):
     """One transition (H = 1: the return is the step's reward s'[0] - 0.1 |a|^2, i.e. one MLP evaluation + sampling) at the one-step
-    tolerance T1 (rtol 1e-5, atol 2e-6)."""
+    tolerance T1 (rtol 1e-5, atol 2e-6).  At H = 1 the return sees output columns 0 (mean) and obs (log-variance) only: zeroing the last
+    mean or log-variance column moves no return at all, the last input row moves one by 34 x T1 and the last hidden row of layer 1 by
+    11 x (CPU, bf16_restatement.mutated).  The other output columns are the edge cases' business (EDGE_CASES_B3, H = 4)."""
     obs, act, pop, P = 17, 6, 500, 20
     om, actions, s0, _, _ = _random_case(obs, act, pop, P, 1, ensemble_size=5, hid=200)
     engine.set_model(to_spec(om, obs, act, precision="bf16x3"))
@@ -85,3 +93,35 @@ def test_bf16x3_fused_plan_equals_per_iteration_path_and_needs_a_specialised_sha
     with pytest.raises(hipets.HipetsError, match="bf16x3"):  # injected eps need the generic kernel
         engine.rollout(torch.zeros(40, 3, act, device=DEV), np.zeros(obs, np.float32), 5, mode="exact",
                        perms=torch.stack([torch.randperm(200) for _ in range(3)]).to(DEV), eps=torch.zeros(3, 200, obs, device=DEV))
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The edges of the two instance families (tests/bf16_restatement.py EDGE_CASES_B3; tests/test_bf16_host.py holds the CPU conditions
+# of every case: each single-column loss moves a return by >= 4 x T2, the oracle's own summation order uses <= T2 / 4)
+# ---------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mode", ["device", "fast"])
+@pytest.mark.parametrize("case", EDGE_CASES_B3, ids=lambda c: c.name)
+def test_bf16x3_edge_cases_replayed_through_the_oracle(engine, monkeypatch, case, mode):
+    """|hip_i - oracle_i| <= 1e-4 max(1, |oracle_i|) (T2) for EVERY candidate, all values finite, the bf16x3 instance at three row
+    tiles; and against the fp32-MFMA kernel on the same draws (FAST: the same row-tile count) err < 2e-5."""
+    hip, ref, D, tol, om, actions, s0 = edge_replay(engine, monkeypatch, case, "bf16x3", mode)
+    err = (hip - ref).abs()
+    edge_parity_line("BF16X3_PARITY", case, "bf16x3", mode, err, D, tol)
+    bad = err > tol
+    assert not bad.any(), f"max |hip - oracle| {err.max():.3e} ({(err / tol).max():.2f} x T2) at candidate {int(bad.nonzero()[0])}"
+    engine.set_model(to_spec(om, case.obs, case.act))
+    f32 = engine.rollout(actions.to(DEV), s0, case.P, mode=mode, seed=SEED, stream_id=SID, rows_per_group=3 if mode == "fast" else 0).cpu()
+    rel = ((hip - f32).abs() / torch.clamp(f32.abs(), min=1.0)).max().item()
+    assert rel < 2e-5, rel
+
+
+@pytest.mark.parametrize("name", list(REFUSED))
+def test_bf16x3_refuses_models_next_to_its_families(engine, name):
+    assert_refused_then_accepted(engine, "bf16x3", "bf16x3", *REFUSED[name])
+
+
+@pytest.mark.parametrize("obs,act,mkw", B3_TOO_WIDE, ids=[f"obs{o}_act{a}" for o, a, _ in B3_TOO_WIDE])
+def test_bf16x3_refuses_inputs_too_wide_for_three_row_tiles(engine, obs, act, mkw):
+    """The mode's only instances run three row tiles, whose three-plane activation rows leave LDS for act_dim <= 64 (obs 24) / 55
+    (obs 41): one column more, and the bf16 table's four- and five-chunk widths, raise."""
+    assert_refused_then_accepted(engine, "bf16x3", "bf16x3", obs, act, {k: v for k, v in mkw.items() if k != "ensemble_size"})
