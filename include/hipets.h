@@ -725,6 +725,48 @@ int hipets_train_steps_loss(hipets_engine* e, const hipets_train_desc* d, const 
 int hipets_train_eval_loss(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows,
                            const int32_t* order, float* score, float* row_score, void* stream, int32_t loss_kind);
 
+/* ---- MBPO model rollouts: the SAC Gaussian actor and the compacting populate step (mbrl/algorithms/mbpo.py:31-63) ----
+ * Additive entry points: scalars and pointers only, no struct, HIPETS_ABI_VERSION stays.  Needs no dynamics model.
+ *
+ * The actor is GaussianPolicy.forward / sample (mbrl/third_party/pytorch_sac_pranz24/model.py:88-108) as SAC.select_action uses it:
+ *   h1 = relu(obs W1^T + b1);  h2 = relu(h1 W2^T + b2);  mean = h2 Wm^T + bm;  log_std = clamp(h2 Ws^T + bs, -20, 2)
+ *   sample != 0:  action = tanh(mean + exp(log_std) * eps) * action_scale + action_bias
+ *   sample == 0:  action = tanh(mean) * action_scale + action_bias
+ * All products are fp32 MFMA with fp32 accumulation, everything after them fp32 op by op (no fused multiply-add).
+ * hipets_policy_set copies DEVICE tensors in nn.Linear's layout -- w1 [hidden, obs_dim], w2 [hidden, hidden], wm / ws [act_dim, hidden],
+ * b1 / b2 [hidden], bm / bs [act_dim] -- and the per-dimension action_scale / action_bias [act_dim] into the engine's own packed layout
+ * (the two heads become ONE product of 2 act_dim columns); it does not synchronise: the source tensors must stay alive until the
+ * work enqueued on `stream` has run (stream-ordered frees, as torch's allocator does them, are fine).
+ * 1 <= obs_dim <= 512, 1 <= hidden <= 1024, 1 <= act_dim <= 32; anything else is HIPETS_ERR_INVALID_ARGUMENT.                       */
+#define HIPETS_POLICY_MAX_OBS 512
+#define HIPETS_POLICY_MAX_HIDDEN 1024
+#define HIPETS_POLICY_MAX_ACT 32
+int hipets_policy_set(hipets_engine* e, int32_t obs_dim, int32_t hidden, int32_t act_dim, const float* w1, const float* b1, const float* w2,
+                      const float* b2, const float* wm, const float* bm, const float* ws, const float* bs, const float* action_scale,
+                      const float* action_bias, void* stream);
+/* One launch: obs DEVICE [batch, obs_dim] -> actions DEVICE [batch, act_dim]; batch >= 1.  eps DEVICE [batch, act_dim] or NULL: with
+ * sample != 0 and eps == NULL the kernel draws eps[row][d] itself, Philox normals keyed by (seed, stream_id, row, d) in a key domain
+ * of their own (independent of the rollouts' draws of the same (seed, stream_id)); hipets_policy_normals returns exactly that table.
+ * Optional taps (NULL = not wanted): mean_out / log_std_out DEVICE [batch, act_dim], the heads before tanh (log_std after its clamp).
+ * A row's arithmetic does not depend on the batch it arrives in: row r of any call equals the one-row call on obs[r].               */
+int hipets_policy_act(hipets_engine* e, const float* obs, int32_t batch, int32_t sample, uint64_t seed, uint64_t stream_id, const float* eps,
+                      float* actions, float* mean_out, float* log_std_out, void* stream);
+/* out DEVICE f32 [batch, act_dim] = the eps hipets_policy_act draws in-kernel for (seed, stream_id).  Needs no policy.              */
+int hipets_policy_normals(hipets_engine* e, int32_t batch, int32_t act_dim, uint64_t seed, uint64_t stream_id, float* out, void* stream);
+/* Launch geometry of hipets_policy_act for `batch` rows of the policy set last: a workgroup owns 16 * row_tiles rows (row_tiles = the
+ * largest of 4, 2, 1 whose activations fit the LDS opt-in limit, no more than the batch needs); lds_bytes = its dynamic LDS.         */
+int hipets_policy_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles, int32_t* lds_bytes);
+/* mbpo.py:53-63 for one rollout step, on the device.  obs / next_obs DEVICE f32 [n, obs_dim], action DEVICE f32 [n, act_dim], rewards
+ * DEVICE f32 [n], dones / accum_dones DEVICE uint8 [n] (non-zero = set).  The rows with accum_dones == 0 are appended in row order
+ * to the staging area, DEVICE f32 [cap * (2 obs_dim + act_dim + 2)]: five arrays one behind the other, obs [cap, obs_dim], action
+ * [cap, act_dim], next_obs [cap, obs_dim], reward [cap], done [cap] (0.0f or 1.0f), every float a plain copy -- starting at row
+ * *offset (DEVICE int64, the running fill); *count_out (DEVICE int32) = the rows kept, *offset += that count, then accum_dones |= dones.
+ * A kept row that would land at or past `cap` is dropped (the counts still advance).
+ * Three ordered launches (per-block counts, one workgroup's scan of them, the scatter); nothing waits on another workgroup.          */
+int hipets_compact_transitions(hipets_engine* e, const float* obs, const float* action, const float* next_obs, const float* rewards,
+                               const uint8_t* dones, uint8_t* accum_dones, int32_t n, int32_t obs_dim, int32_t act_dim, float* staging,
+                               int64_t cap, int64_t* offset, int32_t* count_out, void* stream);
+
 /* ---- instrumentation (bench.py roofline leg) ----------------------------------------------- */
 /* on = 1: every rollout-kernel launch carries a start / stop hipEvent pair on its dispatch packet; on = k > 1: every
  * k-th launch does (a completion signal per packet costs a few microseconds between back-to-back short launches -- the

@@ -125,6 +125,10 @@ struct hipets_engine {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> event_pool;
     // model training (hipets_train_steps / hipets_train_eval): per-member activation slabs, evaluate's partial sums
     DevBuf train_slab, train_partial;
+    // SAC actor (hipets_policy_set / hipets_policy_act, policy.hip): the packed layers, and the block counts of hipets_compact_transitions
+    bool has_policy = false;
+    int policy_obs = 0, policy_hid = 0, policy_act = 0;
+    DevBuf policy_w, policy_b, compact_counts;
 };
 
 #pragma GCC visibility push(hidden)

@@ -47,6 +47,7 @@ COL_FN = {"id": 0, "sin": 1, "cos": 2}  # HIPETS_COL_*
 MAX_OBS_COLUMNS = 512
 KERNEL_CLASSES = ("generic", "hidden_static", "fused", "wide", "bf16")  # HIPETS_KERNEL_*
 REDUCE = {"mean": 0, "mean_std": 1, "min": 2, "max": 3, "worst_k": 4}  # HIPETS_REDUCE_*
+POLICY_MAX_OBS, POLICY_MAX_HIDDEN, POLICY_MAX_ACT = 512, 1024, 32  # HIPETS_POLICY_MAX_*
 
 
 class RewardTermC(C.Structure):  # hipets_reward_term
@@ -229,6 +230,12 @@ SYMBOLS = {
     "hipets_train_steps_loss": _sig("e d:TrainDesc* x y n_rows:i64 idx rows n_steps:i32 step0:i64 loss grad_sq stream loss_kind:i32 "
                                     "bounds_per_member:i32 grad_scale:f32"),
     "hipets_train_eval_loss": _sig("e d:TrainDesc* x y n_rows:i64 order score row_score stream loss_kind:i32"),
+    "hipets_policy_set": _sig("e obs_dim:i32 hidden:i32 act_dim:i32 w1 b1 w2 b2 wm bm ws bs action_scale action_bias stream"),
+    "hipets_policy_act": _sig("e obs batch:i32 sample:i32 seed:u64 stream_id:u64 eps actions mean_out log_std_out stream"),
+    "hipets_policy_normals": _sig("e batch:i32 act_dim:i32 seed:u64 stream_id:u64 out stream"),
+    "hipets_policy_geometry": _sig("e batch:i32 row_tiles:i32* lds_bytes:i32*"),
+    "hipets_compact_transitions": _sig("e obs action next_obs rewards dones accum_dones n:i32 obs_dim:i32 act_dim:i32 staging cap:i64 offset "
+                                       "count_out stream"),
     "hipets_timing_enable": _sig("e on:i32"),
     "hipets_timing_read": _sig("e launches:i64* total_ms:f64* reset:i32"),
 }

@@ -226,3 +226,36 @@ def pack_plan_trace(buffers: dict, max_rows: int):
     """hipets_plan_trace over the device tensors ``buffers`` (one per pointer field) -> (trace, keep-alive list)"""
     t = _lib.PlanTrace(max_rows=int(max_rows), **{name: buf.data_ptr() for name, buf in buffers.items()})
     return t, list(buffers.values())
+
+
+POLICY_TENSORS = ("w1", "b1", "w2", "b2", "wm", "bm", "ws", "bs", "action_scale", "action_bias")  # hipets_policy_set, in header order
+
+
+def pack_policy(policy):
+    """A ``GaussianPolicy``-shaped module (pytorch_sac_pranz24/model.py:66-113: linear1, linear2, mean_linear, log_std_linear,
+    action_scale, action_bias) -> ((obs_dim, hidden, act_dim), {name: tensor} in ``POLICY_TENSORS`` order).  The layer tensors are the
+    module's LIVE parameters (detached, nn.Linear's [out, in]); the reference's scalar action_scale 1 / action_bias 0 are broadcast
+    to [act_dim] here.  Anything that is not shaped like a GaussianPolicy -- a DeterministicPolicy has neither head --, or whose sizes
+    hipets_policy_set refuses, raises UnsupportedModelError."""
+    from .model import UnsupportedModelError
+
+    layers = [getattr(policy, n, None) for n in ("linear1", "linear2", "mean_linear", "log_std_linear")]
+    if any(l is None or getattr(l, "weight", None) is None or getattr(l, "bias", None) is None or l.weight.ndim != 2 for l in layers):
+        raise UnsupportedModelError(f"{type(policy).__name__} is not shaped like a GaussianPolicy (linear1, linear2, mean_linear, log_std_linear with biases)")
+    l1, l2, lm, ls = layers
+    hidden, obs_dim = (int(v) for v in l1.weight.shape)
+    act_dim = int(lm.weight.shape[0])
+    if tuple(l2.weight.shape) != (hidden, hidden) or tuple(lm.weight.shape) != (act_dim, hidden) or tuple(ls.weight.shape) != (act_dim, hidden):
+        raise UnsupportedModelError("GaussianPolicy layer shapes do not chain: expected [hid, obs], [hid, hid] and two [act, hid] heads")
+    if not (1 <= obs_dim <= _lib.POLICY_MAX_OBS and 1 <= hidden <= _lib.POLICY_MAX_HIDDEN and 1 <= act_dim <= _lib.POLICY_MAX_ACT):
+        raise UnsupportedModelError(f"policy sizes (obs {obs_dim}, hidden {hidden}, act {act_dim}) outside the actor kernel's "
+                                    f"(<= {_lib.POLICY_MAX_OBS}, <= {_lib.POLICY_MAX_HIDDEN}, <= {_lib.POLICY_MAX_ACT})")
+    out = {}
+    for name, lin in (("1", l1), ("2", l2), ("m", lm), ("s", ls)):
+        out["w" + name], out["b" + name] = lin.weight.detach(), lin.bias.detach()
+    for name, default in (("action_scale", 1.0), ("action_bias", 0.0)):
+        v = torch.as_tensor(getattr(policy, name, default), dtype=torch.float32).detach().reshape(-1)
+        if v.numel() not in (1, act_dim):
+            raise UnsupportedModelError(f"policy.{name} holds {v.numel()} values for {act_dim} action dims")
+        out[name] = v.expand(act_dim)
+    return (obs_dim, hidden, act_dim), {n: out[n] for n in POLICY_TENSORS}

@@ -11,7 +11,7 @@ import torch
 from . import _lib
 from ._lib import CemParams, HipetsError
 from ._pack import (_check_dev, member_slots, pack_model_desc, pack_plan_trace, pack_planet_desc, pack_reward_terms,  # noqa: F401
-                    pack_rollout_opts, pack_train_desc)
+                    pack_policy, pack_rollout_opts, pack_train_desc)
 from .model import ModelSpec
 from .reduce import ParticleReduce
 
@@ -649,6 +649,88 @@ class Engine:
             self._call("hipets_train_eval_loss", d=d, x=x, y=y, n_rows=N, order=order, score=score, row_score=rs, loss_kind=_lib.TRAIN_LOSS[loss])
         del keep
         return (score, rs) if row_scores else score
+
+    # ---- MBPO model rollouts: the SAC Gaussian actor and the compacting populate step (hipets_policy_* / hipets_compact_transitions) ----
+    def policy_set(self, policy):
+        """Snapshot a ``GaussianPolicy``-shaped module's live weights into the engine (hipets_policy_set; ``_pack.pack_policy`` reads
+        the module or raises UnsupportedModelError).  Device to device where the policy is on this GPU.  Asynchronous."""
+        dims, tensors = pack_policy(policy)
+        on_dev = {n: t.to(device=self.device, dtype=torch.float32).contiguous() for n, t in tensors.items()}
+        self._call("hipets_policy_set", obs_dim=dims[0], hidden=dims[1], act_dim=dims[2], **on_dev)
+        self.policy_dims = dims
+        return dims
+
+    def _policy_dims(self):
+        dims = getattr(self, "policy_dims", None)
+        if dims is None:
+            raise HipetsError("Engine.policy_set() has not been called")
+        return dims
+
+    def policy_act(self, obs: torch.Tensor, *, sample: bool = False, seed: int = 0, stream_id: int = 0, eps: Optional[torch.Tensor] = None,
+                   out: Optional[torch.Tensor] = None, taps: bool = False):
+        """The actor's forward for ``obs`` f32 [B, obs_dim] on the device -> actions f32 [B, act_dim] (hipets_policy_act): the
+        policy's mean action, or with ``sample`` a draw with ``eps`` f32 [B, act_dim] (None: drawn in-kernel from (seed, stream_id),
+        see :meth:`policy_normals`).  ``taps``: returns (actions, mean, log_std), the heads before tanh."""
+        obs_dim, _, act_dim = self._policy_dims()
+        dev = self.device
+        if not isinstance(obs, torch.Tensor) or obs.ndim != 2 or int(obs.shape[0]) < 1:
+            raise ValueError("obs must be a [B, obs_dim] tensor with B >= 1")
+        B = int(obs.shape[0])
+        _check_dev(obs, torch.float32, dev, "obs", (B, obs_dim))
+        if eps is not None:
+            _check_dev(eps, torch.float32, dev, "eps", (B, act_dim))
+        if out is None:
+            out = torch.empty(B, act_dim, dtype=torch.float32, device=dev)
+        else:
+            _check_dev(out, torch.float32, dev, "out", (B, act_dim))
+        mean = torch.empty_like(out) if taps else None
+        log_std = torch.empty_like(out) if taps else None
+        self._call("hipets_policy_act", obs=obs, batch=B, sample=int(bool(sample)), seed=int(seed), stream_id=int(stream_id), eps=eps,
+                   actions=out, mean_out=mean, log_std_out=log_std)
+        return (out, mean, log_std) if taps else out
+
+    def policy_normals(self, batch: int, act_dim: int, seed: int = 0, stream_id: int = 0) -> torch.Tensor:
+        """The eps a sampling :meth:`policy_act` of ``batch`` rows draws in-kernel for (seed, stream_id): f32 [batch, act_dim]."""
+        out = torch.empty(int(batch), int(act_dim), dtype=torch.float32, device=self.device)
+        self._call("hipets_policy_normals", batch=int(batch), act_dim=int(act_dim), seed=int(seed), stream_id=int(stream_id), out=out)
+        return out
+
+    def policy_geometry(self, batch: int):
+        """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of a :meth:`policy_act` of ``batch`` rows."""
+        self._policy_dims()
+        r, lds = C.c_int32(), C.c_int32()
+        self._query("hipets_policy_geometry", batch=int(batch), row_tiles=C.byref(r), lds_bytes=C.byref(lds))
+        return r.value, lds.value
+
+    def compact_transitions(self, obs, action, next_obs, rewards, dones, accum_dones, staging, cap, offset, count_out):
+        """mbpo.py:53-63 for one rollout step (hipets_compact_transitions): the rows whose ``accum_dones`` (uint8 [N], updated in
+        place: ``|= dones``) is 0 are appended in row order to ``staging``, a flat f32 buffer of at least ``cap * (2 obs_dim + act_dim +
+        2)`` elements holding five arrays one behind the other -- obs [cap, obs_dim], action [cap, act_dim], next_obs [cap, obs_dim],
+        reward [cap], done [cap] (``hipets.mbpo.staging_views`` splits it) -- at row ``offset`` (int64 [1], advanced); ``count_out``
+        int32 [1] = the rows kept.  All tensors on the device; ``rewards`` f32 and ``dones`` bool / uint8 of N elements."""
+        dev = self.device
+        if not isinstance(obs, torch.Tensor) or obs.ndim != 2 or not isinstance(action, torch.Tensor) or action.ndim != 2:
+            raise ValueError("obs / action must be [N, obs_dim] / [N, act_dim] tensors")
+        N, od = (int(v) for v in obs.shape)
+        ad = int(action.shape[1])
+        if N < 1:
+            raise ValueError("no rows")
+        _check_dev(obs, torch.float32, dev, "obs")
+        _check_dev(action, torch.float32, dev, "action", (N, ad))
+        _check_dev(next_obs, torch.float32, dev, "next_obs", (N, od))
+        _check_dev(rewards, torch.float32, dev, "rewards", numel=N)
+        if isinstance(dones, torch.Tensor) and dones.dtype == torch.bool:
+            dones = dones.view(torch.uint8)
+        _check_dev(dones, torch.uint8, dev, "dones", numel=N)
+        _check_dev(accum_dones, torch.uint8, dev, "accum_dones", (N,))
+        _check_dev(staging, torch.float32, dev, "staging")
+        cap = int(cap)
+        if cap < 0 or staging.numel() < cap * (2 * od + ad + 2):
+            raise ValueError(f"staging must hold cap * (2 obs_dim + act_dim + 2) = {cap} * {2 * od + ad + 2} floats, got {staging.numel()}")
+        _check_dev(offset, torch.int64, dev, "offset", numel=1)
+        _check_dev(count_out, torch.int32, dev, "count_out", numel=1)
+        self._call("hipets_compact_transitions", obs=obs, action=action, next_obs=next_obs, rewards=rewards, dones=dones, accum_dones=accum_dones,
+                   n=N, obs_dim=od, act_dim=ad, staging=staging, cap=cap, offset=offset, count_out=count_out)
 
     def timing_enable(self, on=True):
         """True / 1: time every rollout-kernel launch; k > 1: every k-th launch; False / 0: off."""
