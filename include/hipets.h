@@ -767,6 +767,43 @@ int hipets_compact_transitions(hipets_engine* e, const float* obs, const float* 
                                const uint8_t* dones, uint8_t* accum_dones, int32_t n, int32_t obs_dim, int32_t act_dim, float* staging,
                                int64_t cap, int64_t* offset, int32_t* count_out, void* stream);
 
+/* ---- SAC updates: SAC.update_parameters (mbrl/third_party/pytorch_sac_pranz24/sac.py:76-173) on the device ----
+ * Additive entry points: scalars and pointers only, no struct, HIPETS_ABI_VERSION stays.  Needs no dynamics model.
+ *
+ * hipets_sac_bind tells the engine where a Gaussian-policy SAC agent LIVES: `ptrs` is a HOST table of HIPETS_SAC_N_PTRS DEVICE
+ * pointers to contiguous f32 tensors, nn.Linear's [out, in] layout, which hipets_sac_update reads and writes IN PLACE (no packed
+ * copy is kept, nothing is written back):
+ *    0 ..  7  policy: linear1.weight, .bias, linear2.weight, .bias, mean_linear.weight, .bias, log_std_linear.weight, .bias
+ *    8 .. 15  their Adam exp_avg, 16 .. 23 their exp_avg_sq (policy_optim)
+ *   24 .. 35  critic: linear1 .. linear6, weight then bias each (linear1-3 = Q1, linear4-6 = Q2; linear1 / 4 are [hidden, obs + act])
+ *   36 .. 47  their exp_avg, 48 .. 59 their exp_avg_sq (critic_optim)
+ *   60 .. 71  critic_target, as the critic
+ *   72 .. 74  log_alpha [1], its exp_avg, its exp_avg_sq (alpha_optim; may be NULL when tuning == 0)
+ *   75        alpha [1]: the entropy coefficient the update uses; with tuning != 0 the update leaves exp(new log_alpha) there
+ *   76, 77    action_scale, action_bias [act_dim]
+ * adam: HOST [3][3] = (beta1, beta2, eps) of critic_optim, policy_optim, alpha_optim (plain Adam: no amsgrad, weight decay, maximize).
+ * 1 <= obs_dim <= 512, 1 <= hidden <= 1024, 1 <= act_dim <= 32 (the HIPETS_POLICY_MAX_* limits), target_update_interval >= 1;
+ * anything else is HIPETS_ERR_INVALID_ARGUMENT.  The table is copied; the tensors must stay where they are until the next bind.   */
+#define HIPETS_SAC_N_PTRS 78
+#define HIPETS_SAC_MAX_BATCH 1024
+int hipets_sac_bind(hipets_engine* e, int32_t obs_dim, int32_t act_dim, int32_t hidden, int32_t tuning, double gamma, double tau,
+                    double target_entropy, int32_t target_update_interval, const double* adam, const void* ptrs, int32_t n_ptrs);
+/* One update, a fixed sequence of 19 ordinary launches on `stream` (no kernel waits on another workgroup, no float atomics: a repeated
+ * call gives the same bits).  batch DEVICE f32 [batch_size, 2 obs_dim + act_dim + 2]: a row is (state, action, next_state, reward,
+ * mask), mask = what sac.py:93-95 leaves in mask_batch; 1 <= batch_size <= HIPETS_SAC_MAX_BATCH.  eps_next / eps_cur DEVICE f32
+ * [batch_size, act_dim]: the normals of policy.sample(next_state) and policy.sample(state), in the order the reference draws them.
+ * update_index = the reference's `updates` (the target's soft update runs when update_index % target_update_interval == 0, with the
+ * critic's NEW values); step_* = the Adam steps each optimizer has taken BEFORE this update; lr_* its learning rate now.
+ * result DEVICE f32 [8] = (qf1_loss, qf2_loss, policy_loss, alpha_loss, alpha, mean reward of the batch, -mean(log_pi), 0).
+ * Products are fp32 MFMA with fp32 accumulation; everything else fp32 op by op in the reference's order.                          */
+int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, const float* eps_next, const float* eps_cur,
+                      int64_t update_index, int64_t step_critic, int64_t step_policy, int64_t step_alpha, double lr_critic, double lr_policy,
+                      double lr_alpha, float* result, void* stream);
+/* Intermediates of the LAST update (batch_size must be that update's), each DEVICE f32 [batch_size] or NULL: the critic's q1 / q2 on
+ * (state, action), the TD target y, log_pi of the next-state sample and of the state sample.                                      */
+int hipets_sac_forward_taps(hipets_engine* e, int32_t batch_size, float* q1, float* q2, float* y, float* log_pi_next, float* log_pi,
+                            void* stream);
+
 /* ---- instrumentation (bench.py roofline leg) ----------------------------------------------- */
 /* on = 1: every rollout-kernel launch carries a start / stop hipEvent pair on its dispatch packet; on = k > 1: every
  * k-th launch does (a completion signal per packet costs a few microseconds between back-to-back short launches -- the

@@ -62,6 +62,16 @@ struct DevBuf {
     T* as() const { return reinterpret_cast<T*>(p); }
 };
 
+// what hipets_sac_bind keeps: the agent's sizes and hyper-parameters, its optimizers' (beta1, beta2, eps) [critic, policy, alpha], and the
+// pointer table (the live torch tensors, include/hipets.h)
+struct SacBind {
+    int obs = 0, act = 0, hid = 0, interval = 1;
+    bool tuning = false;
+    float gamma = 0.f, tau = 0.f, one_minus_tau = 1.f, target_entropy = 0.f;
+    double adam[9] = {};
+    float* p[HIPETS_SAC_N_PTRS] = {};
+};
+
 }  // namespace hipets
 
 #pragma GCC visibility pop  // (the ABI's own opaque type keeps the default)
@@ -129,6 +139,11 @@ struct hipets_engine {
     bool has_policy = false;
     int policy_obs = 0, policy_hid = 0, policy_act = 0;
     DevBuf policy_w, policy_b, compact_counts;
+    // SAC updates (hipets_sac_bind / hipets_sac_update, sac.hip): the bound agent, the scratch activations (grown on demand), a device 1.0f
+    bool has_sac = false;
+    hipets::SacBind sac{};
+    int sac_last_batch = 0;
+    DevBuf sac_ws, sac_one;
 };
 
 #pragma GCC visibility push(hidden)

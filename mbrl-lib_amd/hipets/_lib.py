@@ -48,6 +48,7 @@ MAX_OBS_COLUMNS = 512
 KERNEL_CLASSES = ("generic", "hidden_static", "fused", "wide", "bf16")  # HIPETS_KERNEL_*
 REDUCE = {"mean": 0, "mean_std": 1, "min": 2, "max": 3, "worst_k": 4}  # HIPETS_REDUCE_*
 POLICY_MAX_OBS, POLICY_MAX_HIDDEN, POLICY_MAX_ACT = 512, 1024, 32  # HIPETS_POLICY_MAX_*
+SAC_N_PTRS, SAC_MAX_BATCH = 78, 1024  # HIPETS_SAC_N_PTRS, HIPETS_SAC_MAX_BATCH
 
 
 class RewardTermC(C.Structure):  # hipets_reward_term
@@ -236,6 +237,11 @@ SYMBOLS = {
     "hipets_policy_geometry": _sig("e batch:i32 row_tiles:i32* lds_bytes:i32*"),
     "hipets_compact_transitions": _sig("e obs action next_obs rewards dones accum_dones n:i32 obs_dim:i32 act_dim:i32 staging cap:i64 offset "
                                        "count_out stream"),
+    "hipets_sac_bind": _sig("e obs_dim:i32 act_dim:i32 hidden:i32 tuning:i32 gamma:f64 tau:f64 target_entropy:f64 target_update_interval:i32 "
+                            "adam:f64* ptrs n_ptrs:i32"),
+    "hipets_sac_update": _sig("e batch batch_size:i32 eps_next eps_cur update_index:i64 step_critic:i64 step_policy:i64 step_alpha:i64 "
+                              "lr_critic:f64 lr_policy:f64 lr_alpha:f64 result stream"),
+    "hipets_sac_forward_taps": _sig("e batch_size:i32 q1 q2 y log_pi_next log_pi stream"),
     "hipets_timing_enable": _sig("e on:i32"),
     "hipets_timing_read": _sig("e launches:i64* total_ms:f64* reset:i32"),
 }

@@ -732,6 +732,48 @@ class Engine:
         self._call("hipets_compact_transitions", obs=obs, action=action, next_obs=next_obs, rewards=rewards, dones=dones, accum_dones=accum_dones,
                    n=N, obs_dim=od, act_dim=ad, staging=staging, cap=cap, offset=offset, count_out=count_out)
 
+    # ---- SAC updates (hipets_sac_bind / hipets_sac_update / hipets_sac_forward_taps) -----------------------------------------
+    def sac_bind(self, dims, tuning: bool, gamma: float, tau: float, target_entropy: float, target_update_interval: int, adam, ptrs):
+        """Tell the engine where a SAC agent's tensors live (hipets_sac_bind): ``dims`` = (obs_dim, act_dim, hidden); ``adam`` the
+        three optimizers' (beta1, beta2, eps), critic / policy / alpha; ``ptrs`` the ``_lib.SAC_N_PTRS`` device addresses in the
+        header's order (0 = absent).  The tensors are updated in place by :meth:`sac_update`; the caller keeps them alive."""
+        adam = np.ascontiguousarray(np.asarray(adam, dtype=np.float64).reshape(-1))
+        ptrs = np.ascontiguousarray(np.asarray(ptrs, dtype=np.uint64).reshape(-1))
+        if adam.size != 9:
+            raise ValueError("adam must hold (beta1, beta2, eps) of three optimizers")
+        self.sac_owner = self.sac_dims = None  # (a refused bind leaves no agent in the engine)
+        with torch.cuda.device(self.device):
+            self._query("hipets_sac_bind", obs_dim=int(dims[0]), act_dim=int(dims[1]), hidden=int(dims[2]), tuning=int(bool(tuning)),
+                        gamma=float(gamma), tau=float(tau), target_entropy=float(target_entropy), target_update_interval=int(target_update_interval),
+                        adam=adam.ctypes.data_as(C.POINTER(C.c_double)), ptrs=ptrs, n_ptrs=int(ptrs.size))
+        self.sac_dims = tuple(int(v) for v in dims)
+
+    def sac_update(self, batch: torch.Tensor, eps_next: torch.Tensor, eps_cur: torch.Tensor, update_index: int, steps, lrs, result: torch.Tensor):
+        """One SAC update on the bound agent (hipets_sac_update), asynchronous on the current stream.  ``batch`` f32 [B, 2 obs + act + 2]
+        (state, action, next_state, reward, mask), ``eps_next`` / ``eps_cur`` f32 [B, act], ``steps`` / ``lrs`` = the Adam steps taken
+        before and the learning rates of (critic, policy, alpha), ``result`` f32 [8] -- all device tensors but the scalars."""
+        dims = getattr(self, "sac_dims", None)
+        if dims is None:
+            raise HipetsError("Engine.sac_bind() has not been called")
+        obs, act, _ = dims
+        if not isinstance(batch, torch.Tensor) or batch.ndim != 2:
+            raise ValueError("batch must be a [B, 2 obs + act + 2] tensor")
+        B = int(batch.shape[0])
+        _check_dev(batch, torch.float32, self.device, "batch", (B, 2 * obs + act + 2))
+        _check_dev(eps_next, torch.float32, self.device, "eps_next", (B, act))
+        _check_dev(eps_cur, torch.float32, self.device, "eps_cur", (B, act))
+        _check_dev(result, torch.float32, self.device, "result", numel=8)
+        self._call("hipets_sac_update", batch=batch, batch_size=B, eps_next=eps_next, eps_cur=eps_cur, update_index=int(update_index),
+                   step_critic=int(steps[0]), step_policy=int(steps[1]), step_alpha=int(steps[2]), lr_critic=float(lrs[0]),
+                   lr_policy=float(lrs[1]), lr_alpha=float(lrs[2]), result=result)
+
+    def sac_forward_taps(self, batch_size: int) -> Dict[str, torch.Tensor]:
+        """Intermediates of the last :meth:`sac_update` (of ``batch_size`` rows): q1, q2, y, log_pi_next, log_pi, f32 [B] each."""
+        names = ("q1", "q2", "y", "log_pi_next", "log_pi")
+        out = {n: torch.empty(int(batch_size), dtype=torch.float32, device=self.device) for n in names}
+        self._call("hipets_sac_forward_taps", batch_size=int(batch_size), **out)
+        return out
+
     def timing_enable(self, on=True):
         """True / 1: time every rollout-kernel launch; k > 1: every k-th launch; False / 0: off."""
         self._query("hipets_timing_enable", on=int(on))
