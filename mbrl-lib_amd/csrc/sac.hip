@@ -172,7 +172,10 @@ __global__ __launch_bounds__(kSacThreads) void sac_policy_tail_kernel(const SacP
         a.tanh_x[o] = y;
         a.sech2_x[o] = omy;
         const float dlt = x - mean;
-        float l = -(dlt * dlt) / (2.f * (std * std)) - logf(std) - 0.91893853320467274178f;  // Normal.log_prob
+        // Normal.log_prob.  log(std) is the clamped log_std itself: logf(expf(ls)) came out below ls by 3e-8 per action dim on average
+        // (the device's expf rounds to one side more often than the other), a bias that a mean over the batch -- the logged entropy, the
+        // gradient of alpha -- keeps in full
+        float l = -(dlt * dlt) / (2.f * (std * std)) - ls - 0.91893853320467274178f;
         l -= logf(a.scale[d] * omy + kSacEpsilon);                                           // model.py:103
         lp += l;
     }

@@ -1,6 +1,7 @@
 """TEST HELPER (not collected): our own restatement of one SAC update (mbrl/third_party/pytorch_sac_pranz24/sac.py:76-173 with
 model.py's GaussianPolicy / QNetwork) from explicit weight arrays in torch autograd, in the reference's op order, in float32 or
-float64 (the dtype of the arrays it is given), with torch.optim.Adam written out by hand (train_restatement.adam_);
+float64 (the dtype of the arrays it is given), with torch.optim.Adam written out by hand (train_restatement.adam_), each of the three
+optimizers with its own settings, step count and (for a resumed run) starting moments;
 
 plus a small SAC-shaped agent (TinySAC: the attributes hipets.SACUpdater reads, and a stock-torch ``update_parameters`` over
 torch.optim.Adam) so that the GPU tests run where mbrl is not installed, the shared cases, and the condition every case's inputs
@@ -20,9 +21,14 @@ import train_restatement as tr
 POLICY = ("pw1", "pb1", "pw2", "pb2", "pwm", "pbm", "pws", "pbs")
 CRITIC = tuple(f"c{k}{i}" for i in range(1, 7) for k in "wb")  # cw1, cb1, .. cw6, cb6 (1-3 = Q1, 4-6 = Q2)
 TARGET = tuple("t" + n[1:] for n in CRITIC)
+MOMENTS = POLICY + CRITIC + ("log_alpha",)  # the trained tensors: what has Adam moments
 LOG_SIG_MIN, LOG_SIG_MAX, EPSILON = -20.0, 2.0, 1e-6
 HP = dict(gamma=0.99, tau=0.005, lr=3e-4, alpha=0.2, betas=(0.9, 0.999), eps=1e-8)
 KINK_MARGIN = 1e-4
+# A starting optimizer state spreads its elements' moment scales over this many decades below the gradient's rms (start_state).  All at
+# one scale, sqrt(v) >> eps everywhere and exchanging two optimizers' eps (1e-8 / 1e-7) moves no parameter by the 1e-7 floor of
+# train_restatement.check; a trained network holds quiet units whose moments have decayed, and there eps decides the step.
+START_DECADES = 4.0
 
 
 # ---- the restatement ----------------------------------------------------------------------------------------------------------------
@@ -59,17 +65,31 @@ def q_forward(p, names, state, action, rec=None):
     return out
 
 
+OPTIMIZERS = ("critic", "policy", "alpha")
+
+
+def adam_settings(adam=None, hp=HP):
+    """{"critic" | "policy" | "alpha": {"lr", "betas", "eps"}}: ``hp``'s for every optimizer, overridden by what ``adam`` names"""
+    out = {which: dict(lr=hp["lr"], betas=hp["betas"], eps=hp["eps"]) for which in OPTIMIZERS}
+    for which, own in (adam or {}).items():
+        out[which].update(own)
+    return out
+
+
 def _adam_group(st, names, grads, which, lr, hp):
     st["steps"][which] += 1
     for n, g in zip(names, grads):
         tr.adam_(st["p"][n], g, st["m"][n], st["v"][n], st["steps"][which], lr, betas=hp["betas"], eps=hp["eps"])
 
 
-def update(st, batch, eps_next, eps_cur, updates, hp, interval=1, tuning=True, target_entropy=None):
+def update(st, batch, eps_next, eps_cur, updates, hp, interval=1, tuning=True, target_entropy=None, adam=None, lrs=None):
     """One update in place on ``st`` = {"p": parameters by name (+ "log_alpha"), "m" / "v": Adam moments, "steps": {"critic",
     "policy", "alpha"}, "alpha": the coefficient in use, "scale" / "bias": the action rescaling}.  ``batch`` = (state, action,
-    next_state, reward [B, 1], mask [B, 1]) in st's dtype.  Returns the results and taps, and under "kinks" the arguments of every
-    kink of the update."""
+    next_state, reward [B, 1], mask [B, 1]) in st's dtype.  ``adam``: every optimizer's own settings (adam_settings; None = hp's for
+    all three); ``lrs``: this update's learning rates (critic, policy, alpha) in place of the settings' (a scheduler).  Returns the
+    results and taps, and under "kinks" the arguments of every kink of the update."""
+    adam = adam_settings(hp=hp) if adam is None else adam
+    lr = dict(zip(OPTIMIZERS, lrs)) if lrs is not None else {which: adam[which]["lr"] for which in OPTIMIZERS}
     p = st["p"]
     state, action, next_state, reward, mask = batch
     rec = {"relu": [], "clamp": [], "min": []}
@@ -84,7 +104,7 @@ def update(st, batch, eps_next, eps_cur, updates, hp, interval=1, tuning=True, t
     l1, l2 = F.mse_loss(q1, y), F.mse_loss(q2, y)
     grads = torch.autograd.grad(l1 + l2, [cp[n] for n in CRITIC])
     with torch.no_grad():
-        _adam_group(st, CRITIC, grads, "critic", hp["lr"], hp)
+        _adam_group(st, CRITIC, grads, "critic", lr["critic"], adam["critic"])
     pp = {n: p[n].clone().requires_grad_(True) for n in POLICY}
     pi, lp = policy_sample(pp, state, eps_cur, st["scale"], st["bias"], rec)
     q1p, q2p = q_forward(p, CRITIC, state, pi, rec)
@@ -92,13 +112,13 @@ def update(st, batch, eps_next, eps_cur, updates, hp, interval=1, tuning=True, t
     policy_loss = (alpha * lp - torch.min(q1p, q2p)).mean()
     grads = torch.autograd.grad(policy_loss, [pp[n] for n in POLICY])
     with torch.no_grad():
-        _adam_group(st, POLICY, grads, "policy", hp["lr"], hp)
+        _adam_group(st, POLICY, grads, "policy", lr["policy"], adam["policy"])
         if tuning:
             la = p["log_alpha"].clone().requires_grad_(True)
             with torch.enable_grad():
                 alpha_loss = -(la * (lp + target_entropy).detach()).mean()
                 (g,) = torch.autograd.grad(alpha_loss, [la])
-            _adam_group(st, ["log_alpha"], [g], "alpha", hp["lr"], hp)
+            _adam_group(st, ["log_alpha"], [g], "alpha", lr["alpha"], adam["alpha"])
             st["alpha"] = p["log_alpha"].exp()
             alpha_out = st["alpha"].reshape(())
         else:
@@ -143,9 +163,10 @@ def _layer(g, x, n_out, sigma):
     return w, sign * 0.05 * sigma
 
 
-def make_inputs(obs, act, hid, B, seed, n_updates=1, sigma=None, clamp=False):
+def make_inputs(obs, act, hid, B, seed, n_updates=1, sigma=None, clamp=False, start_draws=None):
     """float64 parameters and ``n_updates`` batches with their normal tables for a shape; ``clamp``: log_std head biases past both
-    bounds of the clamp on the first and the last action dim."""
+    bounds of the clamp on the first and the last action dim.  ``start_draws``: a dict that receives, per trained tensor, the unit
+    draws of a starting optimizer state (start_state), drawn after everything else so that no other draw moves."""
     g = torch.Generator().manual_seed(seed)
     rn = lambda *s: torch.randn(*s, generator=g, dtype=torch.float64)  # noqa: E731
     batches = []
@@ -177,14 +198,39 @@ def make_inputs(obs, act, hid, B, seed, n_updates=1, sigma=None, clamp=False):
     p["log_alpha"] = torch.full((1,), math.log(0.3), dtype=torch.float64)
     scale = 0.5 + torch.rand(act, generator=g, dtype=torch.float64)
     bias = rn(act) * 0.1
+    if start_draws is not None:
+        for n in MOMENTS:
+            start_draws[n] = (rn(*p[n].shape),) + tuple(torch.rand(*p[n].shape, generator=g, dtype=torch.float64) for _ in range(2))
     return p, batches, scale, bias
 
 
-def fresh_state(p, scale, bias, dtype, device="cpu", alpha=HP["alpha"]):
+def fresh_state(p, scale, bias, dtype, device="cpu", alpha=HP["alpha"], start=None):
+    """``start``: {"steps": the optimizers' step counts, "m" / "v": float64 moments by name} to resume from, instead of a new optimizer"""
     ps = {n: t.to(device, dtype).clone() for n, t in p.items()}
-    moments = POLICY + CRITIC + ("log_alpha",)
-    return dict(p=ps, m={n: torch.zeros_like(ps[n]) for n in moments}, v={n: torch.zeros_like(ps[n]) for n in moments},
-                steps=dict(critic=0, policy=0, alpha=0), alpha=alpha, scale=scale.to(device, dtype), bias=bias.to(device, dtype))
+    if start is None:
+        m, v = ({n: torch.zeros_like(ps[n]) for n in MOMENTS} for _ in range(2))
+        steps = dict(critic=0, policy=0, alpha=0)
+    else:
+        m, v = ({n: start[k][n].to(device, dtype).clone() for n in MOMENTS} for k in ("m", "v"))
+        steps = dict(start["steps"])
+    return dict(p=ps, m=m, v=v, steps=steps, alpha=alpha, scale=scale.to(device, dtype), bias=bias.to(device, dtype))
+
+
+def start_state(case, steps, draws):
+    """A resumed optimizer state for ``case``: the step counts ``steps`` and, per trained tensor, moments at the scale of that tensor's
+    gradient in the case's first update (g, taken from the float64 restatement of a new optimizer's first step, m = 0.1 g).  Per
+    element s = rms(g) 10^(-START_DECADES U(0, 1)), exp_avg = s N(0, 1), exp_avg_sq = s^2 U(0.25, 1.25): strictly positive, and
+    m / sqrt(v) of order one and not saturated in every element."""
+    p, batches, scale, bias = case["inputs"]
+    st = fresh_state(p, scale, bias, torch.float64)
+    update(st, batch_tensors(batches[0], torch.float64), batches[0]["eps_next"], batches[0]["eps_cur"], case["first_update"], HP,
+           interval=case["interval"], tuning=case["tuning"], target_entropy=case["target_entropy"])
+    m, v = {}, {}
+    for n in MOMENTS:
+        g = st["m"][n] / (1.0 - HP["betas"][0])
+        s = max(g.pow(2).mean().sqrt().item(), 1e-6) * 10.0 ** (-START_DECADES * draws[n][2])
+        m[n], v[n] = draws[n][0] * s, (draws[n][1] + 0.25) * s ** 2
+    return dict(steps=dict(steps), m=m, v=v)
 
 
 def batch_tensors(b, dtype, reverse_mask=True):
@@ -197,13 +243,15 @@ def restate(case, dtype, eps=None, reverse_rows=False):
     of the case's own normal tables.  ``reverse_rows``: every batch in reverse row order -- the same update with every contraction
     over the batch (the weight gradients, the means) summed the other way round; per-row outputs come back in the case's order."""
     p, batches, scale, bias = case["inputs"]
-    st = fresh_state(p, scale, bias, dtype)
+    st = fresh_state(p, scale, bias, dtype, start=case["start"])
+    adam, lrs = adam_settings(case["adam"]), case["lrs"]
     outs = []
     flip = (lambda t: t.flip(0)) if reverse_rows else (lambda t: t)
     for u, b in enumerate(batches):
         e_next, e_cur = eps[u] if eps is not None else (b["eps_next"], b["eps_cur"])
         out = update(st, tuple(flip(t) for t in batch_tensors(b, dtype)), flip(torch.as_tensor(e_next).to(dtype)), flip(torch.as_tensor(e_cur).to(dtype)),
-                     case["first_update"] + u, HP, interval=case["interval"], tuning=case["tuning"], target_entropy=-float(case["shape"][1]))
+                     case["first_update"] + u, HP, interval=case["interval"], tuning=case["tuning"], target_entropy=case["target_entropy"],
+                     adam=adam, lrs=lrs[u] if lrs is not None else None)
         for k in ("q1", "q2", "y", "log_pi_next", "log_pi"):
             out[k] = flip(out[k])
         outs.append(out)
@@ -236,28 +284,94 @@ CASES = {
     "clamp": dict(shape=(5, 3, 16, 17), seed=2, clamp=True),
     "twenty_i1": dict(shape=(5, 2, 16, 17), seed=0, sigma=3.0, n_updates=20, interval=1),
     "twenty_i3": dict(shape=(5, 2, 16, 17), seed=0, sigma=3.0, n_updates=20, interval=3, first_update=1),
+    # the batch's row stride W = 2 obs + act + 2 a multiple of 4 (16-byte loads of the state rows), batches past 256
+    "s27_8_64_257": dict(shape=(27, 8, 64, 257), seed=25, sigma=3.0),   # W = 64: vector loads with a ragged tail (K = 27), 17 row tiles
+    "s11_4_32_1024": dict(shape=(11, 4, 32, 1024), seed=0, sigma=5.0),  # W = 28, the largest batch
+    "s3_4_20_273": dict(shape=(3, 4, 20, 273), seed=1, sigma=3.0),      # W = 12, K = 3 below one vector group
 }
+# three optimizers that share no number (the policy's beta1 <= 0.5 takes the other branch of Tensor.lerp_), resumed from non-zero
+# moments at three different step counts, and a target entropy that is not -act
+RESUMED_ADAM = dict(critic=dict(lr=3e-4, betas=(0.9, 0.999), eps=1e-8), policy=dict(lr=1e-3, betas=(0.3, 0.95), eps=1e-6),
+                    alpha=dict(lr=5e-4, betas=(0.8, 0.99), eps=1e-7))
+RESUMED_STEPS = dict(critic=7, policy=3, alpha=11)
+_LRS = tuple(RESUMED_ADAM[which]["lr"] for which in ("critic", "policy", "alpha"))
+CASES["resumed"] = dict(shape=(5, 2, 16, 17), seed=0, sigma=3.0, adam=RESUMED_ADAM, start_steps=RESUMED_STEPS, target_entropy=-1.25)
+# ... and three updates from there, a scheduler halving the policy's learning rate before the third
+CASES["resumed_three"] = dict(CASES["resumed"], seed=0, n_updates=3, interval=2, lrs=(_LRS, _LRS, (_LRS[0], 0.5 * _LRS[1], _LRS[2])))
 ONE_UPDATE = [n for n in CASES if n.startswith("s")]
-RECORDED = ("s1_1_1_1", "s5_2_15_15", "s5_2_16_16", "s17_6_17_17", "fixed_alpha", "clamp")  # the cases tests/golden/sac_update_cases.npz holds
+RECORDED = ("s1_1_1_1", "s5_2_15_15", "s5_2_16_16", "s17_6_17_17", "fixed_alpha", "clamp", "resumed")  # the cases tests/golden/sac_update_cases.npz holds
 _BUILT = {}
+
+
+def complete_case(name, spec):
+    """``spec`` with every optional field at its default, its inputs and (with "start_steps") its starting optimizer state"""
+    c = dict(spec)
+    for key, default in (("sigma", None), ("clamp", False), ("tuning", True), ("n_updates", 1), ("interval", 1), ("first_update", 0),
+                         ("adam", None), ("start_steps", None), ("lrs", None), ("target_entropy", -float(c["shape"][1]))):
+        c.setdefault(key, default)
+    c["name"] = name
+    draws = {} if c["start_steps"] is not None else None
+    c["inputs"] = make_inputs(*c["shape"], c["seed"], c["n_updates"], c["sigma"], c["clamp"], start_draws=draws)
+    c["start"] = start_state(c, c["start_steps"], draws) if draws is not None else None
+    return c
+
+
+# every exchange of one per-optimizer quantity between two optimizers (a kernel that reads the policy's beta2 where the alpha
+# optimizer's is meant computes the case with those two exchanged)
+SWAPS = [(field, a, b) for field in ("lr", "beta1", "beta2", "eps", "step") for a, b in (("critic", "policy"), ("policy", "alpha"), ("critic", "alpha"))]
+
+
+def swapped(case, field, a, b):
+    """``case`` with ``field`` of the optimizers ``a`` and ``b`` exchanged"""
+    adam = {which: dict(own, betas=list(own["betas"])) for which, own in adam_settings(case["adam"]).items()}
+    start = dict(case["start"], steps=dict(case["start"]["steps"]))
+    if field == "step":
+        start["steps"][a], start["steps"][b] = start["steps"][b], start["steps"][a]
+    elif field in ("beta1", "beta2"):
+        i = int(field[-1]) - 1
+        adam[a]["betas"][i], adam[b]["betas"][i] = adam[b]["betas"][i], adam[a]["betas"][i]
+    else:
+        adam[a][field], adam[b][field] = adam[b][field], adam[a][field]
+    lrs = None
+    if case["lrs"] is not None:  # (a schedule names its learning rates itself)
+        order = {"lr": {a: b, b: a}}.get(field, {})
+        lrs = [tuple(u[OPTIMIZERS.index(order.get(which, which))] for which in OPTIMIZERS) for u in case["lrs"]]
+    return dict(case, adam=adam, start=start, lrs=lrs)
+
+
+def allowance(f32, f64, f32_others=()):
+    """What train_restatement.check allows between a kernel's result and ``f64``"""
+    d_all = [tr.dist(f32, f64)] + [tr.dist(t, f64) for t in f32_others]
+    d_32 = max(d_all) if max(d_all) > 4 * min(d_all) + 1e-7 else d_all[0]
+    return 4 * d_32 + 1e-7
+
+
+def swap_separation(case, field, a, b):
+    """(what, ratio): over every trained tensor's parameter and moments after the case's updates, the largest distance of the
+    float64 restatement with the exchange from the one without, in units of train_restatement.check's allowance for that quantity.
+    Kernels that make the exchange land within their own error of the exchanged result; that error is what the allowance bounds.
+    So a ratio above 2 means check must refuse them on that quantity."""
+    other, _ = restate(swapped(case, field, a, b), torch.float64)
+    best = ("", 0.0)
+    for kind in ("p", "m", "v"):
+        for n in MOMENTS:
+            ratio = tr.dist(other[kind][n], case["f64"][kind][n]) / allowance(case["f32"][kind][n], case["f64"][kind][n], [case["f32r"][kind][n]])
+            best = max(best, (f"{kind} {n}", ratio), key=lambda t: t[1])
+    return best
 
 
 def build_case(name):
     """The case's inputs and both restatements, computed once per process and shared (nobody edits them)."""
     if name not in _BUILT:
-        c = dict(CASES[name])
-        c.setdefault("sigma", None)
-        c.setdefault("clamp", False)
-        c.setdefault("tuning", True)
-        c.setdefault("n_updates", 1)
-        c.setdefault("interval", 1)
-        c.setdefault("first_update", 0)
-        c["name"] = name
-        c["inputs"] = make_inputs(*c["shape"], c["seed"], c["n_updates"], c["sigma"], c["clamp"])
+        c = complete_case(name, CASES[name])
         c["f64"], c["out64"] = restate(c, torch.float64)
         c["f32"], c["out32"] = restate(c, torch.float32)
         c["f32r"], c["out32r"] = restate(c, torch.float32, reverse_rows=True)  # (train_restatement.check's f32_others)
         check_kinks(c["out32"], c["out64"], name)
+        if c["start"] is not None:  # a condition on the case, like check_kinks: parity with it tells the optimizers' quantities apart
+            c["swaps"] = {s: swap_separation(c, *s) for s in SWAPS}
+            for s, (what, ratio) in c["swaps"].items():
+                assert ratio > 2.0, f"{name}: exchanging {s[0]} of {s[1]} and {s[2]} moves nothing past twice the rule's allowance ({what}: {ratio:.2f}x)"
         _BUILT[name] = c
     return _BUILT[name]
 
@@ -299,7 +413,9 @@ class TinySAC:
     """The attributes hipets.SACUpdater reads from a pytorch_sac_pranz24.SAC, and a stock-torch ``update_parameters`` over
     torch.optim.Adam in the order of sac.py:76-173 (the route an MBPO run takes without the update kernels)."""
 
-    def __init__(self, obs, act, hid, device="cpu", tuning=True, lr=HP["lr"], interval=1, alpha=HP["alpha"], deterministic=False):
+    def __init__(self, obs, act, hid, device="cpu", tuning=True, lr=HP["lr"], interval=1, alpha=HP["alpha"], deterministic=False,
+                 adam=None, target_entropy=None):
+        """``adam``: per-optimizer settings (adam_settings), written into each optimizer's ``param_groups[0]``"""
         self.gamma, self.tau, self.alpha = HP["gamma"], HP["tau"], alpha
         self.target_update_interval, self.automatic_entropy_tuning, self.device = interval, tuning, torch.device(device)
         self.critic = TinyQNetwork(obs, act, hid).to(device)
@@ -314,9 +430,25 @@ class TinySAC:
             self.policy = TinyGaussianPolicy(obs, act, hid).to(device)
         self.policy_optim = torch.optim.Adam(self.policy.parameters(), lr=lr)
         if tuning:
-            self.target_entropy = -float(act)
+            self.target_entropy = -float(act) if target_entropy is None else float(target_entropy)
             self.log_alpha = torch.zeros(1, requires_grad=True, device=device)
             self.alpha_optim = torch.optim.Adam([self.log_alpha], lr=lr)
+        for which, own in (adam or {}).items():
+            if which != "alpha" or tuning:
+                group = getattr(self, which + "_optim").param_groups[0]
+                group["lr"], group["betas"], group["eps"] = own["lr"], tuple(own["betas"]), own["eps"]
+
+    def load_start(self, start):
+        """A starting optimizer state (start_state) into ``optimizer.state``, laid out as torch.optim.Adam._init_group lays it out:
+        ``step`` a float scalar on the host, the moments float32 on the parameter's device"""
+        live = self.params()
+        for n in MOMENTS:
+            if n == "log_alpha" and not self.automatic_entropy_tuning:
+                continue
+            which = "alpha" if n == "log_alpha" else ("policy" if n[0] == "p" else "critic")
+            self.optimizer_of(n).state[live[n]] = dict(step=torch.tensor(float(start["steps"][which]), dtype=torch.float32),
+                                                       exp_avg=start["m"][n].to(self.device, torch.float32).clone(),
+                                                       exp_avg_sq=start["v"][n].to(self.device, torch.float32).clone())
 
     def load(self, p, scale, bias):
         """Parameters by restatement name (float64 arrays) into the modules"""
@@ -405,6 +537,9 @@ def agent_for(case, device):
     """A TinySAC at the case's initial parameters on ``device`` and the memory that replays its batches"""
     obs, act, hid, _ = case["shape"]
     p, batches, scale, bias = case["inputs"]
-    sac = TinySAC(obs, act, hid, device=device, tuning=case["tuning"], interval=case["interval"])
+    sac = TinySAC(obs, act, hid, device=device, tuning=case["tuning"], interval=case["interval"], adam=case["adam"],
+                  target_entropy=case["target_entropy"])
     sac.load(p, scale, bias)
+    if case["start"] is not None:
+        sac.load_start(case["start"])
     return sac, FixedMemory(batches)

@@ -55,6 +55,58 @@ def test_tiny_sac_takes_the_restatement_s_step():
     assert [float(v) for v in outs[0]["losses"]] == list(res)
 
 
+def test_tiny_sac_resumes_as_the_restatement_does():
+    """Three optimizers that share no setting, resumed from non-zero moments at three step counts: torch.optim.Adam in the stand-in
+    agent and the float32 restatement agree bit for bit -- parameters, both moments, the step counts and the 5-tuple."""
+    case = sr.build_case("resumed")
+    sac, memory = sr.agent_for(case, "cpu")
+    for which, own in sr.RESUMED_ADAM.items():
+        group = getattr(sac, which + "_optim").param_groups[0]
+        assert (group["lr"], tuple(group["betas"]), group["eps"]) == (own["lr"], own["betas"], own["eps"])
+    assert sac.target_entropy == case["target_entropy"] != -float(case["shape"][1])
+    B, act = case["shape"][3], case["shape"][1]
+    torch.manual_seed(7)
+    res = sac.update_parameters(memory, B, 0, None, reverse_mask=True)
+    torch.manual_seed(7)
+    eps = [(torch.empty(B, act).normal_(), torch.empty(B, act).normal_())]
+    st, outs = sr.restate(case, torch.float32, eps=eps)
+    live = sac.params()
+    for n, t in live.items():
+        assert torch.equal(t.detach(), st["p"][n]), n
+    for n in sr.MOMENTS:
+        state = sac.optimizer_of(n).state[live[n]]
+        which = "alpha" if n == "log_alpha" else ("policy" if n[0] == "p" else "critic")
+        assert torch.equal(state["exp_avg"], st["m"][n]) and torch.equal(state["exp_avg_sq"], st["v"][n]), n
+        assert float(state["step"]) == st["steps"][which] == sr.RESUMED_STEPS[which] + 1, n
+        assert not torch.equal(st["m"][n], case["start"]["m"][n].float()) and (case["start"]["v"][n] > 0).all()
+    assert [float(v) for v in outs[0]["losses"]] == list(res)
+
+
+@pytest.mark.parametrize("swap", sr.SWAPS, ids=lambda s: "-".join(s))
+def test_resumed_case_tells_the_optimizers_apart(swap):
+    """The condition that makes parity with "resumed" a check of the per-optimizer indexing: exchanging one quantity (a learning
+    rate, a beta, an eps, a step count) between two optimizers moves some parameter or moment of the float64 restatement by more than
+    twice what train_restatement.check allows there."""
+    for name in ("resumed", "resumed_three"):
+        what, ratio = sr.build_case(name)["swaps"][swap]
+        print(f"{name}: {swap}: {what} moves {ratio:.1f}x the allowance")
+        assert ratio > 2.0
+
+
+def test_allowance_is_the_rule_of_check():
+    g = torch.Generator().manual_seed(0)
+    f64 = torch.randn(50, generator=g, dtype=torch.float64)
+    near, far = f64 + 1e-6 * torch.randn(50, generator=g, dtype=torch.float64), f64 + 1e-4 * torch.randn(50, generator=g, dtype=torch.float64)
+    for f32, others in ((near, ()), (near, [far]), (far, [near]), (near, [near * (1 + 1e-7)])):
+        allow = sr.allowance(f32, f64, others)
+        at = f64.clone()
+        at[3] += allow * 0.999
+        sr.tr.check(at, f32, f64, "inside the allowance", others)
+        at[3] = f64[3] + allow * 1.001
+        with pytest.raises(AssertionError):
+            sr.tr.check(at, f32, f64, "past the allowance", others)
+
+
 def test_pack_sac_batch_and_the_reverse_mask_rule():
     g = np.random.default_rng(0)
     B, obs, act = 7, 3, 2
