@@ -804,6 +804,44 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
 int hipets_sac_forward_taps(hipets_engine* e, int32_t batch_size, float* q1, float* q2, float* y, float* log_pi_next, float* log_pi,
                             void* stream);
 
+/* ---- value-bootstrapped planning: the SAC critic and discounted returns with a terminal value ----
+ * Additive entry points: scalars and pointers only, no struct, HIPETS_ABI_VERSION stays.  Need no dynamics model.
+ *
+ * The critic is QNetwork.forward (mbrl/third_party/pytorch_sac_pranz24/model.py:36-61) on xu = [state, action]:
+ *   q1 = linear3(relu(linear2(relu(linear1(xu)))));  q2 = linear6(relu(linear5(relu(linear4(xu)))))
+ * All products are fp32 MFMA with fp32 accumulation, bias and relu fp32 op by op; xu is never written to memory (the kernel reads the
+ * two source arrays).  hipets_critic_set: `ptrs` is a HOST table of HIPETS_CRITIC_N_PTRS DEVICE pointers to contiguous f32 tensors in
+ * nn.Linear's layout -- linear1 .. linear6, weight then bias each; linear1 / linear4 [hidden, obs_dim + act_dim], linear2 / linear5
+ * [hidden, hidden], linear3 / linear6 [1, hidden] -- which it copies into the engine's own packed layout (a SNAPSHOT: call it again
+ * after the critic changed); it does not synchronise: the tensors must stay alive until the work enqueued on `stream` has run.
+ * 1 <= obs_dim <= 512, 1 <= hidden <= 1024, 1 <= act_dim <= 32 (the HIPETS_POLICY_MAX_* limits), n_ptrs == HIPETS_CRITIC_N_PTRS, no
+ * null pointer; anything else is HIPETS_ERR_INVALID_ARGUMENT and leaves the engine without a critic.                                */
+#define HIPETS_CRITIC_N_PTRS 12
+int hipets_critic_set(hipets_engine* e, int32_t obs_dim, int32_t act_dim, int32_t hidden, const void* ptrs, int32_t n_ptrs, void* stream);
+/* One launch: obs DEVICE [batch, obs_dim], actions DEVICE [batch, act_dim] -> q1, q2, qmin DEVICE [batch] f32, each optional (NULL = not
+ * wanted); batch >= 1.  qmin is torch.min(q1, q2) (sac.py:101) as a select without fminf: q1 where q1 < q2 or q1 is NaN, else q2 --
+ * the smaller value, NaN when either is NaN (torch.min's rule; fminf would drop the NaN), q2's bits on a tie.
+ * A row's arithmetic does not depend on the batch it arrives in: row r of any call equals the one-row call on (obs[r], actions[r]).   */
+int hipets_critic_q(hipets_engine* e, const float* obs, const float* actions, int32_t batch, float* q1, float* q2, float* qmin, void* stream);
+/* Launch geometry of hipets_critic_q for `batch` rows of the critic set last, the actor's rule (hipets_policy_geometry): a workgroup
+ * owns 16 * row_tiles rows, row_tiles = the largest of 4, 2, 1 whose two activation buffers -- 16 rows x (max(pad16(obs_dim +
+ * act_dim), pad16(hidden)) + pad16(hidden) + 8) floats per row tile; Q1 and Q2 run one after the other through the same buffers --
+ * fit the LDS opt-in limit, no more than the batch needs; lds_bytes = its dynamic LDS.                                              */
+int hipets_critic_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles, int32_t* lds_bytes);
+/* hipets_trajectory_returns with a discount and an optional terminal value (POLO / LOOP / TD-MPC style planning: a short horizon plus
+ * a learned tail).  rewards, dones, pop, horizon, num_particles, the outputs and the particle reduction as there; terminal_values
+ * DEVICE [B] f32 or NULL.  Per row, for t = 0 .. H-1 in order, every line ONE float32 operation (no fused multiply-add):
+ *     disc = 1; total = 0; terminated = false
+ *     r = terminated ? 0 : rewards[t][row];  terminated |= dones[t][row] != 0
+ *     total = total + disc * r;  disc = disc * gamma
+ *   and, with terminal_values:  total = total + (terminated ? 0 : disc * terminal_values[row])
+ * Both zeroings are selects.  A row that terminated at any step, the last included, gets no bootstrap.  With gamma == 1 and
+ * terminal_values == NULL all three outputs are hipets_trajectory_returns' bits.  gamma outside [0, 1] or NaN is
+ * HIPETS_ERR_INVALID_ARGUMENT.  Needs no model.                                                                                   */
+int hipets_discounted_returns(hipets_engine* e, const float* rewards, const uint8_t* dones, const float* terminal_values, float gamma,
+                              int32_t pop, int32_t horizon, int32_t num_particles, float* returns, float* row_totals, int32_t* first_done,
+                              void* stream);
+
 /* ---- instrumentation (bench.py roofline leg) ----------------------------------------------- */
 /* on = 1: every rollout-kernel launch carries a start / stop hipEvent pair on its dispatch packet; on = k > 1: every
  * k-th launch does (a completion signal per packet costs a few microseconds between back-to-back short launches -- the

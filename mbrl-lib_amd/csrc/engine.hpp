@@ -1,5 +1,5 @@
-// engine.hpp -- private to the host units of the C ABI (include/hipets.h): engine.hip, model.hip, rollout.hip, plan.hip, comm.hip and
-// train.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
+// engine.hpp -- private to the host units of the C ABI (include/hipets.h): engine.hip, model.hip, rollout.hip, plan.hip, comm.hip,
+// train.hip, policy.hip, sac.hip and value.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
 // Host code only; nothing declared here is part of the ABI (hidden visibility).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -144,6 +144,10 @@ struct hipets_engine {
     hipets::SacBind sac{};
     int sac_last_batch = 0;
     DevBuf sac_ws, sac_one;
+    // SAC critic (hipets_critic_set / hipets_critic_q, value.hip): the packed layers of Q1 and Q2
+    bool has_critic = false;
+    int critic_obs = 0, critic_act = 0, critic_hid = 0;
+    DevBuf critic_w, critic_b;
 };
 
 #pragma GCC visibility push(hidden)

@@ -10,6 +10,7 @@
 #include "common.hpp"
 #include "engine.hpp"
 #include "lds_optin.hpp"
+#include "policy_layer.hpp"
 
 namespace hipets {
 
@@ -17,19 +18,9 @@ namespace {
 
 // ---------------------------------------------------------------------------------------------
 // The actor.  A workgroup owns 16 R consecutive rows; their activations live in two LDS buffers that the layers alternate between
-// (A: obs, then h2; B: h1, then the heads), the packed weights stream from L2.  Every product runs on v_mfma_f32_16x16x4_f32 through
-// the compiler's builtin (its own hazard handling: no asm MFMA here).  A wave owns column tiles; for one column tile it keeps the R
-// row tiles' accumulators, so a B fragment (4 coalesced loads of 16 consecutive floats per k-block of 16) feeds 4 R MFMAs.
-// Inside a k-block of 16 lane group q = lane >> 4 supplies k = 16 kb + 4 q + s to MFMA s, for A and B alike (any assignment of the 16
-// k to the 4 x 4 (step, group) slots sums the same products): the A operand of the four steps is ONE ds_read_b128.
-//   packed weights  W[k][n], k < Kp (K rounded up to 16), n < Np (N rounded up to 16), zeros outside K x N (hipets_policy_set)
-//   LDS rows        ld = columns + 4 floats with columns a multiple of 16: ld = 4 (mod 16), so the 16 rows x 4 groups of an A read and
-//                   the 4 row groups x 16 columns of a result store each fall on distinct banks
-// Padding needs no bounds test in the loops: obs columns past obs_dim and rows past the batch are loaded as zeros, a padded output
-// column is relu(0 + 0) = 0, which is what the next layer's padded k rows want.
+// (A: obs, then h2; B: h1, then the heads), the packed weights stream from L2.  The layer itself -- MFMA product, LDS layout, padding
+// rule -- is policy_layer.hpp's, shared with the critic kernel (value.hip).
 // ---------------------------------------------------------------------------------------------
-constexpr int kPolicyThreads = 512;
-constexpr int kPolicyWaves = kPolicyThreads / kWave;
 constexpr float kLogSigMin = -20.f, kLogSigMax = 2.f;  // LOG_SIG_MIN / LOG_SIG_MAX (pytorch_sac_pranz24/model.py:6-7)
 
 struct PolicyArgs {
@@ -55,49 +46,6 @@ __device__ __forceinline__ void policy_normals4(uint32_t row, uint32_t blk, unsi
                                      (uint32_t)(seed >> 32) ^ (uint32_t)(stream_id >> 32) ^ 0xAC7012ACu);
     box_muller(r4.x, r4.y, nrm[0], nrm[1]);
     box_muller(r4.z, r4.w, nrm[2], nrm[3]);
-}
-
-// out[16 R][np] = act(in[16 R][kp] W[kp][np] + bias): wave `wave` of kPolicyWaves runs column tiles wave, wave + kPolicyWaves, ...
-template <int R, bool kRelu>
-__device__ __forceinline__ void policy_layer(const float* __restrict__ in, const int ld_in, const int kp, const float* __restrict__ W,
-                                             const float* __restrict__ bias, const int np, float* __restrict__ out, const int ld_out, const int wave,
-                                             const int lane) {
-    const int r = lane & 15, q = lane >> 4;
-    for (int n0 = wave * kTile; n0 < np; n0 += kPolicyWaves * kTile) {
-        f32x4 c0[R], c1[R];
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-            c0[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            c1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-        const float* wp = W + (size_t)(4 * q) * np + n0 + r;
-        const float* ap = in + r * ld_in + 4 * q;
-#pragma unroll 2
-        for (int k0 = 0; k0 < kp; k0 += kKChunk) {
-            const float b0 = wp[0], b1 = wp[np], b2 = wp[2 * np], b3 = wp[3 * np];
-#pragma unroll
-            for (int i = 0; i < R; ++i) {
-                const f32x4 av = *reinterpret_cast<const f32x4*>(ap + i * kTile * ld_in);
-                c0[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], b0, c0[i], 0, 0, 0);
-                c1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], b1, c1[i], 0, 0, 0);
-                c0[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], b2, c0[i], 0, 0, 0);
-                c1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], b3, c1[i], 0, 0, 0);
-            }
-            wp += (size_t)kKChunk * np;
-            ap += kKChunk;
-        }
-        const float bc = bias[n0 + r];
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-            const f32x4 c = c0[i] + c1[i];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float v = c[j] + bc;
-                if (kRelu) v = v > 0.f ? v : 0.f;
-                out[(i * kTile + 4 * q + j) * ld_out + n0 + r] = v;
-            }
-        }
-    }
 }
 
 template <int R>
@@ -163,23 +111,12 @@ __global__ void policy_normals_kernel(float* out, int B, int act, unsigned long 
     }
 }
 
-// nn.Linear's [N, K] -> packed[k][col0 + n] of a zeroed [Kp][np] image
-__global__ void policy_pack_kernel(float* dst, const float* src, int K, int N, int np, int col0) {
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= (long long)K * N) return;
-    const int n = (int)(i / K), k = (int)(i - (long long)n * K);
-    dst[(size_t)k * np + col0 + n] = src[i];
-}
-
-inline int pad16(int x) { return (x + 15) & ~15; }
-
 struct PolicyGeo {
     int kp0, hp, nph, ld_a, ld_b, R;
     size_t lds;
 };
 
-// The R rule: the largest of 4, 2, 1 row tiles whose two activation buffers fit the opt-in LDS limit (more rows per workgroup =
-// fewer passes over the weights), cut down to what the batch fills.  A row's arithmetic does not depend on R.
+// The R rule is policy_layer.hpp's policy_row_tiles.
 PolicyGeo policy_geometry(const hipets_engine* e, long long batch) {
     PolicyGeo g{};
     g.kp0 = pad16(e->policy_obs);
@@ -188,11 +125,8 @@ PolicyGeo policy_geometry(const hipets_engine* e, long long batch) {
     g.ld_a = std::max(g.kp0, g.hp) + 4;
     g.ld_b = std::max(g.hp, g.nph) + 4;
     const size_t per_tile = (size_t)kTile * 4 * (size_t)(g.ld_a + g.ld_b);
-    int R = 4;
-    while (R > 1 && per_tile * R > e->lds_max) R >>= 1;
-    while (R > 1 && (long long)kTile * (R >> 1) >= batch) R >>= 1;
-    g.R = R;
-    g.lds = per_tile * R;
+    g.R = policy_row_tiles(per_tile, e->lds_max, batch);
+    g.lds = per_tile * g.R;
     return g;
 }
 

@@ -8,6 +8,7 @@
 #include "engine.hpp"
 #include "launch.hpp"
 #include "residency.hpp"
+#include "returns_kernel.hpp"
 #include "rollout_helpers.hpp"
 #include "rollout_smem.hpp"
 
@@ -554,22 +555,7 @@ int hipets_trajectory_returns(hipets_engine* e, const float* rewards, const uint
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);  // (the two-pass form below may run on the engine's row totals)
-    if (P <= kReturnsThreads) {
-        const int cpb = kReturnsThreads / P;  // whole candidates per workgroup
-        hipLaunchKernelGGL(trajectory_returns_kernel, dim3((unsigned)((pop + cpb - 1) / cpb)), dim3(kReturnsThreads), 0, st, rewards, dones, pop, H, P, cpb,
-                           e->reduce, returns, row_totals, first_done);
-        HCHECK(hipGetLastError());
-        return 0;
-    }
-    // a candidate's particles do not fit one workgroup: the row pass, then the particle means
-    if (!row_totals) {
-        if (e->totals.ensure((size_t)B * 4)) return 1;
-        row_totals = e->totals.as<float>();
-    }
-    hipLaunchKernelGGL(trajectory_returns_kernel, dim3((unsigned)((B + kReturnsThreads - 1) / kReturnsThreads)), dim3(kReturnsThreads), 0, st, rewards, dones,
-                       pop, H, P, 0, e->reduce, static_cast<float*>(nullptr), row_totals, first_done);
-    HCHECK(hipGetLastError());
-    return launch_particle_reduce(e, row_totals, returns, pop, P, st);
+    return launch_trajectory_returns<false>(e, rewards, dones, nullptr, 1.0f, pop, H, P, returns, row_totals, first_done, st);
 }
 
 int hipets_particle_reduce(hipets_engine* e, const float* totals, int32_t pop, int32_t num_particles, float* returns, void* stream) {

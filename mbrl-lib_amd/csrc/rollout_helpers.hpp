@@ -32,49 +32,6 @@ __global__ void particle_mean_kernel(const float* totals, float* returns, int po
     returns[c] = particle_value(totals + (size_t)c * P, 1, P, r);
 }
 
-// model_env.py:186-191 over a finished trajectory (hipets_trajectory_returns): rewards / dones [H, B] of rollouts whose reward and
-// termination were evaluated OUTSIDE the rollout kernel (Python callables over the traced states).  One thread per row, so the loads
-// of a step are coalesced over B; per row, in step order, the chain of rollout.hpp's end_step_for_row:
-//     r = term ? 0 : rewards[t][row];  term |= dones[t][row] != 0;  tot += r
-// (a select, like the reference's rewards[terminated] = 0: whatever a terminated row's reward holds, NaN included, adds exactly 0).
-// cand_per_block > 0: the workgroup owns candidates [blockIdx.x * cand_per_block, + cand_per_block) = cand_per_block * P consecutive
-// rows (<= kReturnsThreads); their totals go through LDS to the thread that runs candidate c's particle_value, as particle_mean_kernel
-// above does (the same rule: the same bits).  cand_per_block == 0 (P > kReturnsThreads): rows only, blockDim.x per workgroup,
-// into row_totals (never null then); the launcher runs particle_mean_kernel behind it.
-constexpr int kReturnsThreads = 256;
-__global__ __launch_bounds__(kReturnsThreads) void trajectory_returns_kernel(const float* __restrict__ rewards, const unsigned char* __restrict__ dones,
-                                                                             int pop, int H, int P, int cand_per_block, const ParticleReduce r,
-                                                                             float* __restrict__ returns, float* __restrict__ row_totals,
-                                                                             int* __restrict__ first_done) {
-    __shared__ float tot_s[kReturnsThreads];
-    const long long B = (long long)pop * P;
-    const int tid = threadIdx.x;
-    const int rows_here = cand_per_block > 0 ? cand_per_block * P : (int)blockDim.x;
-    const long long row = (long long)blockIdx.x * rows_here + tid;
-    if (tid < rows_here && row < B) {
-        float tot = 0.0f;
-        bool term = false;
-        int first = H;
-#pragma unroll 4
-        for (int t = 0; t < H; ++t) {
-            const size_t i = (size_t)t * (size_t)B + (size_t)row;
-            const float rw = rewards[i];
-            const bool d = dones[i] != 0;
-            const float r = term ? 0.0f : rw;
-            if (d && !term) first = t;
-            term = term || d;
-            tot += r;
-        }
-        tot_s[tid] = tot;
-        if (row_totals) row_totals[row] = tot;
-        if (first_done) first_done[row] = first;
-    }
-    if (cand_per_block == 0) return;
-    __syncthreads();
-    const long long c = (long long)blockIdx.x * cand_per_block + tid;
-    if (tid < cand_per_block && c < pop) returns[c] = particle_value(tot_s + tid * P, 1, P, r);
-}
-
 // Export of the FAST-mode member schedule (hipets_fast_schedule): sched[t][w] = the member slot workgroup w of nwg draws for step t
 // in its own prologue (common.hpp fast_member: one keyed bijection of the workgroup indices per step, cut into M equal runs -- the
 // reference's "each model gets exactly the same number of samples", gaussian_mlp.py:267-275, at 16 R-row granularity; fixed_model:

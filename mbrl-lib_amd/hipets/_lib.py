@@ -49,6 +49,7 @@ KERNEL_CLASSES = ("generic", "hidden_static", "fused", "wide", "bf16")  # HIPETS
 REDUCE = {"mean": 0, "mean_std": 1, "min": 2, "max": 3, "worst_k": 4}  # HIPETS_REDUCE_*
 POLICY_MAX_OBS, POLICY_MAX_HIDDEN, POLICY_MAX_ACT = 512, 1024, 32  # HIPETS_POLICY_MAX_*
 SAC_N_PTRS, SAC_MAX_BATCH = 78, 1024  # HIPETS_SAC_N_PTRS, HIPETS_SAC_MAX_BATCH
+CRITIC_N_PTRS = 12  # HIPETS_CRITIC_N_PTRS
 
 
 class RewardTermC(C.Structure):  # hipets_reward_term
@@ -242,6 +243,11 @@ SYMBOLS = {
     "hipets_sac_update": _sig("e batch batch_size:i32 eps_next eps_cur update_index:i64 step_critic:i64 step_policy:i64 step_alpha:i64 "
                               "lr_critic:f64 lr_policy:f64 lr_alpha:f64 result stream"),
     "hipets_sac_forward_taps": _sig("e batch_size:i32 q1 q2 y log_pi_next log_pi stream"),
+    "hipets_critic_set": _sig("e obs_dim:i32 act_dim:i32 hidden:i32 ptrs n_ptrs:i32 stream"),
+    "hipets_critic_q": _sig("e obs actions batch:i32 q1 q2 qmin stream"),
+    "hipets_critic_geometry": _sig("e batch:i32 row_tiles:i32* lds_bytes:i32*"),
+    "hipets_discounted_returns": _sig("e rewards dones terminal_values gamma:f32 pop:i32 horizon:i32 num_particles:i32 returns row_totals "
+                                      "first_done stream"),
     "hipets_timing_enable": _sig("e on:i32"),
     "hipets_timing_read": _sig("e launches:i64* total_ms:f64* reset:i32"),
 }

@@ -259,3 +259,54 @@ def pack_policy(policy):
             raise UnsupportedModelError(f"policy.{name} holds {v.numel()} values for {act_dim} action dims")
         out[name] = v.expand(act_dim)
     return (obs_dim, hidden, act_dim), {n: out[n] for n in POLICY_TENSORS}
+
+
+CRITIC_LAYERS = ("linear1", "linear2", "linear3", "linear4", "linear5", "linear6")  # hipets_critic_set's pointer table: weight, bias each
+
+
+def pack_critic(critic, obs_dim: Optional[int] = None):
+    """A ``QNetwork``-shaped module (pytorch_sac_pranz24/model.py:36-61: linear1..3 = Q1, linear4..6 = Q2) -> ((K, hidden), [the 12 LIVE
+    parameters, weight then bias per layer, detached]) with K = obs_dim + act_dim, the width of linear1's input.  ``obs_dim``: how K
+    splits (None: the split is not checked here).  Anything that is not shaped like a QNetwork, or whose sizes hipets_critic_set
+    refuses, raises UnsupportedModelError."""
+    from .model import UnsupportedModelError
+
+    layers = [getattr(critic, n, None) for n in CRITIC_LAYERS]
+    missing = [n for n, l in zip(CRITIC_LAYERS, layers)
+               if l is None or getattr(l, "weight", None) is None or getattr(l, "bias", None) is None or l.weight.ndim != 2]
+    if missing:
+        raise UnsupportedModelError(f"{type(critic).__name__} is not shaped like a QNetwork: no {', '.join(missing)} with a weight and a bias")
+    hidden, K = (int(v) for v in layers[0].weight.shape)
+    want = [(hidden, K), (hidden, hidden), (1, hidden)] * 2
+    for name, lin, shape in zip(CRITIC_LAYERS, layers, want):
+        if tuple(lin.weight.shape) != shape or tuple(lin.bias.shape) != (shape[0],):
+            raise UnsupportedModelError(f"QNetwork layer shapes do not chain: {name} is {tuple(lin.weight.shape)} with a bias of "
+                                        f"{tuple(lin.bias.shape)}, expected {shape} and ({shape[0]},)")
+    if not 1 <= hidden <= _lib.POLICY_MAX_HIDDEN or not 2 <= K <= _lib.POLICY_MAX_OBS + _lib.POLICY_MAX_ACT:
+        raise UnsupportedModelError(f"critic sizes (obs + act {K}, hidden {hidden}) outside the critic kernel's "
+                                    f"(<= {_lib.POLICY_MAX_OBS} + {_lib.POLICY_MAX_ACT}, <= {_lib.POLICY_MAX_HIDDEN})")
+    if obs_dim is not None:
+        check_critic_split(K, int(obs_dim), K - int(obs_dim))
+    tensors = []
+    for lin in layers:
+        tensors += [lin.weight.detach(), lin.bias.detach()]
+    return (K, hidden), tensors
+
+
+def check_discount(discount) -> float:
+    """``discount`` as a float in [0, 1] (what hipets_discounted_returns accepts), or ValueError"""
+    g = float(discount)
+    if not 0.0 <= g <= 1.0:  # (a NaN fails both comparisons)
+        raise ValueError(f"discount must be in [0, 1], got {discount!r}")
+    return g
+
+
+def check_critic_split(K: int, obs_dim: int, act_dim: int):
+    """(obs_dim, act_dim) against a critic whose linear1 takes K inputs and against the kernel's limits, or UnsupportedModelError"""
+    from .model import UnsupportedModelError
+
+    if obs_dim + act_dim != K:
+        raise UnsupportedModelError(f"the critic's linear1 takes {K} inputs, obs_dim + act_dim = {obs_dim} + {act_dim}")
+    if not (1 <= obs_dim <= _lib.POLICY_MAX_OBS and 1 <= act_dim <= _lib.POLICY_MAX_ACT):
+        raise UnsupportedModelError(f"critic sizes (obs {obs_dim}, act {act_dim}) outside the critic kernel's "
+                                    f"(<= {_lib.POLICY_MAX_OBS}, <= {_lib.POLICY_MAX_ACT})")

@@ -10,8 +10,8 @@ import torch
 
 from . import _lib
 from ._lib import CemParams, HipetsError
-from ._pack import (_check_dev, member_slots, pack_model_desc, pack_plan_trace, pack_planet_desc, pack_reward_terms,  # noqa: F401
-                    pack_policy, pack_rollout_opts, pack_train_desc)
+from ._pack import (_check_dev, check_critic_split, check_discount, member_slots, pack_critic, pack_model_desc, pack_plan_trace,  # noqa: F401
+                    pack_planet_desc, pack_reward_terms, pack_policy, pack_rollout_opts, pack_train_desc)
 from .model import ModelSpec
 from .reduce import ParticleReduce
 
@@ -61,6 +61,9 @@ class Engine:
         self.comm_group = None  # torch.distributed group of the communicator's ranks (hipets.dist.init_engine_comm)
         self.plan_mode = "fast"  # (the library's initial value; every fused plan sets its objective's mode: optimizers._prepare_fused)
         self.reduce = ParticleReduce()  # (the library's initial value, the mean; every objective sets its own: _Objective.bind_model)
+        # value-bootstrapped planning (hipets.value): the critic snapshot's sizes and its owner (a weakref to a SACCritic), and how many
+        # SAC updates this engine has run -- snapshots of an actor or a critic compare it
+        self.critic_dims, self.critic_owner, self.sac_updates = None, None, 0
         self._trace = None
 
     def close(self):
@@ -766,6 +769,9 @@ class Engine:
         self._call("hipets_sac_update", batch=batch, batch_size=B, eps_next=eps_next, eps_cur=eps_cur, update_index=int(update_index),
                    step_critic=int(steps[0]), step_policy=int(steps[1]), step_alpha=int(steps[2]), lr_critic=float(lrs[0]),
                    lr_policy=float(lrs[1]), lr_alpha=float(lrs[2]), result=result)
+        # the update kernels write the agent's parameters through raw pointers (no tensor's _version moves): snapshots of the actor or
+        # the critic compare this counter (hipets.value)
+        self.sac_updates += 1
 
     def sac_forward_taps(self, batch_size: int) -> Dict[str, torch.Tensor]:
         """Intermediates of the last :meth:`sac_update` (of ``batch_size`` rows): q1, q2, y, log_pi_next, log_pi, f32 [B] each."""
@@ -773,6 +779,73 @@ class Engine:
         out = {n: torch.empty(int(batch_size), dtype=torch.float32, device=self.device) for n in names}
         self._call("hipets_sac_forward_taps", batch_size=int(batch_size), **out)
         return out
+
+    # ---- value-bootstrapped planning (hipets_critic_* / hipets_discounted_returns) ----------------------------------------------
+    def critic_set(self, critic, obs_dim: int, act_dim: int):
+        """Snapshot a ``QNetwork``-shaped module's live weights into the engine (hipets_critic_set; ``_pack.pack_critic`` reads the
+        module or raises UnsupportedModelError).  Device to device where the critic is on this GPU.  Asynchronous.  Returns
+        (obs_dim, act_dim, hidden)."""
+        (K, hidden), tensors = pack_critic(critic)
+        check_critic_split(K, int(obs_dim), int(act_dim))
+        on_dev = [t.to(device=self.device, dtype=torch.float32).contiguous() for t in tensors]
+        table = np.array([t.data_ptr() for t in on_dev], dtype=np.uint64)
+        self.critic_dims = self.critic_owner = None  # (a refused set leaves no critic in the engine; a SACCritic that sets one claims the slot)
+        self._call("hipets_critic_set", obs_dim=int(obs_dim), act_dim=int(act_dim), hidden=hidden, ptrs=table, n_ptrs=int(table.size))
+        del on_dev  # (the copies are enqueued: torch's allocator frees in stream order)
+        self.critic_dims = (int(obs_dim), int(act_dim), hidden)
+        return self.critic_dims
+
+    def _critic_dims(self):
+        dims = self.critic_dims
+        if dims is None:
+            raise HipetsError("Engine.critic_set() has not been called")
+        return dims
+
+    def critic_q(self, obs: torch.Tensor, actions: torch.Tensor, *, q1: bool = True, q2: bool = True, qmin: bool = True):
+        """The critic's forward for ``obs`` f32 [B, obs_dim] and ``actions`` f32 [B, act_dim] on the device -> (q1, q2, qmin), f32 [B]
+        each (hipets_critic_q, one launch; an output not wanted is None).  qmin = torch.min(q1, q2)."""
+        obs_dim, act_dim, _ = self._critic_dims()
+        dev = self.device
+        if not isinstance(obs, torch.Tensor) or obs.ndim != 2 or int(obs.shape[0]) < 1:
+            raise ValueError("obs must be a [B, obs_dim] tensor with B >= 1")
+        B = int(obs.shape[0])
+        _check_dev(obs, torch.float32, dev, "obs", (B, obs_dim))
+        _check_dev(actions, torch.float32, dev, "actions", (B, act_dim))
+        out = [torch.empty(B, dtype=torch.float32, device=dev) if want else None for want in (q1, q2, qmin)]
+        self._call("hipets_critic_q", obs=obs, actions=actions, batch=B, q1=out[0], q2=out[1], qmin=out[2])
+        return tuple(out)
+
+    def critic_geometry(self, batch: int):
+        """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of a :meth:`critic_q` of ``batch`` rows."""
+        self._critic_dims()
+        r, lds = C.c_int32(), C.c_int32()
+        self._query("hipets_critic_geometry", batch=int(batch), row_tiles=C.byref(r), lds_bytes=C.byref(lds))
+        return r.value, lds.value
+
+    def discounted_returns(self, rewards: torch.Tensor, dones: torch.Tensor, pop: int, num_particles: int, *, gamma: float = 1.0,
+                           terminal_values: Optional[torch.Tensor] = None, row_totals: bool = False, first_done: bool = False):
+        """:meth:`trajectory_returns` with a discount and an optional bootstrap (hipets_discounted_returns): per row
+        ``sum_t gamma^t r_t`` up to and including the first terminating step, plus ``gamma^H terminal_values[row]`` (f32 [B]) for a
+        row that never terminated; then the engine's particle reduction.  Arguments and results as there."""
+        dev = self.device
+        if not isinstance(rewards, torch.Tensor) or rewards.ndim != 2:
+            raise ValueError("rewards must be a [H, B] tensor")
+        H, B = (int(v) for v in rewards.shape)
+        if pop < 1 or num_particles < 1 or pop * num_particles != B:
+            raise ValueError(f"rewards holds {B} rows per step, pop x num_particles = {pop} x {num_particles}")
+        gamma = check_discount(gamma)
+        _check_dev(rewards, torch.float32, dev, "rewards")
+        if isinstance(dones, torch.Tensor) and dones.dtype == torch.bool:
+            dones = dones.view(torch.uint8)  # (one byte per element, 0 / 1)
+        _check_dev(dones, torch.uint8, dev, "dones", (H, B))
+        if terminal_values is not None:
+            _check_dev(terminal_values, torch.float32, dev, "terminal_values", numel=B)
+        out = torch.empty(pop, dtype=torch.float32, device=dev)
+        tot = torch.empty(B, dtype=torch.float32, device=dev) if row_totals else None
+        first = torch.empty(B, dtype=torch.int32, device=dev) if first_done else None
+        self._call("hipets_discounted_returns", rewards=rewards, dones=dones, terminal_values=terminal_values, gamma=gamma, pop=int(pop), horizon=H,
+                   num_particles=int(num_particles), returns=out, row_totals=tot, first_done=first)
+        return (out, tot, first) if (row_totals or first_done) else out
 
     def timing_enable(self, on=True):
         """True / 1: time every rollout-kernel launch; k > 1: every k-th launch; False / 0: off."""

@@ -531,6 +531,7 @@ class CallableTrajectoryEvalFn(_RolloutObjective):
     k of ``seed``).  The trajectory of a call takes ``H * B * (obs + 1) * 4`` bytes; a call beyond ``max_trajectory_bytes`` raises."""
 
     _allow_custom_fns = True
+    _needs_callable = True  # (a subclass that adds something else to the evaluation runs without one: hipets.value)
     kernel_mode = None  # not a fused-plan target: the optimizers run their per-iteration loops and call it; batched agents refuse it
 
     def __init__(self, model, num_particles: int, reward_fn=None, termination_fn=None, engine: Optional[Engine] = None,
@@ -539,7 +540,7 @@ class CallableTrajectoryEvalFn(_RolloutObjective):
         super().__init__(model, num_particles, engine, mode, seed, device, rng, particle_reduce)
         self.reward_fn = reward_fn if reward_fn is not None else self.spec.custom_reward_fn
         self.termination_fn = termination_fn if termination_fn is not None else self.spec.custom_termination_fn
-        if self.reward_fn is None and self.termination_fn is None:
+        if self._needs_callable and self.reward_fn is None and self.termination_fn is None:
             raise ValueError("neither a reward nor a termination callable: this model's objective is fully fused, use HipTrajectoryEvalFn")
         self.check_rowwise, self.max_trajectory_bytes = bool(check_rowwise), int(max_trajectory_bytes)
         self._rowwise_checked = False
@@ -554,14 +555,16 @@ class CallableTrajectoryEvalFn(_RolloutObjective):
             done = _rowwise_output(self.termination_fn(act_rows, obs_rows), n, "termination_fn", boolean=True)
         return rew, done
 
-    def _trajectory(self, initial_state, action_sequences, details):
-        a = self._prep(action_sequences)
-        self.calls += 1
+    def _rewards_and_dones(self, a: torch.Tensor, initial_state):
+        """One traced rollout of this call's stream and what the evaluation reduces: (next_obs [H, B, obs], rewards f32 [H, B], dones
+        bool [H, B]) -- the callables' results where they are set, else the kernel's own rewards / the restated closed-form termination."""
         pop, H, A = a.shape
         P = self.num_particles
         B = pop * P
         next_obs, rewards = self._traced_rollout(a, initial_state)
         obs_rows = next_obs.view(H * B, self.spec.obs_dim)
+        if self.reward_fn is None and self.termination_fn is None:
+            return next_obs, rewards, closed_form_dones(self.spec, obs_rows).reshape(H, B).contiguous()
         act_rows = a.transpose(0, 1).unsqueeze(2).expand(H, pop, P, A).reshape(H * B, A)  # model_env.py:179-182, all steps at once
         rew, done = self._evaluate_callables(act_rows, obs_rows)
         if self.check_rowwise and not self._rowwise_checked:
@@ -573,6 +576,13 @@ class CallableTrajectoryEvalFn(_RolloutObjective):
             self._rowwise_checked = True
         rewards = rewards if rew is None else rew.to(torch.float32).reshape(H, B).contiguous()
         dones = (closed_form_dones(self.spec, obs_rows) if done is None else done).reshape(H, B).contiguous()
+        return next_obs, rewards, dones
+
+    def _trajectory(self, initial_state, action_sequences, details):
+        a = self._prep(action_sequences)
+        self.calls += 1
+        pop, P = a.shape[0], self.num_particles
+        next_obs, rewards, dones = self._rewards_and_dones(a, initial_state)
         if not details:
             return self.engine.trajectory_returns(rewards, dones, pop, P)
         returns, row_totals, first_done = self.engine.trajectory_returns(rewards, dones, pop, P, row_totals=True, first_done=True)
@@ -664,9 +674,18 @@ def make_eval_fn(model, num_particles: int, callables: str = "steps", **kw):
     :class:`CallableTrajectoryEvalFn` (the callables must be row-wise: they run once over all steps' rows).
     Without a ``mode=`` argument the objective runs ``mode='device'``: the reference's TS1 semantics (one balanced permutation
     of all rows per step, gaussian_mlp.py:201-211), every draw made in-kernel; ``mode='fast'`` is the opt-in block-balanced variant.
-    ``particle_reduce=`` (every objective): a :class:`ParticleReduce` or 'mean' / 'min' / 'max', the reduction over the particles."""
+    ``particle_reduce=`` (every objective): a :class:`ParticleReduce` or 'mean' / 'min' / 'max', the reduction over the particles.
+    ``discount=`` / ``terminal_value=agent`` / ``target_critic=``: any of them returns a :class:`hipets.ValueTrajectoryEvalFn` --
+    discounted returns, with an agent ``discount^H min(Q1, Q2)`` of its critic at its actor's mean action as the tail -- for closed-form
+    and row-wise callable rewards / terminations alike (``callables`` is not read then)."""
     if callables not in ("steps", "trajectory"):
         raise ValueError(f"callables must be 'steps' or 'trajectory', got {callables!r}")
+    value_kw = {k: kw.pop(k) for k in ("discount", "terminal_value", "target_critic") if k in kw}
+    if value_kw:  # hipets.value: discounted returns, the agent's critic as the tail (a PlaNet model raises ValueError there)
+        from .value import ValueTrajectoryEvalFn
+
+        return ValueTrajectoryEvalFn(model, num_particles, agent=value_kw.get("terminal_value"), discount=value_kw.get("discount", 1.0),
+                                     target_critic=bool(value_kw.get("target_critic", False)), **kw)
     if isinstance(model, PlaNetSpec) or is_planet_model(getattr(model, "dynamics_model", model)):
         return PlaNetTrajectoryEvalFn(model, num_particles, **kw)
     try:
