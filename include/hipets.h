@@ -767,6 +767,31 @@ int hipets_compact_transitions(hipets_engine* e, const float* obs, const float* 
                                const uint8_t* dones, uint8_t* accum_dones, int32_t n, int32_t obs_dim, int32_t act_dim, float* staging,
                                int64_t cap, int64_t* offset, int32_t* count_out, void* stream);
 
+/* ---- a device-resident SAC replay buffer: the populate's ring form and the batch gather ----
+ * Additive entry points: scalars and pointers only, no struct, HIPETS_ABI_VERSION stays.  Need no dynamics model.
+ *
+ * `ring` is a replay buffer's storage, DEVICE f32 [capacity * (2 obs_dim + act_dim + 2)]: the staging area's five arrays over
+ * `capacity` rows, one behind the other -- obs [capacity, obs_dim], action [capacity, act_dim], next_obs [capacity, obs_dim], reward
+ * [capacity], done [capacity] (0.0f or 1.0f).
+ *
+ * hipets_ring_compact_transitions is hipets_compact_transitions followed by mbrl.util.ReplayBuffer.add_batch (replay_buffer.py:553-599)
+ * for one rollout step: inputs as there; `cursor` is a DEVICE int64[2] = (cur_idx, num_stored).  The k-th row with accum_dones == 0,
+ * in row order, lands at ring row (cur_idx + k) % capacity, every float a plain copy.  Afterwards cur_idx = (cur_idx + kept) %
+ * capacity, num_stored = min(num_stored + kept, capacity) -- add_batch's rule whenever num_stored >= cur_idx, which add_batch
+ * maintains --, *count_out (DEVICE int32) = kept and accum_dones |= dones.  A cur_idx outside [0, capacity) is folded into it first.
+ * n > capacity is HIPETS_ERR_INVALID_ARGUMENT (nothing is launched).  The same three ordered launches (the count kernel is shared);
+ * nothing waits on another workgroup, no atomics; all row arithmetic is 64-bit.                                                     */
+int hipets_ring_compact_transitions(hipets_engine* e, const float* obs, const float* action, const float* next_obs, const float* rewards,
+                                    const uint8_t* dones, uint8_t* accum_dones, int32_t n, int32_t obs_dim, int32_t act_dim, float* ring,
+                                    int64_t capacity, int64_t* cursor, int32_t* count_out, void* stream);
+/* One launch: indices DEVICE int64 [n_rows] -> out DEVICE f32 [n_rows, 2 obs_dim + act_dim + 2], row j = (obs[i], action[i],
+ * next_obs[i], reward[i], mask) of ring row i = indices[j]: the batch layout hipets_sac_update reads (any number of batches behind
+ * each other).  mask = done when reverse_mask == 0, else (done == 0) ? 1.0f : 0.0f (mask_batch.logical_not(), sac.py:93-95).  Plain
+ * copies.  An index outside [0, capacity) reads nothing and makes its whole output row quiet NaN; no error is raised.  n_rows >= 1,
+ * 1 <= obs_dim, act_dim <= 4096, capacity >= 1; anything else is HIPETS_ERR_INVALID_ARGUMENT.                                      */
+int hipets_replay_gather(hipets_engine* e, const float* ring, int64_t capacity, int32_t obs_dim, int32_t act_dim, const int64_t* indices,
+                         int64_t n_rows, int32_t reverse_mask, float* out, void* stream);
+
 /* ---- SAC updates: SAC.update_parameters (mbrl/third_party/pytorch_sac_pranz24/sac.py:76-173) on the device ----
  * Additive entry points: scalars and pointers only, no struct, HIPETS_ABI_VERSION stays.  Needs no dynamics model.
  *

@@ -2,7 +2,10 @@
 // Gaussian actor's forward (hipets_policy_set / _act / _normals / _geometry) and the stable compaction of a step's transitions into a
 // device staging area (hipets_compact_transitions).  The kernels, then the entry points.
 //   policy_act_kernel          GaussianPolicy.forward / sample (third_party/pytorch_sac_pranz24/model.py:88-108), one launch per call
-//   compact_{count,scan,scatter}_kernel   mbpo.py:53-63: numpy's boolean indexing with ~accum_dones as three ordered launches
+//   compact_{count,scan,scatter}_kernel   mbpo.py:53-63: numpy's boolean indexing with ~accum_dones as three ordered launches; the
+//                                         scan and the scatter also in a RING form (hipets_ring_compact_transitions: the kept rows go
+//                                         where ReplayBuffer.add_batch puts them)
+//   replay_gather_kernel                  rows of a ring by index -> the [n, 2 obs + act + 2] batch hipets_sac_update reads
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -166,9 +169,14 @@ __global__ __launch_bounds__(kCompactThreads) void compact_count_kernel(const un
     }
 }
 
-// counts [nb] -> exclusive offsets in place; *base_out = *offset (the step's first staging row); *offset += kept; *count_out = kept
+// counts [nb] -> exclusive offsets in place; *base_out = *offset (the step's first staging row); *offset += kept; *count_out = kept.
+// kRing: `offset` is a replay buffer's (cur_idx, num_stored) over `cap` rows; *base_out = cur_idx, then ReplayBuffer.add_batch's
+// bookkeeping (replay_buffer.py:598-599): cur_idx = (cur_idx + kept) % cap, num_stored = min(num_stored + kept, cap).  A cur_idx
+// outside [0, cap) is folded into it first, so the scatter's rows are in bounds whatever the cursor held.
+template <bool kRing>
 __global__ __launch_bounds__(kScanThreads) void compact_scan_kernel(int* __restrict__ counts, int nb, long long* __restrict__ offset,
-                                                                    int* __restrict__ count_out, long long* __restrict__ base_out) {
+                                                                    int* __restrict__ count_out, long long* __restrict__ base_out,
+                                                                    long long cap) {
     __shared__ int wtot[kScanThreads / kWave];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     int carry = 0;  // (kept rows <= n < 2^31)
@@ -194,13 +202,23 @@ __global__ __launch_bounds__(kScanThreads) void compact_scan_kernel(int* __restr
         __syncthreads();
     }
     if (tid == 0) {
-        const long long base = *offset;
-        *base_out = base;
-        *offset = base + carry;
+        if constexpr (kRing) {
+            long long base = offset[0] % cap;
+            if (base < 0) base += cap;
+            *base_out = base;
+            offset[0] = (base + carry) % cap;
+            offset[1] = min(max(offset[1], 0ll) + carry, cap);
+        } else {
+            const long long base = *offset;
+            *base_out = base;
+            *offset = base + carry;
+        }
         *count_out = carry;
     }
 }
 
+// kRing: row k of the step lands at ring row (*base_p + k) % cap (k < n <= cap and *base_p < cap: one subtraction); nothing is dropped
+template <bool kRing>
 __global__ __launch_bounds__(kCompactThreads) void compact_scatter_kernel(const float* __restrict__ obs, const float* __restrict__ action,
                                                                           const float* __restrict__ next_obs, const float* __restrict__ rewards,
                                                                           const unsigned char* __restrict__ dones, unsigned char* __restrict__ accum,
@@ -220,7 +238,7 @@ __global__ __launch_bounds__(kCompactThreads) void compact_scatter_kernel(const 
     long long d = -1;
     if (keep) {
         d = *base_p + offs[blockIdx.x] + before + __popcll(m & ((1ull << lane) - 1ull));
-        if (d >= cap) d = -1;
+        if (d >= cap) d = kRing ? d - cap : -1;
     }
     dst_s[tid] = d;
     __syncthreads();
@@ -240,6 +258,48 @@ __global__ __launch_bounds__(kCompactThreads) void compact_scatter_kernel(const 
         else staging[o_done + dst] = dones[row] ? 1.f : 0.f;
     }
     if (i < n && dones[i]) accum[i] = 1;
+}
+
+// ---------------------------------------------------------------------------------------------
+// The gather: out[j] = (obs[i], action[i], next_obs[i], reward[i], mask) of ring row i = indices[j], the batch row hipets_sac_update
+// reads.  A block owns kGatherRows output rows, their indices staged in LDS, and walks them as ONE flat (row, column) range: the
+// output write is contiguous over the whole block, each segment read contiguous within its row.  Plain copies.  An index outside
+// [0, cap) reads nothing: its row is quiet NaN.
+// ---------------------------------------------------------------------------------------------
+constexpr int kGatherThreads = 256;
+constexpr int kGatherRows = 16;
+
+__global__ __launch_bounds__(kGatherThreads) void replay_gather_kernel(const float* __restrict__ ring, long long cap, int od, int ad,
+                                                                       const long long* __restrict__ indices, long long n_rows, int reverse_mask,
+                                                                       float* __restrict__ out) {
+    __shared__ long long idx_s[kGatherRows];
+    const int tid = threadIdx.x;
+    const long long row0 = (long long)blockIdx.x * kGatherRows;
+    const int rows_here = (int)min((long long)kGatherRows, n_rows - row0);
+    if (tid < rows_here) {
+        const long long i = indices[row0 + tid];
+        idx_s[tid] = (i >= 0 && i < cap) ? i : -1;
+    }
+    __syncthreads();
+    const int W = 2 * od + ad + 2;
+    const long long o_act = cap * od, o_nobs = cap * (od + ad), o_rew = cap * (2 * od + ad), o_done = o_rew + cap;
+    float* __restrict__ dst = out + row0 * W;
+    for (int t = tid; t < rows_here * W; t += kGatherThreads) {
+        const int r = t / W, c = t - r * W;
+        const long long i = idx_s[r];
+        float v = __int_as_float(0x7fc00000);
+        if (i >= 0) {
+            if (c < od) v = ring[i * od + c];
+            else if (c < od + ad) v = ring[o_act + i * ad + (c - od)];
+            else if (c < 2 * od + ad) v = ring[o_nobs + i * od + (c - od - ad)];
+            else if (c == 2 * od + ad) v = ring[o_rew + i];
+            else {
+                const float done = ring[o_done + i];
+                v = reverse_mask ? (done == 0.f ? 1.f : 0.f) : done;
+            }
+        }
+        dst[t] = v;
+    }
 }
 
 }  // namespace
@@ -361,9 +421,52 @@ int hipets_compact_transitions(hipets_engine* e, const float* obs, const float* 
     long long* base = e->compact_counts.as<long long>();
     int* counts = reinterpret_cast<int*>(base + 1);
     hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)nb), dim3(kCompactThreads), 0, st, accum_dones, n, counts);
-    hipLaunchKernelGGL(compact_scan_kernel, dim3(1), dim3(kScanThreads), 0, st, counts, nb, reinterpret_cast<long long*>(offset), count_out, base);
-    hipLaunchKernelGGL(compact_scatter_kernel, dim3((unsigned)nb), dim3(kCompactThreads), 0, st, obs, action, next_obs, rewards, dones, accum_dones, n,
-                       obs_dim, act_dim, staging, (long long)cap, base, counts);
+    hipLaunchKernelGGL(compact_scan_kernel<false>, dim3(1), dim3(kScanThreads), 0, st, counts, nb, reinterpret_cast<long long*>(offset), count_out, base,
+                       (long long)cap);
+    hipLaunchKernelGGL(compact_scatter_kernel<false>, dim3((unsigned)nb), dim3(kCompactThreads), 0, st, obs, action, next_obs, rewards, dones, accum_dones,
+                       n, obs_dim, act_dim, staging, (long long)cap, base, counts);
+    HCHECK(hipGetLastError());
+    return 0;
+}
+
+int hipets_ring_compact_transitions(hipets_engine* e, const float* obs, const float* action, const float* next_obs, const float* rewards,
+                                    const uint8_t* dones, uint8_t* accum_dones, int32_t n, int32_t obs_dim, int32_t act_dim, float* ring,
+                                    int64_t capacity, int64_t* cursor, int32_t* count_out, void* stream) {
+    if (!e) return fail("null engine");
+    if (!obs || !action || !next_obs || !rewards || !dones || !accum_dones || !ring || !cursor || !count_out) return fail("null argument");
+    if (n < 1) return fail("bad row count");
+    if (obs_dim < 1 || obs_dim > 4096 || act_dim < 1 || act_dim > 4096) return fail("obs_dim / act_dim outside [1, 4096]");
+    if (capacity < 1) return fail("ring capacity < 1");
+    if ((int64_t)n > capacity) return fail("a step of %d rows does not fit a ring of %lld", n, (long long)capacity);
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HCHECK(hipSetDevice(e->device));
+    ENTER_STREAM(e, st);
+    const int nb = (int)(((long long)n + kCompactThreads - 1) / kCompactThreads);
+    if (e->compact_counts.ensure(8 + (size_t)nb * 4)) return 1;
+    long long* base = e->compact_counts.as<long long>();
+    int* counts = reinterpret_cast<int*>(base + 1);
+    hipLaunchKernelGGL(compact_count_kernel, dim3((unsigned)nb), dim3(kCompactThreads), 0, st, accum_dones, n, counts);
+    hipLaunchKernelGGL(compact_scan_kernel<true>, dim3(1), dim3(kScanThreads), 0, st, counts, nb, reinterpret_cast<long long*>(cursor), count_out, base,
+                       (long long)capacity);
+    hipLaunchKernelGGL(compact_scatter_kernel<true>, dim3((unsigned)nb), dim3(kCompactThreads), 0, st, obs, action, next_obs, rewards, dones, accum_dones,
+                       n, obs_dim, act_dim, ring, (long long)capacity, base, counts);
+    HCHECK(hipGetLastError());
+    return 0;
+}
+
+int hipets_replay_gather(hipets_engine* e, const float* ring, int64_t capacity, int32_t obs_dim, int32_t act_dim, const int64_t* indices,
+                         int64_t n_rows, int32_t reverse_mask, float* out, void* stream) {
+    if (!e) return fail("null engine");
+    if (!ring || !indices || !out) return fail("null argument");
+    if (obs_dim < 1 || obs_dim > 4096 || act_dim < 1 || act_dim > 4096) return fail("obs_dim / act_dim outside [1, 4096]");
+    if (capacity < 1) return fail("ring capacity < 1");
+    const long long nb = ((long long)n_rows + kGatherRows - 1) / kGatherRows;
+    if (n_rows < 1 || nb > 0x7fffffffll) return fail("bad row count");
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    HCHECK(hipSetDevice(e->device));
+    ENTER_STREAM(e, st);
+    hipLaunchKernelGGL(replay_gather_kernel, dim3((unsigned)nb), dim3(kGatherThreads), 0, st, ring, (long long)capacity, obs_dim, act_dim,
+                       reinterpret_cast<const long long*>(indices), (long long)n_rows, reverse_mask, out);
     HCHECK(hipGetLastError());
     return 0;
 }

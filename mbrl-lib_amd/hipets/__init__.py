@@ -52,6 +52,7 @@ from .propagation import (  # noqa: F401
 )
 from .trainer import ModelTrainer, make_model_trainer  # noqa: F401
 from .mbpo import SACActor, SACUpdater, make_sac_updater, rollout_model_and_populate_sac_buffer  # noqa: F401
+from .replay import DeviceReplayBuffer, maybe_replace_sac_buffer  # noqa: F401
 from .value import SACCritic, ValueTrajectoryEvalFn  # noqa: F401
 from . import dist  # noqa: F401
 

@@ -238,6 +238,9 @@ SYMBOLS = {
     "hipets_policy_geometry": _sig("e batch:i32 row_tiles:i32* lds_bytes:i32*"),
     "hipets_compact_transitions": _sig("e obs action next_obs rewards dones accum_dones n:i32 obs_dim:i32 act_dim:i32 staging cap:i64 offset "
                                        "count_out stream"),
+    "hipets_ring_compact_transitions": _sig("e obs action next_obs rewards dones accum_dones n:i32 obs_dim:i32 act_dim:i32 ring capacity:i64 "
+                                            "cursor count_out stream"),
+    "hipets_replay_gather": _sig("e ring capacity:i64 obs_dim:i32 act_dim:i32 indices n_rows:i64 reverse_mask:i32 out stream"),
     "hipets_sac_bind": _sig("e obs_dim:i32 act_dim:i32 hidden:i32 tuning:i32 gamma:f64 tau:f64 target_entropy:f64 target_update_interval:i32 "
                             "adam:f64* ptrs n_ptrs:i32"),
     "hipets_sac_update": _sig("e batch batch_size:i32 eps_next eps_cur update_index:i64 step_critic:i64 step_policy:i64 step_alpha:i64 "

@@ -711,6 +711,14 @@ class Engine:
         2)`` elements holding five arrays one behind the other -- obs [cap, obs_dim], action [cap, act_dim], next_obs [cap, obs_dim],
         reward [cap], done [cap] (``hipets.mbpo.staging_views`` splits it) -- at row ``offset`` (int64 [1], advanced); ``count_out``
         int32 [1] = the rows kept.  All tensors on the device; ``rewards`` f32 and ``dones`` bool / uint8 of N elements."""
+        N, od, ad, dones, cap = self._check_step_rows(obs, action, next_obs, rewards, dones, accum_dones, staging, cap, "staging", "cap")
+        _check_dev(offset, torch.int64, self.device, "offset", numel=1)
+        _check_dev(count_out, torch.int32, self.device, "count_out", numel=1)
+        self._call("hipets_compact_transitions", obs=obs, action=action, next_obs=next_obs, rewards=rewards, dones=dones, accum_dones=accum_dones,
+                   n=N, obs_dim=od, act_dim=ad, staging=staging, cap=cap, offset=offset, count_out=count_out)
+
+    def _check_step_rows(self, obs, action, next_obs, rewards, dones, accum_dones, area, cap, area_name, cap_name):
+        """The argument checks the two compactions share: (N, obs_dim, act_dim, dones as uint8, cap)"""
         dev = self.device
         if not isinstance(obs, torch.Tensor) or obs.ndim != 2 or not isinstance(action, torch.Tensor) or action.ndim != 2:
             raise ValueError("obs / action must be [N, obs_dim] / [N, act_dim] tensors")
@@ -726,14 +734,52 @@ class Engine:
             dones = dones.view(torch.uint8)
         _check_dev(dones, torch.uint8, dev, "dones", numel=N)
         _check_dev(accum_dones, torch.uint8, dev, "accum_dones", (N,))
-        _check_dev(staging, torch.float32, dev, "staging")
+        _check_dev(area, torch.float32, dev, area_name)
         cap = int(cap)
-        if cap < 0 or staging.numel() < cap * (2 * od + ad + 2):
-            raise ValueError(f"staging must hold cap * (2 obs_dim + act_dim + 2) = {cap} * {2 * od + ad + 2} floats, got {staging.numel()}")
-        _check_dev(offset, torch.int64, dev, "offset", numel=1)
-        _check_dev(count_out, torch.int32, dev, "count_out", numel=1)
-        self._call("hipets_compact_transitions", obs=obs, action=action, next_obs=next_obs, rewards=rewards, dones=dones, accum_dones=accum_dones,
-                   n=N, obs_dim=od, act_dim=ad, staging=staging, cap=cap, offset=offset, count_out=count_out)
+        if cap < 0 or area.numel() < cap * (2 * od + ad + 2):
+            raise ValueError(f"{area_name} must hold {cap_name} * (2 obs_dim + act_dim + 2) = {cap} * {2 * od + ad + 2} floats, got {area.numel()}")
+        return N, od, ad, dones, cap
+
+    # ---- a device-resident SAC replay buffer (hipets_ring_compact_transitions / hipets_replay_gather; hipets.DeviceReplayBuffer) ----
+    def ring_compact_transitions(self, obs, action, next_obs, rewards, dones, accum_dones, ring, capacity, cursor, count_out):
+        """:meth:`compact_transitions` followed by ``ReplayBuffer.add_batch`` for one rollout step (hipets_ring_compact_transitions):
+        the k-th row whose ``accum_dones`` is 0 lands at row ``(cur_idx + k) % capacity`` of ``ring``, a flat f32 buffer of at least
+        ``capacity * (2 obs_dim + act_dim + 2)`` elements in the staging area's five-array layout over ``capacity`` rows; ``cursor``
+        int64 [2] = (cur_idx, num_stored), advanced as ``add_batch`` advances them; ``count_out`` int32 [1] = the rows kept;
+        ``accum_dones |= dones``.  All tensors on the device.  N > capacity is refused by the library (ERR_INVALID_ARGUMENT)."""
+        N, od, ad, dones, capacity = self._check_step_rows(obs, action, next_obs, rewards, dones, accum_dones, ring, capacity, "ring", "capacity")
+        _check_dev(cursor, torch.int64, self.device, "cursor", numel=2)
+        _check_dev(count_out, torch.int32, self.device, "count_out", numel=1)
+        self._call("hipets_ring_compact_transitions", obs=obs, action=action, next_obs=next_obs, rewards=rewards, dones=dones,
+                   accum_dones=accum_dones, n=N, obs_dim=od, act_dim=ad, ring=ring, capacity=capacity, cursor=cursor, count_out=count_out)
+
+    def replay_gather(self, ring, capacity, obs_dim, act_dim, indices, reverse_mask: bool = False, out: Optional[torch.Tensor] = None):
+        """Rows of ``ring`` (the layout of :meth:`ring_compact_transitions`) by index -> f32 [n, 2 obs_dim + act_dim + 2] on the device,
+        row j = (obs[i], action[i], next_obs[i], reward[i], mask) of row i = indices[j], the batch layout :meth:`sac_update` reads
+        (hipets_replay_gather, one launch); mask = done, or ``1 - done`` under ``reverse_mask``.  ``indices``: an int64 device tensor of
+        n elements -- an index outside [0, capacity) then gives a row of NaN, no error --, or host integers (a numpy array, a list),
+        which are range-checked here (ValueError) and uploaded."""
+        dev = self.device
+        capacity, od, ad = int(capacity), int(obs_dim), int(act_dim)
+        W = 2 * od + ad + 2
+        _check_dev(ring, torch.float32, dev, "ring")
+        if capacity < 1 or od < 1 or ad < 1 or ring.numel() < capacity * W:
+            raise ValueError(f"ring must hold capacity * (2 obs_dim + act_dim + 2) = {capacity} * {W} floats, got {ring.numel()}")
+        if not isinstance(indices, torch.Tensor):
+            host = np.ascontiguousarray(np.asarray(indices).reshape(-1))
+            if host.size and (not np.issubdtype(host.dtype, np.integer) or host.min() < 0 or host.max() >= capacity):
+                raise ValueError(f"indices must be integers in [0, {capacity})")
+            indices = torch.from_numpy(host.astype(np.int64, copy=False)).to(dev)
+        n = int(indices.numel())
+        _check_dev(indices, torch.int64, dev, "indices", numel=n)
+        if out is None:
+            out = torch.empty(n, W, dtype=torch.float32, device=dev)
+        else:
+            _check_dev(out, torch.float32, dev, "out", (n, W))
+        if n:
+            self._call("hipets_replay_gather", ring=ring, capacity=capacity, obs_dim=od, act_dim=ad, indices=indices, n_rows=n,
+                       reverse_mask=int(bool(reverse_mask)), out=out)
+        return out
 
     # ---- SAC updates (hipets_sac_bind / hipets_sac_update / hipets_sac_forward_taps) -----------------------------------------
     def sac_bind(self, dims, tuning: bool, gamma: float, tau: float, target_entropy: float, target_update_interval: int, adam, ptrs):

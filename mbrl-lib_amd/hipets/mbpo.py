@@ -1,12 +1,14 @@
 """MBPO's agent side on the device (mbrl/algorithms/mbpo.py): the model rollouts into the SAC buffer (:31-63) -- the SAC actor as one HIP
 launch, the model step as the existing ``hipets_step`` launch, and a compaction of the step's live rows into a device staging area,
 three plainly ordered pieces per rollout step, one device -> host copy per call -- and SAC's updates (:258-275), a fixed sequence of HIP
-launches per update that works in place on the agent's live torch tensors.
+launches per update that works in place on the agent's live torch tensors.  With a ``hipets.DeviceReplayBuffer`` as the SAC buffer the
+rows never leave the device: the populate compacts straight into its ring, the updates gather their batches from it in one launch.
 
     agent = hipets.SACActor(sac_agent)                    # drop-in for SACAgent.act, numpy in / numpy out
     hipets.rollout_model_and_populate_sac_buffer(model_env, replay_buffer, sac_agent, sac_buffer, True, rollout_length, batch_size)
     updater = hipets.make_sac_updater(sac_agent)          # drop-in for sac_agent.sac_agent.update_parameters
     updater.update_parameters(which_buffer, batch_size, updates_made, logger, reverse_mask=True)
+    sac_buffer = hipets.maybe_replace_sac_buffer(sac_buffer, obs_shape, act_shape, capacity, seed)   # a hipets.DeviceReplayBuffer
 
 ``mbpo.train`` changes one name per piece.  A ``DeterministicPolicy`` runs the reference's code instead, with a warning.
 """
@@ -22,6 +24,7 @@ import torch
 from . import _lib
 from ._pack import pack_policy
 from .model import UnsupportedModelError
+from .replay import DeviceReplayBuffer
 
 
 def find_policy(agent):
@@ -175,7 +178,12 @@ def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_b
     them) and the compaction of the rows not done before, all on the device; ONE device -> host copy at the end (into a pinned buffer kept
     on the environment) feeds one
     ``add_batch`` per step.  ``model_env``'s reset / step counters advance as under the reference's loop.  An agent the actor kernel
-    does not cover runs :func:`reference_populate_loop` over the same environment, with a warning."""
+    does not cover runs :func:`reference_populate_loop` over the same environment, with a warning.
+
+    ``sac_buffer`` a :class:`hipets.DeviceReplayBuffer` on the environment's engine: every step's compaction goes straight into the
+    buffer's ring (``Engine.ring_compact_transitions``) -- no staging area, no bulk copy, no ``add_batch``; the call ends in one copy
+    of the buffer's cursor and the per-step counts (kept in ``sac_buffer.last_populate_counts``) and sets its ``cur_idx`` /
+    ``num_stored``.  A batch larger than the buffer's capacity is a ValueError."""
     try:
         env = _hip_env(model_env)
     except UnsupportedModelError as exc:
@@ -198,6 +206,8 @@ def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_b
         obs = state["obs"]
         N, od = (int(v) for v in obs.shape)
         ad = actor.dims[2]
+        if isinstance(sac_buffer, DeviceReplayBuffer) and sac_buffer.engine is eng:
+            return _populate_ring(env, actor, sac_buffer, state, sac_samples_action, L)
         width = 2 * od + ad + 2
         head = (L + 3) // 4 * 4  # the per-step counts (int32) travel in front of the staging area: one buffer, one copy
         buf = torch.empty(head + N * L * width, dtype=torch.float32, device=dev)
@@ -215,6 +225,28 @@ def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_b
     finally:
         env._return_as_np = True  # (what the reference's reset(return_as_np=True) leaves behind)
     add_staged_batches(sac_buffer, host[head:], cap, host[:head].view(np.int32)[:L], od, ad)
+
+
+def _populate_ring(env, actor, sac_buffer, state, sac_samples_action: bool, L: int):
+    """The rollout steps of :func:`rollout_model_and_populate_sac_buffer` into a DeviceReplayBuffer's ring"""
+    eng, dev = env.engine, env.device
+    obs = state["obs"]
+    N, od = (int(v) for v in obs.shape)
+    if (od, actor.dims[2]) != (sac_buffer.obs_dim, sac_buffer.act_dim):
+        raise ValueError(f"the SAC buffer stores obs {sac_buffer.obs_dim} / act {sac_buffer.act_dim}, the rollout makes {od} / {actor.dims[2]}")
+    if N > sac_buffer.capacity:
+        raise ValueError(f"a rollout batch of {N} rows does not fit a SAC buffer of {sac_buffer.capacity}")
+    counts = torch.zeros(L, dtype=torch.int32, device=dev)
+    accum = torch.zeros(N, dtype=torch.uint8, device=dev)
+    for i in range(L):
+        action = actor.act_device(obs, sample=sac_samples_action)
+        nobs, rew, done, state = env.step(action, state, sample=True)
+        eng.ring_compact_transitions(obs, action, nobs, rew.reshape(-1), done.reshape(-1), accum, sac_buffer.storage, sac_buffer.capacity,
+                                     sac_buffer.cursor, counts[i:i + 1])
+        obs = nobs
+    tail = torch.cat([sac_buffer.cursor, counts.to(torch.int64)]).cpu().tolist()  # the call's ONE device -> host copy
+    sac_buffer.cur_idx, sac_buffer.num_stored = tail[0], tail[1]
+    sac_buffer.last_populate_counts = tail[2:]
 
 
 # ---- SAC's updates (third_party/pytorch_sac_pranz24/sac.py:76-173) ----------------------------------------------------------------
@@ -346,6 +378,7 @@ class SACUpdater:
         self._alpha_seen = None
         self._bound = None
         self._host = None
+        self._host_idx = None
 
     @staticmethod
     def check_batch(batch_size):
@@ -405,29 +438,62 @@ class SACUpdater:
             self._host = (torch.empty(need, dtype=torch.float32, pin_memory=True), torch.empty(max(n, 1), 8, dtype=torch.float32, pin_memory=True))
         return self._host[0][:need].view(n, B, width), self._host[1][:n]
 
+    def _index_staging(self, need: int):
+        if self._host_idx is None or self._host_idx.numel() < need:
+            self._host_idx = torch.empty(need, dtype=torch.int64, pin_memory=True)
+        return self._host_idx[:need]
+
     def update_many(self, memories, batch_size: int, first_update: int, logger=None, reverse_mask: bool = False, *, eps=None):
         """``len(memories)`` consecutive updates, update i sampling ``memories[i]`` (mbpo.py:259-260 picks a buffer per update) with
         index ``first_update + i``: all batches are sampled in order and go up in ONE pinned copy, the 2 n normal tables are drawn in
         order, the n updates are queued behind each other, ONE synchronisation, one small device -> host copy.  Returns the n
-        5-tuples -- bit for bit those of n single :meth:`update_parameters` calls.  ``eps``: n pairs (next-state table, state table) of
-        device tensors [B, act] to use instead of drawing them (a replay of recorded draws).  A batch outside 1 .. 1024 raises
-        UnsupportedModelError."""
+        5-tuples -- bit for bit those of n single :meth:`update_parameters` calls.  A memory that is a
+        :class:`hipets.DeviceReplayBuffer` on this engine only draws its indices on the host (``sample_indices``: its generator is
+        consumed as ``sample`` consumes it, in the memories' order); all indices go up in one copy and ONE gather launch per distinct
+        buffer builds its batches on the device -- the floats ``sample`` + ``pack_sac_batch`` would have uploaded.  ``eps``: n pairs
+        (next-state table, state table) of device tensors [B, act] to use instead of drawing them (a replay of recorded draws).  A
+        batch outside 1 .. 1024 raises UnsupportedModelError."""
         self.check_batch(batch_size)
         n, B = len(memories), int(batch_size)
         if n == 0:
             return []
         obs, act, _ = self.dims
         host, host_res = self._staging(n, B)
+        where = [None] * n  # update i reads (None, its slot of the pinned slab) or (a device buffer's group, its slot there)
+        groups = {}         # id(device buffer) -> [the buffer, its updates' index draws]
+        n_host = 0
         for i, memory in enumerate(memories):
+            if isinstance(memory, DeviceReplayBuffer) and memory.engine is self.engine:
+                if (memory.obs_dim, memory.act_dim) != (obs, act):
+                    raise ValueError(f"the buffer stores obs {memory.obs_dim} / act {memory.act_dim}, expected {obs} / {act}")
+                group = groups.setdefault(id(memory), [memory, []])
+                where[i] = (group, len(group[1]))
+                group[1].append(memory.sample_indices(B))
+                continue
             tr = memory.sample(B).astuple()
             if np.shape(tr[0]) != (B, obs) or np.shape(tr[1]) != (B, act):
                 raise ValueError(f"the buffer's sample is {np.shape(tr[0])} / {np.shape(tr[1])}, expected ({B}, {obs}) / ({B}, {act})")
-            pack_sac_batch(tr, reverse_mask, out=host[i].numpy())
+            pack_sac_batch(tr, reverse_mask, out=host[n_host].numpy())
+            where[i] = (None, n_host)
+            n_host += 1
         steps = self._bind()
         self._sync_alpha()
         dev = self.device
         with torch.cuda.device(dev), torch.no_grad():
-            batch = host.to(dev, non_blocking=True)
+            batch = host[:n_host].to(dev, non_blocking=True) if n_host else None
+            if groups:
+                idx = self._index_staging((n - n_host) * B)
+                o = 0
+                for group in groups.values():
+                    for draw in group[1]:
+                        idx[o:o + B] = torch.from_numpy(np.asarray(draw, dtype=np.int64))
+                        o += B
+                idx_dev = idx.to(dev, non_blocking=True)  # ONE upload of every buffer's draws
+                o = 0
+                for group in groups.values():
+                    m = len(group[1])
+                    group.append(group[0].gather(idx_dev[o:o + m * B], reverse_mask).view(m, B, -1))
+                    o += m * B
             results = torch.empty(n, 8, dtype=torch.float32, device=dev)
             adam = self._current_adam()
             lrs = [a[0] for a in adam]
@@ -438,7 +504,9 @@ class SACUpdater:
                 else:
                     eps_next = torch.empty(B, act, dtype=torch.float32, device=dev).normal_()  # Normal.rsample's draw, next state first
                     eps_cur = torch.empty(B, act, dtype=torch.float32, device=dev).normal_()
-                self.engine.sac_update(batch[i], eps_next, eps_cur, int(first_update) + i, [s + i for s in step0], lrs, results[i])
+                group, slot = where[i]
+                self.engine.sac_update(batch[slot] if group is None else group[2][slot], eps_next, eps_cur, int(first_update) + i,
+                                       [s + i for s in step0], lrs, results[i])
             host_res.copy_(results, non_blocking=True)
             torch.cuda.current_stream(dev).synchronize()
         for group in steps:
