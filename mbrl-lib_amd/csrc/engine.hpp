@@ -1,5 +1,5 @@
 // engine.hpp -- private to the host units of the C ABI (include/hipets.h): engine.hip, model.hip, rollout.hip, plan.hip, comm.hip,
-// train.hip, policy.hip, sac.hip and value.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
+// train.hip, policy.hip, replay.hip, sac.hip and value.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
 // Host code only; nothing declared here is part of the ABI (hidden visibility).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -61,6 +61,9 @@ struct DevBuf {
     template <typename T>
     T* as() const { return reinterpret_cast<T*>(p); }
 };
+
+// a network's weights as hipets_policy_set / hipets_critic_set packed them (policy_layer.hpp): is one set, its sizes, image and biases
+struct MlpSnapshot { bool set = false; int obs = 0, hid = 0, act = 0; DevBuf w, b; };
 
 // what hipets_sac_bind keeps: the agent's sizes and hyper-parameters, its optimizers' (beta1, beta2, eps) [critic, policy, alpha], and the
 // pointer table (the live torch tensors, include/hipets.h)
@@ -135,19 +138,15 @@ struct hipets_engine {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> event_pool;
     // model training (hipets_train_steps / hipets_train_eval): per-member activation slabs, evaluate's partial sums
     DevBuf train_slab, train_partial;
-    // SAC actor (hipets_policy_set / hipets_policy_act, policy.hip): the packed layers, and the block counts of hipets_compact_transitions
-    bool has_policy = false;
-    int policy_obs = 0, policy_hid = 0, policy_act = 0;
-    DevBuf policy_w, policy_b, compact_counts;
+    // the packed layers of the SAC actor (hipets_policy_set / _act, policy.hip) and of the SAC critic, Q1 and Q2 (hipets_critic_set / _q, value.hip)
+    hipets::MlpSnapshot policy, critic;
+    // the block counts of hipets_compact_transitions / hipets_ring_compact_transitions (replay.hip)
+    DevBuf compact_counts;
     // SAC updates (hipets_sac_bind / hipets_sac_update, sac.hip): the bound agent, the scratch activations (grown on demand), a device 1.0f
     bool has_sac = false;
     hipets::SacBind sac{};
     int sac_last_batch = 0;
     DevBuf sac_ws, sac_one;
-    // SAC critic (hipets_critic_set / hipets_critic_q, value.hip): the packed layers of Q1 and Q2
-    bool has_critic = false;
-    int critic_obs = 0, critic_act = 0, critic_hid = 0;
-    DevBuf critic_w, critic_b;
 };
 
 #pragma GCC visibility push(hidden)

@@ -1,13 +1,17 @@
-// policy_layer.hpp -- what the SAC actor kernel (policy.hip) and the SAC critic kernel (value.hip) share: one dense layer of a
-// workgroup's 16 R rows on v_mfma_f32_16x16x4_f32, the packing of an nn.Linear weight into the layer's W[k][n] image, and the R rule.
-// One definition, so a layer's arithmetic is the same in both kernels.  Internal linkage: each unit gets its own copy of the small
-// pack kernel.
+// policy_layer.hpp -- everything the SAC actor kernel (policy.hip) and the SAC critic kernel (value.hip) share, an MLP whose activations
+// live in two LDS buffers: one dense layer of a workgroup's 16 R rows on v_mfma_f32_16x16x4_f32, the staging of a workgroup's input rows,
+// the geometry (padding, LDS row lengths, the R rule), the launch, the packing of nn.Linear layers into the layer's W[k][n] image, the
+// size limits, and the log_std clamp of GaussianPolicy (sac.hip's tails use it too).  One definition each, so a layer's arithmetic and
+// a network's host scaffold are the same in both kernels.  Internal linkage: each unit gets its own copy of the small pack kernel.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstddef>
 
 #include "common.hpp"
+#include "engine.hpp"
+#include "lds_optin.hpp"
 
 namespace hipets {
 
@@ -118,6 +122,91 @@ inline int policy_row_tiles(size_t per_tile, size_t lds_max, long long batch) {
     while (R > 1 && (long long)kTile * (R >> 1) >= batch) R >>= 1;
     return R;
 }
+
+// Buffer A holds the input (kp0 columns), then h2; buffer B h1, then the last layer's np_last columns (the actor's heads: 2 act; the
+// critic's q: one tile of 16, so ld_b = hp + 4).  per_tile: the bytes of both buffers per row tile.
+struct MlpGeo { int kp0, hp, np_last, ld_a, ld_b, R; size_t per_tile, lds; };
+
+inline MlpGeo mlp_geometry(int k0, int hidden, int last_cols, size_t lds_max, long long batch) {
+    MlpGeo g{};
+    g.kp0 = pad16(k0); g.hp = pad16(hidden); g.np_last = pad16(last_cols);
+    g.ld_a = std::max(g.kp0, g.hp) + 4; g.ld_b = std::max(g.hp, g.np_last) + 4;
+    g.per_tile = (size_t)kTile * 4 * (size_t)(g.ld_a + g.ld_b);
+    g.R = policy_row_tiles(g.per_tile, lds_max, batch);
+    g.lds = g.per_tile * g.R;
+    return g;
+}
+
+// the body of hipets_policy_geometry / hipets_critic_geometry behind their "is one set" test (`g`: the geometry of `batch` rows)
+inline int mlp_geometry_query(int32_t batch, const MlpGeo& g, int32_t* row_tiles, int32_t* lds_bytes) {
+    if (batch < 1) return fail("bad batch");
+    if (row_tiles) *row_tiles = g.R;
+    if (lds_bytes) *lds_bytes = (int32_t)g.lds;
+    return 0;
+}
+
+// One launch of a kernel family (its R = 4, 2, 1 instances) at g.R row tiles; LDS past the 64 KiB window is opted in to once per instance and device.
+template <auto kK4, auto kK2, auto kK1, class Args>
+hipError_t launch_mlp(const MlpGeo& g, size_t lds_max, int batch, const Args& a, hipStream_t st) {
+    static LdsOptIn opted[3];
+    void (*kernel)(Args) = kK1;
+    LdsOptIn* once = &opted[0];
+    switch (g.R) {
+        case 4: kernel = kK4; once = &opted[2]; break;
+        case 2: kernel = kK2; once = &opted[1]; break;
+    }
+    if (g.lds > 64 * 1024) {
+        const hipError_t err = full_lds_once(*once, reinterpret_cast<const void*>(kernel), (int)lds_max);
+        if (err != hipSuccess) return err;
+    }
+    const unsigned grid = (unsigned)(((long long)batch + kTile * g.R - 1) / (kTile * g.R));
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(kPolicyThreads), g.lds, st, a);
+    return hipGetLastError();
+}
+
+// A workgroup's 16 R input rows into buffer A, zero padded to kp0 columns; rows past the batch are zeros.  One source array [B, n0]
+// (the actor's observations), or with kTwo a row of src0 followed by a row of src1 [B, n1] (the critic's [s, a], which exists in LDS only).
+template <int R, bool kTwo>
+__device__ __forceinline__ void mlp_stage_input(float* bufA, const int ld_a, const int kp0, const float* src0, const int n0, const float* src1,
+                                                const int n1, const int B, const long long row0, const int tid) {
+    const int K = kTwo ? n0 + n1 : n0;
+    for (int t = tid; t < kTile * R * kp0; t += kPolicyThreads) {
+        const int r = t / kp0, k = t - r * kp0;
+        const long long row = row0 + r;
+        float v = 0.f;
+        if (row < B && k < K) v = (!kTwo || k < n0) ? src0[row * n0 + k] : src1[row * n1 + (k - n0)];
+        bufA[r * ld_a + k] = v;
+    }
+}
+
+// one nn.Linear of a packed network: weight [N, K] -> columns [col0, col0 + N) of the [Kp][np] image at W + w_off, bias [N] -> Bv + b_off
+struct MlpLinear { const float *w, *b; int K, N, np, col0; size_t w_off, b_off; };
+
+// zero the image W [nw] and the biases Bv [nb], pack the layers' weights into it, copy their biases (device to device, on `st`)
+inline int mlp_pack(hipStream_t st, float* W, size_t nw, float* Bv, size_t nb, const MlpLinear* layers, int n_layers) {
+    HCHECK(hipMemsetAsync(W, 0, nw * 4, st));
+    HCHECK(hipMemsetAsync(Bv, 0, nb * 4, st));
+    auto pack = [&](const MlpLinear& l) {
+        const long long n = (long long)l.K * l.N;
+        hipLaunchKernelGGL(policy_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, W + l.w_off, l.w, l.K, l.N, l.np, l.col0);
+    };
+    for (int i = 0; i < n_layers; ++i) pack(layers[i]);
+    HCHECK(hipGetLastError());
+    for (int i = 0; i < n_layers; ++i) HCHECK(hipMemcpyAsync(Bv + layers[i].b_off, layers[i].b, (size_t)layers[i].N * 4, hipMemcpyDeviceToDevice, st));
+    return 0;
+}
+
+// the sizes hipets_policy_set, hipets_critic_set and hipets_sac_bind accept (`who`: "policy" / "critic" / "sac")
+inline int check_mlp_dims(const char* who, int obs_dim, int hidden, int act_dim) {
+    if (obs_dim < 1 || obs_dim > HIPETS_POLICY_MAX_OBS) return fail("%s obs_dim %d outside [1, %d]", who, obs_dim, HIPETS_POLICY_MAX_OBS);
+    if (hidden < 1 || hidden > HIPETS_POLICY_MAX_HIDDEN) return fail("%s hidden width %d outside [1, %d]", who, hidden, HIPETS_POLICY_MAX_HIDDEN);
+    if (act_dim < 1 || act_dim > HIPETS_POLICY_MAX_ACT) return fail("%s act_dim %d outside [1, %d]", who, act_dim, HIPETS_POLICY_MAX_ACT);
+    return 0;
+}
+
+// GaussianPolicy's LOG_SIG_MIN / LOG_SIG_MAX / epsilon (pytorch_sac_pranz24/model.py:6-8) and its torch.clamp of log_std (a NaN stays a NaN)
+constexpr float kLogSigMin = -20.f, kLogSigMax = 2.f, kSacEpsilon = 1e-6f;
+__device__ __forceinline__ float clamp_log_std(float ls) { return ls < kLogSigMin ? kLogSigMin : (ls > kLogSigMax ? kLogSigMax : ls); }
 
 }  // namespace
 

@@ -15,6 +15,8 @@
 
 #include "common.hpp"
 #include "engine.hpp"
+#include "policy_layer.hpp"
+#include "transition_layout.hpp"
 
 namespace hipets {
 
@@ -23,8 +25,6 @@ namespace {
 constexpr int kSacThreads = 256;
 constexpr int kSacWaves = kSacThreads / kWave;
 constexpr int kSacMaxProblems = 12;
-constexpr float kSacLogSigMin = -20.f, kSacLogSigMax = 2.f;  // LOG_SIG_MIN / LOG_SIG_MAX (pytorch_sac_pranz24/model.py:6-7)
-constexpr float kSacEpsilon = 1e-6f;                         // model.py:8
 
 enum SacEpilogue { kEpiBiasRelu = 0, kEpiBias = 1, kEpiMask = 2, kEpiStore = 3, kEpiAdam = 4 };
 
@@ -159,8 +159,7 @@ __global__ __launch_bounds__(kSacThreads) void sac_policy_tail_kernel(const SacP
     for (int d = 0; d < a.act; ++d) {
         const int64_t o = (int64_t)row * a.act + d;
         const float mean = a.mean[o];
-        float ls = a.raw_log_std[o];
-        ls = ls < kSacLogSigMin ? kSacLogSigMin : (ls > kSacLogSigMax ? kSacLogSigMax : ls);
+        const float ls = clamp_log_std(a.raw_log_std[o]);
         const float std = expf(ls);
         const float x = mean + eps[d] * std;  // Normal.rsample
         const float y = tanhf(x);
@@ -200,14 +199,14 @@ __global__ __launch_bounds__(kSacThreads) void sac_policy_tail_bwd_kernel(const 
     const float gl = (1.f / (float)a.B) * *a.alpha;  // d loss / d log_pi of a row
     const float y = a.tanh_x[i], sc = a.scale[d];
     const float raw = a.raw_log_std[i];
-    const float ls = raw < kSacLogSigMin ? kSacLogSigMin : (raw > kSacLogSigMax ? kSacLogSigMax : raw);
+    const float ls = clamp_log_std(raw);
     const float std = expf(ls);
     const float omy = a.sech2_x[i];  // 1 - y^2
     const float u = sc * omy + kSacEpsilon;
     const float dy = a.d_pi[i] * sc + gl * (2.f * sc * y / u);
     const float dx = dy * omy;
     a.d_mean[i] = dx;
-    const bool inside = raw >= kSacLogSigMin && raw <= kSacLogSigMax;
+    const bool inside = raw >= kLogSigMin && raw <= kLogSigMax;
     a.d_log_std[i] = inside ? dx * a.eps_cur[i] * std - gl : 0.f;
 }
 
@@ -439,6 +438,9 @@ struct SacWs {
 enum { kPol = 0, kPolM = 8, kPolV = 16, kCrit = 24, kCritM = 36, kCritV = 48, kTgt = 60, kLogAlpha = 72, kLogAlphaM = 73, kLogAlphaV = 74,
        kAlpha = 75, kScale = 76, kBias = 77 };
 
+// the six tensors of Q-network j of the four a TD step runs: 0, 1 = the target's two, 2, 3 = the critic's two
+inline float* const* q_net(float* const* P, int j) { return j < 2 ? P + kTgt + 6 * j : P + kCrit + 6 * (j - 2); }
+
 }  // namespace
 
 }  // namespace hipets
@@ -453,9 +455,7 @@ int hipets_sac_bind(hipets_engine* e, int32_t obs_dim, int32_t act_dim, int32_t 
     e->has_sac = false;
     e->sac_last_batch = 0;
     if (!adam || !ptrs) return fail("null argument");
-    if (obs_dim < 1 || obs_dim > HIPETS_POLICY_MAX_OBS) return fail("sac obs_dim %d outside [1, %d]", obs_dim, HIPETS_POLICY_MAX_OBS);
-    if (hidden < 1 || hidden > HIPETS_POLICY_MAX_HIDDEN) return fail("sac hidden width %d outside [1, %d]", hidden, HIPETS_POLICY_MAX_HIDDEN);
-    if (act_dim < 1 || act_dim > HIPETS_POLICY_MAX_ACT) return fail("sac act_dim %d outside [1, %d]", act_dim, HIPETS_POLICY_MAX_ACT);
+    if (check_mlp_dims("sac", obs_dim, hidden, act_dim)) return 1;
     if (n_ptrs != HIPETS_SAC_N_PTRS) return fail("sac pointer table holds %d entries, expected %d", n_ptrs, HIPETS_SAC_N_PTRS);
     if (target_update_interval < 1) return fail("sac target_update_interval %d < 1", target_update_interval);
     void* const* tab = reinterpret_cast<void* const*>(ptrs);
@@ -491,14 +491,15 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
     const hipets::SacBind& sb = e->sac;
-    const int B = batch_size, O = sb.obs, A = sb.act, H = sb.hid, K1 = O + A, W = 2 * O + A + 2;
+    const TransitionLayout row(sb.obs, sb.act, 0);  // (the batch's rows: no area)
+    const int B = batch_size, O = sb.obs, A = sb.act, H = sb.hid, K1 = O + A, W = row.width;
     const size_t BH = (size_t)B * H;
     if (e->sac_ws.ensure(SacWs(nullptr, B, H, A).floats * 4)) return 1;
     const SacWs ws(e->sac_ws.as<float>(), B, H, A);
     float* const* P = sb.p;
     const float* one = e->sac_one.as<float>();
-    const float *s = batch, *s2 = batch + O + A;
-    const int r_col = 2 * O + A;
+    const float *s = batch, *s2 = batch + row.c_next;
+    const int r_col = row.c_rew;
     const SacAdam ad_c = adam_at(sb.adam, lr_critic, step_critic + 1), ad_p = adam_at(sb.adam + 3, lr_policy, step_policy + 1),
                   ad_a = adam_at(sb.adam + 6, lr_alpha, step_alpha + 1);
 
@@ -529,9 +530,9 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
     {
         SacLaunch l(kEpiBiasRelu);
         for (int j = 0; j < 4; ++j) {
-            float* const* N = j < 2 ? P + kTgt + 6 * j : P + kCrit + 6 * (j - 2);
+            float* const* N = q_net(P, j);
             const SacSeg state = seg(j < 2 ? s2 : s, W, 1, N[0], 1, K1, O);
-            const SacSeg action = j < 2 ? seg(ws.act, A, 1, N[0] + O, 1, K1, A) : seg(batch + O, W, 1, N[0] + O, 1, K1, A);
+            const SacSeg action = j < 2 ? seg(ws.act, A, 1, N[0] + O, 1, K1, A) : seg(batch + row.c_act, W, 1, N[0] + O, 1, K1, A);
             l.add2(state, action, B, H, ws.qh1 + j * BH, H, N[1]);
         }
         l.go(st);
@@ -539,7 +540,7 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
     {
         SacLaunch l(kEpiBiasRelu);
         for (int j = 0; j < 4; ++j) {
-            float* const* N = j < 2 ? P + kTgt + 6 * j : P + kCrit + 6 * (j - 2);
+            float* const* N = q_net(P, j);
             l.add(seg(ws.qh1 + j * BH, H, 1, N[2], 1, H, H), B, H, ws.qh2 + j * BH, H, N[3]);
         }
         l.go(st);
@@ -551,7 +552,7 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
     const dim3 row_tiles((unsigned)((B + kTile - 1) / kTile));
     {
         for (int j = 0; j < 4; ++j) {
-            float* const* N = j < 2 ? P + kTgt + 6 * j : P + kCrit + 6 * (j - 2);
+            float* const* N = q_net(P, j);
             qt.w3[j] = N[4];
             qt.b3[j] = N[5];
         }

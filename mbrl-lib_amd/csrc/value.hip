@@ -5,11 +5,8 @@
 //                               particle reduction
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-
 #include "common.hpp"
 #include "engine.hpp"
-#include "lds_optin.hpp"
 #include "policy_layer.hpp"
 #include "returns_kernel.hpp"
 
@@ -18,9 +15,9 @@ namespace hipets {
 namespace {
 
 // ---------------------------------------------------------------------------------------------
-// The critic.  Built like the actor (policy.hip): a workgroup owns 16 R consecutive rows, two LDS buffers that the layers alternate
-// between, policy_layer.hpp's layer.  The input [s, a] exists in LDS only: buffer A is filled from the two source arrays, zero padded to
-// pad16(obs + act) columns.  The two networks run ONE AFTER THE OTHER through the same two buffers:
+// The critic.  Built like the actor (policy.hip) on policy_layer.hpp's layer and host scaffold: a workgroup owns 16 R consecutive rows,
+// two LDS buffers that the layers alternate between.  The input [s, a] exists in LDS only: buffer A is filled from the two source
+// arrays, zero padded to pad16(obs + act) columns.  The two networks run ONE AFTER THE OTHER through the same two buffers:
 //   A: [s, a]  -> B: h1 -> A: h2 -> B: column 0 = q      (Q1: linear1..3; then A is filled again and Q2 runs: linear4..6)
 // so the LDS need is the actor's -- 16 R rows x (max(pad16(obs + act), hp) + 4 + hp + 4) floats -- and every shape inside the
 // HIPETS_POLICY_MAX_* limits runs with R >= 1 (obs 512 + act 32, hidden 1024: 131 584 bytes).  A row's q1 waits in a register of the
@@ -46,19 +43,12 @@ template <int R>
 __device__ __forceinline__ float critic_net(const CriticArgs& a, const int net, float* bufA, float* bufB, const long long row0, const int tid) {
     constexpr int kRows = kTile * R;
     const int lane = tid & 63, wave = tid >> 6;
-    const int K = a.obs_dim + a.act;
     const size_t n1 = (size_t)a.kp0 * a.hp, n2 = (size_t)a.hp * a.hp, nw = n1 + n2 + (size_t)a.hp * kTile;
     const float* w = a.w + net * nw;
     const float* b = a.b + net * (2 * a.hp + kTile);
-    // [s, a], zero padded to kp0 columns; rows past the batch are zeros.  (The previous network's last layer read A before its closing
-    // barrier, and nothing reads B between that barrier and the next one.)
-    for (int t = tid; t < kRows * a.kp0; t += kPolicyThreads) {
-        const int r = t / a.kp0, k = t - r * a.kp0;
-        const long long row = row0 + r;
-        float v = 0.f;
-        if (row < a.B && k < K) v = k < a.obs_dim ? a.obs[row * a.obs_dim + k] : a.actions[row * a.act + (k - a.obs_dim)];
-        bufA[r * a.ld_a + k] = v;
-    }
+    // [s, a].  (The previous network's last layer read A before its closing barrier, and nothing reads B between that barrier and the
+    // next one.)
+    mlp_stage_input<R, true>(bufA, a.ld_a, a.kp0, a.obs, a.obs_dim, a.actions, a.act, a.B, row0, tid);
     __syncthreads();
     policy_layer<R, true, kCriticAhead>(bufA, a.ld_a, a.kp0, w, b, a.hp, bufB, a.ld_b, wave, lane);
     __syncthreads();
@@ -88,34 +78,8 @@ __global__ __launch_bounds__(kPolicyThreads) void critic_q_kernel(const CriticAr
     }
 }
 
-struct CriticGeo {
-    int kp0, hp, ld_a, ld_b, R;
-    size_t per_tile, lds;
-};
-
-CriticGeo critic_geometry(const hipets_engine* e, long long batch) {
-    CriticGeo g{};
-    g.kp0 = pad16(e->critic_obs + e->critic_act);
-    g.hp = pad16(e->critic_hid);
-    g.ld_a = std::max(g.kp0, g.hp) + 4;
-    g.ld_b = g.hp + 4;
-    g.per_tile = (size_t)kTile * 4 * (size_t)(g.ld_a + g.ld_b);
-    g.R = policy_row_tiles(g.per_tile, e->lds_max, batch);
-    g.lds = g.per_tile * g.R;
-    return g;
-}
-
-template <int R>
-hipError_t launch_critic(const CriticGeo& g, int lds_max, const CriticArgs& a, hipStream_t st) {
-    static LdsOptIn once;
-    if (g.lds > 64 * 1024) {
-        const hipError_t err = full_lds_once(once, reinterpret_cast<const void*>(&critic_q_kernel<R>), lds_max);
-        if (err != hipSuccess) return err;
-    }
-    const unsigned grid = (unsigned)(((long long)a.B + kTile * R - 1) / (kTile * R));
-    hipLaunchKernelGGL(critic_q_kernel<R>, dim3(grid), dim3(kPolicyThreads), g.lds, st, a);
-    return hipGetLastError();
-}
+// (the last layer is one 16-column tile, column 0 real)
+MlpGeo critic_geometry(const hipets_engine* e, long long batch) { return mlp_geometry(e->critic.obs + e->critic.act, e->critic.hid, kTile, e->lds_max, batch); }
 
 }  // namespace
 
@@ -127,81 +91,57 @@ extern "C" {
 
 int hipets_critic_set(hipets_engine* e, int32_t obs_dim, int32_t act_dim, int32_t hidden, const void* ptrs, int32_t n_ptrs, void* stream) {
     if (!e) return fail("null engine");
-    e->has_critic = false;  // (a refused set leaves no critic behind)
+    e->critic.set = false;  // (a refused set leaves no critic behind)
     if (!ptrs) return fail("null argument");
     if (n_ptrs != HIPETS_CRITIC_N_PTRS) return fail("critic pointer table holds %d entries, expected %d", n_ptrs, HIPETS_CRITIC_N_PTRS);
-    if (obs_dim < 1 || obs_dim > HIPETS_POLICY_MAX_OBS) return fail("critic obs_dim %d outside [1, %d]", obs_dim, HIPETS_POLICY_MAX_OBS);
-    if (hidden < 1 || hidden > HIPETS_POLICY_MAX_HIDDEN) return fail("critic hidden width %d outside [1, %d]", hidden, HIPETS_POLICY_MAX_HIDDEN);
-    if (act_dim < 1 || act_dim > HIPETS_POLICY_MAX_ACT) return fail("critic act_dim %d outside [1, %d]", act_dim, HIPETS_POLICY_MAX_ACT);
+    if (check_mlp_dims("critic", obs_dim, hidden, act_dim)) return 1;
     const float* const* p = static_cast<const float* const*>(ptrs);
     for (int i = 0; i < HIPETS_CRITIC_N_PTRS; ++i)
         if (!p[i]) return fail("critic pointer %d is null", i);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
-    e->critic_obs = obs_dim;
-    e->critic_act = act_dim;
-    e->critic_hid = hidden;
-    const CriticGeo g = critic_geometry(e, 1);
+    MlpSnapshot& c = e->critic;
+    c.obs = obs_dim; c.act = act_dim; c.hid = hidden;
+    const MlpGeo g = critic_geometry(e, 1);
     if (g.per_tile > e->lds_max) return fail("critic too wide for LDS");
     const size_t n1 = (size_t)g.kp0 * g.hp, n2 = (size_t)g.hp * g.hp, n3 = (size_t)g.hp * kTile, nw = n1 + n2 + n3;
     const size_t nb = (size_t)2 * g.hp + kTile;
-    if (e->critic_w.ensure(2 * nw * 4) || e->critic_b.ensure(2 * nb * 4)) return 1;
-    float* W = e->critic_w.as<float>();
-    float* Bv = e->critic_b.as<float>();
-    HCHECK(hipMemsetAsync(W, 0, 2 * nw * 4, st));
-    HCHECK(hipMemsetAsync(Bv, 0, 2 * nb * 4, st));
-    auto pack = [&](float* dst, const float* src, int K, int N, int np) {
-        const long long n = (long long)K * N;
-        hipLaunchKernelGGL(policy_pack_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, dst, src, K, N, np, 0);
-    };
+    if (c.w.ensure(2 * nw * 4) || c.b.ensure(2 * nb * 4)) return 1;
     const int K = obs_dim + act_dim;
+    MlpLinear layers[6];
     for (int net = 0; net < 2; ++net) {
         const float* const* l = p + 6 * net;  // linear(3 net + 1..3): weight, bias each
-        float* w = W + net * nw;
-        float* b = Bv + net * nb;
-        pack(w, l[0], K, hidden, g.hp);
-        pack(w + n1, l[2], hidden, hidden, g.hp);
-        pack(w + n1 + n2, l[4], hidden, 1, kTile);
-        HCHECK(hipGetLastError());
-        HCHECK(hipMemcpyAsync(b, l[1], (size_t)hidden * 4, hipMemcpyDeviceToDevice, st));
-        HCHECK(hipMemcpyAsync(b + g.hp, l[3], (size_t)hidden * 4, hipMemcpyDeviceToDevice, st));
-        HCHECK(hipMemcpyAsync(b + 2 * g.hp, l[5], 4, hipMemcpyDeviceToDevice, st));
+        layers[3 * net + 0] = {l[0], l[1], K, hidden, g.hp, 0, net * nw, net * nb};
+        layers[3 * net + 1] = {l[2], l[3], hidden, hidden, g.hp, 0, net * nw + n1, net * nb + g.hp};
+        layers[3 * net + 2] = {l[4], l[5], hidden, 1, kTile, 0, net * nw + n1 + n2, net * nb + 2 * g.hp};
     }
-    e->has_critic = true;
+    if (mlp_pack(st, c.w.as<float>(), 2 * nw, c.b.as<float>(), 2 * nb, layers, 6)) return 1;
+    c.set = true;
     return 0;
 }
 
 int hipets_critic_q(hipets_engine* e, const float* obs, const float* actions, int32_t batch, float* q1, float* q2, float* qmin, void* stream) {
-    if (!e || !e->has_critic) return fail("engine has no critic (call hipets_critic_set)");
+    if (!e || !e->critic.set) return fail("engine has no critic (call hipets_critic_set)");
     if (!obs || !actions) return fail("null argument");
     if (batch < 1) return fail("bad batch");
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
-    const CriticGeo g = critic_geometry(e, batch);
+    const MlpGeo g = critic_geometry(e, batch);
     CriticArgs a{};
     a.obs = obs; a.actions = actions; a.q1 = q1; a.q2 = q2; a.qmin = qmin;
-    a.w = e->critic_w.as<float>(); a.b = e->critic_b.as<float>();
-    a.B = batch; a.obs_dim = e->critic_obs; a.act = e->critic_act;
+    a.w = e->critic.w.as<float>(); a.b = e->critic.b.as<float>();
+    a.B = batch; a.obs_dim = e->critic.obs; a.act = e->critic.act;
     a.kp0 = g.kp0; a.hp = g.hp; a.ld_a = g.ld_a; a.ld_b = g.ld_b;
-    hipError_t err;
-    switch (g.R) {
-        case 4: err = launch_critic<4>(g, (int)e->lds_max, a, st); break;
-        case 2: err = launch_critic<2>(g, (int)e->lds_max, a, st); break;
-        default: err = launch_critic<1>(g, (int)e->lds_max, a, st); break;
-    }
+    const hipError_t err = launch_mlp<critic_q_kernel<4>, critic_q_kernel<2>, critic_q_kernel<1>>(g, e->lds_max, batch, a, st);
     if (err != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "critic kernel launch failed: %s", hipGetErrorString(err));
     return 0;
 }
 
 int hipets_critic_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles, int32_t* lds_bytes) {
-    if (!e || !e->has_critic) return fail("engine has no critic (call hipets_critic_set)");
-    if (batch < 1) return fail("bad batch");
-    const CriticGeo g = critic_geometry(e, batch);
-    if (row_tiles) *row_tiles = g.R;
-    if (lds_bytes) *lds_bytes = (int32_t)g.lds;
-    return 0;
+    if (!e || !e->critic.set) return fail("engine has no critic (call hipets_critic_set)");
+    return mlp_geometry_query(batch, critic_geometry(e, batch), row_tiles, lds_bytes);
 }
 
 int hipets_discounted_returns(hipets_engine* e, const float* rewards, const uint8_t* dones, const float* terminal_values, float gamma, int32_t pop,

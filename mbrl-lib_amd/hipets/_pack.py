@@ -228,6 +228,7 @@ def pack_plan_trace(buffers: dict, max_rows: int):
     return t, list(buffers.values())
 
 
+POLICY_LAYERS = ("linear1", "linear2", "mean_linear", "log_std_linear")  # GaussianPolicy's nn.Linear modules
 POLICY_TENSORS = ("w1", "b1", "w2", "b2", "wm", "bm", "ws", "bs", "action_scale", "action_bias")  # hipets_policy_set, in header order
 
 
@@ -239,7 +240,7 @@ def pack_policy(policy):
     hipets_policy_set refuses, raises UnsupportedModelError."""
     from .model import UnsupportedModelError
 
-    layers = [getattr(policy, n, None) for n in ("linear1", "linear2", "mean_linear", "log_std_linear")]
+    layers = [getattr(policy, n, None) for n in POLICY_LAYERS]
     if any(l is None or getattr(l, "weight", None) is None or getattr(l, "bias", None) is None or l.weight.ndim != 2 for l in layers):
         raise UnsupportedModelError(f"{type(policy).__name__} is not shaped like a GaussianPolicy (linear1, linear2, mean_linear, log_std_linear with biases)")
     l1, l2, lm, ls = layers
@@ -310,3 +311,44 @@ def check_critic_split(K: int, obs_dim: int, act_dim: int):
     if not (1 <= obs_dim <= _lib.POLICY_MAX_OBS and 1 <= act_dim <= _lib.POLICY_MAX_ACT):
         raise UnsupportedModelError(f"critic sizes (obs {obs_dim}, act {act_dim}) outside the critic kernel's "
                                     f"(<= {_lib.POLICY_MAX_OBS}, <= {_lib.POLICY_MAX_ACT})")
+
+
+# ---- where a SAC transition's floats live (csrc/transition_layout.hpp for the kernels): an AREA of ``cap`` rows is five arrays one behind
+# the other (``staging_views``), a BATCH ROW is (state, action, next state, reward, mask) ----
+def row_width(obs_dim: int, act_dim: int) -> int:
+    """Floats of a batch row, and of an area per row"""
+    return 2 * obs_dim + act_dim + 2
+
+
+def row_columns(obs_dim: int, act_dim: int):
+    """Where a batch row's (action, next state, reward, mask) start; the state starts at 0"""
+    return obs_dim, obs_dim + act_dim, 2 * obs_dim + act_dim, 2 * obs_dim + act_dim + 1
+
+
+def staging_views(flat, cap: int, obs_dim: int, act_dim: int):
+    """The five arrays of hipets_compact_transitions' staging area in ``flat`` (a tensor or a numpy array of at least cap * (2 obs_dim +
+    act_dim + 2) float32): (obs [cap, obs_dim], action [cap, act_dim], next_obs [cap, obs_dim], reward [cap], done [cap] as 0.0 / 1.0)"""
+    o1 = cap * obs_dim
+    o2 = o1 + cap * act_dim
+    o3 = o2 + cap * obs_dim
+    return (flat[:o1].reshape(cap, obs_dim), flat[o1:o2].reshape(cap, act_dim), flat[o2:o3].reshape(cap, obs_dim), flat[o3:o3 + cap],
+            flat[o3 + cap:o3 + 2 * cap])
+
+
+def pack_sac_batch(transitions, reverse_mask: bool = False, out: Optional[np.ndarray] = None) -> np.ndarray:
+    """``memory.sample(batch_size).astuple()`` -> f32 [B, 2 obs + act + 2], a row = (state, action, next_state, reward, mask): what
+    sac.py:80-95 uploads as five tensors.  mask = the terminated flag as a float, or ``1 - terminated`` under ``reverse_mask``
+    (``mask_batch.logical_not()``).  The truncated flags are ignored, as there.  ``out``: a [B, width] array to fill."""
+    state, action, next_state, reward, terminated = (np.asarray(v) for v in transitions[:5])
+    B, obs = state.shape
+    act = action.shape[1]
+    c_act, c_next, c_rew, c_mask = row_columns(obs, act)
+    if out is None:
+        out = np.empty((B, row_width(obs, act)), dtype=np.float32)
+    out[:, :c_act] = state
+    out[:, c_act:c_next] = action
+    out[:, c_next:c_rew] = next_state
+    out[:, c_rew] = np.reshape(reward, B)
+    mask = np.reshape(terminated, B).astype(np.float32)
+    out[:, c_mask] = (mask == 0).astype(np.float32) if reverse_mask else mask
+    return out

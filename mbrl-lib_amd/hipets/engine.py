@@ -11,7 +11,7 @@ import torch
 from . import _lib
 from ._lib import CemParams, HipetsError
 from ._pack import (_check_dev, check_critic_split, check_discount, member_slots, pack_critic, pack_model_desc, pack_plan_trace,  # noqa: F401
-                    pack_planet_desc, pack_reward_terms, pack_policy, pack_rollout_opts, pack_train_desc)
+                    pack_planet_desc, pack_reward_terms, pack_policy, pack_rollout_opts, pack_train_desc, row_width)
 from .model import ModelSpec
 from .reduce import ParticleReduce
 
@@ -46,6 +46,11 @@ _MARSHAL = {name: _marshaller(params) for name, (_, params) in _lib.SYMBOLS.item
 class Engine:
     """One fused planning engine bound to ``device`` (a gfx950 GPU).  Not thread-safe."""
 
+    # the three slots of a SAC agent (hipets.sac), empty -- sizes and owner (a weakref) of the actor's snapshot, the critic's and the bound
+    # agent -- and the SAC updates run so far.  (Class level: an Engine made without __init__ answers "has not been called" too.)
+    policy_dims = policy_owner = critic_dims = critic_owner = sac_dims = sac_owner = None
+    sac_updates = 0
+
     def __init__(self, device="cuda:0"):
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -61,9 +66,6 @@ class Engine:
         self.comm_group = None  # torch.distributed group of the communicator's ranks (hipets.dist.init_engine_comm)
         self.plan_mode = "fast"  # (the library's initial value; every fused plan sets its objective's mode: optimizers._prepare_fused)
         self.reduce = ParticleReduce()  # (the library's initial value, the mean; every objective sets its own: _Objective.bind_model)
-        # value-bootstrapped planning (hipets.value): the critic snapshot's sizes and its owner (a weakref to a SACCritic), and how many
-        # SAC updates this engine has run -- snapshots of an actor or a critic compare it
-        self.critic_dims, self.critic_owner, self.sac_updates = None, None, 0
         self._trace = None
 
     def close(self):
@@ -663,10 +665,10 @@ class Engine:
         self.policy_dims = dims
         return dims
 
-    def _policy_dims(self):
-        dims = getattr(self, "policy_dims", None)
+    def _slot_dims(self, slot: str, setter: str):
+        dims = getattr(self, slot + "_dims")
         if dims is None:
-            raise HipetsError("Engine.policy_set() has not been called")
+            raise HipetsError(f"Engine.{setter}() has not been called")
         return dims
 
     def policy_act(self, obs: torch.Tensor, *, sample: bool = False, seed: int = 0, stream_id: int = 0, eps: Optional[torch.Tensor] = None,
@@ -674,7 +676,7 @@ class Engine:
         """The actor's forward for ``obs`` f32 [B, obs_dim] on the device -> actions f32 [B, act_dim] (hipets_policy_act): the
         policy's mean action, or with ``sample`` a draw with ``eps`` f32 [B, act_dim] (None: drawn in-kernel from (seed, stream_id),
         see :meth:`policy_normals`).  ``taps``: returns (actions, mean, log_std), the heads before tanh."""
-        obs_dim, _, act_dim = self._policy_dims()
+        obs_dim, _, act_dim = self._slot_dims("policy", "policy_set")
         dev = self.device
         if not isinstance(obs, torch.Tensor) or obs.ndim != 2 or int(obs.shape[0]) < 1:
             raise ValueError("obs must be a [B, obs_dim] tensor with B >= 1")
@@ -700,16 +702,19 @@ class Engine:
 
     def policy_geometry(self, batch: int):
         """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of a :meth:`policy_act` of ``batch`` rows."""
-        self._policy_dims()
+        self._slot_dims("policy", "policy_set")
+        return self._geometry("hipets_policy_geometry", batch)
+
+    def _geometry(self, symbol: str, batch: int):
         r, lds = C.c_int32(), C.c_int32()
-        self._query("hipets_policy_geometry", batch=int(batch), row_tiles=C.byref(r), lds_bytes=C.byref(lds))
+        self._query(symbol, batch=int(batch), row_tiles=C.byref(r), lds_bytes=C.byref(lds))
         return r.value, lds.value
 
     def compact_transitions(self, obs, action, next_obs, rewards, dones, accum_dones, staging, cap, offset, count_out):
         """mbpo.py:53-63 for one rollout step (hipets_compact_transitions): the rows whose ``accum_dones`` (uint8 [N], updated in
         place: ``|= dones``) is 0 are appended in row order to ``staging``, a flat f32 buffer of at least ``cap * (2 obs_dim + act_dim +
         2)`` elements holding five arrays one behind the other -- obs [cap, obs_dim], action [cap, act_dim], next_obs [cap, obs_dim],
-        reward [cap], done [cap] (``hipets.mbpo.staging_views`` splits it) -- at row ``offset`` (int64 [1], advanced); ``count_out``
+        reward [cap], done [cap] (``hipets._pack.staging_views`` splits it) -- at row ``offset`` (int64 [1], advanced); ``count_out``
         int32 [1] = the rows kept.  All tensors on the device; ``rewards`` f32 and ``dones`` bool / uint8 of N elements."""
         N, od, ad, dones, cap = self._check_step_rows(obs, action, next_obs, rewards, dones, accum_dones, staging, cap, "staging", "cap")
         _check_dev(offset, torch.int64, self.device, "offset", numel=1)
@@ -736,8 +741,8 @@ class Engine:
         _check_dev(accum_dones, torch.uint8, dev, "accum_dones", (N,))
         _check_dev(area, torch.float32, dev, area_name)
         cap = int(cap)
-        if cap < 0 or area.numel() < cap * (2 * od + ad + 2):
-            raise ValueError(f"{area_name} must hold {cap_name} * (2 obs_dim + act_dim + 2) = {cap} * {2 * od + ad + 2} floats, got {area.numel()}")
+        if cap < 0 or area.numel() < cap * row_width(od, ad):
+            raise ValueError(f"{area_name} must hold {cap_name} * (2 obs_dim + act_dim + 2) = {cap} * {row_width(od, ad)} floats, got {area.numel()}")
         return N, od, ad, dones, cap
 
     # ---- a device-resident SAC replay buffer (hipets_ring_compact_transitions / hipets_replay_gather; hipets.DeviceReplayBuffer) ----
@@ -761,7 +766,7 @@ class Engine:
         which are range-checked here (ValueError) and uploaded."""
         dev = self.device
         capacity, od, ad = int(capacity), int(obs_dim), int(act_dim)
-        W = 2 * od + ad + 2
+        W = row_width(od, ad)
         _check_dev(ring, torch.float32, dev, "ring")
         if capacity < 1 or od < 1 or ad < 1 or ring.numel() < capacity * W:
             raise ValueError(f"ring must hold capacity * (2 obs_dim + act_dim + 2) = {capacity} * {W} floats, got {ring.numel()}")
@@ -801,14 +806,11 @@ class Engine:
         """One SAC update on the bound agent (hipets_sac_update), asynchronous on the current stream.  ``batch`` f32 [B, 2 obs + act + 2]
         (state, action, next_state, reward, mask), ``eps_next`` / ``eps_cur`` f32 [B, act], ``steps`` / ``lrs`` = the Adam steps taken
         before and the learning rates of (critic, policy, alpha), ``result`` f32 [8] -- all device tensors but the scalars."""
-        dims = getattr(self, "sac_dims", None)
-        if dims is None:
-            raise HipetsError("Engine.sac_bind() has not been called")
-        obs, act, _ = dims
+        obs, act, _ = self._slot_dims("sac", "sac_bind")
         if not isinstance(batch, torch.Tensor) or batch.ndim != 2:
             raise ValueError("batch must be a [B, 2 obs + act + 2] tensor")
         B = int(batch.shape[0])
-        _check_dev(batch, torch.float32, self.device, "batch", (B, 2 * obs + act + 2))
+        _check_dev(batch, torch.float32, self.device, "batch", (B, row_width(obs, act)))
         _check_dev(eps_next, torch.float32, self.device, "eps_next", (B, act))
         _check_dev(eps_cur, torch.float32, self.device, "eps_cur", (B, act))
         _check_dev(result, torch.float32, self.device, "result", numel=8)
@@ -816,7 +818,7 @@ class Engine:
                    step_critic=int(steps[0]), step_policy=int(steps[1]), step_alpha=int(steps[2]), lr_critic=float(lrs[0]),
                    lr_policy=float(lrs[1]), lr_alpha=float(lrs[2]), result=result)
         # the update kernels write the agent's parameters through raw pointers (no tensor's _version moves): snapshots of the actor or
-        # the critic compare this counter (hipets.value)
+        # the critic compare this counter (hipets.sac)
         self.sac_updates += 1
 
     def sac_forward_taps(self, batch_size: int) -> Dict[str, torch.Tensor]:
@@ -841,16 +843,10 @@ class Engine:
         self.critic_dims = (int(obs_dim), int(act_dim), hidden)
         return self.critic_dims
 
-    def _critic_dims(self):
-        dims = self.critic_dims
-        if dims is None:
-            raise HipetsError("Engine.critic_set() has not been called")
-        return dims
-
     def critic_q(self, obs: torch.Tensor, actions: torch.Tensor, *, q1: bool = True, q2: bool = True, qmin: bool = True):
         """The critic's forward for ``obs`` f32 [B, obs_dim] and ``actions`` f32 [B, act_dim] on the device -> (q1, q2, qmin), f32 [B]
         each (hipets_critic_q, one launch; an output not wanted is None).  qmin = torch.min(q1, q2)."""
-        obs_dim, act_dim, _ = self._critic_dims()
+        obs_dim, act_dim, _ = self._slot_dims("critic", "critic_set")
         dev = self.device
         if not isinstance(obs, torch.Tensor) or obs.ndim != 2 or int(obs.shape[0]) < 1:
             raise ValueError("obs must be a [B, obs_dim] tensor with B >= 1")
@@ -863,10 +859,8 @@ class Engine:
 
     def critic_geometry(self, batch: int):
         """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of a :meth:`critic_q` of ``batch`` rows."""
-        self._critic_dims()
-        r, lds = C.c_int32(), C.c_int32()
-        self._query("hipets_critic_geometry", batch=int(batch), row_tiles=C.byref(r), lds_bytes=C.byref(lds))
-        return r.value, lds.value
+        self._slot_dims("critic", "critic_set")
+        return self._geometry("hipets_critic_geometry", batch)
 
     def discounted_returns(self, rewards: torch.Tensor, dones: torch.Tensor, pop: int, num_particles: int, *, gamma: float = 1.0,
                            terminal_values: Optional[torch.Tensor] = None, row_totals: bool = False, first_done: bool = False):

@@ -18,6 +18,7 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
+from ._pack import row_columns, row_width, staging_views
 from .model import UnsupportedModelError
 
 
@@ -68,7 +69,7 @@ class DeviceReplayBuffer:
         self.engine = engine
         self.device = engine.device if engine is not None else torch.device(device)
         self.capacity, self.obs_dim, self.act_dim = int(capacity), obs_shape[0], action_shape[0]
-        self.width = 2 * self.obs_dim + self.act_dim + 2
+        self.width = row_width(self.obs_dim, self.act_dim)
         try:
             self.storage = torch.zeros(self.capacity * self.width, dtype=torch.float32, device=self.device)
             self.cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
@@ -97,9 +98,7 @@ class DeviceReplayBuffer:
 
     def views(self):
         """(obs [capacity, obs], action [capacity, act], next_obs [capacity, obs], reward [capacity], done [capacity] as 0.0 / 1.0):
-        views of the storage, on the device (``hipets.mbpo.staging_views`` of it)"""
-        from .mbpo import staging_views
-
+        views of the storage, on the device (``hipets._pack.staging_views`` of it)"""
         return staging_views(self.storage, self.capacity, self.obs_dim, self.act_dim)
 
     # ---- writing ------------------------------------------------------------------------------------------------------------------
@@ -156,7 +155,7 @@ class DeviceReplayBuffer:
 
     def gather(self, indices, reverse_mask: bool = False, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """f32 [n, 2 obs + act + 2] on the device: row j = (obs, action, next_obs, reward, mask) of row ``indices[j]``, ``mask`` the
-        done flag or, under ``reverse_mask``, its negation -- ``hipets.mbpo.pack_sac_batch``'s layout.  One launch
+        done flag or, under ``reverse_mask``, its negation -- ``hipets._pack.pack_sac_batch``'s layout.  One launch
         (``Engine.replay_gather``).  Host indices are range-checked (ValueError)."""
         if self.engine is not None:
             return self.engine.replay_gather(self.storage, self.capacity, self.obs_dim, self.act_dim, indices, reverse_mask, out)
@@ -169,9 +168,9 @@ class DeviceReplayBuffer:
         return rows if out is None else out.copy_(rows)
 
     def _batch(self, rows: np.ndarray):
-        od, ad = self.obs_dim, self.act_dim
-        return _transition_batch(rows[:, :od].copy(), rows[:, od:od + ad].copy(), rows[:, od + ad:2 * od + ad].copy(),
-                                 rows[:, 2 * od + ad].copy(), rows[:, 2 * od + ad + 1] != 0, np.zeros(len(rows), dtype=bool))
+        a, s2, r, m = row_columns(self.obs_dim, self.act_dim)
+        return _transition_batch(rows[:, :a].copy(), rows[:, a:s2].copy(), rows[:, s2:r].copy(), rows[:, r].copy(), rows[:, m] != 0,
+                                 np.zeros(len(rows), dtype=bool))
 
     def _batch_from_indices(self, indices):
         return self._batch(self.gather(indices).cpu().numpy())

@@ -12,118 +12,15 @@ the actor and the critic; the objective re-takes them when the agent changed (se
 """
 from __future__ import annotations
 
-import weakref
 from typing import Optional
 
 import numpy as np
 import torch
 
-from ._pack import check_critic_split, check_discount, pack_critic
-from .mbpo import SACActor
-from .model import PlaNetSpec, UnsupportedModelError, is_planet_model
+from ._pack import check_discount
+from .model import PlaNetSpec, is_planet_model
 from .objectives import CallableTrajectoryEvalFn
-
-
-def find_critic(agent, target: bool = False):
-    """The critic module of an ``mbrl.planning.SACAgent`` (``.sac_agent.critic``), a ``pytorch_sac_pranz24.SAC`` (``.critic``) -- their
-    ``critic_target`` with ``target`` -- or a bare ``QNetwork``-shaped module."""
-    inner = getattr(agent, "sac_agent", agent)
-    name = "critic_target" if target else "critic"
-    module = getattr(inner, name, None)
-    if module is not None:
-        return module
-    if getattr(inner, "linear1", None) is not None:  # a bare module (it has no target of its own)
-        return inner
-    raise UnsupportedModelError(f"{type(agent).__name__} has no {name}: expected an mbrl SACAgent, a pytorch_sac_pranz24 SAC or a QNetwork-shaped module")
-
-
-class _Snapshot:
-    """When was a module's snapshot in an engine taken?  ``moved()``: a watched parameter's ``_version`` changed (a stock optimizer
-    step, a ``load_state_dict``), or the engine ran ``sac_update`` since (its kernels write parameters through raw pointers: no version
-    moves).  ``watch``: further modules whose parameters are watched too -- for a ``critic_target`` the live ``critic``: the stock
-    agent writes its target as ``target_param.data.copy_(...)`` (pytorch_sac_pranz24/utils.py:28, 33), which moves no version of the
-    target's, but every such write follows a ``critic_optim.step()``, which moves the critic's."""
-
-    def __init__(self, module, engine, watch=()):
-        self.modules, self.engine = (module,) + tuple(m for m in watch if m is not None and m is not module), engine
-        self.mark()
-
-    def _state(self):
-        return tuple(int(p._version) for m in self.modules for p in m.parameters()), self.engine.sac_updates
-
-    def mark(self):
-        self.state = self._state()
-
-    def moved(self) -> bool:
-        return self.state != self._state()
-
-
-class SACCritic:
-    """``QNetwork.forward`` (pytorch_sac_pranz24/model.py:36-61) on the critic kernel (hipets_critic_q).  ``agent``: an
-    ``mbrl.planning.SACAgent``, a ``pytorch_sac_pranz24.SAC`` or a bare ``QNetwork``-shaped module (linear1..3 = Q1, linear4..6 = Q2);
-    ``target``: the agent's ``critic_target``.  Anything else raises UnsupportedModelError with the reason.  The engine holds a SNAPSHOT
-    of the weights: ``refresh()`` after the critic changed (``stale()`` tells; for a target it also watches the agent's live
-    ``critic``, whose optimizer step precedes every stock soft update).  ``obs_dim``: where the critic's input splits into state and
-    action; by default read off the agent's policy, else fixed by the first ``q`` call."""
-
-    def __init__(self, agent, engine=None, target: bool = False, obs_dim: Optional[int] = None):
-        self.critic = find_critic(agent, target)
-        (self.K, self.hidden), tensors = pack_critic(self.critic)
-        if obs_dim is None:
-            l1 = getattr(getattr(getattr(agent, "sac_agent", agent), "policy", None), "linear1", None)
-            if getattr(l1, "weight", None) is not None and l1.weight.ndim == 2:
-                obs_dim = int(l1.weight.shape[1])
-        self.split = None
-        if obs_dim is not None:
-            check_critic_split(self.K, int(obs_dim), self.K - int(obs_dim))
-            self.split = (int(obs_dim), self.K - int(obs_dim))
-        if engine is None:
-            from .engine import get_engine
-
-            p = tensors[0]
-            engine = get_engine(p.device if p.device.type == "cuda" else "cuda")
-        self.engine, self.device = engine, engine.device
-        live = getattr(getattr(agent, "sac_agent", agent), "critic", None) if target else None
-        self._snapshot = _Snapshot(self.critic, engine, watch=(live,) if isinstance(live, torch.nn.Module) else ())
-        if self.split is not None:
-            self.refresh()
-
-    @property
-    def dims(self):
-        """(obs_dim, act_dim, hidden); the first two are None until the split is known"""
-        return (self.split or (None, None)) + (self.hidden,)
-
-    def refresh(self):
-        """Re-snapshot the critic's live weights (device to device where the critic is on the engine's GPU)."""
-        if self.split is None:
-            raise ValueError("the critic's state / action split is not known yet: pass obs_dim=, or call q(obs, actions) once")
-        self.engine.critic_set(self.critic, *self.split)
-        self.engine.critic_owner = weakref.ref(self)
-        self._snapshot.mark()
-
-    def owns_engine(self) -> bool:
-        owner = self.engine.critic_owner
-        return owner is not None and owner() is self
-
-    def stale(self) -> bool:
-        """Does the engine's snapshot differ from the live critic as far as can be told without reading it: a parameter's version
-        moved, the engine ran a SAC update since, or another critic sits in the engine's slot?"""
-        return not self.owns_engine() or self._snapshot.moved()
-
-    def q(self, obs_t: torch.Tensor, act_t: torch.Tensor, q1: bool = True, q2: bool = True, qmin: bool = True):
-        """``obs_t`` f32 [B, obs_dim], ``act_t`` f32 [B, act_dim] on the device -> (q1, q2, qmin) f32 [B] on the device (one not
-        wanted is None); qmin = torch.min(q1, q2)."""
-        if not isinstance(obs_t, torch.Tensor) or not isinstance(act_t, torch.Tensor) or obs_t.ndim != 2 or act_t.ndim != 2:
-            raise ValueError("obs / actions must be [B, obs_dim] / [B, act_dim] tensors")
-        split = (int(obs_t.shape[1]), int(act_t.shape[1]))
-        if self.split is None:
-            check_critic_split(self.K, *split)
-            self.split = split
-        if split != self.split:
-            raise ValueError(f"obs / actions must be [B, {self.split[0]}] / [B, {self.split[1]}], got {tuple(obs_t.shape)} / {tuple(act_t.shape)}")
-        if not self.owns_engine():  # (another critic's weights sit in the engine)
-            self.refresh()
-        return self.engine.critic_q(obs_t, act_t, q1=q1, q2=q2, qmin=qmin)
+from .sac import SACActor, SACCritic, _Snapshot, find_critic  # noqa: F401  (their home before hipets.sac)
 
 
 class ValueTrajectoryEvalFn(CallableTrajectoryEvalFn):
@@ -154,25 +51,21 @@ class ValueTrajectoryEvalFn(CallableTrajectoryEvalFn):
             raise ValueError("value-bootstrapped objectives are not available for PlaNet latent models (no critic over latent states)")
         super().__init__(model, num_particles, reward_fn, termination_fn, engine, mode, seed, device, rng, check_rowwise, max_trajectory_bytes,
                          particle_reduce)
-        self.actor = self.critic = self._actor_snapshot = None
+        self.actor = self.critic = None
         if agent is not None:
             self.actor = SACActor(agent, engine=self.engine)
             self.critic = SACCritic(agent, engine=self.engine, target=target_critic, obs_dim=self.spec.obs_dim)
             if self.actor.dims[0] != self.spec.obs_dim or self.actor.dims[2] != self.spec.act_dim or self.critic.split[1] != self.spec.act_dim:
                 raise ValueError(f"the agent acts on (obs {self.actor.dims[0]}, act {self.actor.dims[2]}), its critic on (obs {self.critic.split[0]}, "
                                  f"act {self.critic.split[1]}); the model has (obs {self.spec.obs_dim}, act {self.spec.act_dim})")
-            self._actor_snapshot = _Snapshot(self.actor.policy, self.engine)
 
     def refresh_agent(self, force: bool = True):
         """Re-snapshot the actor's and the critic's live weights; ``force=False``: only what may have changed (the class docstring)."""
         if self.actor is None:
             return
-        owner = getattr(self.engine, "policy_owner", None)
-        if force or owner is None or owner() is not self.actor or self._actor_snapshot.moved():
-            self.actor.refresh()
-            self._actor_snapshot.mark()
-        if force or self.critic.stale():
-            self.critic.refresh()
+        for part in (self.actor, self.critic):
+            if force or part.stale():
+                part.refresh()
 
     def _terminal(self, next_obs: torch.Tensor):
         """(terminal_actions [B, act], terminal_values [B]) on the last predicted states, or (None, None) without an agent"""

@@ -81,6 +81,10 @@ CRITIC_CASES = [
     ("k23_h256", 17, 6, 256, (1000,)),          # many workgroups, a ragged last one
     ("k23_h512", 17, 6, 512, ("R+1",)),         # the middle R
     ("k393_h1024", 376, 17, 1024, (40,)),       # Humanoid's K at the LDS limit
+    # the two-source input staging: the obs / act boundary at k = 1 with everything padded (hidden 2: with a one-wide hidden layer a
+    # relu that is off leaves the first layers without influence on 37% of the rows, and the separation below cannot hold) ...
+    ("k2_h2", 1, 1, 2, (1, 17)),
+    ("k17_h16", 16, 1, 16, (16,)),              # ... and exactly on a k-block edge, K one past it
 ]
 CASE_ROWS = 1000
 _BUILT = {}
