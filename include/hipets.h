@@ -661,7 +661,12 @@ int hipets_plan_planet_icem_batched(hipets_engine* e, const hipets_icem_params* 
  * decay (model_trainer.py:63-68).  Parameters and Adam state are caller-owned DEVICE f32 tensors in torch's layout, updated in
  * place: weights[l] [E, d_l, d_{l+1}], biases[l] [E, 1, d_{l+1}] with d_0 = in_dim, d_1 .. d_{n_layers-1} = hid and
  * d_{n_layers} = 2 out_dim (mean | raw logvar columns).  Limits: E <= 16, 2 <= n_layers <= 8, in_dim <= 512, hid <= 256,
- * out_dim <= 512, max_batch <= 256; anything else fails with HIPETS_ERR_INVALID_ARGUMENT.                                   */
+ * out_dim <= 512, max_batch <= 256 (the HIPETS_TRAIN_MAX_* limits); anything else fails with HIPETS_ERR_INVALID_ARGUMENT.  */
+#define HIPETS_TRAIN_MAX_MEMBERS 16
+#define HIPETS_TRAIN_MAX_HID 256
+#define HIPETS_TRAIN_MAX_IN 512
+#define HIPETS_TRAIN_MAX_OUT 512
+#define HIPETS_TRAIN_MAX_BATCH 256
 typedef struct {
     int32_t ensemble_size;   /* E                                                                                    */
     int32_t n_layers;        /* linear layers = num_layers of GaussianMLP + 1                                        */

@@ -6,16 +6,19 @@
 //   sac_policy_tail_kernel / sac_policy_tail_bwd_kernel   GaussianPolicy.sample behind its heads (model.py:95-108) and its gradient
 //   sac_q_tail_kernel    the N = 1 output layers of the Q-networks, fused with the TD target / the policy's min-Q and their gradients
 //   sac_finish_kernel    the losses, the Adam step on log_alpha, the result slot
-// Every product runs on v_mfma_f32_16x16x4_f32 through the compiler's builtin.  Launch order is the only synchronisation: no kernel
-// waits on another workgroup; no float atomics: every reduction has a fixed order.
+// Every product runs on v_mfma_f32_16x16x4_f32 through the compiler's builtin: sac_seg_acc is the k-loop, tile_walk.hpp the tiles'
+// numbering and the lane-to-element map, adam.hpp the optimizers' rule (on the host and on the device).  Launch order is the only
+// synchronisation: no kernel waits on another workgroup; no float atomics: every reduction has a fixed order.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
 
+#include "adam.hpp"
 #include "common.hpp"
 #include "engine.hpp"
 #include "policy_layer.hpp"
+#include "tile_walk.hpp"
 #include "transition_layout.hpp"
 
 namespace hipets {
@@ -45,30 +48,14 @@ struct SacProblem {
     int nseg, M, N, ldo, tiles_n;
 };
 
-// torch.optim.Adam of one optimizer at one step (the host's double arithmetic, rounded once)
-struct SacAdam {
-    float one_minus_beta1, beta2, one_minus_beta2, eps, neg_step_size, bc2_sqrt;
-};
-
 struct SacMmArgs {
     SacProblem p[kSacMaxProblems];
     int tile_start[kSacMaxProblems + 1];
     int np, epilogue;
-    SacAdam adam;
+    AdamScalars adam;
     int soft;  // kEpiAdam: apply target = target * (1 - tau) + param * tau with the new parameter value
     float tau, one_minus_tau;
 };
-
-// torch.optim.Adam, single-tensor order, no weight decay; returns the new parameter
-__device__ __forceinline__ float sac_adam(float p, float g, float* m, float* v, const SacAdam& a) {
-    const float mo = *m, w = a.one_minus_beta1;
-    const float mn = w < 0.5f ? mo + w * (g - mo) : g - (g - mo) * (1.f - w);  // Tensor.lerp_
-    const float vn = *v * a.beta2 + a.one_minus_beta2 * g * g;
-    *m = mn;
-    *v = vn;
-    const float denom = sqrtf(vn) / a.bc2_sqrt + a.eps;
-    return p + a.neg_step_size * (mn / denom);
-}
 
 // the operands of k = k .. k + 3 of one row / column: one 16-byte load where k is the contiguous direction and the row is aligned
 __device__ __forceinline__ f32x4 sac_ld4(const float* __restrict__ row, int sk, int k, int K, bool valid, bool vec) {
@@ -81,7 +68,9 @@ __device__ __forceinline__ f32x4 sac_ld4(const float* __restrict__ row, int sk, 
 }
 
 // c0 / c1 += one segment's share of the 16 x 16 tile at (m0, n0).  Inside a k-block of 16 lane group q = lane >> 4 supplies
-// k = 16 kb + 4 q + s to MFMA s, for A and B alike; the result is C[m0 + 4 q + i][n0 + (lane & 15)] in element i.
+// k = 16 kb + 4 q + s to MFMA s, for A and B alike; the result lies as tile_walk.hpp says.
+// (train.hip's mm_tile is the other k-loop of the learning kernels and stays apart: it gives lane group q the steps k0 + q, k0 + 4 + q,
+// ... one float per load, so the two sum along k in different orders -- other bits -- and load differently -- other speed.)
 __device__ __forceinline__ void sac_seg_acc(f32x4& c0, f32x4& c1, const SacSeg& s, int M, int N, int m0, int n0, int lane) {
     const int r = lane & 15, q = lane >> 4;
     const bool av = m0 + r < M, bv = n0 + r < N;
@@ -110,18 +99,18 @@ __global__ __launch_bounds__(kSacThreads) void sac_mm_kernel(const SacMmArgs a) 
     while (pi + 1 < a.np && t >= a.tile_start[pi + 1]) ++pi;
     const SacProblem& p = a.p[pi];
     const int lt = t - a.tile_start[pi];
-    const int m0 = (lt / p.tiles_n) << 4, n0 = (lt % p.tiles_n) << 4;
+    const int m0 = tile_m0(lt, p.tiles_n), n0 = tile_n0(lt, p.tiles_n);
     f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
     sac_seg_acc(c0, c1, p.s[0], p.M, p.N, m0, n0, lane);
     if (p.nseg > 1) sac_seg_acc(c0, c1, p.s[1], p.M, p.N, m0, n0, lane);
     const f32x4 c = c0 + c1;
-    const int col = n0 + (lane & 15);
+    const int col = tile_col(n0, lane);
     if (col >= p.N) return;
     const int epi = a.epilogue;
     const float bc = (epi == kEpiBiasRelu || epi == kEpiBias) ? p.aux[col] : 0.f;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const int row = m0 + 4 * (lane >> 4) + i;
+        const int row = tile_row(m0, lane, i);
         if (row >= p.M) continue;
         const int64_t o = (int64_t)row * p.ldo + col;
         if (epi == kEpiBiasRelu) {
@@ -134,7 +123,7 @@ __global__ __launch_bounds__(kSacThreads) void sac_mm_kernel(const SacMmArgs a) 
         } else if (epi == kEpiStore) {
             p.out[o] = c[i];
         } else {
-            const float pn = sac_adam(p.out[o], c[i], p.m + o, p.v + o, a.adam);
+            const float pn = adam_update(p.out[o], c[i], p.m + o, p.v + o, a.adam);
             p.out[o] = pn;
             if (a.soft && p.target) p.target[o] = p.target[o] * a.one_minus_tau + pn * a.tau;  // utils.soft_update
         }
@@ -245,10 +234,10 @@ __global__ __launch_bounds__(kSacThreads) void sac_q_tail_kernel(const SacQTailA
         f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
         sac_seg_acc(c0, c1, s, a.B, 1, m0, 0, lane);
         const f32x4 c = c0 + c1;
-        if ((lane & 15) == 0) {
+        if (tile_col(0, lane) == 0) {  // the one column of the tile
             const float b = *a.b3[wave];
 #pragma unroll
-            for (int i = 0; i < 4; ++i) qs[wave][4 * (lane >> 4) + i] = c[i] + b;
+            for (int i = 0; i < 4; ++i) qs[wave][tile_row(0, lane, i)] = c[i] + b;
         }
     }
     __syncthreads();
@@ -299,7 +288,7 @@ struct SacFinishArgs {
     float* result;
     int B, width, r_col, tuning;
     float target_entropy;
-    SacAdam adam;
+    AdamScalars adam;
 };
 
 __device__ __forceinline__ double sac_block_sum(double x, double* red) {
@@ -344,7 +333,7 @@ __global__ __launch_bounds__(kSacThreads) void sac_finish_kernel(const SacFinish
     if (a.tuning) {
         alpha_loss = (float)(-(sa / nb));
         const float g = (float)(-(st / nb));  // d alpha_loss / d log_alpha
-        const float ln = sac_adam(la, g, a.m, a.v, a.adam);
+        const float ln = adam_update(la, g, a.m, a.v, a.adam);
         *a.log_alpha = ln;
         alpha = expf(ln);
         *a.alpha = alpha;
@@ -378,8 +367,8 @@ struct SacLaunch {
         p.s[0] = s0;
         p.nseg = 1;
         p.M = M; p.N = N; p.out = out; p.ldo = ldo; p.aux = aux;
-        p.tiles_n = (N + kTile - 1) / kTile;
-        a.tile_start[a.np + 1] = a.tile_start[a.np] + ((M + kTile - 1) / kTile) * p.tiles_n;
+        p.tiles_n = tiles_across(N);
+        a.tile_start[a.np + 1] = a.tile_start[a.np] + tiles_across(M) * p.tiles_n;
         ++a.np;
         return p;
     }
@@ -399,18 +388,6 @@ struct SacLaunch {
         hipLaunchKernelGGL(sac_mm_kernel, dim3((unsigned)((tiles + kSacWaves - 1) / kSacWaves)), dim3(kSacThreads), 0, st, a);
     }
 };
-
-SacAdam adam_at(const double* h /* beta1, beta2, eps */, double lr, long long step) {
-    SacAdam a;
-    const double bc1 = 1.0 - std::pow(h[0], (double)step), bc2 = 1.0 - std::pow(h[1], (double)step);
-    a.one_minus_beta1 = (float)(1.0 - h[0]);
-    a.beta2 = (float)h[1];
-    a.one_minus_beta2 = (float)(1.0 - h[1]);
-    a.eps = (float)h[2];
-    a.neg_step_size = (float)(-(lr / bc1));
-    a.bc2_sqrt = (float)std::pow(bc2, 0.5);
-    return a;
-}
 
 inline size_t up4(size_t n) { return (n + 3) & ~(size_t)3; }
 
@@ -500,8 +477,9 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
     const float* one = e->sac_one.as<float>();
     const float *s = batch, *s2 = batch + row.c_next;
     const int r_col = row.c_rew;
-    const SacAdam ad_c = adam_at(sb.adam, lr_critic, step_critic + 1), ad_p = adam_at(sb.adam + 3, lr_policy, step_policy + 1),
-                  ad_a = adam_at(sb.adam + 6, lr_alpha, step_alpha + 1);
+    // optimizer o's (beta1, beta2, eps) are sb.adam[3 o ..]: the critic's, the policy's, alpha's
+    auto adam_of = [&](int o, double lr, long long steps_taken) { return adam_scalars(lr, sb.adam[3 * o], sb.adam[3 * o + 1], sb.adam[3 * o + 2], steps_taken + 1); };
+    const AdamScalars ad_c = adam_of(0, lr_critic, step_critic), ad_p = adam_of(1, lr_policy, step_policy), ad_a = adam_of(2, lr_alpha, step_alpha);
 
     // ---- 1. the policy's forward over [s'; s] and the sample tail ----
     {

@@ -3,7 +3,9 @@
 //   train_step_kernel  Model.update (mbrl/models/model.py:129-167) + torch.optim.Adam for a chunk of consecutive minibatches, one
 //                      instantiation per loss kind (NLL, MSE); a BasicEnsemble is per-member bounds and grad_scale = 1 / E
 //   train_eval_kernel  GaussianMLP.eval_score over the whole evaluation set (gaussian_mlp.py:337-361), mean columns only
-// Every product runs on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32 accumulate).
+// Every product runs on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32 accumulate): mm_tile is the k-loop, tile_walk.hpp the tiles'
+// numbering and the lane-to-element map, adam.hpp the optimizer's rule.  The host side by job: train_check (the arguments),
+// train_slab (train.hpp: the slab's layout), train_fill (what both argument blocks share), train_chunk and the chunk loop.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +14,7 @@
 
 #include "engine.hpp"
 #include "lds_optin.hpp"
+#include "tile_walk.hpp"
 #include "train.hpp"
 
 namespace hipets {
@@ -21,10 +24,12 @@ namespace {
 using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // One 16 x 16 tile of C = A . B (M x K by K x N), element (i, k) of A at A[i * sam + k * sak], (k, j) of B at B[k * sbk + j * sbn].
-// Lane l feeds A[m0 + (l & 15)][k + (l >> 4)] and B[k + (l >> 4)][n0 + (l & 15)]; the result is C[m0 + 4 (l >> 4) + i][n0 + (l & 15)]
-// in element i.  The operands come from L1 / L2 (or LDS) one float per lane, so the loop waits on load latency: kDeep blocks of 4
+// Lane l feeds A[m0 + (l & 15)][k + (l >> 4)] and B[k + (l >> 4)][n0 + (l & 15)]; the result lies as tile_walk.hpp says.
+// The operands come from L1 / L2 (or LDS) one float per lane, so the loop waits on load latency: kDeep blocks of 4
 // k-steps issue their 8 loads before their 4 MFMAs (forward and dA products), the others blocks of 2 (the dW product: the deeper
 // form there spilt SGPRs to scratch).  Two accumulators over alternate k-steps; out-of-range operands are zeros.
+// (sac.hip's sac_seg_acc is the other k-loop of the learning kernels and stays apart: lane group q takes k0 + q, k0 + 4 + q, ... here
+// and k0 + 4 q + s there, so the two sum along k in different orders -- other bits -- and load differently -- other speed.)
 template <bool kDeep>
 __device__ __forceinline__ f32x4 mm_tile(const float* __restrict__ A, int sam, int sak, int M, const float* __restrict__ B, int sbk, int sbn,
                                          int N, int K, int m0, int n0, int lane) {
@@ -103,18 +108,6 @@ __device__ __forceinline__ float softplus_grad(float x) {
     return z / (z + 1.f);
 }
 
-// torch.optim.Adam, non-fused single-tensor order (weight decay coupled into the gradient); returns the new parameter
-__device__ __forceinline__ float adam(float p, float g, float* m, float* v, const TrainStepArgs& a, float nss, float bc2s) {
-    g = g + a.weight_decay * p;
-    const float mo = *m, w = a.one_minus_beta1;
-    const float mn = w < 0.5f ? mo + w * (g - mo) : g - (g - mo) * (1.f - w);  // Tensor.lerp_
-    const float vn = *v * a.beta2 + a.one_minus_beta2 * g * g;
-    *m = mn;
-    *v = vn;
-    const float denom = sqrtf(vn) / bc2s + a.eps;
-    return p + nss * (mn / denom);
-}
-
 template <class T>
 __device__ __forceinline__ T wave_sum(T x) {
 #pragma unroll
@@ -132,10 +125,10 @@ __global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainSt
     const int e = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     constexpr int kWaves = kTrainThreads / 64;
     const int E = a.ensemble_size, L = a.n_layers, in = a.dims[0], out = a.out_dim, out2 = 2 * out, bmax = a.max_batch;
-    float* slab = a.slab + (int64_t)e * a.slab_stride;
-    float* A0 = slab + a.off_a[0];
-    float* T = slab + a.off_t;
-    float* O = slab + a.off_o;
+    float* slab = a.slab + (int64_t)e * a.at.stride;
+    float* A0 = slab + a.at.off_a[0];
+    float* T = slab + a.at.off_t;
+    float* O = slab + a.at.off_o;
     for (int s = 0; s < a.n_steps; ++s) {
         const int nb = min(max(a.rows[s], 1), bmax);
         const int32_t* ix = a.idx + ((int64_t)s * E + e) * bmax;
@@ -154,22 +147,22 @@ __global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainSt
         // ---- forward: Z_l = A_l W_l + b_l, A_{l+1} = act(Z_l); the output layer's raw columns go to O ----
         for (int l = 0; l < L; ++l) {
             const int din = a.dims[l], dout = a.dims[l + 1];
-            const float* Ain = slab + a.off_a[l];
+            const float* Ain = slab + a.at.off_a[l];
             const float* W = a.w[l] + (int64_t)e * din * dout;
             const float* bias = a.b[l] + (int64_t)e * dout;
             const bool hidden = l < L - 1;
-            float* Z = hidden ? slab + a.off_z[l] : O;
-            float* An = hidden ? slab + a.off_a[l + 1] : nullptr;
-            const int tn = (dout + 15) >> 4, tiles = ((nb + 15) >> 4) * tn;
+            float* Z = hidden ? slab + a.at.off_z[l] : O;
+            float* An = hidden ? slab + a.at.off_a[l + 1] : nullptr;
+            const int tn = tiles_across(dout), tiles = tiles_across(nb) * tn;
             for (int t = wave; t < tiles; t += kWaves) {
-                const int m0 = (t / tn) << 4, n0 = (t % tn) << 4;
+                const int m0 = tile_m0(t, tn), n0 = tile_n0(t, tn);
                 const f32x4 c = mm_tile<true>(Ain, din, 1, nb, W, dout, 1, dout, din, m0, n0, lane);
-                const int col = n0 + (lane & 15);
+                const int col = tile_col(n0, lane);
                 if (col < dout) {
                     const float bc = bias[col];
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {
-                        const int row = m0 + 4 * (lane >> 4) + i;
+                        const int row = tile_row(m0, lane, i);
                         if (row < nb) {
                             const float z = c[i] + bc;
                             Z[row * dout + col] = z;
@@ -180,7 +173,7 @@ __global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainSt
             }
             __syncthreads();
         }
-        float* D = slab + a.off_d0;
+        float* D = slab + a.at.off_d0;
         acc_t lsum = 0;
         if constexpr (kLoss == kTrainLossMSE) {
             // ---- MSE tail (gaussian_mlp.py:283-289): the plain sum of squared errors; O and D are [nb, out] ----
@@ -218,23 +211,23 @@ __global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainSt
         int cur = 0;
         for (int l = L - 1; l >= 0; --l) {
             const int din = a.dims[l], dout = a.dims[l + 1];
-            const float* Dc = slab + (cur ? a.off_d1 : a.off_d0);
-            float* Dn = slab + (cur ? a.off_d0 : a.off_d1);
+            const float* Dc = slab + (cur ? a.at.off_d1 : a.at.off_d0);
+            float* Dn = slab + (cur ? a.at.off_d0 : a.at.off_d1);
             const int64_t wo = (int64_t)e * din * dout;
             float* W = a.w[l] + wo;
             float* mW = a.mw[l] + wo;
             float* vW = a.vw[l] + wo;
             if (l > 0) {
-                const float* Zp = slab + a.off_z[l - 1];
-                const int tn = (din + 15) >> 4, tiles = ((nb + 15) >> 4) * tn;
+                const float* Zp = slab + a.at.off_z[l - 1];
+                const int tn = tiles_across(din), tiles = tiles_across(nb) * tn;
                 for (int t = wave; t < tiles; t += kWaves) {
-                    const int m0 = (t / tn) << 4, n0 = (t % tn) << 4;
+                    const int m0 = tile_m0(t, tn), n0 = tile_n0(t, tn);
                     const f32x4 c = mm_tile<true>(Dc, dout, 1, nb, W, 1, dout, din, dout, m0, n0, lane);
-                    const int col = n0 + (lane & 15);
+                    const int col = tile_col(n0, lane);
                     if (col < din) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            const int row = m0 + 4 * (lane >> 4) + i;
+                            const int row = tile_row(m0, lane, i);
                             if (row < nb) Dn[row * din + col] = c[i] * act_grad(a.activation, Zp[row * din + col], a.leaky_slope);
                         }
                     }
@@ -260,25 +253,27 @@ __global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainSt
                         for (int r = 0; r < nb; ++r) g += Dc[r * dout + j];
                     }
                     gsq += (acc_t)g * (acc_t)g;
-                    bias[j] = adam(bias[j], g, mB + j, vB + j, a, nss, bc2s);
+                    const float p = bias[j];
+                    bias[j] = adam_update(p, g + a.weight_decay * p, mB + j, vB + j, a.adam, nss, bc2s);  // (coupled weight decay)
                 }
             }
             __syncthreads();  // every read of the old W_l (dA above) is done
             {
-                const float* Ain = slab + a.off_a[l];
-                const int tn = (dout + 15) >> 4, tiles = ((din + 15) >> 4) * tn;
+                const float* Ain = slab + a.at.off_a[l];
+                const int tn = tiles_across(dout), tiles = tiles_across(din) * tn;
                 for (int t = wave; t < tiles; t += kWaves) {
-                    const int m0 = (t / tn) << 4, n0 = (t % tn) << 4;
+                    const int m0 = tile_m0(t, tn), n0 = tile_n0(t, tn);
                     const f32x4 c = mm_tile<false>(Ain, 1, din, din, Dc, dout, 1, dout, nb, m0, n0, lane);
-                    const int col = n0 + (lane & 15);
+                    const int col = tile_col(n0, lane);
                     if (col < dout) {
 #pragma unroll
                         for (int i = 0; i < 4; ++i) {
-                            const int row = m0 + 4 * (lane >> 4) + i;
+                            const int row = tile_row(m0, lane, i);
                             if (row < din) {
                                 const int64_t o = (int64_t)row * dout + col;
                                 gsq += (acc_t)c[i] * (acc_t)c[i];
-                                W[o] = adam(W[o], c[i], mW + o, vW + o, a, nss, bc2s);
+                                const float p = W[o];
+                                W[o] = adam_update(p, c[i] + a.weight_decay * p, mW + o, vW + o, a.adam, nss, bc2s);
                             }
                         }
                     }
@@ -336,16 +331,16 @@ __global__ __launch_bounds__(kEvalThreads) void train_eval_kernel(const TrainEva
         const int dout = hidden ? ld : out;
         const float* W = a.w[l] + (int64_t)e * din * ld;
         const float* bias = a.b[l] + (int64_t)e * ld;
-        const int tn = (dout + 15) >> 4, tiles = ((nr + 15) >> 4) * tn;
+        const int tn = tiles_across(dout), tiles = tiles_across(nr) * tn;
         for (int t = wave; t < tiles; t += kWaves) {
-            const int m0 = (t / tn) << 4, n0 = (t % tn) << 4;
+            const int m0 = tile_m0(t, tn), n0 = tile_n0(t, tn);
             const f32x4 c = mm_tile<true>(cur, din, 1, nr, W, ld, 1, dout, din, m0, n0, lane);
-            const int col = n0 + (lane & 15);
+            const int col = tile_col(n0, lane);
             if (col < dout) {
                 const float bc = bias[col];
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
-                    const int row = m0 + 4 * (lane >> 4) + i;
+                    const int row = tile_row(m0, lane, i);
                     if (row < nr) {
                         const float z = c[i] + bc;
                         if (hidden) {
@@ -422,10 +417,37 @@ int train_check(const hipets_train_desc* d, bool adam, int loss_kind) {
     return 0;
 }
 
-void train_dims(const hipets_train_desc* d, int loss_kind, int32_t* dims) {
-    dims[0] = d->in_dim;
-    for (int l = 1; l < d->n_layers; ++l) dims[l] = d->hid;
-    dims[d->n_layers] = loss_kind == HIPETS_TRAIN_LOSS_MSE ? d->out_dim : 2 * d->out_dim;
+// what TrainStepArgs and TrainEvalArgs share: the layers' widths and parameters, the dataset, the counts
+template <class Args>
+void train_fill(Args& a, const hipets_train_desc* d, int loss_kind, const float* x, const float* y, int64_t n_rows) {
+    a.dims[0] = d->in_dim;
+    for (int l = 1; l < d->n_layers; ++l) a.dims[l] = d->hid;
+    a.dims[d->n_layers] = loss_kind == HIPETS_TRAIN_LOSS_MSE ? d->out_dim : 2 * d->out_dim;
+    for (int l = 0; l < d->n_layers; ++l) {
+        a.w[l] = static_cast<float*>(d->weights[l]);
+        a.b[l] = static_cast<float*>(d->biases[l]);
+    }
+    a.x = x;
+    a.y = y;
+    a.n_rows = n_rows;
+    a.n_layers = d->n_layers;
+    a.out_dim = d->out_dim;
+    a.ensemble_size = d->ensemble_size;
+    a.activation = d->activation;
+    a.leaky_slope = d->leaky_slope;
+}
+
+// steps per launch: the caller's, or launches of ~50 ms at most: a step costs ~ 6 B P flops per member at the ~50 GFLOP/s per CU the
+// kernel reaches (measured at both halfcheetah shapes)
+int train_chunk(const hipets_train_desc* d, const int32_t* dims) {
+    int chunk = d->steps_per_launch;
+    if (chunk == 0) {
+        double params = 0.0;
+        for (int l = 0; l < d->n_layers; ++l) params += (double)dims[l] * dims[l + 1];
+        const double step_us = 20.0 + 6.0 * d->max_batch * params / 5.0e4;
+        chunk = (int)std::max(1.0, std::min((double)kTrainMaxSteps, 50000.0 / step_us));
+    }
+    return std::min(chunk, kTrainMaxSteps);
 }
 
 }  // namespace
@@ -478,63 +500,30 @@ int hipets_train_steps_loss(hipets_engine* e, const hipets_train_desc* d, const 
     ENTER_STREAM(e, st);
     TrainStepArgs a{};
     const int L = d->n_layers, E = d->ensemble_size, Bm = d->max_batch;
-    train_dims(d, loss_kind, a.dims);
-    int64_t off = 0, widest = 0;
-    auto take = [&](int64_t n) { const int64_t o = off; off += (n + 63) / 64 * 64; return o; };
-    for (int l = 0; l < L; ++l) a.off_a[l] = take((int64_t)Bm * a.dims[l]);
-    for (int l = 0; l + 1 < L; ++l) a.off_z[l] = take((int64_t)Bm * a.dims[l + 1]);
-    for (int l = 1; l <= L; ++l) widest = std::max<int64_t>(widest, a.dims[l]);
-    a.off_o = take((int64_t)Bm * a.dims[L]);
-    a.off_t = take((int64_t)Bm * d->out_dim);
-    a.off_d0 = take((int64_t)Bm * widest);
-    a.off_d1 = take((int64_t)Bm * widest);
-    a.slab_stride = off;
-    if (e->train_slab.ensure((size_t)E * off * sizeof(float))) return 1;
+    train_fill(a, d, loss_kind, x, y, n_rows);
+    a.at = train_slab(a.dims, L, d->out_dim, Bm);
+    if (e->train_slab.ensure((size_t)E * a.at.stride * sizeof(float))) return 1;
     a.slab = e->train_slab.as<float>();
     for (int l = 0; l < L; ++l) {
-        a.w[l] = static_cast<float*>(d->weights[l]);
-        a.b[l] = static_cast<float*>(d->biases[l]);
         a.mw[l] = static_cast<float*>(d->exp_avg_w[l]);
         a.mb[l] = static_cast<float*>(d->exp_avg_b[l]);
         a.vw[l] = static_cast<float*>(d->exp_avg_sq_w[l]);
         a.vb[l] = static_cast<float*>(d->exp_avg_sq_b[l]);
     }
-    a.x = x;
-    a.y = y;
     a.min_logvar = d->min_logvar;
     a.max_logvar = d->max_logvar;
     a.bounds_stride = bounds_per_member ? d->out_dim : 0;
     a.grad_scale = grad_scale;
-    a.n_rows = n_rows;
-    a.n_layers = L;
-    a.out_dim = d->out_dim;
-    a.ensemble_size = E;
     a.max_batch = Bm;
-    a.activation = d->activation;
-    a.leaky_slope = d->leaky_slope;
-    // torch passes these python floats to float32 tensor ops: one rounding each
-    a.weight_decay = (float)d->weight_decay;
-    a.one_minus_beta1 = (float)(1.0 - d->beta1);
-    a.beta2 = (float)d->beta2;
-    a.one_minus_beta2 = (float)(1.0 - d->beta2);
-    a.eps = (float)d->eps;
-    // launches of ~50 ms at most: a step costs ~ 6 B P flops per member at the ~50 GFLOP/s per CU the kernel reaches
-    // (measured at both halfcheetah shapes)
-    int chunk = d->steps_per_launch;
-    if (chunk == 0) {
-        double params = 0.0;
-        for (int l = 0; l < L; ++l) params += (double)a.dims[l] * a.dims[l + 1];
-        const double step_us = 20.0 + 6.0 * Bm * params / 5.0e4;
-        chunk = (int)std::max(1.0, std::min((double)kTrainMaxSteps, 50000.0 / step_us));
-    }
-    chunk = std::min(chunk, kTrainMaxSteps);
+    a.weight_decay = (float)d->weight_decay;  // (a python float handed to a float32 tensor op: one rounding)
+    a.adam = adam_scalars(d->lr, d->beta1, d->beta2, d->eps, step0 + 1);  // (the part no step changes)
+    const int chunk = train_chunk(d, a.dims);
     for (int s0 = 0; s0 < n_steps; s0 += chunk) {
         const int n = std::min(chunk, n_steps - s0);
-        for (int i = 0; i < n; ++i) {  // torch.optim.Adam (_single_tensor_adam): python-float bias corrections
-            const double t = (double)(step0 + s0 + i + 1);
-            const double bc1 = 1.0 - std::pow(d->beta1, t), bc2 = 1.0 - std::pow(d->beta2, t);
-            a.neg_step_size[i] = (float)(-(d->lr / bc1));
-            a.bc2_sqrt[i] = (float)std::pow(bc2, 0.5);
+        for (int i = 0; i < n; ++i) {
+            const AdamScalars ad = adam_scalars(d->lr, d->beta1, d->beta2, d->eps, step0 + s0 + i + 1);
+            a.neg_step_size[i] = ad.neg_step_size;
+            a.bc2_sqrt[i] = ad.bc2_sqrt;
         }
         a.n_steps = n;
         a.idx = idx + (int64_t)s0 * E * Bm;
@@ -562,26 +551,13 @@ int hipets_train_eval_loss(hipets_engine* e, const hipets_train_desc* d, const f
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
     TrainEvalArgs a{};
-    const int L = d->n_layers, E = d->ensemble_size;
-    train_dims(d, loss_kind, a.dims);
-    for (int l = 0; l < L; ++l) {
-        a.w[l] = static_cast<const float*>(d->weights[l]);
-        a.b[l] = static_cast<const float*>(d->biases[l]);
-    }
+    train_fill(a, d, loss_kind, x, y, n_rows);
     a.tiles = (int)((n_rows + kEvalRows - 1) / kEvalRows);
-    if (e->train_partial.ensure((size_t)E * a.tiles * sizeof(float))) return 1;
+    if (e->train_partial.ensure((size_t)d->ensemble_size * a.tiles * sizeof(float))) return 1;
     a.partial = e->train_partial.as<float>();
-    a.x = x;
-    a.y = y;
     a.order = order;
     a.row_score = row_score;
     a.score = score;
-    a.n_rows = n_rows;
-    a.n_layers = L;
-    a.out_dim = d->out_dim;
-    a.ensemble_size = E;
-    a.activation = d->activation;
-    a.leaky_slope = d->leaky_slope;
     a.max_width = std::max(std::max(d->in_dim, d->hid), d->out_dim);
     hipError_t err = launch_train_eval(a, st);
     if (err != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "train eval kernel launch failed: %s", hipGetErrorString(err));

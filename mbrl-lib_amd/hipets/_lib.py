@@ -48,6 +48,7 @@ MAX_OBS_COLUMNS = 512
 KERNEL_CLASSES = ("generic", "hidden_static", "fused", "wide", "bf16")  # HIPETS_KERNEL_*
 REDUCE = {"mean": 0, "mean_std": 1, "min": 2, "max": 3, "worst_k": 4}  # HIPETS_REDUCE_*
 POLICY_MAX_OBS, POLICY_MAX_HIDDEN, POLICY_MAX_ACT = 512, 1024, 32  # HIPETS_POLICY_MAX_*
+TRAIN_MAX_MEMBERS, TRAIN_MAX_HID, TRAIN_MAX_IN, TRAIN_MAX_OUT, TRAIN_MAX_BATCH = 16, 256, 512, 512, 256  # HIPETS_TRAIN_MAX_*
 SAC_N_PTRS, SAC_MAX_BATCH = 78, 1024  # HIPETS_SAC_N_PTRS, HIPETS_SAC_MAX_BATCH
 CRITIC_N_PTRS = 12  # HIPETS_CRITIC_N_PTRS
 

@@ -22,6 +22,8 @@ from typing import Callable, Dict, List, Optional, Tuple
 import numpy as np
 import torch
 
+from ._lib import (TRAIN_MAX_BATCH as MAX_BATCH, TRAIN_MAX_HID as MAX_HID, TRAIN_MAX_IN as MAX_IN, TRAIN_MAX_MEMBERS as MAX_MEMBERS,
+                   TRAIN_MAX_OUT as MAX_OUT)  # the library's shape limits (HIPETS_TRAIN_MAX_* of include/hipets.h) under this module's names
 from .model import UnsupportedModelError, _ACT_BY_CLASS
 
 # model_trainer.py:20-28 (the logger group's columns)
@@ -35,7 +37,6 @@ MODEL_LOG_FORMAT = [
     ("model_best_val_score", "MBVSCORE", "float"),
 ]
 
-MAX_MEMBERS, MAX_HID, MAX_IN, MAX_OUT, MAX_BATCH = 16, 256, 512, 512, 256
 _KEEP_STOCK = "; keep mbrl.models.ModelTrainer for this model"
 
 

@@ -23,29 +23,10 @@ def _host():
     return json.loads(bytes(z["meta_json"]).decode()), {k: z[k] for k in z.files if k != "meta_json"}
 
 
-class CpuEngine:
-    """Engine.train_steps / train_eval in float32 on the CPU through the restatement (host-logic tests only)."""
-
-    device = torch.device("cpu")
-
-    def train_steps(self, weights, biases, exp_avg, exp_avg_sq, lo, hi, x, y, idx, rows, step0, *, lr, betas=(0.9, 0.999), eps=1e-8,
-                    weight_decay=0.0, activation="silu", leaky_slope=0.01, steps_per_launch=0):
-        losses, gsqs = [], []
-        for s in range(idx.shape[0]):
-            sel = idx[s, :, :int(rows[s])].long()
-            l, g = tr.train_step(weights, biases, exp_avg, exp_avg_sq, x[sel], y[sel], lo.reshape(1, -1), hi.reshape(1, -1), activation,
-                                 step0 + s + 1, lr, weight_decay, eps, leaky_slope)
-            losses.append(l)
-            gsqs.append(g)
-        return torch.stack(losses), torch.stack(gsqs)
-
-    def train_eval(self, weights, biases, x, y, order=None, *, activation="silu", leaky_slope=0.01, row_scores=False):
-        score = tr.eval_score(weights, biases, x, y, activation, leaky_slope)
-        if not row_scores:
-            return score
-        xo, yo = (x[order.long()], y[order.long()]) if order is not None else (x, y)
-        _, _, o = tr.forward(weights, biases, xo.unsqueeze(0).expand(weights[0].shape[0], -1, -1), activation, leaky_slope)
-        return score, ((o[..., :y.shape[1]] - yo) ** 2).sum(-1)
+def CpuEngine():
+    """Engine.train_steps / train_eval in float32 on the CPU through the restatement (host-logic tests only), with the keywords the
+    engine had before the loss kinds and no others."""
+    return tr.CpuEngine(kinds=False)
 
 
 @pytest.mark.parametrize("act", tr.ACTS)

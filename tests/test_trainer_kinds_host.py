@@ -292,6 +292,13 @@ def test_header_and_binding_carry_the_new_entry_points():
     assert [n for n, _ in _lib.SYMBOLS["hipets_train_steps_loss"][1]][:12] == [n for n, _ in _lib.SYMBOLS["hipets_train_steps"][1]]
     assert [n for n, _ in _lib.SYMBOLS["hipets_train_eval_loss"][1]][:9] == [n for n, _ in _lib.SYMBOLS["hipets_train_eval"][1]]
     assert _lib.ABI_VERSION == 9 and _lib.TRAIN_LOSS == {"nll": 0, "mse": 1}
+    # the trainer's shape limits: one macro each, mirrored by the binding, read from there by the trainer, used by the kernels' host side
+    hpp = open(os.path.join(ROOT, "mbrl-lib_amd", "csrc", "train.hpp")).read()
+    for name, alias in (("MEMBERS", "MAX_MEMBERS"), ("HID", "MAX_HID"), ("IN", "MAX_IN"), ("OUT", "MAX_OUT"), ("BATCH", "MAX_BATCH")):
+        macro = re.search(r"^#define HIPETS_TRAIN_MAX_" + name + r" (\d+)$", src, flags=re.M)
+        assert macro, name
+        assert int(macro.group(1)) == getattr(_lib, "TRAIN_MAX_" + name) == getattr(hipets.trainer, alias), name
+        assert re.search(r"constexpr int kTrainMax\w+ = HIPETS_TRAIN_MAX_" + name + r";", hpp), name
 
 
 # ---- the restatements against the reference's own update ------------------------------------------------------------------------
