@@ -872,6 +872,63 @@ int hipets_discounted_returns(hipets_engine* e, const float* rewards, const uint
                               int32_t pop, int32_t horizon, int32_t num_particles, float* returns, float* row_totals, int32_t* first_done,
                               void* stream);
 
+/* ---- ensemble predictions and uncertainty: what every member predicts for a batch, and how much they disagree ----
+ * Additive entry points: the descriptor hipets_set_model takes, scalars and pointers; no struct changes, HIPETS_ABI_VERSION stays.
+ *
+ * GaussianMLP.forward(x, use_propagation=False) (mbrl/models/gaussian_mlp.py:140-154, 277-281), BasicEnsemble._default_forward
+ * (basic_ensemble.py:94-99) and OneDTransitionRewardModel.forward over _get_model_input (one_dim_tr_model.py:103-116, 138-140): every
+ * requested member's forward of the SAME rows in one launch.  All products are fp32 MFMA with fp32 accumulation; bias, activation
+ * (every HIPETS_ACT_*, leaky_slope for LEAKY_RELU; SiLU and sigmoid through the hardware's exp2 and reciprocal, as the rollout
+ * kernels compute them) and the head fp32 op by op.  The head is gaussian_mlp.py:150-153 literally:
+ *     mean = out[..., :out_dim];  logvar = max_logvar - softplus(max_logvar - out[..., out_dim:]);  logvar = min_logvar + softplus(logvar - min_logvar)
+ * with F.softplus's definition (beta 1, threshold 20); the bounds are per member for HIPETS_ENSEMBLE_BASIC and shared otherwise; a
+ * deterministic model has no log-variance head.
+ *
+ * hipets_ensemble_set takes the descriptor of hipets_set_model / hipets_set_model_columns (cols / n_cols: the column table of a
+ * HIPETS_OBS_COLUMNS model, NULL / 0 for every other obs_process) and keeps a SNAPSHOT of its own -- all ensemble_size members' weights
+ * and biases, the normaliser, the bounds, the member list (the elite set), the column table -- apart from the rollout model: with or
+ * without an ensemble snapshot every other call behaves as before, and the model set by hipets_set_model is not touched.  fp32 only:
+ * HIPETS_PREC_BF16X3 / HIPETS_PREC_BF16 are refused, and so are ensemble_size > 16, in_dim > 512, out_dim > 512 (the
+ * HIPETS_ENSEMBLE_MAX_* limits below), hid > HIPETS_POLICY_MAX_HIDDEN and a shape whose LDS need at one row tile -- 16 rows x (pad16(in_dim) + 4 [the kept input] + pad16(hid) + 4 +
+ * max(pad16(hid), pad16(out_total)) + 4 [the two activation buffers] + 2 out_dim [the per-row accumulators]) floats -- exceeds the LDS
+ * opt-in limit (HIPETS_ERR_INVALID_ARGUMENT).  The reward / termination fields of the descriptor are not read.  A refused set leaves the
+ * engine without an ensemble.  Synchronises `stream` before it returns.                                                              */
+#define HIPETS_ENSEMBLE_MAX_MEMBERS 16
+#define HIPETS_ENSEMBLE_MAX_IN 512
+#define HIPETS_ENSEMBLE_MAX_OUT 512
+int hipets_ensemble_set(hipets_engine* e, const hipets_model_desc* desc, const hipets_obs_column* cols, int32_t n_cols, void* stream);
+/* One launch over `batch` >= 1 rows and n members: all ensemble_size members in index order (only_elite == 0), or the n_members of the
+ * descriptor's member list in list order.  The model input is EITHER built from obs DEVICE [batch, obs_dim] and actions DEVICE [batch,
+ * act_dim] -- obs_process, concatenation, the normaliser in the descriptor's dtype (HIPETS_NORM_F64: (x - mean) * (1 / std) in f64, as
+ * the rollout kernels form it) -- with model_in NULL, OR read from model_in DEVICE [batch, in_dim] (what forward(x) takes) with obs and
+ * actions NULL; it is built once per workgroup and kept for all members.  Outputs, DEVICE f32, each optional (NULL = not wanted; all
+ * NULL is an error, and so is logvar for a deterministic model):
+ *   mean [n, batch, out_dim], logvar [n, batch, out_dim]
+ *   stats [batch, 4], reduced over the n members and all out_dim columns inside the launch:
+ *     [0] max_std       = max_m sqrt(sum_d exp(logvar[m, d]))            (MOPO's penalty; 0 for a deterministic model)
+ *     [1] disagreement  = sqrt(sum_d Var_m(mean[m, d]))                  (population variance: divided by n)
+ *     [2] total_std     = sqrt(sum_d (Var_m(mean[m, d]) + mean_m exp(logvar[m, d])))   (the mixture's predictive std; = [1] if deterministic)
+ *     [3] max_deviation = max_m sqrt(sum_d (mean[m, d] - mean[0, d])^2)  (the farthest member from the first requested one: a one-pass
+ *                         discrepancy in the spirit of MOReL's)
+ *   The variance is accumulated about the first requested member's mean (shifted sums), never as E[x^2] - E[x]^2 of the raw means.
+ * A row's arithmetic depends neither on the batch it arrives in, nor on the row tiles of the launch, nor on which outputs are
+ * requested; a NaN or inf in a row stays in that row (the two maxima follow torch.max: a NaN wins).                                  */
+int hipets_ensemble_predict(hipets_engine* e, const float* obs, const float* actions, const float* model_in, int32_t batch, int32_t only_elite,
+                            float* mean, float* logvar, float* stats, void* stream);
+/* Launch geometry of hipets_ensemble_predict for `batch` rows of the ensemble set last, the actor's rule (hipets_policy_geometry): a
+ * workgroup owns 16 * row_tiles rows, row_tiles = the largest of 4, 2, 1 whose LDS need (hipets_ensemble_set) fits the opt-in limit, no
+ * more than the batch needs; lds_bytes = its dynamic LDS.                                                                            */
+int hipets_ensemble_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles, int32_t* lds_bytes);
+/* An uncertainty penalty and halt on a model step's rewards and dones (MOPO's r - lambda u; MOReL's halt): one elementwise launch over
+ * stats DEVICE [batch, 4] (hipets_ensemble_predict), rewards DEVICE [batch] f32 and dones DEVICE [batch] uint8, both updated in place.
+ * Per row, every line ONE float32 operation (no fused multiply-add), with u = stats[row * 4 + stat] (stat in 0 .. 3):
+ *     p = coef * u;  rewards[row] = rewards[row] - p
+ *     if halt_threshold is not NaN and u > halt_threshold:  dones[row] = 1, and with use_halt_reward: rewards[row] = halt_reward
+ * A NaN u never halts; it makes the reward NaN through the subtraction (coef * NaN is NaN, for coef == 0 too).  dones may be NULL when
+ * halt_threshold is NaN.  Needs no model.                                                                                                                    */
+int hipets_uncertainty_penalty(hipets_engine* e, const float* stats, int32_t stat, float coef, float halt_threshold, float halt_reward,
+                               int32_t use_halt_reward, int32_t batch, float* rewards, uint8_t* dones, void* stream);
+
 /* ---- instrumentation (bench.py roofline leg) ----------------------------------------------- */
 /* on = 1: every rollout-kernel launch carries a start / stop hipEvent pair on its dispatch packet; on = k > 1: every
  * k-th launch does (a completion signal per packet costs a few microseconds between back-to-back short launches -- the

@@ -119,7 +119,8 @@ void hipets_destroy(hipets_engine* e) {
     for (DevBuf* b : {&e->w3pack, &e->wpack, &e->bpack, &e->layer_meta, &e->norm_mean, &e->norm_std, &e->min_lv, &e->max_lv, &e->no_delta, &e->members,
                       &e->s0, &e->state, &e->totals, &e->term, &e->exchange, &e->step_keys, &e->plan_keys, &e->mu, &e->disp, &e->population, &e->values,
                       &e->best_value, &e->best_solution, &e->past_action, &e->kept, &e->elite_idx, &e->keep_idx, &e->planet_w, &e->planet_b, &e->planet_member, &e->planet_ops, &e->shard_values, &e->gathered, &e->census, &e->train_slab, &e->train_partial,
-                      &e->policy.w, &e->policy.b, &e->compact_counts, &e->sac_ws, &e->sac_one, &e->critic.w, &e->critic.b})
+                      &e->policy.w, &e->policy.b, &e->compact_counts, &e->sac_ws, &e->sac_one, &e->critic.w, &e->critic.b,
+                      &e->ensemble.w, &e->ensemble.b, &e->ensemble.norm, &e->ensemble.lv, &e->ensemble.cols})
         b->release();
     for (auto& ev : e->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (auto& ev : e->event_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }

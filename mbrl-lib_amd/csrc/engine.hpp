@@ -1,5 +1,5 @@
 // engine.hpp -- private to the host units of the C ABI (include/hipets.h): engine.hip, model.hip, rollout.hip, plan.hip, comm.hip,
-// train.hip, policy.hip, replay.hip, sac.hip and value.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
+// train.hip, policy.hip, replay.hip, sac.hip, value.hip and ensemble.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
 // Host code only; nothing declared here is part of the ABI (hidden visibility).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -64,6 +64,19 @@ struct DevBuf {
 
 // a network's weights as hipets_policy_set / hipets_critic_set packed them (policy_layer.hpp): is one set, its sizes, image and biases
 struct MlpSnapshot { bool set = false; int obs = 0, hid = 0, act = 0; DevBuf w, b; };
+
+// what hipets_ensemble_set keeps (ensemble.hip): the dynamics ensemble's shape, every member's padded W[k][n] images and biases (member e, layer
+// l at e * wmember + its layer offset), the normaliser (mean, std, 1 / std: [3][in_dim] doubles), the log-variance bounds (min rows, then
+// max rows: lv_rows each, indexed by member where every member owns its own), the elite list and the column table
+struct EnsembleSnapshot {
+    bool set = false;
+    int E = 0, M = 0, obs_dim = 0, act_dim = 0, in_dim = 0, out_dim = 0, hid = 0, n_layers = 0;
+    int activation = 0, obs_process = 0, normalizer = 0, deterministic = 0, lv_rows = 1;
+    float slope = 0.f;
+    int members[HIPETS_ENSEMBLE_MAX_MEMBERS] = {};
+    size_t wmember = 0, bmember = 0;
+    DevBuf w, b, norm, lv, cols;
+};
 
 // what hipets_sac_bind keeps: the agent's sizes and hyper-parameters, its optimizers' (beta1, beta2, eps) [critic, policy, alpha], and the
 // pointer table (the live torch tensors, include/hipets.h)
@@ -147,6 +160,8 @@ struct hipets_engine {
     hipets::SacBind sac{};
     int sac_last_batch = 0;
     DevBuf sac_ws, sac_one;
+    // the dynamics ensemble as hipets_ensemble_set packed it (hipets_ensemble_predict, ensemble.hip); apart from the rollout model slot above
+    hipets::EnsembleSnapshot ensemble;
 };
 
 #pragma GCC visibility push(hidden)

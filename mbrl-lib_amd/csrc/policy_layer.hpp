@@ -104,6 +104,71 @@ __device__ __forceinline__ void policy_layer(const float* __restrict__ in, const
     }
 }
 
+// policy_layer's sibling for a network whose activation is a run-time fact (the dynamics ensemble, ensemble.hip): the same products in
+// the same order into the same accumulators -- the kAhead form always -- and out = post(acc + bias), `post` a callable on the f32x4 a
+// lane holds of one row tile (4 rows of one column; the identity for a network's last layer), so that a run-time switch over the
+// activation is taken once per four values.  policy_layer itself is left as it is: the kernels built on it keep their code.
+template <int R, int kAhead, class Post>
+__device__ __forceinline__ void mlp_layer_post(const float* __restrict__ in, const int ld_in, const int kp, const float* __restrict__ W,
+                                               const float* __restrict__ bias, const int np, float* __restrict__ out, const int ld_out, const int wave,
+                                               const int lane, const Post post) {
+    static_assert(kAhead > 1, "the plain loop alone is policy_layer<R, kRelu, 1>");
+    const int r = lane & 15, q = lane >> 4;
+    for (int n0 = wave * kTile; n0 < np; n0 += kPolicyWaves * kTile) {
+        f32x4 c0[R], c1[R];
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            c0[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+            c1[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+        const float* wp = W + (size_t)(4 * q) * np + n0 + r;
+        const float* ap = in + r * ld_in + 4 * q;
+        int k_done = 0;
+        for (; k_done + kAhead * kKChunk <= kp; k_done += kAhead * kKChunk) {
+            float bv[kAhead][4];
+#pragma unroll
+            for (int u = 0; u < kAhead; ++u) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) bv[u][s] = wp[(size_t)(u * kKChunk) * np + (size_t)s * np];
+            }
+#pragma unroll
+            for (int u = 0; u < kAhead; ++u) {
+#pragma unroll
+                for (int i = 0; i < R; ++i) {
+                    const f32x4 av = *reinterpret_cast<const f32x4*>(ap + i * kTile * ld_in + u * kKChunk);
+                    c0[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], bv[u][0], c0[i], 0, 0, 0);
+                    c1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], bv[u][1], c1[i], 0, 0, 0);
+                    c0[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], bv[u][2], c0[i], 0, 0, 0);
+                    c1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], bv[u][3], c1[i], 0, 0, 0);
+                }
+            }
+            wp += (size_t)(kAhead * kKChunk) * np;
+            ap += kAhead * kKChunk;
+        }
+#pragma unroll 2
+        for (int k0 = k_done; k0 < kp; k0 += kKChunk) {
+            const float b0 = wp[0], b1 = wp[np], b2 = wp[2 * np], b3 = wp[3 * np];
+#pragma unroll
+            for (int i = 0; i < R; ++i) {
+                const f32x4 av = *reinterpret_cast<const f32x4*>(ap + i * kTile * ld_in);
+                c0[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[0], b0, c0[i], 0, 0, 0);
+                c1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[1], b1, c1[i], 0, 0, 0);
+                c0[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[2], b2, c0[i], 0, 0, 0);
+                c1[i] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[3], b3, c1[i], 0, 0, 0);
+            }
+            wp += (size_t)kKChunk * np;
+            ap += kKChunk;
+        }
+        const float bc = bias[n0 + r];
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+            const f32x4 c = post(c0[i] + c1[i] + f32x4{bc, bc, bc, bc});
+#pragma unroll
+            for (int j = 0; j < 4; ++j) out[(i * kTile + 4 * q + j) * ld_out + n0 + r] = c[j];
+        }
+    }
+}
+
 // nn.Linear's [N, K] -> packed[k][col0 + n] of a zeroed [Kp][np] image
 __global__ void policy_pack_kernel(float* dst, const float* src, int K, int N, int np, int col0) {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;

@@ -55,6 +55,7 @@ from .mbpo import rollout_model_and_populate_sac_buffer  # noqa: F401
 from .replay import DeviceReplayBuffer, maybe_replace_sac_buffer  # noqa: F401
 from .sac import SACActor, SACCritic, SACUpdater, make_sac_updater  # noqa: F401
 from .value import ValueTrajectoryEvalFn  # noqa: F401
+from .ensemble import EnsemblePredictor, UncertaintyPenalty  # noqa: F401
 from . import dist  # noqa: F401
 
 __version__ = "0.1.0"

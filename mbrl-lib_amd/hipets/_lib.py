@@ -51,6 +51,8 @@ POLICY_MAX_OBS, POLICY_MAX_HIDDEN, POLICY_MAX_ACT = 512, 1024, 32  # HIPETS_POLI
 TRAIN_MAX_MEMBERS, TRAIN_MAX_HID, TRAIN_MAX_IN, TRAIN_MAX_OUT, TRAIN_MAX_BATCH = 16, 256, 512, 512, 256  # HIPETS_TRAIN_MAX_*
 SAC_N_PTRS, SAC_MAX_BATCH = 78, 1024  # HIPETS_SAC_N_PTRS, HIPETS_SAC_MAX_BATCH
 CRITIC_N_PTRS = 12  # HIPETS_CRITIC_N_PTRS
+ENSEMBLE_MAX_MEMBERS, ENSEMBLE_MAX_IN, ENSEMBLE_MAX_OUT = 16, 512, 512  # HIPETS_ENSEMBLE_MAX_*
+ENSEMBLE_STATS = ("max_std", "disagreement", "total_std", "max_deviation")  # columns of hipets_ensemble_predict's stats
 
 
 class RewardTermC(C.Structure):  # hipets_reward_term
@@ -252,6 +254,11 @@ SYMBOLS = {
     "hipets_critic_geometry": _sig("e batch:i32 row_tiles:i32* lds_bytes:i32*"),
     "hipets_discounted_returns": _sig("e rewards dones terminal_values gamma:f32 pop:i32 horizon:i32 num_particles:i32 returns row_totals "
                                       "first_done stream"),
+    "hipets_ensemble_set": _sig("e desc:ModelDesc* cols:ObsColumnC* n_cols:i32 stream"),
+    "hipets_ensemble_predict": _sig("e obs actions model_in batch:i32 only_elite:i32 mean logvar stats stream"),
+    "hipets_ensemble_geometry": _sig("e batch:i32 row_tiles:i32* lds_bytes:i32*"),
+    "hipets_uncertainty_penalty": _sig("e stats stat:i32 coef:f32 halt_threshold:f32 halt_reward:f32 use_halt_reward:i32 batch:i32 rewards dones "
+                                       "stream"),
     "hipets_timing_enable": _sig("e on:i32"),
     "hipets_timing_read": _sig("e launches:i64* total_ms:f64* reset:i32"),
 }

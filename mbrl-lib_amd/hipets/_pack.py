@@ -111,6 +111,31 @@ def pack_model_desc(spec: ModelSpec, ws, bs):
     return d, cols, keep
 
 
+def ensemble_lds_bytes(in_dim: int, hid: int, out_dim: int, deterministic: bool, n_layers: int, row_tiles: int = 1) -> int:
+    """Dynamic LDS of a hipets_ensemble_predict workgroup of ``row_tiles`` row tiles (csrc/ensemble.hip ensemble_geo): per row the kept
+    input (pad16(in) + 4 floats), the two activation buffers (pad16(hid) + 4 and max(pad16(hid), pad16(out_total)) + 4) and the two
+    per-column accumulators (2 out_dim); ``n_layers`` does not enter (it only decides which buffer is the wide one)."""
+    pad16 = lambda x: (int(x) + 15) // 16 * 16  # noqa: E731
+    hp, npo = pad16(hid), pad16(out_dim if deterministic else 2 * out_dim)
+    return 16 * 4 * (pad16(in_dim) + 4 + hp + 4 + max(hp, npo) + 4 + 2 * int(out_dim)) * int(row_tiles)
+
+
+def check_ensemble_shape(spec: ModelSpec, lds_max: int = 160 * 1024):
+    """What hipets_ensemble_set refuses, told without a device: raises UnsupportedModelError naming the reason (fp32 only, E <= 16,
+    in_dim / out_dim <= 512, hid <= 1024, one row tile within ``lds_max`` bytes of LDS)."""
+    from .model import UnsupportedModelError
+
+    if spec.precision != "f32":
+        raise UnsupportedModelError(f"ensemble predictions run in fp32 only: precision {spec.precision!r} has no ensemble kernel")
+    for what, v, lim in (("ensemble_size", spec.ensemble_size, _lib.ENSEMBLE_MAX_MEMBERS), ("in_dim", spec.in_dim, _lib.ENSEMBLE_MAX_IN),
+                         ("out_dim", spec.out_dim, _lib.ENSEMBLE_MAX_OUT), ("hidden width", spec.hid, _lib.POLICY_MAX_HIDDEN)):
+        if v > lim:
+            raise UnsupportedModelError(f"ensemble {what} {v} above {lim}")
+    need = ensemble_lds_bytes(spec.in_dim, spec.hid, spec.out_dim, spec.deterministic, len(spec.weights))
+    if need > lds_max:
+        raise UnsupportedModelError(f"ensemble too wide for LDS: one row tile needs {need} bytes, the limit is {lds_max}")
+
+
 def pack_planet_desc(spec, tensors):
     """hipets_planet_desc of a ``PlaNetSpec`` over its converted tensors (``_lib._PLANET_TENSORS`` order) -> (desc, keep-alive list)"""
     d = _lib.PlanetDesc(latent_size=spec.latent_size, action_size=spec.action_size, belief_size=spec.belief_size, hidden_size=spec.hidden_size,

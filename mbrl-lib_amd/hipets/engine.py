@@ -10,7 +10,7 @@ import torch
 
 from . import _lib
 from ._lib import CemParams, HipetsError
-from ._pack import (_check_dev, check_critic_split, check_discount, member_slots, pack_critic, pack_model_desc, pack_plan_trace,  # noqa: F401
+from ._pack import (_check_dev, check_critic_split, check_discount, check_ensemble_shape, member_slots, pack_critic, pack_model_desc, pack_plan_trace,  # noqa: F401
                     pack_planet_desc, pack_reward_terms, pack_policy, pack_rollout_opts, pack_train_desc, row_width)
 from .model import ModelSpec
 from .reduce import ParticleReduce
@@ -50,6 +50,8 @@ class Engine:
     # agent -- and the SAC updates run so far.  (Class level: an Engine made without __init__ answers "has not been called" too.)
     policy_dims = policy_owner = critic_dims = critic_owner = sac_dims = sac_owner = None
     sac_updates = 0
+    # the ensemble slot (hipets.ensemble): the spec whose snapshot hipets_ensemble_set took, and its owner (a weakref)
+    ensemble_spec = ensemble_owner = None
 
     def __init__(self, device="cuda:0"):
         self.device = torch.device(device)
@@ -886,6 +888,80 @@ class Engine:
         self._call("hipets_discounted_returns", rewards=rewards, dones=dones, terminal_values=terminal_values, gamma=gamma, pop=int(pop), horizon=H,
                    num_particles=int(num_particles), returns=out, row_totals=tot, first_done=first)
         return (out, tot, first) if (row_totals or first_done) else out
+
+    # ---- ensemble predictions and uncertainty (hipets_ensemble_* / hipets_uncertainty_penalty) ------------------------------------
+    def ensemble_set(self, spec: ModelSpec):
+        """Snapshot ``spec`` -- every member, the normaliser, the bounds, the elite list -- into the engine's ensemble slot
+        (hipets_ensemble_set), apart from the rollout model of :meth:`set_model`.  A shape the kernel does not cover raises
+        UnsupportedModelError before anything is called; a refused set leaves the slot empty."""
+        spec.validate()
+        check_ensemble_shape(spec)
+        ws = [w.detach().to(device=self.device, dtype=torch.float32).contiguous() for w in spec.weights]
+        bs = [b.detach().to(device=self.device, dtype=torch.float32).contiguous() for b in spec.biases]
+        d, cols, keep = pack_model_desc(spec, ws, bs)
+        self.ensemble_spec = self.ensemble_owner = None
+        self._call("hipets_ensemble_set", desc=d, cols=cols, n_cols=0 if cols is None else len(cols))
+        del keep
+        self.ensemble_spec = spec
+
+    def _ensemble_spec(self) -> ModelSpec:
+        if self.ensemble_spec is None:
+            raise HipetsError("Engine.ensemble_set() has not been called")
+        return self.ensemble_spec
+
+    def ensemble_predict(self, obs: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None, *,
+                         model_in: Optional[torch.Tensor] = None, only_elite: bool = False, mean: bool = True, logvar: bool = True,
+                         stats: bool = False):
+        """Every requested member's forward of the same rows in one launch (hipets_ensemble_predict): from ``obs`` f32 [B, obs_dim] and
+        ``actions`` f32 [B, act_dim], or from a ready ``model_in`` f32 [B, in_dim].  Returns (mean [n, B, out_dim], logvar [n, B,
+        out_dim], stats [B, 4]) on the device, None for an output not wanted; n = all members, or with ``only_elite`` the spec's
+        member list.  The columns of ``stats``: ``_lib.ENSEMBLE_STATS``."""
+        spec, dev = self._ensemble_spec(), self.device
+        raw = obs is not None or actions is not None
+        if raw == (model_in is not None) or (raw and (obs is None or actions is None)):
+            raise ValueError("give either obs and actions, or model_in")
+        first = model_in if model_in is not None else obs
+        if not isinstance(first, torch.Tensor) or first.ndim != 2 or int(first.shape[0]) < 1:
+            raise ValueError("the input must be a [B, width] tensor with B >= 1")
+        B = int(first.shape[0])
+        if model_in is not None:
+            _check_dev(model_in, torch.float32, dev, "model_in", (B, spec.in_dim))
+        else:
+            _check_dev(obs, torch.float32, dev, "obs", (B, spec.obs_dim))
+            _check_dev(actions, torch.float32, dev, "actions", (B, spec.act_dim))
+        if logvar and spec.deterministic:
+            raise ValueError("a deterministic model has no log-variance head")
+        n = len(spec.members) if only_elite else spec.ensemble_size
+        out = [torch.empty(shape, dtype=torch.float32, device=dev) if want else None
+               for want, shape in ((mean, (n, B, spec.out_dim)), (logvar, (n, B, spec.out_dim)), (stats, (B, 4)))]
+        self._call("hipets_ensemble_predict", obs=obs, actions=actions, model_in=model_in, batch=B, only_elite=int(bool(only_elite)),
+                   mean=out[0], logvar=out[1], stats=out[2])
+        return tuple(out)
+
+    def ensemble_geometry(self, batch: int):
+        """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of an :meth:`ensemble_predict` of ``batch`` rows."""
+        self._ensemble_spec()
+        return self._geometry("hipets_ensemble_geometry", batch)
+
+    def uncertainty_penalty(self, stats: torch.Tensor, stat: int, coef: float, rewards: torch.Tensor, dones: Optional[torch.Tensor] = None, *,
+                            halt_threshold: Optional[float] = None, halt_reward: Optional[float] = None):
+        """``rewards`` f32 [B] -= coef * stats[:, stat], in place; with ``halt_threshold`` the rows above it get ``dones`` (uint8 or bool
+        [B], in place) = 1 and, with ``halt_reward``, that reward (hipets_uncertainty_penalty; one launch, bit for bit
+        tests/ensemble_restatement.penalty_np)."""
+        dev = self.device
+        B = int(rewards.numel())
+        _check_dev(stats, torch.float32, dev, "stats", (B, 4))
+        _check_dev(rewards, torch.float32, dev, "rewards", numel=B)
+        if dones is not None:
+            if dones.dtype == torch.bool:
+                dones = dones.view(torch.uint8)  # (one byte per element, 0 / 1)
+            _check_dev(dones, torch.uint8, dev, "dones", numel=B)
+        elif halt_threshold is not None:
+            raise ValueError("a halt threshold needs dones")
+        self._call("hipets_uncertainty_penalty", stats=stats, stat=int(stat), coef=float(coef),
+                   halt_threshold=float("nan") if halt_threshold is None else float(halt_threshold),
+                   halt_reward=0.0 if halt_reward is None else float(halt_reward), use_halt_reward=int(halt_reward is not None), batch=B,
+                   rewards=rewards, dones=dones)
 
     def timing_enable(self, on=True):
         """True / 1: time every rollout-kernel launch; k > 1: every k-th launch; False / 0: off."""

@@ -41,6 +41,38 @@ def _hip_env(model_env):
     return env
 
 
+class PenalisedEnv:
+    """A view of a ``hipets.ModelEnv`` whose ``step`` applies an :class:`hipets.UncertaintyPenalty` (one statistics launch of the
+    ensemble kernel on the step's (obs, action), one penalty launch on its rewards and dones).  The environment itself is not changed:
+    whoever else holds it steps it unpenalised, and its counters and streams advance whichever of the two is stepped."""
+
+    def __init__(self, env, penalty):
+        from .ensemble import EnsemblePredictor
+
+        self.env, self.penalty = env, penalty
+        self.predictor = EnsemblePredictor(env, engine=env.engine)  # (UnsupportedModelError for a model the kernel does not cover)
+        self.engine, self.device = env.engine, env.device
+
+    def reset(self, *args, **kwargs):
+        return self.env.reset(*args, **kwargs)
+
+    def step(self, actions, model_state, sample: bool = False):
+        return self.env._step(actions, model_state, sample, self.predictor, self.penalty)
+
+
+def _penalised(env, penalty):
+    """the penalised view of ``env`` for ``penalty``, made once per pair and kept with the environment (its step is not touched); an
+    environment that carries that very penalty is its own"""
+    if getattr(env, "uncertainty", None) == penalty:
+        return env
+    if not hasattr(env, "_step"):
+        raise UnsupportedModelError("the model environment has no step that takes an uncertainty penalty")
+    views = env.__dict__.setdefault("_penalised_views", {})  # (a global weak map would keep every environment alive: a view holds its own)
+    if penalty not in views:
+        views[penalty] = PenalisedEnv(env, penalty)
+    return views[penalty]
+
+
 def _actor(agent, engine) -> SACActor:
     if isinstance(agent, SACActor):
         return agent
@@ -98,7 +130,7 @@ def _host_copy(env, buf: torch.Tensor) -> np.ndarray:
 
 
 def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_buffer, sac_samples_action: bool, rollout_horizon: int,
-                                          batch_size: int):
+                                          batch_size: int, *, uncertainty=None):
     """``mbrl.algorithms.mbpo.rollout_model_and_populate_sac_buffer`` (mbpo.py:31-63), same signature.  ``model_env``: a
     ``hipets.ModelEnv``, or a live ``mbrl.models.ModelEnv`` (wrapped once, cached); ``agent``: what :class:`SACActor` takes, or a
     SACActor.  ``replay_buffer.sample`` stays on the host (the buffer's RNG is consumed as the reference consumes it) and the initial
@@ -111,17 +143,32 @@ def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_b
     ``sac_buffer`` a :class:`hipets.DeviceReplayBuffer` on the environment's engine: every step's compaction goes straight into the
     buffer's ring (``Engine.ring_compact_transitions``) -- no staging area, no bulk copy, no ``add_batch``; the call ends in one copy
     of the buffer's cursor and the per-step counts (kept in ``sac_buffer.last_populate_counts``) and sets its ``cur_idx`` /
-    ``num_stored``.  A batch larger than the buffer's capacity is a ValueError."""
+    ``num_stored``.  A batch larger than the buffer's capacity is a ValueError.
+
+    ``uncertainty`` (keyword only; not in the reference): a :class:`hipets.UncertaintyPenalty`.  The rollout steps then run through a
+    penalised view of the environment (:class:`PenalisedEnv`, made once per environment and penalty; the environment itself stays as
+    it is): after every model step one statistics launch of the ensemble kernel on the step's (obs, action) and one penalty launch on
+    its rewards and dones, so both the staging area and the ring store the penalised rewards and dones, and a halted row is stored
+    once and dropped from the later steps.  The reference-loop fall-backs step the same penalised view; a model the ensemble kernel
+    does not cover runs the reference's loop, with one warning, over the live model's own torch forward
+    (:class:`hipets.ensemble.ReferencePenalisedEnv`)."""
     try:
         env = _hip_env(model_env)
+        stepper = env if uncertainty is None else _penalised(env, uncertainty)
     except UnsupportedModelError as exc:
+        if uncertainty is not None and not hasattr(model_env, "dynamics_model"):
+            raise  # (no live model to run the reference's forward on)
         warnings.warn(f"hipets.rollout_model_and_populate_sac_buffer: running the reference's loop ({exc})", stacklevel=2)
+        if uncertainty is not None:
+            from .ensemble import ReferencePenalisedEnv
+
+            model_env = ReferencePenalisedEnv(model_env, uncertainty)
         return reference_populate_loop(model_env, replay_buffer, agent, sac_buffer, sac_samples_action, rollout_horizon, batch_size)
     try:
         actor = _actor(agent, env.engine)
     except UnsupportedModelError as exc:
         warnings.warn(f"hipets.rollout_model_and_populate_sac_buffer: running the reference's loop over the model environment ({exc})", stacklevel=2)
-        return reference_populate_loop(env, replay_buffer, agent, sac_buffer, sac_samples_action, rollout_horizon, batch_size)
+        return reference_populate_loop(stepper, replay_buffer, agent, sac_buffer, sac_samples_action, rollout_horizon, batch_size)
     batch = replay_buffer.sample(batch_size)
     initial_obs, *_ = batch.astuple()
     L = int(rollout_horizon)
@@ -133,14 +180,14 @@ def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_b
         N, od = (int(v) for v in state["obs"].shape)
         ad = actor.dims[2]
         if isinstance(sac_buffer, DeviceReplayBuffer) and sac_buffer.engine is env.engine:
-            return _populate_ring(env, actor, sac_buffer, state, sac_samples_action, L)
+            return _populate_ring(stepper, actor, sac_buffer, state, sac_samples_action, L)
         head = (L + 3) // 4 * 4  # the per-step counts (int32) travel in front of the staging area: one buffer, one copy
         buf = torch.empty(head + N * L * row_width(od, ad), dtype=torch.float32, device=env.device)
         counts = buf[:head].view(torch.int32)
         counts.zero_()
         staging, cap = buf[head:], N * L
         offset = torch.zeros(1, dtype=torch.int64, device=env.device)
-        _rollout_steps(env, actor, state, sac_samples_action, L,
+        _rollout_steps(stepper, actor, state, sac_samples_action, L,
                        lambda i, *rows: env.engine.compact_transitions(*rows, staging, cap, offset, counts[i:i + 1]))
         host = _host_copy(env, buf)
     finally:

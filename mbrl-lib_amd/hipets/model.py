@@ -416,13 +416,17 @@ def _read_gaussian_mlp(mlp):
 
 
 def spec_from_model_env(model_env, obs_dim: Optional[int] = None, act_dim: Optional[int] = None,
-                        allow_custom_fns: bool = False) -> ModelSpec:
+                        allow_custom_fns: bool = False, propagation: Optional[str] = None) -> ModelSpec:
     """Read a live ``mbrl.models.ModelEnv`` (or anything shaped like it).  No copy of the big tensors:
     the spec holds references to the live parameters; ``Engine.set_model`` packs them on device.
 
     ``allow_custom_fns``: a ``reward_fn`` / ``termination_fn`` that is not one of mbrl.env's closed forms is kept as a
     Python callable (``spec.custom_reward_fn`` / ``spec.custom_termination_fn``) for the UNFUSED path (the model
-    transition stays fused, the callables run as torch ops between steps) instead of raising."""
+    transition stays fused, the callables run as torch ops between steps) instead of raising.
+
+    ``propagation``: what to record for a model whose own ``propagation_method`` is None -- one built for plain forward passes
+    (``forward(x, use_propagation=False)``: hipets.EnsemblePredictor, which reads no propagation); by default such a model is
+    refused as before."""
     dm = model_env.dynamics_model
     mlp = getattr(dm, "model", None)
     ensemble_kind = "gaussian_mlp"
@@ -476,7 +480,7 @@ def spec_from_model_env(model_env, obs_dim: Optional[int] = None, act_dim: Optio
         min_logvar=lv_lo, max_logvar=lv_hi, ensemble_kind=ensemble_kind,
         elite_models=list(mlp.elite_models) if getattr(mlp, "elite_models", None) is not None else None,
         activation=act_name or "relu", leaky_slope=slope,
-        propagation=mlp.propagation_method, deterministic=deterministic,
+        propagation=mlp.propagation_method if mlp.propagation_method is not None else propagation, deterministic=deterministic,
         norm_mean=norm.mean.detach() if norm is not None else None,
         norm_std=norm.std.detach() if norm is not None else None,
         target_is_delta=bool(dm.target_is_delta), no_delta_list=list(dm.no_delta_list or []),

@@ -302,11 +302,21 @@ class ModelEnv:
     MAP_STREAM_KEY = "hipets_map_stream"
 
     def __init__(self, model, engine: Optional[Engine] = None, mode: str = "device", seed: int = 0, device=None,
-                 generator: Optional[torch.Generator] = None):
+                 generator: Optional[torch.Generator] = None, uncertainty=None):
         """``mode`` as for :class:`HipTrajectoryEvalFn`: 'device' (default; the reference's per-row balanced member shuffle and iid
-        eps, drawn in-kernel), 'fast' (one member per workgroup of 16-48 consecutive rows), 'exact' (the reference's own torch draws)."""
+        eps, drawn in-kernel), 'fast' (one member per workgroup of 16-48 consecutive rows), 'exact' (the reference's own torch draws).
+        ``uncertainty``: a :class:`hipets.UncertaintyPenalty` -- every ``step`` then runs, after its model step, one statistics launch
+        of the ensemble kernel on the step's (obs, action) and one penalty launch on its rewards and dones (``hipets.ensemble``); a
+        model that kernel does not cover raises UnsupportedModelError here.  None: nothing is added."""
         self._eval = HipTrajectoryEvalFn(model, 1, engine=engine, mode=mode, seed=seed, device=device, rng=generator)
         self.engine, self.device, self.mode, self.seed = self._eval.engine, self._eval.device, mode, int(seed)
+        self.uncertainty, self._predictor = uncertainty, None
+        if uncertainty is not None:
+            from .ensemble import EnsemblePredictor, UncertaintyPenalty
+
+            if not isinstance(uncertainty, UncertaintyPenalty):
+                raise TypeError("uncertainty must be a hipets.UncertaintyPenalty")
+            self._predictor = EnsemblePredictor(self, engine=self.engine)
         self._return_as_np = True
         self._steps = 0
         self._resets = 0
@@ -374,6 +384,11 @@ class ModelEnv:
 
     def step(self, actions, model_state: Dict[str, torch.Tensor], sample: bool = False):
         """model_env.py:87-140: (next_observs, rewards, dones, next_model_state)."""
+        return self._step(actions, model_state, sample, self._predictor, self.uncertainty)
+
+    def _step(self, actions, model_state, sample, predictor, penalty):
+        """``step`` with the uncertainty penalty as an argument (``predictor`` None: none): what a penalised view of this environment
+        calls (hipets.mbpo), so that the environment's own counters and streams advance whoever steps it"""
         assert len(actions.shape) == 2  # batch, action_dim
         self._eval.bind_model()
         if isinstance(actions, np.ndarray):
@@ -412,6 +427,8 @@ class ModelEnv:
             sched = self._fast_map(B, keyed)[0] if keyed else None
             nobs, rew, done = self.engine.step(obs, actions, mode="fast", sample=sample, seed=self.seed, stream_id=self._steps,
                                                member_schedule=sched)
+        if predictor is not None:  # (rew [B, 1] and done [B, 1] are this step's own tensors: penalised in place)
+            predictor.penalise(penalty, obs, actions, rew.view(-1), done.view(-1))
         next_state = {**model_state, "obs": nobs}
         if self._return_as_np:
             return nobs.cpu().numpy(), rew.cpu().numpy(), done.cpu().numpy(), next_state
