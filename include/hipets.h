@@ -929,6 +929,37 @@ int hipets_ensemble_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles
 int hipets_uncertainty_penalty(hipets_engine* e, const float* stats, int32_t stat, float coef, float halt_threshold, float halt_reward,
                                int32_t use_halt_reward, int32_t batch, float* rewards, uint8_t* dones, void* stream);
 
+/* ---- policy rollouts: the SAC actor rolled through the dynamics ensemble, the action sequences that seed a plan ----
+ * Additive entry points: scalars and pointers; no struct changes, HIPETS_ABI_VERSION stays.  They read the snapshots hipets_policy_set
+ * and hipets_ensemble_set hold and need no set call of their own.
+ *
+ * hipets_policy_rollout: ONE launch rolls n rows through `horizon` steps.  Row r at step t = 0 .. horizon - 1:
+ *   a_t     = GaussianPolicy(s_t) exactly as hipets_policy_act computes it: the mean action tanh(mean) * scale + bias for rows r < mean_rows,
+ *             tanh(mean + exp(log_std) * eps) * scale + bias for the others, eps from the table eps DEVICE [horizon, n, act_dim] or, with
+ *             eps NULL, drawn in-kernel as hipets_policy_act draws row t * n + r under (seed, stream_id): hipets_policy_normals(batch =
+ *             horizon * n) returns exactly that table.
+ *   x       = the model input of (s_t, a_t) exactly as hipets_ensemble_predict builds it (obs_process including column tables,
+ *             concatenation, the normaliser in its own dtype).
+ *   pred    = the mean over the requested members -- the descriptor's member list in list order (only_elite != 0; all members where the
+ *             model has no elite set, as for HIPETS_ENSEMBLE_BASIC) or all ensemble_size members in index order -- of each member's MEAN
+ *             head, with the bits hipets_ensemble_predict gives: fp32, acc = m_0; acc += m_i in requested order; one division by the count.
+ *             (propagation "expectation" with ModelEnv.step(..., sample=False): gaussian_mlp.py:213-215, basic_ensemble.py:131-136.)
+ *   s_{t+1} = one_dim_tr_model.py:281-286: the learned-reward column (the last) is dropped; s_t + pred under target_is_delta except the
+ *             no_delta dims, which take pred; otherwise pred.  No termination test; NaN and inf propagate within their row.
+ * Outputs, DEVICE f32: actions [n, horizon, act_dim]; states [horizon + 1, n, obs_dim] (states[0] = s0) or NULL.  s0 DEVICE [n, obs_dim].
+ * A workgroup owns 16 * row_tiles consecutive rows for the whole horizon and never waits for another.  A row's arithmetic depends
+ * neither on n nor on the row tiles; only its in-kernel draws do (they are keyed on t * n + r).
+ * HIPETS_ERR_INVALID_ARGUMENT, each with a message: no policy snapshot or no ensemble snapshot; the policy's (obs_dim, act_dim) differs
+ * from the ensemble's; the ensemble's out_dim is not obs_dim + learned_rewards; n < 1; horizon < 1; horizon * n > 2^31 - 1; mean_rows outside
+ * [0, n]; a pair of snapshots whose LDS need at one row tile -- 16 rows x (pad16(obs_dim) + 4 [the state] + act_dim rounded up to 4 + the larger of
+ * the actor's two buffers (pad16(hidden) + 4 + max(pad16(hidden), pad16(2 act_dim)) + 4) and the model's areas (hipets_ensemble_set's input and
+ * two buffers + out_dim [the members' sum])) floats -- exceeds the LDS opt-in limit (the message names the bytes).                            */
+int hipets_policy_rollout(hipets_engine* e, const float* s0, int32_t n, int32_t horizon, int32_t mean_rows, int32_t only_elite, uint64_t seed,
+                          uint64_t stream_id, const float* eps, float* actions, float* states, void* stream);
+/* Launch geometry of hipets_policy_rollout for n rows, the actor's rule (hipets_policy_geometry) on the LDS need above; the same refusals
+ * about the snapshots.                                                                                                                */
+int hipets_policy_rollout_geometry(hipets_engine* e, int32_t n, int32_t* row_tiles, int32_t* lds_bytes);
+
 /* ---- instrumentation (bench.py roofline leg) ----------------------------------------------- */
 /* on = 1: every rollout-kernel launch carries a start / stop hipEvent pair on its dispatch packet; on = k > 1: every
  * k-th launch does (a completion signal per packet costs a few microseconds between back-to-back short launches -- the

@@ -1,5 +1,5 @@
 // engine.hpp -- private to the host units of the C ABI (include/hipets.h): engine.hip, model.hip, rollout.hip, plan.hip, comm.hip,
-// train.hip, policy.hip, replay.hip, sac.hip, value.hip and ensemble.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
+// train.hip, policy.hip, replay.hip, sac.hip, value.hip, ensemble.hip and policy_rollout.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
 // Host code only; nothing declared here is part of the ABI (hidden visibility).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -67,15 +67,18 @@ struct MlpSnapshot { bool set = false; int obs = 0, hid = 0, act = 0; DevBuf w, 
 
 // what hipets_ensemble_set keeps (ensemble.hip): the dynamics ensemble's shape, every member's padded W[k][n] images and biases (member e, layer
 // l at e * wmember + its layer offset), the normaliser (mean, std, 1 / std: [3][in_dim] doubles), the log-variance bounds (min rows, then
-// max rows: lv_rows each, indexed by member where every member owns its own), the elite list and the column table
+// max rows: lv_rows each, indexed by member where every member owns its own), the elite list, the column table and the delta rule
 struct EnsembleSnapshot {
     bool set = false;
     int E = 0, M = 0, obs_dim = 0, act_dim = 0, in_dim = 0, out_dim = 0, hid = 0, n_layers = 0;
     int activation = 0, obs_process = 0, normalizer = 0, deterministic = 0, lv_rows = 1;
+    // how a prediction becomes the next observation (one_dim_tr_model.py:281-286; read by hipets_policy_rollout alone): bit d of
+    // no_delta (HIPETS_ENSEMBLE_MAX_OUT bits, on the device) = observation dim d is predicted absolutely
+    int target_is_delta = 0, learned_rewards = 0;
     float slope = 0.f;
     int members[HIPETS_ENSEMBLE_MAX_MEMBERS] = {};
     size_t wmember = 0, bmember = 0;
-    DevBuf w, b, norm, lv, cols;
+    DevBuf w, b, norm, lv, cols, no_delta;
 };
 
 // what hipets_sac_bind keeps: the agent's sizes and hyper-parameters, its optimizers' (beta1, beta2, eps) [critic, policy, alpha], and the

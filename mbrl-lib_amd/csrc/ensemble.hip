@@ -8,6 +8,7 @@
 #include <cmath>
 #include <vector>
 
+#include "agent_forms.hpp"
 #include "closed_forms.hpp"
 #include "common.hpp"
 #include "engine.hpp"
@@ -32,7 +33,6 @@ namespace {
 // the shifted values are of the size of the members' spread, so nothing cancels against the means' own size (the one-pass E[x^2] - E[x]^2
 // of the raw means loses every digit the spread does not share with the mean).
 // ---------------------------------------------------------------------------------------------
-constexpr int kEnsAhead = 4;       // policy_layer's kAhead: k-blocks whose weight loads a wave issues ahead of their MFMAs (the critic's choice)
 constexpr int kHeadLanes = 8;      // lanes of a row in the head
 constexpr int kEnsMaxMembers = HIPETS_ENSEMBLE_MAX_MEMBERS, kEnsMaxIn = HIPETS_ENSEMBLE_MAX_IN, kEnsMaxOut = HIPETS_ENSEMBLE_MAX_OUT;
 
@@ -51,35 +51,6 @@ struct EnsArgs {
     float slope;
     int members[kEnsMaxMembers];            // the n requested members, in order
 };
-
-// the activation modules of GaussianMLP (gaussian_mlp.py:88-96) on the four values a lane holds, as the rollout kernels state them
-// (gemm_f32.hpp): SiLU and sigmoid through the hardware's exp2 and reciprocal, relu as a select (a NaN stays a NaN); `act` < 0: none
-__device__ __forceinline__ f32x4 ens_activate(const int act, f32x4 z, const float slope) {
-    constexpr float kNegLog2e = -1.44269504088896340736f;
-    switch (act) {
-        case HIPETS_ACT_RELU:
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = z[j] < 0.f ? 0.f : z[j];
-            return z;
-        case HIPETS_ACT_SILU:
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = z[j] * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(z[j] * kNegLog2e));
-            return z;
-        case HIPETS_ACT_LEAKY_RELU:
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = z[j] > 0.f ? z[j] : z[j] * slope;
-            return z;
-        case HIPETS_ACT_TANH:
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = tanhf(z[j]);
-            return z;
-        case HIPETS_ACT_SIGMOID:
-#pragma unroll
-            for (int j = 0; j < 4; ++j) z[j] = __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(z[j] * kNegLog2e));
-            return z;
-        default: return z;
-    }
-}
 
 // torch.nn.functional.softplus (beta 1, threshold 20)
 __device__ __forceinline__ float ens_softplus(const float x) { return x > 20.f ? x : log1pf(expf(x)); }
@@ -117,10 +88,7 @@ __global__ __launch_bounds__(kPolicyThreads) void ensemble_predict_kernel(const 
             if (a.model_in) {
                 v = a.model_in[row * a.in_dim + k];
             } else {
-                v = k < obs_in ? processed_obs(a.obs + row * a.obs_dim, k, a.obs_process, a.cols) : a.actions[row * a.act_dim + (k - obs_in)];
-                // the normaliser in its own dtype (util/math.py:129-143); f64 as the rollout kernel forms it: (x - mean) * (1 / std)
-                if (a.normalizer == HIPETS_NORM_F64) v = (float)(((double)v - a.norm[k]) * a.norm[2 * a.in_dim + k]);
-                else if (a.normalizer == HIPETS_NORM_F32) v = (v - (float)a.norm[k]) / (float)a.norm[a.in_dim + k];
+                v = model_input_element(a.obs + row * a.obs_dim, a.actions + row * a.act_dim, k, obs_in, a.in_dim, a.obs_process, a.cols, a.normalizer, a.norm);
             }
         }
         X[r * a.ld_x + k] = v;
@@ -143,21 +111,8 @@ __global__ __launch_bounds__(kPolicyThreads) void ensemble_predict_kernel(const 
         const float* b = a.b + (size_t)m * a.bmember;
         // (X is complete; the previous member's head has read its buffer, which layer 0 or 1 writes again)
         __syncthreads();
-        const float* in = X;
-        int ld_in = a.ld_x, kp = a.kp0;
-        for (int l = 0; l < L; ++l) {
-            float* out = (l & 1) ? buf1 : buf0;
-            const int ld_out = (l & 1) ? a.ld1 : a.ld0;
-            // (one call site for hidden and last layers: `act` < 0 is the last layer's identity)
-            const bool last = l == L - 1;
-            const int np = last ? a.npo : a.hp, act_l = last ? -1 : act;
-            mlp_layer_post<R, kEnsAhead>(in, ld_in, kp, w, b, np, out, ld_out, wave, lane,
-                                         [act_l, slope](const f32x4 z) { return ens_activate(act_l, z, slope); });
-            w += (size_t)kp * np;
-            b += np;
-            __syncthreads();
-            in = out; ld_in = ld_out; kp = a.hp;
-        }
+        int ld_in;
+        const float* in = ens_member_forward<R>(X, a.ld_x, a.kp0, a.hp, a.npo, L, w, b, buf0, a.ld0, buf1, a.ld1, act, slope, wave, lane, ld_in);
         if (!head) continue;
         // ---- the head: gaussian_mlp.py:150-153, the outputs, the member's share of the statistics ----
         const float* o = in + hrow * ld_in;
@@ -239,28 +194,6 @@ __global__ void uncertainty_penalty_kernel(const float* stats, int stat, float c
         if (use_halt_reward) r = halt_reward;
     }
     rewards[row] = r;
-}
-
-// LDS of the snapshot's shape: X, the two buffers, the two per-(row, column) accumulators
-struct EnsGeo { int kp0, hp, npo, ld_x, ld0, ld1; MlpGeo g; };
-
-EnsGeo ensemble_geo(int in_dim, int hid, int out_dim, int deterministic, int n_layers, size_t lds_max, long long batch) {
-    EnsGeo x{};
-    x.kp0 = pad16(in_dim); x.hp = pad16(hid); x.npo = pad16(deterministic ? out_dim : 2 * out_dim);
-    x.ld_x = x.kp0 + 4;
-    const int wide = std::max(x.hp, x.npo) + 4, narrow = x.hp + 4;
-    x.ld0 = ((n_layers - 1) & 1) == 0 ? wide : narrow;  // (the last layer writes buffer (L - 1) & 1)
-    x.ld1 = ((n_layers - 1) & 1) == 1 ? wide : narrow;
-    x.g.kp0 = x.kp0; x.g.hp = x.hp; x.g.np_last = x.npo; x.g.ld_a = x.ld0; x.g.ld_b = x.ld1;
-    x.g.per_tile = (size_t)kTile * 4 * (size_t)(x.ld_x + x.ld0 + x.ld1 + 2 * out_dim);
-    x.g.R = policy_row_tiles(x.g.per_tile, lds_max, batch);
-    x.g.lds = x.g.per_tile * x.g.R;
-    return x;
-}
-
-EnsGeo ensemble_geo(const hipets_engine* e, long long batch) {
-    const EnsembleSnapshot& s = e->ensemble;
-    return ensemble_geo(s.in_dim, s.hid, s.out_dim, s.deterministic, s.n_layers, e->lds_max, batch);
 }
 
 }  // namespace
@@ -375,11 +308,18 @@ int hipets_ensemble_set(hipets_engine* e, const hipets_model_desc* d, const hipe
         if (s.cols.ensure(sizeof(hipets_obs_column) * n_cols)) return 1;
         HCHECK(hipMemcpyAsync(s.cols.p, cols, sizeof(hipets_obs_column) * n_cols, hipMemcpyHostToDevice, st));
     }
+    // the delta rule, for hipets_policy_rollout (a prediction itself does not read it): bit d = dim d is predicted absolutely
+    uint32_t no_delta[kEnsMaxOut / 32] = {};
+    for (int i = 0; d->no_delta && i < d->n_no_delta; ++i)
+        if (d->no_delta[i] >= 0 && d->no_delta[i] < kEnsMaxOut) no_delta[d->no_delta[i] >> 5] |= 1u << (d->no_delta[i] & 31);
+    if (s.no_delta.ensure(sizeof(no_delta))) return 1;
+    HCHECK(hipMemcpyAsync(s.no_delta.p, no_delta, sizeof(no_delta), hipMemcpyHostToDevice, st));
     HCHECK(hipStreamSynchronize(st));  // the host staging and the caller's arrays may go away after return
     s.E = E; s.M = d->n_members; s.obs_dim = d->obs_dim; s.act_dim = d->act_dim; s.in_dim = d->in_dim; s.out_dim = d->out_dim;
     s.hid = d->hid; s.n_layers = L; s.activation = d->activation; s.slope = d->leaky_slope; s.obs_process = d->obs_process;
     s.normalizer = d->normalizer; s.deterministic = d->deterministic ? 1 : 0; s.lv_rows = lv_rows;
     for (int i = 0; i < d->n_members; ++i) s.members[i] = d->members[i];
+    s.target_is_delta = d->target_is_delta ? 1 : 0; s.learned_rewards = d->learned_rewards ? 1 : 0;
     s.wmember = wmember; s.bmember = bmember;
     s.set = true;
     return 0;

@@ -5,6 +5,7 @@
 
 #include "common.hpp"
 #include "engine.hpp"
+#include "agent_forms.hpp"
 #include "policy_layer.hpp"
 
 namespace hipets {
@@ -13,7 +14,8 @@ namespace {
 
 // The actor.  A workgroup owns 16 R consecutive rows; their activations live in two LDS buffers that the layers alternate between
 // (A: obs, then h2; B: h1, then the heads), the packed weights stream from L2.  The layer, the LDS layout and the host scaffold --
-// geometry, launch, packing -- are policy_layer.hpp's, shared with the critic kernel (value.hip).
+// geometry, launch, packing -- are policy_layer.hpp's, shared with the critic kernel (value.hip); the draws and the head's arithmetic
+// are agent_forms.hpp's, shared with the policy-rollout kernel (policy_rollout.hip).
 struct PolicyArgs {
     const float* obs;      // [B, obs_dim]
     const float* eps;      // [B, act] or null
@@ -29,15 +31,6 @@ struct PolicyArgs {
     int sample;
     unsigned long long seed, stream_id;
 };
-
-// eps of (row, dims 4 blk .. 4 blk + 3): Philox4x32-10 with the counter word "POLI" where the rollouts' draws carry their step, under a
-// key of its own -- no actor draw shares a (counter, key) with a model draw of the same (seed, stream)
-__device__ __forceinline__ void policy_normals4(uint32_t row, uint32_t blk, unsigned long long seed, unsigned long long stream_id, float (&nrm)[4]) {
-    const Philox4 r4 = philox4x32_10(row, 0x504F4C49u /* "POLI" */, blk, (uint32_t)stream_id, (uint32_t)seed,
-                                     (uint32_t)(seed >> 32) ^ (uint32_t)(stream_id >> 32) ^ 0xAC7012ACu);
-    box_muller(r4.x, r4.y, nrm[0], nrm[1]);
-    box_muller(r4.z, r4.w, nrm[2], nrm[3]);
-}
 
 template <int R>
 __global__ __launch_bounds__(kPolicyThreads) void policy_act_kernel(const PolicyArgs a) {
@@ -67,14 +60,10 @@ __global__ __launch_bounds__(kPolicyThreads) void policy_act_kernel(const Policy
             const int d = 4 * blk + s;
             if (d < a.act) {
                 const float mean = bufB[r * a.ld_b + d];
-                const float ls = clamp_log_std(bufB[r * a.ld_b + a.act + d]);
                 const long long o = row * a.act + d;
-                float x = mean;
-                if (a.sample) {
-                    const float e = a.eps ? a.eps[o] : nrm[s];
-                    x = mean + expf(ls) * e;  // Normal.rsample: loc + eps * scale
-                }
-                a.actions[o] = tanhf(x) * a.scale[d] + a.bias[d];
+                float ls;
+                a.actions[o] = policy_head_action(mean, bufB[r * a.ld_b + a.act + d], a.sample != 0, a.sample ? (a.eps ? a.eps[o] : nrm[s]) : 0.f, a.scale[d],
+                                                  a.bias[d], ls);
                 if (a.mean_out) a.mean_out[o] = mean;
                 if (a.log_std_out) a.log_std_out[o] = ls;
             }
@@ -95,9 +84,6 @@ __global__ void policy_normals_kernel(float* out, int B, int act, unsigned long 
         if (d < act) out[row * act + d] = nrm[s];
     }
 }
-
-// (the last layer is the two heads: columns [0, act) mean, [act, 2 act) log_std)
-MlpGeo policy_geometry(const hipets_engine* e, long long batch) { return mlp_geometry(e->policy.obs, e->policy.hid, 2 * e->policy.act, e->lds_max, batch); }
 
 }  // namespace
 

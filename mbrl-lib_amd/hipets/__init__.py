@@ -56,6 +56,7 @@ from .replay import DeviceReplayBuffer, maybe_replace_sac_buffer  # noqa: F401
 from .sac import SACActor, SACCritic, SACUpdater, make_sac_updater  # noqa: F401
 from .value import ValueTrajectoryEvalFn  # noqa: F401
 from .ensemble import EnsemblePredictor, UncertaintyPenalty  # noqa: F401
+from .policy_rollout import PolicyPrior, PolicyRollout  # noqa: F401
 from . import dist  # noqa: F401
 
 __version__ = "0.1.0"

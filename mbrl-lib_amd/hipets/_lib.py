@@ -259,6 +259,8 @@ SYMBOLS = {
     "hipets_ensemble_geometry": _sig("e batch:i32 row_tiles:i32* lds_bytes:i32*"),
     "hipets_uncertainty_penalty": _sig("e stats stat:i32 coef:f32 halt_threshold:f32 halt_reward:f32 use_halt_reward:i32 batch:i32 rewards dones "
                                        "stream"),
+    "hipets_policy_rollout": _sig("e s0 n:i32 horizon:i32 mean_rows:i32 only_elite:i32 seed:u64 stream_id:u64 eps actions states stream"),
+    "hipets_policy_rollout_geometry": _sig("e n:i32 row_tiles:i32* lds_bytes:i32*"),
     "hipets_timing_enable": _sig("e on:i32"),
     "hipets_timing_read": _sig("e launches:i64* total_ms:f64* reset:i32"),
 }

@@ -120,6 +120,19 @@ def ensemble_lds_bytes(in_dim: int, hid: int, out_dim: int, deterministic: bool,
     return 16 * 4 * (pad16(in_dim) + 4 + hp + 4 + max(hp, npo) + 4 + 2 * int(out_dim)) * int(row_tiles)
 
 
+def policy_rollout_lds_bytes(obs_dim: int, act_dim: int, actor_hidden: int, in_dim: int, hid: int, out_dim: int, deterministic: bool, n_layers: int,
+                             row_tiles: int = 1) -> int:
+    """Dynamic LDS of a hipets_policy_rollout workgroup of ``row_tiles`` row tiles (csrc/policy_rollout.hip rollout_geo): per row the
+    state (pad16(obs) + 4 floats), the action (act rounded up to 4) and the larger of the actor's two buffers (pad16(hidden) + 4 and
+    max(pad16(hidden), pad16(2 act)) + 4) and the model's areas (the ensemble kernel's input and two buffers, and the members' sum:
+    out_dim) -- the two networks never run at once and share that space."""
+    pad16 = lambda x: (int(x) + 15) // 16 * 16  # noqa: E731
+    hpa = pad16(actor_hidden)
+    actor = hpa + 4 + max(hpa, pad16(2 * act_dim)) + 4
+    model = ensemble_lds_bytes(in_dim, hid, out_dim, deterministic, n_layers) // 64 - int(out_dim)
+    return 16 * 4 * (pad16(obs_dim) + 4 + (int(act_dim) + 3) // 4 * 4 + max(actor, model)) * int(row_tiles)
+
+
 def check_ensemble_shape(spec: ModelSpec, lds_max: int = 160 * 1024):
     """What hipets_ensemble_set refuses, told without a device: raises UnsupportedModelError naming the reason (fp32 only, E <= 16,
     in_dim / out_dim <= 512, hid <= 1024, one row tile within ``lds_max`` bytes of LDS)."""

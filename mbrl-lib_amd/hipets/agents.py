@@ -21,8 +21,8 @@ import torch
 from . import dist as hdist
 from ._lib import HipetsError
 from .engine import Engine
-from .objectives import HipTrajectoryEvalFn, _BoundObjective, make_eval_fn
-from .optimizers import ICEMOptimizer, Optimizer, _run_fused_plan
+from .objectives import HipTrajectoryEvalFn, PlaNetTrajectoryEvalFn, _BoundObjective, make_eval_fn
+from .optimizers import ICEMOptimizer, Optimizer, _PlanOptimizer, _run_fused_plan
 
 # ---------------------------------------------------------------------------------------------
 # TrajectoryOptimizer / Agent
@@ -121,6 +121,11 @@ class _OptimizerSnapshot:
             setattr(self.optimizer, k, v.clone() if torch.is_tensor(v) else v)
 
 
+def _refuse_latent_prior(eval_fn):
+    if isinstance(eval_fn, PlaNetTrajectoryEvalFn):
+        raise ValueError("a policy prior rolls an actor over observations: a PlaNet objective plans over latent states, for which there is none")
+
+
 class TrajectoryOptimizer:
     """trajectory_opt.py:490-572: tiles the action bounds over the horizon, instantiates the optimizer,
     warm-starts each call from the previous solution shifted by ``replan_freq``."""
@@ -139,11 +144,18 @@ class TrajectoryOptimizer:
         self.horizon = planning_horizon
 
     def optimize(self, trajectory_eval_fn: Callable[[torch.Tensor], torch.Tensor],
-                 callback: Optional[Callable] = None) -> np.ndarray:
+                 callback: Optional[Callable] = None, extra_candidates: Optional[torch.Tensor] = None) -> np.ndarray:
         """(A plan that is re-run after a timed-out rollout -- see below -- invokes ``callback`` again for every iteration of the
-        second run: a callback that accumulates sees the iterations of the voided attempt followed by those of the valid one.)"""
+        second run: a callback that accumulates sees the iterations of the voided attempt followed by those of the valid one.)
+        ``extra_candidates`` [num, H, A]: rows every iteration's population takes (the optimizers' keyword); a re-run reuses them."""
+        kw = {}
+        if extra_candidates is not None:
+            if not isinstance(self.optimizer, _PlanOptimizer):  # (a stock optimizer's **kwargs would swallow the rows unused)
+                raise TypeError(f"{type(self.optimizer).__name__}.optimize takes no extra_candidates keyword: a policy prior needs one of "
+                                "hipets' optimizers (CEMOptimizer, MPPIOptimizer, ICEMOptimizer)")
+            kw["extra_candidates"] = extra_candidates
         snapshot = _OptimizerSnapshot(self.optimizer, trajectory_eval_fn)
-        best_solution = self.optimizer.optimize(trajectory_eval_fn, x0=self.previous_solution, callback=callback)
+        best_solution = self.optimizer.optimize(trajectory_eval_fn, x0=self.previous_solution, callback=callback, **kw)
         plan = best_solution.cpu().numpy()  # the one device->host sync of a plan (:568)
         # Everything the plan enqueued has executed now.  If a persistent DEVICE-mode rollout inside it gave up waiting for
         # another workgroup's rows (CUs taken by another process: hipets.h, hipets_check_async_error) the plan was built on
@@ -153,7 +165,7 @@ class TrajectoryOptimizer:
             if not snapshot.engines_report_timeout():
                 break
             snapshot.restore()
-            best_solution = self.optimizer.optimize(trajectory_eval_fn, x0=self.previous_solution, callback=callback)
+            best_solution = self.optimizer.optimize(trajectory_eval_fn, x0=self.previous_solution, callback=callback, **kw)
             plan = best_solution.cpu().numpy()
         else:
             if snapshot.engines_report_timeout():
@@ -190,12 +202,31 @@ class TrajectoryOptimizerAgent(Agent):
         self.optimizer_args = {"optimizer_cfg": optimizer_cfg, "action_lb": np.array(action_lb),
                                "action_ub": np.array(action_ub)}
         self.trajectory_eval_fn = None
+        self.policy_prior = None
         self.actions_to_use: List[np.ndarray] = []
         self.replan_freq = replan_freq
         self.verbose = verbose
 
     def set_trajectory_eval_fn(self, trajectory_eval_fn):
+        if self.policy_prior is not None:
+            _refuse_latent_prior(trajectory_eval_fn)
         self.trajectory_eval_fn = trajectory_eval_fn
+
+    def set_policy_prior(self, prior):
+        """``prior``: a :class:`hipets.PolicyPrior` -- per plan its action sequences, the learned policy rolled through the model from
+        the plan's observation, enter every iteration's population (the optimizers' ``extra_candidates``); None: plans run as
+        without one (the fused one-call plan where the objective allows it)."""
+        if prior is not None:
+            if not callable(getattr(prior, "sequences", None)):
+                raise TypeError(f"a policy prior needs a sequences(obs, horizon=...) method, got {type(prior).__name__}")
+            _refuse_latent_prior(self.trajectory_eval_fn)
+        self.policy_prior = prior
+
+    def _prior_candidates(self, obs):
+        """the plan's extra candidates: computed ONCE per plan, before the optimizer runs (a re-run plan reuses them)"""
+        if self.policy_prior is None:
+            return None
+        return self.policy_prior.sequences(obs, horizon=self.optimizer.horizon)
 
     def reset(self, planning_horizon: Optional[int] = None):
         if planning_horizon:  # :644-651
@@ -221,7 +252,8 @@ class TrajectoryOptimizerAgent(Agent):
         plan_time = 0.0
         if not self.actions_to_use:  # re-plan is necessary (:678)
             start_time = time.time()
-            plan = self.optimizer.optimize(_BoundObjective(self.trajectory_eval_fn, obs), callback=optimizer_callback)
+            plan = self.optimizer.optimize(_BoundObjective(self.trajectory_eval_fn, obs), callback=optimizer_callback,
+                                           extra_candidates=self._prior_candidates(obs))
             plan_time = time.time() - start_time
             self.actions_to_use.extend([a for a in plan[: self.replan_freq]])
         action = self.actions_to_use.pop(0)
@@ -231,7 +263,7 @@ class TrajectoryOptimizerAgent(Agent):
 
     def plan(self, obs: np.ndarray, **_kwargs) -> np.ndarray:
         self._require_eval_fn()
-        return self.optimizer.optimize(_BoundObjective(self.trajectory_eval_fn, obs))
+        return self.optimizer.optimize(_BoundObjective(self.trajectory_eval_fn, obs), extra_candidates=self._prior_candidates(obs))
 
 
 class _BatchedAgent(Agent):
@@ -260,6 +292,14 @@ class _BatchedAgent(Agent):
         self.calls += 1
         return self.calls
 
+    def set_policy_prior(self, prior):
+        raise NotImplementedError("batched plans run inside the library, which takes no extra candidates: a policy prior needs a TrajectoryOptimizerAgent")
+
+    @staticmethod
+    def _refuse_extra(kwargs):
+        if kwargs.get("extra_candidates") is not None:
+            raise ValueError("batched plans run inside the library, which takes no extra_candidates: use a TrajectoryOptimizerAgent with a policy prior")
+
     def _plan(self, kind: str, args, obs_batch, latent, belief, population_sizes, **kw):
         """One plan call for all environments, see :func:`_run_fused_plan`."""
         return _run_fused_plan(kind, args, self.eval_fn, obs_batch, self.seed ^ self.eval_fn.seed, self._next_plan_id, population_sizes,
@@ -274,6 +314,7 @@ class _BatchedAgent(Agent):
 
     def act(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
         """One action per environment, [n_env, A]."""
+        self._refuse_extra(_kwargs)
         return self.plan(obs_batch, latent=latent, belief=belief)[:, 0]
 
 
@@ -297,6 +338,7 @@ class BatchedCEMAgent(_BatchedAgent):
                                          return_mean_elites, clipped_normal, unbiased_var=True)
 
     def plan(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
+        self._refuse_extra(_kwargs)
         best = self._plan("cem", (self._params, self.previous_solution, self.lower, self.upper), obs_batch, latent, belief,
                           [self._params.population_size])
         return self._shift(best)
@@ -316,6 +358,7 @@ class BatchedMPPIAgent(_BatchedAgent):
         self.refinements, self.population_size, self.gamma, self.sigma, self.beta = int(num_iterations), int(population_size), gamma, sigma, beta
 
     def plan(self, obs_batch: np.ndarray, latent=None, belief=None, **_kwargs) -> np.ndarray:
+        self._refuse_extra(_kwargs)
         self._plan("mppi", (self.population_size, self.horizon, self.act_dim, self.refinements, self.gamma, self.beta,
                    self.mean, self.lower, self.upper), obs_batch, latent, belief, [self.population_size])
         return self.mean.cpu().numpy()
@@ -340,6 +383,7 @@ class BatchedICEMAgent(_BatchedAgent):
         self.has_elite = False  # (the elites persist across reset(), like ICEMOptimizer.elite, Appendix B6)
 
     def plan(self, obs_batch: np.ndarray, keep_idx: Optional[torch.Tensor] = None, latent=None, belief=None, **_kwargs) -> np.ndarray:
+        self._refuse_extra(_kwargs)
         sizes, params = self._opt._fused_plan(self.horizon, self.act_dim, self.has_elite)
         best = self._plan("icem", (params, self.previous_solution, self.lower, self.upper, self.elite, self.has_elite),
                           obs_batch, latent, belief, sizes, keep_idx=keep_idx)
@@ -360,9 +404,12 @@ def complete_agent_cfg(env, agent_cfg):
     return agent_cfg
 
 
-def create_trajectory_optim_agent_for_model(model_env, agent_cfg, num_particles: int = 1, **eval_kw):
-    """trajectory_opt.py:719-749, with the objective bound to the fused kernel."""
+def create_trajectory_optim_agent_for_model(model_env, agent_cfg, num_particles: int = 1, policy_prior=None, **eval_kw):
+    """trajectory_opt.py:719-749, with the objective bound to the fused kernel.  ``policy_prior``: a :class:`hipets.PolicyPrior` for
+    ``agent.set_policy_prior``."""
     complete_agent_cfg(model_env, agent_cfg)
     agent = _instantiate(agent_cfg)
     agent.set_trajectory_eval_fn(make_eval_fn(model_env, num_particles, **eval_kw))
+    if policy_prior is not None:
+        agent.set_policy_prior(policy_prior)
     return agent

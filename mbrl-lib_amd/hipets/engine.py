@@ -963,6 +963,37 @@ class Engine:
                    halt_reward=0.0 if halt_reward is None else float(halt_reward), use_halt_reward=int(halt_reward is not None), batch=B,
                    rewards=rewards, dones=dones)
 
+    # ---- policy rollouts: the actor rolled through the ensemble (hipets_policy_rollout) ---------------------------------------------
+    def policy_rollout(self, s0: torch.Tensor, horizon: int, *, mean_rows: int = 0, only_elite: bool = True, seed: int = 0, stream_id: int = 0,
+                       eps: Optional[torch.Tensor] = None, states: bool = False):
+        """The snapshot actor (:meth:`policy_set`) rolled ``horizon`` steps through the snapshot ensemble's expected next observation
+        (:meth:`ensemble_set`) from ``s0`` f32 [n, obs_dim] on the device, one launch (hipets_policy_rollout).  Rows below ``mean_rows``
+        take the mean action, the others sample with ``eps`` f32 [horizon, n, act_dim] (None: drawn in-kernel from (seed, stream_id);
+        ``policy_normals(horizon * n, act_dim, seed, stream_id)`` is that table).  Returns actions f32 [n, horizon, act_dim], and with
+        ``states`` also the visited states f32 [horizon + 1, n, obs_dim]."""
+        obs_dim, _, act_dim = self._slot_dims("policy", "policy_set")
+        self._ensemble_spec()
+        dev, H = self.device, int(horizon)
+        if not isinstance(s0, torch.Tensor) or s0.ndim != 2 or int(s0.shape[0]) < 1:
+            raise ValueError("s0 must be a [n, obs_dim] tensor with n >= 1")
+        n = int(s0.shape[0])
+        _check_dev(s0, torch.float32, dev, "s0", (n, obs_dim))
+        if H < 1:
+            raise ValueError(f"horizon must be >= 1, got {horizon}")
+        if eps is not None:
+            _check_dev(eps, torch.float32, dev, "eps", (H, n, act_dim))
+        actions = torch.empty(n, H, act_dim, dtype=torch.float32, device=dev)
+        visited = torch.empty(H + 1, n, obs_dim, dtype=torch.float32, device=dev) if states else None
+        self._call("hipets_policy_rollout", s0=s0, n=n, horizon=H, mean_rows=int(mean_rows), only_elite=int(bool(only_elite)), seed=int(seed),
+                   stream_id=int(stream_id), eps=eps, actions=actions, states=visited)
+        return (actions, visited) if states else actions
+
+    def policy_rollout_geometry(self, n: int):
+        """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of a :meth:`policy_rollout` of ``n`` rows."""
+        r, lds = C.c_int32(), C.c_int32()
+        self._query("hipets_policy_rollout_geometry", n=int(n), row_tiles=C.byref(r), lds_bytes=C.byref(lds))
+        return r.value, lds.value
+
     def timing_enable(self, on=True):
         """True / 1: time every rollout-kernel launch; k > 1: every k-th launch; False / 0: off."""
         self._query("hipets_timing_enable", on=int(on))

@@ -143,9 +143,40 @@ class _PlanOptimizer(Optimizer):
 
     @staticmethod
     def _whole_plan(fused, callback, injected, kwargs) -> bool:
-        """Does the plan run as one library call?  With a fused objective and no callback, injected draws (parity tests) or
-        ``force_generic``."""
-        return fused is not None and callback is None and injected is None and not kwargs.get("force_generic", False)
+        """Does the plan run as one library call?  With a fused objective and no callback, injected draws (parity tests),
+        ``extra_candidates`` or ``force_generic``."""
+        return (fused is not None and callback is None and injected is None and kwargs.get("extra_candidates") is None
+                and not kwargs.get("force_generic", False))
+
+    def _extra_candidates(self, kwargs, shape, smallest: int):
+        """The ``extra_candidates`` of one ``optimize()`` call, checked before anything runs: None, or (rows [num, H, A] clamped to
+        the bounds on the device, mask [num, 1, 1] of the rows that are finite throughout).  ``shape``: the plan variable's, ``smallest``:
+        the fewest rows an iteration of this plan samples.  Every iteration's population takes them in :meth:`_inject`."""
+        extra = kwargs.get("extra_candidates")
+        if extra is None:
+            return None
+        if self.engine.comm_world > 1:
+            raise ValueError("extra_candidates on a sharded engine (one with a communicator) is not supported: every rank would have to hold the same rows")
+        if len(shape) != 2:
+            raise ValueError(f"extra_candidates needs a plan variable [H, A], this plan's is {tuple(shape)}")
+        if not isinstance(extra, torch.Tensor) or extra.dtype != torch.float32 or extra.ndim != 3 or tuple(extra.shape[1:]) != tuple(shape):
+            got = (tuple(extra.shape), extra.dtype) if isinstance(extra, torch.Tensor) else type(extra).__name__
+            raise ValueError(f"extra_candidates must be a float32 tensor [num, {shape[0]}, {shape[1]}], got {got}")
+        num = int(extra.shape[0])
+        if num > smallest:
+            raise ValueError(f"extra_candidates holds {num} rows, the smallest iteration of this plan samples {smallest}")
+        extra = extra.detach().to(self.device)
+        finite = torch.isfinite(extra).all(dim=2).all(dim=1)[:, None, None]
+        return torch.minimum(torch.maximum(extra, self.lower_bound), self.upper_bound), finite
+
+    @staticmethod
+    def _inject(population: torch.Tensor, extra):
+        """Rows [0, num) of the freshly sampled ``population`` <- the clamped candidates; a candidate row holding a non-finite value
+        leaves its row as sampled.  Torch ops on the current stream: no host synchronisation."""
+        if extra is not None and extra[0].shape[0]:
+            rows, finite = extra
+            head = population[:rows.shape[0]]
+            head.copy_(torch.where(finite, rows, head))
 
 
 class CEMOptimizer(_PlanOptimizer):
@@ -190,6 +221,7 @@ class CEMOptimizer(_PlanOptimizer):
     def optimize(self, obj_fun: Callable[[torch.Tensor], torch.Tensor], x0: Optional[torch.Tensor] = None,
                  callback: Optional[Callable[[torch.Tensor, torch.Tensor, int], None]] = None, **kwargs) -> torch.Tensor:
         x0 = x0.to(device=self.device, dtype=torch.float32).contiguous()
+        extra = self._extra_candidates(kwargs, x0.shape, int(self.population_size))
         self.calls += 1
         fused, seed = self._fused_objective(obj_fun, eligible=x0.ndim == 2, planet_ok=True)
         noise = kwargs.get("noise")  # optional injected z per iteration (parity tests)
@@ -208,6 +240,7 @@ class CEMOptimizer(_PlanOptimizer):
             if z is None and self.sampler == "torch":
                 z = rd.population_noise(tuple(population.shape), self._clipped_normal).to(self.device).contiguous()
             self.engine.cem_sample(p, mu, dispersion, self.lower_bound, self.upper_bound, population, z=z, seed=seed, stream_id=stream)
+            self._inject(population, extra)
             values = fused.evaluate_seeded(obj_fun.obs, population, seed, stream) if fused is not None else obj_fun(population)
             if callback is not None:
                 callback(population, values, i)
@@ -240,6 +273,7 @@ class MPPIOptimizer(_PlanOptimizer):
     def optimize(self, obj_fun: Callable[[torch.Tensor], torch.Tensor], x0: Optional[torch.Tensor] = None,
                  callback: Optional[Callable[[torch.Tensor, torch.Tensor, int], None]] = None, **kwargs) -> torch.Tensor:
         H, A, pop = self.planning_horizon, self.action_dimension, self.population_size
+        extra = self._extra_candidates(kwargs, (H, A), int(pop))
         self.calls += 1
         fused, seed = self._fused_objective(obj_fun)
         noise = kwargs.get("noise")
@@ -260,6 +294,7 @@ class MPPIOptimizer(_PlanOptimizer):
                 z = rd.population_noise((pop, H, A), False).to(self.device).contiguous()
             self.engine.mppi_sample(pop, H, A, self.beta, self.mean, past_action, self.lower_bound, self.upper_bound, population,
                                     z=z, seed=seed, stream_id=stream)
+            self._inject(population, extra)
             values = fused.evaluate_seeded(obj_fun.obs, population, seed, stream) if fused is not None else obj_fun(population)
             values = _device_f32(values, self.device)
             if callback is not None:  # the reference calls back after the NaN filter here (:297-300)
@@ -336,6 +371,7 @@ class ICEMOptimizer(_PlanOptimizer):
         x0 = x0.to(device=self.device, dtype=torch.float32).contiguous()
         H, A = x0.shape
         K, keep = int(self.elite_num), int(self.keep_elite_size)
+        extra = self._extra_candidates(kwargs, (H, A), min([self._iteration_size(i) for i in range(self.num_iterations)], default=0))
         self.calls += 1
         fused, seed = self._fused_objective(obj_fun)
         inject = kwargs.get("inject")  # optional injected draws per iteration (parity tests)
@@ -365,6 +401,7 @@ class ICEMOptimizer(_PlanOptimizer):
                 normals = normals.to(self.device, torch.float32).contiguous()
             eng.icem_sample(n, H, A, self.colored_noise_exponent, mu, var, self.lower_bound, self.upper_bound, population,
                             normals=normals, seed=seed, stream_id=sid)
+            self._inject(population[:n], extra)  # (the sampled part: kept / shifted elites and the mean row stay)
             if self.elite is not None:
                 if "keep_perm" in inj:
                     perm = inj["keep_perm"].to(self.device)
