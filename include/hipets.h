@@ -18,10 +18,16 @@
  *     except hipets_set_model which copies weights into its own packed layout.
  *   - `stream` is a hipStream_t (pass torch.cuda.current_stream().cuda_stream); all work is enqueued asynchronously on it.
  *     An engine's workspace is shared by its calls, so their work executes in call order: a call on another stream than the
- *     previous call's makes its stream wait (device side) for that call's work.  Two entry points synchronise `stream` before
- *     returning, because they read caller-owned DEVICE tensors that may be freed right after the call: hipets_set_model and
- *     hipets_planet_set_model.  hipets_timing_read waits for the events it reports; the one-time co-residency self-test of a
- *     persistent DEVICE-mode kernel instance synchronises once (hipets_set_persistent).  Nothing else synchronises.
+ *     previous call's makes its stream wait (device side) for that call's work.  The launch-only helpers take no part in that
+ *     ordering, because they use no workspace: each launches on `stream` a kernel that touches the caller's buffers alone, waits
+ *     for no other call and is waited for by none, so the caller orders them as it orders its own kernels.  They are
+ *     hipets_cem_sample, hipets_cem_refit, hipets_cem_refit_elites, hipets_gather_rows, hipets_mppi_sample, hipets_mppi_update,
+ *     hipets_icem_sample, hipets_icem_shift, hipets_particle_reduce, hipets_fast_schedule, hipets_fast_normals,
+ *     hipets_device_perms and hipets_policy_normals.  Four entry points take part in the ordering and also synchronise `stream`
+ *     before returning, because they read caller-owned DEVICE tensors and HOST staging that may be freed right after the call:
+ *     hipets_set_model, hipets_set_model_columns, hipets_planet_set_model and hipets_ensemble_set.  hipets_timing_read waits for
+ *     the events it reports; the one-time co-residency self-test of a persistent DEVICE-mode kernel instance synchronises once
+ *     (hipets_set_persistent); hipets_sac_bind makes one blocking 16-byte copy.  Nothing else synchronises.
  *   - HOST arrays are consumed before the call returns, so temporaries are fine: observations are copied into
  *     pinned staging buffers owned by the engine and uploaded asynchronously from there; model descriptors are
  *     uploaded inside hipets_set_model, which synchronises.
