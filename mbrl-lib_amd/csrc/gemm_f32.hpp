@@ -19,6 +19,10 @@ namespace hipets {
 __device__ __forceinline__ void mfma16x16x4(const float a, const float b, f32x4& c) {
     asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(c) : "v"(a), "v"(b));
 }
+// ... with the weight operand read from an AccVGPR (gfx950 MFMAs take A / B from either file): the resident op heads below
+__device__ __forceinline__ void mfma16x16x4_ra(const float a, const float b, f32x4& c) {
+    asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(c) : "a"(a), "v"(b));
+}
 // >= 12 wait states between the last 8-pass MFMA and a VALU read of its result (cdna4 ISA, XDL write -> VALU read)
 __device__ __forceinline__ void mfma_drain() { asm volatile("s_nop 15" ::: "memory"); }
 
@@ -94,6 +98,20 @@ __host__ __device__ inline void hipets_bound_fail(const int line) {
 #define HIPETS_BOUND(cond) ((void)0)
 #endif
 
+// RESIDENT OP HEADS (KSpec::RES; the straight persistent form of the fused fp32 instances with one wave per SIMD, R = 3).  There a
+// workgroup is bound to ONE member for the whole launch, so what a wave needs before the first MFMA of an op -- its biases and the
+// chunk-0 weight fragments of its column tiles -- are the same bits at every step.  They are loaded ONCE per launch, straight into
+// AccVGPRs (these instances leave ~200 of the 256 idle), and every step's op starts from them: accumulators from the resident
+// bias, the chunk-0 MFMAs with their weight operand in the AccVGPR file; the only loads in front of the first MFMA are the
+// activation fragments from LDS.  From chunk 1 on the k loop is the ordinary one (same operands, same order: same bits).
+// One head = at most kMaxCT = 3 strided column tiles + 3 extra units of a wave: 6 fragments + 6 bias quads, of which a wave's
+// (CT, EX) uses CT + EX each; the others are never loaded or read (no register).
+struct ResHead {
+    f32x4 b[3], bx[3], bv[3], bvx[3];
+};
+__device__ __forceinline__ void res_load(f32x4& dst, const float* const p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(dst) : "v"(p) : "memory"); }
+__device__ __forceinline__ void res_pin(f32x4& v) { asm volatile("" : "+a"(v)); }
+
 struct NoTail {};  // wave_gemm's TL: the ordinary epilogue (activation, store as the next op's LDS image)
 // A fused tail = four stages over the accumulators (units) a wave finished: prep(slot, c, r) for EVERY unit of a group first -- it
 // only loads (LDS) what the unit will need into its slot, so the round trips of all units overlap --, then draw(slot a, slot b, c_a,
@@ -164,12 +182,16 @@ struct KsArgs {
 
 // KS bit 0 (KSI): the input image's last k chunk is NOT in LDS -- it is rebuilt from ks->part_in; bit 1 (KSO): see above;
 // bit 2: no k-split, only the one-tile k loop that fetches two chunks ahead (kTriple: ops with a static chunk count, planet.hpp)
-template <int R, int CT, int EX, int ACT, class TL = NoTail, int LD = -1, bool SPL = false, int KCS = -1, int KS = 0>
+// RES: 1 = the op's head is *rh (resident, see ResHead); 3 = one of rh[0..2], chosen by the wave-uniform rsel (the hidden-fed layers share
+// one code body: only the head -- bias init + chunk-0 MFMAs -- exists per layer, behind a switch; the rest of the k loop once)
+template <int R, int CT, int EX, int ACT, class TL = NoTail, int LD = -1, bool SPL = false, int KCS = -1, int KS = 0, int RES = 0>
 __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* __restrict__ out, const int ld_rt,
                                           const float* __restrict__ W, const float* __restrict__ bias, const int KC_rt,
                                           const int tail_steps, const int c_first, const Extras ex,
                                           const bool apply_act, const int act, const float slope, const int lane,
-                                          Prof& prof, const TL* tl = nullptr, const int ldi_rt = 0, const KsArgs* ks = nullptr) {
+                                          Prof& prof, const TL* tl = nullptr, const int ldi_rt = 0, const KsArgs* ks = nullptr,
+                                          const ResHead* rh = nullptr, const int rsel = 0) {
+    static_assert(!RES || (LD > 0 && KS == 0 && R >= 3 && CT <= 3 && EX <= 3), "resident heads: shape-specialised one-wave-per-SIMD instances");
     constexpr int CTn = CT > 0 ? CT : 1;
     constexpr int EXn = EX > 0 ? EX : 1;
     constexpr bool KSI = (KS & 1) != 0, KSO = (KS & 2) != 0;
@@ -198,10 +220,12 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
     const float* ap = in + (lane & 15) * ldi + 4 * (lane >> 4);
     // biases of this lane's columns: loaded before the k loop so their latency hides behind it
     f32x4 bv[CTn], bvx[EXn];
+    if constexpr (!RES) {
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) bv[ct] = *reinterpret_cast<const f32x4*>(bias + (c_first + kWaves * ct) * 16 + 4 * (lane >> 4));
 #pragma unroll
     for (int e = 0; e < EX; ++e) bvx[e] = *reinterpret_cast<const f32x4*>(bias + exc[e] * 16 + 4 * (lane >> 4));
+    }
     // The weight block of this op as a raw buffer (base = W, wave-uniform): a fragment load is buffer_load_dwordx4 v, v_off, s[rsrc],
     // s_chunk offen -- the loop-invariant per-lane offset in a VGPR, the chunk offset (kk KiB) in an SGPR, NO address VALU work in
     // the k loop (fp32 MFMAs and VALU instructions exclude each other on a SIMD: every v_lshl_add_u64 there is MFMA-pipe idle time)
@@ -385,7 +409,14 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
         }
     }
     GemmFrags<R, CT, EX> f0, f1;
-    load(f0, 0);
+    if constexpr (RES) {  // chunk 0: the weight fragments are resident, only the activation fragments (LDS) are fetched
+#pragma unroll
+        for (int r = 0; r < (CT > 0 ? R : 0); ++r) f0.a[r] = *reinterpret_cast<const f32x4*>(ap + r * 16 * ldi);
+#pragma unroll
+        for (int e = 0; e < EX; ++e) f0.ax[e] = *reinterpret_cast<const f32x4*>(ap + axoff[e]);
+    } else {
+        load(f0, 0);
+    }
     // One-tile k-split instances fetch TWO chunks ahead (kTriple below): a wave's 12 MFMAs per chunk (384 cycles) are no cover for an
     // L2 round trip issued somewhere inside the previous chunk
     // (ops whose chunk count is a compile-time fact -- KCS: everything fed by a hidden layer -- so that the loop's remainder is no run-time
@@ -396,18 +427,21 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
     // accumulators start at the bias (C input of the first MFMA) instead of zero: no add in the epilogue.  Initialised AFTER
     // chunk 0's fragment loads were issued: the bias loads are older, so waiting for them leaves the fragments in flight
     // (initialising first serialised two L2 round trips per layer: ~1.2k cycles of "set-up" per layer in the phase profile)
+    if constexpr (!RES) {
 #pragma unroll
     for (int ct = 0; ct < CTn; ++ct)
 #pragma unroll
         for (int r = 0; r < R; ++r) acc[ct][r] = CT > 0 ? bv[ct] : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int e = 0; e < EXn; ++e) accx[e] = EX > 0 ? bvx[e] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
     // Pin every accumulator's initial value HERE: to the compiler an asm MFMA is an ordinary reader of its C operand, so it may
     // sink the (VALU) initialisation -- a copy of the bias, the zeros of the odd-k-step accumulators -- down to just in front of
     // the first MFMA that uses the register, inside a k-step, behind that k-step's s_nop: a VALU write followed at once by an MFMA
     // reading it as SrcC (hazard (1) below; found in the ISA of the cfg4 instances by __graft_entry__.scan_isa_hazards (tests/test_abi.py), where it returned
     // wrong sums).  An empty asm that "modifies" the register makes the value opaque: it must be complete before this point.
     auto pin = [](f32x4& v) __attribute__((always_inline)) { asm volatile("" : "+v"(v)); };
+    if constexpr (!RES) {
 #pragma unroll
     for (int ct = 0; ct < CTn; ++ct)
 #pragma unroll
@@ -422,6 +456,7 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
     }
     if constexpr (kSplit) pin(acc_odd);
     prof.mark(14);
+    }
     f32x4 a_last = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (KSI) {  // this lane's fragment of the input's last chunk: the activation of the four partial sums, in ONE fixed order
         static_assert(ACT == HIPETS_ACT_SILU, "k-split instances are SiLU instances");
@@ -457,7 +492,119 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
             }
         prof.mark(7);  // (profiling builds) the k-split share: its loads' round trip + 16 MFMAs
     }
-    if constexpr (KCS > 0 && !kTriple) {
+    if constexpr (RES != 0) {
+        auto acc_init = [&](const f32x4* const b, const f32x4* const bx) __attribute__((always_inline)) {
+#pragma unroll
+            for (int ct = 0; ct < CTn; ++ct)
+#pragma unroll
+                for (int r = 0; r < R; ++r) acc[ct][r] = CT > 0 ? b[ct] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int e = 0; e < EXn; ++e) accx[e] = EX > 0 ? bx[e] : f32x4{0.f, 0.f, 0.f, 0.f};
+        };
+        auto pin_acc = [&]() __attribute__((always_inline)) {
+#pragma unroll
+            for (int ct = 0; ct < CTn; ++ct)
+#pragma unroll
+                for (int r = 0; r < R; ++r) {
+                    if constexpr (CT > 0) pin(acc[ct][r]);
+                    if constexpr (CT > 0 && kSplitAll) pin(acco[ct][r]);
+                }
+#pragma unroll
+            for (int e = 0; e < EXn; ++e) {
+                if constexpr (EX > 0) pin(accx[e]);
+                if constexpr (EX > 0 && kSplitAll) pin(accxo[e]);
+            }
+            if constexpr (kSplit) pin(acc_odd);
+        };
+        // Resident head (RES): the accumulators start from the resident bias (v_accvgpr_read: VALU writes, pinned ahead of the k-step's
+        // s_nop like every initial value), then chunk 0 with the weight operand in AccVGPRs; chunk 1's fragment loads ride behind its
+        // MFMAs exactly as compute_il places them.  An op of ONE chunk runs its tail steps from the head.  Every arm ends drained.
+        auto mfma_unit_h = [&](const ResHead& h, const GemmFrags<R, CT, EX>& f, const int s, const int u) __attribute__((always_inline)) {
+            if constexpr (kSplit) {
+                f32x4& dst = (s & 1) ? acc_odd : (CT ? acc[0][0] : accx[0]);
+                if constexpr (CT) mfma16x16x4_ra(h.b[0][s], f.a[0][s], dst);
+                else mfma16x16x4_ra(h.bx[0][s], f.ax[0][s], dst);
+            } else if (u < CT * R) {
+                const int ct = u / R, r = u - ct * R;
+                if constexpr (kSplitAll) mfma16x16x4_ra(h.b[ct][s], f.a[r][s], (s & 1) ? acco[ct][r] : acc[ct][r]);
+                else mfma16x16x4_ra(h.b[ct][s], f.a[r][s], acc[ct][r]);
+            } else {
+                const int e = u - CT * R;
+                if constexpr (kSplitAll) mfma16x16x4_ra(h.bx[e][s], f.ax[e][s], (s & 1) ? accxo[e] : accx[e]);
+                else mfma16x16x4_ra(h.bx[e][s], f.ax[e][s], accx[e]);
+            }
+        };
+        auto head = [&](const ResHead& h) __attribute__((always_inline)) {
+            acc_init(h.bv, h.bvx);
+            pin_acc();
+            prof.mark(14);
+            auto kstep_h = [&](const int s) __attribute__((always_inline)) {
+                asm volatile("s_nop 1");
+#pragma unroll
+                for (int u = 0; u < kNU; ++u) mfma_unit_h(h, f0, s, u);
+            };
+            if (KC >= 2) {
+#pragma unroll
+                for (int ks_ = 0; ks_ < 4; ++ks_) {
+                    asm volatile("s_nop 1");
+#pragma unroll
+                    for (int u = 0; u < kNU; ++u) {
+                        mfma_unit_h(h, f0, ks_, u);
+                        loads_behind(f1, 1, ks_ * kNU + u + 1);
+                    }
+                }
+                if constexpr (RES == 3 || KCS <= 0) drain_all();  // (an arm of the layer switch / of the run-time chunk count; straight-line code otherwise)
+            } else {
+                switch (tail_steps) {
+                    case 1: kstep_h(0); drain_all(); break;
+                    case 2: kstep_h(0); kstep_h(1); drain_all(); break;
+                    case 3: kstep_h(0); kstep_h(1); kstep_h(2); drain_all(); break;
+                    default: kstep_h(0); kstep_h(1); kstep_h(2); kstep_h(3); drain_all(); break;
+                }
+            }
+        };
+        // chunks 1 .. KC - 1 behind a head: the two-set loop with the sets' roles swapped (chunk 1 is in f1)
+        auto rest = [&]() __attribute__((always_inline)) {
+            if (KC < 2) return;
+            int kk = 1;
+            if constexpr (KCS > 0) {
+#pragma unroll
+                for (int k2 = 1; k2 + 2 < KCS; k2 += 2) {
+                    compute_il(f1, f0, k2 + 1);
+                    compute_il(f0, f1, k2 + 2);
+                }
+                constexpr int kEndR = KCS >= 3 ? 1 + ((KCS - 2) / 2) * 2 : 1;  // where that loop leaves k2: the largest odd number <= KCS - 1
+                if constexpr (kEndR + 1 < KCS) {
+                    compute_il(f1, f0, kEndR + 1);
+                    compute_tail(f0);
+                } else {
+                    compute_tail(f1);
+                }
+            } else {
+                for (; kk + 2 < KC; kk += 2) {
+                    compute_il(f1, f0, kk + 1);
+                    compute_il(f0, f1, kk + 2);
+                }
+                if (kk > 1) drain_all();
+                if (kk + 1 < KC) {
+                    compute_il(f1, f0, kk + 1);
+                    compute_tail(f0);
+                } else {
+                    compute_tail(f1);
+                }
+            }
+        };
+        if constexpr (RES == 1) {
+            head(rh[0]);
+        } else {
+            switch (rsel) {
+                case 0: head(rh[0]); break;
+                case 1: head(rh[1]); break;
+                default: head(rh[2]); break;
+            }
+        }
+        rest();
+    } else if constexpr (KCS > 0 && !kTriple) {
         constexpr int kEnd = KCS >= 2 ? ((KCS - 1) / 2) * 2 : 0;  // the loop below leaves kk at the smallest even number >= KCS - 2
 #pragma unroll
         for (int kk = 0; kk + 2 < KCS; kk += 2) {
@@ -716,12 +863,14 @@ __device__ __forceinline__ void wave_gemm_ex(int nex, const float* in, float* ou
 // from it and the wave index through ONE branch, and only the two wave_gemm instances the shape needs are compiled;
 // CS < 0: it is read from the layer table and dispatched through the (full, nex) switches.
 // KS (shape-specialised ops of one-tile workgroups): wave_gemm's k-split bits; part_in / part_out: the partial-sum buffers (KsArgs)
-template <int R, int ACT = -1, int CS = -1, class TL = NoTail, int LD = -1, bool SPL = false, int KCS = -1, int KS = 0>
+// RES / rh / rsel: wave_gemm's resident head (shape-specialised ops whose strided tiles go through in one pass)
+template <int R, int ACT = -1, int CS = -1, class TL = NoTail, int LD = -1, bool SPL = false, int KCS = -1, int KS = 0, int RES = 0>
 __device__ __forceinline__ void linear_op(const float* W, const float* bias, const LayerMeta lm, const int ld, const bool apply_act,
                                           const int activation, const float slope, const float* in, float* out, const int wave,
                                           const int lane, Prof& prof, const TL* tl = nullptr, const int ldi = 0,
-                                          const float* part_in = nullptr, float* part_out = nullptr) {
+                                          const float* part_in = nullptr, float* part_out = nullptr, const ResHead* rh = nullptr, const int rsel = 0) {
     static_assert(std::is_same<TL, NoTail>::value || CS >= 0, "a fused tail needs a shape-specialised op");
+    static_assert(!RES || (CS >= 0 && CS / kWaves <= 3 && KS == 0), "resident heads: one pass of a shape-specialised op");
     static_assert(!KS || CS >= 0, "k-split needs a shape-specialised op");
     const int KC = lm.Kp / kKChunk;
     if constexpr ((KS & 2) != 0) {
@@ -764,13 +913,13 @@ __device__ __forceinline__ void linear_op(const float* W, const float* bias, con
         constexpr int lo = nu / kWaves, hi = (nu + kWaves - 1) / kWaves;
         if constexpr (lo == hi) {
             if constexpr (last > 0 || lo > 0)
-                wave_gemm<R, last, lo, ACT, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks);
+                wave_gemm<R, last, lo, ACT, TL, LD, SPL, KCS, KS, RES>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks, rh, rsel);
         } else {
             if (wave < nu % kWaves) {
-                wave_gemm<R, last, hi, ACT, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks);
+                wave_gemm<R, last, hi, ACT, TL, LD, SPL, KCS, KS, RES>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks, rh, rsel);
             } else {
                 if constexpr (last > 0 || lo > 0)
-                    wave_gemm<R, last, lo, ACT, TL, LD, SPL, KCS, KS>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks);
+                    wave_gemm<R, last, lo, ACT, TL, LD, SPL, KCS, KS, RES>(in, out, ld, W, bias, KC, lm.tail_steps, c_first, ex, apply_act, activation, slope, lane, prof, tl, ldi, &ks, rh, rsel);
             }
         }
     } else {
@@ -802,6 +951,40 @@ __device__ __forceinline__ void linear_op(const float* W, const float* bias, con
         }
     }
     }  // (not a k-split producer)
+}
+
+// The head of one shape-specialised op (CS column tiles) as THIS wave's share of it needs it -- linear_op's dealing: strided tiles
+// wave + kWaves ct, leftover unit e = (tile kWaves full + (wave + kWaves e) / R, ...) -- requested into AccVGPRs; the caller waits
+// (s_waitcnt vmcnt(0)) once for all ops.  A wave with one leftover unit fewer than `hi` requests its unit 0 again for the slot it
+// never reads: branch-free, every address a valid one.
+template <int R, int CS>
+__device__ __forceinline__ void res_load_op(ResHead& h, const float* const W, const float* const bias, const int KC, const int wave, const int lane) {
+    constexpr int full = CS / kWaves, rem = CS % kWaves, nu = rem * R;
+    constexpr int lo = nu / kWaves, hi = (nu + kWaves - 1) / kWaves;
+    static_assert(full <= 3 && hi <= 3, "one pass, at most three leftover units");
+#pragma unroll
+    for (int ct = 0; ct < full; ++ct) {
+        const int c = wave + kWaves * ct;
+        res_load(h.b[ct], W + ((size_t)c * KC * 64 + lane) * 4);
+        res_load(h.bv[ct], bias + c * 16 + 4 * (lane >> 4));
+    }
+#pragma unroll
+    for (int e = 0; e < hi; ++e) {
+        const int u = wave + kWaves * e;  // (units nu and up do not exist: unit 0's tile, a valid one, for the slot nobody reads)
+        const int c = kWaves * full + (u < nu ? u : 0) / R;
+        res_load(h.bx[e], W + ((size_t)c * KC * 64 + lane) * 4);
+        res_load(h.bvx[e], bias + c * 16 + 4 * (lane >> 4));
+    }
+}
+// ... and the same registers re-defined in place (empty asm, "+a"): behind the wait for the loads, and wherever the allocator must not
+// be free to move the resident set to other registers (the step loop's back edge)
+template <int R, int CS>
+__device__ __forceinline__ void res_pin_op(ResHead& h) {
+    constexpr int full = CS / kWaves, hi = ((CS % kWaves) * R + kWaves - 1) / kWaves;
+#pragma unroll
+    for (int ct = 0; ct < full; ++ct) { res_pin(h.b[ct]); res_pin(h.bv[ct]); }
+#pragma unroll
+    for (int e = 0; e < hi; ++e) { res_pin(h.bx[e]); res_pin(h.bvx[e]); }
 }
 
 }  // namespace hipets

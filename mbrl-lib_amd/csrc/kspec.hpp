@@ -21,6 +21,7 @@ namespace hipets {
 // shape-specialised fp32 instances, feed the fused tail (KSpec::FUSE).  Wider ones (cfg4': 47) keep the plain order: a wave's share
 // is a dozen units there, and twice the accumulators (or a dozen inlined tails) do not fit the register file.
 constexpr int kSplMaxTiles = 8;
+constexpr int kResLayers = 5;  // ops of a model a KSpec::RES instance runs: input layer, three hidden-fed layers, output layer
 
 constexpr int lean_ld(int hidc, int outc) {
     int m = (hidc > outc ? hidc : outc) * 16;
@@ -29,7 +30,7 @@ constexpr int lean_ld(int hidc, int outc) {
 }
 
 template <int ACT_, int HIDC_ = -1, int OUTC_ = -1, int NORM_ = -1, int OBSP_ = -1, int REW_ = -1, int TERM_ = -1, int KMODE_ = -1, int PREC_ = 0,
-          int FUSE_ = 0>
+          int FUSE_ = 0, int RES_ = 0>
 struct KSpec {
     // WIDE (fused fp32 instances whose output layer is wider than kSplMaxTiles column tiles -- cfg4': 47): no LDS image of the outputs
     // exists at all, so the two activation buffers hold hidden activations only (row stride for HIDC tiles) and the model-input
@@ -54,6 +55,11 @@ struct KSpec {
     // of 7, no LDS round trip of the 2 x out_dim outputs).  Needs reward / termination forms that read state dims 0..3 only.
     // (output layers of up to 8 column tiles: beyond that -- cfg4' has 47 -- a wave's tail covers a dozen units and the instance spills)
     static constexpr bool FUSE = FUSE_ != 0 && LEAN && PREC_ == HIPETS_PREC_F32 && (OUTC_ <= kSplMaxTiles || WIDE);
+    // RES (fused fp32 instances, not WIDE, R = 3: rollout_kernel asserts the R): the instance of the STRAIGHT PERSISTENT form only -- every
+    // launched workgroup serves one logical workgroup, i.e. one member, for the whole launch -- with the op heads resident in AccVGPRs
+    // (gemm_f32.hpp ResHead).  Models of kResLayers ops: the hidden-fed layers' heads are told apart by a switch over exactly three.
+    static constexpr bool RES = RES_ != 0;
+    static_assert(!RES || (FUSE && !WIDE), "resident op heads: fused fp32 instances");
     static constexpr bool SPL_OUT = OUTC_ >= 0 && OUTC_ <= kSplMaxTiles;  // the output layer sums even / odd k-steps separately (wave_gemm SPL)
     // K-split of the leftover hidden column tile (gemm_f32.hpp KsArgs): the fused fp32 instances whose hidden layers leave ONE column tile over
     // (13 = 3 x 4 + 1), used by the kernel for ONE-TILE workgroups only (R = 1: rollout_kernel's kKS)
@@ -104,7 +110,8 @@ __device__ __forceinline__ void mlp_layer_b3(const ModelDev& md, const LayerMeta
 // part: the two k-split partial-sum buffers of a KSpec::KSPLIT one-tile workgroup ([2][kWaves][64][4] floats, alternating by layer)
 template <int R, class S>
 __device__ __forceinline__ void mlp_layer(const ModelDev& md, const LayerMeta* lmeta, const int l, const int member,
-                                          const float* in, float* out, const int wave, const int lane, Prof& prof, float* part = nullptr) {
+                                          const float* in, float* out, const int wave, const int lane, Prof& prof, float* part = nullptr,
+                                          const ResHead* heads = nullptr) {
     const LayerMeta lm = lmeta[l];  // staged in LDS once per launch (a global scalar load here cost ~400 cycles per layer)
     const float* W = md.w + (size_t)member * md.wmember + lm.woff;
     const float* bias = md.b + (size_t)member * md.bmember + lm.boff;
@@ -122,6 +129,10 @@ __device__ __forceinline__ void mlp_layer(const ModelDev& md, const LayerMeta* l
         // puts v_mov copies straight behind asm MFMAs -- which it believes complete at once (wave_gemm, "drain_all") -- and the
         // interleaved + unrolled build returned wrong sums (caught by the cfg5 parity tests); R = 1 measured 1 % slower unrolled.
         constexpr int kHidChunks = MinWavesOf<R>::value == 1 ? S::HIDC : -1;
+        if constexpr (S::RES) {  // (never an output layer here: the fused instances run it through mlp_output_layer_fused)
+            if (l == 0) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD, false, -1, 0, 1>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, 0, nullptr, nullptr, heads);
+            else linear_op<R, S::ACT, S::HIDC, NoTail, S::LD, false, kHidChunks, 0, 3>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, 0, nullptr, nullptr, heads + 1, l - 1);
+        } else
         if (l == 0) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof, nullptr, S::WIDE ? md.ld_in : 0);
         else if (l < md.n_layers - 1) linear_op<R, S::ACT, S::HIDC, NoTail, S::LD, false, kHidChunks>(W, bias, lm, md.ld, true, md.activation, md.slope, in, out, wave, lane, prof);
         else linear_op<R, S::ACT, S::OUTC, NoTail, S::LD, (S::OUTC <= kSplMaxTiles), kHidChunks>(W, bias, lm, md.ld, false, md.activation, md.slope, in, out, wave, lane, prof);
@@ -146,16 +157,45 @@ __device__ __forceinline__ void mlp_layer(const ModelDev& md, const LayerMeta* l
 // The OUTPUT layer of a KSpec::FUSE instance: the "head pair" pack, accumulators handed to `tl` (no LDS image of the outputs)
 template <int R, class S, class TL>
 __device__ __forceinline__ void mlp_output_layer_fused(const ModelDev& md, const LayerMeta* lmeta, const int member, const float* in,
-                                                       const int wave, const int lane, Prof& prof, const TL& tl, const float* part = nullptr) {
+                                                       const int wave, const int lane, Prof& prof, const TL& tl, const float* part = nullptr,
+                                                       const ResHead* heads = nullptr) {
     const LayerMeta lm = lmeta[md.n_layers - 1];
     const float* W = md.w + (size_t)member * md.wmember + lm.woff_pairs;
     const float* bias = md.b + (size_t)member * md.bmember + lm.boff_pairs;
     if constexpr (S::KSPLIT && R == 1) {  // the last hidden layer (index n_layers - 2) left its 13th tile as partial sums
         const float* const pi = part + ((md.n_layers - 2) & 1) * (kWaves * 64 * 4);
         linear_op<R, S::ACT, S::OUTC, TL, S::LD, S::SPL_OUT, S::HIDC, 1>(W, bias, lm, md.ld, false, md.activation, md.slope, in, nullptr, wave, lane, prof, &tl, 0, pi);
+    } else if constexpr (S::RES) {
+        linear_op<R, S::ACT, S::OUTC, TL, S::LD, S::SPL_OUT, S::HIDC, 0, 1>(W, bias, lm, md.ld, false, md.activation, md.slope, in, nullptr, wave, lane, prof, &tl, 0, nullptr, nullptr, heads + kResLayers - 1);
     } else {
         linear_op<R, S::ACT, S::OUTC, TL, S::LD, S::SPL_OUT, MinWavesOf<R>::value == 1 ? S::HIDC : -1>(W, bias, lm, md.ld, false, md.activation, md.slope, in, nullptr, wave, lane, prof, &tl);
     }
+}
+
+// a RES instance's heads, one per op; nothing in every other instance
+template <bool RES> struct ResHeadStore {
+    ResHead h[kResLayers];
+    __device__ __forceinline__ ResHead* get() { return h; }
+};
+template <> struct ResHeadStore<false> {
+    __device__ __forceinline__ ResHead* get() { return nullptr; }
+};
+
+// The heads of all kResLayers ops of member `member` for this wave, requested into AccVGPRs (the caller waits once and pins them)
+template <int R, class S>
+__device__ __forceinline__ void res_load_heads(ResHead* const heads, const ModelDev& md, const LayerMeta* lmeta, const int member, const int wave, const int lane) {
+    const float* const Wm = md.w + (size_t)member * md.wmember;
+    const float* const bm = md.b + (size_t)member * md.bmember;
+#pragma unroll
+    for (int l = 0; l < kResLayers - 1; ++l) res_load_op<R, S::HIDC>(heads[l], Wm + lmeta[l].woff, bm + lmeta[l].boff, lmeta[l].Kp / kKChunk, wave, lane);
+    const LayerMeta lo = lmeta[kResLayers - 1];
+    res_load_op<R, S::OUTC>(heads[kResLayers - 1], Wm + lo.woff_pairs, bm + lo.boff_pairs, lo.Kp / kKChunk, wave, lane);
+}
+template <int R, class S>
+__device__ __forceinline__ void res_pin_heads(ResHead* const heads) {
+#pragma unroll
+    for (int l = 0; l < kResLayers - 1; ++l) res_pin_op<R, S::HIDC>(heads[l]);
+    res_pin_op<R, S::OUTC>(heads[kResLayers - 1]);
 }
 
 }  // namespace hipets

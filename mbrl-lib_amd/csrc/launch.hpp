@@ -6,6 +6,7 @@
 #include "kspec.hpp"
 #include "lds_optin.hpp"
 #include "planet_types.hpp"
+#include "residency_rule.hpp"
 #include "rollout_types.hpp"
 
 namespace hipets {
@@ -107,8 +108,8 @@ inline bool lean_call(const ModelDev& md, const RolloutArgs& ra) {
 }
 
 // the lean fp32 instance X(hc, oc, rw, tm, ob) of the tables above, as rollout_inst.inc instantiates it for launch mode KMODE
-template <int HC, int OC, int RW, int TM, int OB, int KMODE>
-using LeanSpec = KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, OB, RW, TM, KMODE, HIPETS_PREC_F32, 1>;
+template <int HC, int OC, int RW, int TM, int OB, int KMODE, int RES = 0>
+using LeanSpec = KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, OB, RW, TM, KMODE, HIPETS_PREC_F32, 1, RES>;
 
 // does the model have the shape of the lean fp32 instance X(hc, oc, rw, tm, ob) of the tables above (the LDS row stride included)?
 inline bool lean_shape_is(const ModelDev& md, const int hc, const int oc, const int rw, const int tm, const int ob) {
@@ -190,12 +191,24 @@ inline bool hid_static_call(const ModelDev& md, const RolloutArgs& ra) {
 // layout (RolloutArgs::wide_lds); generic_silu: the generic instance with the SiLU epilogue fixed.  Refusals: no_b3 / no_bf16 (bf16x3 and
 // bf16 arithmetic exist in shape-specialised instances only: a model or call without one fails, it never runs another arithmetic),
 // no_wide (LDS sized for a WIDE instance that does not exist for this R / call).
-enum class RolloutInstance { lean, lean_wide, b3, bf16, hidden_static, generic_silu, generic, no_b3, no_bf16, no_wide };
+// lean_resident: the KSpec::RES twin of a plain lean instance (op heads resident in AccVGPRs), for the straight persistent form alone.
+enum class RolloutInstance { lean, lean_resident, lean_wide, b3, bf16, hidden_static, generic_silu, generic, no_b3, no_bf16, no_wide };
+// May a DEVICE rollout of `logical` workgroups of R row tiles ask for the resident-heads instance (RolloutArgs::resident_heads)?  Its
+// premise: one wave per SIMD with the whole register file (R = 3: residency_rule.hpp), a model of kResLayers ops, and a persistent launch in which every
+// launched workgroup serves exactly one logical workgroup for the whole horizon -- at most one per CU.  (A pure host rule; the caller
+// still has to find that many workgroups co-resident: rollout.hip falls back to the plain instance where the capacity query says no.)
+inline bool resident_heads_call(const ModelDev& md, const int R, const int logical, const int n_cu, const int horizon) {
+    static_assert(kResLayers == kResHeadOps, "the host rule and the kernel count the same ops");
+    return md.precision == HIPETS_PREC_F32 && resident_heads_wanted(R, md.n_layers, logical, n_cu, horizon);
+}
 inline RolloutInstance pick_rollout_instance(const ModelDev& md, const RolloutArgs& ra, const int R) {
     const bool lean = lean_call(md, ra);
     if (md.precision == HIPETS_PREC_BF16X3) return lean && b3_shape_exists(md, R) ? RolloutInstance::b3 : RolloutInstance::no_b3;
     if (md.precision == HIPETS_PREC_BF16) return lean && b3_shape_exists(md, R) ? RolloutInstance::bf16 : RolloutInstance::no_bf16;
-    if (lean && lean_shape(md, R) == (ra.wide_lds ? LeanShape::wide : LeanShape::plain)) return ra.wide_lds ? RolloutInstance::lean_wide : RolloutInstance::lean;
+    if (lean && lean_shape(md, R) == (ra.wide_lds ? LeanShape::wide : LeanShape::plain)) {
+        if (ra.wide_lds) return RolloutInstance::lean_wide;
+        return ra.resident_heads && !ra.whole_horizon && R == 3 && md.n_layers == kResLayers ? RolloutInstance::lean_resident : RolloutInstance::lean;
+    }
     if (ra.wide_lds) return RolloutInstance::no_wide;
     if (hid_static_call(md, ra)) return RolloutInstance::hidden_static;
     return md.activation == HIPETS_ACT_SILU ? RolloutInstance::generic_silu : RolloutInstance::generic;

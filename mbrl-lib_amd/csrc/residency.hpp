@@ -105,7 +105,7 @@ inline hipError_t resident_capacity(KernelRec& k, const int want, const unsigned
 // failed (CUs held by another process, a masked device, an occupancy estimate that does not hold on this ROCm build): *persistent_ok goes
 // false -- per-step launches until hipets_set_persistent(e, 1).  With a capacity, persistent_pays (residency_rule.hpp) chooses.
 inline hipError_t decide_launch_form(KernelRec& k, const int logical, const unsigned lds, const int lds_max, const int n_cu, const ModelDev& md, const RolloutArgs& ra,
-                                     int* census, const long long poll_ticks, hipStream_t st, bool* persistent_ok, bool* persistent) {
+                                     int* census, const long long poll_ticks, hipStream_t st, bool* persistent_ok, bool* persistent, int* capacity_out = nullptr) {
     int capacity = 0;
     RolloutArgs q = ra;
     q.census = census;
@@ -113,6 +113,7 @@ inline hipError_t decide_launch_form(KernelRec& k, const int logical, const unsi
     const hipError_t e = resident_capacity(k, logical, lds, lds_max, md, q, st, &capacity);
     if (e == hipSuccess && capacity <= 0) *persistent_ok = false;
     *persistent = capacity > 0 && persistent_pays(logical, capacity, n_cu);
+    if (capacity_out) *capacity_out = capacity;
     return e;
 }
 

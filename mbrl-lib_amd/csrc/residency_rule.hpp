@@ -35,4 +35,16 @@ int resident_capacity_rule(Occ& oc, const int want, const int wg_cap, SelfTest&&
 // they free up; fixed turns (3 for some workgroups, 2 for the rest) measured slower there (cfg5: 7.3 vs 6.6 ms).
 inline bool persistent_pays(const int logical, const int capacity, const int n_cu) { return logical <= capacity || capacity <= n_cu; }
 
+// The resident-heads instance of a lean fp32 shape (kspec.hpp KSpec::RES) keeps a wave's op heads in registers for the whole launch: right
+// only where a launched workgroup serves ONE logical workgroup -- one member -- from the first step to the last.  Asked for
+// (resident_heads_wanted) by a DEVICE rollout of `logical` workgroups of R row tiles when the instance exists -- R = 3: one wave per
+// SIMD with the whole register file (the R = 4 instance, 13 MFMA units per wave, did not fit the heads next to its accumulators: 40 bytes
+// of scratch per lane in the build's report, so it is not instantiated); a model of kResHeadOps ops -- and the call can be one persistent launch with at most one workgroup per CU; kept
+// (resident_heads_kept) only if the capacity query then finds all of them co-resident: no turns, no per-step launches.
+constexpr int kResHeadOps = 5;
+inline bool resident_heads_wanted(const int R, const int n_layers, const int logical, const int n_cu, const int horizon) {
+    return R == 3 && n_layers == kResHeadOps && logical >= 1 && logical <= n_cu && horizon > 1;
+}
+inline bool resident_heads_kept(const bool persistent, const int capacity, const int logical) { return persistent && capacity >= logical; }
+
 }  // namespace hipets

@@ -54,11 +54,11 @@ int launch_rollout(hipets_engine* e, int R, int grid, size_t lds, const RolloutA
 }
 
 // persistent form or one launch per step, for a DEVICE rollout of `logical` workgroups (residency.hpp decide_launch_form)
-int launch_form(hipets_engine* e, int R, int logical, size_t lds, RolloutArgs ra, hipStream_t st, bool* persistent) {
+int launch_form(hipets_engine* e, int R, int logical, size_t lds, RolloutArgs ra, hipStream_t st, bool* persistent, int* capacity = nullptr) {
     ra.lds_bytes = (unsigned)lds;
     KernelRec* k = rollout_instance(e, R, ra);
     if (!k) return 1;
-    HCHECK(decide_launch_form(*k, logical, (unsigned)lds, (int)e->lds_max, e->num_cu, e->md, ra, e->census.as<int>(), e->poll_ticks, st, &e->persistent_ok, persistent));
+    HCHECK(decide_launch_form(*k, logical, (unsigned)lds, (int)e->lds_max, e->num_cu, e->md, ra, e->census.as<int>(), e->poll_ticks, st, &e->persistent_ok, persistent, capacity));
     return 0;
 }
 
@@ -337,7 +337,18 @@ int rollout_impl(hipets_engine* e, const float* actions, const float* s0, int32_
         // table.  Only as many workgroups as are resident at once are launched; a batch with more logical workgroups (cfg4: 435)
         // is served in turns, workgroup b taking b, b + grid, ... every step.
         bool persistent = device && per_step && e->persistent_ok && H > 1;
-        if (persistent && launch_form(e, R, domains * groups, lds, ra, st, &persistent)) return 1;
+        // the resident-heads instance (KSpec::RES) where the launch can be a STRAIGHT persistent one: it is asked for first, and kept only if
+        // all logical workgroups of the call are co-resident in it; the plain instance -- turns, or one launch per step -- otherwise
+        ra.resident_heads = persistent && !g.wide && resident_heads_call(md, R, domains * groups, e->num_cu, H) ? 1 : 0;
+        if (ra.resident_heads) {
+            int capacity = 0;
+            if (launch_form(e, R, domains * groups, lds, ra, st, &persistent, &capacity)) return 1;
+            if (!resident_heads_kept(persistent, capacity, domains * groups)) {
+                ra.resident_heads = 0;
+                persistent = e->persistent_ok;
+            }
+        }
+        if (persistent && !ra.resident_heads && launch_form(e, R, domains * groups, lds, ra, st, &persistent)) return 1;
         if (!persistent) {  // the persistent form starts from s0 itself and writes every row's total at the end
             hipLaunchKernelGGL(init_state_kernel, dim3((unsigned)((B * md.obs_dim + 255) / 256)), dim3(256), 0, st,
                                e->state.as<float>(), e->totals.as<float>(), e->term.as<unsigned char>(), e->s0.as<float>(), (int)B,
@@ -484,7 +495,7 @@ int hipets_kernel_class(hipets_engine* e, int32_t pop, int32_t P, int32_t horizo
     probe.wide_lds = g.wide ? 1 : 0;
     int cls = HIPETS_KERNEL_GENERIC;
     switch (pick_rollout_instance(md, probe, g.R)) {
-        case RolloutInstance::lean: case RolloutInstance::b3: cls = HIPETS_KERNEL_FUSED; break;
+        case RolloutInstance::lean: case RolloutInstance::lean_resident: case RolloutInstance::b3: cls = HIPETS_KERNEL_FUSED; break;
         case RolloutInstance::bf16: cls = HIPETS_KERNEL_BF16; break;
         case RolloutInstance::lean_wide: cls = HIPETS_KERNEL_WIDE; break;
         case RolloutInstance::hidden_static: cls = HIPETS_KERNEL_HIDDEN_STATIC; break;

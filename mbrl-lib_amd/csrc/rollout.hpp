@@ -884,6 +884,21 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
     };
     (void)dma_collect;
 
+    // KSpec::RES: the launch rule (launch.hpp resident_heads_call, rollout.hip) picks this instance for the straight persistent form only.
+    // This wave's op heads of its member -- fixed for the launch -- go into AccVGPRs once, here (the layer table is in LDS since the
+    // prologue's barrier); every step's ops start from them (gemm_f32.hpp ResHead).
+    static_assert(!S::RES || (R == 3 && MinWaves<R, S>::value == 1), "resident op heads: one wave per SIMD (512 registers per lane)");
+    ResHeadStore<S::RES> head_store;  // (empty in every other instance)
+    ResHead* const heads = head_store.get();
+    if constexpr (S::RES) {
+        if (!straight || md.n_layers != kResLayers) {  // (never launched like this; a launch that is, fails loudly instead of computing with another form's heads)
+            if (tid == 0 && ra.error_flag) *ra.error_flag = 1;
+            return;
+        }
+        res_load_heads<R, S>(heads, md, sm.lmeta, member_dom, wave, lane);
+        vmem_drain();
+        res_pin_heads<R, S>(heads);
+    }
     bool one_tile = false;  // this turn serves a one-tile logical workgroup (kRagged; workgroup-uniform)
     for (int q_seq = 0; q_seq < n_seq; ++q_seq) {
         stamp_seq = q_seq;
@@ -932,7 +947,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                     if (one_tile) mlp_layer<1, S>(md, sm.lmeta, l, member, cur, nxt, wave, lane, prof, sm.part);
                     else mlp_layer<R, S>(md, sm.lmeta, l, member, cur, nxt, wave, lane, prof, sm.part);
                 } else {
-                    mlp_layer<R, S>(md, sm.lmeta, l, member, cur, nxt, wave, lane, prof, sm.part);
+                    mlp_layer<R, S>(md, sm.lmeta, l, member, cur, nxt, wave, lane, prof, sm.part, heads);
                 }
                 __syncthreads();
                 prof.mark(8);
@@ -1114,7 +1129,7 @@ __global__ __launch_bounds__(kThreads, (MinWaves<R, S>::value)) void rollout_ker
                 if (one_tile) mlp_output_layer_fused<1, S>(md, sm.lmeta, member, cur, wave, lane, prof, tail, sm.part);
                 else mlp_output_layer_fused<R, S>(md, sm.lmeta, member, cur, wave, lane, prof, tail, sm.part);
             } else {
-                mlp_output_layer_fused<R, S>(md, sm.lmeta, member, cur, wave, lane, prof, tail, sm.part);
+                mlp_output_layer_fused<R, S>(md, sm.lmeta, member, cur, wave, lane, prof, tail, sm.part, heads);
             }
             // straight persistent form: what the two sides of this barrier exchange goes through LDS; the tail's write-through
             // hand-over stores need not have been acknowledged (__syncthreads() would wait for that -- about a microsecond --

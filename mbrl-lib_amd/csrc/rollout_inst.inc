@@ -37,6 +37,8 @@
 #endif
 #define HIPETS_TRY_SHAPE(HC, OC, RW, TM, OB) \
     if (lean_shape_is(md, HC, OC, RW, TM, OB)) return &rec<LeanSpec<HC, OC, RW, TM, OB, HIPETS_LEAN_MODE>>();
+#define HIPETS_TRY_RES_SHAPE(HC, OC, RW, TM, OB) \
+    if (lean_shape_is(md, HC, OC, RW, TM, OB)) return &rec<LeanSpec<HC, OC, RW, TM, OB, HIPETS_LEAN_MODE, 1>>();
 #define HIPETS_TRY_PREC(PREC, HC, OC, RW, TM) \
     if (b3_shape_is(md, HC, OC, RW, TM)) return &rec<KSpec<HIPETS_ACT_SILU, HC, OC, HIPETS_NORM_F64, HIPETS_OBS_NONE, RW, TM, HIPETS_LEAN_MODE, PREC>>();
 #define HIPETS_TRY_B3(HC, OC, RW, TM) HIPETS_TRY_PREC(HIPETS_PREC_BF16X3, HC, OC, RW, TM)
@@ -74,6 +76,10 @@ KernelRec* HIPETS_SPEC_FN(const RolloutInstance pick, const ModelDev& md) {
         HIPETS_B3_SHAPES(HIPETS_TRY_B3)
     } else if (pick == RolloutInstance::bf16) {
         HIPETS_BF16_SHAPES(HIPETS_TRY_BF16)
+#if HIPETS_PART == 1 && HIPETS_R == 3
+    } else if (pick == RolloutInstance::lean_resident) {  // (step-synchronous unit, one wave per SIMD: the only place these instances exist)
+        HIPETS_LEAN_SHAPES(HIPETS_TRY_RES_SHAPE)
+#endif
     } else {
         HIPETS_LEAN_SHAPES(HIPETS_TRY_SHAPE)
     }
@@ -87,6 +93,7 @@ KernelRec* HIPETS_FN()(const ModelDev& md, const RolloutArgs& ra, hipError_t* wh
     *why = hipErrorNotSupported;
     switch (pick) {
         case RolloutInstance::lean:
+        case RolloutInstance::lean_resident:
         case RolloutInstance::lean_wide:
         case RolloutInstance::b3:
         case RolloutInstance::bf16: return (ra.whole_horizon ? HIPETS_FN(_fast) : HIPETS_FN(_exact))(pick, md);

@@ -132,7 +132,9 @@ struct RolloutArgs {
     // tag is the awaited step: self-validating, so no fence, flag or grid barrier is involved (MI355X_MICROARCH.md R2).
     unsigned long long* exchange;  // null: per-step launches
     unsigned tag_base;             // step t's hand-over carries tag tag_base + t + 1 (the engine advances it by H per launch: no clearing)
-    void* layout_pad_unused;       // never read or written: keeps the later fields at their kernarg offsets (profiles/one_launch_path.json)
+    int resident_heads;            // HOST only (launch.hpp resident_heads_call; no kernel reads it): the call is a straight persistent launch -- as
+                                   // many launched as logical workgroups -- and asks for the KSpec::RES instance of its shape
+    int layout_pad_unused[2];      // never read or written: keeps the later fields at their kernarg offsets (profiles/one_launch_path.json)
     int n_logical;                 // persistent form: logical workgroups (member domain x row group); a launched workgroup serves the
                                    // logical ones wg, wg + gridDim.x, ... one after the other within every step (batches larger than the chip)
     int ragged_last_turn;          // persistent form, KSpec::WIDE two-tile instances: when the row tiles the LAST turn of a step would serve
