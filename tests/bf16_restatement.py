@@ -75,14 +75,29 @@ MUTATIONS = ("in_row", "hid_row", "mean_col", "lv_col")
 NUDGES = (-2, -1, 1, 2)
 
 
+def input_rows_of_state_dim(obs_process, d):
+    """The layer-0 input rows state dim `d` feeds after obs preprocessing (oracle/pets_oracle.py obs_halfcheetah: [s1, sin s2, cos s2,
+    s3:], the same width; obs_cartpole_pets: [sin s1, cos s1, s0, s2:], one column more)."""
+    if obs_process == "halfcheetah":
+        return {0: [], 1: [0], 2: [1, 2]}.get(d, [d])
+    if obs_process == "cartpole_pets":
+        return {0: [2], 1: [0, 1]}.get(d, [d + 1])
+    return [d]
+
+
 def edge_case(obs, act, pop, P, H, seed=0, gain=2.0, g_in=16.0, g_lv=8.0, **mkw):
-    """scaled_case, and on top of `gain`: the layer-0 input row of state dim obs - 1 times `g_in`, the output layer's column
-    2 out - 1 (the last log-variance) times `g_lv`.  The last state dim then feeds back into the network at every step, and its own
-    mean and variance -- the last mean column, the last log-variance column -- reach state dim 0, which the reward reads."""
+    """scaled_case, and on top of `gain`: the layer-0 input row(s) state dim obs - 1 feeds after obs preprocessing times `g_in`, the
+    output layer's column 2 out - 1 (the last log-variance) times `g_lv`.  The last state dim then feeds back into the network at every
+    step, and its own mean and variance -- the last mean column, the last log-variance column -- reach state dim 0, which the reward
+    reads.  Learned rewards: columns out - 1 / 2 out - 1 are the REWARD's mean and log-variance; the last state dim's own log-variance
+    column, out + obs - 1, gets `g_lv` too -- both paths into the return are gained."""
     om, actions, s0, perms, eps = scaled_case(obs, act, pop, P, H, seed=seed, gain=gain, **mkw)
     w = [x.clone() for x in om.weights]
-    w[0][:, obs - 1, :] *= g_in
+    for r in input_rows_of_state_dim(om.obs_process, obs - 1):
+        w[0][:, r, :] *= g_in
     w[-1][:, :, 2 * om.out_size - 1] *= g_lv
+    if om.learned_rewards:
+        w[-1][:, :, om.out_size + obs - 1] *= g_lv
     return dataclasses.replace(om, weights=w), actions, s0, perms, eps
 
 
@@ -141,15 +156,16 @@ def reference_rollout(monkeypatch, prec, om, actions, s0, P, acc64=False, nudge=
         return po.rollout(om, actions, s0, P, **kw)
 
 
-def cpu_draws(om, pop, P, H, mode):
-    """oracle kwargs of a (SEED, SID) rollout from the CPU restatements of the in-kernel draws (both modes run three row tiles)."""
+def cpu_draws(om, pop, P, H, mode, row_tiles=3):
+    """oracle kwargs of a (SEED, SID) rollout from the CPU restatements of the in-kernel draws at `row_tiles` row tiles per workgroup
+    (the FAST member schedule is per workgroup; the bf16 / bf16x3 instances run three in both modes)."""
     B, M = pop * P, len(om.active_members)
     kw = dict(eps=torch.from_numpy(device_draws.fast_normals(H, B, om.out_size, SEED, SID)))
     if mode == "device":
         kw["perms"] = torch.stack([torch.from_numpy(feistel_perm.permutation(B, SEED, SID, t).astype(np.int64)) for t in range(H)])
     else:
-        sched = torch.from_numpy(device_draws.member_schedule(H, device_draws.fast_workgroups(B, 3), M, SEED, SID))
-        wg = torch.as_tensor(np.asarray(device_draws.fast_row_workgroup(torch.arange(B), P, 3))).long()
+        sched = torch.from_numpy(device_draws.member_schedule(H, device_draws.fast_workgroups(B, row_tiles), M, SEED, SID))
+        wg = torch.as_tensor(np.asarray(device_draws.fast_row_workgroup(torch.arange(B), P, row_tiles))).long()
         kw["members"] = torch.stack([sched[t].long()[wg] for t in range(H)])
     return kw
 
@@ -161,11 +177,20 @@ def tolerance(prec, ref, D):
 
 
 def threshold_margin(om, trace):
-    """smallest distance of a traced height from the humanoid thresholds 1.0 / 2.0 (inf without that termination function)"""
-    if om.termination != "humanoid":
+    """smallest distance of a traced next state from a threshold of the model's termination function (tests/test_gpu_closed_forms.py
+    threshold_margin lists them): humanoid heights 1.0 / 2.0; cartpole |x| 2.4, |theta| 12 degrees; inverted_pendulum |dim 1| 0.2; hopper
+    height 0.7, |angle| 0.2, |dims 1..| 100.  inf for models without one of these termination functions."""
+    if om.termination not in ("humanoid", "cartpole", "inverted_pendulum", "hopper"):
         return float("inf")
-    z = torch.stack([n[:, 0] for n in trace["next_obs"]])
-    return torch.minimum((z - 1.0).abs(), (z - 2.0).abs()).min().item()
+    n = torch.stack(trace["next_obs"])
+    if om.termination == "humanoid":
+        z = n[..., 0]
+        return torch.minimum((z - 1.0).abs(), (z - 2.0).abs()).min().item()
+    if om.termination == "cartpole":
+        return torch.minimum((n[..., 0].abs() - 2.4).abs(), (n[..., 2].abs() - 12 * 2 * np.pi / 360).abs()).min().item()
+    if om.termination == "inverted_pendulum":
+        return (n[..., 1].abs() - 0.2).abs().min().item()
+    return min((n[..., 0] - 0.7).abs().min().item(), (n[..., 1].abs() - 0.2).abs().min().item(), (n[..., 1:].abs() - 100.0).abs().min().item())
 
 
 def edge_figures(monkeypatch, case, prec, mode, draws=None):
