@@ -112,6 +112,80 @@ struct ResHead {
 __device__ __forceinline__ void res_load(f32x4& dst, const float* const p) { asm volatile("global_load_dwordx4 %0, %1, off" : "=a"(dst) : "v"(p) : "memory"); }
 __device__ __forceinline__ void res_pin(f32x4& v) { asm volatile("" : "+a"(v)); }
 
+// CONDITIONAL K-STEPS (shape-specialised ops with one wave per SIMD, R >= 3: wave_gemm's kStraight).  Whether a k-step of an op runs is
+// a wave-uniform RUN-TIME fact in two places -- the last chunk holds 1..4 real k-steps, the input layer has 1.. chunks -- and written as
+// C++ control flow around the asm MFMAs it costs what the k loop otherwise avoids: where the arms begin and meet, the register
+// allocator copies EVERY accumulator of the wave (clumps of ~20 v_mov_b64 between two MFMAs), and every arm must end in a pipe drain
+// so that those copies read finished results.  Here the choice stays out of the compiler's sight: one k-step of up to NC column tiles x
+// R row tiles + NE extra units is ONE asm statement that jumps over its own MFMAs when n <= S (n in an SGPR, S the k-step's number).
+// The compiler sees straight-line code with the accumulators tied in place: no phis, no copies, no drains per arm.  The k-step's s_nop 1
+// guard (hazard (1) of wave_gemm) sits inside the statement, behind the branch.  An asm statement takes at most 30 operands, an
+// accumulator ("+v") counts twice: the wave's share goes through in as few statements as that allows (kstep_if in wave_gemm).
+// WC: the register file of the weight operands, "v" or "a" (resident heads).
+#define HIPETS_KT_MF(C, B, A) "v_mfma_f32_16x16x4_f32 %[" #C "], %[" #B "], %[" #A "], %[" #C "]\n\t"
+#define HIPETS_KT_COL3(ct) HIPETS_KT_MF(c##ct##0, b##ct, a0) HIPETS_KT_MF(c##ct##1, b##ct, a1) HIPETS_KT_MF(c##ct##2, b##ct, a2)
+#define HIPETS_KT_COL4(ct) HIPETS_KT_COL3(ct) HIPETS_KT_MF(c##ct##3, b##ct, a3)
+#define HIPETS_KT_EX(e) HIPETS_KT_MF(x##e, bx##e, ax##e)
+#define HIPETS_KT_ACC3(ct) [c##ct##0] "+v"(*c[ct][0]), [c##ct##1] "+v"(*c[ct][1]), [c##ct##2] "+v"(*c[ct][2])
+#define HIPETS_KT_ACC4(ct) HIPETS_KT_ACC3(ct), [c##ct##3] "+v"(*c[ct][3])
+#define HIPETS_KT_XACC(e) [x##e] "+v"(*x[e])
+#define HIPETS_KT_A3 [a0] "v"(a[0]), [a1] "v"(a[1]), [a2] "v"(a[2])
+#define HIPETS_KT_A4 HIPETS_KT_A3, [a3] "v"(a[3])
+#define HIPETS_KT_B(WC, ct) [b##ct] WC(b[ct])
+#define HIPETS_KT_XIN(WC, e) [bx##e] WC(bx[e]), [ax##e] "v"(ax[e])
+#define HIPETS_KT_ASM(BODY, OUTS, INS)                                                                                        \
+    asm volatile("s_cmp_le_i32 %[n], %[s]\n\ts_cbranch_scc1 .Lhipets_kt%=\n\ts_nop 1\n\t" BODY ".Lhipets_kt%=:" \
+                 : OUTS : INS, [n] "s"(n), [s] "n"(S) : "scc")
+#define HIPETS_KT_COMMA ,
+#define HIPETS_KT_SHAPES(WC)                                                                                                                        \
+    if constexpr (R == 3 && NC == 3 && NE == 1)                                                                                                     \
+        HIPETS_KT_ASM(HIPETS_KT_COL3(0) HIPETS_KT_COL3(1) HIPETS_KT_COL3(2) HIPETS_KT_EX(0),                                                        \
+                      HIPETS_KT_ACC3(0) HIPETS_KT_COMMA HIPETS_KT_ACC3(1) HIPETS_KT_COMMA HIPETS_KT_ACC3(2) HIPETS_KT_COMMA HIPETS_KT_XACC(0),      \
+                      HIPETS_KT_B(WC, 0) HIPETS_KT_COMMA HIPETS_KT_B(WC, 1) HIPETS_KT_COMMA HIPETS_KT_B(WC, 2) HIPETS_KT_COMMA HIPETS_KT_A3         \
+                          HIPETS_KT_COMMA HIPETS_KT_XIN(WC, 0));                                                                                    \
+    else if constexpr (R == 3 && NC == 3 && NE == 0)                                                                                                \
+        HIPETS_KT_ASM(HIPETS_KT_COL3(0) HIPETS_KT_COL3(1) HIPETS_KT_COL3(2),                                                                        \
+                      HIPETS_KT_ACC3(0) HIPETS_KT_COMMA HIPETS_KT_ACC3(1) HIPETS_KT_COMMA HIPETS_KT_ACC3(2),                                        \
+                      HIPETS_KT_B(WC, 0) HIPETS_KT_COMMA HIPETS_KT_B(WC, 1) HIPETS_KT_COMMA HIPETS_KT_B(WC, 2) HIPETS_KT_COMMA HIPETS_KT_A3);       \
+    else if constexpr (R == 3 && NC == 1 && NE == 1)                                                                                                \
+        HIPETS_KT_ASM(HIPETS_KT_COL3(0) HIPETS_KT_EX(0), HIPETS_KT_ACC3(0) HIPETS_KT_COMMA HIPETS_KT_XACC(0),                                       \
+                      HIPETS_KT_B(WC, 0) HIPETS_KT_COMMA HIPETS_KT_A3 HIPETS_KT_COMMA HIPETS_KT_XIN(WC, 0));                                        \
+    else if constexpr (R == 3 && NC == 1 && NE == 2)                                                                                                \
+        HIPETS_KT_ASM(HIPETS_KT_COL3(0) HIPETS_KT_EX(0) HIPETS_KT_EX(1), HIPETS_KT_ACC3(0) HIPETS_KT_COMMA HIPETS_KT_XACC(0) HIPETS_KT_COMMA HIPETS_KT_XACC(1), \
+                      HIPETS_KT_B(WC, 0) HIPETS_KT_COMMA HIPETS_KT_A3 HIPETS_KT_COMMA HIPETS_KT_XIN(WC, 0) HIPETS_KT_COMMA HIPETS_KT_XIN(WC, 1));   \
+    else if constexpr (R == 4 && NC == 2 && NE == 0)                                                                                                \
+        HIPETS_KT_ASM(HIPETS_KT_COL4(0) HIPETS_KT_COL4(1), HIPETS_KT_ACC4(0) HIPETS_KT_COMMA HIPETS_KT_ACC4(1),                                     \
+                      HIPETS_KT_B(WC, 0) HIPETS_KT_COMMA HIPETS_KT_B(WC, 1) HIPETS_KT_COMMA HIPETS_KT_A4);                                          \
+    else if constexpr (R == 4 && NC == 1 && NE == 0)                                                                                                \
+        HIPETS_KT_ASM(HIPETS_KT_COL4(0), HIPETS_KT_ACC4(0), HIPETS_KT_B(WC, 0) HIPETS_KT_COMMA HIPETS_KT_A4);                                       \
+    else if constexpr (R == 4 && NC == 1 && NE == 1)                                                                                                \
+        HIPETS_KT_ASM(HIPETS_KT_COL4(0) HIPETS_KT_EX(0), HIPETS_KT_ACC4(0) HIPETS_KT_COMMA HIPETS_KT_XACC(0),                                       \
+                      HIPETS_KT_B(WC, 0) HIPETS_KT_COMMA HIPETS_KT_A4 HIPETS_KT_COMMA HIPETS_KT_XIN(WC, 0));                                        \
+    else if constexpr (R == 4 && NC == 1 && NE == 2)                                                                                                \
+        HIPETS_KT_ASM(HIPETS_KT_COL4(0) HIPETS_KT_EX(0) HIPETS_KT_EX(1), HIPETS_KT_ACC4(0) HIPETS_KT_COMMA HIPETS_KT_XACC(0) HIPETS_KT_COMMA HIPETS_KT_XACC(1), \
+                      HIPETS_KT_B(WC, 0) HIPETS_KT_COMMA HIPETS_KT_A4 HIPETS_KT_COMMA HIPETS_KT_XIN(WC, 0) HIPETS_KT_COMMA HIPETS_KT_XIN(WC, 1));   \
+    else if constexpr (NC == 0 && NE == 1)                                                                                                          \
+        HIPETS_KT_ASM(HIPETS_KT_EX(0), HIPETS_KT_XACC(0), HIPETS_KT_XIN(WC, 0));                                                                    \
+    else if constexpr (NC == 0 && NE == 2)                                                                                                          \
+        HIPETS_KT_ASM(HIPETS_KT_EX(0) HIPETS_KT_EX(1), HIPETS_KT_XACC(0) HIPETS_KT_COMMA HIPETS_KT_XACC(1),                                         \
+                      HIPETS_KT_XIN(WC, 0) HIPETS_KT_COMMA HIPETS_KT_XIN(WC, 1));                                                                   \
+    else if constexpr (NC == 0 && NE == 3)                                                                                                          \
+        HIPETS_KT_ASM(HIPETS_KT_EX(0) HIPETS_KT_EX(1) HIPETS_KT_EX(2), HIPETS_KT_XACC(0) HIPETS_KT_COMMA HIPETS_KT_XACC(1) HIPETS_KT_COMMA HIPETS_KT_XACC(2), \
+                      HIPETS_KT_XIN(WC, 0) HIPETS_KT_COMMA HIPETS_KT_XIN(WC, 1) HIPETS_KT_COMMA HIPETS_KT_XIN(WC, 2));                              \
+    else                                                                                                                                            \
+        static_assert(R < 0, "conditional k-step: a (row tiles, column tiles, extras) share the shape tables do not produce")
+// c[ct][r] / x[e]: the accumulators of the k-step's parity; b / bx, a / ax: element S of the weight and activation fragments
+template <int R, int NC, int NE, int S, bool WA>
+__device__ __forceinline__ void mfma_kstep_if(const int n, f32x4* const (&c)[NC > 0 ? NC : 1][R], f32x4* const (&x)[NE > 0 ? NE : 1],
+                                              const float (&b)[NC > 0 ? NC : 1], const float (&a)[R], const float (&bx)[NE > 0 ? NE : 1],
+                                              const float (&ax)[NE > 0 ? NE : 1]) {
+    if constexpr (WA) {
+        HIPETS_KT_SHAPES("a");
+    } else {
+        HIPETS_KT_SHAPES("v");
+    }
+}
+
 struct NoTail {};  // wave_gemm's TL: the ordinary epilogue (activation, store as the next op's LDS image)
 // A fused tail = four stages over the accumulators (units) a wave finished: prep(slot, c, r) for EVERY unit of a group first -- it
 // only loads (LDS) what the unit will need into its slot, so the round trips of all units overlap --, then draw(slot a, slot b, c_a,
@@ -202,6 +276,9 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
     const int ld = LD > 0 ? LD : ld_rt;
     const int ldi = ldi_rt > 0 ? ldi_rt : ld;  // row stride of `in` when it differs from the output's (KSpec::WIDE: the model-input image)
     const int KC = KCS > 0 ? KCS : KC_rt;
+    // one wave per SIMD, shape-specialised, no k-split: the ops whose run-time choices are conditional k-steps (mfma_kstep_if), not branches
+    constexpr bool kStraight = LD > 0 && MinWavesOf<R>::value == 1 && KS == 0;
+    const int tail_sgpr = kStraight ? __builtin_amdgcn_readfirstlane(tail_steps) : tail_steps;
 
     const int exc[kMaxExtras] = {ex.c0, ex.c1, ex.c2, ex.c3};
     const int exr[kMaxExtras] = {ex.r0, ex.r1, ex.r2, ex.r3};
@@ -379,8 +456,63 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
             for (int e = 0; e < EX; ++e) asm volatile("" : "+v"(accxo[e]));
         }
     };
+    // k-step S of `f` if n > S (mfma_kstep_if above; n wave-uniform): the wave's units in as few statements as the operand limit allows --
+    // one, but for the 13 units of an R = 4 wave (two column tiles, then the third with the extra unit).  WA: weights from a resident head.
+    auto kstep_if = [&](const auto& wb, const auto& wbx, const GemmFrags<R, CT, EX>& f, auto sc, auto wa, const int n) __attribute__((always_inline)) {
+        constexpr int S = decltype(sc)::value;
+        constexpr bool WA = decltype(wa)::value;
+        constexpr bool odd = (S & 1) != 0;
+        float ea[R] = {}, eax[EXn] = {}, ebx[EXn] = {};
+        f32x4* px[EXn] = {};
+#pragma unroll
+        for (int r = 0; r < (CT > 0 ? R : 0); ++r) ea[r] = f.a[r][S];
+#pragma unroll
+        for (int e = 0; e < EX; ++e) {
+            eax[e] = f.ax[e][S];
+            ebx[e] = wbx[e][S];
+            px[e] = (kSplitAll && odd) ? &accxo[e] : ((kSplit && odd) ? &acc_odd : &accx[e]);
+        }
+        if constexpr (kSplit && CT > 0) {  // (not produced by the shape tables: a lone strided tile at R = 1 only)
+            static_assert(R < 0, "conditional k-step: one strided unit");
+        } else if constexpr (2 * (CT * R + EX) + CT + (CT > 0 ? R : 0) + 2 * EX + 1 <= 30) {
+            f32x4* pc[CTn][R] = {};
+            float eb[CTn] = {};
+#pragma unroll
+            for (int ct = 0; ct < CT; ++ct) {
+                eb[ct] = wb[ct][S];
+#pragma unroll
+                for (int r = 0; r < R; ++r) pc[ct][r] = (kSplitAll && odd) ? &acco[ct][r] : &acc[ct][r];
+            }
+            mfma_kstep_if<R, CT, EX, S, WA>(n, pc, px, eb, ea, ebx, eax);
+        } else {
+            static_assert(CT == 3, "two statements: the widest share is three column tiles and the extra units");
+            f32x4* p01[2][R];
+            f32x4* p2[1][R];
+            float e01[2], e2[1];
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+                e01[ct] = wb[ct][S];
+#pragma unroll
+                for (int r = 0; r < R; ++r) p01[ct][r] = (kSplitAll && odd) ? &acco[ct][r] : &acc[ct][r];
+            }
+            e2[0] = wb[2][S];
+#pragma unroll
+            for (int r = 0; r < R; ++r) p2[0][r] = (kSplitAll && odd) ? &acco[2][r] : &acc[2][r];
+            f32x4* pnone[1] = {nullptr};
+            const float enone[1] = {0.f};
+            mfma_kstep_if<R, 2, 0, S, WA>(n, p01, pnone, e01, ea, enone, enone);
+            mfma_kstep_if<R, 1, EX, S, WA>(n, p2, px, e2, ea, ebx, eax);
+        }
+    };
     // last chunk: only the k-steps that hold real (non-padding) weights, e.g. 2 of 4 for K = 200
     auto compute_tail = [&](const GemmFrags<R, CT, EX>& f) __attribute__((always_inline)) {
+        if constexpr (kStraight) {  // k-step 0 always runs; 1..3 skip themselves inside their asm statement: nothing here for the compiler to merge
+            kstep(f, 0);
+            kstep_if(f.b, f.bx, f, std::integral_constant<int, 1>{}, std::false_type{}, tail_sgpr);
+            kstep_if(f.b, f.bx, f, std::integral_constant<int, 2>{}, std::false_type{}, tail_sgpr);
+            kstep_if(f.b, f.bx, f, std::integral_constant<int, 3>{}, std::false_type{}, tail_sgpr);
+            return;
+        }
         switch (tail_steps) {
             case 1: kstep(f, 0); drain_all(); break;
             case 2: kstep(f, 0); kstep(f, 1); drain_all(); break;
@@ -427,36 +559,43 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
     // accumulators start at the bias (C input of the first MFMA) instead of zero: no add in the epilogue.  Initialised AFTER
     // chunk 0's fragment loads were issued: the bias loads are older, so waiting for them leaves the fragments in flight
     // (initialising first serialised two L2 round trips per layer: ~1.2k cycles of "set-up" per layer in the phase profile)
-    if constexpr (!RES) {
-#pragma unroll
-    for (int ct = 0; ct < CTn; ++ct)
-#pragma unroll
-        for (int r = 0; r < R; ++r) acc[ct][r] = CT > 0 ? bv[ct] : f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int e = 0; e < EXn; ++e) accx[e] = EX > 0 ? bvx[e] : f32x4{0.f, 0.f, 0.f, 0.f};
-    }
     // Pin every accumulator's initial value HERE: to the compiler an asm MFMA is an ordinary reader of its C operand, so it may
     // sink the (VALU) initialisation -- a copy of the bias, the zeros of the odd-k-step accumulators -- down to just in front of
     // the first MFMA that uses the register, inside a k-step, behind that k-step's s_nop: a VALU write followed at once by an MFMA
     // reading it as SrcC (hazard (1) below; found in the ISA of the cfg4 instances by __graft_entry__.scan_isa_hazards (tests/test_abi.py), where it returned
     // wrong sums).  An empty asm that "modifies" the register makes the value opaque: it must be complete before this point.
     auto pin = [](f32x4& v) __attribute__((always_inline)) { asm volatile("" : "+v"(v)); };
-    if constexpr (!RES) {
+    // ... and the same with the number of the forked body it stands in (kForked below) as an asm comment: identical statements in every
+    // body are hoisted back in front of the fork, and each body then begins by copying the accumulators it was to initialise itself
+    auto pin_in = [](f32x4& v, auto body) __attribute__((always_inline)) {
+        if constexpr (decltype(body)::value == 0) asm volatile("" : "+v"(v));
+        else asm volatile("; body %1" : "+v"(v) : "n"(decltype(body)::value));
+    };
+    auto acc_from_bias = [&](auto body) __attribute__((always_inline)) {
 #pragma unroll
-    for (int ct = 0; ct < CTn; ++ct)
+        for (int ct = 0; ct < CTn; ++ct)
 #pragma unroll
-        for (int r = 0; r < R; ++r) {
-            if constexpr (CT > 0) pin(acc[ct][r]);
-            if constexpr (CT > 0 && kSplitAll) pin(acco[ct][r]);
+            for (int r = 0; r < R; ++r) acc[ct][r] = CT > 0 ? bv[ct] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int e = 0; e < EXn; ++e) accx[e] = EX > 0 ? bvx[e] : f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int ct = 0; ct < CTn; ++ct)
+#pragma unroll
+            for (int r = 0; r < R; ++r) {
+                if constexpr (CT > 0) pin_in(acc[ct][r], body);
+                if constexpr (CT > 0 && kSplitAll) pin_in(acco[ct][r], body);
+            }
+#pragma unroll
+        for (int e = 0; e < EXn; ++e) {
+            if constexpr (EX > 0) pin_in(accx[e], body);
+            if constexpr (EX > 0 && kSplitAll) pin_in(accxo[e], body);
         }
-#pragma unroll
-    for (int e = 0; e < EXn; ++e) {
-        if constexpr (EX > 0) pin(accx[e]);
-        if constexpr (EX > 0 && kSplitAll) pin(accxo[e]);
-    }
-    if constexpr (kSplit) pin(acc_odd);
-    prof.mark(14);
-    }
+        if constexpr (kSplit) pin_in(acc_odd, body);
+        prof.mark(14);
+    };
+    // (an op that forks into whole bodies -- kStraight with a run-time chunk count, below -- initialises inside each body)
+    constexpr bool kForked = kStraight && KCS <= 0;
+    if constexpr (!RES && !kForked) acc_from_bias(std::integral_constant<int, 0>{});
     f32x4 a_last = f32x4{0.f, 0.f, 0.f, 0.f};
     if constexpr (KSI) {  // this lane's fragment of the input's last chunk: the activation of the four partial sums, in ONE fixed order
         static_assert(ACT == HIPETS_ACT_SILU, "k-split instances are SiLU instances");
@@ -501,20 +640,20 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
 #pragma unroll
             for (int e = 0; e < EXn; ++e) accx[e] = EX > 0 ? bx[e] : f32x4{0.f, 0.f, 0.f, 0.f};
         };
-        auto pin_acc = [&]() __attribute__((always_inline)) {
+        auto pin_acc = [&](auto body) __attribute__((always_inline)) {
 #pragma unroll
             for (int ct = 0; ct < CTn; ++ct)
 #pragma unroll
                 for (int r = 0; r < R; ++r) {
-                    if constexpr (CT > 0) pin(acc[ct][r]);
-                    if constexpr (CT > 0 && kSplitAll) pin(acco[ct][r]);
+                    if constexpr (CT > 0) pin_in(acc[ct][r], body);
+                    if constexpr (CT > 0 && kSplitAll) pin_in(acco[ct][r], body);
                 }
 #pragma unroll
             for (int e = 0; e < EXn; ++e) {
-                if constexpr (EX > 0) pin(accx[e]);
-                if constexpr (EX > 0 && kSplitAll) pin(accxo[e]);
+                if constexpr (EX > 0) pin_in(accx[e], body);
+                if constexpr (EX > 0 && kSplitAll) pin_in(accxo[e], body);
             }
-            if constexpr (kSplit) pin(acc_odd);
+            if constexpr (kSplit) pin_in(acc_odd, body);
         };
         // Resident head (RES): the accumulators start from the resident bias (v_accvgpr_read: VALU writes, pinned ahead of the k-step's
         // s_nop like every initial value), then chunk 0 with the weight operand in AccVGPRs; chunk 1's fragment loads ride behind its
@@ -534,76 +673,91 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
                 else mfma16x16x4_ra(h.bx[e][s], f.ax[e][s], accx[e]);
             }
         };
-        auto head = [&](const ResHead& h) __attribute__((always_inline)) {
+        auto head_init = [&](const ResHead& h, auto body) __attribute__((always_inline)) {
             acc_init(h.bv, h.bvx);
-            pin_acc();
+            pin_acc(body);
             prof.mark(14);
-            auto kstep_h = [&](const int s) __attribute__((always_inline)) {
+        };
+        auto head_full = [&](const ResHead& h) __attribute__((always_inline)) {  // chunk 0, chunk 1's fragments on their way into f1
+#pragma unroll
+            for (int ks_ = 0; ks_ < 4; ++ks_) {
                 asm volatile("s_nop 1");
 #pragma unroll
-                for (int u = 0; u < kNU; ++u) mfma_unit_h(h, f0, s, u);
-            };
-            if (KC >= 2) {
-#pragma unroll
-                for (int ks_ = 0; ks_ < 4; ++ks_) {
-                    asm volatile("s_nop 1");
-#pragma unroll
-                    for (int u = 0; u < kNU; ++u) {
-                        mfma_unit_h(h, f0, ks_, u);
-                        loads_behind(f1, 1, ks_ * kNU + u + 1);
-                    }
-                }
-                if constexpr (RES == 3 || KCS <= 0) drain_all();  // (an arm of the layer switch / of the run-time chunk count; straight-line code otherwise)
-            } else {
-                switch (tail_steps) {
-                    case 1: kstep_h(0); drain_all(); break;
-                    case 2: kstep_h(0); kstep_h(1); drain_all(); break;
-                    case 3: kstep_h(0); kstep_h(1); kstep_h(2); drain_all(); break;
-                    default: kstep_h(0); kstep_h(1); kstep_h(2); kstep_h(3); drain_all(); break;
+                for (int u = 0; u < kNU; ++u) {
+                    mfma_unit_h(h, f0, ks_, u);
+                    loads_behind(f1, 1, ks_ * kNU + u + 1);
                 }
             }
         };
-        // chunks 1 .. KC - 1 behind a head: the two-set loop with the sets' roles swapped (chunk 1 is in f1)
-        auto rest = [&]() __attribute__((always_inline)) {
-            if (KC < 2) return;
-            int kk = 1;
-            if constexpr (KCS > 0) {
-#pragma unroll
-                for (int k2 = 1; k2 + 2 < KCS; k2 += 2) {
-                    compute_il(f1, f0, k2 + 1);
-                    compute_il(f0, f1, k2 + 2);
-                }
-                constexpr int kEndR = KCS >= 3 ? 1 + ((KCS - 2) / 2) * 2 : 1;  // where that loop leaves k2: the largest odd number <= KCS - 1
-                if constexpr (kEndR + 1 < KCS) {
-                    compute_il(f1, f0, kEndR + 1);
-                    compute_tail(f0);
-                } else {
-                    compute_tail(f1);
-                }
+        if constexpr (KCS > 0) {
+            // ops fed by a hidden layer: straight-line code behind the head (the only choice left is WHICH head: the arms of the layer switch)
+            static_assert(KCS >= 2, "a hidden width of more than one chunk");
+            auto head = [&](const ResHead& h) __attribute__((always_inline)) {
+                head_init(h, std::integral_constant<int, 0>{});
+                head_full(h);
+                if constexpr (RES == 3) drain_all();  // (an arm of the layer switch)
+            };
+            if constexpr (RES == 1) {
+                head(rh[0]);
             } else {
+                switch (rsel) {
+                    case 0: head(rh[0]); break;
+                    case 1: head(rh[1]); break;
+                    default: head(rh[2]); break;
+                }
+            }
+            // chunks 1 .. KCS - 1: the two-set loop with the sets' roles swapped (chunk 1 is in f1)
+#pragma unroll
+            for (int k2 = 1; k2 + 2 < KCS; k2 += 2) {
+                compute_il(f1, f0, k2 + 1);
+                compute_il(f0, f1, k2 + 2);
+            }
+            constexpr int kEndR = KCS >= 3 ? 1 + ((KCS - 2) / 2) * 2 : 1;  // where that loop leaves k2: the largest odd number <= KCS - 1
+            if constexpr (kEndR + 1 < KCS) {
+                compute_il(f1, f0, kEndR + 1);
+                compute_tail(f0);
+            } else {
+                compute_tail(f1);
+            }
+        } else {
+            // The input layer (run-time chunk count): the op forks ONCE, before its first MFMA, into a whole body per case -- one chunk /
+            // an even / an odd number of them -- and the bodies meet in front of the epilogue.  Inside a body the fragment set the tail
+            // reads is fixed, so nothing merges between MFMAs (forking behind the loop, "one chunk left or two", cost a copy of every
+            // accumulator where the arms began and met, and a drain each).  Every body ends drained: the epilogue's own wait is dropped.
+            // The accumulators are initialised INSIDE each body (pin_in): initialised in front of the fork, every body began by copying them.
+            static_assert(RES == 1, "one head");
+            const ResHead& h = rh[0];
+            if (KC < 2) {  // the head IS the tail chunk
+                head_init(h, std::integral_constant<int, 1>{});
+                asm volatile("s_nop 1");
+#pragma unroll
+                for (int u = 0; u < kNU; ++u) mfma_unit_h(h, f0, 0, u);
+                kstep_if(h.b, h.bx, f0, std::integral_constant<int, 1>{}, std::true_type{}, tail_sgpr);
+                kstep_if(h.b, h.bx, f0, std::integral_constant<int, 2>{}, std::true_type{}, tail_sgpr);
+                kstep_if(h.b, h.bx, f0, std::integral_constant<int, 3>{}, std::true_type{}, tail_sgpr);
+                drain_all();
+            } else if ((KC & 1) == 0) {  // chunks 1 .. KC - 1 are an odd number: pairs, then the tail from f1
+                head_init(h, std::integral_constant<int, 2>{});
+                head_full(h);
+                for (int kk = 1; kk + 2 < KC; kk += 2) {
+                    compute_il(f1, f0, kk + 1);
+                    compute_il(f0, f1, kk + 2);
+                }
+                compute_tail(f1);
+                drain_all();
+            } else {  // an even number: pairs, one more full chunk, the tail from f0
+                head_init(h, std::integral_constant<int, 3>{});
+                head_full(h);
+                int kk = 1;
                 for (; kk + 2 < KC; kk += 2) {
                     compute_il(f1, f0, kk + 1);
                     compute_il(f0, f1, kk + 2);
                 }
-                if (kk > 1) drain_all();
-                if (kk + 1 < KC) {
-                    compute_il(f1, f0, kk + 1);
-                    compute_tail(f0);
-                } else {
-                    compute_tail(f1);
-                }
-            }
-        };
-        if constexpr (RES == 1) {
-            head(rh[0]);
-        } else {
-            switch (rsel) {
-                case 0: head(rh[0]); break;
-                case 1: head(rh[1]); break;
-                default: head(rh[2]); break;
+                compute_il(f1, f0, kk + 1);
+                compute_tail(f0);
+                drain_all();
             }
         }
-        rest();
     } else if constexpr (KCS > 0 && !kTriple) {
         constexpr int kEnd = KCS >= 2 ? ((KCS - 1) / 2) * 2 : 0;  // the loop below leaves kk at the smallest even number >= KCS - 2
 #pragma unroll
@@ -673,6 +827,28 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
             drain_all();
             last_frag(f2);
             compute_tail(f2);
+        }
+    } else if constexpr (kStraight) {
+        // The input layer (run-time chunk count): forked ONCE on the parity of the count, before the first MFMA, into two whole bodies
+        // in which the tail's fragment set is fixed (see the resident twin of this code above); both initialise their accumulators themselves and end drained
+        if (KC & 1) {
+            acc_from_bias(std::integral_constant<int, 1>{});
+            int kk = 0;
+            for (; kk + 2 < KC; kk += 2) {
+                compute_il(f0, f1, kk + 1);
+                compute_il(f1, f0, kk + 2);
+            }
+            compute_tail(f0);
+            drain_all();
+        } else {
+            acc_from_bias(std::integral_constant<int, 2>{});
+            compute_il(f0, f1, 1);
+            for (int kk = 1; kk + 2 < KC; kk += 2) {
+                compute_il(f1, f0, kk + 1);
+                compute_il(f0, f1, kk + 2);
+            }
+            compute_tail(f1);
+            drain_all();
         }
     } else {
         int kk = 0;
@@ -749,7 +925,7 @@ __device__ __forceinline__ void wave_gemm(const float* __restrict__ in, float* _
 #pragma unroll
         for (int e = 0; e < EX; ++e) accx[e] += accxo[e];
     }
-    mfma_drain();
+    if constexpr (!kForked) mfma_drain();  // (the bodies of a run-time chunk count end drained)
     __builtin_amdgcn_sched_barrier(0);
     prof.mark(11);
     if constexpr (!std::is_same<TL, NoTail>::value) {
