@@ -667,7 +667,8 @@ int hipets_plan_planet_icem_batched(hipets_engine* e, const hipets_icem_params* 
  * decay (model_trainer.py:63-68).  Parameters and Adam state are caller-owned DEVICE f32 tensors in torch's layout, updated in
  * place: weights[l] [E, d_l, d_{l+1}], biases[l] [E, 1, d_{l+1}] with d_0 = in_dim, d_1 .. d_{n_layers-1} = hid and
  * d_{n_layers} = 2 out_dim (mean | raw logvar columns).  Limits: E <= 16, 2 <= n_layers <= 8, in_dim <= 512, hid <= 256,
- * out_dim <= 512, max_batch <= 256 (the HIPETS_TRAIN_MAX_* limits); anything else fails with HIPETS_ERR_INVALID_ARGUMENT.  */
+ * out_dim <= 512, max_batch <= 256 (the HIPETS_TRAIN_MAX_* limits; max_batch <= HIPETS_TRAIN_SPLIT_MAX_BATCH = 1024 under
+ * hipets_set_train_kernel(HIPETS_TRAIN_KERNEL_SPLIT), below); anything else fails with HIPETS_ERR_INVALID_ARGUMENT.              */
 #define HIPETS_TRAIN_MAX_MEMBERS 16
 #define HIPETS_TRAIN_MAX_HID 256
 #define HIPETS_TRAIN_MAX_IN 512
@@ -691,7 +692,8 @@ typedef struct {
     const float* min_logvar; /* DEVICE [out_dim] (constant: learn_logvar_bounds = False)                              */
     const float* max_logvar;
     double lr, beta1, beta2, eps, weight_decay; /* param_groups[0] of the optimizer                                   */
-    int32_t steps_per_launch; /* 0 = the library's choice (launches of at most ~50 ms); else at most this many steps  */
+    int32_t steps_per_launch; /* 0 = the library's choice (launches of at most ~50 ms); else at most this many steps;
+                                 not read under HIPETS_TRAIN_KERNEL_SPLIT, where every step is its own launches          */
 } hipets_train_desc;
 /* n_steps consecutive minibatch steps (Model.update, model.py:129-167): step s runs member e on dataset rows
  * idx[s, e, 0 .. rows[s]) of x DEVICE f32 [n_rows, in_dim] (model inputs, normalised) and y DEVICE f32 [n_rows, out_dim]
@@ -735,6 +737,22 @@ int hipets_train_steps_loss(hipets_engine* e, const hipets_train_desc* d, const 
  * means), under HIPETS_TRAIN_LOSS_NLL 2 out_dim wide (the first out_dim are).  The score is the same squared error.          */
 int hipets_train_eval_loss(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows,
                            const int32_t* order, float* score, float* row_score, void* stream, int32_t loss_kind);
+
+/* Which kernels hipets_train_steps / hipets_train_steps_loss run: engine state, like hipets_set_plan_mode; host only (additive entry
+ * point, HIPETS_ABI_VERSION stays).
+ *   HIPETS_TRAIN_KERNEL_MEMBER (the default)  one workgroup per member runs a chunk of steps in one launch; max_batch <= HIPETS_TRAIN_MAX_BATCH.
+ *   HIPETS_TRAIN_KERNEL_SPLIT                 the row-split step: three stream-ordered launches per minibatch step -- 32-row blocks run
+ *     forward, loss and the dA chain; 64 x 64 blocks of every W form dW over all rows with Adam fused; one launch sums the loss and
+ *     grad_sq partials in a fixed order -- so a member's step spreads over many CUs; max_batch <= HIPETS_TRAIN_SPLIT_MAX_BATCH.  The
+ *     semantics are hipets_train_steps_loss' in full (both loss kinds, per-member bounds, grad_scale, ragged rows, outside indices);
+ *     the sums run in another order than the member kernel's, so the two agree to rounding, not bit for bit.  Results are deterministic
+ *     and do not depend on how a run is cut into calls.  steps_per_launch has no meaning here and is ignored (every step is its own
+ *     launches; the step's Adam scalars travel as launch arguments).
+ * hipets_train_eval / hipets_train_eval_loss are the same under both.  An unknown kind fails with HIPETS_ERR_INVALID_ARGUMENT.          */
+#define HIPETS_TRAIN_KERNEL_MEMBER 0
+#define HIPETS_TRAIN_KERNEL_SPLIT 1
+#define HIPETS_TRAIN_SPLIT_MAX_BATCH 1024
+int hipets_set_train_kernel(hipets_engine* e, int32_t kind);
 
 /* ---- MBPO model rollouts: the SAC Gaussian actor and the compacting populate step (mbrl/algorithms/mbpo.py:31-63) ----
  * Additive entry points: scalars and pointers only, no struct, HIPETS_ABI_VERSION stays.  Needs no dynamics model.

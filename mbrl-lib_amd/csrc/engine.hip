@@ -118,7 +118,7 @@ void hipets_destroy(hipets_engine* e) {
     comm_release(e);
     for (DevBuf* b : {&e->w3pack, &e->wpack, &e->bpack, &e->layer_meta, &e->norm_mean, &e->norm_std, &e->min_lv, &e->max_lv, &e->no_delta, &e->members,
                       &e->s0, &e->state, &e->totals, &e->term, &e->exchange, &e->step_keys, &e->plan_keys, &e->mu, &e->disp, &e->population, &e->values,
-                      &e->best_value, &e->best_solution, &e->past_action, &e->kept, &e->elite_idx, &e->keep_idx, &e->planet_w, &e->planet_b, &e->planet_member, &e->planet_ops, &e->shard_values, &e->gathered, &e->census, &e->train_slab, &e->train_partial,
+                      &e->best_value, &e->best_solution, &e->past_action, &e->kept, &e->elite_idx, &e->keep_idx, &e->planet_w, &e->planet_b, &e->planet_member, &e->planet_ops, &e->shard_values, &e->gathered, &e->census, &e->train_slab, &e->train_partial, &e->train_split_part,
                       &e->policy.w, &e->policy.b, &e->compact_counts, &e->sac_ws, &e->sac_one, &e->critic.w, &e->critic.b,
                       &e->ensemble.w, &e->ensemble.b, &e->ensemble.norm, &e->ensemble.lv, &e->ensemble.cols})
         b->release();
@@ -137,6 +137,13 @@ int hipets_set_plan_mode(hipets_engine* e, int32_t mode) {
     if (!e) return fail("null engine");
     if (mode != HIPETS_MODE_FAST && mode != HIPETS_MODE_DEVICE) return fail("plan mode must be HIPETS_MODE_FAST or HIPETS_MODE_DEVICE");
     e->plan_mode = mode;
+    return 0;
+}
+
+int hipets_set_train_kernel(hipets_engine* e, int32_t kind) {
+    if (!e) return fail("null engine");
+    if (kind != HIPETS_TRAIN_KERNEL_MEMBER && kind != HIPETS_TRAIN_KERNEL_SPLIT) return fail("train kernel must be HIPETS_TRAIN_KERNEL_MEMBER or HIPETS_TRAIN_KERNEL_SPLIT");
+    e->train_kernel = kind;
     return 0;
 }
 

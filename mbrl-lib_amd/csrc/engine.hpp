@@ -1,5 +1,5 @@
 // engine.hpp -- private to the host units of the C ABI (include/hipets.h): engine.hip, model.hip, rollout.hip, plan.hip, comm.hip,
-// train.hip, policy.hip, replay.hip, sac.hip, value.hip, ensemble.hip and policy_rollout.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
+// train.hip, train_split.hip, policy.hip, replay.hip, sac.hip, value.hip, ensemble.hip and policy_rollout.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
 // Host code only; nothing declared here is part of the ABI (hidden visibility).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -154,6 +154,9 @@ struct hipets_engine {
     std::vector<std::pair<hipEvent_t, hipEvent_t>> event_pool;
     // model training (hipets_train_steps / hipets_train_eval): per-member activation slabs, evaluate's partial sums
     DevBuf train_slab, train_partial;
+    // which kernels the steps run (hipets_set_train_kernel), and the split step's loss / grad_sq partials (train_split.hip)
+    int train_kernel = HIPETS_TRAIN_KERNEL_MEMBER;
+    DevBuf train_split_part;
     // the packed layers of the SAC actor (hipets_policy_set / _act, policy.hip) and of the SAC critic, Q1 and Q2 (hipets_critic_set / _q, value.hip)
     hipets::MlpSnapshot policy, critic;
     // the block counts of hipets_compact_transitions / hipets_ring_compact_transitions (replay.hip)

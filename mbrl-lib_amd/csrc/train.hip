@@ -5,7 +5,8 @@
 //   train_eval_kernel  GaussianMLP.eval_score over the whole evaluation set (gaussian_mlp.py:337-361), mean columns only
 // Every product runs on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32 accumulate): mm_tile is the k-loop, tile_walk.hpp the tiles'
 // numbering and the lane-to-element map, adam.hpp the optimizer's rule.  The host side by job: train_check (the arguments),
-// train_slab (train.hpp: the slab's layout), train_fill (what both argument blocks share), train_chunk and the chunk loop.
+// train_slab and train_fill (train.hpp: the slab's layout, what the argument blocks share), train_chunk and the chunk loop.  Under
+// HIPETS_TRAIN_KERNEL_SPLIT the steps leave for train_split.hip behind the same checks; the elementwise helpers are train_math.hpp's.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,6 +17,8 @@
 #include "lds_optin.hpp"
 #include "tile_walk.hpp"
 #include "train.hpp"
+#include "train_math.hpp"
+#include "train_split.hpp"
 
 namespace hipets {
 
@@ -68,51 +71,6 @@ __device__ __forceinline__ f32x4 mm_tile(const float* __restrict__ A, int sam, i
         c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, c0, 0, 0, 0);
     }
     return c0 + c1;
-}
-
-// the activation modules of GaussianMLP (gaussian_mlp.py:88-96) and their derivatives in terms of the pre-activation z
-__device__ __forceinline__ float act_fwd(int act, float z, float slope) {
-    switch (act) {
-        case HIPETS_ACT_RELU: return z > 0.f ? z : 0.f;
-        case HIPETS_ACT_SILU: return z / (1.f + expf(-z));
-        case HIPETS_ACT_LEAKY_RELU: return z > 0.f ? z : z * slope;
-        case HIPETS_ACT_TANH: return tanhf(z);
-        default: return 1.f / (1.f + expf(-z));
-    }
-}
-
-__device__ __forceinline__ float act_grad(int act, float z, float slope) {
-    switch (act) {
-        case HIPETS_ACT_RELU: return z > 0.f ? 1.f : 0.f;
-        case HIPETS_ACT_SILU: {
-            const float s = 1.f / (1.f + expf(-z));
-            return s * (1.f + z * (1.f - s));
-        }
-        case HIPETS_ACT_LEAKY_RELU: return z > 0.f ? 1.f : slope;
-        case HIPETS_ACT_TANH: {
-            const float t = tanhf(z);
-            return 1.f - t * t;
-        }
-        default: {
-            const float s = 1.f / (1.f + expf(-z));
-            return s * (1.f - s);
-        }
-    }
-}
-
-// torch.nn.functional.softplus (beta 1, threshold 20) and its derivative
-__device__ __forceinline__ float softplus(float x) { return x > 20.f ? x : log1pf(expf(x)); }
-__device__ __forceinline__ float softplus_grad(float x) {
-    if (x > 20.f) return 1.f;
-    const float z = expf(x);
-    return z / (z + 1.f);
-}
-
-template <class T>
-__device__ __forceinline__ T wave_sum(T x) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-    return x;
 }
 
 // kLoss = the loss tail: kTrainLossNLL (output layer 2 out wide, mean | raw logvar) or kTrainLossMSE (output layer out wide).
@@ -391,7 +349,8 @@ __global__ __launch_bounds__(256) void train_eval_reduce_kernel(const TrainEvalA
 
 // ---- the C ABI's argument checks (hipets_train_steps / hipets_train_eval below) ----
 
-int train_check(const hipets_train_desc* d, bool adam, int loss_kind) {
+// max_batch_limit: of the kernels the call runs (the member kernel's, or the split step's under HIPETS_TRAIN_KERNEL_SPLIT)
+int train_check(const hipets_train_desc* d, bool adam, int loss_kind, int max_batch_limit = kTrainMaxBatch) {
     if (!d) return fail("null train desc");
     if (loss_kind != HIPETS_TRAIN_LOSS_NLL && loss_kind != HIPETS_TRAIN_LOSS_MSE) return fail("unknown loss kind %d", loss_kind);
     if (d->ensemble_size < 1 || d->ensemble_size > kTrainMaxMembers) return fail("ensemble_size %d outside [1, %d]", d->ensemble_size, kTrainMaxMembers);
@@ -400,7 +359,7 @@ int train_check(const hipets_train_desc* d, bool adam, int loss_kind) {
     if (d->hid < 1 || d->hid > kTrainMaxHid) return fail("hid %d outside [1, %d]", d->hid, kTrainMaxHid);
     if (d->out_dim < 1 || d->out_dim > kTrainMaxOut) return fail("out_dim %d outside [1, %d]", d->out_dim, kTrainMaxOut);
     if (d->activation < HIPETS_ACT_RELU || d->activation > HIPETS_ACT_SIGMOID) return fail("unknown activation %d", d->activation);
-    if (d->max_batch < 1 || d->max_batch > kTrainMaxBatch) return fail("max_batch %d outside [1, %d]", d->max_batch, kTrainMaxBatch);
+    if (d->max_batch < 1 || d->max_batch > max_batch_limit) return fail("max_batch %d outside [1, %d]", d->max_batch, max_batch_limit);
     if (!d->weights || !d->biases) return fail("null parameter arrays");
     for (int l = 0; l < d->n_layers; ++l)
         if (!d->weights[l] || !d->biases[l]) return fail("null parameter of layer %d", l);
@@ -415,26 +374,6 @@ int train_check(const hipets_train_desc* d, bool adam, int loss_kind) {
         if (d->steps_per_launch < 0) return fail("steps_per_launch %d < 0", d->steps_per_launch);
     }
     return 0;
-}
-
-// what TrainStepArgs and TrainEvalArgs share: the layers' widths and parameters, the dataset, the counts
-template <class Args>
-void train_fill(Args& a, const hipets_train_desc* d, int loss_kind, const float* x, const float* y, int64_t n_rows) {
-    a.dims[0] = d->in_dim;
-    for (int l = 1; l < d->n_layers; ++l) a.dims[l] = d->hid;
-    a.dims[d->n_layers] = loss_kind == HIPETS_TRAIN_LOSS_MSE ? d->out_dim : 2 * d->out_dim;
-    for (int l = 0; l < d->n_layers; ++l) {
-        a.w[l] = static_cast<float*>(d->weights[l]);
-        a.b[l] = static_cast<float*>(d->biases[l]);
-    }
-    a.x = x;
-    a.y = y;
-    a.n_rows = n_rows;
-    a.n_layers = d->n_layers;
-    a.out_dim = d->out_dim;
-    a.ensemble_size = d->ensemble_size;
-    a.activation = d->activation;
-    a.leaky_slope = d->leaky_slope;
 }
 
 // steps per launch: the caller's, or launches of ~50 ms at most: a step costs ~ 6 B P flops per member at the ~50 GFLOP/s per CU the
@@ -488,7 +427,8 @@ int hipets_train_steps_loss(hipets_engine* e, const hipets_train_desc* d, const 
                             const int32_t* rows, int32_t n_steps, int64_t step0, float* loss, float* grad_sq, void* stream, int32_t loss_kind,
                             int32_t bounds_per_member, float grad_scale) {
     if (!e) return fail("null engine");
-    if (train_check(d, true, loss_kind)) return 1;
+    const bool split = e->train_kernel == HIPETS_TRAIN_KERNEL_SPLIT;
+    if (train_check(d, true, loss_kind, split ? kSplitMaxBatch : kTrainMaxBatch)) return 1;
     if (!std::isfinite(grad_scale) || !(grad_scale > 0.f)) return fail("grad_scale %g is not a finite positive number", (double)grad_scale);
     if (!x || !y || !idx || !rows || !loss || !grad_sq) return fail("null argument");
     if (n_rows < 1 || n_rows > INT32_MAX) return fail("n_rows %lld outside [1, 2^31)", (long long)n_rows);
@@ -498,6 +438,7 @@ int hipets_train_steps_loss(hipets_engine* e, const hipets_train_desc* d, const 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
+    if (split) return train_split_steps(e, d, x, y, n_rows, idx, rows, n_steps, step0, loss, grad_sq, st, loss_kind, bounds_per_member, grad_scale);
     TrainStepArgs a{};
     const int L = d->n_layers, E = d->ensemble_size, Bm = d->max_batch;
     train_fill(a, d, loss_kind, x, y, n_rows);

@@ -97,6 +97,26 @@ struct TrainEvalArgs {
     float leaky_slope;
 };
 
+// what TrainStepArgs, TrainEvalArgs and TrainSplitArgs (train_split.hpp) share: the layers' widths and parameters, the dataset, the counts
+template <class Args>
+inline void train_fill(Args& a, const hipets_train_desc* d, int loss_kind, const float* x, const float* y, int64_t n_rows) {
+    a.dims[0] = d->in_dim;
+    for (int l = 1; l < d->n_layers; ++l) a.dims[l] = d->hid;
+    a.dims[d->n_layers] = loss_kind == HIPETS_TRAIN_LOSS_MSE ? d->out_dim : 2 * d->out_dim;
+    for (int l = 0; l < d->n_layers; ++l) {
+        a.w[l] = static_cast<float*>(d->weights[l]);
+        a.b[l] = static_cast<float*>(d->biases[l]);
+    }
+    a.x = x;
+    a.y = y;
+    a.n_rows = n_rows;
+    a.n_layers = d->n_layers;
+    a.out_dim = d->out_dim;
+    a.ensemble_size = d->ensemble_size;
+    a.activation = d->activation;
+    a.leaky_slope = d->leaky_slope;
+}
+
 hipError_t launch_train_steps(const TrainStepArgs& a, int loss_kind, hipStream_t st);
 hipError_t launch_train_eval(const TrainEvalArgs& a, hipStream_t st);
 

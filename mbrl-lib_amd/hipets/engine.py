@@ -597,7 +597,7 @@ class Engine:
     def train_steps(self, weights, biases, exp_avg, exp_avg_sq, min_logvar, max_logvar, x: torch.Tensor, y: torch.Tensor,
                     idx: torch.Tensor, rows: torch.Tensor, step0: int, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
                     weight_decay: float = 0.0, activation: str = "silu", leaky_slope: float = 0.01, steps_per_launch: int = 0,
-                    loss: str = "nll", grad_scale: float = 1.0, bounds_per_member: bool = False):
+                    loss: str = "nll", grad_scale: float = 1.0, bounds_per_member: bool = False, kernel: str = "member"):
         """``n_steps = idx.shape[0]`` minibatch steps of Model.update + torch.optim.Adam on every member, in place on the DEVICE
         tensors ``weights`` / ``biases`` and the Adam state ``exp_avg`` / ``exp_avg_sq`` (pairs of per-layer lists (w, b)).
         x [N, in] / y [N, out] f32 = the dataset's model inputs and targets; idx int32 [n_steps, E, max_batch] its rows per
@@ -605,7 +605,12 @@ class Engine:
         DEVICE f32 [n_steps, E] (hipets.h: hipets_train_steps).  Asynchronous on the current stream.
         ``loss`` "mse": a deterministic model (last layer out wide, bounds None, loss = the member's sum of squared errors);
         ``bounds_per_member``: min_logvar / max_logvar are [E, out]; ``grad_scale`` multiplies the loss gradient (1 / E for a
-        BasicEnsemble).  Any of them off its default goes through hipets_train_steps_loss."""
+        BasicEnsemble).  Any of them off its default goes through hipets_train_steps_loss.
+        ``kernel``: "member" (one workgroup per member, a chunk of steps per launch; max_batch <= 256) or "split" (the row-split step:
+        three launches per step that spread a member over many CUs; max_batch <= 1024; ``steps_per_launch`` is ignored; same
+        semantics, sums in another order).  The engine's setting (hipets_set_train_kernel) is set for the call and put back."""
+        if kernel not in _lib.TRAIN_KERNEL:
+            raise ValueError("kernel must be 'member' or 'split'")
         dev = self.device
         out_dim = int(y.shape[-1]) if y.dim() == 2 else -1
         _check_dev(x, torch.float32, dev, "x")
@@ -625,11 +630,17 @@ class Engine:
         losses = torch.empty(n_steps, E, dtype=torch.float32, device=dev)
         gsq = torch.empty(n_steps, E, dtype=torch.float32, device=dev)
         kw = dict(d=d, x=x, y=y, n_rows=int(x.shape[0]), idx=idx, rows=rows, n_steps=n_steps, step0=int(step0), loss=losses, grad_sq=gsq)
-        if loss == "nll" and not bounds_per_member and float(grad_scale) == 1.0:
-            self._call("hipets_train_steps", **kw)
-        else:
-            self._call("hipets_train_steps_loss", loss_kind=_lib.TRAIN_LOSS[loss], bounds_per_member=int(bool(bounds_per_member)),
-                       grad_scale=float(grad_scale), **kw)
+        if kernel != "member":
+            self._query("hipets_set_train_kernel", kind=_lib.TRAIN_KERNEL[kernel])
+        try:
+            if loss == "nll" and not bounds_per_member and float(grad_scale) == 1.0:
+                self._call("hipets_train_steps", **kw)
+            else:
+                self._call("hipets_train_steps_loss", loss_kind=_lib.TRAIN_LOSS[loss], bounds_per_member=int(bool(bounds_per_member)),
+                           grad_scale=float(grad_scale), **kw)
+        finally:
+            if kernel != "member":
+                self._query("hipets_set_train_kernel", kind=_lib.TRAIN_KERNEL["member"])
         del keep
         return losses, gsq
 

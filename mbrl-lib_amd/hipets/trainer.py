@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from ._lib import (TRAIN_MAX_BATCH as MAX_BATCH, TRAIN_MAX_HID as MAX_HID, TRAIN_MAX_IN as MAX_IN, TRAIN_MAX_MEMBERS as MAX_MEMBERS,
-                   TRAIN_MAX_OUT as MAX_OUT)  # the library's shape limits (HIPETS_TRAIN_MAX_* of include/hipets.h) under this module's names
+                   TRAIN_MAX_OUT as MAX_OUT, TRAIN_SPLIT_MAX_BATCH as SPLIT_MAX_BATCH)  # the library's shape limits (HIPETS_TRAIN_MAX_* of include/hipets.h) under this module's names
 from .model import UnsupportedModelError, _ACT_BY_CLASS
 
 # model_trainer.py:20-28 (the logger group's columns)
@@ -192,14 +192,22 @@ class ModelTrainer:
     """Drop-in for ``mbrl.models.ModelTrainer``: same constructor, ``train`` / ``evaluate`` signatures and return values, the
     same patience / best-weights / elite logic, logger group and callbacks.  Minibatch steps run in chunks inside one
     kernel launch per chunk; ``batch_callback`` is replayed in order after each epoch from one device read per epoch.
+    ``step_kernel``: "member" = one workgroup per member (batch sizes up to 256); "split" = the row-split step, three launches per
+    minibatch step that spread a member over many CUs (batch sizes up to 1024); "auto" (the default) = "member" wherever it runs --
+    every result of a batch size up to 256 keeps its bits -- and "split" for batch sizes 257..1024.
+    ``steps_per_launch`` (0 = the library's choice) cuts the member kernel's launches; the split step ignores it.
     Training runs on ``engine``'s GPU (default: ``device`` or cuda:current) whatever device the model lives on; the trained
     weights are written back into the live parameters (their ``_version`` changes, so fused agents re-pack)."""
 
     _LOG_GROUP_NAME = "model_train"
 
     def __init__(self, model, optim_lr: float = 1e-4, weight_decay: float = 1e-5, optim_eps: float = 1e-8, logger=None, *,
-                 engine=None, device=None, steps_per_launch: int = 0, extended: bool = False):
+                 engine=None, device=None, steps_per_launch: int = 0, extended: bool = False, step_kernel: str = "auto"):
         from .engine import get_engine
+
+        if step_kernel not in ("auto", "member", "split"):
+            raise ValueError("step_kernel must be 'auto', 'member' or 'split'")
+        self.step_kernel = step_kernel
 
         self.model = model
         self._kind = _read_model(model, extended)
@@ -318,14 +326,17 @@ class ModelTrainer:
     def _run_steps(self, x, y, idx, rows):
         g = self.optimizer.param_groups[0]
         dev = self.engine.device
-        if idx.shape[2] > MAX_BATCH:
-            raise UnsupportedModelError(f"batch size {idx.shape[2]} > {MAX_BATCH}" + _KEEP_STOCK)
+        split = self.step_kernel == "split" or (self.step_kernel == "auto" and idx.shape[2] > MAX_BATCH)
+        limit = SPLIT_MAX_BATCH if split else MAX_BATCH
+        if idx.shape[2] > limit:
+            raise UnsupportedModelError(f"batch size {idx.shape[2]} > {limit}" + (" (step_kernel='member')" if self.step_kernel == "member" else "")
+                                        + _KEEP_STOCK)
         lo, hi = self._bounds()
         loss, gsq = self.engine.train_steps(
             self._w[0], self._w[1], (self._m[0], self._m[1]), (self._v[0], self._v[1]), lo, hi, x, y,
             torch.from_numpy(np.ascontiguousarray(idx)).to(dev), torch.from_numpy(np.ascontiguousarray(rows)).to(dev), self._step,
             lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], activation=self._act, leaky_slope=self._slope,
-            steps_per_launch=self.steps_per_launch, **self._engine_kw)
+            steps_per_launch=self.steps_per_launch, **self._engine_kw, **({"kernel": "split"} if split else {}))
         self._step += int(idx.shape[0])
         return loss, gsq
 

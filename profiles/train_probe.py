@@ -5,7 +5,15 @@ synchronisations (loss.item() + one .item() per parameter tensor for grad_norm, 
 
     python profiles/train_probe.py [--out profiles/train_epoch.json] [--steps 400]
 
-Run under `rocprofv3 --kernel-trace --stats -- python profiles/train_probe.py` for the per-kernel summary."""
+Run under `rocprofv3 --kernel-trace --stats -- python profiles/train_probe.py` for the per-kernel summary.
+
+With --routes it times the step kernels against each other instead: at both shapes and at B = 512 and 1024 of
+the same widths, the split kernels, the member kernel (where it runs: B <= 256) and the eager baseline take turns in one process,
+--rounds times each; medians and the spread (min .. max) go to profiles/train_split.json.  --split-only SHAPE runs nothing but
+split steps at one shape: the run to put under rocprofv3 for the split of a step over its three kernels.
+
+    python profiles/train_probe.py --routes [--rounds 5] [--steps 1000] [--eager-steps 100]
+    rocprofv3 --kernel-trace --stats -- python profiles/train_probe.py --split-only mbpo_halfcheetah"""
 import argparse
 import json
 import os
@@ -27,8 +35,62 @@ SHAPES = {  # E, B, in, hid, out, linear layers (conf/dynamics_model/gaussian_ml
     "pets_halfcheetah": (7, 32, 24, 200, 18, 5),
     "mbpo_halfcheetah": (7, 256, 23, 200, 18, 5),
 }
+ROUTE_SHAPES = dict(SHAPES, b512_halfcheetah_widths=(7, 512, 23, 200, 18, 5), b1024_halfcheetah_widths=(7, 1024, 23, 200, 18, 5))
 N = 100_000
 DEV = "cuda:0"
+
+
+def _setup(shape, steps):
+    E, B, in_dim, hid, out, L = shape
+    g = torch.Generator().manual_seed(0)
+    x = torch.randn(N, in_dim, generator=g).to(DEV)
+    y = (torch.randn(N, out, generator=g) * 0.3).to(DEV)
+    ws, bs = tr.random_model(E, in_dim, hid, out, L, 0, dtype=torch.float32)
+    lo, hi = -10 * torch.ones(out, device=DEV), 0.5 * torch.ones(out, device=DEV)
+    idx = torch.randint(0, N, (steps, E, B), generator=g, dtype=torch.int32).to(DEV)
+    rows = torch.full((steps,), B, dtype=torch.int32, device=DEV)
+    return x, y, ws, bs, lo, hi, idx, rows
+
+
+def measure_routes(name, rounds, steps, eager_steps):
+    """us per step of the three routes at one shape, interleaved: {route: {"median", "min", "max", "rounds"}}"""
+    shape = ROUTE_SHAPES[name]
+    E, B, in_dim, hid, out, L = shape
+    eng = hipets.get_engine(DEV)
+    x, y, ws, bs, lo, hi, idx, rows = _setup(shape, steps)
+    state = {r: tr.fresh_state(ws, bs, torch.float32, DEV) for r in ("split", "member", "eager")}
+
+    def hip(route, n):
+        w, b, m, v = state[route]
+        eng.train_steps(w, b, m, v, lo, hi, x, y, idx[:n], rows[:n], 0, lr=1e-3, weight_decay=1e-5, kernel=route)
+
+    def eager(n):
+        we, be, me, ve = state["eager"]
+        for s in range(n):
+            sel = idx[s].long()
+            loss, dws, dbs = tr.nll_step(we, be, x[sel], y[sel], lo.reshape(1, -1), hi.reshape(1, -1), "silu")
+            _ = loss.sum().item()
+            _ = sum(gg.norm().item() ** 2 for gg in dws + dbs)
+            for li in range(L):
+                tr.adam_(we[li], dws[li], me[0][li], ve[0][li], s + 1, 1e-3, weight_decay=1e-5)
+                tr.adam_(be[li], dbs[li], me[1][li], ve[1][li], s + 1, 1e-3, weight_decay=1e-5)
+
+    routes = {"split": (lambda n: hip("split", n), steps), "eager": (eager, eager_steps)}
+    if B <= hipets._lib.TRAIN_MAX_BATCH:
+        routes["member"] = (lambda n: hip("member", n), steps)
+    times = {r: [] for r in routes}
+    for rnd in range(rounds + 1):  # (round 0 warms every route up)
+        for r, (fn, n) in routes.items():
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn(n)
+            torch.cuda.synchronize()
+            if rnd:
+                times[r].append((time.perf_counter() - t0) / n * 1e6)
+    res = {r: {"median_us_per_step": round(float(np.median(t)), 1), "min": round(min(t), 1), "max": round(max(t), 1), "rounds": len(t)}
+           for r, t in times.items()}
+    res["shape"] = dict(zip(("E", "B", "in", "hid", "out", "linear_layers"), shape))
+    return res
 
 
 def measure(name, steps, eager_steps):
@@ -95,7 +157,24 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "train_epoch.json"))
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--eager-steps", type=int, default=60)
+    ap.add_argument("--routes", action="store_true")
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--split-only", default=None, metavar="SHAPE")
     a = ap.parse_args()
+    if a.split_only:
+        x, y, ws, bs, lo, hi, idx, rows = _setup(ROUTE_SHAPES[a.split_only], a.steps)
+        w, b, m, v = tr.fresh_state(ws, bs, torch.float32, DEV)
+        hipets.get_engine(DEV).train_steps(w, b, m, v, lo, hi, x, y, idx, rows, 0, lr=1e-3, weight_decay=1e-5, kernel="split")
+        torch.cuda.synchronize()
+        return
+    if a.routes:
+        res = {name: measure_routes(name, a.rounds, a.steps, a.eager_steps) for name in ROUTE_SHAPES}
+        res["device"] = torch.cuda.get_device_name(0)
+        print(json.dumps(res, indent=1))
+        out = a.out if a.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "train_split.json")
+        with open(out, "w") as f:
+            json.dump(res, f, indent=1)
+        return
     res = {name: measure(name, a.steps, a.eager_steps) for name in SHAPES}
     res["device"] = torch.cuda.get_device_name(0)
     print(json.dumps(res, indent=1))
