@@ -858,6 +858,18 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
 int hipets_sac_forward_taps(hipets_engine* e, int32_t batch_size, float* q1, float* q2, float* y, float* log_pi_next, float* log_pi,
                             void* stream);
 
+/* Which kernel runs the strided products of hipets_sac_update (every sac_mm launch of the 19; the tail and finish kernels are the same
+ * under both): engine state, like hipets_set_train_kernel; host only, takes no stream (additive entry point, HIPETS_ABI_VERSION stays).
+ *   HIPETS_SAC_PRODUCT_TILE (the default)  one 16 x 16 result tile per wave, operands fetched from global memory per k-block.
+ *   HIPETS_SAC_PRODUCT_BLOCKED             one 64 x 64 block per workgroup: both operands staged through LDS in double-buffered k chunks
+ *     of 32 with 16-byte global loads along whichever direction is contiguous, 2 x 2 tiles per wave, 16 MFMAs per 4 LDS reads.  Per tile
+ *     it issues the tile kernel's MFMAs in the tile kernel's order on the same operands and ends in the same epilogue: every result of
+ *     an update is the tile kernel's BIT FOR BIT; the two differ in speed only (DESIGN.md section 30 has the measurements).
+ * An unknown kind fails with HIPETS_ERR_INVALID_ARGUMENT and leaves the setting as it was.                                        */
+#define HIPETS_SAC_PRODUCT_TILE 0
+#define HIPETS_SAC_PRODUCT_BLOCKED 1
+int hipets_set_sac_product(hipets_engine* e, int32_t kind);
+
 /* ---- value-bootstrapped planning: the SAC critic and discounted returns with a terminal value ----
  * Additive entry points: scalars and pointers only, no struct, HIPETS_ABI_VERSION stays.  Need no dynamics model.
  *

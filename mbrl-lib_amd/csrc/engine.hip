@@ -147,6 +147,13 @@ int hipets_set_train_kernel(hipets_engine* e, int32_t kind) {
     return 0;
 }
 
+int hipets_set_sac_product(hipets_engine* e, int32_t kind) {
+    if (!e) return fail("null engine");
+    if (kind != HIPETS_SAC_PRODUCT_TILE && kind != HIPETS_SAC_PRODUCT_BLOCKED) return fail("sac product must be HIPETS_SAC_PRODUCT_TILE or HIPETS_SAC_PRODUCT_BLOCKED");
+    e->sac_product = kind;
+    return 0;
+}
+
 int hipets_set_particle_reduce(hipets_engine* e, int32_t kind, float kappa, int32_t worst_k) {
     if (!e) return fail("null engine");
     if (kind < HIPETS_REDUCE_MEAN || kind > HIPETS_REDUCE_WORST_K) return fail("unknown particle reduction %d (HIPETS_REDUCE_MEAN .. HIPETS_REDUCE_WORST_K)", kind);

@@ -165,6 +165,7 @@ struct hipets_engine {
     bool has_sac = false;
     hipets::SacBind sac{};
     int sac_last_batch = 0;
+    int sac_product = HIPETS_SAC_PRODUCT_TILE;  // which kernel runs the products of an update (hipets_set_sac_product)
     DevBuf sac_ws, sac_one;
     // the dynamics ensemble as hipets_ensemble_set packed it (hipets_ensemble_predict, ensemble.hip); apart from the rollout model slot above
     hipets::EnsembleSnapshot ensemble;

@@ -3,6 +3,8 @@
 // entry points.
 //   sac_mm_kernel        up to kSacMaxProblems strided products C = A . B per launch, a 16 x 16 tile per wave, one epilogue per launch:
 //                        bias (+ relu), relu mask (the dz chain), plain store, or torch-order Adam (+ the target's soft update)
+//   sac_mm_blocked_kernel  the same launches, a 64 x 64 block per workgroup with both operands staged through LDS and 2 x 2 tiles per wave
+//                        (hipets_set_sac_product): the tile kernel's MFMAs per tile in its order and its epilogue, so its bits
 //   sac_policy_tail_kernel / sac_policy_tail_bwd_kernel   GaussianPolicy.sample behind its heads (model.py:95-108) and its gradient
 //   sac_q_tail_kernel    the N = 1 output layers of the Q-networks, fused with the TD target / the policy's min-Q and their gradients
 //   sac_finish_kernel    the losses, the Adam step on log_alpha, the result slot
@@ -45,12 +47,13 @@ struct SacProblem {
     const float* aux;  // bias [N] (kEpiBias*), or the activations [M, ldo] whose sign masks the result (kEpiMask)
     float *m, *v;      // kEpiAdam: exp_avg / exp_avg_sq of `out`
     float* target;     // kEpiAdam: the target network's copy of `out`, or null
-    int nseg, M, N, ldo, tiles_n;
+    int nseg, M, N, ldo, tiles_n, blocks_n;
 };
 
 struct SacMmArgs {
     SacProblem p[kSacMaxProblems];
-    int tile_start[kSacMaxProblems + 1];
+    int tile_start[kSacMaxProblems + 1];   // sac_mm_kernel: the first tile of every problem (a prefix sum)
+    int block_start[kSacMaxProblems + 1];  // sac_mm_blocked_kernel: the first 64 x 64 block of every problem
     int np, epilogue;
     AdamScalars adam;
     int soft;  // kEpiAdam: apply target = target * (1 - tau) + param * tau with the new parameter value
@@ -91,18 +94,10 @@ __device__ __forceinline__ void sac_seg_acc(f32x4& c0, f32x4& c1, const SacSeg& 
     }
 }
 
-__global__ __launch_bounds__(kSacThreads) void sac_mm_kernel(const SacMmArgs a) {
-    const int lane = threadIdx.x & 63;
-    const int t = __builtin_amdgcn_readfirstlane((int)blockIdx.x * kSacWaves + ((int)threadIdx.x >> 6));
-    if (t >= a.tile_start[a.np]) return;
-    int pi = 0;
-    while (pi + 1 < a.np && t >= a.tile_start[pi + 1]) ++pi;
-    const SacProblem& p = a.p[pi];
-    const int lt = t - a.tile_start[pi];
-    const int m0 = tile_m0(lt, p.tiles_n), n0 = tile_n0(lt, p.tiles_n);
-    f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
-    sac_seg_acc(c0, c1, p.s[0], p.M, p.N, m0, n0, lane);
-    if (p.nseg > 1) sac_seg_acc(c0, c1, p.s[1], p.M, p.N, m0, n0, lane);
+// The launch's epilogue on one finished 16 x 16 tile at (m0, n0): c0 + c1, then the lane's four elements under col < N, row < M.
+// Both product kernels end every tile here, so the two agree bit for bit wherever their k-loops do.
+__device__ __forceinline__ void sac_tile_epilogue(const SacMmArgs& a, const SacProblem& p, const f32x4& c0, const f32x4& c1, int m0, int n0,
+                                                  int lane) {
     const f32x4 c = c0 + c1;
     const int col = tile_col(n0, lane);
     if (col >= p.N) return;
@@ -126,6 +121,206 @@ __global__ __launch_bounds__(kSacThreads) void sac_mm_kernel(const SacMmArgs a) 
             const float pn = adam_update(p.out[o], c[i], p.m + o, p.v + o, a.adam);
             p.out[o] = pn;
             if (a.soft && p.target) p.target[o] = p.target[o] * a.one_minus_tau + pn * a.tau;  // utils.soft_update
+        }
+    }
+}
+
+__global__ __launch_bounds__(kSacThreads) void sac_mm_kernel(const SacMmArgs a) {
+    const int lane = threadIdx.x & 63;
+    const int t = __builtin_amdgcn_readfirstlane((int)blockIdx.x * kSacWaves + ((int)threadIdx.x >> 6));
+    if (t >= a.tile_start[a.np]) return;
+    int pi = 0;
+    while (pi + 1 < a.np && t >= a.tile_start[pi + 1]) ++pi;
+    const SacProblem& p = a.p[pi];
+    const int lt = t - a.tile_start[pi];
+    const int m0 = tile_m0(lt, p.tiles_n), n0 = tile_n0(lt, p.tiles_n);
+    f32x4 c0 = {0.f, 0.f, 0.f, 0.f}, c1 = {0.f, 0.f, 0.f, 0.f};
+    sac_seg_acc(c0, c1, p.s[0], p.M, p.N, m0, n0, lane);
+    if (p.nseg > 1) sac_seg_acc(c0, c1, p.s[1], p.M, p.N, m0, n0, lane);
+    sac_tile_epilogue(a, p, c0, c1, m0, n0, lane);
+}
+
+// ---- the blocked product (HIPETS_SAC_PRODUCT_BLOCKED): the same SacMmArgs launch, a 64 x 64 block of one problem per workgroup -------
+// Wave w holds the 2 x 2 tiles at (32 (w >> 1), 32 (w & 1)) of the block with sac_seg_acc's two accumulators per tile.  Both operands of
+// the block travel through LDS in k chunks of 32 = two k-blocks of 16, double-buffered: the next chunk's global loads are issued before
+// the current chunk is multiplied and stored to the other buffer behind it (one barrier per chunk).  A panel is [64 rows or columns][32 k]
+// floats at a row stride of kSacPanelStride, so lane (r, q)'s operands k = 16 kb + 4 q + 0 .. 3 of a tile are ONE ds_read_b128 and feed
+// the two tiles that share the row (A) or the column (B): 4 reads, 16 MFMAs per k-block.  Per tile the MFMAs and their order are
+// sac_seg_acc's -- k-blocks in order, MFMA s takes k = 16 kb + 4 q + s, 0 and 2 into c0, 1 and 3 into c1, segment 0 before segment 1, no
+// k-block at or past K -- and the operands are the same floats or the same selected zeros, so every tile leaves the k-loop with
+// sac_mm_kernel's bits and ends in the same epilogue.
+constexpr int kSacChunk = 32;        // k per staged chunk
+constexpr int kSacPanelStride = 40;  // floats per panel row: 32 + 8.  Row r starts at bank quad 10 r (mod 16): even for every r, and k-quad
+                                     // q adds q.  A b128 read is served in the lane groups {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, ...
+                                     // (DESIGN.md section 8): eight rows at q and the other eight at q + 1 -- 8 even and 8 odd quads of
+                                     // banks, {0, 2, ..., 14} + q and + q + 1: all 64 banks once.  (Stride 36 folds rows 4 and 13 of
+                                     // such a group onto one quad.)
+constexpr int kSacPanelFloats = kBlock * kSacPanelStride;
+enum SacStageMode { kStageK = 0, kStageRow = 1, kStageScalar = 2 };
+
+// one operand of one segment as the block sees it: element (row, k) at p[row * sr + k * sk], rows r0 .. r0 + 63 below R
+struct SacPanelSrc {
+    const float* p;
+    int sr, sk, R, r0, K, mode;
+};
+
+// 16-byte loads run along k where k is the contiguous direction (forward products, the A side of the dz chains: sac_seg_acc's own
+// condition), else along the rows / columns where those are (the dW products, the B side of the dz chains); everything else -- stride 0,
+// a misaligned base -- is loaded float by float.  A group of four that crosses K, M or N is loaded float by float in either mode.
+__device__ __forceinline__ SacPanelSrc sac_panel_src(const float* p, int sr, int sk, int R, int r0, int K) {
+    const bool al = (reinterpret_cast<uintptr_t>(p) & 15) == 0;
+    const int mode = (sk == 1 && (sr & 3) == 0 && al) ? kStageK : ((sr == 1 && (sk & 3) == 0 && al) ? kStageRow : kStageScalar);
+    return SacPanelSrc{p, sr, sk, R, r0, K, mode};
+}
+
+// Who loads what of the chunk at k0: two groups of four per thread.  kStageK / kStageScalar: four k of one row each (rows (tid >> 3) and
+// + 32, k quad tid & 7: eight lanes read 128 contiguous bytes of a row).  kStageRow: four rows at one k each (k = (lane & 15) and + 16,
+// row quad (lane >> 4) + 4 wave).
+// ... any chunk, group by group through sac_ld4: past R and past K zeros, selected, never read
+__device__ __forceinline__ void sac_panel_fetch(f32x4 (&v)[2], const SacPanelSrc& s, int k0, int tid) {
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (s.mode == kStageRow) {
+            const int k = k0 + (tid & 15) + 16 * h, r = s.r0 + 4 * (((tid & 63) >> 4) + 4 * (tid >> 6));
+            const bool there = k < s.K;
+            v[h] = sac_ld4(s.p + (int64_t)(there ? k : 0) * s.sk, s.sr, r, s.R, there, true);
+        } else {
+            const int row = s.r0 + (tid >> 3) + 32 * h;
+            const bool there = row < s.R;
+            v[h] = sac_ld4(s.p + (int64_t)(there ? row : 0) * s.sr, s.sk, k0 + 4 * (tid & 7), s.K, there, s.mode == kStageK);
+        }
+    }
+}
+
+// ... a chunk that lies below K whole (and, kStageRow, in a block that lies below R whole): two 16-byte loads, no branch and no use of
+// the loaded value, so that nothing waits for them before the chunk in LDS has been multiplied.  A row past R loads row 0;
+// sac_panel_store selects its zeros.
+template <int kMode>
+__device__ __forceinline__ void sac_panel_fetch_whole(f32x4 (&v)[2], const SacPanelSrc& s, int k0, int tid) {
+    if constexpr (kMode == kStageRow) {
+        const float* cp = s.p + (int64_t)(k0 + (tid & 15)) * s.sk + s.r0 + 4 * (((tid & 63) >> 4) + 4 * (tid >> 6));
+        v[0] = *reinterpret_cast<const f32x4*>(cp);
+        v[1] = *reinterpret_cast<const f32x4*>(cp + (int64_t)16 * s.sk);
+    } else {
+        const int row = s.r0 + (tid >> 3), k = k0 + 4 * (tid & 7);
+        v[0] = *reinterpret_cast<const f32x4*>(s.p + (int64_t)(row < s.R ? row : 0) * s.sr + k);
+        v[1] = *reinterpret_cast<const f32x4*>(s.p + (int64_t)(row + 32 < s.R ? row + 32 : 0) * s.sr + k);
+    }
+}
+
+// ... into the panel: one ds_write_b128 per group (eight lanes fill one row's 32 banks; zeros for a row past R), or the transposing
+// four ds_write_b32
+__device__ __forceinline__ void sac_panel_store(float* panel, const f32x4 (&v)[2], const SacPanelSrc& s, int mode, int tid) {
+    const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        if (mode == kStageRow) {
+            float* d = panel + 4 * (((tid & 63) >> 4) + 4 * (tid >> 6)) * kSacPanelStride + (tid & 15) + 16 * h;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) d[e * kSacPanelStride] = v[h][e];
+        } else {
+            const int row = (tid >> 3) + 32 * h;
+            *reinterpret_cast<f32x4*>(panel + row * kSacPanelStride + 4 * (tid & 7)) = s.r0 + row < s.R ? v[h] : zero;
+        }
+    }
+}
+
+// one k-block of 16 of the wave's 2 x 2 tiles: pa / pb = the lane's row of tile row 0 / tile column 0 at the k-block's quad q
+__device__ __forceinline__ void sac_block_kstep(f32x4 (&c0)[2][2], f32x4 (&c1)[2][2], const float* pa, const float* pb) {
+    f32x4 av[2], bv[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        av[i] = *reinterpret_cast<const f32x4*>(pa + 16 * i * kSacPanelStride);
+        bv[i] = *reinterpret_cast<const f32x4*>(pb + 16 * i * kSacPanelStride);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            c0[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][0], bv[j][0], c0[i][j], 0, 0, 0);
+            c1[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][1], bv[j][1], c1[i][j], 0, 0, 0);
+            c0[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][2], bv[j][2], c0[i][j], 0, 0, 0);
+            c1[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][3], bv[j][3], c1[i][j], 0, 0, 0);
+        }
+    }
+}
+
+// One segment's share of the block, chunk by chunk.  <kMA, kMB> = the modes of a segment whose whole chunks may be loaded by
+// sac_panel_fetch_whole (its ragged last chunk, if any, goes through sac_panel_fetch); <kStageScalar, kStageScalar> = any segment, every
+// chunk through sac_panel_fetch.  The instances exist so that the loop of the frequent mode pairs is straight code: with the modes
+// tested inside the loop the compiler joined the paths' pending loads and waited for each before it issued the next.
+template <int kMA, int kMB>
+__device__ __forceinline__ void sac_block_segment(f32x4 (&c0)[2][2], f32x4 (&c1)[2][2], float* sA, float* sB, const SacPanelSrc& A,
+                                                  const SacPanelSrc& B, int tid, int off_a, int off_b) {
+    constexpr bool kWhole = kMA != kStageScalar;
+    const int K = A.K, ma = kWhole ? kMA : A.mode, mb = kWhole ? kMB : B.mode;
+    if (K <= 0) return;
+    f32x4 fa[2], fb[2];
+    auto fetch = [&](int k0) {
+        if (kWhole && k0 + kSacChunk <= K) {
+            sac_panel_fetch_whole<kMA>(fa, A, k0, tid);
+            sac_panel_fetch_whole<kMB>(fb, B, k0, tid);
+        } else {
+            sac_panel_fetch(fa, A, k0, tid);
+            sac_panel_fetch(fb, B, k0, tid);
+        }
+    };
+    auto stage = [&](int buf) {
+        sac_panel_store(sA + buf * kSacPanelFloats, fa, A, ma, tid);
+        sac_panel_store(sB + buf * kSacPanelFloats, fb, B, mb, tid);
+    };
+    fetch(0);
+    stage(0);
+    __syncthreads();
+    for (int k0 = 0, buf = 0; k0 < K; k0 += kSacChunk, buf ^= 1) {
+        const bool more = k0 + kSacChunk < K;
+        if (more) fetch(k0 + kSacChunk);  // the next chunk travels while this one is multiplied
+        const float* pa = sA + buf * kSacPanelFloats + off_a;
+        const float* pb = sB + buf * kSacPanelFloats + off_b;
+        sac_block_kstep(c0, c1, pa, pb);
+        if (K - k0 > 16) sac_block_kstep(c0, c1, pa + 16, pb + 16);  // (a second half past K is no k-block of the tile kernel's)
+        if (more) stage(buf ^ 1);
+        __syncthreads();  // (the last one: the next segment may fill buffer 0)
+    }
+}
+
+__global__ __launch_bounds__(kSacThreads) void sac_mm_blocked_kernel(const SacMmArgs a) {
+    __shared__ __attribute__((aligned(16))) float sA[2 * kSacPanelFloats];
+    __shared__ __attribute__((aligned(16))) float sB[2 * kSacPanelFloats];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
+    const int b = blockIdx.x;
+    int pi = 0;
+    while (pi + 1 < a.np && b >= a.block_start[pi + 1]) ++pi;
+    const SacProblem& p = a.p[pi];
+    const int lb = b - a.block_start[pi];
+    const int bm0 = block_m0(lb, p.blocks_n), bn0 = block_n0(lb, p.blocks_n);
+    const int wm = block_wave_m0(wave), wn = block_wave_n0(wave);
+    const int off_a = (wm + r) * kSacPanelStride + 4 * q, off_b = (wn + r) * kSacPanelStride + 4 * q;
+    f32x4 c0[2][2], c1[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) c0[i][j] = c1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int si = 0; si < p.nseg; ++si) {
+        const SacSeg& s = p.s[si];
+        const SacPanelSrc A = sac_panel_src(s.A, s.sam, s.sak, p.M, bm0, s.K), B = sac_panel_src(s.B, s.sbn, s.sbk, p.N, bn0, s.K);
+        // the pairs of an update: forward products (k, k), the dz chains (k, columns), the dW products (rows, columns) inside M and N
+        const bool rows_a = A.mode == kStageRow && bm0 + kBlock <= p.M, cols_b = B.mode == kStageRow && bn0 + kBlock <= p.N;
+        if (A.mode == kStageK && B.mode == kStageK)
+            sac_block_segment<kStageK, kStageK>(c0, c1, sA, sB, A, B, tid, off_a, off_b);
+        else if (A.mode == kStageK && cols_b)
+            sac_block_segment<kStageK, kStageRow>(c0, c1, sA, sB, A, B, tid, off_a, off_b);
+        else if (rows_a && cols_b)
+            sac_block_segment<kStageRow, kStageRow>(c0, c1, sA, sB, A, B, tid, off_a, off_b);
+        else
+            sac_block_segment<kStageScalar, kStageScalar>(c0, c1, sA, sB, A, B, tid, off_a, off_b);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int m0 = bm0 + wm + 16 * i, n0 = bn0 + wn + 16 * j;
+            if (m0 < p.M && n0 < p.N) sac_tile_epilogue(a, p, c0[i][j], c1[i][j], m0, n0, lane);
         }
     }
 }
@@ -369,6 +564,8 @@ struct SacLaunch {
         p.M = M; p.N = N; p.out = out; p.ldo = ldo; p.aux = aux;
         p.tiles_n = tiles_across(N);
         a.tile_start[a.np + 1] = a.tile_start[a.np] + tiles_across(M) * p.tiles_n;
+        p.blocks_n = blocks_across(N);
+        a.block_start[a.np + 1] = a.block_start[a.np] + blocks_across(M) * p.blocks_n;
         ++a.np;
         return p;
     }
@@ -383,9 +580,13 @@ struct SacLaunch {
         SacProblem& p = add(s0, M, N, param, N);
         p.m = m; p.v = v; p.target = target;
     }
-    void go(hipStream_t st) {
+    // one launch of the table on the engine's product kernel (hipets_set_sac_product)
+    void go(hipStream_t st, int product) {
         const int tiles = a.tile_start[a.np];
-        hipLaunchKernelGGL(sac_mm_kernel, dim3((unsigned)((tiles + kSacWaves - 1) / kSacWaves)), dim3(kSacThreads), 0, st, a);
+        if (product == HIPETS_SAC_PRODUCT_BLOCKED)
+            hipLaunchKernelGGL(sac_mm_blocked_kernel, dim3((unsigned)a.block_start[a.np]), dim3(kSacThreads), 0, st, a);
+        else
+            hipLaunchKernelGGL(sac_mm_kernel, dim3((unsigned)((tiles + kSacWaves - 1) / kSacWaves)), dim3(kSacThreads), 0, st, a);
     }
 };
 
@@ -468,6 +669,7 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
     const hipets::SacBind& sb = e->sac;
+    const int product = e->sac_product;
     const TransitionLayout row(sb.obs, sb.act, 0);  // (the batch's rows: no area)
     const int B = batch_size, O = sb.obs, A = sb.act, H = sb.hid, K1 = O + A, W = row.width;
     const size_t BH = (size_t)B * H;
@@ -486,18 +688,18 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
         SacLaunch l(kEpiBiasRelu);
         l.add(seg(s2, W, 1, P[kPol + 0], 1, O, O), B, H, ws.ph1, H, P[kPol + 1]);
         l.add(seg(s, W, 1, P[kPol + 0], 1, O, O), B, H, ws.ph1 + BH, H, P[kPol + 1]);
-        l.go(st);
+        l.go(st, product);
     }
     {
         SacLaunch l(kEpiBiasRelu);
         l.add(seg(ws.ph1, H, 1, P[kPol + 2], 1, H, H), 2 * B, H, ws.ph2, H, P[kPol + 3]);
-        l.go(st);
+        l.go(st, product);
     }
     {
         SacLaunch l(kEpiBias);
         l.add(seg(ws.ph2, H, 1, P[kPol + 4], 1, H, H), 2 * B, A, ws.mean, A, P[kPol + 5]);
         l.add(seg(ws.ph2, H, 1, P[kPol + 6], 1, H, H), 2 * B, A, ws.lstd, A, P[kPol + 7]);
-        l.go(st);
+        l.go(st, product);
     }
     {
         SacPolicyTailArgs t{ws.mean, ws.lstd, eps_next, eps_cur, P[kScale], P[kBias], ws.act, ws.tanh_x, ws.sech2_x, ws.log_pi, B, A};
@@ -513,7 +715,7 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
             const SacSeg action = j < 2 ? seg(ws.act, A, 1, N[0] + O, 1, K1, A) : seg(batch + row.c_act, W, 1, N[0] + O, 1, K1, A);
             l.add2(state, action, B, H, ws.qh1 + j * BH, H, N[1]);
         }
-        l.go(st);
+        l.go(st, product);
     }
     {
         SacLaunch l(kEpiBiasRelu);
@@ -521,7 +723,7 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
             float* const* N = q_net(P, j);
             l.add(seg(ws.qh1 + j * BH, H, 1, N[2], 1, H, H), B, H, ws.qh2 + j * BH, H, N[3]);
         }
-        l.go(st);
+        l.go(st, product);
     }
     SacQTailArgs qt{};
     qt.h2 = ws.qh2; qt.batch = batch; qt.log_pi = ws.log_pi; qt.alpha = P[kAlpha];
@@ -542,7 +744,7 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
         SacLaunch l(kEpiMask);
         for (int i = 0; i < 2; ++i)
             l.add(seg(ws.dz2 + i * BH, H, 1, P[kCrit + 6 * i + 2], H, 1, H), B, H, ws.dz1 + i * BH, H, ws.qh1 + (2 + i) * BH);
-        l.go(st);
+        l.go(st, product);
     }
     {
         SacLaunch l(kEpiAdam);
@@ -563,7 +765,7 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
             l.adam(seg(dq, 0, 1, ws.qh2 + (2 + i) * BH, H, 1, B), 1, H, N[4], M[4], V[4], T[4]);
             l.adam(seg(dq, 0, 1, one, 0, 0, B), 1, 1, N[5], M[5], V[5], T[5]);
         }
-        l.go(st);
+        l.go(st, product);
     }
     // ---- 4. the policy's gradient through the updated critic ----
     {
@@ -572,12 +774,12 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
             float* const* N = P + kCrit + 6 * j;
             l.add2(seg(s, W, 1, N[0], 1, K1, O), seg(pi, A, 1, N[0] + O, 1, K1, A), B, H, ws.qh1 + j * BH, H, N[1]);
         }
-        l.go(st);
+        l.go(st, product);
     }
     {
         SacLaunch l(kEpiBiasRelu);
         for (int j = 0; j < 2; ++j) l.add(seg(ws.qh1 + j * BH, H, 1, P[kCrit + 6 * j + 2], 1, H, H), B, H, ws.qh2 + j * BH, H, P[kCrit + 6 * j + 3]);
-        l.go(st);
+        l.go(st, product);
     }
     {
         for (int j = 0; j < 2; ++j) {
@@ -590,12 +792,12 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
     {
         SacLaunch l(kEpiMask);
         for (int i = 0; i < 2; ++i) l.add(seg(ws.dz2 + i * BH, H, 1, P[kCrit + 6 * i + 2], H, 1, H), B, H, ws.dz1 + i * BH, H, ws.qh1 + i * BH);
-        l.go(st);
+        l.go(st, product);
     }
     {
         SacLaunch l(kEpiStore);  // d pi = dz1_1 W1_1[:, obs:] + dz1_2 W1_2[:, obs:]: no weight gradients in this pass
         l.add2(seg(ws.dz1, H, 1, P[kCrit + 0] + O, K1, 1, H), seg(ws.dz1 + BH, H, 1, P[kCrit + 6] + O, K1, 1, H), B, A, ws.d_pi, A);
-        l.go(st);
+        l.go(st, product);
     }
     {
         SacPolicyBwdArgs t{ws.lstd + (size_t)B * A, ws.tanh_x + (size_t)B * A, ws.sech2_x + (size_t)B * A, eps_cur, P[kScale], ws.d_pi, P[kAlpha], ws.d_mean, ws.d_lstd, B, A};
@@ -605,12 +807,12 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
     {
         SacLaunch l(kEpiMask);
         l.add2(seg(ws.d_mean, A, 1, P[kPol + 4], H, 1, A), seg(ws.d_lstd, A, 1, P[kPol + 6], H, 1, A), B, H, ws.pdh2, H, ph2s);
-        l.go(st);
+        l.go(st, product);
     }
     {
         SacLaunch l(kEpiMask);
         l.add(seg(ws.pdh2, H, 1, P[kPol + 2], H, 1, H), B, H, ws.pdh1, H, ph1s);
-        l.go(st);
+        l.go(st, product);
     }
     {
         SacLaunch l(kEpiAdam);
@@ -626,7 +828,7 @@ int hipets_sac_update(hipets_engine* e, const float* batch, int32_t batch_size, 
         l.adam(seg(ws.d_mean, 1, A, one, 0, 0, B), A, 1, N[5], M[5], V[5], nullptr);
         l.adam(seg(ws.d_lstd, 1, A, ph2s, H, 1, B), A, H, N[6], M[6], V[6], nullptr);
         l.adam(seg(ws.d_lstd, 1, A, one, 0, 0, B), A, 1, N[7], M[7], V[7], nullptr);
-        l.go(st);
+        l.go(st, product);
     }
     // ---- 5. the alpha step and the result slot ----
     {

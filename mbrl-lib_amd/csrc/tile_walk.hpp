@@ -21,4 +21,14 @@ __device__ __forceinline__ int tile_n0(int t, int tn) { return (t % tn) << 4; }
 __device__ __forceinline__ int tile_col(int n0, int lane) { return n0 + (lane & 15); }
 __device__ __forceinline__ int tile_row(int m0, int lane, int i) { return m0 + 4 * (lane >> 4) + i; }
 
+// The blocked product of sac.hip (sac_mm_blocked_kernel) deals 64 x 64 blocks of 4 x 4 tiles to workgroups, numbered like the tiles:
+// block b of a result that is bn blocks wide, in row-major block order.  Wave w of the workgroup owns the 2 x 2 tiles at rows
+// 32 (w >> 1), columns 32 (w & 1) of the block.
+constexpr int kBlock = 64;
+__host__ __device__ __forceinline__ int blocks_across(int n) { return (n + kBlock - 1) / kBlock; }
+__device__ __forceinline__ int block_m0(int b, int bn) { return (b / bn) * kBlock; }
+__device__ __forceinline__ int block_n0(int b, int bn) { return (b % bn) * kBlock; }
+__device__ __forceinline__ int block_wave_m0(int wave) { return (wave >> 1) << 5; }
+__device__ __forceinline__ int block_wave_n0(int wave) { return (wave & 1) << 5; }
+
 }  // namespace hipets

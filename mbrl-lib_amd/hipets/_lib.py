@@ -52,6 +52,7 @@ TRAIN_MAX_MEMBERS, TRAIN_MAX_HID, TRAIN_MAX_IN, TRAIN_MAX_OUT, TRAIN_MAX_BATCH =
 TRAIN_KERNEL = {"member": 0, "split": 1}  # HIPETS_TRAIN_KERNEL_*
 TRAIN_SPLIT_MAX_BATCH = 1024  # HIPETS_TRAIN_SPLIT_MAX_BATCH
 SAC_N_PTRS, SAC_MAX_BATCH = 78, 1024  # HIPETS_SAC_N_PTRS, HIPETS_SAC_MAX_BATCH
+SAC_PRODUCT = {"tile": 0, "blocked": 1}  # HIPETS_SAC_PRODUCT_*
 CRITIC_N_PTRS = 12  # HIPETS_CRITIC_N_PTRS
 ENSEMBLE_MAX_MEMBERS, ENSEMBLE_MAX_IN, ENSEMBLE_MAX_OUT = 16, 512, 512  # HIPETS_ENSEMBLE_MAX_*
 ENSEMBLE_STATS = ("max_std", "disagreement", "total_std", "max_deviation")  # columns of hipets_ensemble_predict's stats
@@ -252,6 +253,7 @@ SYMBOLS = {
     "hipets_sac_update": _sig("e batch batch_size:i32 eps_next eps_cur update_index:i64 step_critic:i64 step_policy:i64 step_alpha:i64 "
                               "lr_critic:f64 lr_policy:f64 lr_alpha:f64 result stream"),
     "hipets_sac_forward_taps": _sig("e batch_size:i32 q1 q2 y log_pi_next log_pi stream"),
+    "hipets_set_sac_product": _sig("e kind:i32"),
     "hipets_critic_set": _sig("e obs_dim:i32 act_dim:i32 hidden:i32 ptrs n_ptrs:i32 stream"),
     "hipets_critic_q": _sig("e obs actions batch:i32 q1 q2 qmin stream"),
     "hipets_critic_geometry": _sig("e batch:i32 row_tiles:i32* lds_bytes:i32*"),

@@ -815,10 +815,15 @@ class Engine:
                         adam=adam.ctypes.data_as(C.POINTER(C.c_double)), ptrs=ptrs, n_ptrs=int(ptrs.size))
         self.sac_dims = tuple(int(v) for v in dims)
 
-    def sac_update(self, batch: torch.Tensor, eps_next: torch.Tensor, eps_cur: torch.Tensor, update_index: int, steps, lrs, result: torch.Tensor):
+    def sac_update(self, batch: torch.Tensor, eps_next: torch.Tensor, eps_cur: torch.Tensor, update_index: int, steps, lrs, result: torch.Tensor,
+                   *, product: str = "tile"):
         """One SAC update on the bound agent (hipets_sac_update), asynchronous on the current stream.  ``batch`` f32 [B, 2 obs + act + 2]
         (state, action, next_state, reward, mask), ``eps_next`` / ``eps_cur`` f32 [B, act], ``steps`` / ``lrs`` = the Adam steps taken
-        before and the learning rates of (critic, policy, alpha), ``result`` f32 [8] -- all device tensors but the scalars."""
+        before and the learning rates of (critic, policy, alpha), ``result`` f32 [8] -- all device tensors but the scalars.
+        ``product``: "tile" (a 16 x 16 tile per wave) or "blocked" (64 x 64 blocks staged through LDS) runs the update's products: the
+        same bits, another speed.  The engine's setting (hipets_set_sac_product) is set for the call and put back."""
+        if product not in _lib.SAC_PRODUCT:
+            raise ValueError("product must be 'tile' or 'blocked'")
         obs, act, _ = self._slot_dims("sac", "sac_bind")
         if not isinstance(batch, torch.Tensor) or batch.ndim != 2:
             raise ValueError("batch must be a [B, 2 obs + act + 2] tensor")
@@ -827,9 +832,15 @@ class Engine:
         _check_dev(eps_next, torch.float32, self.device, "eps_next", (B, act))
         _check_dev(eps_cur, torch.float32, self.device, "eps_cur", (B, act))
         _check_dev(result, torch.float32, self.device, "result", numel=8)
-        self._call("hipets_sac_update", batch=batch, batch_size=B, eps_next=eps_next, eps_cur=eps_cur, update_index=int(update_index),
-                   step_critic=int(steps[0]), step_policy=int(steps[1]), step_alpha=int(steps[2]), lr_critic=float(lrs[0]),
-                   lr_policy=float(lrs[1]), lr_alpha=float(lrs[2]), result=result)
+        if product != "tile":
+            self._query("hipets_set_sac_product", kind=_lib.SAC_PRODUCT[product])
+        try:
+            self._call("hipets_sac_update", batch=batch, batch_size=B, eps_next=eps_next, eps_cur=eps_cur, update_index=int(update_index),
+                       step_critic=int(steps[0]), step_policy=int(steps[1]), step_alpha=int(steps[2]), lr_critic=float(lrs[0]),
+                       lr_policy=float(lrs[1]), lr_alpha=float(lrs[2]), result=result)
+        finally:
+            if product != "tile":
+                self._query("hipets_set_sac_product", kind=_lib.SAC_PRODUCT["tile"])
         # the update kernels write the agent's parameters through raw pointers (no tensor's _version moves): snapshots of the actor or
         # the critic compare this counter (hipets.sac)
         self.sac_updates += 1

@@ -229,6 +229,21 @@ def _adam_state(opt, params):
     return ms, vs, steps
 
 
+SAC_PRODUCTS = ("tile", "blocked", "auto")
+# product="auto": the blocked kernel from this hidden width on, the smallest measured width at which its launch sequence took less time
+# than the tile kernel's with ranges that do not overlap (it won at 1024 and lost at 256 and 512); None = it won at no measured width
+SAC_BLOCKED_MIN_HIDDEN = 1024
+
+
+def sac_product_for(product: str, hidden: int) -> str:
+    """The kernel ("tile" or "blocked") that runs the products of an agent ``hidden`` wide under ``product`` ("tile", "blocked" or "auto")."""
+    if product not in SAC_PRODUCTS:
+        raise ValueError(f"product must be one of {SAC_PRODUCTS}, not {product!r}")
+    if product != "auto":
+        return product
+    return "blocked" if SAC_BLOCKED_MIN_HIDDEN is not None and int(hidden) >= SAC_BLOCKED_MIN_HIDDEN else "tile"
+
+
 class SACUpdater(_SlotOwner):
     """``SAC.update_parameters`` (pytorch_sac_pranz24/sac.py:76-173) on the update kernels (hipets_sac_update): same signature, same
     5-tuple.  ``agent``: an ``mbrl.planning.SACAgent``, a ``pytorch_sac_pranz24.SAC`` or an object shaped like one (policy, critic,
@@ -242,10 +257,14 @@ class SACUpdater(_SlotOwner):
     tables of an update are drawn by torch on the device as ``Normal.rsample`` draws them, next-state table first.
 
     Raises UnsupportedModelError for what the kernels do not cover (a DeterministicPolicy, modules off the engine's device, Adam
-    settings other than the plain ones, sizes past the HIPETS_POLICY_MAX_* limits, a batch outside 1 .. 1024)."""
+    settings other than the plain ones, sizes past the HIPETS_POLICY_MAX_* limits, a batch outside 1 .. 1024).
+
+    ``product``: the kernel behind the update's matrix products -- "tile" (the default: a 16 x 16 tile per wave), "blocked" (64 x 64
+    blocks staged through LDS; the same results bit for bit) or "auto" (:func:`sac_product_for` picks by the hidden width)."""
     slot = "sac"
 
-    def __init__(self, agent, engine=None, batch_size: Optional[int] = None):
+    def __init__(self, agent, engine=None, batch_size: Optional[int] = None, product: str = "tile"):
+        sac_product_for(product, 0)  # (ValueError for an unknown name, whatever the agent)
         sac = getattr(agent, "sac_agent", agent)
         missing = [n for n in _SAC_ATTRS if not hasattr(sac, n)]
         if missing:
@@ -256,6 +275,7 @@ class SACUpdater(_SlotOwner):
             raise UnsupportedModelError("automatic_entropy_tuning without log_alpha / alpha_optim / target_entropy")
         (obs, hid, act), pol = pack_policy(sac.policy)  # (a DeterministicPolicy has no heads: UnsupportedModelError)
         self.dims = (obs, act, hid)
+        self.product = sac_product_for(product, hid)
         self.check_batch(batch_size)
         for net, name in ((sac.critic, "critic"), (sac.critic_target, "critic_target")):
             try:
@@ -421,7 +441,7 @@ class SACUpdater(_SlotOwner):
                     eps_cur = torch.empty(B, act, dtype=torch.float32, device=dev).normal_()
                 group, slot = where[i]
                 self.engine.sac_update(batch[slot] if group is None else group[2][slot], eps_next, eps_cur, int(first_update) + i,
-                                       [s + i for s in step0], lrs, results[i])
+                                       [s + i for s in step0], lrs, results[i], product=self.product)
             host_res.copy_(results, non_blocking=True)
             torch.cuda.current_stream(dev).synchronize()
         for group in steps:
@@ -461,11 +481,13 @@ class ReferenceSACUpdater:
         return [self.update_parameters(m, batch_size, int(first_update) + i, logger, reverse_mask) for i, m in enumerate(memories)]
 
 
-def make_sac_updater(agent, engine=None, batch_size: Optional[int] = None):
+def make_sac_updater(agent, engine=None, batch_size: Optional[int] = None, product: str = "tile"):
     """A :class:`SACUpdater` for ``agent`` where the update kernels cover it; otherwise -- with ONE warning that names the reason --
-    an object whose ``update_parameters`` is the agent's own (and whose ``update_many`` loops over it)."""
+    an object whose ``update_parameters`` is the agent's own (and whose ``update_many`` loops over it).  ``product`` as
+    :class:`SACUpdater` takes it (an unknown name raises ValueError either way)."""
+    sac_product_for(product, 0)
     try:
-        return SACUpdater(agent, engine=engine, batch_size=batch_size)
+        return SACUpdater(agent, engine=engine, batch_size=batch_size, product=product)
     except UnsupportedModelError as exc:
         warnings.warn(f"hipets.make_sac_updater: running the agent's own update_parameters ({exc})", stacklevel=2)
         return ReferenceSACUpdater(agent)

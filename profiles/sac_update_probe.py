@@ -123,6 +123,56 @@ def measure_shape(engine, dev, shape, reps):
     return res, (sac_t, sac_h, up, memory)
 
 
+def spread(ms):
+    ms = sorted(ms)
+    return {"median_ms": float(np.median(ms)), "min_ms": ms[0], "max_ms": ms[-1], "n": len(ms)}
+
+
+def interleaved(engine, dev, shape, rounds, products=("tile", "blocked"), torch_route=True):
+    """The product routes take turns in one process over the same replay rows, batches and normal tables: per round and route 3 warm-up
+    calls of its own, then one timed sample of each quantity -- the 19 launches alone (device events around 20 queued updates) and
+    update_many per update (a host clock around a call that ends in a device -> host copy).  Median with min and max over the rounds,
+    per update.  The stock torch route, as measure_shape has it, takes its turn in every round too."""
+    obs, act, hid, B = shape
+    memory = ReplayBuffer(100_000, obs, act, np.random.default_rng(0))
+    torch.manual_seed(0)
+    ups = {pr: hipets.SACUpdater(sr.TinySAC(obs, act, hid, device=dev), engine=engine, product=pr) for pr in products}
+    sac_t = sr.TinySAC(obs, act, hid, device=dev)
+    batch = torch.from_numpy(np.stack([mbpo.pack_sac_batch(memory.sample(B).astuple(), True) for _ in range(N_UPDATES)])).to(dev)
+    eps = torch.randn(N_UPDATES, 2, B, act, device=dev)
+    result = torch.empty(N_UPDATES, 8, device=dev)
+    count, steps = [0], {pr: 0 for pr in products}
+
+    def launches(pr):
+        ups[pr]._bind()
+        for i in range(N_UPDATES):
+            engine.sac_update(batch[i], eps[i, 0], eps[i, 1], i, (steps[pr],) * 3, (3e-4, 3e-4, 3e-4), result[i], product=pr)
+            steps[pr] += 1
+
+    def many(pr):
+        ups[pr].update_many([memory] * N_UPDATES, B, count[0], None, reverse_mask=True)
+        count[0] += N_UPDATES
+
+    def stock():
+        for _ in range(N_UPDATES):
+            sac_t.update_parameters(memory, B, count[0], None, reverse_mask=True)
+            count[0] += 1
+
+    out = {"launch_sequence_device_per_update": {pr: [] for pr in products}, "update_many_20_per_update": {pr: [] for pr in products},
+           "torch_update_parameters": []}
+    for _ in range(rounds):
+        for pr in products:
+            out["launch_sequence_device_per_update"][pr].append(pp.events(lambda: launches(pr), 1)["median_ms"] / N_UPDATES)
+            out["update_many_20_per_update"][pr].append(pp.wall(lambda: many(pr), 1)["median_ms"] / N_UPDATES)
+        if torch_route:
+            out["torch_update_parameters"].append(pp.wall(stock, 1)["median_ms"] / N_UPDATES)
+    res = {"shape": dict(obs=obs, act=act, hidden=hid, batch=B), "rounds": rounds,
+           "torch_update_parameters": spread(out["torch_update_parameters"]) if torch_route else None}
+    for key in ("launch_sequence_device_per_update", "update_many_20_per_update"):
+        res[key] = {pr: spread(v) for pr, v in out[key].items()}
+    return res
+
+
 def iteration_share(engine, dev, agents, reps):
     """populate at rollout length 1 (100 000 rows) + 20 updates at the mbpo_halfcheetah shape: the update loop's share, both routes"""
     sac_t, sac_h, up, memory = agents
@@ -159,10 +209,28 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sac_update.json"))
     ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--product", choices=("tile", "blocked", "interleaved"), default="tile",
+                    help="the product kernel of the hipets route; 'interleaved': tile and blocked take turns (writes profiles/sac_blocked.json)")
+    ap.add_argument("--rounds", type=int, default=7, help="rounds of the interleaved mode")
+    ap.add_argument("--shapes", nargs="*", default=None, help="interleaved mode: a subset of the shapes")
     args = ap.parse_args()
     assert torch.cuda.is_available(), "this probe measures on the GPU: no GPU, no numbers"
     dev = torch.device("cuda:0")
     engine = hipets.get_engine(dev)
+    if args.product != "tile":
+        # one route alone (for a kernel trace of its own: no torch route, no host shares), or both taking turns
+        shapes = dict(SHAPES, hidden_256=(17, 6, 256, 256))
+        alone = args.product == "blocked"
+        out = os.path.join(ROOT, "profiles", "sac_blocked.json") if args.out == ap.get_default("out") else args.out
+        res = {"device": torch.cuda.get_device_name(0), "rounds": args.rounds, "updates_per_call": N_UPDATES, "shapes": {}}
+        for name in args.shapes or shapes:
+            res["shapes"][name] = interleaved(engine, dev, shapes[name], args.rounds, ("blocked",) if alone else ("tile", "blocked"), not alone)
+        if not alone:
+            os.makedirs(os.path.dirname(os.path.abspath(out)), exist_ok=True)
+            with open(out, "w") as f:
+                json.dump(res, f, indent=1)
+        print(json.dumps(res, indent=1))
+        return
     res = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "updates_per_many_call": N_UPDATES,
            "torch_route": "tests/sac_restatement.TinySAC.update_parameters (sac.py:76-173's op sequence, torch.optim.Adam)", "shapes": {}}
     keep = None
