@@ -1,4 +1,5 @@
-// common.hpp -- device helpers shared by the rollout and optimizer kernels (gfx950 only).
+// common.hpp -- device helpers shared by the rollout, optimizer and learning kernels (gfx950 only): the vector types and the fp32 MFMA
+// of the compiler's builtin, the random streams.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -7,6 +8,13 @@
 namespace hipets {
 
 using f32x4 = __attribute__((ext_vector_type(4))) float;
+using f32x2 = __attribute__((ext_vector_type(2))) float;
+typedef f32x4 f32x4u __attribute__((aligned(4)));  // dword-aligned vector loads: a row of W starts wherever din x dout puts it
+typedef f32x2 f32x2u __attribute__((aligned(4)));
+
+// c += a b on one 16 x 16 tile over four k: v_mfma_f32_16x16x4_f32 through the builtin (train.hip, train_split.hip, sac.hip; the rollout
+// kernels issue theirs from inline asm, gemm_f32.hpp)
+__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // Build switches of the kernel experiments that were measured and settled: the arms they selected were
 // removed with them and are in the version history.  A build that still names one would silently produce the default kernel and

@@ -87,10 +87,10 @@ __device__ __forceinline__ void sac_seg_acc(f32x4& c0, f32x4& c1, const SacSeg& 
         const int k = k0 + 4 * q;
         const f32x4 a = sac_ld4(pa, s.sak, k, K, av, va);
         const f32x4 b = sac_ld4(pb, s.sbk, k, K, bv, vb);
-        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[0], b[0], c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[1], b[1], c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[2], b[2], c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a[3], b[3], c1, 0, 0, 0);
+        c0 = mfma4(a[0], b[0], c0);
+        c1 = mfma4(a[1], b[1], c1);
+        c0 = mfma4(a[2], b[2], c0);
+        c1 = mfma4(a[3], b[3], c1);
     }
 }
 
@@ -237,10 +237,10 @@ __device__ __forceinline__ void sac_block_kstep(f32x4 (&c0)[2][2], f32x4 (&c1)[2
     for (int i = 0; i < 2; ++i) {
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
-            c0[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][0], bv[j][0], c0[i][j], 0, 0, 0);
-            c1[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][1], bv[j][1], c1[i][j], 0, 0, 0);
-            c0[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][2], bv[j][2], c0[i][j], 0, 0, 0);
-            c1[i][j] = __builtin_amdgcn_mfma_f32_16x16x4f32(av[i][3], bv[j][3], c1[i][j], 0, 0, 0);
+            c0[i][j] = mfma4(av[i][0], bv[j][0], c0[i][j]);
+            c1[i][j] = mfma4(av[i][1], bv[j][1], c1[i][j]);
+            c0[i][j] = mfma4(av[i][2], bv[j][2], c0[i][j]);
+            c1[i][j] = mfma4(av[i][3], bv[j][3], c1[i][j]);
         }
     }
 }

@@ -3,16 +3,18 @@
 //   train_step_kernel  Model.update (mbrl/models/model.py:129-167) + torch.optim.Adam for a chunk of consecutive minibatches, one
 //                      instantiation per loss kind (NLL, MSE); a BasicEnsemble is per-member bounds and grad_scale = 1 / E
 //   train_eval_kernel  GaussianMLP.eval_score over the whole evaluation set (gaussian_mlp.py:337-361), mean columns only
-// Every product runs on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32 accumulate): mm_tile is the k-loop, tile_walk.hpp the tiles'
-// numbering and the lane-to-element map, adam.hpp the optimizer's rule.  The host side by job: train_check (the arguments),
-// train_slab and train_fill (train.hpp: the slab's layout, what the argument blocks share), train_chunk and the chunk loop.  Under
-// HIPETS_TRAIN_KERNEL_SPLIT the steps leave for train_split.hip behind the same checks; the elementwise helpers are train_math.hpp's.
+// Every product runs on v_mfma_f32_16x16x4_f32 (fp32 operands, fp32 accumulate; common.hpp's mfma4): mm_tile is the k-loop,
+// tile_walk.hpp the tiles' numbering and the lane-to-element map, adam.hpp the optimizer's rule, train_math.hpp the activations and
+// the MSE tail (mse_tail; the NLL tail and the Kahan sum stand here and in train_split.hip, see there).  The host side by job: train_check (the arguments), train_slab,
+// train_fill and train_fill_step (train.hpp: the slab's layout, what the argument blocks share), train_chunk and the chunk loop.
+// Under HIPETS_TRAIN_KERNEL_SPLIT the steps leave for train_split.hip behind the same checks.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cmath>
 #include <type_traits>
 
+#include "common.hpp"
 #include "engine.hpp"
 #include "lds_optin.hpp"
 #include "tile_walk.hpp"
@@ -23,8 +25,6 @@
 namespace hipets {
 
 namespace {
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // One 16 x 16 tile of C = A . B (M x K by K x N), element (i, k) of A at A[i * sam + k * sak], (k, j) of B at B[k * sbk + j * sbn].
 // Lane l feeds A[m0 + (l & 15)][k + (l >> 4)] and B[k + (l >> 4)][n0 + (l & 15)]; the result lies as tile_walk.hpp says.
@@ -51,10 +51,10 @@ __device__ __forceinline__ f32x4 mm_tile(const float* __restrict__ A, int sam, i
     for (; kDeep && k0 + 16 <= K; k0 += 16) {
         const float a0 = av ? *a0p : 0.f, a1 = av ? *a1p : 0.f, a2 = av ? *a2p : 0.f, a3 = av ? *a3p : 0.f;
         const float b0 = bv ? *b0p : 0.f, b1 = bv ? *b1p : 0.f, b2 = bv ? *b2p : 0.f, b3 = bv ? *b3p : 0.f;
-        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, c1, 0, 0, 0);
-        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a2, b2, c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a3, b3, c1, 0, 0, 0);
+        c0 = mfma4(a0, b0, c0);
+        c1 = mfma4(a1, b1, c1);
+        c0 = mfma4(a2, b2, c0);
+        c1 = mfma4(a3, b3, c1);
         a0p += 4 * sa4; a1p += 4 * sa4; a2p += 4 * sa4; a3p += 4 * sa4;
         b0p += 4 * sb4; b1p += 4 * sb4; b2p += 4 * sb4; b3p += 4 * sb4;
     }
@@ -62,13 +62,13 @@ __device__ __forceinline__ f32x4 mm_tile(const float* __restrict__ A, int sam, i
         const int ka = k0 + q, kb = k0 + 4 + q;
         const float a0 = av ? pa[(int64_t)ka * sak] : 0.f, b0 = bv ? pb[(int64_t)ka * sbk] : 0.f;
         const float a1 = av ? pa[(int64_t)kb * sak] : 0.f, b1 = bv ? pb[(int64_t)kb * sbk] : 0.f;
-        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, c0, 0, 0, 0);
-        c1 = __builtin_amdgcn_mfma_f32_16x16x4f32(a1, b1, c1, 0, 0, 0);
+        c0 = mfma4(a0, b0, c0);
+        c1 = mfma4(a1, b1, c1);
     }
     for (; k0 < K; k0 += 4) {
         const int k = k0 + q;
         const float a0 = (av && k < K) ? pa[(int64_t)k * sak] : 0.f, b0 = (bv && k < K) ? pb[(int64_t)k * sbk] : 0.f;
-        c0 = __builtin_amdgcn_mfma_f32_16x16x4f32(a0, b0, c0, 0, 0, 0);
+        c0 = mfma4(a0, b0, c0);
     }
     return c0 + c1;
 }
@@ -136,12 +136,11 @@ __global__ __launch_bounds__(kTrainThreads) void train_step_kernel(const TrainSt
         if constexpr (kLoss == kTrainLossMSE) {
             // ---- MSE tail (gaussian_mlp.py:283-289): the plain sum of squared errors; O and D are [nb, out] ----
             for (int t = tid; t < nb * out; t += kTrainThreads) {
-                const float d = O[t] - T[t];
-                lsum += (acc_t)d * (acc_t)d;
-                D[t] = 2.f * d * a.grad_scale;
+                mse_tail(O[t], T[t], a.grad_scale, lsum, D[t]);
             }
         } else {
-            // ---- NLL tail (gaussian_mlp.py:143-153, 291-305; util/math.py:41-64) and its gradient w.r.t. O ----
+            // ---- NLL tail (gaussian_mlp.py:143-153, 291-305; util/math.py:41-64) and its gradient w.r.t. O: the lines of
+            // train_rows_kernel (train_split.hip), operation for operation (train_math.hpp: why not a function) ----
             const float scale = 1.f / (float)(nb * out) * a.grad_scale;  // mean over batch and output dims (times 1 / E: BasicEnsemble.loss)
             const float* mxv = a.max_logvar + (int64_t)e * a.bounds_stride;
             const float* mnv = a.min_logvar + (int64_t)e * a.bounds_stride;
@@ -442,21 +441,10 @@ int hipets_train_steps_loss(hipets_engine* e, const hipets_train_desc* d, const 
     TrainStepArgs a{};
     const int L = d->n_layers, E = d->ensemble_size, Bm = d->max_batch;
     train_fill(a, d, loss_kind, x, y, n_rows);
+    train_fill_step(a, d, bounds_per_member, grad_scale);
     a.at = train_slab(a.dims, L, d->out_dim, Bm);
     if (e->train_slab.ensure((size_t)E * a.at.stride * sizeof(float))) return 1;
     a.slab = e->train_slab.as<float>();
-    for (int l = 0; l < L; ++l) {
-        a.mw[l] = static_cast<float*>(d->exp_avg_w[l]);
-        a.mb[l] = static_cast<float*>(d->exp_avg_b[l]);
-        a.vw[l] = static_cast<float*>(d->exp_avg_sq_w[l]);
-        a.vb[l] = static_cast<float*>(d->exp_avg_sq_b[l]);
-    }
-    a.min_logvar = d->min_logvar;
-    a.max_logvar = d->max_logvar;
-    a.bounds_stride = bounds_per_member ? d->out_dim : 0;
-    a.grad_scale = grad_scale;
-    a.max_batch = Bm;
-    a.weight_decay = (float)d->weight_decay;  // (a python float handed to a float32 tensor op: one rounding)
     a.adam = adam_scalars(d->lr, d->beta1, d->beta2, d->eps, step0 + 1);  // (the part no step changes)
     const int chunk = train_chunk(d, a.dims);
     for (int s0 = 0; s0 < n_steps; s0 += chunk) {

@@ -1,5 +1,6 @@
 // train.hpp -- GaussianMLP ensemble training (ModelTrainer.train / evaluate, mbrl/models/model_trainer.py:70-262): the limits, the
-// slab's layout and the kernel argument blocks of train.hip (its kernels and launchers, and its entry points of the C ABI).
+// slab's layout and the kernel argument blocks of train.hip (its kernels and launchers, and its entry points of the C ABI), and the
+// host fill of what the argument blocks share: train_fill (all three) and train_fill_step (the two step blocks, train_split.hpp's too).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -115,6 +116,23 @@ inline void train_fill(Args& a, const hipets_train_desc* d, int loss_kind, const
     a.ensemble_size = d->ensemble_size;
     a.activation = d->activation;
     a.leaky_slope = d->leaky_slope;
+}
+
+// what TrainStepArgs and TrainSplitArgs share beyond train_fill: the Adam state, the logvar bounds and their member stride, the scalars of a step
+template <class Args>
+inline void train_fill_step(Args& a, const hipets_train_desc* d, int32_t bounds_per_member, float grad_scale) {
+    for (int l = 0; l < d->n_layers; ++l) {
+        a.mw[l] = static_cast<float*>(d->exp_avg_w[l]);
+        a.mb[l] = static_cast<float*>(d->exp_avg_b[l]);
+        a.vw[l] = static_cast<float*>(d->exp_avg_sq_w[l]);
+        a.vb[l] = static_cast<float*>(d->exp_avg_sq_b[l]);
+    }
+    a.min_logvar = d->min_logvar;
+    a.max_logvar = d->max_logvar;
+    a.bounds_stride = bounds_per_member ? d->out_dim : 0;
+    a.grad_scale = grad_scale;
+    a.max_batch = d->max_batch;
+    a.weight_decay = (float)d->weight_decay;  // (a python float handed to a float32 tensor op: one rounding)
 }
 
 hipError_t launch_train_steps(const TrainStepArgs& a, int loss_kind, hipStream_t st);

@@ -1,5 +1,10 @@
 // train_math.hpp -- the elementwise device functions both training paths share (train.hip: one workgroup per member; train_split.hip:
-// the row-split step): GaussianMLP's activations and their derivatives, torch's softplus, a wave's sum.
+// the row-split step): GaussianMLP's activations and their derivatives, torch's softplus, the MSE tail of one output element with its
+// gradient (mse_tail), a wave's sum.  Plain functions, like tile_walk.hpp's and for its reason.  Not here, although both kernels of
+// either path hold the same lines: the NLL tail and the compensated (Kahan) sum of the MSE bias gradients.  As functions (value,
+// reference and pointer parameters were tried) they compiled to the same registers but to another instruction order in
+// train_step_kernel<NLL>, train_rows_kernel<NLL> and train_dw_kernel<MSE>, so each kernel keeps its copy and names the other
+// (DESIGN.md section 29).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -43,6 +48,14 @@ __device__ __forceinline__ float softplus_grad(float x) {
     if (x > 20.f) return 1.f;
     const float z = expf(x);
     return z / (z + 1.f);
+}
+
+// GaussianMLP._mse_loss on one output element (gaussian_mlp.py:283-289): the loss is a plain sum of squared errors, accumulated in
+// double (and rounded once per step)
+__device__ __forceinline__ void mse_tail(float o, float target, float grad_scale, double& loss_sum, float& d_out) {
+    const float d = o - target;
+    loss_sum += (double)d * (double)d;
+    d_out = 2.f * d * grad_scale;
 }
 
 template <class T>

@@ -9,13 +9,19 @@
 // activation panel; W^T of the dA product, whose rows are contiguous along k) as one 16-byte load of k .. k + 3 per lane -- lane group q
 // takes k0 + 4 q + s in MFMA s -- an n-contiguous one (W of the forward product, the dW panels) as one 8-byte load whose two values
 // belong to two tiles of interleaved columns.  No float atomics, no polling: every sum has one owner and a fixed order.
+// Shared with train.hip and sac.hip: the vector types and mfma4 (common.hpp), the activations and the MSE tail (train_math.hpp),
+// the 64 x 64 block walk of the dW kernel (tile_walk.hpp), the host fill of the argument block (train.hpp), Adam's rule (adam.hpp).
+// The k-loops, the dW kernel's fetch / stage / multiply chunk loop, the NLL tail and the Kahan sum are this file's own (DESIGN.md
+// section 29).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <type_traits>
 
+#include "common.hpp"
 #include "engine.hpp"
 #include "lds_optin.hpp"
+#include "tile_walk.hpp"
 #include "train_math.hpp"
 #include "train_split.hpp"
 
@@ -23,15 +29,8 @@ namespace hipets {
 
 namespace {
 
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-typedef f32x4 f32x4u __attribute__((aligned(4)));  // a row of W starts wherever din x dout puts it: dword-aligned vector loads
-typedef f32x2 f32x2u __attribute__((aligned(4)));
-
 constexpr int kRowsWaves = kSplitRowsThreads / 64;
 constexpr int kDwWaves = kSplitDwThreads / 64;
-
-__device__ __forceinline__ f32x4 mfma4(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
 
 // One block of 16 k-steps of a 32 x 32 result block: rows 0..15 / 16..31 of the panel (pa0 / pa1: the lane's row, k-contiguous, 16-byte
 // aligned) against 32 columns of B.  Lane (r, q) = (lane & 15, lane >> 4) holds k0 + 4 q + s in MFMA s, on both sides.
@@ -191,11 +190,10 @@ __global__ __launch_bounds__(kSplitRowsThreads) void train_rows_kernel(const Tra
             const int rr = t / out, j = t - rr * out;
             float* o = Dl + (int64_t)(r0 + rr) * ldo;
             const float tv = srow[rr] >= 0 ? a.y[(int64_t)srow[rr] * out + j] : 0.f;
-            const float d = o[j] - tv;
-            lsum += (acc_t)d * (acc_t)d;
-            o[j] = 2.f * d * a.grad_scale;
+            mse_tail(o[j], tv, a.grad_scale, lsum, o[j]);
         }
     } else {
+        // train_step_kernel's NLL tail (train.hip), operation for operation (train_math.hpp: why not a function)
         const float scale = 1.f / (float)(nb * out) * a.grad_scale;  // the mean runs over ALL rows of the step, not the block's
         const float* mxv = a.max_logvar + (int64_t)e * a.bounds_stride;
         const float* mnv = a.min_logvar + (int64_t)e * a.bounds_stride;
@@ -284,17 +282,17 @@ __global__ __launch_bounds__(kSplitDwThreads) void train_dw_kernel(const TrainSp
     __shared__ acc_t red[kDwWaves];
     const int l = blockIdx.y, e = blockIdx.z, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 15, q = lane >> 4;
     const int din = a.dims[l], dout = a.dims[l + 1];
-    const int nbj = (dout + kSplitDwBlock - 1) / kSplitDwBlock;
     if ((int)blockIdx.x >= split_dw_blocks(din, dout)) return;  // (the grid's x extent is the widest layer's)
-    const int bi = blockIdx.x / nbj, i0 = bi * kSplitDwBlock, j0 = (blockIdx.x - bi * nbj) * kSplitDwBlock;
+    const unsigned bn = blocks_across(dout);
+    const int i0 = block_m0(blockIdx.x, bn), j0 = block_n0(blockIdx.x, bn);
     const int nb = min(max(a.rows[0], 1), a.max_batch);
     const float* slab = a.slab + (int64_t)e * a.at.stride;
     const float* Ag = slab + a.at.off_a[l];
     const float* Dg = slab + a.at.off_d[l];
     const int lda = split_ld(din), ldd = split_ld(dout);
-    const int iw = (wave >> 1) * 32, jw = (wave & 1) * 32;       // the wave's 32 x 32 block of the 64 x 64
+    const int iw = block_wave_m0(wave), jw = block_wave_n0(wave);  // the wave's 32 x 32 block of the 64 x 64
     const int c4 = (tid & 15) * 4, sr = tid >> 4;                // staging: this thread's float4 column and its two rows sr, sr + 16
-    const bool bias_col = bi == 0 && tid < kSplitDwBlock && j0 + tid < dout;  // this thread sums column j0 + tid of dZ for db
+    const bool bias_col = i0 == 0 && tid < kBlock && j0 + tid < dout;  // this thread sums column j0 + tid of dZ for db
     f32x4 acc[2][2];
 #pragma unroll
     for (int i = 0; i < 2; ++i) acc[i][0] = acc[i][1] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -431,6 +429,7 @@ int train_split_steps(hipets_engine* e, const hipets_train_desc* d, const float*
     TrainSplitArgs a{};
     const int L = d->n_layers, E = d->ensemble_size, Bm = d->max_batch;
     train_fill(a, d, loss_kind, x, y, n_rows);
+    train_fill_step(a, d, bounds_per_member, grad_scale);
     a.at = train_split_slab(a.dims, L, Bm);
     a.row_blocks = (Bm + kSplitRows - 1) / kSplitRows;
     for (int l = 0; l < L; ++l) a.dw_blocks = std::max(a.dw_blocks, split_dw_blocks(a.dims[l], a.dims[l + 1]));
@@ -439,18 +438,6 @@ int train_split_steps(hipets_engine* e, const hipets_train_desc* d, const float*
     a.slab = e->train_slab.as<float>();
     a.loss_part = e->train_split_part.as<double>();
     a.gsq_part = a.loss_part + (size_t)E * a.row_blocks;
-    for (int l = 0; l < L; ++l) {
-        a.mw[l] = static_cast<float*>(d->exp_avg_w[l]);
-        a.mb[l] = static_cast<float*>(d->exp_avg_b[l]);
-        a.vw[l] = static_cast<float*>(d->exp_avg_sq_w[l]);
-        a.vb[l] = static_cast<float*>(d->exp_avg_sq_b[l]);
-    }
-    a.min_logvar = d->min_logvar;
-    a.max_logvar = d->max_logvar;
-    a.bounds_stride = bounds_per_member ? d->out_dim : 0;
-    a.grad_scale = grad_scale;
-    a.max_batch = Bm;
-    a.weight_decay = (float)d->weight_decay;
     for (int s = 0; s < n_steps; ++s) {
         a.adam = adam_scalars(d->lr, d->beta1, d->beta2, d->eps, step0 + s + 1);
         a.idx = idx + (int64_t)s * E * Bm;

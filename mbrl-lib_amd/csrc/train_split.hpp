@@ -1,5 +1,6 @@
 // train_split.hpp -- the row-split training step (train_split.hip; HIPETS_TRAIN_KERNEL_SPLIT of include/hipets.h): its limits, the
-// slab's layout, the LDS need of the rows kernel and the argument block its three kernels share.
+// slab's layout, the LDS need of the rows kernel and the argument block its three kernels share (filled by train.hpp's train_fill and
+// train_fill_step).  The dW kernel's 64 x 64 blocks and their waves' corners are tile_walk.hpp's.
 //   train_rows_kernel          grid (row block, member): 32 rows through forward, loss tail and the dA chain, activations LDS-resident
 //   train_dw_kernel            grid (64 x 64 block of W, layer, member): dW = A_l^T dZ_l over all rows, Adam fused; first row of blocks: db
 //   train_split_finish_kernel  grid (member): the step's loss and grad_sq partials, summed in a fixed order
@@ -8,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "tile_walk.hpp"
 #include "train.hpp"
 
 namespace hipets {
@@ -15,10 +17,10 @@ namespace hipets {
 constexpr int kSplitMaxBatch = HIPETS_TRAIN_SPLIT_MAX_BATCH;
 constexpr int kSplitRows = 32;           // rows of a row block: two 16-row MFMA tiles that share every weight fragment
 constexpr int kSplitRowsThreads = 512;   // 8 waves, each a block of kSplitRows x 32 result columns at a time
-constexpr int kSplitDwThreads = 256;     // 4 waves, each a 2 x 2 block of 16 x 16 tiles of a 64 x 64 block of W
-constexpr int kSplitDwBlock = 64;        // rows and columns of W per dW workgroup
+constexpr int kSplitDwThreads = 256;     // 4 waves, each a 2 x 2 block of 16 x 16 tiles of a kBlock x kBlock block of W (tile_walk.hpp: 64)
 constexpr int kSplitDwChunk = 32;        // minibatch rows per staged K-chunk of the dW product
-constexpr int kSplitDwStride = 80;       // floats per LDS row of a chunk: 64 + 16, so k-steps q and q + 1 lie 16 banks apart
+constexpr int kSplitDwStride = 80;       // floats per LDS row of a chunk: kBlock + 16, so k-steps q and q + 1 lie 16 banks apart
+static_assert(kSplitDwStride == kBlock + 16 && kSplitDwThreads == 4 * 64, "the dW kernel's staging and its four waves are written for 64 x 64 blocks");
 
 // floats per row of a slab section / of an LDS panel that is `width` wide: rows start 16-byte aligned (the panel: plus one float4,
 // so the rows of a 32 k wide panel do not all start in one bank)
@@ -55,10 +57,8 @@ inline TrainSplitSlab train_split_slab(const int32_t* dims, int n_layers, int ma
     return s;
 }
 
-// blocks of W_l the dW kernel cuts a din x dout layer into, row-major
-__host__ __device__ constexpr int split_dw_blocks(int din, int dout) {
-    return ((din + kSplitDwBlock - 1) / kSplitDwBlock) * ((dout + kSplitDwBlock - 1) / kSplitDwBlock);
-}
+// blocks of W_l the dW kernel cuts a din x dout layer into, in tile_walk.hpp's row-major block order
+__host__ __device__ __forceinline__ int split_dw_blocks(int din, int dout) { return blocks_across(din) * blocks_across(dout); }
 
 // One minibatch step.  The fields train_fill sets carry TrainStepArgs' names; idx / rows / loss / grad_sq point at THIS step's entries,
 // and the step's two Adam values travel as plain members (no per-launch table: steps_per_launch has no meaning here).

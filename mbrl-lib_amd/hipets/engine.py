@@ -2,6 +2,7 @@
 device memory and streams; every computation is a libhipets call."""
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 from typing import Dict, Optional
 
@@ -99,6 +100,19 @@ class Engine:
     def _query(self, symbol: str, **kw):
         """``_call`` for a host-only query or switch: no device scope"""
         self._call(symbol, False, **kw)
+
+    @contextlib.contextmanager
+    def _setting(self, symbol: str, table: dict, value: str, default: str):
+        """An engine switch (``symbol(kind=table[name])``) held at ``value`` for one call and put back to ``default`` behind it, also
+        when the call raises; at the default no switch call is made."""
+        if value == default:
+            yield
+            return
+        self._query(symbol, kind=table[value])
+        try:
+            yield
+        finally:
+            self._query(symbol, kind=table[default])
 
     # ---- model ------------------------------------------------------------------------------
     def set_model(self, spec: ModelSpec):
@@ -630,17 +644,12 @@ class Engine:
         losses = torch.empty(n_steps, E, dtype=torch.float32, device=dev)
         gsq = torch.empty(n_steps, E, dtype=torch.float32, device=dev)
         kw = dict(d=d, x=x, y=y, n_rows=int(x.shape[0]), idx=idx, rows=rows, n_steps=n_steps, step0=int(step0), loss=losses, grad_sq=gsq)
-        if kernel != "member":
-            self._query("hipets_set_train_kernel", kind=_lib.TRAIN_KERNEL[kernel])
-        try:
+        with self._setting("hipets_set_train_kernel", _lib.TRAIN_KERNEL, kernel, "member"):
             if loss == "nll" and not bounds_per_member and float(grad_scale) == 1.0:
                 self._call("hipets_train_steps", **kw)
             else:
                 self._call("hipets_train_steps_loss", loss_kind=_lib.TRAIN_LOSS[loss], bounds_per_member=int(bool(bounds_per_member)),
                            grad_scale=float(grad_scale), **kw)
-        finally:
-            if kernel != "member":
-                self._query("hipets_set_train_kernel", kind=_lib.TRAIN_KERNEL["member"])
         del keep
         return losses, gsq
 
@@ -832,15 +841,10 @@ class Engine:
         _check_dev(eps_next, torch.float32, self.device, "eps_next", (B, act))
         _check_dev(eps_cur, torch.float32, self.device, "eps_cur", (B, act))
         _check_dev(result, torch.float32, self.device, "result", numel=8)
-        if product != "tile":
-            self._query("hipets_set_sac_product", kind=_lib.SAC_PRODUCT[product])
-        try:
+        with self._setting("hipets_set_sac_product", _lib.SAC_PRODUCT, product, "tile"):
             self._call("hipets_sac_update", batch=batch, batch_size=B, eps_next=eps_next, eps_cur=eps_cur, update_index=int(update_index),
                        step_critic=int(steps[0]), step_policy=int(steps[1]), step_alpha=int(steps[2]), lr_critic=float(lrs[0]),
                        lr_policy=float(lrs[1]), lr_alpha=float(lrs[2]), result=result)
-        finally:
-            if product != "tile":
-                self._query("hipets_set_sac_product", kind=_lib.SAC_PRODUCT["tile"])
         # the update kernels write the agent's parameters through raw pointers (no tensor's _version moves): snapshots of the actor or
         # the critic compare this counter (hipets.sac)
         self.sac_updates += 1

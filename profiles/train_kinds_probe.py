@@ -29,7 +29,6 @@ for p in (ROOT, os.path.join(ROOT, "mbrl-lib_amd"), os.path.join(ROOT, "tests"))
         sys.path.insert(0, p)
 
 import hipets  # noqa: E402
-import train_loss_restatement as tlr  # noqa: E402
 import train_restatement as tr  # noqa: E402
 from hipets import _lib  # noqa: E402
 from hipets._pack import pack_train_desc  # noqa: E402
@@ -43,7 +42,7 @@ def _inputs(kind, E, steps):
     g = torch.Generator().manual_seed(0)
     x = torch.randn(N, IN, generator=g).to(DEV)
     y = (torch.randn(N, OUT, generator=g) * 0.3).to(DEV)
-    ws, bs = tlr.random_model_kind(kind, E, IN, HID, OUT, L, 0, dtype=torch.float32)
+    ws, bs = tr.random_model(E, IN, HID, OUT, L, 0, dtype=torch.float32, kind=kind)
     w, b = [t.to(DEV) for t in ws], [t.to(DEV) for t in bs]
     m = ([torch.zeros_like(t) for t in w], [torch.zeros_like(t) for t in b])
     v = ([torch.zeros_like(t) for t in w], [torch.zeros_like(t) for t in b])
@@ -111,7 +110,7 @@ def new_kind(name, kind, E, basic, steps, eager_steps):
     lo = hi = None
     kw = dict(loss=kind)
     if kind == "nll":
-        lo, hi = (t.float().to(DEV).contiguous() for t in tlr.member_bounds(E, OUT))
+        lo, hi = (t.float().to(DEV).contiguous() for t in tr.member_bounds(E, OUT))
         kw.update(bounds_per_member=True)
     scale = float(torch.tensor(1.0) / E) if basic else 1.0
     kw.update(grad_scale=scale)
@@ -132,10 +131,10 @@ def new_kind(name, kind, E, basic, steps, eager_steps):
         total, grads = 0.0, []
         for gi, sl in enumerate(groups):
             if kind == "mse":
-                loss, dws, dbs = tlr.mse_step(we[gi], be[gi], x[sel[sl]], y[sel[sl]], "silu", grad_scale=scale)
+                loss, dws, dbs = tr.mse_step(we[gi], be[gi], x[sel[sl]], y[sel[sl]], "silu", grad_scale=scale)
             else:
-                loss, dws, dbs = tlr.nll_step_kind(we[gi], be[gi], x[sel[sl]], y[sel[sl]], lo[sl].unsqueeze(1), hi[sl].unsqueeze(1), "silu",
-                                                   grad_scale=scale)
+                loss, dws, dbs = tr.nll_step(we[gi], be[gi], x[sel[sl]], y[sel[sl]], lo[sl].unsqueeze(1), hi[sl].unsqueeze(1), "silu",
+                                            grad_scale=scale)
             total = total + loss.sum()
             grads.append((dws, dbs))
         _ = (total * scale).item()

@@ -45,10 +45,11 @@ def snapshot(s):
 class FakeLib:
     """Records (symbol, {header parameter name: value}) of every call and returns 0.  Scalars arrive as ctypes' argtypes of the header's
     type deliver them (a Python int wraps into uint64_t); struct pointers as snapshots; byref'd output scalars are filled from
-    ``outputs[symbol][name]``; ``peek[name] = (ctype, n)`` copies n elements out from behind a plain pointer parameter or struct field."""
+    ``outputs[symbol][name]``; ``peek[name] = (ctype, n)`` copies n elements out from behind a plain pointer parameter or struct field;
+    ``raises[symbol]`` is raised by that call once it is recorded."""
 
     def __init__(self):
-        self.calls, self.outputs, self.peek = [], {}, {}
+        self.calls, self.outputs, self.peek, self.raises = [], {}, {}, {}
 
     def __getattr__(self, symbol):
         if not symbol.startswith("hipets_"):
@@ -63,6 +64,8 @@ class FakeLib:
                 if name in self.peek and isinstance(rec[name], int):
                     rec[name + "_data"] = self._copy(rec[name], name)
             self.calls.append((symbol, rec))
+            if symbol in self.raises:
+                raise self.raises[symbol]
             return 0
 
         return fn
@@ -613,6 +616,46 @@ def test_train_desc_with_and_without_adam(eng):
     (score, rs), rec = call(eng, "train_eval", "hipets_train_eval", extra={"d": ANY, "n_rows": N, "score": ANY, "row_score": ANY}, weights=ws, biases=bs,
                             x=x, y=y, order=order, activation="tanh", leaky_slope=0.03, row_scores=True)
     assert rs.shape == (E, N) and (rec["score"], rec["row_score"]) == (score.data_ptr(), rs.data_ptr())
+
+
+SWITCHED_CALLS = {  # method -> (the switch, its table, default name, other name, keyword, the call it wraps)
+    "train_steps": ("hipets_set_train_kernel", _lib.TRAIN_KERNEL, "member", "split", "kernel", "hipets_train_steps"),
+    "sac_update": ("hipets_set_sac_product", _lib.SAC_PRODUCT, "tile", "blocked", "product", "hipets_sac_update"),
+}
+
+
+@pytest.mark.parametrize("method", sorted(SWITCHED_CALLS))
+def test_per_call_switches_are_set_called_and_put_back(eng, method):
+    """Engine.train_steps(kernel=) / Engine.sac_update(product=): off the default the library sees set, the call, reset -- the reset
+    also when the call raises; at the default no switch call is made at all."""
+    switch, table, default, other, keyword, symbol = SWITCHED_CALLS[method]
+    if method == "train_steps":
+        out, mb = OBS, 4
+        like = lambda ts: [torch.zeros_like(x) for x in ts]  # noqa: E731
+        ws, bs = [t(E, 5, HID), t(E, HID, 2 * out)], [t(E, 1, HID), t(E, 1, 2 * out)]
+        kw = dict(weights=ws, biases=bs, exp_avg=(like(ws), like(bs)), exp_avg_sq=(like(ws), like(bs)), min_logvar=t(1, out), max_logvar=t(1, out),
+                  x=t(10, 5), y=t(10, out), idx=t(2, E, mb, dtype=torch.int32), rows=t(2, dtype=torch.int32), step0=0, lr=1e-3)
+    else:
+        eng.sac_dims, B = (OBS, ACT, HID), 6
+        kw = dict(batch=t(B, 2 * OBS + ACT + 2), eps_next=t(B, ACT), eps_cur=t(B, ACT), update_index=0, steps=(0, 0, 0), lrs=(1e-3, 1e-3, 1e-3),
+                  result=t(8))
+    run = getattr(eng, method)
+    order = lambda: [(s, r["kind"]) if s == switch else s for s, r in eng._lib.calls]  # noqa: E731
+    run(**kw, **{keyword: other})
+    assert order() == [(switch, table[other]), symbol, (switch, table[default])]
+    eng._lib.calls.clear()
+    eng._lib.raises[symbol] = HipetsError("refused", _lib.ERR_INVALID_ARGUMENT)
+    with pytest.raises(HipetsError, match="refused"):
+        run(**kw, **{keyword: other})
+    assert order() == [(switch, table[other]), symbol, (switch, table[default])]
+    eng._lib.calls.clear()
+    del eng._lib.raises[symbol]
+    run(**kw, **{keyword: default})
+    run(**kw)
+    assert order() == [symbol, symbol]
+    with pytest.raises(ValueError):
+        run(**kw, **{keyword: "neither"})
+    assert order() == [symbol, symbol]
 
 
 @pytest.mark.parametrize("n_env", [1, 2])

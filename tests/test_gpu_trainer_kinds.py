@@ -60,7 +60,7 @@ def test_member_bounds_and_grad_scale_are_read(engine):
     i = r["inputs"]
     sel = i["idx"][0].long()
     w, b, m, v = tr.fresh_state(i["ws"], i["bs"], torch.float64, "cpu")
-    loss_shared, gsq_unscaled = tlr.train_step_kind("nll", w, b, m, v, i["x"][sel], i["y"][sel], i["lo"][:1], i["hi"][:1], "silu", 1, tr.LR, tr.WD)
+    loss_shared, gsq_unscaled = tr.train_step(w, b, m, v, i["x"][sel], i["y"][sel], i["lo"][:1], i["hi"][:1], "silu", 1, tr.LR, tr.WD, kind="nll")
     loss, gsq = r["hip"][4][0].double().cpu(), r["hip"][5][0].double().cpu()
     assert abs(loss[1] - loss_shared[1]).item() > 1e-2 and abs(loss[0] - loss_shared[0]).item() < 1e-5
     assert torch.allclose(gsq[0] * 9, gsq_unscaled[0], rtol=1e-4)
@@ -122,7 +122,7 @@ def test_evaluate_mse_reads_an_out_wide_last_layer(engine):
     it with a row stride of 2 out instead of out gives another score."""
     E, in_dim, hid, out, L, N = 3, 9, 24, 17, 3, 70
     g = torch.Generator().manual_seed(4)
-    ws, bs = tlr.random_model_kind("mse", E, in_dim, hid, out, L, 4)
+    ws, bs = tr.random_model(E, in_dim, hid, out, L, 4, kind="mse")
     x = torch.randn(N, in_dim, generator=g, dtype=torch.float64)
     y = torch.randn(N, out, generator=g, dtype=torch.float64)
     ref = tr.eval_score(ws, bs, x, y, "silu")
@@ -172,7 +172,7 @@ def test_train_matches_reference_trainer(engine, name):
     lists the figures per recording); 10x the larger of the two distances is allowed, the margin tests/test_gpu_trainer.py took over its
     measured 2e-6."""
     meta, arr = _golden(name)
-    measured = [_weight_distance(_train(meta, arr, tlr.CpuEngineKinds(mirrored=mirrored))[0], meta, arr) for mirrored in (False, True)]
+    measured = [_weight_distance(_train(meta, arr, tr.CpuEngine(mirrored=mirrored))[0], meta, arr) for mirrored in (False, True)]
     bound = 10 * max(measured)
     mlp, rng, losses, scores, tb = _train(meta, arr, engine)
     got = _weight_distance(mlp, meta, arr)
@@ -203,7 +203,7 @@ def test_model_env_repacks_after_training_a_basic_ensemble(engine):
     def ensemble(ws, bs):
         mlp = tlr.TinyBasicEnsemble(E, obs_dim + act_dim, hid, obs_dim, L, act="silu")
         mlp.propagation_method = "expectation"
-        tlr.load_params_kind(mlp, ws, bs)
+        tr.load_params(mlp, ws, bs)
         return mlp
 
     mlp = ensemble(*tr.random_model(E, obs_dim + act_dim, hid, obs_dim, L, 11, dtype=torch.float32))

@@ -2,7 +2,7 @@
 factory's two fall-back branches, the trainer's host logic (batches consumed, RNG, loss and grad_norm composition, optimizer
 state_dict, elites) for a BasicEnsemble (NLL / deterministic) and a deterministic GaussianMLP against the reference ModelTrainer's
 recordings (tests/golden/trainerx_*.npz, tests/make_trainer_loss_golden.py) with the device steps on a CPU stand-in of the engine,
-the additive C ABI, and the restatements (tests/train_loss_restatement.py) against the reference's own Model.update in float64."""
+the additive C ABI, and the restatements (tests/train_restatement.py) against the reference's own Model.update in float64."""
 import json
 import os
 import re
@@ -40,15 +40,15 @@ def _models():
 def test_new_kinds_are_refused_by_default_and_construct_when_extended():
     for name, model in _models().items():
         with pytest.raises(hipets.UnsupportedModelError, match="keep mbrl.models.ModelTrainer"):
-            hipets.ModelTrainer(model, engine=tlr.CpuEngineKinds())
-        trainer = hipets.ModelTrainer(model, engine=tlr.CpuEngineKinds(), extended=True)
+            hipets.ModelTrainer(model, engine=tr.CpuEngine())
+        trainer = hipets.ModelTrainer(model, engine=tr.CpuEngine(), extended=True)
         assert trainer._out == 4 and [tuple(t.shape) for t in trainer._w[0]] == [(3, 5, 8), (3, 8, 8), (3, 8, 4 if "mse" in name else 8)], name
     with pytest.raises(TypeError):
         hipets.ModelTrainer(_models()["gmlp_mse"], 1e-3, 1e-5, 1e-8, None, True)  # extended is keyword-only
 
 
 def test_still_refused_when_extended_with_the_reason():
-    E = tlr.CpuEngineKinds
+    E = tr.CpuEngine
     cases = {
         "learn_logvar_bounds": tr.TinyGaussianMLP(3, 5, 8, 4, 3, learn_logvar_bounds=True),
         "member 1: learn_logvar_bounds": tlr.TinyBasicEnsemble(3, 5, 8, 4, 3, learn_logvar_bounds=True),
@@ -81,7 +81,7 @@ def test_factory_returns_the_hip_trainer_for_every_trainable_kind():
     for name, model in models.items():
         with warnings.catch_warnings():
             warnings.simplefilter("error")
-            trainer = hipets.make_model_trainer(model, optim_lr=3e-4, weight_decay=2e-5, optim_eps=1e-7, engine=tlr.CpuEngineKinds())
+            trainer = hipets.make_model_trainer(model, optim_lr=3e-4, weight_decay=2e-5, optim_eps=1e-7, engine=tr.CpuEngine())
         assert type(trainer) is hipets.ModelTrainer, name
         g = trainer.optimizer.param_groups[0]
         assert (g["lr"], g["weight_decay"], g["eps"]) == (3e-4, 2e-5, 1e-7)
@@ -102,7 +102,7 @@ def test_factory_falls_back_to_the_stock_trainer_with_one_warning(monkeypatch):
     model = tr.TinyDynamicsModel(tr.TinyGaussianMLP(3, 5, 8, 4, 3, learn_logvar_bounds=True))
     with warnings.catch_warnings(record=True) as caught:
         warnings.simplefilter("always")
-        trainer = hipets.make_model_trainer(model, optim_lr=3e-4, weight_decay=2e-5, optim_eps=1e-7, logger="L", engine=tlr.CpuEngineKinds())
+        trainer = hipets.make_model_trainer(model, optim_lr=3e-4, weight_decay=2e-5, optim_eps=1e-7, logger="L", engine=tr.CpuEngine())
     assert type(trainer) is StockTrainer and made == [(model, 3e-4, 2e-5, 1e-7, "L")]
     assert len(caught) == 1 and "learn_logvar_bounds=True" in str(caught[0].message)
 
@@ -112,7 +112,7 @@ def test_factory_reraises_where_the_stock_trainer_cannot_be_imported(monkeypatch
     monkeypatch.setitem(sys.modules, "mbrl.models", None)
     model = tr.TinyDynamicsModel(tr.TinyGaussianMLP(3, 5, 8, 4, 3, learn_logvar_bounds=True))
     with pytest.raises(hipets.UnsupportedModelError, match="learn_logvar_bounds=True"):
-        hipets.make_model_trainer(model, engine=tlr.CpuEngineKinds())
+        hipets.make_model_trainer(model, engine=tr.CpuEngine())
 
 
 def test_todays_kind_calls_the_engine_with_todays_arguments_only():
@@ -135,7 +135,7 @@ def trained(request):
     """One train() per golden with the device steps on the CPU stand-in, shared by the tests below (which only read it)."""
     meta, arr = _golden(request.param)
     mlp, model, train, val, rng = tlr.golden_setup(meta, arr)
-    engine = tlr.CpuEngineKinds()
+    engine = tr.CpuEngine()
     trainer = hipets.ModelTrainer(model, optim_lr=meta["lr"], weight_decay=meta["weight_decay"], engine=engine, extended=True)
     batches = []
     with warnings.catch_warnings(record=True) as caught:
@@ -245,7 +245,7 @@ def test_optimizer_state_dict_follows_the_live_parameter_order(trained):
     opt.load_state_dict(sd)
     back = opt.state_dict()
     _, model2, _, _, _ = tlr.golden_setup(meta, arr)
-    trainer2 = hipets.ModelTrainer(model2, optim_lr=meta["lr"], engine=tlr.CpuEngineKinds(), extended=True)
+    trainer2 = hipets.ModelTrainer(model2, optim_lr=meta["lr"], engine=tr.CpuEngine(), extended=True)
     trainer2.optimizer.load_state_dict(back)
     assert trainer2._step == steps
     for k in (0, 1):
@@ -262,7 +262,7 @@ def test_adam_state_from_epoch_1_lands_in_member_rows(name):
     [1, ., .] moments, which must land in row e of the stacked tensors (and come back out at k)."""
     meta, arr = _golden(name)
     _, model, _, _, _ = tlr.golden_setup(meta, arr)
-    trainer = hipets.ModelTrainer(model, optim_lr=meta["lr"], engine=tlr.CpuEngineKinds(), extended=True)
+    trainer = hipets.ModelTrainer(model, optim_lr=meta["lr"], engine=tr.CpuEngine(), extended=True)
     n = len(meta["param_shapes"])
     group = dict(trainer.optimizer.state_dict()["param_groups"][0], params=list(range(n)))
     trainer.optimizer.load_state_dict({"state": {int(k): {"step": torch.tensor(float(meta["adam_step_epoch1"])), "exp_avg": torch.from_numpy(arr[f"m_{k}"]),
@@ -323,7 +323,7 @@ def test_restatement_equals_reference_update_float64(kind):
     scale = 1.0 / E if m["basic"] else 1.0
     for step in range(2):
         x, y = torch.from_numpy(a[f"u_{kind}_x{step}"]), torch.from_numpy(a[f"u_{kind}_y{step}"])
-        loss, gsq = tlr.train_step_kind(loss_kind, ws, bs, ms, vs, x, y, lo, hi, m["act"], step + 1, 1e-2, 1e-3, grad_scale=scale)
+        loss, gsq = tr.train_step(ws, bs, ms, vs, x, y, lo, hi, m["act"], step + 1, 1e-2, 1e-3, grad_scale=scale, kind=loss_kind)
         total = ((loss + terms).sum() * scale).item()
         assert abs(total - m["loss"][step]) < 1e-12 * max(1.0, abs(total))
         assert abs(gsq.sum().item() - m["grad_norm"][step]) < 1e-12 * max(1.0, gsq.sum().item())

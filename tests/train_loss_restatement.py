@@ -1,7 +1,7 @@
 """TEST HELPER (not collected): what the tests of the loss kinds hipets.ModelTrainer trains with ``extended=True`` need next to
-tests/train_restatement.py (which restates the update of either kind): TinyBasicEnsemble, a ``members`` ModuleList of one-member
-TinyGaussianMLPs in the reference's parameter order, and golden_setup for the tests/golden/trainerx_*.npz recordings.  The ``*_kind``
-names are the restatement's functions under the names and argument orders they had when this module held a copy of each."""
+tests/train_restatement.py (which restates the update of either kind, ``kind=``): TinyBasicEnsemble, a ``members`` ModuleList of
+one-member TinyGaussianMLPs in the reference's parameter order, golden_setup for the tests/golden/trainerx_*.npz recordings, and
+run_steps_kind, the restatement's run_steps as the tests of the kinds run it."""
 from __future__ import annotations
 
 import json
@@ -11,20 +11,6 @@ import numpy as np
 import torch
 
 import train_restatement as tr
-from train_restatement import bounds_3d, member_bounds, mse_step, seq_matmul  # noqa: F401  (used through this module)
-
-nll_step_kind = tr.nll_step
-load_params_kind = tr.load_params
-CpuEngineKinds = tr.CpuEngine
-
-
-def train_step_kind(kind, ws, bs, ms, vs, x, y, min_lv, max_lv, act, step, lr, weight_decay, eps=1e-8, slope=0.01, grad_scale=1.0,
-                    sequential=False):
-    return tr.train_step(ws, bs, ms, vs, x, y, min_lv, max_lv, act, step, lr, weight_decay, eps, slope, grad_scale, sequential, kind=kind)
-
-
-def random_model_kind(kind, E, in_dim, hid, out, n_layers, seed, dtype=torch.float64):
-    return tr.random_model(E, in_dim, hid, out, n_layers, seed, dtype, kind=kind)
 
 
 def run_steps_kind(engine, kind, E, B, in_dim, hid, out, n_layers, act, n_steps, N=None, seed=0, steps_per_launch=0, ragged_last=False, *,
