@@ -25,7 +25,11 @@
  *     hipets_icem_sample, hipets_icem_shift, hipets_particle_reduce, hipets_fast_schedule, hipets_fast_normals,
  *     hipets_device_perms and hipets_policy_normals.  Four entry points take part in the ordering and also synchronise `stream`
  *     before returning, because they read caller-owned DEVICE tensors and HOST staging that may be freed right after the call:
- *     hipets_set_model, hipets_set_model_columns, hipets_planet_set_model and hipets_ensemble_set.  hipets_timing_read waits for
+ *     hipets_set_model, hipets_set_model_columns, hipets_planet_set_model and hipets_ensemble_set.  The three entry points of the
+ *     PlaNet posterior update (hipets_planet_posterior_set_model, hipets_planet_encode, hipets_planet_posterior_update) are
+ *     BLOCKING calls without a `stream` parameter: they take part in the ordering on the device's default (null) stream and
+ *     synchronise it before returning, so their results are complete on return and valid on every stream; inputs made on another
+ *     stream must be complete when they are called.  hipets_timing_read waits for
  *     the events it reports; the one-time co-residency self-test of a persistent DEVICE-mode kernel instance synchronises once
  *     (hipets_set_persistent); hipets_sac_bind makes one blocking 16-byte copy.  Nothing else synchronises.
  *   - HOST arrays are consumed before the call returns, so temporaries are fine: observations are copied into
@@ -995,6 +999,54 @@ int hipets_policy_rollout(hipets_engine* e, const float* s0, int32_t n, int32_t 
 /* Launch geometry of hipets_policy_rollout for n rows, the actor's rule (hipets_policy_geometry) on the LDS need above; the same refusals
  * about the snapshots.                                                                                                                */
 int hipets_policy_rollout_geometry(hipets_engine* e, int32_t n, int32_t* row_tiles, int32_t* lds_bytes);
+
+/* ---- PlaNet posterior update: the conv encoder and the belief step of every environment step ----
+ * Additive entry points: scalars and pointers only, no struct, HIPETS_ABI_VERSION stays.  Need no other model in the engine.
+ *
+ * PlaNetModel.update_posterior (mbrl/models/planet.py:592-641 -> :309-347) for n_env environments at once: pixel normalisation
+ * (x / 256 - 0.5), Conv2dEncoder (mbrl/models/util.py:101-157: Conv2d + ReLU layers without padding, flatten in C, H, W order, an
+ * optional Linear), BeliefModel (Linear + ReLU over [latent | action], GRUCell), posterior_transition_model (Linear + ReLU over
+ * [belief | encoding], Linear, MeanStdCat) and latent = mean + std * eps.  All products are fp32 MFMA with fp32 accumulation; bias,
+ * ReLU, gates and the softplus tail fp32 op by op.  Ordinary launches only: one per conv layer (an implicit GEMM: rows = the
+ * (image, oh, ow) output positions, columns = C_out, k = (kh, kw, c)), one for the Linear when there is one, one for the encoding
+ * half of the posterior's first Linear, one for the head (16 environments per workgroup).  A layer with few rows and much weight
+ * is dealt over workgroups by column tiles and, past that, by K ranges whose partial sums the NEXT launch adds in range order: the
+ * split is a function of the layer's shape alone, so an image's results do not depend on n_env or on its slot in the batch.
+ *
+ * hipets_planet_posterior_set_model: conv_dims HOST [n_conv][4] = (C_in, C_out, kernel, stride) per layer, image_chw HOST [3];
+ * enc_size = the encoder's output width (= the flattened last conv output when there is no Linear); `ptrs` a HOST table of
+ * n_ptrs = 2 n_conv + 12 DEVICE pointers to contiguous f32 tensors in torch's layouts: per conv layer weight [C_out, C_in, k, k]
+ * and bias; fc weight [enc_size, flat] and bias (both NULL: nn.Identity); embedding weight [belief, latent + action] and bias; GRUCell
+ * weight_ih, bias_ih, weight_hh, bias_hh (gates r | z | n); posterior[0] weight [hidden, belief + enc_size] and bias; posterior[2]
+ * weight [2 latent, hidden] and bias.  It copies them into the engine's packed layout (a SNAPSHOT, like hipets_critic_set) and
+ * blocks until the copies are done (Conventions above), like hipets_planet_set_model.  Outside the limits below, a layer whose kernel does not fit its input, a layer of more than
+ * HIPETS_ENCODER_MAX_LAYER_FLOATS outputs per image, or a head whose LDS need -- 16 rows x (max(pad16(latent + action), pad16(hidden))
+ * + max(pad16(belief), pad16(2 latent)) + pad16(belief) + 2 pad16(3 belief) + 20) floats -- exceeds the LDS opt-in limit is
+ * HIPETS_ERR_INVALID_ARGUMENT and leaves the engine without a posterior model.                                                      */
+#define HIPETS_ENCODER_MAX_CONVS 6
+#define HIPETS_ENCODER_MAX_CHANNELS 512
+#define HIPETS_ENCODER_MAX_KERNEL 8
+#define HIPETS_ENCODER_MAX_STRIDE 4
+#define HIPETS_ENCODER_MAX_IMAGE 128
+#define HIPETS_ENCODER_MAX_FLAT 4096
+#define HIPETS_ENCODER_MAX_ENV 64
+#define HIPETS_ENCODER_MAX_LAYER_FLOATS 1048576
+#define HIPETS_POSTERIOR_MAX_LATENT 512
+#define HIPETS_POSTERIOR_MAX_ACTION 64
+#define HIPETS_POSTERIOR_MAX_BELIEF 1024
+#define HIPETS_POSTERIOR_MAX_HIDDEN 1024
+int hipets_planet_posterior_set_model(hipets_engine* e, int32_t n_conv, const int32_t* conv_dims, const int32_t* image_chw, int32_t enc_size,
+                                      int32_t latent, int32_t action, int32_t belief, int32_t hidden, float min_std, const void* ptrs,
+                                      int32_t n_ptrs);
+/* The encoder alone: obs DEVICE [n_env, C, H, W], uint8 (obs_is_u8 != 0) or f32, raw pixel values -> out_enc DEVICE f32
+ * [n_env, enc_size].  1 <= n_env <= HIPETS_ENCODER_MAX_ENV.  Blocking, as hipets_planet_posterior_update is. */
+int hipets_planet_encode(hipets_engine* e, const void* obs, int32_t obs_is_u8, int32_t n_env, float* out_enc);
+/* One posterior step of n_env environments, IN PLACE on latent_inout DEVICE f32 [n_env, latent] and belief_inout [n_env, belief]:
+ * obs as above; action DEVICE f32 [n_env, action] or NULL (zeros); eps_or_null DEVICE f32 [n_env, latent], the standard normals, or
+ * NULL for the posterior mean; first_mask_or_null DEVICE uint8 [n_env] or NULL: a non-zero entry starts that environment from zero
+ * latent, belief and action (planet.py:583-590, 619-624), whatever the three arrays hold for it.                                     */
+int hipets_planet_posterior_update(hipets_engine* e, const void* obs, int32_t obs_is_u8, int32_t n_env, const float* action,
+                                   float* latent_inout, float* belief_inout, const float* eps_or_null, const uint8_t* first_mask_or_null);
 
 /* ---- instrumentation (bench.py roofline leg) ----------------------------------------------- */
 /* on = 1: every rollout-kernel launch carries a start / stop hipEvent pair on its dispatch packet; on = k > 1: every

@@ -120,7 +120,8 @@ void hipets_destroy(hipets_engine* e) {
                       &e->s0, &e->state, &e->totals, &e->term, &e->exchange, &e->step_keys, &e->plan_keys, &e->mu, &e->disp, &e->population, &e->values,
                       &e->best_value, &e->best_solution, &e->past_action, &e->kept, &e->elite_idx, &e->keep_idx, &e->planet_w, &e->planet_b, &e->planet_member, &e->planet_ops, &e->shard_values, &e->gathered, &e->census, &e->train_slab, &e->train_partial, &e->train_split_part,
                       &e->policy.w, &e->policy.b, &e->compact_counts, &e->sac_ws, &e->sac_one, &e->critic.w, &e->critic.b,
-                      &e->ensemble.w, &e->ensemble.b, &e->ensemble.norm, &e->ensemble.lv, &e->ensemble.cols})
+                      &e->ensemble.w, &e->ensemble.b, &e->ensemble.norm, &e->ensemble.lv, &e->ensemble.cols,
+                      &e->posterior.w, &e->posterior.b, &e->posterior.act[0], &e->posterior.act[1]})
         b->release();
     for (auto& ev : e->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
     for (auto& ev : e->event_pool) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }

@@ -1,5 +1,5 @@
 // engine.hpp -- private to the host units of the C ABI (include/hipets.h): engine.hip, model.hip, rollout.hip, plan.hip, comm.hip,
-// train.hip, train_split.hip, policy.hip, replay.hip, sac.hip, value.hip, ensemble.hip and policy_rollout.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
+// train.hip, train_split.hip, policy.hip, replay.hip, sac.hip, value.hip, ensemble.hip, policy_rollout.hip and planet_posterior.hip.  The engine struct, the thread's error state, stream entry, host staging, and the few functions one unit offers another.
 // Host code only; nothing declared here is part of the ABI (hidden visibility).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -79,6 +79,26 @@ struct EnsembleSnapshot {
     int members[HIPETS_ENSEMBLE_MAX_MEMBERS] = {};
     size_t wmember = 0, bmember = 0;
     DevBuf w, b, norm, lv, cols, no_delta;
+};
+
+// what hipets_planet_posterior_set_model keeps (planet_posterior.hip): the product chain of the encoder -- the conv layers, the optional
+// Linear and the encoding half of the posterior's first Linear, each one implicit-GEMM launch -- and the head's sizes; the packed W[k][n]
+// images and biases of chain and head; the chain's activation buffers, grown to the largest n_env seen
+struct PosteriorLayer {
+    int C_in = 0, C_out = 0, k = 1, stride = 1, H = 1, W = 1, OH = 1, OW = 1;  // a Linear is a 1 x 1 kernel on a 1 x 1 image
+    int K = 0, Kp = 0, Np = 0, relu = 0, chw_out = 0;                          // chw_out: the last conv layer stores in flatten (C, H, W) order
+    int splits = 1, kb_per_split = 0;                                         // the K ranges (k-blocks of 16 each) and their number
+    size_t w_off = 0, b_off = 0;
+};
+struct PosteriorSnapshot {
+    bool set = false;
+    int n_layers = 0, n_conv = 0, has_fc = 0;  // n_layers = n_conv + has_fc + 1 (the posterior's encoding half comes last)
+    int C = 0, H = 0, W = 0, flat = 0, enc = 0, latent = 0, action = 0, belief = 0, hidden = 0;
+    float min_std = 0.f;
+    PosteriorLayer layers[HIPETS_ENCODER_MAX_CONVS + 2];
+    size_t head_w[5] = {}, head_b[5] = {};  // embed, w_ih, w_hh, posterior[0] belief half (zero bias), posterior[2]
+    size_t head_lds = 0;
+    DevBuf w, b, act[2];
 };
 
 // what hipets_sac_bind keeps: the agent's sizes and hyper-parameters, its optimizers' (beta1, beta2, eps) [critic, policy, alpha], and the
@@ -169,6 +189,8 @@ struct hipets_engine {
     DevBuf sac_ws, sac_one;
     // the dynamics ensemble as hipets_ensemble_set packed it (hipets_ensemble_predict, ensemble.hip); apart from the rollout model slot above
     hipets::EnsembleSnapshot ensemble;
+    // the PlaNet posterior update as hipets_planet_posterior_set_model packed it (planet_posterior.hip)
+    hipets::PosteriorSnapshot posterior;
 };
 
 #pragma GCC visibility push(hidden)

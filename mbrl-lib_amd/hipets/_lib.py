@@ -54,6 +54,10 @@ TRAIN_SPLIT_MAX_BATCH = 1024  # HIPETS_TRAIN_SPLIT_MAX_BATCH
 SAC_N_PTRS, SAC_MAX_BATCH = 78, 1024  # HIPETS_SAC_N_PTRS, HIPETS_SAC_MAX_BATCH
 SAC_PRODUCT = {"tile": 0, "blocked": 1}  # HIPETS_SAC_PRODUCT_*
 CRITIC_N_PTRS = 12  # HIPETS_CRITIC_N_PTRS
+# HIPETS_ENCODER_MAX_* / HIPETS_POSTERIOR_MAX_*: conv layers, channels, kernel, stride, image side, flattened encoding, environments,
+# outputs of one layer per image; latent, action, belief, hidden
+ENCODER_MAX = {"convs": 6, "channels": 512, "kernel": 8, "stride": 4, "image": 128, "flat": 4096, "env": 64, "layer_floats": 1 << 20}
+POSTERIOR_MAX = {"latent": 512, "action": 64, "belief": 1024, "hidden": 1024}
 ENSEMBLE_MAX_MEMBERS, ENSEMBLE_MAX_IN, ENSEMBLE_MAX_OUT = 16, 512, 512  # HIPETS_ENSEMBLE_MAX_*
 ENSEMBLE_STATS = ("max_std", "disagreement", "total_std", "max_deviation")  # columns of hipets_ensemble_predict's stats
 
@@ -266,6 +270,10 @@ SYMBOLS = {
                                        "stream"),
     "hipets_policy_rollout": _sig("e s0 n:i32 horizon:i32 mean_rows:i32 only_elite:i32 seed:u64 stream_id:u64 eps actions states stream"),
     "hipets_policy_rollout_geometry": _sig("e n:i32 row_tiles:i32* lds_bytes:i32*"),
+    "hipets_planet_posterior_set_model": _sig("e n_conv:i32 conv_dims:i32* image_chw:i32* enc_size:i32 latent:i32 action:i32 belief:i32 hidden:i32 "
+                                              "min_std:f32 ptrs n_ptrs:i32"),
+    "hipets_planet_encode": _sig("e obs obs_is_u8:i32 n_env:i32 out_enc"),
+    "hipets_planet_posterior_update": _sig("e obs obs_is_u8:i32 n_env:i32 action latent_inout belief_inout eps_or_null first_mask_or_null"),
     "hipets_timing_enable": _sig("e on:i32"),
     "hipets_timing_read": _sig("e launches:i64* total_ms:f64* reset:i32"),
 }

@@ -53,6 +53,8 @@ class Engine:
     sac_updates = 0
     # the ensemble slot (hipets.ensemble): the spec whose snapshot hipets_ensemble_set took, and its owner (a weakref)
     ensemble_spec = ensemble_owner = None
+    # the posterior slot (hipets.planet_posterior): the spec whose snapshot hipets_planet_posterior_set_model took
+    posterior_spec = None
 
     def __init__(self, device="cuda:0"):
         self.device = torch.device(device)
@@ -582,6 +584,70 @@ class Engine:
         is_static = C.c_int32(-1)
         self._query("hipets_planet_kernel_class", is_static=C.byref(is_static))
         return "static" if is_static.value else "generic"
+
+    # ---- PlaNet posterior update (hipets_planet_posterior_set_model / hipets_planet_encode / hipets_planet_posterior_update) ----
+    def _posterior_call(self, symbol: str, **kw):
+        """The posterior entry points are blocking calls on the device's default stream (include/hipets.h, Conventions): what torch's
+        current stream holds -- the inputs' producers -- is drained first where that is another stream; on return the results are
+        complete and valid on every stream."""
+        cur = torch.cuda.current_stream(self.device)
+        if cur != torch.cuda.default_stream(self.device):
+            cur.synchronize()
+        self._call(symbol, **kw)
+
+    def planet_posterior_set_model(self, spec):
+        """Snapshot the encoder, belief and posterior tensors of a ``hipets.PlaNetPosteriorSpec`` into the engine.  Blocking."""
+        spec.validate()
+        on_dev = [None if t is None else t.detach().to(device=self.device, dtype=torch.float32).contiguous() for t in spec.tensors()]
+        table = np.array([0 if t is None else t.data_ptr() for t in on_dev], dtype=np.uint64)
+        dims = [int(v) for w, s in zip(spec.conv_weights, spec.strides) for v in (w.shape[1], w.shape[0], w.shape[2], s)]
+        self.posterior_spec = None  # (a refused set leaves no posterior model in the engine)
+        self._posterior_call("hipets_planet_posterior_set_model", n_conv=len(spec.conv_weights), conv_dims=(C.c_int32 * len(dims))(*dims),
+                   image_chw=(C.c_int32 * 3)(*spec.image_shape), enc_size=spec.encoding_size, latent=spec.latent_size, action=spec.action_size,
+                   belief=spec.belief_size, hidden=spec.hidden_size, min_std=float(spec.min_std), ptrs=table, n_ptrs=int(table.size))
+        del on_dev  # (the call has blocked until the copies were done)
+        self.posterior_spec = spec
+
+    def _posterior_obs(self, obs, n_env: int):
+        """``obs`` -- numpy or torch, host or device, [n_env, C, H, W] ([C, H, W] for one environment) of raw pixel values -- as a
+        contiguous device tensor, uint8 if it came as uint8 and float32 otherwise."""
+        spec = self.posterior_spec
+        if spec is None:
+            raise HipetsError("Engine.planet_posterior_set_model() has not been called")
+        t = torch.as_tensor(obs)
+        shape = tuple(spec.image_shape)
+        if tuple(t.shape) == shape and n_env == 1:
+            t = t.unsqueeze(0)
+        if tuple(t.shape) != (n_env,) + shape:
+            raise ValueError(f"obs has shape {tuple(t.shape)}, expected {(n_env,) + shape}")
+        return t.to(device=self.device, dtype=torch.uint8 if t.dtype == torch.uint8 else torch.float32).contiguous()
+
+    def planet_encode(self, obs, n_env: int = 1) -> torch.Tensor:
+        """``Conv2dEncoder.forward`` on the normalised pixels of ``obs`` -> f32 [n_env, encoding_size] on the device."""
+        x = self._posterior_obs(obs, n_env)
+        out = torch.empty(n_env, self.posterior_spec.encoding_size, dtype=torch.float32, device=self.device)
+        self._posterior_call("hipets_planet_encode", obs=x, obs_is_u8=int(x.dtype == torch.uint8), n_env=n_env, out_enc=out)
+        return out
+
+    def planet_posterior_update(self, obs, latent: torch.Tensor, belief: torch.Tensor, action: Optional[torch.Tensor] = None,
+                                eps: Optional[torch.Tensor] = None, first_mask: Optional[torch.Tensor] = None):
+        """One posterior step IN PLACE on ``latent`` f32 [n_env, latent] and ``belief`` f32 [n_env, belief] (device tensors);
+        ``action`` f32 [n_env, action] or None (zeros), ``eps`` f32 [n_env, latent] or None (the posterior mean), ``first_mask`` uint8
+        [n_env] or None: a non-zero entry starts that environment from zero latent, belief and action."""
+        dev = self.device
+        if not isinstance(latent, torch.Tensor) or latent.ndim != 2:
+            raise ValueError("latent must be a [n_env, latent] tensor")
+        n_env = int(latent.shape[0])
+        x = self._posterior_obs(obs, n_env)
+        spec = self.posterior_spec
+        _check_dev(latent, torch.float32, dev, "latent", (n_env, spec.latent_size))
+        _check_dev(belief, torch.float32, dev, "belief", (n_env, spec.belief_size))
+        for name, t, dtype, shape in (("action", action, torch.float32, (n_env, spec.action_size)), ("eps", eps, torch.float32, (n_env, spec.latent_size)),
+                                      ("first_mask", first_mask, torch.uint8, (n_env,))):
+            if t is not None:
+                _check_dev(t, dtype, dev, name, shape)
+        self._posterior_call("hipets_planet_posterior_update", obs=x, obs_is_u8=int(x.dtype == torch.uint8), n_env=n_env, action=action, latent_inout=latent,
+                   belief_inout=belief, eps_or_null=eps, first_mask_or_null=first_mask)
 
     def plan_planet_cem(self, p: CemParams, x0, lower, upper, latent0: torch.Tensor, belief0: torch.Tensor, num_particles: int,
                         seed: int = 0, plan_id: int = 0, out: Optional[torch.Tensor] = None, n_env: int = 1) -> torch.Tensor:

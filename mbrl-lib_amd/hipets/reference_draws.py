@@ -75,6 +75,12 @@ def planet_rollout_draws(latent_size: int, B: int, H: int, rng: torch.Generator)
     return torch.stack([torch.randn(B, latent_size, generator=rng, device=rng.device) for _ in range(H)])
 
 
+def planet_posterior_draws(latent_size: int, n_env: int, rng: torch.Generator) -> torch.Tensor:
+    """``PlaNetModel.update_posterior`` (planet.py:592-641 -> 331-333 -> 299-305): one ``randn([n_env, latent])`` from ``rng`` -- the
+    ``rng`` argument, else the model's own generator -- on the generator's device.  (``only_posterior=True``: no prior sample is drawn.)"""
+    return torch.randn([n_env, latent_size], generator=rng, device=rng.device)
+
+
 def population_noise(shape, clipped_normal: bool) -> torch.Tensor:
     """The standard-normal draws of CEMOptimizer._sample_population on a CPU device, from torch's global generator:
     ``randn`` for the clipped-normal branch (trajectory_opt.py:116-117), otherwise mbrl.util.math.truncated_normal_
