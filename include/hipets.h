@@ -789,6 +789,21 @@ int hipets_policy_normals(hipets_engine* e, int32_t batch, int32_t act_dim, uint
 /* Launch geometry of hipets_policy_act for `batch` rows of the policy set last: a workgroup owns 16 * row_tiles rows (row_tiles = the
  * largest of 4, 2, 1 whose activations fit the LDS opt-in limit, no more than the batch needs); lds_bytes = its dynamic LDS.         */
 int hipets_policy_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles, int32_t* lds_bytes);
+/* Which form hipets_policy_act and hipets_critic_q run: engine state, like hipets_set_sac_product; host only, takes no stream (additive
+ * entry point, HIPETS_ABI_VERSION stays).
+ *   HIPETS_AGENT_KERNEL_TILE (the default)  a row's full-width activations in two LDS buffers: 64 / 32 / 16 rows per workgroup at
+ *     hidden <= 256 / 512 / 1024, the whole packed network streamed once per workgroup.
+ *   HIPETS_AGENT_KERNEL_WIDE                64 rows per workgroup at every width: layers 1 and 2 chained over column chunks of h1 (64,
+ *     128 or 256 wide, the only part of h1 in LDS), h2 accumulated in registers by a transposed product and fed to the last layer from
+ *     there, the 8 waves' partial head sums added in wave order.  LDS: max(64 x (pad16(K) + chunk + 8), 8 x 64 x (pad16(last) + 4))
+ *     floats; every shape inside the HIPETS_POLICY_MAX_* limits runs.  Reads the same packed images; same inputs, outputs, draws and
+ *     batch independence (row r of any call equals the one-row call), fp32 MFMA with fp32 accumulation -- but it SUMS IN ANOTHER ORDER,
+ *     so its results agree with the tile form's to rounding, not bit for bit (DESIGN.md section 32 has the design and measurements).
+ * While the wide form is selected hipets_policy_geometry / hipets_critic_geometry report its 4 row tiles and its LDS bytes.
+ * An unknown kind fails with HIPETS_ERR_INVALID_ARGUMENT and leaves the setting as it was.                                        */
+#define HIPETS_AGENT_KERNEL_TILE 0
+#define HIPETS_AGENT_KERNEL_WIDE 1
+int hipets_set_agent_kernel(hipets_engine* e, int32_t kind);
 /* mbpo.py:53-63 for one rollout step, on the device.  obs / next_obs DEVICE f32 [n, obs_dim], action DEVICE f32 [n, act_dim], rewards
  * DEVICE f32 [n], dones / accum_dones DEVICE uint8 [n] (non-zero = set).  The rows with accum_dones == 0 are appended in row order
  * to the staging area, DEVICE f32 [cap * (2 obs_dim + act_dim + 2)]: five arrays one behind the other, obs [cap, obs_dim], action

@@ -155,6 +155,13 @@ int hipets_set_sac_product(hipets_engine* e, int32_t kind) {
     return 0;
 }
 
+int hipets_set_agent_kernel(hipets_engine* e, int32_t kind) {
+    if (!e) return fail("null engine");
+    if (kind != HIPETS_AGENT_KERNEL_TILE && kind != HIPETS_AGENT_KERNEL_WIDE) return fail("agent kernel must be HIPETS_AGENT_KERNEL_TILE or HIPETS_AGENT_KERNEL_WIDE");
+    e->agent_kernel = kind;
+    return 0;
+}
+
 int hipets_set_particle_reduce(hipets_engine* e, int32_t kind, float kappa, int32_t worst_k) {
     if (!e) return fail("null engine");
     if (kind < HIPETS_REDUCE_MEAN || kind > HIPETS_REDUCE_WORST_K) return fail("unknown particle reduction %d (HIPETS_REDUCE_MEAN .. HIPETS_REDUCE_WORST_K)", kind);

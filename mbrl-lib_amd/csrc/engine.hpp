@@ -186,6 +186,7 @@ struct hipets_engine {
     hipets::SacBind sac{};
     int sac_last_batch = 0;
     int sac_product = HIPETS_SAC_PRODUCT_TILE;  // which kernel runs the products of an update (hipets_set_sac_product)
+    int agent_kernel = HIPETS_AGENT_KERNEL_TILE;  // which form hipets_policy_act / hipets_critic_q run (hipets_set_agent_kernel; agent_wide.hpp)
     DevBuf sac_ws, sac_one;
     // the dynamics ensemble as hipets_ensemble_set packed it (hipets_ensemble_predict, ensemble.hip); apart from the rollout model slot above
     hipets::EnsembleSnapshot ensemble;

@@ -6,6 +6,7 @@
 #include "common.hpp"
 #include "engine.hpp"
 #include "agent_forms.hpp"
+#include "agent_wide.hpp"
 #include "policy_layer.hpp"
 
 namespace hipets {
@@ -141,7 +142,15 @@ int hipets_policy_act(hipets_engine* e, const float* obs, int32_t batch, int32_t
     a.kp0 = g.kp0; a.hp = g.hp; a.nph = g.np_last; a.ld_a = g.ld_a; a.ld_b = g.ld_b;
     a.sample = sample != 0;
     a.seed = seed; a.stream_id = stream_id;
-    const hipError_t err = launch_mlp<policy_act_kernel<4>, policy_act_kernel<2>, policy_act_kernel<1>>(g, e->lds_max, batch, a, st);
+    hipError_t err;
+    if (e->agent_kernel == HIPETS_AGENT_KERNEL_WIDE) {  // the same images and arguments, the wide form's launch (agent_wide.hip)
+        WideActorArgs wa{a.obs, a.eps, a.actions, a.mean_out, a.log_std_out, {a.w1, a.w2, a.wh, a.b1, a.b2, a.bh}, a.scale, a.bias,
+                         a.B, a.obs_dim, a.act, a.sample, a.seed, a.stream_id, {}};
+        if (!agent_wide_geometry(p.obs, p.hid, 2 * p.act, e->lds_max, wa.g)) return fail("policy does not fit the wide kernel's LDS");
+        err = launch_actor_wide(wa, e->lds_max, st);
+    } else {
+        err = launch_mlp<policy_act_kernel<4>, policy_act_kernel<2>, policy_act_kernel<1>>(g, e->lds_max, batch, a, st);
+    }
     if (err != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "policy kernel launch failed: %s", hipGetErrorString(err));
     return 0;
 }
@@ -160,6 +169,7 @@ int hipets_policy_normals(hipets_engine* e, int32_t batch, int32_t act_dim, uint
 
 int hipets_policy_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles, int32_t* lds_bytes) {
     if (!e || !e->policy.set) return fail("engine has no policy (call hipets_policy_set)");
+    if (e->agent_kernel == HIPETS_AGENT_KERNEL_WIDE) return wide_geometry_query(batch, e->policy.obs, e->policy.hid, 2 * e->policy.act, e->lds_max, row_tiles, lds_bytes);
     return mlp_geometry_query(batch, policy_geometry(e, batch), row_tiles, lds_bytes);
 }
 

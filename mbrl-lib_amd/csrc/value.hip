@@ -6,6 +6,7 @@
 #include <hip/hip_runtime.h>
 
 #include "common.hpp"
+#include "agent_wide.hpp"
 #include "engine.hpp"
 #include "policy_layer.hpp"
 #include "returns_kernel.hpp"
@@ -134,13 +135,26 @@ int hipets_critic_q(hipets_engine* e, const float* obs, const float* actions, in
     a.w = e->critic.w.as<float>(); a.b = e->critic.b.as<float>();
     a.B = batch; a.obs_dim = e->critic.obs; a.act = e->critic.act;
     a.kp0 = g.kp0; a.hp = g.hp; a.ld_a = g.ld_a; a.ld_b = g.ld_b;
-    const hipError_t err = launch_mlp<critic_q_kernel<4>, critic_q_kernel<2>, critic_q_kernel<1>>(g, e->lds_max, batch, a, st);
+    hipError_t err;
+    if (e->agent_kernel == HIPETS_AGENT_KERNEL_WIDE) {  // the same images, the wide form's launch (agent_wide.hip)
+        const size_t n1 = (size_t)g.kp0 * g.hp, n2 = (size_t)g.hp * g.hp, nw = n1 + n2 + (size_t)g.hp * kTile, nb = (size_t)2 * g.hp + kTile;
+        WideCriticArgs wa{obs, actions, q1, q2, qmin, {}, batch, a.obs_dim, a.act, {}};
+        for (int net = 0; net < 2; ++net) {
+            const float *w = a.w + net * nw, *b = a.b + net * nb;
+            wa.net[net] = {w, w + n1, w + n1 + n2, b, b + g.hp, b + 2 * g.hp};
+        }
+        if (!agent_wide_geometry(a.obs_dim + a.act, e->critic.hid, kTile, e->lds_max, wa.g)) return fail("critic does not fit the wide kernel's LDS");
+        err = launch_critic_wide(wa, e->lds_max, st);
+    } else {
+        err = launch_mlp<critic_q_kernel<4>, critic_q_kernel<2>, critic_q_kernel<1>>(g, e->lds_max, batch, a, st);
+    }
     if (err != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "critic kernel launch failed: %s", hipGetErrorString(err));
     return 0;
 }
 
 int hipets_critic_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles, int32_t* lds_bytes) {
     if (!e || !e->critic.set) return fail("engine has no critic (call hipets_critic_set)");
+    if (e->agent_kernel == HIPETS_AGENT_KERNEL_WIDE) return wide_geometry_query(batch, e->critic.obs + e->critic.act, e->critic.hid, kTile, e->lds_max, row_tiles, lds_bytes);
     return mlp_geometry_query(batch, critic_geometry(e, batch), row_tiles, lds_bytes);
 }
 

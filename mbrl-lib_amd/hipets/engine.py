@@ -69,6 +69,7 @@ class Engine:
         self.planet_spec = None
         self.comm_world, self.comm_rank = 1, 0
         self.comm_group = None  # torch.distributed group of the communicator's ranks (hipets.dist.init_engine_comm)
+        self.agent_kernel = "tile"  # (the library's initial value; set_agent_kernel)
         self.plan_mode = "fast"  # (the library's initial value; every fused plan sets its objective's mode: optimizers._prepare_fused)
         self.reduce = ParticleReduce()  # (the library's initial value, the mean; every objective sets its own: _Objective.bind_model)
         self._trace = None
@@ -760,10 +761,12 @@ class Engine:
         return dims
 
     def policy_act(self, obs: torch.Tensor, *, sample: bool = False, seed: int = 0, stream_id: int = 0, eps: Optional[torch.Tensor] = None,
-                   out: Optional[torch.Tensor] = None, taps: bool = False):
+                   out: Optional[torch.Tensor] = None, taps: bool = False, kernel: Optional[str] = None):
         """The actor's forward for ``obs`` f32 [B, obs_dim] on the device -> actions f32 [B, act_dim] (hipets_policy_act): the
         policy's mean action, or with ``sample`` a draw with ``eps`` f32 [B, act_dim] (None: drawn in-kernel from (seed, stream_id),
-        see :meth:`policy_normals`).  ``taps``: returns (actions, mean, log_std), the heads before tanh."""
+        see :meth:`policy_normals`).  ``taps``: returns (actions, mean, log_std), the heads before tanh.  ``kernel``: "tile" or "wide",
+        set for the call and put back (None: the engine's setting, :meth:`set_agent_kernel`)."""
+        setting = self._agent_setting(kernel)
         obs_dim, _, act_dim = self._slot_dims("policy", "policy_set")
         dev = self.device
         if not isinstance(obs, torch.Tensor) or obs.ndim != 2 or int(obs.shape[0]) < 1:
@@ -778,8 +781,9 @@ class Engine:
             _check_dev(out, torch.float32, dev, "out", (B, act_dim))
         mean = torch.empty_like(out) if taps else None
         log_std = torch.empty_like(out) if taps else None
-        self._call("hipets_policy_act", obs=obs, batch=B, sample=int(bool(sample)), seed=int(seed), stream_id=int(stream_id), eps=eps,
-                   actions=out, mean_out=mean, log_std_out=log_std)
+        with setting:
+            self._call("hipets_policy_act", obs=obs, batch=B, sample=int(bool(sample)), seed=int(seed), stream_id=int(stream_id), eps=eps,
+                       actions=out, mean_out=mean, log_std_out=log_std)
         return (out, mean, log_std) if taps else out
 
     def policy_normals(self, batch: int, act_dim: int, seed: int = 0, stream_id: int = 0) -> torch.Tensor:
@@ -788,15 +792,34 @@ class Engine:
         self._call("hipets_policy_normals", batch=int(batch), act_dim=int(act_dim), seed=int(seed), stream_id=int(stream_id), out=out)
         return out
 
-    def policy_geometry(self, batch: int):
-        """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of a :meth:`policy_act` of ``batch`` rows."""
+    def policy_geometry(self, batch: int, kernel: Optional[str] = None):
+        """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of a :meth:`policy_act` of ``batch`` rows
+        under ``kernel``."""
         self._slot_dims("policy", "policy_set")
-        return self._geometry("hipets_policy_geometry", batch)
+        return self._geometry("hipets_policy_geometry", batch, kernel)
 
-    def _geometry(self, symbol: str, batch: int):
+    def _geometry(self, symbol: str, batch: int, kernel: Optional[str] = None):
+        setting = self._agent_setting(kernel)
         r, lds = C.c_int32(), C.c_int32()
-        self._query(symbol, batch=int(batch), row_tiles=C.byref(r), lds_bytes=C.byref(lds))
+        with setting:
+            self._query(symbol, batch=int(batch), row_tiles=C.byref(r), lds_bytes=C.byref(lds))
         return r.value, lds.value
+
+    def _agent_setting(self, kernel: Optional[str]):
+        """The engine's agent kernel held at ``kernel`` for one call (None: as it is); ValueError for an unknown name, before any call."""
+        current = getattr(self, "agent_kernel", "tile")  # (the library's initial value)
+        if kernel is not None and kernel not in _lib.AGENT_KERNEL:
+            raise ValueError(f"kernel must be one of {tuple(_lib.AGENT_KERNEL)}, not {kernel!r}")
+        return self._setting("hipets_set_agent_kernel", _lib.AGENT_KERNEL, current if kernel is None else kernel, current)
+
+    def set_agent_kernel(self, kernel: str):
+        """Which form :meth:`policy_act`, :meth:`critic_q` and their geometry queries run when called without ``kernel=``
+        (hipets_set_agent_kernel): "tile", the library's initial value, or "wide" -- 64 rows per workgroup at every hidden width, another
+        summation order."""
+        if kernel not in _lib.AGENT_KERNEL:
+            raise ValueError(f"kernel must be one of {tuple(_lib.AGENT_KERNEL)}, not {kernel!r}")
+        self._query("hipets_set_agent_kernel", kind=_lib.AGENT_KERNEL[kernel])
+        self.agent_kernel = kernel
 
     def compact_transitions(self, obs, action, next_obs, rewards, dones, accum_dones, staging, cap, offset, count_out):
         """mbpo.py:53-63 for one rollout step (hipets_compact_transitions): the rows whose ``accum_dones`` (uint8 [N], updated in
@@ -937,9 +960,11 @@ class Engine:
         self.critic_dims = (int(obs_dim), int(act_dim), hidden)
         return self.critic_dims
 
-    def critic_q(self, obs: torch.Tensor, actions: torch.Tensor, *, q1: bool = True, q2: bool = True, qmin: bool = True):
+    def critic_q(self, obs: torch.Tensor, actions: torch.Tensor, *, q1: bool = True, q2: bool = True, qmin: bool = True, kernel: Optional[str] = None):
         """The critic's forward for ``obs`` f32 [B, obs_dim] and ``actions`` f32 [B, act_dim] on the device -> (q1, q2, qmin), f32 [B]
-        each (hipets_critic_q, one launch; an output not wanted is None).  qmin = torch.min(q1, q2)."""
+        each (hipets_critic_q, one launch; an output not wanted is None).  qmin = torch.min(q1, q2).  ``kernel``: "tile" or "wide",
+        set for the call and put back (None: the engine's setting, :meth:`set_agent_kernel`)."""
+        setting = self._agent_setting(kernel)
         obs_dim, act_dim, _ = self._slot_dims("critic", "critic_set")
         dev = self.device
         if not isinstance(obs, torch.Tensor) or obs.ndim != 2 or int(obs.shape[0]) < 1:
@@ -948,13 +973,15 @@ class Engine:
         _check_dev(obs, torch.float32, dev, "obs", (B, obs_dim))
         _check_dev(actions, torch.float32, dev, "actions", (B, act_dim))
         out = [torch.empty(B, dtype=torch.float32, device=dev) if want else None for want in (q1, q2, qmin)]
-        self._call("hipets_critic_q", obs=obs, actions=actions, batch=B, q1=out[0], q2=out[1], qmin=out[2])
+        with setting:
+            self._call("hipets_critic_q", obs=obs, actions=actions, batch=B, q1=out[0], q2=out[1], qmin=out[2])
         return tuple(out)
 
-    def critic_geometry(self, batch: int):
-        """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of a :meth:`critic_q` of ``batch`` rows."""
+    def critic_geometry(self, batch: int, kernel: Optional[str] = None):
+        """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of a :meth:`critic_q` of ``batch`` rows
+        under ``kernel``."""
         self._slot_dims("critic", "critic_set")
-        return self._geometry("hipets_critic_geometry", batch)
+        return self._geometry("hipets_critic_geometry", batch, kernel)
 
     def discounted_returns(self, rewards: torch.Tensor, dones: torch.Tensor, pop: int, num_particles: int, *, gamma: float = 1.0,
                            terminal_values: Optional[torch.Tensor] = None, row_totals: bool = False, first_done: bool = False):

@@ -23,7 +23,7 @@ import torch
 
 from .model import UnsupportedModelError
 from .replay import DeviceReplayBuffer
-from .sac import LOG_KEYS, ReferenceSACUpdater, SACActor, SACUpdater, find_policy, make_sac_updater  # noqa: F401  (their home before hipets.sac)
+from .sac import LOG_KEYS, ReferenceSACUpdater, SACActor, SACUpdater, agent_kernel_for, find_policy, make_sac_updater  # noqa: F401  (their home before hipets.sac)
 from ._pack import pack_sac_batch, row_width, staging_views  # noqa: F401
 
 _ENVS = weakref.WeakKeyDictionary()    # a live mbrl ModelEnv -> its hipets.ModelEnv
@@ -73,15 +73,15 @@ def _penalised(env, penalty):
     return views[penalty]
 
 
-def _actor(agent, engine) -> SACActor:
-    if isinstance(agent, SACActor):
+def _actor(agent, engine, kernel: str = "tile") -> SACActor:
+    if isinstance(agent, SACActor):  # (its own kernel= stands)
         return agent
     try:
         actor = _ACTORS.get(agent)
     except TypeError:  # (an agent that cannot be weakly referenced gets a fresh actor per call)
-        return SACActor(agent, engine=engine)
-    if actor is None or actor.engine is not engine or actor.policy is not find_policy(agent):
-        actor = _ACTORS[agent] = SACActor(agent, engine=engine)
+        return SACActor(agent, engine=engine, kernel=kernel)
+    if actor is None or actor.engine is not engine or actor.policy is not find_policy(agent) or actor.kernel_choice != kernel:
+        actor = _ACTORS[agent] = SACActor(agent, engine=engine, kernel=kernel)
     return actor
 
 
@@ -130,7 +130,7 @@ def _host_copy(env, buf: torch.Tensor) -> np.ndarray:
 
 
 def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_buffer, sac_samples_action: bool, rollout_horizon: int,
-                                          batch_size: int, *, uncertainty=None):
+                                          batch_size: int, *, uncertainty=None, agent_kernel: str = "tile"):
     """``mbrl.algorithms.mbpo.rollout_model_and_populate_sac_buffer`` (mbpo.py:31-63), same signature.  ``model_env``: a
     ``hipets.ModelEnv``, or a live ``mbrl.models.ModelEnv`` (wrapped once, cached); ``agent``: what :class:`SACActor` takes, or a
     SACActor.  ``replay_buffer.sample`` stays on the host (the buffer's RNG is consumed as the reference consumes it) and the initial
@@ -145,6 +145,9 @@ def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_b
     of the buffer's cursor and the per-step counts (kept in ``sac_buffer.last_populate_counts``) and sets its ``cur_idx`` /
     ``num_stored``.  A batch larger than the buffer's capacity is a ValueError.
 
+    ``agent_kernel`` (keyword only; not in the reference): the ``kernel=`` of the :class:`SACActor` made for ``agent`` -- "tile", "wide"
+    or "auto"; a SACActor passed in keeps its own.
+
     ``uncertainty`` (keyword only; not in the reference): a :class:`hipets.UncertaintyPenalty`.  The rollout steps then run through a
     penalised view of the environment (:class:`PenalisedEnv`, made once per environment and penalty; the environment itself stays as
     it is): after every model step one statistics launch of the ensemble kernel on the step's (obs, action) and one penalty launch on
@@ -152,6 +155,7 @@ def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_b
     once and dropped from the later steps.  The reference-loop fall-backs step the same penalised view; a model the ensemble kernel
     does not cover runs the reference's loop, with one warning, over the live model's own torch forward
     (:class:`hipets.ensemble.ReferencePenalisedEnv`)."""
+    agent_kernel_for(agent_kernel, 0)  # (ValueError for an unknown name, whichever loop runs)
     try:
         env = _hip_env(model_env)
         stepper = env if uncertainty is None else _penalised(env, uncertainty)
@@ -165,7 +169,7 @@ def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_b
             model_env = ReferencePenalisedEnv(model_env, uncertainty)
         return reference_populate_loop(model_env, replay_buffer, agent, sac_buffer, sac_samples_action, rollout_horizon, batch_size)
     try:
-        actor = _actor(agent, env.engine)
+        actor = _actor(agent, env.engine, agent_kernel)
     except UnsupportedModelError as exc:
         warnings.warn(f"hipets.rollout_model_and_populate_sac_buffer: running the reference's loop over the model environment ({exc})", stacklevel=2)
         return reference_populate_loop(stepper, replay_buffer, agent, sac_buffer, sac_samples_action, rollout_horizon, batch_size)

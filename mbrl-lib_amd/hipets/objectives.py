@@ -694,7 +694,8 @@ def make_eval_fn(model, num_particles: int, callables: str = "steps", **kw):
     ``particle_reduce=`` (every objective): a :class:`ParticleReduce` or 'mean' / 'min' / 'max', the reduction over the particles.
     ``discount=`` / ``terminal_value=agent`` / ``target_critic=``: any of them returns a :class:`hipets.ValueTrajectoryEvalFn` --
     discounted returns, with an agent ``discount^H min(Q1, Q2)`` of its critic at its actor's mean action as the tail -- for closed-form
-    and row-wise callable rewards / terminations alike (``callables`` is not read then)."""
+    and row-wise callable rewards / terminations alike (``callables`` is not read then); ``agent_kernel=`` beside them picks the form of
+    the agent's actor and critic kernels ("tile", "wide" or "auto")."""
     if callables not in ("steps", "trajectory"):
         raise ValueError(f"callables must be 'steps' or 'trajectory', got {callables!r}")
     value_kw = {k: kw.pop(k) for k in ("discount", "terminal_value", "target_critic") if k in kw}

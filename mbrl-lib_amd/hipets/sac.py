@@ -35,6 +35,11 @@ def find_critic(agent, target: bool = False):
     raise UnsupportedModelError(f"{type(agent).__name__} has no {name}: expected an mbrl SACAgent, a pytorch_sac_pranz24 SAC or a QNetwork-shaped module")
 
 
+def _kernel_kw(kernel: str) -> dict:
+    """the ``kernel=`` keyword of an engine call; none for the tile form: that call is the one made before there was a choice"""
+    return {} if kernel == "tile" else {"kernel": kernel}
+
+
 def _engine_of(tensor):
     from .engine import get_engine
 
@@ -86,6 +91,38 @@ class _Snapshot(_SlotOwner):
         return dims
 
 
+AGENT_KERNELS = ("tile", "wide", "auto")
+# kernel="auto": the wide form from this hidden width on, the smallest measured width at which its median was below the tile form's
+# with ranges that do not overlap, for the actor AND the critic (profiles/agent_wide.json, DESIGN.md section 32: both won at 512 and
+# 1024; the critic also at 256, where the actor was not measured, and widths that were not measured stay on the tile form); None = it
+# won at no measured width
+AGENT_WIDE_MIN_HIDDEN = 512
+
+
+def agent_kernel_for(kernel: str, hidden: int) -> str:
+    """The form ("tile" or "wide") of the actor's and the critic's forward for an agent ``hidden`` wide under ``kernel`` ("tile", "wide"
+    or "auto").  By the hidden width alone, never by the batch: the two forms sum in different orders, and ``act(obs)`` must stay row 0
+    of the batched call."""
+    if kernel not in AGENT_KERNELS:
+        raise ValueError(f"kernel must be one of {AGENT_KERNELS}, not {kernel!r}")
+    if kernel != "auto":
+        return kernel
+    return "wide" if AGENT_WIDE_MIN_HIDDEN is not None and int(hidden) >= AGENT_WIDE_MIN_HIDDEN else "tile"
+
+
+def agent_wide_geometry(k0: int, hidden: int, last_cols: int, lds_max: int = 160 * 1024):
+    """(chunk width, h2 column tiles of the busiest wave, dynamic LDS bytes) of the wide form -- csrc/agent_wide.hpp's rule restated:
+    64 input rows [64][pad16(k0) + 4] and one h1 chunk [64][wc + 4] in LDS, wc the widest of 256, 128, 64 that fits beside the input
+    and no wider than the hidden layer needs; behind the chain the same bytes hold the 8 waves' head partials [8][64][pad16(last) + 4].
+    ``k0``: obs_dim (actor) / obs_dim + act_dim (critic); ``last_cols``: 2 act_dim / 1."""
+    kp0, hp, npl = (-(-int(v) // 16) * 16 for v in (k0, hidden, last_cols))
+    chain = lambda wc: 64 * 4 * (kp0 + 4 + wc + 4)  # noqa: E731
+    wc = 256
+    while wc > 64 and (chain(wc) > lds_max or wc // 2 >= hp):
+        wc //= 2
+    return wc, -(-(hp // 16) // 8), max(chain(wc), 8 * 64 * 4 * (npl + 4))
+
+
 class SACActor(_Snapshot):
     """``GaussianPolicy.forward / sample`` (pytorch_sac_pranz24/model.py:88-108) as ``SAC.select_action`` uses them, on the actor kernel
     (hipets_policy_act).  ``agent``: an ``mbrl.planning.SACAgent``, a ``pytorch_sac_pranz24.SAC`` or a bare ``GaussianPolicy``; anything
@@ -93,12 +130,18 @@ class SACActor(_Snapshot):
     SAC updates (``rollout_model_and_populate_sac_buffer`` does it at every call).
 
     Sampling draws eps in-kernel from (``seed``, the number of sampling calls so far): two actors with one seed and one call history
-    draw the same actions; ``last_draw`` = the (seed, stream_id) of the latest one, for ``Engine.policy_normals``."""
+    draw the same actions; ``last_draw`` = the (seed, stream_id) of the latest one, for ``Engine.policy_normals``.
+
+    ``kernel``: "tile" (the default), "wide" (64 rows per workgroup at every hidden width: hipets_set_agent_kernel; the same function
+    in another summation order) or "auto" (:func:`agent_kernel_for` picks by the hidden width).  The object applies its choice at every
+    call, so objects with different choices can share an engine."""
     slot = "policy"
 
-    def __init__(self, agent, engine=None, seed: int = 0):
+    def __init__(self, agent, engine=None, seed: int = 0, kernel: str = "tile"):
+        agent_kernel_for(kernel, 0)  # (ValueError for an unknown name, whatever the agent)
         self.policy = find_policy(agent)
         self.dims, _ = pack_policy(self.policy)  # (UnsupportedModelError for anything that is not a GaussianPolicy of the kernel's sizes)
+        self.kernel_choice, self.kernel = kernel, agent_kernel_for(kernel, self.dims[1])
         super().__init__(self.policy, engine if engine is not None else _engine_of(self.policy.linear1.weight))
         self.device, self.seed = self.engine.device, int(seed)
         self.draws = 0
@@ -121,7 +164,7 @@ class SACActor(_Snapshot):
             self.draws += 1
             stream = self.draws
             self.last_draw = (self.seed, stream)
-        return self.engine.policy_act(obs_t, sample=sample, seed=self.seed, stream_id=stream, eps=eps)
+        return self.engine.policy_act(obs_t, sample=sample, seed=self.seed, stream_id=stream, eps=eps, **_kernel_kw(self.kernel))
 
     def act(self, obs: np.ndarray, sample: bool = False, batched: bool = False, **_kwargs) -> np.ndarray:
         """``SACAgent.act`` (mbrl/planning/sac_wrapper.py:27-46): the mean action, or a sampled one; ``batched``: obs is [B, obs_dim]."""
@@ -138,12 +181,14 @@ class SACCritic(_Snapshot):
     ``target``: the agent's ``critic_target``.  Anything else raises UnsupportedModelError with the reason.  The engine holds a SNAPSHOT
     of the weights: ``refresh()`` after the critic changed (``stale()`` tells; for a target it also watches the agent's live
     ``critic``, whose optimizer step precedes every stock soft update).  ``obs_dim``: where the critic's input splits into state and
-    action; by default read off the agent's policy, else fixed by the first ``q`` call."""
+    action; by default read off the agent's policy, else fixed by the first ``q`` call.  ``kernel``: as :class:`SACActor` takes it."""
     slot = "critic"
 
-    def __init__(self, agent, engine=None, target: bool = False, obs_dim: Optional[int] = None):
+    def __init__(self, agent, engine=None, target: bool = False, obs_dim: Optional[int] = None, kernel: str = "tile"):
+        agent_kernel_for(kernel, 0)
         self.critic = find_critic(agent, target)
         (self.K, self.hidden), tensors = pack_critic(self.critic)
+        self.kernel_choice, self.kernel = kernel, agent_kernel_for(kernel, self.hidden)
         if obs_dim is None:
             l1 = getattr(getattr(getattr(agent, "sac_agent", agent), "policy", None), "linear1", None)
             if getattr(l1, "weight", None) is not None and l1.weight.ndim == 2:
@@ -182,7 +227,7 @@ class SACCritic(_Snapshot):
             raise ValueError(f"obs / actions must be [B, {self.split[0]}] / [B, {self.split[1]}], got {tuple(obs_t.shape)} / {tuple(act_t.shape)}")
         if not self.owns():  # (another critic's weights sit in the engine)
             self.refresh()
-        return self.engine.critic_q(obs_t, act_t, q1=q1, q2=q2, qmin=qmin)
+        return self.engine.critic_q(obs_t, act_t, q1=q1, q2=q2, qmin=qmin, **_kernel_kw(self.kernel))
 
 
 # ---- SAC's updates (third_party/pytorch_sac_pranz24/sac.py:76-173) ----------------------------------------------------------------

@@ -28,6 +28,7 @@ class ValueTrajectoryEvalFn(CallableTrajectoryEvalFn):
     undiscounted objective of ``ModelEnv.evaluate_action_sequences`` (model_env.py:145-191) with a discount and the SAC agent's critic
     at the mean action of its actor as the tail.  ``agent``: what :class:`SACCritic` and ``hipets.SACActor`` take (it needs both a
     Gaussian policy and a critic); ``None`` gives discounting alone.  ``target_critic``: bootstrap from ``critic_target``.
+    ``agent_kernel``: the ``kernel=`` of both ("tile", "wide" or "auto").
 
     Rewards and terminations are :class:`CallableTrajectoryEvalFn`'s: the callables where given (``reward_fn`` / ``termination_fn``, or
     the spec's custom ones; they must be row-wise), else the kernel's own reward and the closed-form termination restated over the
@@ -45,7 +46,7 @@ class ValueTrajectoryEvalFn(CallableTrajectoryEvalFn):
 
     def __init__(self, model, num_particles: int, agent=None, discount: float = 1.0, target_critic: bool = False, reward_fn=None,
                  termination_fn=None, engine=None, mode: str = "device", seed: int = 0, device=None, rng: Optional[torch.Generator] = None,
-                 check_rowwise: bool = True, max_trajectory_bytes: int = 2 << 30, particle_reduce=None):
+                 check_rowwise: bool = True, max_trajectory_bytes: int = 2 << 30, particle_reduce=None, agent_kernel: str = "tile"):
         self.discount = check_discount(discount)
         if isinstance(model, PlaNetSpec) or is_planet_model(getattr(model, "dynamics_model", model)):
             raise ValueError("value-bootstrapped objectives are not available for PlaNet latent models (no critic over latent states)")
@@ -53,8 +54,8 @@ class ValueTrajectoryEvalFn(CallableTrajectoryEvalFn):
                          particle_reduce)
         self.actor = self.critic = None
         if agent is not None:
-            self.actor = SACActor(agent, engine=self.engine)
-            self.critic = SACCritic(agent, engine=self.engine, target=target_critic, obs_dim=self.spec.obs_dim)
+            self.actor = SACActor(agent, engine=self.engine, kernel=agent_kernel)
+            self.critic = SACCritic(agent, engine=self.engine, target=target_critic, obs_dim=self.spec.obs_dim, kernel=agent_kernel)
             if self.actor.dims[0] != self.spec.obs_dim or self.actor.dims[2] != self.spec.act_dim or self.critic.split[1] != self.spec.act_dim:
                 raise ValueError(f"the agent acts on (obs {self.actor.dims[0]}, act {self.actor.dims[2]}), its critic on (obs {self.critic.split[0]}, "
                                  f"act {self.critic.split[1]}); the model has (obs {self.spec.obs_dim}, act {self.spec.act_dim})")
