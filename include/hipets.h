@@ -974,6 +974,23 @@ int hipets_ensemble_predict(hipets_engine* e, const float* obs, const float* act
  * workgroup owns 16 * row_tiles rows, row_tiles = the largest of 4, 2, 1 whose LDS need (hipets_ensemble_set) fits the opt-in limit, no
  * more than the batch needs; lds_bytes = its dynamic LDS.                                                                            */
 int hipets_ensemble_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles, int32_t* lds_bytes);
+/* Which form hipets_ensemble_predict runs: engine state, like hipets_set_agent_kernel; host only, takes no stream (additive entry
+ * point, HIPETS_ABI_VERSION stays).
+ *   HIPETS_ENSEMBLE_KERNEL_TILE (the default)  the form described above: the input, two activation buffers and the per-column variance
+ *     accumulators of a row in LDS -- 64 / 32 / 16 rows per workgroup as the model widens (16 at 393-200x4-754).
+ *   HIPETS_ENSEMBLE_KERNEL_WIDE                16 R rows per workgroup, R = 4 where 16 R x (pad16(in_dim) + 4 + pad16(hid) + 4 + 16) floats
+ *     fit the LDS opt-in limit, else R = 2, by the model's shape alone: LDS holds the kept input and ONE hidden buffer that the hidden
+ *     layers update in place; the output layer, the head and the statistics' per-(row, column) state stay in registers of the wave that
+ *     owns a mean column tile for all members; row sums go through a fixed 16-lane butterfly and the 8 waves' partials in wave order.
+ *     Reads the same packed images; same arguments, outputs, NaN rule and independence of batch, position and requested outputs, fp32
+ *     MFMA with fp32 accumulation -- but every prediction is summed k ascending in ONE accumulator (the tile form: two alternating), so
+ *     its results agree with the tile form's to rounding, not bit for bit (DESIGN.md section 33 has the design and measurements).
+ *     A model for which R = 2 does not fit runs the tile form under this setting too: nothing is refused that the tile form accepts.
+ * While the wide form is selected hipets_ensemble_geometry reports its R (whatever the batch) and its LDS bytes, or the tile form's
+ * values for a model that falls back.  An unknown kind fails with HIPETS_ERR_INVALID_ARGUMENT and leaves the setting as it was.        */
+#define HIPETS_ENSEMBLE_KERNEL_TILE 0
+#define HIPETS_ENSEMBLE_KERNEL_WIDE 1
+int hipets_set_ensemble_kernel(hipets_engine* e, int32_t kind);
 /* An uncertainty penalty and halt on a model step's rewards and dones (MOPO's r - lambda u; MOReL's halt): one elementwise launch over
  * stats DEVICE [batch, 4] (hipets_ensemble_predict), rewards DEVICE [batch] f32 and dones DEVICE [batch] uint8, both updated in place.
  * Per row, every line ONE float32 operation (no fused multiply-add), with u = stats[row * 4 + stat] (stat in 0 .. 3):

@@ -83,6 +83,12 @@ __device__ __forceinline__ f32x4 ens_activate(const int act, f32x4 z, const floa
     }
 }
 
+// the two scalar forms of the ensemble's head (both forms of hipets_ensemble_predict):
+// torch.nn.functional.softplus (beta 1, threshold 20)
+__device__ __forceinline__ float ens_softplus(const float x) { return x > 20.f ? x : log1pf(expf(x)); }
+// torch.max's NaN rule: a NaN wins and stays
+__device__ __forceinline__ float nan_max(const float acc, const float v) { return (v > acc || v != v) ? v : acc; }
+
 // one member's forward of the workgroup's rows: X -> buf0: h1 -> buf1: h2 -> buf0: h3 ... -> buf[(L - 1) & 1]: the last layer's np_last
 // columns; returns that buffer and, through `ld_last`, its row length.  A barrier follows every layer; the caller's barrier precedes the
 // first (X complete, the previous reader of the buffers done).  `w` / `b`: the member's images, layers in order.

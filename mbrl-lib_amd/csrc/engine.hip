@@ -162,6 +162,13 @@ int hipets_set_agent_kernel(hipets_engine* e, int32_t kind) {
     return 0;
 }
 
+int hipets_set_ensemble_kernel(hipets_engine* e, int32_t kind) {
+    if (!e) return fail("null engine");
+    if (kind != HIPETS_ENSEMBLE_KERNEL_TILE && kind != HIPETS_ENSEMBLE_KERNEL_WIDE) return fail("ensemble kernel must be HIPETS_ENSEMBLE_KERNEL_TILE or HIPETS_ENSEMBLE_KERNEL_WIDE");
+    e->ensemble_kernel = kind;
+    return 0;
+}
+
 int hipets_set_particle_reduce(hipets_engine* e, int32_t kind, float kappa, int32_t worst_k) {
     if (!e) return fail("null engine");
     if (kind < HIPETS_REDUCE_MEAN || kind > HIPETS_REDUCE_WORST_K) return fail("unknown particle reduction %d (HIPETS_REDUCE_MEAN .. HIPETS_REDUCE_WORST_K)", kind);

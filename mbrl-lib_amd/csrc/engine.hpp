@@ -190,6 +190,7 @@ struct hipets_engine {
     DevBuf sac_ws, sac_one;
     // the dynamics ensemble as hipets_ensemble_set packed it (hipets_ensemble_predict, ensemble.hip); apart from the rollout model slot above
     hipets::EnsembleSnapshot ensemble;
+    int ensemble_kernel = HIPETS_ENSEMBLE_KERNEL_TILE;  // which form hipets_ensemble_predict runs (hipets_set_ensemble_kernel; ensemble_wide.hpp)
     // the PlaNet posterior update as hipets_planet_posterior_set_model packed it (planet_posterior.hip)
     hipets::PosteriorSnapshot posterior;
 };

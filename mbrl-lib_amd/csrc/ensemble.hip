@@ -12,6 +12,7 @@
 #include "closed_forms.hpp"
 #include "common.hpp"
 #include "engine.hpp"
+#include "ensemble_wide.hpp"
 #include "policy_layer.hpp"
 
 namespace hipets {
@@ -52,9 +53,6 @@ struct EnsArgs {
     int members[kEnsMaxMembers];            // the n requested members, in order
 };
 
-// torch.nn.functional.softplus (beta 1, threshold 20)
-__device__ __forceinline__ float ens_softplus(const float x) { return x > 20.f ? x : log1pf(expf(x)); }
-
 // sum over the 8 lanes of a row (aligned groups of 8 consecutive lanes): every lane gets the same bits
 __device__ __forceinline__ float row_sum(float x) {
     x += __shfl_xor(x, 1);
@@ -62,9 +60,6 @@ __device__ __forceinline__ float row_sum(float x) {
     x += __shfl_xor(x, 4);
     return x;
 }
-
-// torch.max's NaN rule: a NaN wins and stays
-__device__ __forceinline__ float nan_max(const float acc, const float v) { return (v > acc || v != v) ? v : acc; }
 
 template <int R>
 __global__ __launch_bounds__(kPolicyThreads) void ensemble_predict_kernel(const EnsArgs a) {
@@ -336,6 +331,22 @@ int hipets_ensemble_predict(hipets_engine* e, const float* obs, const float* act
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
+    EnsWideArgs wa{};
+    if (e->ensemble_kernel == HIPETS_ENSEMBLE_KERNEL_WIDE &&
+        ensemble_wide_geometry(s.in_dim, s.hid, s.out_dim, s.deterministic, e->lds_max, wa.g)) {  // the same images and arguments (ensemble_wide.hip)
+        wa.obs = obs; wa.actions = actions; wa.model_in = model_in; wa.mean = mean; wa.logvar = logvar; wa.stats = stats;
+        wa.w = s.w.as<float>(); wa.b = s.b.as<float>(); wa.norm = s.norm.as<double>(); wa.lv = s.lv.as<float>(); wa.cols = s.cols.as<hipets_obs_column>();
+        wa.wmember = s.wmember; wa.bmember = s.bmember;
+        wa.B = batch; wa.n = only_elite ? s.M : s.E;
+        wa.obs_dim = s.obs_dim; wa.act_dim = s.act_dim; wa.in_dim = s.in_dim; wa.out_dim = s.out_dim; wa.n_layers = s.n_layers;
+        wa.activation = s.activation; wa.obs_process = s.obs_process; wa.normalizer = s.normalizer; wa.deterministic = s.deterministic;
+        wa.lv_per_member = s.lv_rows > 1 ? s.lv_rows : 0;
+        wa.slope = s.slope;
+        for (int i = 0; i < wa.n; ++i) wa.members[i] = only_elite ? s.members[i] : i;
+        const hipError_t werr = launch_ensemble_wide(wa, e->lds_max, st);
+        if (werr != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "wide ensemble kernel launch failed: %s", hipGetErrorString(werr));
+        return 0;
+    }
     const EnsGeo x = ensemble_geo(e, batch);
     EnsArgs a{};
     a.obs = obs; a.actions = actions; a.model_in = model_in; a.mean = mean; a.logvar = logvar; a.stats = stats;
@@ -355,6 +366,14 @@ int hipets_ensemble_predict(hipets_engine* e, const float* obs, const float* act
 
 int hipets_ensemble_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles, int32_t* lds_bytes) {
     if (!e || !e->ensemble.set) return fail("engine has no ensemble (call hipets_ensemble_set)");
+    EnsWideGeo wg{};
+    const EnsembleSnapshot& s = e->ensemble;
+    if (e->ensemble_kernel == HIPETS_ENSEMBLE_KERNEL_WIDE && ensemble_wide_geometry(s.in_dim, s.hid, s.out_dim, s.deterministic, e->lds_max, wg)) {
+        if (batch < 1) return fail("bad batch");
+        if (row_tiles) *row_tiles = wg.R;  // (by the shape alone)
+        if (lds_bytes) *lds_bytes = wg.lds;
+        return 0;
+    }
     return mlp_geometry_query(batch, ensemble_geo(e, batch).g, row_tiles, lds_bytes);
 }
 

@@ -55,6 +55,7 @@ SAC_N_PTRS, SAC_MAX_BATCH = 78, 1024  # HIPETS_SAC_N_PTRS, HIPETS_SAC_MAX_BATCH
 SAC_PRODUCT = {"tile": 0, "blocked": 1}  # HIPETS_SAC_PRODUCT_*
 CRITIC_N_PTRS = 12  # HIPETS_CRITIC_N_PTRS
 AGENT_KERNEL = {"tile": 0, "wide": 1}  # HIPETS_AGENT_KERNEL_*
+ENSEMBLE_KERNEL = {"tile": 0, "wide": 1}  # HIPETS_ENSEMBLE_KERNEL_*
 # HIPETS_ENCODER_MAX_* / HIPETS_POSTERIOR_MAX_*: conv layers, channels, kernel, stride, image side, flattened encoding, environments,
 # outputs of one layer per image; latent, action, belief, hidden
 ENCODER_MAX = {"convs": 6, "channels": 512, "kernel": 8, "stride": 4, "image": 128, "flat": 4096, "env": 64, "layer_floats": 1 << 20}
@@ -249,6 +250,7 @@ SYMBOLS = {
     "hipets_policy_normals": _sig("e batch:i32 act_dim:i32 seed:u64 stream_id:u64 out stream"),
     "hipets_policy_geometry": _sig("e batch:i32 row_tiles:i32* lds_bytes:i32*"),
     "hipets_set_agent_kernel": _sig("e kind:i32"),
+    "hipets_set_ensemble_kernel": _sig("e kind:i32"),
     "hipets_compact_transitions": _sig("e obs action next_obs rewards dones accum_dones n:i32 obs_dim:i32 act_dim:i32 staging cap:i64 offset "
                                        "count_out stream"),
     "hipets_ring_compact_transitions": _sig("e obs action next_obs rewards dones accum_dones n:i32 obs_dim:i32 act_dim:i32 ring capacity:i64 "

@@ -70,6 +70,7 @@ class Engine:
         self.comm_world, self.comm_rank = 1, 0
         self.comm_group = None  # torch.distributed group of the communicator's ranks (hipets.dist.init_engine_comm)
         self.agent_kernel = "tile"  # (the library's initial value; set_agent_kernel)
+        self.ensemble_kernel = "tile"  # (the library's initial value; set_ensemble_kernel)
         self.plan_mode = "fast"  # (the library's initial value; every fused plan sets its objective's mode: optimizers._prepare_fused)
         self.reduce = ParticleReduce()  # (the library's initial value, the mean; every objective sets its own: _Objective.bind_model)
         self._trace = None
@@ -1030,12 +1031,14 @@ class Engine:
 
     def ensemble_predict(self, obs: Optional[torch.Tensor] = None, actions: Optional[torch.Tensor] = None, *,
                          model_in: Optional[torch.Tensor] = None, only_elite: bool = False, mean: bool = True, logvar: bool = True,
-                         stats: bool = False):
+                         stats: bool = False, kernel: Optional[str] = None):
         """Every requested member's forward of the same rows in one launch (hipets_ensemble_predict): from ``obs`` f32 [B, obs_dim] and
         ``actions`` f32 [B, act_dim], or from a ready ``model_in`` f32 [B, in_dim].  Returns (mean [n, B, out_dim], logvar [n, B,
         out_dim], stats [B, 4]) on the device, None for an output not wanted; n = all members, or with ``only_elite`` the spec's
-        member list.  The columns of ``stats``: ``_lib.ENSEMBLE_STATS``."""
+        member list.  The columns of ``stats``: ``_lib.ENSEMBLE_STATS``.  ``kernel``: "tile" or "wide", set for the call and put back
+        (None: the engine's setting, :meth:`set_ensemble_kernel`)."""
         spec, dev = self._ensemble_spec(), self.device
+        setting = self._ensemble_setting(kernel)
         raw = obs is not None or actions is not None
         if raw == (model_in is not None) or (raw and (obs is None or actions is None)):
             raise ValueError("give either obs and actions, or model_in")
@@ -1053,14 +1056,32 @@ class Engine:
         n = len(spec.members) if only_elite else spec.ensemble_size
         out = [torch.empty(shape, dtype=torch.float32, device=dev) if want else None
                for want, shape in ((mean, (n, B, spec.out_dim)), (logvar, (n, B, spec.out_dim)), (stats, (B, 4)))]
-        self._call("hipets_ensemble_predict", obs=obs, actions=actions, model_in=model_in, batch=B, only_elite=int(bool(only_elite)),
-                   mean=out[0], logvar=out[1], stats=out[2])
+        with setting:
+            self._call("hipets_ensemble_predict", obs=obs, actions=actions, model_in=model_in, batch=B, only_elite=int(bool(only_elite)),
+                       mean=out[0], logvar=out[1], stats=out[2])
         return tuple(out)
 
-    def ensemble_geometry(self, batch: int):
-        """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of an :meth:`ensemble_predict` of ``batch`` rows."""
+    def ensemble_geometry(self, batch: int, kernel: Optional[str] = None):
+        """(row tiles per workgroup -- a workgroup owns 16 of them rows --, dynamic LDS bytes) of an :meth:`ensemble_predict` of ``batch``
+        rows under ``kernel`` (None: the engine's setting)."""
         self._ensemble_spec()
-        return self._geometry("hipets_ensemble_geometry", batch)
+        with self._ensemble_setting(kernel):
+            return self._geometry("hipets_ensemble_geometry", batch)
+
+    def _ensemble_setting(self, kernel: Optional[str]):
+        current = getattr(self, "ensemble_kernel", "tile")  # (the library's initial value)
+        if kernel is not None and kernel not in _lib.ENSEMBLE_KERNEL:
+            raise ValueError(f"kernel must be one of {tuple(_lib.ENSEMBLE_KERNEL)}, not {kernel!r}")
+        return self._setting("hipets_set_ensemble_kernel", _lib.ENSEMBLE_KERNEL, current if kernel is None else kernel, current)
+
+    def set_ensemble_kernel(self, kernel: str):
+        """Which form :meth:`ensemble_predict` runs when the call names none (hipets_set_ensemble_kernel): "tile", the library's initial
+        value, or "wide" -- 64 rows per workgroup (32 for a very wide input), one hidden buffer in LDS, the output layer and the
+        statistics' state in registers; another summation order, so equal to the tile form to rounding, not bit for bit."""
+        if kernel not in _lib.ENSEMBLE_KERNEL:
+            raise ValueError(f"kernel must be one of {tuple(_lib.ENSEMBLE_KERNEL)}, not {kernel!r}")
+        self._query("hipets_set_ensemble_kernel", kind=_lib.ENSEMBLE_KERNEL[kernel])
+        self.ensemble_kernel = kernel
 
     def uncertainty_penalty(self, stats: torch.Tensor, stat: int, coef: float, rewards: torch.Tensor, dones: Optional[torch.Tensor] = None, *,
                             halt_threshold: Optional[float] = None, halt_reward: Optional[float] = None):

@@ -74,15 +74,52 @@ def _as_model_env(dm):
                                  action_space=box(in_dim - obs_in), device=getattr(dm, "device", None))
 
 
+ENSEMBLE_KERNELS = ("tile", "wide", "auto")
+# kernel="auto": the wide form where it measured faster than the tile form with the routes taking turns (profiles/ensemble_wide.json,
+# DESIGN.md section 33): models whose output layer is at least this many columns wide (pad16(out_total)).  None: nowhere.
+ENSEMBLE_WIDE_MIN_OUT_COLS = 768
+
+
+def ensemble_wide_geometry(in_dim: int, hid: int, out_dim: int, deterministic: bool = False, lds_max: int = 160 * 1024):
+    """(row tiles R, mean column tiles per wave T, hidden column tiles per wave TH, dynamic LDS bytes) of the wide form, or None where the
+    wide setting runs the tile form -- csrc/ensemble_wide.hpp's rule restated: LDS holds 16 R rows of the input (pad16(in) + 4 floats),
+    of ONE hidden buffer (pad16(hid) + 4) and 2 x 8 partial row sums; R = 4 where that fits and a wave owns at most two hidden and three
+    mean column tiles, else R = 2 with two hidden tiles, or up to eight beside at most two mean tiles.  By the shape alone."""
+    kp0, hp, outp = (-(-int(v) // 16) * 16 for v in (in_dim, hid, out_dim))
+    t, th = -(-(outp // 16) // 8), -(-(hp // 16) // 8)
+    for r in (4, 2):
+        lds = 16 * r * 4 * (kp0 + 4 + hp + 4 + 16)
+        fits = (th <= 2 and t <= 3) if r == 4 else (t <= 4 if th <= 2 else (th <= 8 and t <= 2))
+        if lds <= lds_max and fits:
+            return r, t, th, lds
+    return None
+
+
+def ensemble_kernel_for(kernel: str, out_dim: int, deterministic: bool = False) -> str:
+    """The form ("tile" or "wide") of the ensemble's forward under ``kernel`` ("tile", "wide" or "auto").  By the model's shape alone,
+    never by the batch: the two forms sum in different orders, and a row must keep its bits across batch sizes."""
+    if kernel not in ENSEMBLE_KERNELS:
+        raise ValueError(f"kernel must be one of {ENSEMBLE_KERNELS}, not {kernel!r}")
+    if kernel != "auto":
+        return kernel
+    cols = -(-int(out_dim if deterministic else 2 * out_dim) // 16) * 16
+    return "wide" if ENSEMBLE_WIDE_MIN_OUT_COLS is not None and cols >= ENSEMBLE_WIDE_MIN_OUT_COLS else "tile"
+
+
 class EnsemblePredictor(_SlotOwner):
     """All members' predictions for a batch, and their uncertainty statistics, on the ensemble kernel.  ``model``: what
     ``hipets.ModelEnv`` accepts -- a live ``mbrl.models.ModelEnv`` (or a ``hipets.ModelEnv`` over one), a ``ModelSpec`` -- or a bare
     ``OneDTransitionRewardModel``.  A model the kernel does not cover (bf16 precisions, more than 16 members, widths past the limits)
     raises UnsupportedModelError here.  The engine holds a SNAPSHOT: it is taken again when ``model_version`` says the live model was
-    trained in between, or when another predictor's model sits in the engine."""
+    trained in between, or when another predictor's model sits in the engine.
+
+    ``kernel``: "tile" (the default), "wide" (hipets_set_ensemble_kernel: 64 rows per workgroup, the output layer and the statistics in
+    registers; the same function in another summation order) or "auto" (:func:`ensemble_kernel_for` picks by the model's shape).  The
+    object applies its choice at every call and puts the engine's setting back."""
     slot = "ensemble"
 
-    def __init__(self, model, engine=None, device=None):
+    def __init__(self, model, engine=None, device=None, kernel: str = "tile"):
+        ensemble_kernel_for(kernel, 1)  # (ValueError for an unknown name, whatever the model)
         if hasattr(model, "_eval") and hasattr(model, "spec"):  # a hipets.ModelEnv: the model it was built from
             engine = engine if engine is not None else model.engine
             model = model._eval._live if model._eval._live is not None else model.spec
@@ -95,6 +132,7 @@ class EnsemblePredictor(_SlotOwner):
             self._version = model_version(self._live)
         self.spec.validate()
         check_ensemble_shape(self.spec)  # (before anything touches a device)
+        self.kernel_choice, self.kernel = kernel, ensemble_kernel_for(kernel, self.spec.out_dim, self.spec.deterministic)
         if engine is None:
             from .engine import get_engine
 
@@ -127,25 +165,28 @@ class EnsemblePredictor(_SlotOwner):
         """(mean [n, B, out_dim], logvar [n, B, out_dim] or None for a deterministic model) of raw ``obs`` [B, obs_dim] / ``act`` [B,
         act_dim]: the model's own obs_process, concatenation and normaliser, then every member's forward."""
         self.refresh()
-        mean, logvar, _ = self.engine.ensemble_predict(self._dev(obs), self._dev(act), only_elite=only_elite, logvar=not self.spec.deterministic)
+        mean, logvar, _ = self.engine.ensemble_predict(self._dev(obs), self._dev(act), only_elite=only_elite, logvar=not self.spec.deterministic,
+                                                         kernel=self.kernel)
         return mean, logvar
 
     def forward(self, model_in, only_elite: bool = False):
         """``model.forward(x, use_propagation=False)`` for a ready model input ``x`` [B, in_dim]: (mean, logvar | None), [n, B, out_dim]."""
         self.refresh()
-        mean, logvar, _ = self.engine.ensemble_predict(model_in=self._dev(model_in), only_elite=only_elite, logvar=not self.spec.deterministic)
+        mean, logvar, _ = self.engine.ensemble_predict(model_in=self._dev(model_in), only_elite=only_elite, logvar=not self.spec.deterministic,
+                                                         kernel=self.kernel)
         return mean, logvar
 
     def uncertainty(self, obs, act, only_elite: bool = True) -> torch.Tensor:
         """stats f32 [B, 4] -- max_std, disagreement, total_std, max_deviation (hipets_ensemble_predict) -- of raw ``obs`` / ``act``,
         reduced over the members inside the launch: no [n, B, out_dim] tensor is written."""
         self.refresh()
-        return self.engine.ensemble_predict(self._dev(obs), self._dev(act), only_elite=only_elite, mean=False, logvar=False, stats=True)[2]
+        return self.engine.ensemble_predict(self._dev(obs), self._dev(act), only_elite=only_elite, mean=False, logvar=False, stats=True,
+                                            kernel=self.kernel)[2]
 
     def geometry(self, batch: int):
         """(row tiles per workgroup, dynamic LDS bytes) of a launch over ``batch`` rows"""
         self.refresh()
-        return self.engine.ensemble_geometry(batch)
+        return self.engine.ensemble_geometry(batch, kernel=self.kernel)
 
     def penalise(self, penalty: UncertaintyPenalty, obs: torch.Tensor, act: torch.Tensor, rewards: torch.Tensor, dones: torch.Tensor):
         """One statistics launch on the step's (``obs``, ``act``) and one penalty launch on its ``rewards`` f32 [B] / ``dones`` (bool or

@@ -46,11 +46,11 @@ class PenalisedEnv:
     ensemble kernel on the step's (obs, action), one penalty launch on its rewards and dones).  The environment itself is not changed:
     whoever else holds it steps it unpenalised, and its counters and streams advance whichever of the two is stepped."""
 
-    def __init__(self, env, penalty):
+    def __init__(self, env, penalty, ensemble_kernel: str = "tile"):
         from .ensemble import EnsemblePredictor
 
         self.env, self.penalty = env, penalty
-        self.predictor = EnsemblePredictor(env, engine=env.engine)  # (UnsupportedModelError for a model the kernel does not cover)
+        self.predictor = EnsemblePredictor(env, engine=env.engine, kernel=ensemble_kernel)  # (UnsupportedModelError for a model the kernel does not cover)
         self.engine, self.device = env.engine, env.device
 
     def reset(self, *args, **kwargs):
@@ -60,17 +60,18 @@ class PenalisedEnv:
         return self.env._step(actions, model_state, sample, self.predictor, self.penalty)
 
 
-def _penalised(env, penalty):
-    """the penalised view of ``env`` for ``penalty``, made once per pair and kept with the environment (its step is not touched); an
-    environment that carries that very penalty is its own"""
+def _penalised(env, penalty, ensemble_kernel: str = "tile"):
+    """the penalised view of ``env`` for ``penalty`` and the predictor's ``ensemble_kernel``, made once per such pair and kept with the
+    environment (its step is not touched); an environment that carries that very penalty is its own"""
     if getattr(env, "uncertainty", None) == penalty:
         return env
     if not hasattr(env, "_step"):
         raise UnsupportedModelError("the model environment has no step that takes an uncertainty penalty")
     views = env.__dict__.setdefault("_penalised_views", {})  # (a global weak map would keep every environment alive: a view holds its own)
-    if penalty not in views:
-        views[penalty] = PenalisedEnv(env, penalty)
-    return views[penalty]
+    key = penalty if ensemble_kernel == "tile" else (penalty, ensemble_kernel)
+    if key not in views:
+        views[key] = PenalisedEnv(env, penalty, ensemble_kernel)
+    return views[key]
 
 
 def _actor(agent, engine, kernel: str = "tile") -> SACActor:
@@ -130,7 +131,8 @@ def _host_copy(env, buf: torch.Tensor) -> np.ndarray:
 
 
 def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_buffer, sac_samples_action: bool, rollout_horizon: int,
-                                          batch_size: int, *, uncertainty=None, agent_kernel: str = "tile"):
+                                          batch_size: int, *, uncertainty=None, agent_kernel: str = "tile",
+                                          ensemble_kernel: str = "tile"):
     """``mbrl.algorithms.mbpo.rollout_model_and_populate_sac_buffer`` (mbpo.py:31-63), same signature.  ``model_env``: a
     ``hipets.ModelEnv``, or a live ``mbrl.models.ModelEnv`` (wrapped once, cached); ``agent``: what :class:`SACActor` takes, or a
     SACActor.  ``replay_buffer.sample`` stays on the host (the buffer's RNG is consumed as the reference consumes it) and the initial
@@ -154,11 +156,17 @@ def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_b
     its rewards and dones, so both the staging area and the ring store the penalised rewards and dones, and a halted row is stored
     once and dropped from the later steps.  The reference-loop fall-backs step the same penalised view; a model the ensemble kernel
     does not cover runs the reference's loop, with one warning, over the live model's own torch forward
-    (:class:`hipets.ensemble.ReferencePenalisedEnv`)."""
-    agent_kernel_for(agent_kernel, 0)  # (ValueError for an unknown name, whichever loop runs)
+    (:class:`hipets.ensemble.ReferencePenalisedEnv`).
+
+    ``ensemble_kernel`` (keyword only; not in the reference): the ``kernel=`` of the penalised view's :class:`hipets.EnsemblePredictor`
+    -- "tile", "wide" or "auto" --, for the staging and the ring path alike; without ``uncertainty`` it is only checked."""
+    from .ensemble import ensemble_kernel_for
+
+    agent_kernel_for(agent_kernel, 0)
+    ensemble_kernel_for(ensemble_kernel, 1)  # (ValueError for an unknown name, whichever loop runs)
     try:
         env = _hip_env(model_env)
-        stepper = env if uncertainty is None else _penalised(env, uncertainty)
+        stepper = env if uncertainty is None else _penalised(env, uncertainty, ensemble_kernel)
     except UnsupportedModelError as exc:
         if uncertainty is not None and not hasattr(model_env, "dynamics_model"):
             raise  # (no live model to run the reference's forward on)
