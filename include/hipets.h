@@ -757,6 +757,24 @@ int hipets_train_eval_loss(hipets_engine* e, const hipets_train_desc* d, const f
 #define HIPETS_TRAIN_KERNEL_SPLIT 1
 #define HIPETS_TRAIN_SPLIT_MAX_BATCH 1024
 int hipets_set_train_kernel(hipets_engine* e, int32_t kind);
+/* Wide models: engine state, like hipets_set_train_kernel; host only, takes no stream (additive entry point, HIPETS_ABI_VERSION stays).
+ *   HIPETS_TRAIN_WIDTH_NARROW (the default)  everything above, hid <= HIPETS_TRAIN_MAX_HID.
+ *   HIPETS_TRAIN_WIDTH_WIDE                  hipets_train_steps / hipets_train_steps_loss run the wide step whatever hipets_set_train_kernel
+ *     says, and hipets_train_eval / hipets_train_eval_loss the wide evaluate pass; both accept hid <= HIPETS_TRAIN_WIDE_MAX_HID and
+ *     max_batch <= HIPETS_TRAIN_SPLIT_MAX_BATCH, the other limits stand.  A wide step is the row-split step with another rows kernel: a
+ *     workgroup of 32 rows keeps ONE activation panel in LDS (131 584 bytes at the limits) and every layer overwrites it in place -- the
+ *     layer's whole 32 x d result waits in the accumulators of the eight waves until all of them have read the panel -- forward, through
+ *     the loss and back along the dA chain; the dW / Adam launch and the launch that sums the partials are the row-split step's own.  The
+ *     evaluate pass runs the same forward chain, then hipets_train_eval's tail and reduction.  The semantics are
+ *     hipets_train_steps_loss' and hipets_train_eval_loss' in full (both loss kinds, per-member bounds, grad_scale, ragged rows, outside
+ *     indices, order, row_score); every element is summed k ascending in one accumulator, an order the layer's shape fixes alone, so the
+ *     results agree with the other kernels' to rounding, not bit for bit, are deterministic and do not depend on the batch size or on how
+ *     a run is cut into calls.  steps_per_launch is ignored.  (DESIGN.md section 34 has the design and the measurements.)
+ * An unknown kind fails with HIPETS_ERR_INVALID_ARGUMENT and leaves the setting as it was.                                            */
+#define HIPETS_TRAIN_WIDTH_NARROW 0
+#define HIPETS_TRAIN_WIDTH_WIDE 1
+#define HIPETS_TRAIN_WIDE_MAX_HID 1024
+int hipets_set_train_width(hipets_engine* e, int32_t kind);
 
 /* ---- MBPO model rollouts: the SAC Gaussian actor and the compacting populate step (mbrl/algorithms/mbpo.py:31-63) ----
  * Additive entry points: scalars and pointers only, no struct, HIPETS_ABI_VERSION stays.  Needs no dynamics model.

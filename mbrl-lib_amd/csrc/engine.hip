@@ -148,6 +148,13 @@ int hipets_set_train_kernel(hipets_engine* e, int32_t kind) {
     return 0;
 }
 
+int hipets_set_train_width(hipets_engine* e, int32_t kind) {
+    if (!e) return fail("null engine");
+    if (kind != HIPETS_TRAIN_WIDTH_NARROW && kind != HIPETS_TRAIN_WIDTH_WIDE) return fail("train width must be HIPETS_TRAIN_WIDTH_NARROW or HIPETS_TRAIN_WIDTH_WIDE");
+    e->train_width = kind;
+    return 0;
+}
+
 int hipets_set_sac_product(hipets_engine* e, int32_t kind) {
     if (!e) return fail("null engine");
     if (kind != HIPETS_SAC_PRODUCT_TILE && kind != HIPETS_SAC_PRODUCT_BLOCKED) return fail("sac product must be HIPETS_SAC_PRODUCT_TILE or HIPETS_SAC_PRODUCT_BLOCKED");

@@ -176,6 +176,7 @@ struct hipets_engine {
     DevBuf train_slab, train_partial;
     // which kernels the steps run (hipets_set_train_kernel), and the split step's loss / grad_sq partials (train_split.hip)
     int train_kernel = HIPETS_TRAIN_KERNEL_MEMBER;
+    int train_width = HIPETS_TRAIN_WIDTH_NARROW;  // hipets_set_train_width: WIDE runs the steps and evaluate on train_wide.hip's kernels
     DevBuf train_split_part;
     // the packed layers of the SAC actor (hipets_policy_set / _act, policy.hip) and of the SAC critic, Q1 and Q2 (hipets_critic_set / _q, value.hip)
     hipets::MlpSnapshot policy, critic;

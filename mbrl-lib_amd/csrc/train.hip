@@ -7,7 +7,8 @@
 // tile_walk.hpp the tiles' numbering and the lane-to-element map, adam.hpp the optimizer's rule, train_math.hpp the activations and
 // the MSE tail (mse_tail; the NLL tail and the Kahan sum stand here and in train_split.hip, see there).  The host side by job: train_check (the arguments), train_slab,
 // train_fill and train_fill_step (train.hpp: the slab's layout, what the argument blocks share), train_chunk and the chunk loop.
-// Under HIPETS_TRAIN_KERNEL_SPLIT the steps leave for train_split.hip behind the same checks.
+// Under HIPETS_TRAIN_KERNEL_SPLIT the steps leave for train_split.hip behind the same checks; under HIPETS_TRAIN_WIDTH_WIDE the steps and
+// the evaluate tiles run on train_wide.hip's kernels, with its hid limit.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,6 +22,7 @@
 #include "train.hpp"
 #include "train_math.hpp"
 #include "train_split.hpp"
+#include "train_wide.hpp"
 
 namespace hipets {
 
@@ -348,14 +350,15 @@ __global__ __launch_bounds__(256) void train_eval_reduce_kernel(const TrainEvalA
 
 // ---- the C ABI's argument checks (hipets_train_steps / hipets_train_eval below) ----
 
-// max_batch_limit: of the kernels the call runs (the member kernel's, or the split step's under HIPETS_TRAIN_KERNEL_SPLIT)
-int train_check(const hipets_train_desc* d, bool adam, int loss_kind, int max_batch_limit = kTrainMaxBatch) {
+// max_batch_limit, hid_limit: of the kernels the call runs (the member kernel's; the split step's batch limit under
+// HIPETS_TRAIN_KERNEL_SPLIT; the wide kernels' batch and hid limits under HIPETS_TRAIN_WIDTH_WIDE)
+int train_check(const hipets_train_desc* d, bool adam, int loss_kind, int max_batch_limit = kTrainMaxBatch, int hid_limit = kTrainMaxHid) {
     if (!d) return fail("null train desc");
     if (loss_kind != HIPETS_TRAIN_LOSS_NLL && loss_kind != HIPETS_TRAIN_LOSS_MSE) return fail("unknown loss kind %d", loss_kind);
     if (d->ensemble_size < 1 || d->ensemble_size > kTrainMaxMembers) return fail("ensemble_size %d outside [1, %d]", d->ensemble_size, kTrainMaxMembers);
     if (d->n_layers < 2 || d->n_layers > HIPETS_MAX_LAYERS) return fail("n_layers %d outside [2, %d]", d->n_layers, HIPETS_MAX_LAYERS);
     if (d->in_dim < 1 || d->in_dim > kTrainMaxIn) return fail("in_dim %d outside [1, %d]", d->in_dim, kTrainMaxIn);
-    if (d->hid < 1 || d->hid > kTrainMaxHid) return fail("hid %d outside [1, %d]", d->hid, kTrainMaxHid);
+    if (d->hid < 1 || d->hid > hid_limit) return fail("hid %d outside [1, %d]", d->hid, hid_limit);
     if (d->out_dim < 1 || d->out_dim > kTrainMaxOut) return fail("out_dim %d outside [1, %d]", d->out_dim, kTrainMaxOut);
     if (d->activation < HIPETS_ACT_RELU || d->activation > HIPETS_ACT_SIGMOID) return fail("unknown activation %d", d->activation);
     if (d->max_batch < 1 || d->max_batch > max_batch_limit) return fail("max_batch %d outside [1, %d]", d->max_batch, max_batch_limit);
@@ -398,13 +401,19 @@ hipError_t launch_train_steps(const TrainStepArgs& a, int loss_kind, hipStream_t
     return hipGetLastError();
 }
 
-hipError_t launch_train_eval(const TrainEvalArgs& a, hipStream_t st) {
+// wide: the tiles run on train_wide.hip's kernel (one in-place panel, hidden widths up to 1024); the reduction is the same
+hipError_t launch_train_eval(const TrainEvalArgs& a, hipStream_t st, bool wide) {
     const size_t lds = (size_t)2 * kEvalRows * a.max_width * sizeof(float);
     static LdsOptIn once;
-    hipError_t err = full_lds_once(once, reinterpret_cast<const void*>(&train_eval_kernel), 2 * kEvalRows * kTrainMaxIn * (int)sizeof(float));
-    if (err != hipSuccess) return err;
-    hipLaunchKernelGGL(train_eval_kernel, dim3(a.tiles, a.ensemble_size), dim3(kEvalThreads), lds, st, a);
-    err = hipGetLastError();
+    hipError_t err;
+    if (wide) {
+        err = launch_train_wide_eval(a, st);
+    } else {
+        err = full_lds_once(once, reinterpret_cast<const void*>(&train_eval_kernel), 2 * kEvalRows * kTrainMaxIn * (int)sizeof(float));
+        if (err != hipSuccess) return err;
+        hipLaunchKernelGGL(train_eval_kernel, dim3(a.tiles, a.ensemble_size), dim3(kEvalThreads), lds, st, a);
+        err = hipGetLastError();
+    }
     if (err != hipSuccess) return err;
     hipLaunchKernelGGL(train_eval_reduce_kernel, dim3(a.ensemble_size), dim3(256), 0, st, a);
     return hipGetLastError();
@@ -426,8 +435,8 @@ int hipets_train_steps_loss(hipets_engine* e, const hipets_train_desc* d, const 
                             const int32_t* rows, int32_t n_steps, int64_t step0, float* loss, float* grad_sq, void* stream, int32_t loss_kind,
                             int32_t bounds_per_member, float grad_scale) {
     if (!e) return fail("null engine");
-    const bool split = e->train_kernel == HIPETS_TRAIN_KERNEL_SPLIT;
-    if (train_check(d, true, loss_kind, split ? kSplitMaxBatch : kTrainMaxBatch)) return 1;
+    const bool wide = e->train_width == HIPETS_TRAIN_WIDTH_WIDE, split = wide || e->train_kernel == HIPETS_TRAIN_KERNEL_SPLIT;
+    if (train_check(d, true, loss_kind, split ? kSplitMaxBatch : kTrainMaxBatch, wide ? kTrainWideMaxHid : kTrainMaxHid)) return 1;
     if (!std::isfinite(grad_scale) || !(grad_scale > 0.f)) return fail("grad_scale %g is not a finite positive number", (double)grad_scale);
     if (!x || !y || !idx || !rows || !loss || !grad_sq) return fail("null argument");
     if (n_rows < 1 || n_rows > INT32_MAX) return fail("n_rows %lld outside [1, 2^31)", (long long)n_rows);
@@ -437,7 +446,7 @@ int hipets_train_steps_loss(hipets_engine* e, const hipets_train_desc* d, const 
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
-    if (split) return train_split_steps(e, d, x, y, n_rows, idx, rows, n_steps, step0, loss, grad_sq, st, loss_kind, bounds_per_member, grad_scale);
+    if (split) return train_split_steps(e, d, x, y, n_rows, idx, rows, n_steps, step0, loss, grad_sq, st, loss_kind, bounds_per_member, grad_scale, wide);
     TrainStepArgs a{};
     const int L = d->n_layers, E = d->ensemble_size, Bm = d->max_batch;
     train_fill(a, d, loss_kind, x, y, n_rows);
@@ -473,7 +482,8 @@ int hipets_train_eval(hipets_engine* e, const hipets_train_desc* d, const float*
 int hipets_train_eval_loss(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows, const int32_t* order,
                            float* score, float* row_score, void* stream, int32_t loss_kind) {
     if (!e) return fail("null engine");
-    if (train_check(d, false, loss_kind)) return 1;
+    const bool wide = e->train_width == HIPETS_TRAIN_WIDTH_WIDE;
+    if (train_check(d, false, loss_kind, wide ? kSplitMaxBatch : kTrainMaxBatch, wide ? kTrainWideMaxHid : kTrainMaxHid)) return 1;
     if (!x || !y || !score) return fail("null argument");
     if (n_rows < 1 || n_rows > INT32_MAX) return fail("n_rows %lld outside [1, 2^31)", (long long)n_rows);
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
@@ -488,7 +498,7 @@ int hipets_train_eval_loss(hipets_engine* e, const hipets_train_desc* d, const f
     a.row_score = row_score;
     a.score = score;
     a.max_width = std::max(std::max(d->in_dim, d->hid), d->out_dim);
-    hipError_t err = launch_train_eval(a, st);
+    hipError_t err = launch_train_eval(a, st, wide);
     if (err != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "train eval kernel launch failed: %s", hipGetErrorString(err));
     return 0;
 }

@@ -136,6 +136,6 @@ inline void train_fill_step(Args& a, const hipets_train_desc* d, int32_t bounds_
 }
 
 hipError_t launch_train_steps(const TrainStepArgs& a, int loss_kind, hipStream_t st);
-hipError_t launch_train_eval(const TrainEvalArgs& a, hipStream_t st);
+hipError_t launch_train_eval(const TrainEvalArgs& a, hipStream_t st, bool wide);
 
 }  // namespace hipets

@@ -24,6 +24,7 @@
 #include "tile_walk.hpp"
 #include "train_math.hpp"
 #include "train_split.hpp"
+#include "train_wide.hpp"
 
 namespace hipets {
 
@@ -407,14 +408,20 @@ __global__ __launch_bounds__(64) void train_split_finish_kernel(const TrainSplit
     }
 }
 
+// wide: the rows kernel is train_wide.hip's (one in-place panel, hidden widths up to 1024); the other two launches are the same
 template <int kLoss>
-hipError_t launch_split_step(const TrainSplitArgs& a, hipStream_t st) {
+hipError_t launch_split_step(const TrainSplitArgs& a, hipStream_t st, bool wide) {
     static LdsOptIn once;
-    hipError_t err = full_lds_once(once, reinterpret_cast<const void*>(&train_rows_kernel<kLoss>), split_rows_lds_bytes(kTrainMaxIn, kTrainMaxHid));
-    if (err != hipSuccess) return err;
-    const size_t lds = (size_t)split_rows_lds_bytes(a.dims[0], a.dims[1]);
-    hipLaunchKernelGGL(train_rows_kernel<kLoss>, dim3(a.row_blocks, a.ensemble_size), dim3(kSplitRowsThreads), lds, st, a);
-    if ((err = hipGetLastError()) != hipSuccess) return err;
+    hipError_t err;
+    if (wide) {
+        if ((err = launch_train_wide_rows(a, kLoss, st)) != hipSuccess) return err;
+    } else {
+        err = full_lds_once(once, reinterpret_cast<const void*>(&train_rows_kernel<kLoss>), split_rows_lds_bytes(kTrainMaxIn, kTrainMaxHid));
+        if (err != hipSuccess) return err;
+        const size_t lds = (size_t)split_rows_lds_bytes(a.dims[0], a.dims[1]);
+        hipLaunchKernelGGL(train_rows_kernel<kLoss>, dim3(a.row_blocks, a.ensemble_size), dim3(kSplitRowsThreads), lds, st, a);
+        if ((err = hipGetLastError()) != hipSuccess) return err;
+    }
     hipLaunchKernelGGL(train_dw_kernel<kLoss>, dim3(a.dw_blocks, a.n_layers, a.ensemble_size), dim3(kSplitDwThreads), 0, st, a);
     if ((err = hipGetLastError()) != hipSuccess) return err;
     hipLaunchKernelGGL(train_split_finish_kernel<kLoss>, dim3(a.ensemble_size), dim3(64), 0, st, a);
@@ -425,7 +432,7 @@ hipError_t launch_split_step(const TrainSplitArgs& a, hipStream_t st) {
 
 int train_split_steps(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows, const int32_t* idx,
                       const int32_t* rows, int32_t n_steps, int64_t step0, float* loss, float* grad_sq, hipStream_t st, int32_t loss_kind,
-                      int32_t bounds_per_member, float grad_scale) {
+                      int32_t bounds_per_member, float grad_scale, bool wide) {
     TrainSplitArgs a{};
     const int L = d->n_layers, E = d->ensemble_size, Bm = d->max_batch;
     train_fill(a, d, loss_kind, x, y, n_rows);
@@ -444,8 +451,8 @@ int train_split_steps(hipets_engine* e, const hipets_train_desc* d, const float*
         a.rows = rows + s;
         a.loss = loss + (int64_t)s * E;
         a.grad_sq = grad_sq + (int64_t)s * E;
-        const hipError_t err = loss_kind == kTrainLossMSE ? launch_split_step<kTrainLossMSE>(a, st) : launch_split_step<kTrainLossNLL>(a, st);
-        if (err != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "split train step launch failed: %s", hipGetErrorString(err));
+        const hipError_t err = loss_kind == kTrainLossMSE ? launch_split_step<kTrainLossMSE>(a, st, wide) : launch_split_step<kTrainLossNLL>(a, st, wide);
+        if (err != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "%s train step launch failed: %s", wide ? "wide" : "split", hipGetErrorString(err));
     }
     return 0;
 }

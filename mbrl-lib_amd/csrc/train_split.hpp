@@ -92,10 +92,11 @@ struct TrainSplitArgs {
 };
 
 #pragma GCC visibility push(hidden)
-// hipets_train_steps_loss under HIPETS_TRAIN_KERNEL_SPLIT, after its argument checks and stream entry (train.hip)
+// hipets_train_steps_loss under HIPETS_TRAIN_KERNEL_SPLIT, after its argument checks and stream entry (train.hip); wide: under
+// HIPETS_TRAIN_WIDTH_WIDE, the same step with train_wide.hip's rows kernel in place of train_rows_kernel
 int train_split_steps(hipets_engine* e, const hipets_train_desc* d, const float* x, const float* y, int64_t n_rows, const int32_t* idx,
                       const int32_t* rows, int32_t n_steps, int64_t step0, float* loss, float* grad_sq, hipStream_t st, int32_t loss_kind,
-                      int32_t bounds_per_member, float grad_scale);
+                      int32_t bounds_per_member, float grad_scale, bool wide);
 #pragma GCC visibility pop
 
 }  // namespace hipets

@@ -51,6 +51,8 @@ POLICY_MAX_OBS, POLICY_MAX_HIDDEN, POLICY_MAX_ACT = 512, 1024, 32  # HIPETS_POLI
 TRAIN_MAX_MEMBERS, TRAIN_MAX_HID, TRAIN_MAX_IN, TRAIN_MAX_OUT, TRAIN_MAX_BATCH = 16, 256, 512, 512, 256  # HIPETS_TRAIN_MAX_*
 TRAIN_KERNEL = {"member": 0, "split": 1}  # HIPETS_TRAIN_KERNEL_*
 TRAIN_SPLIT_MAX_BATCH = 1024  # HIPETS_TRAIN_SPLIT_MAX_BATCH
+TRAIN_WIDTH = {"narrow": 0, "wide": 1}  # HIPETS_TRAIN_WIDTH_*
+TRAIN_WIDE_MAX_HID = 1024  # HIPETS_TRAIN_WIDE_MAX_HID
 SAC_N_PTRS, SAC_MAX_BATCH = 78, 1024  # HIPETS_SAC_N_PTRS, HIPETS_SAC_MAX_BATCH
 SAC_PRODUCT = {"tile": 0, "blocked": 1}  # HIPETS_SAC_PRODUCT_*
 CRITIC_N_PTRS = 12  # HIPETS_CRITIC_N_PTRS
@@ -244,6 +246,7 @@ SYMBOLS = {
     "hipets_train_steps_loss": _sig("e d:TrainDesc* x y n_rows:i64 idx rows n_steps:i32 step0:i64 loss grad_sq stream loss_kind:i32 "
                                     "bounds_per_member:i32 grad_scale:f32"),
     "hipets_set_train_kernel": _sig("e kind:i32"),
+    "hipets_set_train_width": _sig("e kind:i32"),
     "hipets_train_eval_loss": _sig("e d:TrainDesc* x y n_rows:i64 order score row_score stream loss_kind:i32"),
     "hipets_policy_set": _sig("e obs_dim:i32 hidden:i32 act_dim:i32 w1 b1 w2 b2 wm bm ws bs action_scale action_bias stream"),
     "hipets_policy_act": _sig("e obs batch:i32 sample:i32 seed:u64 stream_id:u64 eps actions mean_out log_std_out stream"),

@@ -690,9 +690,12 @@ class Engine:
         BasicEnsemble).  Any of them off its default goes through hipets_train_steps_loss.
         ``kernel``: "member" (one workgroup per member, a chunk of steps per launch; max_batch <= 256) or "split" (the row-split step:
         three launches per step that spread a member over many CUs; max_batch <= 1024; ``steps_per_launch`` is ignored; same
-        semantics, sums in another order).  The engine's setting (hipets_set_train_kernel) is set for the call and put back."""
-        if kernel not in _lib.TRAIN_KERNEL:
-            raise ValueError("kernel must be 'member' or 'split'")
+        semantics, sums in another order) or "wide" (the split step with a rows kernel that keeps one in-place activation panel: hidden
+        widths up to 1024, max_batch <= 1024; hipets_set_train_width).  The engine's setting (hipets_set_train_kernel, or
+        hipets_set_train_width for "wide") is set for the call and put back."""
+        wide = kernel == "wide"
+        if not wide and kernel not in _lib.TRAIN_KERNEL:
+            raise ValueError("kernel must be 'member', 'split' or 'wide'")
         dev = self.device
         out_dim = int(y.shape[-1]) if y.dim() == 2 else -1
         _check_dev(x, torch.float32, dev, "x")
@@ -712,7 +715,7 @@ class Engine:
         losses = torch.empty(n_steps, E, dtype=torch.float32, device=dev)
         gsq = torch.empty(n_steps, E, dtype=torch.float32, device=dev)
         kw = dict(d=d, x=x, y=y, n_rows=int(x.shape[0]), idx=idx, rows=rows, n_steps=n_steps, step0=int(step0), loss=losses, grad_sq=gsq)
-        with self._setting("hipets_set_train_kernel", _lib.TRAIN_KERNEL, kernel, "member"):
+        with self._setting("hipets_set_train_kernel", _lib.TRAIN_KERNEL, "member" if wide else kernel, "member"), self._train_width(wide):
             if loss == "nll" and not bounds_per_member and float(grad_scale) == 1.0:
                 self._call("hipets_train_steps", **kw)
             else:
@@ -721,11 +724,18 @@ class Engine:
         del keep
         return losses, gsq
 
+    def _train_width(self, wide: bool):
+        """The engine's train width (hipets_set_train_width) held at "wide" for one call; nothing at "narrow", the library's value."""
+        return self._setting("hipets_set_train_width", _lib.TRAIN_WIDTH, "wide" if wide else "narrow", "narrow")
+
     def train_eval(self, weights, biases, x: torch.Tensor, y: torch.Tensor, order: Optional[torch.Tensor] = None, *,
-                   activation: str = "silu", leaky_slope: float = 0.01, row_scores: bool = False, loss: str = "nll"):
+                   activation: str = "silu", leaky_slope: float = 0.01, row_scores: bool = False, loss: str = "nll", kernel: str = "tile"):
         """GaussianMLP.eval_score averaged over rows and dims, per member: DEVICE f32 [E] (and, with ``row_scores``, the
         [E, N] per-row squared-error sums in pass order).  Asynchronous on the current stream.  ``loss`` "mse": the last layer is
-        out wide (a deterministic model), through hipets_train_eval_loss."""
+        out wide (a deterministic model), through hipets_train_eval_loss.  ``kernel``: "tile" (hidden widths up to 256) or "wide" (up to
+        1024: the wide step's forward chain; hipets_set_train_width, set for the call and put back)."""
+        if kernel not in ("tile", "wide"):
+            raise ValueError("kernel must be 'tile' or 'wide'")
         dev = self.device
         _check_dev(x, torch.float32, dev, "x")
         _check_dev(y, torch.float32, dev, "y")
@@ -738,10 +748,11 @@ class Engine:
         E = int(weights[0].shape[0])
         score = torch.empty(E, dtype=torch.float32, device=dev)
         rs = torch.empty(E, N, dtype=torch.float32, device=dev) if row_scores else None
-        if loss == "nll":
-            self._call("hipets_train_eval", d=d, x=x, y=y, n_rows=N, order=order, score=score, row_score=rs)
-        else:
-            self._call("hipets_train_eval_loss", d=d, x=x, y=y, n_rows=N, order=order, score=score, row_score=rs, loss_kind=_lib.TRAIN_LOSS[loss])
+        with self._train_width(kernel == "wide"):
+            if loss == "nll":
+                self._call("hipets_train_eval", d=d, x=x, y=y, n_rows=N, order=order, score=score, row_score=rs)
+            else:
+                self._call("hipets_train_eval_loss", d=d, x=x, y=y, n_rows=N, order=order, score=score, row_score=rs, loss_kind=_lib.TRAIN_LOSS[loss])
         del keep
         return (score, rs) if row_scores else score
 

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from ._lib import (TRAIN_MAX_BATCH as MAX_BATCH, TRAIN_MAX_HID as MAX_HID, TRAIN_MAX_IN as MAX_IN, TRAIN_MAX_MEMBERS as MAX_MEMBERS,
-                   TRAIN_MAX_OUT as MAX_OUT, TRAIN_SPLIT_MAX_BATCH as SPLIT_MAX_BATCH)  # the library's shape limits (HIPETS_TRAIN_MAX_* of include/hipets.h) under this module's names
+                   TRAIN_MAX_OUT as MAX_OUT, TRAIN_SPLIT_MAX_BATCH as SPLIT_MAX_BATCH, TRAIN_WIDE_MAX_HID as WIDE_MAX_HID)  # the library's shape limits (HIPETS_TRAIN_MAX_* of include/hipets.h) under this module's names
 from .model import UnsupportedModelError, _ACT_BY_CLASS
 
 # model_trainer.py:20-28 (the logger group's columns)
@@ -49,21 +49,21 @@ class _Kind:
         self.mlps, self.basic, self.layers, self.act, self.slope, self.loss = mlps, basic, layers, act, slope, loss
 
 
-def _read_model(model, extended: bool = False) -> _Kind:
+def _read_model(model, extended: bool = False, max_hid: int = MAX_HID) -> _Kind:
     """The model's kind and live parameters, or UnsupportedModelError.  ``extended``: deterministic GaussianMLPs (MSE loss) and
-    BasicEnsembles of one-member GaussianMLPs are accepted as well."""
+    BasicEnsembles of one-member GaussianMLPs are accepted as well.  ``max_hid``: the hidden width the trainer's kernels take."""
     mlp = getattr(model, "model", None)
     if mlp is None or not hasattr(model, "_process_batch"):
         raise UnsupportedModelError("hipets.ModelTrainer trains a OneDTransitionRewardModel" + _KEEP_STOCK)
     if hasattr(mlp, "members") and not hasattr(mlp, "hidden_layers"):
         if not extended:
             raise UnsupportedModelError("BasicEnsemble is not supported" + _KEEP_STOCK)
-        return _read_basic_ensemble(mlp)
-    layers, act, slope, loss = _read_mlp(mlp, extended)
+        return _read_basic_ensemble(mlp, max_hid)
+    layers, act, slope, loss = _read_mlp(mlp, extended, max_hid)
     return _Kind([mlp], False, [[(lin.weight, lin.bias, None)] for lin in layers], act, slope, loss)
 
 
-def _read_basic_ensemble(ens) -> _Kind:
+def _read_basic_ensemble(ens, max_hid: int = MAX_HID) -> _Kind:
     """A BasicEnsemble (mbrl/models/basic_ensemble.py) whose members are one-member GaussianMLPs of one shape, activation and loss."""
     members = list(ens.members)
     if not members:
@@ -75,7 +75,7 @@ def _read_basic_ensemble(ens) -> _Kind:
         if hasattr(m, "members"):
             raise UnsupportedModelError(f"BasicEnsemble member {i} is an ensemble itself" + _KEEP_STOCK)
         try:
-            read.append(_read_mlp(m, True))
+            read.append(_read_mlp(m, True, max_hid))
         except UnsupportedModelError as exc:
             raise UnsupportedModelError(f"BasicEnsemble member {i}: {exc}") from None
         if int(read[-1][0][0].weight.shape[0]) != 1 or int(getattr(m, "num_members", 1)) != 1:
@@ -93,7 +93,7 @@ def _read_basic_ensemble(ens) -> _Kind:
     return _Kind(members, True, stacked, act, slope, loss)
 
 
-def _read_mlp(mlp, extended: bool):
+def _read_mlp(mlp, extended: bool, max_hid: int = MAX_HID):
     """([linear layers], activation, slope, loss kind) of one GaussianMLP or UnsupportedModelError."""
     if not hasattr(mlp, "hidden_layers") or not hasattr(mlp, "mean_and_logvar"):
         raise UnsupportedModelError("dynamics_model.model is not a GaussianMLP" + _KEEP_STOCK)
@@ -120,9 +120,10 @@ def _read_mlp(mlp, extended: bool):
     E, in_dim, hid = (int(v) for v in w0.shape)
     out2 = int(layers[-1].weight.shape[2])
     max_cols = MAX_OUT if deterministic else 2 * MAX_OUT
-    if E > MAX_MEMBERS or hid > MAX_HID or in_dim > MAX_IN or out2 > max_cols:
+    if E > MAX_MEMBERS or hid > max_hid or in_dim > MAX_IN or out2 > max_cols:
+        wider = f"; step_kernel=\"wide\" trains hid <= {WIDE_MAX_HID}" if MAX_HID < hid <= WIDE_MAX_HID and max_hid < WIDE_MAX_HID else ""
         raise UnsupportedModelError(f"ensemble {E} x in {in_dim} x hid {hid} x out {out2} exceeds the trained shapes (E <= {MAX_MEMBERS}, "
-                                    f"in <= {MAX_IN}, hid <= {MAX_HID}, out <= {max_cols} columns)" + _KEEP_STOCK)
+                                    f"in <= {MAX_IN}, hid <= {max_hid}, out <= {max_cols} columns{wider})" + _KEEP_STOCK)
     return layers, act or "relu", slope, "mse" if deterministic else "nll"
 
 
@@ -194,8 +195,10 @@ class ModelTrainer:
     kernel launch per chunk; ``batch_callback`` is replayed in order after each epoch from one device read per epoch.
     ``step_kernel``: "member" = one workgroup per member (batch sizes up to 256); "split" = the row-split step, three launches per
     minibatch step that spread a member over many CUs (batch sizes up to 1024); "auto" (the default) = "member" wherever it runs --
-    every result of a batch size up to 256 keeps its bits -- and "split" for batch sizes 257..1024.
-    ``steps_per_launch`` (0 = the library's choice) cuts the member kernel's launches; the split step ignores it.
+    every result of a batch size up to 256 keeps its bits -- and "split" for batch sizes 257..1024; "wide" = the split step with a rows
+    kernel that keeps one in-place activation panel, and the evaluate pass on the same forward chain: hidden widths up to 1024 (the
+    others: 256) at every batch size up to 1024.  "auto" never picks it.
+    ``steps_per_launch`` (0 = the library's choice) cuts the member kernel's launches; the split and wide steps ignore it.
     Training runs on ``engine``'s GPU (default: ``device`` or cuda:current) whatever device the model lives on; the trained
     weights are written back into the live parameters (their ``_version`` changes, so fused agents re-pack)."""
 
@@ -205,12 +208,12 @@ class ModelTrainer:
                  engine=None, device=None, steps_per_launch: int = 0, extended: bool = False, step_kernel: str = "auto"):
         from .engine import get_engine
 
-        if step_kernel not in ("auto", "member", "split"):
-            raise ValueError("step_kernel must be 'auto', 'member' or 'split'")
+        if step_kernel not in ("auto", "member", "split", "wide"):
+            raise ValueError("step_kernel must be 'auto', 'member', 'split' or 'wide'")
         self.step_kernel = step_kernel
 
         self.model = model
-        self._kind = _read_model(model, extended)
+        self._kind = _read_model(model, extended, WIDE_MAX_HID if step_kernel == "wide" else MAX_HID)
         self._act, self._slope = self._kind.act, self._kind.slope
         self._train_iteration = 0
         self.logger = logger
@@ -326,8 +329,9 @@ class ModelTrainer:
     def _run_steps(self, x, y, idx, rows):
         g = self.optimizer.param_groups[0]
         dev = self.engine.device
+        wide = self.step_kernel == "wide"
         split = self.step_kernel == "split" or (self.step_kernel == "auto" and idx.shape[2] > MAX_BATCH)
-        limit = SPLIT_MAX_BATCH if split else MAX_BATCH
+        limit = SPLIT_MAX_BATCH if split or wide else MAX_BATCH
         if idx.shape[2] > limit:
             raise UnsupportedModelError(f"batch size {idx.shape[2]} > {limit}" + (" (step_kernel='member')" if self.step_kernel == "member" else "")
                                         + _KEEP_STOCK)
@@ -336,7 +340,7 @@ class ModelTrainer:
             self._w[0], self._w[1], (self._m[0], self._m[1]), (self._v[0], self._v[1]), lo, hi, x, y,
             torch.from_numpy(np.ascontiguousarray(idx)).to(dev), torch.from_numpy(np.ascontiguousarray(rows)).to(dev), self._step,
             lr=g["lr"], betas=g["betas"], eps=g["eps"], weight_decay=g["weight_decay"], activation=self._act, leaky_slope=self._slope,
-            steps_per_launch=self.steps_per_launch, **self._engine_kw, **({"kernel": "split"} if split else {}))
+            steps_per_launch=self.steps_per_launch, **self._engine_kw, **({"kernel": "wide"} if wide else {"kernel": "split"} if split else {}))
         self._step += int(idx.shape[0])
         return loss, gsq
 
@@ -476,7 +480,8 @@ class ModelTrainer:
             y = torch.cat(ys).to(dev, torch.float32).contiguous()
             order = None
         res = self.engine.train_eval(self._w[0], self._w[1], x, y, order, activation=self._act, leaky_slope=self._slope,
-                                     row_scores=batch_callback is not None, **({"loss": "mse"} if self._kind.loss == "mse" else {}))
+                                     row_scores=batch_callback is not None, **({"loss": "mse"} if self._kind.loss == "mse" else {}),
+                                     **({"kernel": "wide"} if self.step_kernel == "wide" else {}))
         score, rs = res if batch_callback is not None else (res, None)
         if batch_callback is not None:
             rs_h = rs.cpu().numpy()

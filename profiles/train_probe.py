@@ -13,7 +13,14 @@ the same widths, the split kernels, the member kernel (where it runs: B <= 256) 
 split steps at one shape: the run to put under rocprofv3 for the split of a step over its three kernels.
 
     python profiles/train_probe.py --routes [--rounds 5] [--steps 1000] [--eager-steps 100]
-    rocprofv3 --kernel-trace --stats -- python profiles/train_probe.py --split-only mbpo_halfcheetah"""
+    rocprofv3 --kernel-trace --stats -- python profiles/train_probe.py --split-only mbpo_halfcheetah
+
+With --routes --wide the shapes are E 7, five linear layers, B 256 and 32 at hidden 200, 256, 400, 512 and 1024; the
+wide kernels, the eager baseline and -- where they run: hidden <= 256 -- the split kernels take turns; the result goes to
+profiles/train_wide.json.  --split-only SHAPE --kernel wide is the run for the kernel trace of the wide step's three launches.
+
+    python profiles/train_probe.py --routes --wide [--rounds 5] [--steps 300] [--eager-steps 60]
+    rocprofv3 --kernel-trace --stats -- python profiles/train_probe.py --split-only b256_hid1024 --kernel wide"""
 import argparse
 import json
 import os
@@ -36,6 +43,7 @@ SHAPES = {  # E, B, in, hid, out, linear layers (conf/dynamics_model/gaussian_ml
     "mbpo_halfcheetah": (7, 256, 23, 200, 18, 5),
 }
 ROUTE_SHAPES = dict(SHAPES, b512_halfcheetah_widths=(7, 512, 23, 200, 18, 5), b1024_halfcheetah_widths=(7, 1024, 23, 200, 18, 5))
+WIDE_SHAPES = {f"b{B}_hid{hid}": (7, B, 23, hid, 18, 5) for B in (256, 32) for hid in (200, 256, 400, 512, 1024)}
 N = 100_000
 DEV = "cuda:0"
 
@@ -52,13 +60,14 @@ def _setup(shape, steps):
     return x, y, ws, bs, lo, hi, idx, rows
 
 
-def measure_routes(name, rounds, steps, eager_steps):
-    """us per step of the three routes at one shape, interleaved: {route: {"median", "min", "max", "rounds"}}"""
-    shape = ROUTE_SHAPES[name]
+def measure_routes(name, rounds, steps, eager_steps, wide=False):
+    """us per step of the routes at one shape, interleaved: {route: {"median", "min", "max", "rounds"}}.  ``wide``: the wide kernels
+    take a turn, the member kernel none."""
+    shape = {**ROUTE_SHAPES, **WIDE_SHAPES}[name]
     E, B, in_dim, hid, out, L = shape
     eng = hipets.get_engine(DEV)
     x, y, ws, bs, lo, hi, idx, rows = _setup(shape, steps)
-    state = {r: tr.fresh_state(ws, bs, torch.float32, DEV) for r in ("split", "member", "eager")}
+    state = {r: tr.fresh_state(ws, bs, torch.float32, DEV) for r in ("split", "member", "wide", "eager")}
 
     def hip(route, n):
         w, b, m, v = state[route]
@@ -75,8 +84,12 @@ def measure_routes(name, rounds, steps, eager_steps):
                 tr.adam_(we[li], dws[li], me[0][li], ve[0][li], s + 1, 1e-3, weight_decay=1e-5)
                 tr.adam_(be[li], dbs[li], me[1][li], ve[1][li], s + 1, 1e-3, weight_decay=1e-5)
 
-    routes = {"split": (lambda n: hip("split", n), steps), "eager": (eager, eager_steps)}
-    if B <= hipets._lib.TRAIN_MAX_BATCH:
+    routes = {"eager": (eager, eager_steps)}
+    if hid <= hipets._lib.TRAIN_MAX_HID:
+        routes["split"] = (lambda n: hip("split", n), steps)
+    if wide:
+        routes["wide"] = (lambda n: hip("wide", n), steps)
+    elif B <= hipets._lib.TRAIN_MAX_BATCH:
         routes["member"] = (lambda n: hip("member", n), steps)
     times = {r: [] for r in routes}
     for rnd in range(rounds + 1):  # (round 0 warms every route up)
@@ -160,18 +173,20 @@ def main():
     ap.add_argument("--routes", action="store_true")
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--split-only", default=None, metavar="SHAPE")
+    ap.add_argument("--wide", action="store_true")
+    ap.add_argument("--kernel", default="split", choices=("split", "wide"))
     a = ap.parse_args()
     if a.split_only:
-        x, y, ws, bs, lo, hi, idx, rows = _setup(ROUTE_SHAPES[a.split_only], a.steps)
+        x, y, ws, bs, lo, hi, idx, rows = _setup({**ROUTE_SHAPES, **WIDE_SHAPES}[a.split_only], a.steps)
         w, b, m, v = tr.fresh_state(ws, bs, torch.float32, DEV)
-        hipets.get_engine(DEV).train_steps(w, b, m, v, lo, hi, x, y, idx, rows, 0, lr=1e-3, weight_decay=1e-5, kernel="split")
+        hipets.get_engine(DEV).train_steps(w, b, m, v, lo, hi, x, y, idx, rows, 0, lr=1e-3, weight_decay=1e-5, kernel=a.kernel)
         torch.cuda.synchronize()
         return
     if a.routes:
-        res = {name: measure_routes(name, a.rounds, a.steps, a.eager_steps) for name in ROUTE_SHAPES}
+        res = {name: measure_routes(name, a.rounds, a.steps, a.eager_steps, a.wide) for name in (WIDE_SHAPES if a.wide else ROUTE_SHAPES)}
         res["device"] = torch.cuda.get_device_name(0)
         print(json.dumps(res, indent=1))
-        out = a.out if a.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "train_split.json")
+        out = a.out if a.out != ap.get_default("out") else os.path.join(ROOT, "profiles", "train_wide.json" if a.wide else "train_split.json")
         with open(out, "w") as f:
             json.dump(res, f, indent=1)
         return
