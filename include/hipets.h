@@ -1004,10 +1004,26 @@ int hipets_ensemble_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles
  *     MFMA with fp32 accumulation -- but every prediction is summed k ascending in ONE accumulator (the tile form: two alternating), so
  *     its results agree with the tile form's to rounding, not bit for bit (DESIGN.md section 33 has the design and measurements).
  *     A model for which R = 2 does not fit runs the tile form under this setting too: nothing is refused that the tile form accepts.
- * While the wide form is selected hipets_ensemble_geometry reports its R (whatever the batch) and its LDS bytes, or the tile form's
- * values for a model that falls back.  An unknown kind fails with HIPETS_ERR_INVALID_ARGUMENT and leaves the setting as it was.        */
+ *   HIPETS_ENSEMBLE_KERNEL_BF16                the wide form's outline on the bf16 matrix pipe (v_mfma_f32_16x16x32_bf16), reduced
+ *     precision by name.  Arithmetic: for every linear layer BOTH operands are rounded to bf16 nearest-even; products are exact;
+ *     accumulation is fp32, in an order of the kernel's own (32-wide k chunks ascending); bias and activation are fp32.  The model input
+ *     is built exactly as in the other forms (obs preprocessing and the normaliser in their own dtype, then float32) and rounded to bf16
+ *     only as layer 0's operand; the bf16 store of a hidden layer's activated result is the next layer's operand rounding.  The output
+ *     layer's results, the log-variance clamps, all four statistics (variance about the first requested member's mean) and
+ *     hipets_uncertainty_penalty stay fp32 and follow the rules above.  All activations, deterministic models and per-member bounds.
+ *     Reads the SAME fp32 snapshot (a HIPETS_PREC_BF16 / _BF16X3 descriptor stays refused by hipets_ensemble_set): the first predict
+ *     under this form after a hipets_ensemble_set packs bf16 weight images from the snapshot's own fp32 images on the device.
+ *     Geometry, by the model's shape alone: LDS holds per row the input (64 bytes per 32-wide k chunk + 16) and one hidden buffer
+ *     (likewise) as bf16 and 64 bytes of partial row sums; R = 4 where 16 R rows fit the LDS opt-in limit and hid <= 256 and
+ *     out_dim <= 256, else R = 2 with hid <= 256, or with hid <= 1024 and out_dim <= 128.  A model outside these is REFUSED by
+ *     hipets_ensemble_predict and hipets_ensemble_geometry with HIPETS_ERR_INVALID_ARGUMENT naming the form: it never runs fp32 under
+ *     this name.  Same arguments, outputs, NaN rule and independence of batch, position and requested outputs.
+ * While the wide or the bf16 form is selected hipets_ensemble_geometry reports its R (whatever the batch) and its LDS bytes, or under the
+ * wide form the tile form's values for a model that falls back.  hipets_policy_rollout ignores the setting.  An unknown kind fails with
+ * HIPETS_ERR_INVALID_ARGUMENT and leaves the setting as it was.                                                                        */
 #define HIPETS_ENSEMBLE_KERNEL_TILE 0
 #define HIPETS_ENSEMBLE_KERNEL_WIDE 1
+#define HIPETS_ENSEMBLE_KERNEL_BF16 2
 int hipets_set_ensemble_kernel(hipets_engine* e, int32_t kind);
 /* An uncertainty penalty and halt on a model step's rewards and dones (MOPO's r - lambda u; MOReL's halt): one elementwise launch over
  * stats DEVICE [batch, 4] (hipets_ensemble_predict), rewards DEVICE [batch] f32 and dones DEVICE [batch] uint8, both updated in place.

@@ -120,7 +120,7 @@ void hipets_destroy(hipets_engine* e) {
                       &e->s0, &e->state, &e->totals, &e->term, &e->exchange, &e->step_keys, &e->plan_keys, &e->mu, &e->disp, &e->population, &e->values,
                       &e->best_value, &e->best_solution, &e->past_action, &e->kept, &e->elite_idx, &e->keep_idx, &e->planet_w, &e->planet_b, &e->planet_member, &e->planet_ops, &e->shard_values, &e->gathered, &e->census, &e->train_slab, &e->train_partial, &e->train_split_part,
                       &e->policy.w, &e->policy.b, &e->compact_counts, &e->sac_ws, &e->sac_one, &e->critic.w, &e->critic.b,
-                      &e->ensemble.w, &e->ensemble.b, &e->ensemble.norm, &e->ensemble.lv, &e->ensemble.cols,
+                      &e->ensemble.w, &e->ensemble.wb, &e->ensemble.b, &e->ensemble.norm, &e->ensemble.lv, &e->ensemble.cols,
                       &e->posterior.w, &e->posterior.b, &e->posterior.act[0], &e->posterior.act[1]})
         b->release();
     for (auto& ev : e->events) { (void)hipEventDestroy(ev.first); (void)hipEventDestroy(ev.second); }
@@ -171,7 +171,8 @@ int hipets_set_agent_kernel(hipets_engine* e, int32_t kind) {
 
 int hipets_set_ensemble_kernel(hipets_engine* e, int32_t kind) {
     if (!e) return fail("null engine");
-    if (kind != HIPETS_ENSEMBLE_KERNEL_TILE && kind != HIPETS_ENSEMBLE_KERNEL_WIDE) return fail("ensemble kernel must be HIPETS_ENSEMBLE_KERNEL_TILE or HIPETS_ENSEMBLE_KERNEL_WIDE");
+    if (kind != HIPETS_ENSEMBLE_KERNEL_TILE && kind != HIPETS_ENSEMBLE_KERNEL_WIDE && kind != HIPETS_ENSEMBLE_KERNEL_BF16)
+        return fail("ensemble kernel must be HIPETS_ENSEMBLE_KERNEL_TILE, HIPETS_ENSEMBLE_KERNEL_WIDE or HIPETS_ENSEMBLE_KERNEL_BF16");
     e->ensemble_kernel = kind;
     return 0;
 }

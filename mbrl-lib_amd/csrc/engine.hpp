@@ -79,6 +79,10 @@ struct EnsembleSnapshot {
     int members[HIPETS_ENSEMBLE_MAX_MEMBERS] = {};
     size_t wmember = 0, bmember = 0;
     DevBuf w, b, norm, lv, cols, no_delta;
+    // the bf16 form's A-operand images (ensemble_bf16.hpp), packed from `w` on the device by the first predict under that form after a set
+    DevBuf wb;
+    bool bf16_packed = false;
+    size_t wbmember = 0;
 };
 
 // what hipets_planet_posterior_set_model keeps (planet_posterior.hip): the product chain of the encoder -- the conv layers, the optional

@@ -12,6 +12,7 @@
 #include "closed_forms.hpp"
 #include "common.hpp"
 #include "engine.hpp"
+#include "ensemble_bf16.hpp"
 #include "ensemble_wide.hpp"
 #include "policy_layer.hpp"
 
@@ -203,6 +204,7 @@ int hipets_ensemble_set(hipets_engine* e, const hipets_model_desc* d, const hipe
     if (!e) return fail("null engine");
     EnsembleSnapshot& s = e->ensemble;
     s.set = false;  // (a refused set leaves no snapshot behind)
+    s.bf16_packed = false;  // (the bf16 form's images follow the first predict that wants them)
     if (!d) return fail("null argument");
     if (d->precision == HIPETS_PREC_BF16X3 || d->precision == HIPETS_PREC_BF16)
         return fail("ensemble predictions run in fp32 only: precision %s has no ensemble kernel", d->precision == HIPETS_PREC_BF16 ? "bf16" : "bf16x3");
@@ -323,7 +325,7 @@ int hipets_ensemble_set(hipets_engine* e, const hipets_model_desc* d, const hipe
 int hipets_ensemble_predict(hipets_engine* e, const float* obs, const float* actions, const float* model_in, int32_t batch, int32_t only_elite,
                             float* mean, float* logvar, float* stats, void* stream) {
     if (!e || !e->ensemble.set) return fail("engine has no ensemble (call hipets_ensemble_set)");
-    const EnsembleSnapshot& s = e->ensemble;
+    EnsembleSnapshot& s = e->ensemble;
     if (model_in ? (obs || actions) : (!obs || !actions)) return fail("give either obs and actions, or model_in");
     if (batch < 1) return fail("bad batch");
     if (!mean && !logvar && !stats) return fail("no output requested");
@@ -331,6 +333,31 @@ int hipets_ensemble_predict(hipets_engine* e, const float* obs, const float* act
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     HCHECK(hipSetDevice(e->device));
     ENTER_STREAM(e, st);
+    if (e->ensemble_kernel == HIPETS_ENSEMBLE_KERNEL_BF16) {  // bf16 operands, its own images (ensemble_bf16.hip); never the fp32 forms behind this name
+        EnsBf16Args ba{};
+        if (!ensemble_bf16_geometry(s.in_dim, s.hid, s.out_dim, e->lds_max, ba.g))
+            return fail("ensemble kernel bf16 has no instance for %d-%dx%d-%d (hid <= 256 with out_dim <= 512, or hid <= 1024 with out_dim <= 128): use the tile or the wide form",
+                        s.in_dim, s.hid, s.n_layers - 1, s.out_dim);
+        if (!s.bf16_packed) {
+            s.wbmember = ens_bf16_member_entries(ba.g, s.n_layers, s.deterministic);
+            if (s.wb.ensure(s.wbmember * s.E * sizeof(uint4))) return 1;
+            const hipError_t perr = pack_ensemble_bf16(s.wb.as<uint4>(), s.w.as<float>(), s.wmember, s.E, s.in_dim, s.hid, s.out_dim, s.n_layers, s.deterministic, ba.g, st);
+            if (perr != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "bf16 ensemble pack launch failed: %s", hipGetErrorString(perr));
+            s.bf16_packed = true;
+        }
+        ba.obs = obs; ba.actions = actions; ba.model_in = model_in; ba.mean = mean; ba.logvar = logvar; ba.stats = stats;
+        ba.wb = s.wb.as<uint4>(); ba.b = s.b.as<float>(); ba.norm = s.norm.as<double>(); ba.lv = s.lv.as<float>(); ba.cols = s.cols.as<hipets_obs_column>();
+        ba.wbmember = s.wbmember; ba.bmember = s.bmember;
+        ba.B = batch; ba.n = only_elite ? s.M : s.E;
+        ba.obs_dim = s.obs_dim; ba.act_dim = s.act_dim; ba.in_dim = s.in_dim; ba.out_dim = s.out_dim; ba.n_layers = s.n_layers;
+        ba.activation = s.activation; ba.obs_process = s.obs_process; ba.normalizer = s.normalizer; ba.deterministic = s.deterministic;
+        ba.lv_per_member = s.lv_rows > 1 ? s.lv_rows : 0;
+        ba.slope = s.slope;
+        for (int i = 0; i < ba.n; ++i) ba.members[i] = only_elite ? s.members[i] : i;
+        const hipError_t berr = launch_ensemble_bf16(ba, e->lds_max, st);
+        if (berr != hipSuccess) return fail_kind(HIPETS_ERR_RUNTIME, "bf16 ensemble kernel launch failed: %s", hipGetErrorString(berr));
+        return 0;
+    }
     EnsWideArgs wa{};
     if (e->ensemble_kernel == HIPETS_ENSEMBLE_KERNEL_WIDE &&
         ensemble_wide_geometry(s.in_dim, s.hid, s.out_dim, s.deterministic, e->lds_max, wa.g)) {  // the same images and arguments (ensemble_wide.hip)
@@ -368,6 +395,15 @@ int hipets_ensemble_geometry(hipets_engine* e, int32_t batch, int32_t* row_tiles
     if (!e || !e->ensemble.set) return fail("engine has no ensemble (call hipets_ensemble_set)");
     EnsWideGeo wg{};
     const EnsembleSnapshot& s = e->ensemble;
+    if (e->ensemble_kernel == HIPETS_ENSEMBLE_KERNEL_BF16) {
+        EnsBf16Geo bg{};
+        if (batch < 1) return fail("bad batch");
+        if (!ensemble_bf16_geometry(s.in_dim, s.hid, s.out_dim, e->lds_max, bg))
+            return fail("ensemble kernel bf16 has no instance for %d-%dx%d-%d", s.in_dim, s.hid, s.n_layers - 1, s.out_dim);
+        if (row_tiles) *row_tiles = bg.R;  // (by the shape alone)
+        if (lds_bytes) *lds_bytes = bg.lds;
+        return 0;
+    }
     if (e->ensemble_kernel == HIPETS_ENSEMBLE_KERNEL_WIDE && ensemble_wide_geometry(s.in_dim, s.hid, s.out_dim, s.deterministic, e->lds_max, wg)) {
         if (batch < 1) return fail("bad batch");
         if (row_tiles) *row_tiles = wg.R;  // (by the shape alone)

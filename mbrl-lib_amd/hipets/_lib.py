@@ -57,7 +57,7 @@ SAC_N_PTRS, SAC_MAX_BATCH = 78, 1024  # HIPETS_SAC_N_PTRS, HIPETS_SAC_MAX_BATCH
 SAC_PRODUCT = {"tile": 0, "blocked": 1}  # HIPETS_SAC_PRODUCT_*
 CRITIC_N_PTRS = 12  # HIPETS_CRITIC_N_PTRS
 AGENT_KERNEL = {"tile": 0, "wide": 1}  # HIPETS_AGENT_KERNEL_*
-ENSEMBLE_KERNEL = {"tile": 0, "wide": 1}  # HIPETS_ENSEMBLE_KERNEL_*
+ENSEMBLE_KERNEL = {"tile": 0, "wide": 1, "bf16": 2}  # HIPETS_ENSEMBLE_KERNEL_*
 # HIPETS_ENCODER_MAX_* / HIPETS_POSTERIOR_MAX_*: conv layers, channels, kernel, stride, image side, flattened encoding, environments,
 # outputs of one layer per image; latent, action, belief, hidden
 ENCODER_MAX = {"convs": 6, "channels": 512, "kernel": 8, "stride": 4, "image": 128, "flat": 4096, "env": 64, "layer_floats": 1 << 20}

@@ -1046,7 +1046,7 @@ class Engine:
         """Every requested member's forward of the same rows in one launch (hipets_ensemble_predict): from ``obs`` f32 [B, obs_dim] and
         ``actions`` f32 [B, act_dim], or from a ready ``model_in`` f32 [B, in_dim].  Returns (mean [n, B, out_dim], logvar [n, B,
         out_dim], stats [B, 4]) on the device, None for an output not wanted; n = all members, or with ``only_elite`` the spec's
-        member list.  The columns of ``stats``: ``_lib.ENSEMBLE_STATS``.  ``kernel``: "tile" or "wide", set for the call and put back
+        member list.  The columns of ``stats``: ``_lib.ENSEMBLE_STATS``.  ``kernel``: "tile", "wide" or "bf16", set for the call and put back
         (None: the engine's setting, :meth:`set_ensemble_kernel`)."""
         spec, dev = self._ensemble_spec(), self.device
         setting = self._ensemble_setting(kernel)
@@ -1088,7 +1088,8 @@ class Engine:
     def set_ensemble_kernel(self, kernel: str):
         """Which form :meth:`ensemble_predict` runs when the call names none (hipets_set_ensemble_kernel): "tile", the library's initial
         value, or "wide" -- 64 rows per workgroup (32 for a very wide input), one hidden buffer in LDS, the output layer and the
-        statistics' state in registers; another summation order, so equal to the tile form to rounding, not bit for bit."""
+        statistics' state in registers; another summation order, so equal to the tile form to rounding, not bit for bit --, or "bf16" --
+        the wide form's outline with every linear layer's operands rounded to bf16 (fp32 accumulation, fp32 everything else)."""
         if kernel not in _lib.ENSEMBLE_KERNEL:
             raise ValueError(f"kernel must be one of {tuple(_lib.ENSEMBLE_KERNEL)}, not {kernel!r}")
         self._query("hipets_set_ensemble_kernel", kind=_lib.ENSEMBLE_KERNEL[kernel])

@@ -74,7 +74,7 @@ def _as_model_env(dm):
                                  action_space=box(in_dim - obs_in), device=getattr(dm, "device", None))
 
 
-ENSEMBLE_KERNELS = ("tile", "wide", "auto")
+ENSEMBLE_KERNELS = ("tile", "wide", "bf16", "auto")
 # kernel="auto": the wide form where it measured faster than the tile form with the routes taking turns (profiles/ensemble_wide.json,
 # DESIGN.md section 33): models whose output layer is at least this many columns wide (pad16(out_total)).  None: nowhere.
 ENSEMBLE_WIDE_MIN_OUT_COLS = 768
@@ -95,9 +95,25 @@ def ensemble_wide_geometry(in_dim: int, hid: int, out_dim: int, deterministic: b
     return None
 
 
+def ensemble_bf16_geometry(in_dim: int, hid: int, out_dim: int, lds_max: int = 160 * 1024):
+    """(row tiles R, mean column tiles per wave T, hidden column tiles per wave TH, dynamic LDS bytes) of the bf16 form, or None where
+    the predict call refuses the model -- csrc/ensemble_bf16.hpp's rule restated: LDS holds 16 R rows of the input (64 bytes per 32-wide
+    k chunk + 16) and of ONE hidden buffer (likewise), both bf16, and 2 x 8 partial row sums; R = 4 where that fits and a wave owns at
+    most two hidden and two mean column tiles, else R = 2 with two hidden tiles, or up to eight beside one mean tile.  By the shape alone."""
+    kc0, kch = -(-int(in_dim) // 32), -(-int(hid) // 32)
+    t, th = -(-(-(-int(out_dim) // 16)) // 8), -(-(-(-int(hid) // 16)) // 8)
+    for r in (4, 2):
+        lds = 16 * r * (64 * kc0 + 16 + 64 * kch + 16 + 4 * 16)
+        fits = (th <= 2 and t <= 2) if r == 4 else (t <= 4 if th <= 2 else (th <= 8 and t <= 1))
+        if lds <= lds_max and fits:
+            return r, t, th, lds
+    return None
+
+
 def ensemble_kernel_for(kernel: str, out_dim: int, deterministic: bool = False) -> str:
-    """The form ("tile" or "wide") of the ensemble's forward under ``kernel`` ("tile", "wide" or "auto").  By the model's shape alone,
-    never by the batch: the two forms sum in different orders, and a row must keep its bits across batch sizes."""
+    """The form ("tile", "wide" or "bf16") of the ensemble's forward under ``kernel`` (one of those, or "auto").  By the model's shape
+    alone, never by the batch: the forms sum in different orders, and a row must keep its bits across batch sizes.  "auto" chooses
+    between the two fp32 forms only: reduced precision is asked for by name."""
     if kernel not in ENSEMBLE_KERNELS:
         raise ValueError(f"kernel must be one of {ENSEMBLE_KERNELS}, not {kernel!r}")
     if kernel != "auto":
@@ -114,8 +130,12 @@ class EnsemblePredictor(_SlotOwner):
     trained in between, or when another predictor's model sits in the engine.
 
     ``kernel``: "tile" (the default), "wide" (hipets_set_ensemble_kernel: 64 rows per workgroup, the output layer and the statistics in
-    registers; the same function in another summation order) or "auto" (:func:`ensemble_kernel_for` picks by the model's shape).  The
-    object applies its choice at every call and puts the engine's setting back."""
+    registers; the same function in another summation order), "bf16" (the wide form's outline on the bf16 matrix pipe: for every
+    linear layer both operands rounded to bf16 nearest-even, exact products, fp32 accumulation; bias, activation, the log-variance
+    clamps, the statistics and the penalty in fp32 -- a ranking of rows by disagreement, not seven digits; reads the same fp32
+    snapshot, so ``precision="bf16"`` specs stay refused; a model with no instance (:func:`ensemble_bf16_geometry`) is refused by the
+    predict call, never run in fp32) or "auto" (:func:`ensemble_kernel_for` picks between "tile" and "wide" by the model's shape).
+    The object applies its choice at every call and puts the engine's setting back."""
     slot = "ensemble"
 
     def __init__(self, model, engine=None, device=None, kernel: str = "tile"):

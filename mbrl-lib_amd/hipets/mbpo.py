@@ -159,7 +159,7 @@ def rollout_model_and_populate_sac_buffer(model_env, replay_buffer, agent, sac_b
     (:class:`hipets.ensemble.ReferencePenalisedEnv`).
 
     ``ensemble_kernel`` (keyword only; not in the reference): the ``kernel=`` of the penalised view's :class:`hipets.EnsemblePredictor`
-    -- "tile", "wide" or "auto" --, for the staging and the ring path alike; without ``uncertainty`` it is only checked."""
+    -- "tile", "wide", "bf16" or "auto" --, for the staging and the ring path alike; without ``uncertainty`` it is only checked."""
     from .ensemble import ensemble_kernel_for
 
     agent_kernel_for(agent_kernel, 0)
